@@ -17,12 +17,19 @@ the frame queue (weak scaling; frames are independent, spotfinder/spotfinder.cc:
 the per-frame spot lists are gathered to rank 0 once per `--gather-every` batches: an
 all_gather of the ranks' row counts, then exactly the written rows by RCCL send / recv
 (`--gather padded`: round 3's all_gather of fixed-size blocks to every rank, for A/B).
-Every batch waited for is checked against committed oracle results ("results_checked").  `--single-process` drives the N GPUs from ONE process instead --
+With `--full` every batch waited for is checked against committed oracle results ("results_checked").  `--single-process` drives the N GPUs from ONE process instead --
 one context and one host thread per GPU behind ffs_multi_init, the C++ driver's model
 (`spotfinder --gpus N`) -- so both designs get a curve.
 
 Prints ONE JSON line (rank 0).  torch is used only for device memory and
 torch.distributed; the product is libffs_hip.so behind include/ffs_hip.h.
+
+A plain run does what its headline figure needs: set-up, the W warm-up steps and a short clock-settling
+warm-up, ONE timed region of exactly `--steps` steps (`ms_per_step` = that region / steps), the outputs
+of its last step when `--dump-outputs DIR` is given, and the line.  `--full` adds everything else the
+line has carried: the median of `--reps` repetitions (5), the steady / drain split, the committed-oracle
+check of every timed batch and the digests of every box and reflection, the kernel-alone legs and the
+roofline, the streamed legs, the drop-in binary end to end (cli_e2e) and the CPU baseline.
 """
 import argparse
 import json
@@ -191,6 +198,41 @@ def make_inputs(workload, n_unique, rank):
         mask = synth.config1_mask()
     frames = synth.frames(p, range(n_unique), threads=min(16, os.cpu_count() or 1))
     return frames, mask
+
+
+DUMP_BYTES = 60 << 20       # --dump-outputs: all files together stay under 64 MB
+
+
+def last_batch_outputs(st):
+    """What the caller of the timed path holds after Stream.wait_counts on `st`: every frame's counts, and the batch's boxes and
+    reflections from the library's host arrays (ffs_stream_batch_arrays; valid until the next wait on this stream)."""
+    import ctypes as C
+    bp, rp, nb, nr = C.c_void_p(), C.c_void_p(), C.c_uint32(), C.c_uint32()
+    st.ctx._check(st._lib.ffs_stream_batch_arrays(st._h, C.byref(bp), C.byref(nb), C.byref(rp), C.byref(nr)))
+
+    def table(ptr, n, dt):
+        a = np.frombuffer((C.c_uint8 * (n * dt.itemsize)).from_address(ptr.value), dt) if n else np.zeros(0, dt)
+        return np.stack([a[f].astype(np.float64) for f in dt.names], axis=1)
+    from ffs_amd import api
+    counts = st.last_frame_counts
+    out = {f: counts[f].astype(np.float64) for f in counts.dtype.names}
+    out["boxes"] = table(bp, nb.value, api.BOX_DT)                  # columns: api.BOX_DT's fields
+    out["reflections"] = table(rp, nr.value, api.REFL_DT)           # columns: api.REFL_DT's fields
+    return out
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: each array as <out_dir>/<name>.npy in float64.  When they come to more than DUMP_BYTES, each array of more
+    than 1 MB keeps a fixed, seeded sample of its rows, in order (the same rows from run to run for outputs of the same shape)."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {k: np.asarray(v, np.float64) for k, v in arrays.items()}
+    big = sum(a.nbytes for a in arrays.values() if a.nbytes > 1 << 20)
+    small = sum(a.nbytes for a in arrays.values()) - big
+    for name, a in arrays.items():
+        if a.nbytes > 1 << 20 and small + big > DUMP_BYTES:
+            keep = int(len(a) * (DUMP_BYTES - small) / big)
+            a = a[np.sort(np.random.default_rng(0).choice(len(a), keep, replace=False))]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def stale_note(summary, kernel_name):
@@ -469,6 +511,7 @@ def bench_sweep(args, dev, local_rank):
     from ffs_amd import fixtures
     expected = fixtures.load_expected_sweep("sweep16m")
     check = {"sweeps": 0, "bad_sweeps": 0, "first_bad": None}
+    last_sweep = {}         # the last sweep's 3D reflection table and (found, calculated, filtered by size / separation)
 
     def sweep():
         nonlocal n_refl
@@ -491,6 +534,7 @@ def bench_sweep(args, dev, local_rank):
         refl, n_calc, fs, fp = stack.finish()
         finish_ms.append(stack.last_finish_ms())
         n_refl = len(refl)
+        last_sweep.update(refl=refl, counts=(len(refl), n_calc, fs, fp))
         if expected is not None:
             got = (len(refl), n_calc, fs, fp)
             want = (expected["n_reflections"], expected["n_calculated"], expected["n_filtered_size"], expected["n_filtered_sep"])
@@ -513,6 +557,10 @@ def bench_sweep(args, dev, local_rank):
         sweep()
     torch.cuda.synchronize(dev)
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs:
+        refl = last_sweep["refl"]
+        dump_outputs(args.dump_outputs, {"reflections_3d": np.stack([refl[f].astype(np.float64) for f in refl.dtype.names], axis=1),
+                                         "counts_3d": last_sweep["counts"]})
     results_checked = None if expected is None else bool(check["sweeps"] > 0 and check["bad_sweeps"] == 0)
     out = {
         "metric": "detector frames/s (Eiger-16M 100-frame sweep, 2D + 3D connected components)", "value": round(steps * NZ / elapsed, 1),
@@ -530,7 +578,7 @@ def bench_sweep(args, dev, local_rank):
                                       "components; tests/golden/make_golden_bench.py --only sweep16m)"}
                           if expected is not None else {"skipped": "no committed oracle results for this sweep"}),
     }
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline_sweep(p, mask, NZ)
     print(json.dumps(out), flush=True)
     return 0 if results_checked is not False else 6
@@ -752,8 +800,13 @@ def main():
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--no-settle", action="store_true", help="no untimed settling regions between the warm-up steps and the timed repetitions")
-    ap.add_argument("--reps", type=int, default=5,
-                    help="repetitions of the timed `steps`-step region; `value` comes from the median one")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: repetitions, steady / drain, the oracle check of every timed batch, "
+                         "kernel-alone legs and roofline, streamed legs, cli_e2e, CPU baseline (a plain run times one region)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="write what the last timed step returned (per-frame counts, boxes, reflections) as DIR/<name>.npy, float64")
+    ap.add_argument("--reps", type=int, default=None,
+                    help="repetitions of the timed `steps`-step region; `value` comes from the median one (default: 1, with --full 5)")
     ap.add_argument("--batch", type=int, default=32, help="frames per step and per GPU")
     ap.add_argument("--workload", default="eiger16m", choices=sorted(WORKLOADS) + ["sweep16m"],
                     help="sweep16m = BASELINE.json configs[4]: a 100-frame Eiger-16M rotation sweep through the 2D path, "
@@ -789,6 +842,10 @@ def main():
     ap.add_argument("--launch-timeout", type=float, default=1500.0)
     ap.add_argument("--tune", default="", help="ffs_ctx_set_tuning pairs for A/B runs, 'key=value,key=value' (results are the same)")
     args = ap.parse_args()
+    if args.reps is None:
+        args.reps = 5 if args.full else 1
+    if args.dump_outputs and (args.dry_run or (args.single_process and args.gpus > 1)):
+        ap.error("--dump-outputs: not with --dry-run or --single-process")
 
     launched = "WORLD_SIZE" in os.environ
     if args.gpus > 1 and not launched and not args.single_process:
@@ -804,7 +861,7 @@ def main():
 
     # The drop-in binary end to end, before this process initialises the GPU (its children are exec'ed)
     e2e = None
-    if (world == 1 and rank == 0 and not args.no_cli_e2e and args.workload == "eiger16m"
+    if (args.full and world == 1 and rank == 0 and not args.no_cli_e2e and args.workload == "eiger16m"
             and args.algorithm == "dispersion"):
         e2e = cli_e2e(n_images=args.cli_images, long_images=args.cli_long_images)
 
@@ -858,7 +915,7 @@ def main():
     # frames (tests/golden/bench_workloads.npz, generated by tests/golden/make_golden_bench.py), and after the timing one batch
     # per stream has every box and reflection compared through their digests.  A mismatch fails the run.
     from ffs_amd import fixtures
-    expected = fixtures.load_expected(args.workload, args.algorithm, rank, B)
+    expected = fixtures.load_expected(args.workload, args.algorithm, rank, B) if args.full else None
     check = {"batches": 0, "bad_batches": 0, "first_bad": None}
 
     def check_counts(st):
@@ -1007,8 +1064,9 @@ def main():
     def reap(done):
         nonlocal strong_px
         _, nbx, nst = done.wait_counts()      # (every frame's boxes and centroids are in the library's host arrays)
-        check_counts(done)
-        thr_ms.append(done.timings()["threshold"])
+        if args.full:
+            check_counts(done)
+            thr_ms.append(done.timings()["threshold"])
         gather(None, done)
         strong_px += nst
         return nbx
@@ -1055,22 +1113,25 @@ def main():
     # first the early repetitions (0.36, 0.34, 0.33 ms per step against 0.32 from the fourth on) paid for it.
     # (40 iterations of the ceiling probe, ~25 ms: tools/rep_probe.py -- the streaming kernel takes 0.325 ms in the first 20 steps after
     # half a second of idleness and 0.292 ms from the fourth repetition on, and the ceiling itself is under-read on cold clocks)
-    peak_read, peak_mix = streams[0].bench_hbm(iters=40)
-    ms_cand, ms_exact = streams[0].bench_threshold(ptr, pitch, fstride, B, iters=10)
-    ms_dense = None
-    if not ext:
-        ctx.set_params(want_reflections=1, algorithm=0, want_strong_mask=1)
-        ms_dense, _ = streams[0].bench_threshold(ptr, pitch, fstride, B, iters=10)
-        ctx.set_params(want_reflections=1, algorithm=0, want_strong_mask=0)
+    if args.full:
+        peak_read, peak_mix = streams[0].bench_hbm(iters=40)
+        ms_cand, ms_exact = streams[0].bench_threshold(ptr, pitch, fstride, B, iters=10)
+        ms_dense = None
+        if not ext:
+            ctx.set_params(want_reflections=1, algorithm=0, want_strong_mask=1)
+            ms_dense, _ = streams[0].bench_threshold(ptr, pitch, fstride, B, iters=10)
+            ctx.set_params(want_reflections=1, algorithm=0, want_strong_mask=0)
     run_steps(args.warmup)
     # Untimed, after the W warm-up steps the driver asked for: regions of the same K steps until two in a row agree within 1 % (at most
     # eight).  The GPU's clocks follow its load over tens of milliseconds; W = 5 steps are 1.5 ms, and without this the repetitions below
     # read 0.322, 0.311, 0.303, 0.295, 0.297 ms per step (profiles/r06q_bench_lines_steps20.jsonl) -- a ramp, not the pipeline.  Every
     # one of these regions is listed in the line (`settling_ms_per_step`); the timed repetitions that follow are all listed too.
+    # A plain run settles on regions of at most 100 steps (~30 ms, what the clocks need), so that a large K costs no more than a small one.
     settling = []
+    settle_k = args.steps if args.full else min(args.steps, 100)
     if not args.no_settle:
         for _ in range(8):
-            el, _ = timed(args.steps)
+            el, _ = timed(settle_k)
             settling.append(el)
             if len(settling) >= 2 and abs(settling[-1] - settling[-2]) < 0.01 * settling[-2]:
                 break
@@ -1085,12 +1146,15 @@ def main():
         times.append(el)
     strong_steps = strong_px
     elapsed = statistics.median(times)
-    # the fixed tail of a run (the last batches' sparse launches drain after the last streaming kernel), made visible:
-    # steady = (T(2K) - T(K)) / K, drain = T(K) - K steady
-    thr_timed = list(thr_ms)          # (the batches of the `reps` timed regions)
-    el2, _ = timed(2 * args.steps)
-    steady = max(0.0, (el2 - elapsed) / args.steps)
-    drain = max(0.0, elapsed - steady * args.steps)
+    if args.dump_outputs and rank == 0:      # the last timed step's batch: the last one waited for, on its stream
+        dump_outputs(args.dump_outputs, last_batch_outputs(streams[(args.steps - 1) % len(streams)]))
+    if args.full:
+        # the fixed tail of a run (the last batches' sparse launches drain after the last streaming kernel), made visible:
+        # steady = (T(2K) - T(K)) / K, drain = T(K) - K steady
+        thr_timed = list(thr_ms)          # (the batches of the `reps` timed regions)
+        el2, _ = timed(2 * args.steps)
+        steady = max(0.0, (el2 - elapsed) / args.steps)
+        drain = max(0.0, elapsed - steady * args.steps)
     digests_ok = None
     if expected is not None:          # untimed: every box and reflection of one more batch per stream, through their digests
         digests_ok = True
@@ -1113,21 +1177,22 @@ def main():
         g = gather_buf[last_gather[0]].cpu().numpy()
         n_ranks_seen = ranks_seen(g, spot_cap)
 
-    alg_bytes = float(W) * H * bytes_per_px * B
-    # The kernel's duration for the roofline: standard algorithm = the average over every batch of the timed regions, each from the
-    # events on its own dispatch (the contract: "average launch duration, measured live with HIP events over the timed region");
-    # `ms_alone` = the same kernel launched alone in a loop (ffs_bench_threshold: each launch behind the fills that reset the
-    # stream's planes, i.e. on cold mask tables).  Extended algorithm: its first pass alone (the stage's events span three kernels).
-    ms_alone = ms_cand
-    if not ext and thr_timed:
-        ms_cand = float(sum(thr_timed) / len(thr_timed))
-    achieved = alg_bytes / (ms_cand * 1e-3) / 1e9
-    tm = streams[0].timings()
-    traffic, traffic_src = pmc_traffic(args.workload + ("_extended" if ext else ""), B)
-    traffic_dense, traffic_dense_src = pmc_traffic(args.workload + "_dense", B)
+    if args.full:
+        alg_bytes = float(W) * H * bytes_per_px * B
+        # The kernel's duration for the roofline: standard algorithm = the average over every batch of the timed regions, each from the
+        # events on its own dispatch (the contract: "average launch duration, measured live with HIP events over the timed region");
+        # `ms_alone` = the same kernel launched alone in a loop (ffs_bench_threshold: each launch behind the fills that reset the
+        # stream's planes, i.e. on cold mask tables).  Extended algorithm: its first pass alone (the stage's events span three kernels).
+        ms_alone = ms_cand
+        if not ext and thr_timed:
+            ms_cand = float(sum(thr_timed) / len(thr_timed))
+        achieved = alg_bytes / (ms_cand * 1e-3) / 1e9
+        tm = streams[0].timings()
+        traffic, traffic_src = pmc_traffic(args.workload + ("_extended" if ext else ""), B)
+        traffic_dense, traffic_dense_src = pmc_traffic(args.workload + "_dense", B)
 
     streamed = None
-    if not args.no_streamed:
+    if args.full and not args.no_streamed:
         # host frames in each stream's pinned staging buffer -> H2D + full hot path per batch
         bufs = []
         for st in streams:
@@ -1195,7 +1260,6 @@ def main():
     out = None
     if rank == 0:
         total_frames = world * args.steps * B
-        phys = (traffic if traffic else alg_bytes) / (ms_cand * 1e-3) / 1e9
         out = {
             "metric": ("detector frames/s (Eiger-16M 4362x4148 uint16)" if args.workload == "eiger16m"
                        else f"detector frames/s ({args.workload})") + (", extended dispersion" if ext else ""),
@@ -1225,13 +1289,9 @@ def main():
                        "strong_pixels_per_frame": round(strong_steps / max(1, args.steps * B), 1)},
             "repetitions": {"n": len(times), "ms_per_step": [round(t / args.steps * 1e3, 4) for t in times],
                             "value_from": "median repetition of the same steps-step region (barrier + synchronize on both sides of each)"},
-            "steady_ms_per_step": round(steady * 1e3, 4),
-            "drain_ms": round(drain * 1e3, 4),
-            "settling_ms_per_step": [round(t / args.steps * 1e3, 4) for t in settling],
-            "settling": "untimed regions of the same K steps after the W warm-up steps, until two in a row agree within 1 % (at most 8): the GPU's "
-                        "clocks follow its load over tens of ms; --no-settle switches it off",
-            "order_of_legs": "memory-ceiling probe (40 iterations) and the kernel-alone legs, THEN warm-up and the timed regions: a GPU that idled "
-                             "while Python loaded the fixtures needs ~30 ms of load to reach its clocks (tools/rep_probe.py); every repetition is listed",
+            "settling_ms_per_step": [round(t / settle_k * 1e3, 4) for t in settling],
+            "settling": f"untimed regions of the same {settle_k} steps after the W warm-up steps, until two in a row agree within 1 % (at most "
+                        "8): the GPU's clocks follow its load over tens of ms; --no-settle switches it off",
             "n_ranks_seen": n_ranks_seen,
             "results_checked": results_checked,
             "results_check": ({"batches_compared_in_timed_regions": check["batches"], "bad_batches": check["bad_batches"],
@@ -1239,46 +1299,55 @@ def main():
                                "against": "tests/golden/bench_workloads.npz (oracle results for this rank's frames: reference standalone.cc "
                                           "threshold + restated connected components; tests/golden/make_golden_bench.py)"}
                               if expected is not None else
-                              {"skipped": "no committed oracle results for this workload / rank / batch size"}),
-            "roofline": {"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS,
-                         "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic,
-                         "traffic_source": traffic_src,
-                         "measured_peak": {"read_only_GBps": round(peak_read, 1), "read_write_2to1_GBps": round(peak_mix, 1),
-                                           "probe": "ffs_bench_hbm: linear 16 B/lane reads of the batch's pixel buffer; the same with an "
-                                                    "8 B zero store per 16 B read (the kernel's read/write mix)"},
-                         "frac_physical": (round(phys / HBM_PEAK_GBS, 4) if traffic else None),
-                         "frac_of_measured_read": round(phys / max(peak_read, 1.0), 4),
-                         "target": "frac_of_measured_read >= 0.80 (physical bytes / time / read ceiling measured in this run); `frac` is "
-                                   "SURVEY 8(d)'s algorithmic fraction, which credits 2 B/px the kernel never moves (it reads 1.0 at 0.289 ms: above that it "
-                                   "says nothing); `frac_physical` = PMC bytes / time / nominal 8 TB/s",
-                         "kernel": ("k_stream_u16<2,true> (extended first pass)" if ext else
-                                    "k_stream_u16 (whole threshold stage)" if dt == np.uint16 else "k_stream_u32 (whole threshold stage)"),
-                         "ms_per_launch": round(ms_cand, 4),
-                         "ms_per_launch_from": (f"mean over the {len(thr_timed)} batches of the timed regions, each from the HIP events on its own dispatch "
-                                                "(in the pipeline, beside the other batches' sparse launches)" if (not ext and thr_timed) else
-                                                "ffs_bench_threshold: the kernel launched alone, 10 launches"),
-                         "ms_per_launch_alone": round(ms_alone, 4),
-                         "algorithmic_bytes_per_launch": int(alg_bytes),
-                         "exact_kernel_ms_per_launch": round(ms_exact, 4),
-                         "dense_mask": False,
-                         "note": "algorithmic bytes = SURVEY 8(d): pixel + 1 mask byte read + 1 strong-mask byte written per pixel; the kernel "
-                                 "reads the mask as bit tables and leaves the strong mask bit-packed (1 bit/px, non-zero words only), so its physical "
-                                 "traffic is below the algorithmic figure (`traffic`, `physical_GBps`); `with_dense_mask` is the same kernel also "
-                                 "writing the byte mask (want_strong_mask=1)",
-                         "physical_GBps": (round(traffic / (ms_cand * 1e-3) / 1e9, 1) if traffic else None),
-                         "with_dense_mask": ({"ms_per_launch": round(ms_dense, 4),
-                                              "achieved": round(alg_bytes / (ms_dense * 1e-3) / 1e9, 1),
-                                              "frac": round(alg_bytes / (ms_dense * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
-                                              "traffic": traffic_dense, "traffic_source": traffic_dense_src,
-                                              "frac_of_measured_mix": round((traffic_dense or alg_bytes) / (ms_dense * 1e-3) / 1e9 / max(peak_mix, 1.0), 4)}
-                                             if ms_dense else None)},
-            "stage_ms_last_batch": {k: round(v, 4) for k, v in tm.items()},
+                              {"skipped": "no committed oracle results for this workload / rank / batch size" if args.full
+                                          else "a plain run: --full compares every timed batch with the committed oracle results"}),
         }
-        # the whole threshold stage (streaming kernel + fix-up) against the same algorithmic bytes
-        out["roofline"]["threshold_stage_frac"] = round(
-            alg_bytes / ((ms_cand + ms_exact) * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)
+        if args.full:
+            phys = (traffic if traffic else alg_bytes) / (ms_cand * 1e-3) / 1e9
+            out.update({
+                "steady_ms_per_step": round(steady * 1e3, 4),
+                "drain_ms": round(drain * 1e3, 4),
+                "order_of_legs": "memory-ceiling probe (40 iterations) and the kernel-alone legs, THEN warm-up and the timed regions: a GPU that idled "
+                                 "while Python loaded the fixtures needs ~30 ms of load to reach its clocks (tools/rep_probe.py); every repetition is listed",
+                "roofline": {"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS,
+                             "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic,
+                             "traffic_source": traffic_src,
+                             "measured_peak": {"read_only_GBps": round(peak_read, 1), "read_write_2to1_GBps": round(peak_mix, 1),
+                                               "probe": "ffs_bench_hbm: linear 16 B/lane reads of the batch's pixel buffer; the same with an "
+                                                        "8 B zero store per 16 B read (the kernel's read/write mix)"},
+                             "frac_physical": (round(phys / HBM_PEAK_GBS, 4) if traffic else None),
+                             "frac_of_measured_read": round(phys / max(peak_read, 1.0), 4),
+                             "target": "frac_of_measured_read >= 0.80 (physical bytes / time / read ceiling measured in this run); `frac` is "
+                                       "SURVEY 8(d)'s algorithmic fraction, which credits 2 B/px the kernel never moves (it reads 1.0 at 0.289 ms: above that it "
+                                       "says nothing); `frac_physical` = PMC bytes / time / nominal 8 TB/s",
+                             "kernel": ("k_stream_u16<2,true> (extended first pass)" if ext else
+                                        "k_stream_u16 (whole threshold stage)" if dt == np.uint16 else "k_stream_u32 (whole threshold stage)"),
+                             "ms_per_launch": round(ms_cand, 4),
+                             "ms_per_launch_from": (f"mean over the {len(thr_timed)} batches of the timed regions, each from the HIP events on its own dispatch "
+                                                    "(in the pipeline, beside the other batches' sparse launches)" if (not ext and thr_timed) else
+                                                    "ffs_bench_threshold: the kernel launched alone, 10 launches"),
+                             "ms_per_launch_alone": round(ms_alone, 4),
+                             "algorithmic_bytes_per_launch": int(alg_bytes),
+                             "exact_kernel_ms_per_launch": round(ms_exact, 4),
+                             "dense_mask": False,
+                             "note": "algorithmic bytes = SURVEY 8(d): pixel + 1 mask byte read + 1 strong-mask byte written per pixel; the kernel "
+                                     "reads the mask as bit tables and leaves the strong mask bit-packed (1 bit/px, non-zero words only), so its physical "
+                                     "traffic is below the algorithmic figure (`traffic`, `physical_GBps`); `with_dense_mask` is the same kernel also "
+                                     "writing the byte mask (want_strong_mask=1)",
+                             "physical_GBps": (round(traffic / (ms_cand * 1e-3) / 1e9, 1) if traffic else None),
+                             "with_dense_mask": ({"ms_per_launch": round(ms_dense, 4),
+                                                  "achieved": round(alg_bytes / (ms_dense * 1e-3) / 1e9, 1),
+                                                  "frac": round(alg_bytes / (ms_dense * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
+                                                  "traffic": traffic_dense, "traffic_source": traffic_dense_src,
+                                                  "frac_of_measured_mix": round((traffic_dense or alg_bytes) / (ms_dense * 1e-3) / 1e9 / max(peak_mix, 1.0), 4)}
+                                                 if ms_dense else None)},
+                "stage_ms_last_batch": {k: round(v, 4) for k, v in tm.items()},
+            })
+            # the whole threshold stage (streaming kernel + fix-up) against the same algorithmic bytes
+            out["roofline"]["threshold_stage_frac"] = round(
+                alg_bytes / ((ms_cand + ms_exact) * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)
         if use_dist:
-            n_timed = args.warmup + (len(times) + 2) * args.steps
+            n_timed = args.warmup + (len(times) + (2 if args.full else 0)) * args.steps
             out["config"]["gather_host_ms_per_step"] = {"pack": round(gather_s[0] / n_timed * 1e3, 4),
                                                         "collective": round(gather_s[1] / n_timed * 1e3, 4),
                                                         **{k: round(v / n_timed * 1e3, 4) for k, v in gather_t.items()}}
@@ -1296,7 +1365,7 @@ def main():
                 "submit_call_ms": round(submit_ms, 3)}
         if e2e is not None:
             out["cli_e2e"] = e2e
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(frames, mask, ext)
         print(json.dumps(out), flush=True)
     if dist is not None:

@@ -13,6 +13,8 @@ What is recorded (data only -- inputs, or seeds + SHA-256 of inputs, and expecte
                            Eiger-16M + module-gap mask): SHA-256 of the images as produced by the
                            reference's generator (compiled into /tmp from h5read.c when HDF5 headers
                            are available), and the reference's strong-pixel lists for them
+  dispersion_random.npz    the six seeded frames of tests/test_oracle_golden.py::test_port_equals_compiled_reference
+                           (tests/golden_util.py: random_input): SHA-256 of input and mask, the reference's strong masks
 The expected outputs come from StandaloneSpotfinder<double>::standard_dispersion
 (baseline/spotfinder/standalone.cc:258-270) through oracle/ref_shim.cc.
 """
@@ -28,9 +30,11 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
 sys.path.insert(0, os.path.join(ROOT, "fast-feedback-service_amd", "python"))
 sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.dirname(HERE))
 
 from ffs_amd import synth  # noqa: E402
 from oracle import oracle as O  # noqa: E402
+import golden_util  # noqa: E402
 
 
 def sha(a):
@@ -143,8 +147,19 @@ def main():
         out[f"sample{i}/strong_k"] = np.flatnonzero(strong).astype(np.uint32)
         print(f"sample {i}: {int(strong.sum())} strong")
     np.savez_compressed(os.path.join(HERE, "dispersion_samples.npz"), **out)
+    random_cases()
     for f in sorted(os.listdir(HERE)):
         print(f, os.path.getsize(os.path.join(HERE, f)))
+
+
+def random_cases():
+    out = {}
+    for seed in range(6):
+        img, m = golden_util.random_input(seed)
+        out[f"seed{seed}/input_sha256"] = np.array(sha(img))
+        out[f"seed{seed}/mask_sha256"] = np.array(sha(m))
+        out[f"seed{seed}/strong"] = np.packbits(O.RefSpotfinder(img.shape[1], img.shape[0])(img, m), axis=None)
+    np.savez_compressed(os.path.join(HERE, "dispersion_random.npz"), **out)
 
 
 if __name__ == "__main__":

@@ -42,3 +42,28 @@ def samples(indices=range(6)):
         img = synth.reference_sample(i)
         assert sha(img) == str(z[f"sample{i}/input_sha256"])
         yield i, img, mask, z[f"sample{i}/strong_k"]
+
+
+def random_input(seed):
+    """The seeded frame and mask of test_oracle_golden.py::test_port_equals_compiled_reference (Poisson background at one of
+    five levels, ten bright pixels, a pixel above 2^24 for odd seeds, 3 % of the pixels masked)."""
+    rng = np.random.default_rng(seed)
+    H, W = int(rng.integers(20, 200)), int(rng.integers(20, 300))
+    lam = float(rng.choice([0.05, 1.0, 7.0, 200.0, 5000.0]))
+    img = rng.poisson(lam, (H, W)).astype(np.uint32)
+    for _ in range(10):
+        y, x = rng.integers(0, H), rng.integers(0, W)
+        img[y, x] += rng.integers(10, 60000)
+    if seed % 2:
+        img[rng.integers(0, H), rng.integers(0, W)] = (1 << 24) + 17
+    mask = (rng.random((H, W)) > 0.03).astype(np.uint8)
+    return img, mask
+
+
+def random_case(seed):
+    """random_input(seed) and the reference's strong mask for it (dispersion_random.npz)."""
+    z = np.load(os.path.join(GOLD, "dispersion_random.npz"))
+    img, mask = random_input(seed)
+    assert sha(img) == str(z[f"seed{seed}/input_sha256"]) and sha(mask) == str(z[f"seed{seed}/mask_sha256"]), \
+        "numpy's generator drifted from the fixture"
+    return img, mask, np.unpackbits(z[f"seed{seed}/strong"])[: img.size].reshape(img.shape)

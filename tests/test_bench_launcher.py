@@ -67,3 +67,28 @@ def test_three_ranks_gather_rows_with_an_empty_rank_and_the_padded_partner():
         assert p.returncode == 0, p.stderr[-2000:]
         d = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("{")][0])
         assert d["n_gpus"] == 3 and d["n_ranks_seen"] == 3, d     # (the empty rank is seen too: its tag travels with its count)
+
+
+def test_dumped_outputs_stay_under_64_mb_and_sample_the_same_rows(tmp_path):
+    # --dump-outputs: float64 files; a batch whose tables exceed the budget keeps a fixed, seeded sample of their rows and every
+    # small per-frame array whole
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    rng = np.random.default_rng(1)
+    boxes = rng.integers(0, 4000, (3_000_000, 5))
+    boxes[:, 0] = np.arange(len(boxes))                       # (a row's index: which rows were kept)
+    arrays = {"n_boxes": np.arange(256, dtype=np.uint32), "boxes": boxes, "reflections": rng.random((1_000_000, 17), dtype=np.float32)}
+    for d in (tmp_path / "a", tmp_path / "b"):
+        bench.dump_outputs(str(d), arrays)
+    got = {p.name: np.load(p) for p in (tmp_path / "a").iterdir()}
+    assert sorted(got) == ["boxes.npy", "n_boxes.npy", "reflections.npy"]
+    assert sum(p.stat().st_size for p in (tmp_path / "a").iterdir()) <= 64 << 20
+    assert all(a.dtype == np.float64 for a in got.values())
+    assert np.array_equal(got["n_boxes.npy"], np.arange(256))
+    assert 0 < len(got["boxes.npy"]) < 3_000_000 and got["reflections.npy"].shape[1] == 17
+    for name, a in got.items():
+        assert np.array_equal(a, np.load(tmp_path / "b" / name))
+    kept = got["boxes.npy"][:, 0].astype(np.int64)
+    assert np.all(np.diff(kept) > 0)                          # rows of the input, in their order
+    assert np.array_equal(got["boxes.npy"], boxes[kept].astype(np.float64))

@@ -117,3 +117,47 @@ def test_partial_batches_and_two_in_flight_without_lists(ffs):
         for f, fr in enumerate(res):
             assert_frame_matches_oracle(fr, frames[f + 3], mask, precomputed=want[f + 3])
     _pipeline(streams, d_frames.data_ptr() + 3 * fstride, pitch, fstride, 5, 6, check)
+
+
+def test_plain_and_full_runs_time_the_steps_and_dump_the_last_step(ffs, tmp_path):
+    """bench.py as the driver runs it: a plain run times ONE region of exactly --steps steps and carries none of the --full legs;
+    --dump-outputs writes what the last timed step returned, the same in both runs and bit for bit the committed oracle results."""
+    import json
+    import subprocess
+    from ffs_amd import api, fixtures
+    steps, B = 6, 32
+    lines = {}
+    for kind, extra in (("plain", []), ("full", ["--full", "--no-cpu-baseline", "--no-streamed", "--no-cli-e2e"])):
+        p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", "2",
+                            "--dump-outputs", str(tmp_path / kind), *extra], capture_output=True, text=True, timeout=600, cwd=tmp_path)
+        assert p.returncode == 0, p.stderr[-2000:]
+        lines[kind] = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("{")][-1])
+    plain, full = lines["plain"], lines["full"]
+    assert plain["steps"] == steps and plain["repetitions"]["n"] == 1 and plain["ms_per_step"] > 0
+    assert abs(plain["value"] - B * 1e3 / plain["ms_per_step"]) < 1e-3 * plain["value"]
+    assert not {"roofline", "steady_ms_per_step", "cpu_baseline", "cli_e2e", "streamed_frames_per_s"} & set(plain)
+    assert full["repetitions"]["n"] == 5 and "roofline" in full and full["results_checked"] is True
+    for k in ("metric", "unit", "higher_is_better", "dtype"):
+        assert plain[k] == full[k]
+
+    names = sorted(f.name for f in (tmp_path / "plain").iterdir())
+    assert names == sorted(f.name for f in (tmp_path / "full").iterdir())
+    got = {n[:-4]: np.load(tmp_path / "plain" / n) for n in names}
+    for n, a in got.items():
+        assert a.dtype == np.float64 and np.array_equal(a, np.load(tmp_path / "full" / (n + ".npy"))), n
+    assert np.array_equal(got["frame_id"], np.arange((steps - 1) * B, steps * B))
+    assert got["n_boxes"].sum() == len(got["boxes"]) and got["n_reflections"].sum() == len(got["reflections"])
+
+    def records(table, dt):
+        out = np.zeros(len(table), dt)
+        for i, f in enumerate(dt.names):
+            out[f] = table[:, i]
+        return out
+    boxes, refls = records(got["boxes"], api.BOX_DT), records(got["reflections"], api.REFL_DT)
+    expected = fixtures.load_expected("eiger16m", "dispersion", 0, B)
+    assert np.array_equal(got["num_strong_pixels"], expected["num_strong_pixels"])
+    b0 = r0 = 0
+    for f in range(B):
+        nb, nr = int(got["n_boxes"][f]), int(got["n_reflections"][f])
+        assert fixtures.frame_digest(boxes[b0:b0 + nb], refls[r0:r0 + nr]) == expected["digest"][f].tobytes(), f
+        b0, r0 = b0 + nb, r0 + nr

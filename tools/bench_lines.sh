@@ -2,10 +2,11 @@
 # The four bench lines at the driver's arguments (--steps 20 --warmup 5), one JSON line each:  gpurun -- 'bash tools/bench_lines.sh <tag>'
 tag=${1:-lines}
 out=gpurun_out/${tag}_bench_lines_steps20.jsonl; : > $out
-python bench.py --steps 20 --warmup 5 >> $out 2> gpurun_out/${tag}_bench.err || echo "eiger16m failed"
-python bench.py --steps 20 --warmup 5 --algorithm dispersion_extended --no-cli-e2e >> $out 2>> gpurun_out/${tag}_bench.err || echo "extended failed"
-python bench.py --steps 20 --warmup 5 --workload jungfrau9m --no-cli-e2e >> $out 2>> gpurun_out/${tag}_bench.err || echo "jungfrau failed"
-python bench.py --steps 20 --warmup 5 --workload sweep16m --no-cli-e2e >> $out 2>> gpurun_out/${tag}_bench.err || echo "sweep failed"
+err=${out%.jsonl}.err; : > $err
+python bench.py --full --steps 20 --warmup 5 >> $out 2>> $err || echo "eiger16m failed"
+python bench.py --full --steps 20 --warmup 5 --algorithm dispersion_extended --no-cli-e2e >> $out 2>> $err || echo "extended failed"
+python bench.py --full --steps 20 --warmup 5 --workload jungfrau9m --no-cli-e2e >> $out 2>> $err || echo "jungfrau failed"
+python bench.py --full --steps 20 --warmup 5 --workload sweep16m --no-cli-e2e >> $out 2>> $err || echo "sweep failed"
 python - <<PY
 import json
 for ln in open("$out"):

@@ -1,7 +1,7 @@
 #!/bin/bash
 # extended dispersion: A/B of tuning sets through bench.py
 for t in "" "ccl_grid=64" "ccl_grid=128" "sparse_stage=3" "ccl_grid=16"; do
-  python bench.py --no-cpu-baseline --no-streamed --no-cli-e2e --steps 60 --reps 3 --algorithm dispersion_extended ${t:+--tune $t} > /tmp/x.json 2>/tmp/x.err
+  python bench.py --full --no-cpu-baseline --no-streamed --no-cli-e2e --steps 60 --reps 3 --algorithm dispersion_extended ${t:+--tune $t} > /tmp/x.json 2>/tmp/x.err
   python - <<PY
 import json
 d=json.load(open("/tmp/x.json")); r=d["roofline"]

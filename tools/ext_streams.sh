@@ -1,7 +1,7 @@
 #!/bin/bash
 # extended dispersion: whole-pipeline step time against the number of streams in flight (how much of the sparse stage overlaps)
 for st in 1 2 4 6 8; do
-  python bench.py --no-cpu-baseline --no-streamed --no-cli-e2e --steps 60 --reps 3 --streams $st --algorithm dispersion_extended "$@" > /tmp/x.json 2>/tmp/x.err
+  python bench.py --full --no-cpu-baseline --no-streamed --no-cli-e2e --steps 60 --reps 3 --streams $st --algorithm dispersion_extended "$@" > /tmp/x.json 2>/tmp/x.err
   python - <<PY
 import json
 d=json.load(open("/tmp/x.json")); r=d["roofline"]

@@ -5,7 +5,7 @@ tag=${1:-kcheck}; shift
 out=gpurun_out/$tag; mkdir -p $out
 python -m pytest tests -m gpu -q -x -k "golden or parity or fuzz or edge or extended or numerics or fullsize" > $out/tests.log 2>&1; rc=$?; tail -3 $out/tests.log
 [ $rc -ne 0 ] && exit $rc
-python bench.py --no-cpu-baseline --no-streamed --no-cli-e2e --steps 100 "$@" > $out/bench.json 2> $out/bench.err; rc=$?
+python bench.py --full --no-cpu-baseline --no-streamed --no-cli-e2e --steps 100 "$@" > $out/bench.json 2> $out/bench.err; rc=$?
 python - <<PY
 import json
 d=json.load(open("$out/bench.json")); r=d["roofline"]

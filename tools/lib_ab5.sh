@@ -4,7 +4,7 @@
 other=$1; shift
 for rep in 1 2 3; do for lib in "" $other; do
   for steps in 20 100; do
-  FFS_HIP_LIB=$lib python bench.py --no-cpu-baseline --no-streamed --no-cli-e2e --steps $steps --warmup 5 --reps 5 "$@" > /tmp/x.json 2>/tmp/x.err || { echo "${lib:-this build} FAILED"; tail -3 /tmp/x.err; continue; }
+  FFS_HIP_LIB=$lib python bench.py --full --no-cpu-baseline --no-streamed --no-cli-e2e --steps $steps --warmup 5 --reps 5 "$@" > /tmp/x.json 2>/tmp/x.err || { echo "${lib:-this build} FAILED"; tail -3 /tmp/x.err; continue; }
   python -c "
 import json; d=json.load(open('/tmp/x.json')); r=d['roofline']; print('${lib:-this build} steps $steps:', d['value'], 'fps | ms/step', d['ms_per_step'], 'steady', d['steady_ms_per_step'], 'drain', d['drain_ms'], '| kernel (events)', r['ms_per_launch'], 'alone', r['ms_per_launch_alone'], '| checked', d.get('results_checked'))"
   done

@@ -1,7 +1,7 @@
 #!/bin/bash
 # the standard path with the streaming kernel's wave logs (strong_log=1) against the bit plane (0): bench line, alternating
 for t in strong_log=0 strong_log=1 strong_log=0 strong_log=1; do
-  python bench.py --no-cpu-baseline --no-streamed --no-cli-e2e --steps 100 --reps 5 --tune $t "$@" > /tmp/x.json 2>/tmp/x.err
+  python bench.py --full --no-cpu-baseline --no-streamed --no-cli-e2e --steps 100 --reps 5 --tune $t "$@" > /tmp/x.json 2>/tmp/x.err
   python - <<PY
 import json
 d=json.load(open("/tmp/x.json")); r=d["roofline"]
