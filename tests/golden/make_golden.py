@@ -15,6 +15,9 @@ What is recorded (data only -- inputs, or seeds + SHA-256 of inputs, and expecte
                            are available), and the reference's strong-pixel lists for them
   dispersion_random.npz    the six seeded frames of tests/test_oracle_golden.py::test_port_equals_compiled_reference
                            (tests/golden_util.py: random_input): SHA-256 of input and mask, the reference's strong masks
+  dispersion_ties.npz      the tie frames of tests/tie_windows.py at the default parameters (16- and 32-bit pixels): SHA-256
+                           of each frame (image and mask), the reference's strong masks as packed bits
+                           (`python tests/golden/make_golden.py ties` writes this file alone)
 The expected outputs come from StandaloneSpotfinder<double>::standard_dispersion
 (baseline/spotfinder/standalone.cc:258-270) through oracle/ref_shim.cc.
 """
@@ -148,6 +151,7 @@ def main():
         print(f"sample {i}: {int(strong.sum())} strong")
     np.savez_compressed(os.path.join(HERE, "dispersion_samples.npz"), **out)
     random_cases()
+    tie_cases()
     for f in sorted(os.listdir(HERE)):
         print(f, os.path.getsize(os.path.join(HERE, f)))
 
@@ -162,5 +166,21 @@ def random_cases():
     np.savez_compressed(os.path.join(HERE, "dispersion_random.npz"), **out)
 
 
+def tie_cases():
+    import tie_windows
+    out = {}
+    for dt in ("uint16", "uint32"):
+        tf = tie_windows.frame(dt)
+        out[f"{dt}/digest"] = np.array(tf.digest())
+        out[f"{dt}/shape"] = np.array(tf.image.shape)
+        out[f"{dt}/strong"] = np.packbits(ref_mask(tf.image, tf.mask), axis=None)
+    np.savez_compressed(os.path.join(HERE, "dispersion_ties.npz"), **out)
+
+
 if __name__ == "__main__":
-    main()
+    if sys.argv[1:] == ["ties"]:
+        if not O.have_ref():
+            sys.exit("oracle/_ref/libffs_ref.so missing: run `make -C oracle` where /root/reference exists")
+        tie_cases()
+    else:
+        main()
