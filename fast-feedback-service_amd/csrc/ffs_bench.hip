@@ -25,6 +25,11 @@ extern "C" int ffs_bench_threshold(ffs_stream* s, const void* device_pixels, siz
     }
     s->ext_e_clean = false;
     ThresholdArgs ta = make_threshold_args(s, device_pixels, pitch, fstride, n_frames);
+    if (!ext && !win_default(c->params) && !window_kernel_for(s, ta)) {
+        // (threshold_path 2 at another window: the batch has no dense kernel, k_exact_w gathers every pixel -- nothing here to time)
+        c->err = "ffs_bench_threshold: threshold_path 2 with a window other than 3,3 has no dense kernel to time";
+        return FFS_ERR_INVALID;
+    }
     const bool e_sparse = ext && c->tune.ext_erode != 0 && c->tune.ext_e_sparse;   // (the hot path clears the signal-region plane behind the previous batch)
     ta.eplane_clean = e_sparse ? 1 : 0;
     if (!ext) (void)wave_logs_for(s, ta, n_frames);   // (the kernel as the hot path launches it)

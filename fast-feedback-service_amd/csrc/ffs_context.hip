@@ -92,6 +92,8 @@ extern "C" void ffs_default_params(ffs_params* p) {
     p->want_strong_mask = 0;
     p->algorithm = FFS_ALGO_DISPERSION;
     p->extended_flavour = 0;
+    p->kernel_half_x = 3;     // standalone.cc:16 (kernel_size_ = 3,3)
+    p->kernel_half_y = 3;
 }
 
 extern "C" int ffs_device_count(void) {
@@ -402,9 +404,20 @@ extern "C" int ffs_ctx_apply_resolution_mask(ffs_ctx* c, float wavelength, float
 
 extern "C" int ffs_ctx_set_params(ffs_ctx* c, const ffs_params* p) {
     if (!c || !p) return FFS_ERR_INVALID;
-    if (p->min_count < 2 || p->min_count > 49 || p->nsig_b < 0 || p->nsig_s < 0 || p->threshold < 0) {
-        c->err = "ffs_ctx_set_params: need 2 <= min_count <= 49, nsig_b >= 0, nsig_s >= 0, threshold >= 0";
+    if (p->kernel_half_x < 0 || p->kernel_half_x > kWinMaxHalf || p->kernel_half_y < 0 || p->kernel_half_y > kWinMaxHalf) {
+        c->err = "ffs_ctx_set_params: kernel_half_x / kernel_half_y must be in 1..7 (0 = 3)";
+        return FFS_ERR_INVALID;
+    }
+    const int win_px = (2 * win_half(p->kernel_half_x) + 1) * (2 * win_half(p->kernel_half_y) + 1);
+    if (p->min_count < 2 || p->min_count > win_px || p->nsig_b < 0 || p->nsig_s < 0 || p->threshold < 0) {
+        c->err = "ffs_ctx_set_params: need 2 <= min_count <= (2*kernel_half_x+1)*(2*kernel_half_y+1) (49 for the 7x7 window), "
+                 "nsig_b >= 0, nsig_s >= 0, threshold >= 0";
         return FFS_ERR_INVALID;  // the asserts of standalone.cc:52-63
+    }
+    if (p->algorithm == FFS_ALGO_DISPERSION_EXTENDED && !win_default(*p)) {
+        c->err = "ffs_ctx_set_params: the extended dispersion algorithm needs the 7x7 window (kernel_half_x = kernel_half_y = 3): "
+                 "its erosion and final pass derive from it";
+        return FFS_ERR_INVALID;
     }
     if ((p->algorithm != FFS_ALGO_DISPERSION && p->algorithm != FFS_ALGO_DISPERSION_EXTENDED)
         || (p->extended_flavour != 0 && p->extended_flavour != 1)) {
@@ -430,6 +443,7 @@ extern "C" int ffs_ctx_set_tuning(ffs_ctx* c, const char* key, long long value) 
     auto in = [&](long long lo, long long hi) { return value >= lo && value <= hi; };
     bool ok = true;
     if (k == "threshold_path") { if ((ok = in(0, 2))) t.threshold_path = (int)value; }
+    else if (k == "window_kernel") { if ((ok = in(0, 1))) t.window_kernel = (int)value; }
     else if (k == "ext_first_pass") { if ((ok = value == 0 || value == 2)) t.ext_first_pass = (int)value; }
     else if (k == "sparse_stage") { if ((ok = in(1, 3))) t.sparse_stage = (int)value; }
     else if (k == "device_lists") { if ((ok = in(0, 2))) t.device_lists = (int)value; }

@@ -45,6 +45,8 @@ constexpr int kSOwned = 62;
 __host__ __device__ inline int band_first_row(int band, int band_rows, int band_rows2, int band_split) {
     return band < band_split ? band * band_rows : band_split * band_rows + (band - band_split) * band_rows2;
 }
+// General-window kernel (kernels_window.hpp): a lane holds one eight-pixel group (16 / 32 bytes) of a row; lanes 1..62 own output
+constexpr int kWinOwned = 62;
 constexpr int kInfoExtraRows = 3;    // ginfo row y carries the mask bits of row y and the window counts of row y - 3
 
 // Exact-stage tiles: one 256-thread workgroup per 8 rows.
@@ -120,6 +122,11 @@ struct ThresholdArgs {
     uint32_t handoff_seq;
     int dbg_prio;              // tuning "stream_prio": the 16-bit streaming kernel raises its waves' issue priority (s_setprio 3)
     int dbg;                   // timing experiments (-DFFS_EXPERIMENTS builds only; results are wrong when set)
+    // the window (ffs_params.kernel_half_x / _y, 1..7): the general-window kernel (kernels_window.hpp) and k_exact's runtime-window
+    // gather (exact_strong_w); the 7x7 kernels above have it built in
+    int kx, ky;
+    int w_strips, w_band_rows, w_bands;   // general-window kernel: a wave per (strip of 62 eight-pixel groups, band of rows, frame)
+    float w_kS, w_kB;          // its float32 screens: nsig_s^2 (1 - 2^-16), nsig_b^2 (1 - 2^-16); 0 = screen off
 };
 
 // The streaming launch's units.  A unit = one wave = one band of one strip; units are numbered band after band (u = band * n_strips +

@@ -111,6 +111,8 @@ struct Tuning {
     int assembly_threads = 7;   // helper threads that assemble a batch's result arrays beside the caller (made with the context's first large batch)
     int wait_ahead = 1;         // a thread of the context assembles each batch's result arrays as soon as the GPU has finished it (0: ffs_wait does)
     int sparse_priority = 0;    // priority of the context's sparse HIP streams: 0 = highest, 1 = lowest, 2 = the dense stream's
+    int window_kernel = 0;      // 1: the general-window kernel (kernels_window.hpp) also runs the 7x7 window -- the A/B and cross-check partner
+                                //    of k_stream_u16 / k_stream_u32; 0: only windows other than 3,3 take it
 #ifdef FFS_EXPERIMENTS
     struct Exp {
         int k1_debug = 0, chain_skip = 0, chain_stop = 0, dummy_us = 0, dummy_wg = 32, dummy_threads = 1024, dummy_lds = 0;
@@ -381,6 +383,10 @@ static int guarded(ffs_ctx* c, F&& body) {
     } while (0)
 
 // ---- small helpers ------------------------------------------------------------------------------------------
+// window half-sizes of a parameter set (ffs_params.kernel_half_x / _y: 0 means 3)
+constexpr int kWinMaxHalf = 7;
+static inline int win_half(int v) { return v ? v : 3; }
+static inline bool win_default(const ffs_params& p) { return win_half(p.kernel_half_x) == 3 && win_half(p.kernel_half_y) == 3; }
 static inline int round_up(int v, int m) { return (v + m - 1) / m * m; }
 static inline uint32_t occ_frame_words(const Layout& L) { return (uint32_t)(((uint64_t)L.H * (L.mpitch / 16) + 31) / 32 + 2); }  // (+2: the chain reads a word ahead)
 // per-tile counts | ... | [last - 1] workgroups of k_frame_chain through with the bright list | [last] entries of the bright list;
@@ -438,6 +444,7 @@ extern std::atomic<int> g_live_stacks;   // 3D stacks alive in the process (ffs_
 bool wave_logs_for(ffs_stream* s, ThresholdArgs& a, uint32_t n_frames);
 void bench_launch_dense(ffs_stream* s, const ThresholdArgs& a, uint32_t n_frames, hipEvent_t start, hipEvent_t stop);
 void bench_launch_rest(ffs_stream* s, const ThresholdArgs& a, uint32_t n_frames);
+bool window_kernel_for(const ffs_stream* s, const ThresholdArgs& a);   // this batch's threshold stage is the general-window kernel
 // ffs_wait.hip
 int ffs_wait_impl(ffs_stream* s, const ffs_frame_result** results, uint32_t* n_results);
 void ahead_register(ffs_stream* s);   // the batch just enqueued may be assembled ahead of its ffs_wait

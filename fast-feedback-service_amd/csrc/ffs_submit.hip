@@ -12,6 +12,7 @@
 #include "kernels_chain.hpp"
 #include "kernels_band.hpp"
 #include "kernels_decode.hpp"
+#include "kernels_window.hpp"
 
 bool chain_prepare_device() {   // more than 64 KB of dynamic LDS has to be asked for, per device
     const hipError_t e1 = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_frame_chain<uint16_t>), hipFuncAttributeMaxDynamicSharedMemorySize, kChainDynBytes);
@@ -127,6 +128,21 @@ ThresholdArgs make_threshold_args(ffs_stream* s, const void* img, size_t pitch, 
             }
         }
     }
+    a.kx = win_half(p.kernel_half_x);
+    a.ky = win_half(p.kernel_half_y);
+    {   // the general-window kernel: strips of 62 owned eight-pixel groups; bands at least 6 windows tall (the 2ky + 1 warm-up rows
+        // of a band stay below a sixth of its rows), as many as fill the machine about four times over
+        const int g8 = (L.W + 7) / 8;
+        a.w_strips = (g8 + kWinOwned - 1) / kWinOwned;
+        const long long per_band = std::max<long long>(1, (long long)a.w_strips * n_frames);
+        const int min_rows = std::max(32, 6 * (2 * a.ky + 1));
+        const long long nb = std::max<long long>(1, std::min<long long>(16384 / per_band, std::max(1, L.H / min_rows)));
+        a.w_band_rows = (int)((L.H + nb - 1) / nb + 7) / 8 * 8;
+        a.w_bands = (L.H + a.w_band_rows - 1) / a.w_band_rows;
+        // (only where the float32 arithmetic of the screens can neither overflow nor lose its margin: DESIGN.md section 3.3b)
+        a.w_kS = (std::isfinite(p.nsig_s) && p.nsig_s <= 1024.0) ? (float)(p.nsig_s * p.nsig_s * (1.0 - 1.0 / 65536.0)) : 0.0f;
+        a.w_kB = (std::isfinite(p.nsig_b) && p.nsig_b <= 1024.0) ? (float)(p.nsig_b * p.nsig_b * (1.0 - 1.0 / 65536.0)) : 0.0f;
+    }
     a.dplane = s->d_dplane;
     a.eplane = s->d_eplane;
     a.eplane_clean = s->ext_e_clean ? 1 : 0;
@@ -167,6 +183,32 @@ static void launch_stream(ffs_stream* s, const ThresholdArgs& a, uint32_t n_fram
     else if (s->ctx->tune.rows_ahead >= 4) hipExtLaunchKernelGGL((k_stream_u16<4, false, false>), grid, dim3(64), 0, st, start, stop, 0, a);
     else hipExtLaunchKernelGGL((k_stream_u16<2, false, false>), grid, dim3(64), 0, st, start, stop, 0, a);
 }
+// The general-window kernel (kernels_window.hpp): windows other than 3,3, or every window with tuning "window_kernel" = 1.  The
+// standard algorithm on the plane paths only (no wave logs: those belong to k_stream_u16); the cross-check path (threshold_path 2)
+// keeps its gather.
+bool window_kernel_for(const ffs_stream* s, const ThresholdArgs& a) {
+    return s->batch_params.algorithm == FFS_ALGO_DISPERSION && a.bright_to_plane != 2
+           && (!win_default(s->batch_params) || s->ctx->tune.window_kernel == 1);
+}
+template <typename PixelT>
+static void launch_window_t(const ThresholdArgs& a, dim3 grid, hipStream_t st, hipEvent_t start, hipEvent_t stop) {
+    const size_t lds = win_ring_bytes((int)sizeof(PixelT), a.ky);
+    switch (a.kx) {
+        case 1: hipExtLaunchKernelGGL((k_window<PixelT, 1>), grid, dim3(64), lds, st, start, stop, 0, a); break;
+        case 2: hipExtLaunchKernelGGL((k_window<PixelT, 2>), grid, dim3(64), lds, st, start, stop, 0, a); break;
+        case 3: hipExtLaunchKernelGGL((k_window<PixelT, 3>), grid, dim3(64), lds, st, start, stop, 0, a); break;
+        case 4: hipExtLaunchKernelGGL((k_window<PixelT, 4>), grid, dim3(64), lds, st, start, stop, 0, a); break;
+        case 5: hipExtLaunchKernelGGL((k_window<PixelT, 5>), grid, dim3(64), lds, st, start, stop, 0, a); break;
+        case 6: hipExtLaunchKernelGGL((k_window<PixelT, 6>), grid, dim3(64), lds, st, start, stop, 0, a); break;
+        default: hipExtLaunchKernelGGL((k_window<PixelT, 7>), grid, dim3(64), lds, st, start, stop, 0, a); break;
+    }
+}
+static void launch_window(ffs_stream* s, const ThresholdArgs& a, uint32_t n_frames, hipEvent_t start, hipEvent_t stop, hipStream_t st = nullptr) {
+    const dim3 grid((unsigned)(a.w_strips * a.w_bands), n_frames);
+    if (!st) st = s->st;
+    if (s->ctx->pixel_bytes == 4) launch_window_t<uint32_t>(a, grid, st, start, stop);
+    else launch_window_t<uint16_t>(a, grid, st, start, stop);
+}
 static void launch_bright_fix(ffs_stream* s, const ThresholdArgs& a, hipStream_t st) {
     if (s->ctx->pixel_bytes == 4) hipLaunchKernelGGL(k_bright_fix<uint32_t>, dim3(32), dim3(256), 0, st, a);
     else hipLaunchKernelGGL(k_bright_fix<uint16_t>, dim3(32), dim3(256), 0, st, a);
@@ -175,6 +217,11 @@ static void launch_bright_fix(ffs_stream* s, const ThresholdArgs& a, hipStream_t
 // predicate; rewrites the plane, the per-tile counts and sets the byte mask's 1s
 static void launch_exact(ffs_stream* s, const ThresholdArgs& a, uint32_t n_frames, hipStream_t st) {
     const dim3 grid((unsigned)a.n_tiles, n_frames);
+    if (a.kx != 3 || a.ky != 3) {   // (the runtime-window gather: exact_strong_w)
+        if (s->ctx->pixel_bytes == 4) hipLaunchKernelGGL(k_exact_w<uint32_t>, grid, dim3(256), 0, st, a);
+        else hipLaunchKernelGGL(k_exact_w<uint16_t>, grid, dim3(256), 0, st, a);
+        return;
+    }
     if (s->ctx->pixel_bytes == 4) hipLaunchKernelGGL(k_exact<uint32_t>, grid, dim3(256), 0, st, a);
     else hipLaunchKernelGGL(k_exact<uint16_t>, grid, dim3(256), 0, st, a);
 }
@@ -290,10 +337,12 @@ bool wave_logs_for(ffs_stream* s, ThresholdArgs& a, uint32_t n_frames) {
 
 void bench_launch_dense(ffs_stream* s, const ThresholdArgs& a, uint32_t n_frames, hipEvent_t start, hipEvent_t stop) {
     if (s->batch_params.algorithm == FFS_ALGO_DISPERSION_EXTENDED) launch_ext_first(s, a, n_frames, start, stop);
+    else if (window_kernel_for(s, a)) launch_window(s, a, n_frames, start, stop);
     else launch_stream(s, a, n_frames, start, stop);
 }
 void bench_launch_rest(ffs_stream* s, const ThresholdArgs& a, uint32_t n_frames) {
     if (s->batch_params.algorithm == FFS_ALGO_DISPERSION_EXTENDED) launch_ext_rest(s, a, n_frames, s->st);
+    else if (window_kernel_for(s, a)) return;   // (it decides every pixel itself)
     else if (a.bright_to_plane) launch_exact(s, a, n_frames, s->st);
     else if (!a.wlog) launch_bright_fix(s, a, s->st);   // (with wave logs the sparse launch decides the bright windows)
 }
@@ -388,7 +437,9 @@ int enqueue_batch(ffs_stream* s, const void* d_img, size_t pitch, size_t fstride
     // "streamed": the plane the sparse stage reads was produced by a streaming kernel into a zeroed plane (and is zeroed
     // again by the compaction); path 0 also keeps the occupancy bitmap in step with it
     const bool streamed = !ext;
-    const bool list_path = streamed && !ta.bright_to_plane;
+    // the general-window kernel (kernels_window.hpp) decides every pixel itself: no bright-window list, no fix-up, no wave logs
+    const bool window = streamed && window_kernel_for(s, ta);
+    const bool list_path = streamed && !ta.bright_to_plane && !window;
     bool dense_resets = false;   // fills went into the stream's own dense stream: this batch's kernel has to follow them there
     if (wait_upload && ext) HIP_TRY(c, hipStreamWaitEvent(s->st, s->ev[1], 0));
     if (streamed && s->bits_dirty) {  // (another algorithm or a failed batch left bits behind)
@@ -481,6 +532,15 @@ int enqueue_batch(ffs_stream* s, const void* d_img, size_t pitch, size_t fstride
         launch_ext_first(s, ta, n, ev_start, nullptr, true, ext_plane_clean, counts_were_clean);
         launch_ext_rest(s, ta, n, s->st);
         HIP_TRY(c, hipEventRecord(s->ev[2], s->st));
+        if (s->st2 != s->st) HIP_TRY(c, hipStreamWaitEvent(s->st2, s->ev[2], 0));
+    } else if (window) {
+        // The plane, the per-tile counts, the byte mask when it is asked for and the occupancy bitmap when the one-launch sparse stage
+        // reads it: what that stage reads after k_exact
+        ThresholdArgs tw = ta;
+        tw.dense_mask = (p.want_strong_mask || c->tune.dense_mask) ? 1 : 0;
+        tw.occ = (c->tune.occupancy_bitmap && will_chain) ? s->d_occ : nullptr;
+        if (wait_upload) HIP_TRY(c, hipStreamWaitEvent(s->st, s->ev[1], 0));
+        launch_window(s, tw, n, ev_start, s->ev[2]);
         if (s->st2 != s->st) HIP_TRY(c, hipStreamWaitEvent(s->st2, s->ev[2], 0));
     } else if (list_path && aside) {
         // the bright-window fix-up goes to the sparse stream (or into the sparse launch itself: chain_first; with wave logs the
@@ -580,6 +640,7 @@ int enqueue_batch(ffs_stream* s, const void* d_img, size_t pitch, size_t fstride
     ca.summary = s->d_summary;
     // (the byte mask: zero-filled by the streaming kernels only when asked for; the exact stages always produce it)
     ca.dense_bytes = ((list_path || (ext && ext_stream_first(ta))) ? ta.dense_mask : 1) ? 1 : 0;
+    if (window) ca.dense_bytes = (p.want_strong_mask || c->tune.dense_mask) ? 1 : 0;   // (as launched above)
     ca.need_lists = need_lists ? 1 : 0;
     // (the launch that merges wave logs and the run-based launch of dense frames can do without the lists)
     const bool runs_launch = will_chain && !use_log && c->pixel_bytes == 2 && runs_ok && (dense_batch || c->tune.chain_runs == 2);
@@ -615,7 +676,8 @@ int enqueue_batch(ffs_stream* s, const void* d_img, size_t pitch, size_t fstride
 
     s->chain_mode = will_chain;
     s->path_bits = (use_log ? FFS_PATH_WAVE_LOGS : 0u) | (will_chain && !banded ? FFS_PATH_FRAME_CHAIN : 0u) | (banded ? FFS_PATH_BANDS : 0u)
-                   | (runs_launch ? FFS_PATH_RUNS : 0u) | (!will_chain ? FFS_PATH_GRID_KERNELS : 0u) | (ext ? FFS_PATH_EXTENDED : 0u);
+                   | (runs_launch ? FFS_PATH_RUNS : 0u) | (!will_chain ? FFS_PATH_GRID_KERNELS : 0u) | (ext ? FFS_PATH_EXTENDED : 0u)
+                   | (window ? FFS_PATH_WINDOW : 0u);
     if (s->chain_mode) {
         ChainArgs A{};
         A.c = ca;

@@ -124,6 +124,58 @@ __device__ bool exact_strong(const ThresholdArgs& a, const uint8_t* img, int x, 
     return exact_decide<DISP_ONLY>(a, m, sx, sy, pc, centre_valid);
 }
 
+// exact_strong at the runtime window (2 a.kx + 1) x (2 a.ky + 1), kx, ky in 1..7: what k_exact<., true> gathers on the cross-check
+// path (tuning "threshold_path" = 2) for windows other than 3,3.  Row after row (at most 15), 16 pixels from an even column cover
+// the (<= 15 wide) window row; 64-bit sums, the same predicate.  Shares nothing with kernels_window.hpp but exact_decide.
+template <typename PixelT>
+__device__ bool exact_strong_w(const ThresholdArgs& a, const uint8_t* img, int x, int y) {
+    const int W = a.W, H = a.H;
+    const int xs = max(x - a.kx, 0), xe = min(x + a.kx, W - 1);  // window clipped to the image, :126-130
+    const int bx = min(xs & ~1, a.pitch_px - 16);
+    const uint32_t rm = (xe - bx + 1 >= 32 ? ~0u : ((1u << (xe - bx + 1)) - 1u)) & ~((1u << (xs - bx)) - 1u);
+    const int sh = bx & 7;
+    uint32_t m = 0, pc = 0;
+    unsigned long long sx = 0, sy = 0;
+    bool centre_valid = false;
+#pragma unroll 1
+    for (int yy = max(y - a.ky, 0); yy <= min(y + a.ky, H - 1); ++yy) {
+        const uint8_t* mp = a.maskbits + (uint64_t)yy * a.mpitch + (bx >> 3);
+        uint32_t mb = (uint32_t)mp[0] | ((uint32_t)mp[1] << 8);
+        if (sh) mb |= (uint32_t)mp[2] << 16;   // (bx <= pitch_px - 18 then: inside the row)
+        const uint32_t bits = (mb >> sh) & rm;
+        const uint8_t* rp = img + (uint64_t)yy * a.pitch + (uint64_t)bx * sizeof(PixelT);
+        uint32_t p[16];
+        if constexpr (sizeof(PixelT) == 2) {
+            const uint4 q0 = *reinterpret_cast<const uint4*>(rp), q1 = *reinterpret_cast<const uint4*>(rp + 16);
+            const uint32_t w[8] = {q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, q1.z, q1.w};
+#pragma unroll
+            for (int j = 0; j < 8; ++j) { p[2 * j] = w[j] & 0xFFFFu; p[2 * j + 1] = w[j] >> 16; }
+        } else {
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const uint4 v = *reinterpret_cast<const uint4*>(rp + 16 * q);
+                p[4 * q] = v.x; p[4 * q + 1] = v.y; p[4 * q + 2] = v.z; p[4 * q + 3] = v.w;
+            }
+        }
+        if (yy == y) {  // the candidate itself
+            const int q = x - bx;
+            centre_valid = (mb >> (sh + q)) & 1u;
+#pragma unroll
+            for (int j = 0; j < 16; ++j)
+                if (j == q) pc = p[j];
+        }
+#pragma unroll
+        for (int q = 0; q < 16; ++q) {
+            const bool inc = ((bits >> q) & 1u) && (sizeof(PixelT) == 2 || p[q] < (1u << 24));
+            const uint32_t pv = inc ? p[q] : 0u;
+            m += inc ? 1u : 0u;
+            sx += pv;
+            sy += (unsigned long long)pv * pv;
+        }
+    }
+    return exact_decide<false>(a, m, sx, sy, pc, centre_valid);
+}
+
 // The same decision from the same sums with HALF the registers: the window's rows come in two batches (four, then three) -- two
 // memory round trips instead of one, 16 + 4 registers of pixels and mask bits in flight instead of 28 + 7.  For callers that must
 // stay small (kernels_band.hpp: a one-wave workgroup that has to fit where a streaming wave has left).
@@ -205,7 +257,8 @@ __device__ __forceinline__ uint32_t ext_erode_hrow(const ThresholdArgs& a, const
 //         y0 - 7 .. y0 + 14 of the first-pass plane a.dplane into LDS (dynamic: 18 rows of the plane), writes its own eight rows
 //         of E to a.eplane (for --writeout / ffs_stream_debug_bitplane) and takes every window's E bits from LDS: one launch and a
 //         round trip of the plane less than k_ext_erode + MODE 2.
-template <typename PixelT, int NT, int LISTCAP, int MODE = 0>
+// WIN (MODE 0 only): the runtime window of exact_strong_w instead of the 7x7 one.
+template <typename PixelT, int NT, int LISTCAP, int MODE = 0, bool WIN = false>
 __device__ __forceinline__ void exact_tile(const ThresholdArgs& a) {
     // The stage is latency-bound (sparse gathers).  Measured dead ends: a smaller LDS footprint
     // (more tiles resident) and one-wave workgroups both made it slower.  Round 4, extended algorithm (MODE 2, profiles/r04r_ext_final_*):
@@ -329,6 +382,7 @@ __device__ __forceinline__ void exact_tile(const ThresholdArgs& a) {
             const int y = y0 + row;
             bool strong;
             if constexpr (MODE == 1) strong = ext_final_strong<PixelT>(a, img, esrc, e_y0, x, y);
+            else if constexpr (WIN) strong = exact_strong_w<PixelT>(a, img, x, y);
             else strong = exact_strong<PixelT>(a, img, x, y);
             if (strong) {
                 sbytes[(uint64_t)y * a.bpitch + x] = 1;
@@ -391,6 +445,11 @@ template <typename PixelT>
 __global__ __launch_bounds__(256) void k_exact(const ThresholdArgs a) { exact_tile<PixelT, 256, kExactListCap>(a); }
 template __global__ void k_exact<uint16_t>(const ThresholdArgs);
 template __global__ void k_exact<uint32_t>(const ThresholdArgs);
+// the same at the runtime window (a.kx, a.ky): windows other than 3,3 on the cross-check path (threshold_path 2)
+template <typename PixelT>
+__global__ __launch_bounds__(256) void k_exact_w(const ThresholdArgs a) { exact_tile<PixelT, 256, kExactListCap, 0, true>(a); }
+template __global__ void k_exact_w<uint16_t>(const ThresholdArgs);
+template __global__ void k_exact_w<uint32_t>(const ThresholdArgs);
 // Inclusive prefix sum over the 64 lanes in six DPP adds (row_shr 1/2/4/8 inside the rows of 16, then row_bcast:15 and
 // row_bcast:31 carry the row totals on) instead of six ds_bpermute round trips.
 __device__ __forceinline__ uint32_t wave_inclusive_scan(uint32_t v) {

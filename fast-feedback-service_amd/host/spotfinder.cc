@@ -62,6 +62,7 @@ struct Args {
     std::string algorithm = "dispersion", detector_json, gather = "host";
     std::string max_valid = "trusted";   // trusted | none | N
     uint32_t min_count = 2;
+    int kernel_half_x = 3, kernel_half_y = 3;   // --kernel-size
     bool cpu_decode = false, no_numa_pinning = false, single_buffer = false, all_threads = false, read_only = false, clean_exit = false;
 };
 
@@ -72,12 +73,14 @@ static void usage() {
       "                  [--min-spot-size-3d N] [--max-peak-centroid-separation N] [--start-index N]\n"
       "                  [-t S] [-fd FD] [-a ALGO] [--dmin MIN D] [--dmax MAX D] [-w \xce\xbb] [--detector JSON]\n"
       "                  [-h5] [--output-for-index] [--batch N] [--cpu-decode] [--strict-dtype]\n"
-      "                  [--max-valid trusted|none|N] [--min-count N]\n"
+      "                  [--max-valid trusted|none|N] [--min-count N] [--kernel-size N | NX,NY]\n"
       "                  [--devices D0,D1,... | --gpus N] [--no-numa-pinning] [--single-buffer] [--all-threads] [--read-only] [--clean-exit]\n"
       "--max-valid: a centre pixel above this value is never strong (the reference's kernels test it against the\n"
       "              data set's trusted maximum).  trusted (default) = the frame source's trusted-range maximum when it is\n"
       "              below the pixel type's maximum, none = no test (the CPU baseline's behaviour), N = this value\n"
-      "--min-count: valid pixels a 7x7 window needs (default 2, the CPU baseline's; the reference's kernels use 3)\n"
+      "--min-count: valid pixels a window needs (default 2, the CPU baseline's; the reference's kernels use 3)\n"
+      "--kernel-size: half-size of the dispersion window, both axes (N) or along x and y (NX,NY), each 1..7 (default 3:\n"
+      "              the 7x7 window; DIALS spotfinder.threshold.dispersion.kernel_size).  Not with -a dispersion_extended\n"
       "--validate:  every image is also decided by an independent path (every valid pixel's window gathered from memory,\n"
       "              no streaming kernel) and the two strong-pixel masks are compared: Match / Mismatch per image\n"
       "--devices / --gpus: one context and worker pool per GPU, all pulling frames from the one queue\n"
@@ -182,6 +185,20 @@ static Args parse_args(int argc, char** argv) {
             r.max_valid = need(i, s);
             if (r.max_valid != "trusted" && r.max_valid != "none") (void)u32(r.max_valid, s);
         }
+        else if (s == "--kernel-size") {
+            const std::string& v = need(i, s);
+            const size_t comma = v.find(',');
+            auto half = [&](const std::string& t) {
+                const uint32_t k = u32(t, s);
+                if (k < 1 || k > 7) arg_error("--kernel-size takes half-sizes 1..7: " + v);
+                return (int)k;
+            };
+            if (comma == std::string::npos) r.kernel_half_x = r.kernel_half_y = half(v);
+            else {
+                r.kernel_half_x = half(v.substr(0, comma));
+                r.kernel_half_y = half(v.substr(comma + 1));
+            }
+        }
         else if (s == "--min-count") { r.min_count = u32(need(i, s), s); if (r.min_count < 2) arg_error("--min-count must be at least 2"); }
         else if (s == "--no-numa-pinning") r.no_numa_pinning = true;
         else if (s == "--single-buffer") r.single_buffer = true;
@@ -196,6 +213,12 @@ static Args parse_args(int argc, char** argv) {
     if (r.sample && !r.file.empty()) arg_error("Argument 'FILE.nxs' not allowed with '--sample'");
     if (!r.sample && r.file.empty() && !implicit_sample) arg_error("One of the arguments '--sample' or 'FILE.nxs' is required");
     if (r.file.empty()) r.sample = true;
+    {
+        std::string lower = r.algorithm;
+        std::transform(lower.begin(), lower.end(), lower.begin(), [](unsigned char ch) { return (char)std::tolower(ch); });
+        if (lower == "dispersion_extended" && (r.kernel_half_x != 3 || r.kernel_half_y != 3))
+            arg_error("--kernel-size other than 3 is not available with the dispersion_extended algorithm");
+    }
     return r;
 }
 
@@ -591,6 +614,8 @@ int main(int argc, char** argv) {
     prm.algorithm = algorithm;
     prm.max_valid = max_valid;
     prm.min_count = (int32_t)args.min_count;
+    prm.kernel_half_x = args.kernel_half_x;
+    prm.kernel_half_y = args.kernel_half_y;
     if (args.validate) prm.want_strong_mask = 1;   // the masks are what --validate compares (spotfinder.cc:1012-1053)
     for (ffs_ctx* cx : ctxs) FFS_CHECK(cx, ffs_ctx_set_params(cx, &prm));
     if (max_valid >= 0) std::printf("Trusted range: centre pixels above %lld are not spots\n", (long long)max_valid);

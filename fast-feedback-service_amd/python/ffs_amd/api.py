@@ -28,7 +28,8 @@ class Params(C.Structure):
                 ("min_spot_size", C.c_uint32), ("min_spot_size_3d", C.c_uint32),
                 ("max_peak_centroid_separation", C.c_float),
                 ("want_reflections", C.c_int32), ("want_strong_list", C.c_int32),
-                ("want_strong_mask", C.c_int32), ("algorithm", C.c_int32), ("extended_flavour", C.c_int32)]
+                ("want_strong_mask", C.c_int32), ("algorithm", C.c_int32), ("extended_flavour", C.c_int32),
+                ("kernel_half_x", C.c_int32), ("kernel_half_y", C.c_int32)]   # window half-sizes, 1..7 (0 = 3)
 
 
 ALGO_DISPERSION, ALGO_DISPERSION_EXTENDED = 0, 1
@@ -405,7 +406,7 @@ class Stream:
         self.ctx._check(self._lib.ffs_stream_timings(self._h, t))
         return dict(zip(("h2d", "threshold", "ccl", "d2h", "total"), list(t)))
 
-    PATH_BITS = {"wave_logs": 1, "frame_chain": 2, "bands": 4, "runs": 8, "grid_kernels": 16, "extended": 32}
+    PATH_BITS = {"wave_logs": 1, "frame_chain": 2, "bands": 4, "runs": 8, "grid_kernels": 16, "extended": 32, "window": 64}
 
     def last_path(self):
         """ffs_stream_last_path: (set of the launches the last batch took, times ffs_wait ran it again)."""

@@ -8,7 +8,8 @@
  * (0 = FFS_OK, negative = error; ffs_last_error() gives the text).  No
  * exceptions cross this boundary and no torch / HIP types appear in it.
  *
- * Data flow of one batch:
+ * Data flow of one batch (a window other than 7x7 -- ffs_params.kernel_half_x / _y -- takes
+ * the general-window kernel of kernels_window.hpp instead of the streaming kernel below):
  *   frames (u16/u32: dense host rows, pitched device rows, or bitshuffle-LZ4 chunks decoded on the GPU)
  *     -> ONE streaming threshold kernel per batch: exact integer 7x7 window sums, a conservative group
  *        screen, and the oracle's float64 predicate (baseline/spotfinder/standalone.cc:113-174) decided
@@ -42,7 +43,7 @@ typedef struct ffs_stream ffs_stream;
 typedef struct ffs_stack3d ffs_stack3d;
 
 /* Algorithm parameters.  Defaults (ffs_default_params) are the oracle's,
- * baseline/spotfinder/standalone.cc:16-20: 7x7 window, min_count 2, nsig_b 6,
+ * baseline/spotfinder/standalone.cc:16-20: 7x7 window (kernel_half_x = kernel_half_y = 3), min_count 2, nsig_b 6,
  * nsig_s 3, threshold 0; the GPU reference's launch wrapper defaults
  * (spotfinder/spotfinder.cuh:18-20) differ only in min_count = 3. */
 typedef struct {
@@ -64,6 +65,12 @@ typedef struct {
     int32_t extended_flavour; /* extended only.  0 = baseline.cpp:730-761 rules (default); 1 = where the
                                  device kernels differ structurally: erosion skips masked neighbours
                                  (erosion.cu:101-105), second pass needs n > 0 (thresholding.cu:472) */
+    int32_t kernel_half_x;    /* window half-width along x (fast) and ... */
+    int32_t kernel_half_y;    /* ... along y (slow): the window is (2*kx+1) x (2*ky+1) pixels (kernel_size_{x,y},
+                                 standalone.cc:16,121-122; DIALS dispersion.kernel_size).  1..7 each; 0 means 3, so a
+                                 zero-initialised struct keeps the 7x7 window.  Needs 2 <= min_count <= (2kx+1)(2ky+1).
+                                 Anything but 3,3 runs the general-window kernel (FFS_PATH_WINDOW); refused together with
+                                 FFS_ALGO_DISPERSION_EXTENDED */
 } ffs_params;
 
 #define FFS_ALGO_DISPERSION 0
@@ -197,6 +204,9 @@ int ffs_ctx_set_params(ffs_ctx *ctx, const ffs_params *p);
  *   "direct_records"   (1) records written straight into pinned host memory (before the first stream is created)
  *   "chain_first" (2), "bright_cap" (2^20), "frames_per_group", "target_waves" (16384), "stream_bands" (0: from target_waves; > 0: that many bands, any number), "dense_mask" (0),
  *   "occupancy_bitmap" (1), "decode_in_dense_stream" (1), "rows_ahead" (3: rows of loads a streaming wave keeps in flight), "ccl_grid" (32),
+ *   "window_kernel"    (0) 0 = the general-window threshold kernel (any kernel_half_x / _y in 1..7, exact sums, the oracle's float64
+ *                          predicate) runs only for windows other than 3,3; 1 = it runs for every window, 3,3 included (the A/B and
+ *                          cross-check partner of the 7x7 streaming kernels: same results)
  *   "assembly_threads" (7: helper threads that build a batch's result arrays; 3, 12 and 15 measure the same): see DESIGN.md.
  *   "band_taper" (0), "ext_rest_aside" (0), "ext_fused" (0): round 4's A/B partners (tapered bands of the streaming kernels;
  *                          extended algorithm: erosion + final pass in the sparse stream / fused into one kernel) -- measured, no
@@ -289,6 +299,7 @@ int ffs_stream_timings(ffs_stream *s, float ms[5]);
 #define FFS_PATH_RUNS 8u           /* ... the one launch's forest over runs of strong pixels (dense frames) */
 #define FFS_PATH_GRID_KERNELS 16u  /* sparse stage: four grid-wide kernels */
 #define FFS_PATH_EXTENDED 32u      /* extended dispersion */
+#define FFS_PATH_WINDOW 64u        /* the general-window threshold kernel (a window other than 3,3, or tuning "window_kernel" = 1) */
 int ffs_stream_last_path(ffs_stream *s, uint32_t *path_bits, uint32_t *reruns);
 
 /* Centres of mass of the last batch's reflections as rows (frame_id, x, y, z) of float32 -- the
