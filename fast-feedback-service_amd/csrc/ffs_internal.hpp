@@ -2,9 +2,11 @@
 // include/ffs_hip.h, error plumbing, and the few functions one unit calls in another.  Host side only; the kernels
 // live in kernels_*.hpp, each included by exactly one unit:
 //   ffs_context.hip  contexts, masks (kernels_mask.hpp), tuning, streams
-//   ffs_submit.hip   launch geometry, the launches of a batch (threshold -> sparse stage), submit entry points,
-//                    compressed input (kernels_stream / threshold / extended / ccl / chain / decode)
-//   ffs_wait.hip     ffs_wait: overflow re-runs, result assembly, result accessors
+//   ffs_submit.hip   launch geometry, one batch (enqueue_batch: plan_batch decides its path once, a BatchPlan; then the resets, the
+//                    threshold stage and the sparse stage are launched from that plan), submit entry points, compressed input
+//                    (kernels_stream / threshold / extended / window / ccl / chain / band / decode)
+//   ffs_wait.hip     ffs_wait: overflow re-runs (rerun_batch: the same batch again with a Rerun override), result assembly,
+//                    result accessors
 //   ffs_stack3d.hip  rotation sweeps: the device-resident 3D stack and the exchange between GPUs (kernels_stack3d)
 //   ffs_bench.hip    measurement entry points (kernel timings, memory ceiling, native pipeline loop, sqrt self-test)
 // No exception leaves the library (guarded()).
@@ -228,9 +230,7 @@ struct ffs_stream {
     uint32_t max_comp = 0;    // components per frame the record buffers hold
     ffs_stream* big = nullptr;               // one-frame stream with room for frames that exceed cap / max_comp
     std::vector<OverflowFrame> ovf;          // such frames of the last batch, re-run on `big`
-    int force_path = -1;                     // >= 0: threshold path of the next enqueue (bright-list overflow -> 1)
     bool lists_valid = true;                 // the last batch left its strong-pixel lists on the device
-    bool plane_once = false;                 // the next enqueue takes the plane (a batch the logs could not serve is run again)
     bool log_off = false;                    // the wave logs could not serve a batch of this stream (dense frames, a log overflow): the plane from then on
     uint2* d_wlog = nullptr;                 // wave logs of the streaming kernel (allocated on first use, sized for the launch geometry)
     uint32_t* d_wlog_n = nullptr;
@@ -242,12 +242,10 @@ struct ffs_stream {
     uint32_t* d_band_seam = nullptr;
     uint32_t band_slots = 0;                 // (frame, band) pairs the three buffers hold
     uint32_t band_backoff = 0;               // batches this stream still sends through k_frame_chain after a band overflowed its plan (flag 128: dense data)
-    bool bands_once_off = false;             // the next enqueue takes k_frame_chain (the batch that raised flag 128 is run again)
     bool band_mode = false;                  // this batch's sparse stage is k_band_cc + k_frame_merge
     uint32_t path_bits = 0;                  // which launches the last batch took (ffs_stream_last_path)
     uint32_t reruns = 0;                     // times ffs_wait ran the last batch again (a plan that did not hold it)
-    bool force_grid = false;                 // the next enqueue takes the grid-wide sparse kernels (a frame's runs overflowed the one launch)
-    bool runs_overflowed = false;            // ... and dense batches of this stream keep taking them
+    bool runs_overflowed = false;            // a frame's runs overflowed the one launch: dense batches of this stream take the grid-wide sparse kernels
     uint32_t *d_pack_k = nullptr, *d_pack_i = nullptr;  // a batch's lists packed end to end for another device's 3D stack
     StackSlice *d_pack_tab = nullptr, *h_pack_tab = nullptr;
     hipEvent_t ev_pack = nullptr;            // the packed lists are ready on the source device
@@ -383,6 +381,17 @@ static int guarded(ffs_ctx* c, F&& body) {
     } while (0)
 
 // ---- small helpers ------------------------------------------------------------------------------------------
+// What ffs_wait asks of the enqueue that runs a batch AGAIN because a plan did not hold it (ffs_wait.hip, rerun_batch); the default
+// is a normal batch.  An argument of that one call: what a stream remembers beyond it (log_off, runs_overflowed, band_backoff) is
+// in ffs_stream.
+struct Rerun {
+    int threshold_path = -1;   // >= 0: the threshold path of this enqueue (bright-list overflow -> 1)
+    bool plane = false;        // takes the plane (a batch the wave logs could not serve)
+    bool no_bands = false;     // takes k_frame_chain (the batch that raised flag 128)
+    bool grid = false;         // takes the grid-wide sparse kernels (a frame's runs overflowed the one launch)
+};
+// extended algorithm: the strip erosion stores only the non-zero words of a signal-region plane that was cleared behind the previous batch
+static inline bool ext_sparse_erode(const Tuning& t) { return t.ext_erode != 0 && t.ext_e_sparse; }
 // window half-sizes of a parameter set (ffs_params.kernel_half_x / _y: 0 means 3)
 constexpr int kWinMaxHalf = 7;
 static inline int win_half(int v) { return v ? v : 3; }
@@ -434,16 +443,19 @@ int ensure_host_staging(ffs_stream* s, size_t bytes);   // pinned staging of at 
 size_t default_staging_bytes(const ffs_stream* s);      // max_batch raw frames (+ the slack incompressible chunks need)
 // ffs_submit.hip
 bool chain_prepare_device();   // asks for k_frame_chain's dynamic LDS on the current device; false: use the four kernels
-ThresholdArgs make_threshold_args(ffs_stream* s, const void* img, size_t pitch, size_t fstride, uint32_t n_frames);
+ThresholdArgs make_threshold_args(ffs_stream* s, const void* img, size_t pitch, size_t fstride, uint32_t n_frames, const Rerun& how);
 int check_layout(ffs_stream* s, size_t pitch, size_t fstride, uint32_t n_frames);
 int ensure_extended_buffers(ffs_stream* s);
-int enqueue_batch(ffs_stream* s, const void* d_img, size_t pitch, size_t fstride, uint32_t n, const ffs_params* snapshot = nullptr);
-// one launch of the threshold stage's dense kernel on s->st with HIP events on the dispatch itself (either may be null),
-// and of the kernel that follows it (k_bright_fix / k_exact; extended: erosion + final pass) -- what ffs_bench_threshold times
+int enqueue_batch(ffs_stream* s, const void* d_img, size_t pitch, size_t fstride, uint32_t n, const ffs_params* snapshot = nullptr,
+                  const Rerun& how = Rerun{});
 extern std::atomic<int> g_live_stacks;   // 3D stacks alive in the process (ffs_stack3d.hip)
-bool wave_logs_for(ffs_stream* s, ThresholdArgs& a, uint32_t n_frames);
-void bench_launch_dense(ffs_stream* s, const ThresholdArgs& a, uint32_t n_frames, hipEvent_t start, hipEvent_t stop);
-void bench_launch_rest(ffs_stream* s, const ThresholdArgs& a, uint32_t n_frames);
+bool wave_logs_for(ffs_stream* s, ThresholdArgs& a, uint32_t n_frames, const Rerun& how);
+// The threshold stage where all of it runs in s->st, in its two steps: the dense kernel, with HIP events on the dispatch itself (either
+// may be null), and the kernels that follow it (k_bright_fix / k_exact; extended: erosion + final pass; none behind the general-window
+// kernel or with wave logs).  What enqueue_batch launches for such a batch, and what ffs_bench_threshold times.
+void launch_dense_kernel(ffs_stream* s, const ThresholdArgs& a, uint32_t n_frames, hipEvent_t start, hipEvent_t stop,
+                         bool plane_clean = false, bool counts_clean = false);
+void launch_dense_rest(ffs_stream* s, const ThresholdArgs& a, uint32_t n_frames);
 bool window_kernel_for(const ffs_stream* s, const ThresholdArgs& a);   // this batch's threshold stage is the general-window kernel
 // ffs_wait.hip
 int ffs_wait_impl(ffs_stream* s, const ffs_frame_result** results, uint32_t* n_results);

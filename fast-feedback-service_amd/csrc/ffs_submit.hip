@@ -24,7 +24,7 @@ bool chain_prepare_device() {   // more than 64 KB of dynamic LDS has to be aske
     return e1 == hipSuccess && e2 == hipSuccess && e3 == hipSuccess && e4 == hipSuccess && e5 == hipSuccess;
 }
 
-ThresholdArgs make_threshold_args(ffs_stream* s, const void* img, size_t pitch, size_t fstride, uint32_t n_frames) {
+ThresholdArgs make_threshold_args(ffs_stream* s, const void* img, size_t pitch, size_t fstride, uint32_t n_frames, const Rerun& how) {
     const ffs_ctx* c = s->ctx;
     const Layout& L = c->L;
     const ffs_params& p = s->batch_params;
@@ -63,7 +63,7 @@ ThresholdArgs make_threshold_args(ffs_stream* s, const void* img, size_t pitch, 
     }
     // bright windows (sum p >= 65536; 32-bit pixels >= 2^24): onto the list k_bright_fix works off, or -- tuning
     // "threshold_path" = 1, and whenever that list overflowed (ffs_wait re-runs the batch) -- into the plane as candidates
-    a.bright_to_plane = s->force_path >= 0 ? s->force_path : c->tune.threshold_path;
+    a.bright_to_plane = how.threshold_path >= 0 ? how.threshold_path : c->tune.threshold_path;
     a.overflow = s->d_overflow;
     a.bright_n = s->d_tile_counts + tile_counts_bytes(s) / 4 - 1;
     a.bright_list = s->d_bright;
@@ -147,7 +147,7 @@ ThresholdArgs make_threshold_args(ffs_stream* s, const void* img, size_t pitch, 
     a.eplane = s->d_eplane;
     a.eplane_clean = s->ext_e_clean ? 1 : 0;
     a.ext_flavour = p.extended_flavour;
-    a.ext_variant = (c->pixel_bytes == 2 && s->force_path < 0) ? c->tune.ext_first_pass : 0;
+    a.ext_variant = (c->pixel_bytes == 2 && how.threshold_path < 0) ? c->tune.ext_first_pass : 0;
     a.ext_strips = (L.pitch_px + kExtOwnedPx - 1) / kExtOwnedPx;
     {   // one pixel per lane: bands of 64..256 rows keep the 6-row warm-up below 10 %
         const long long ext_target = 8192;
@@ -170,18 +170,21 @@ static size_t stream_log_slots(const ThresholdArgs& a, uint32_t n_frames) {
     return (size_t)n_groups * (size_t)a.n_bands * (size_t)a.n_strips;
 }
 
+// The instantiation of the streaming kernels a launch takes.  Rows of loads a wave keeps in flight: tuning "rows_ahead", within what
+// exists for the pixel size (16-bit: 2, 3 or 4; 32-bit: 2 or 3, so 4 means 3); the kernels that zero-fill the byte mask (dense_mask) and
+// the extended algorithm's first pass (16-bit pixels only) exist with two rows.
+using StreamKernel = void (*)(ThresholdArgs);
+static StreamKernel stream_kernel(const ffs_ctx* c, bool dense_mask, bool extended) {
+    const int rows = std::clamp(c->tune.rows_ahead, 2, c->pixel_bytes == 4 ? 3 : 4);
+    if (c->pixel_bytes == 4) return dense_mask ? k_stream_u32<2, true> : rows == 3 ? k_stream_u32<3, false> : k_stream_u32<2, false>;
+    if (extended) return dense_mask ? k_stream_u16<2, true, true> : k_stream_u16<2, true, false>;
+    if (dense_mask) return k_stream_u16<2, false, true>;
+    return rows == 4 ? k_stream_u16<4, false, false> : rows == 3 ? k_stream_u16<3, false, false> : k_stream_u16<2, false, false>;
+}
 // The whole standard threshold in one kernel: final strong plane + per-tile counts (atomics into zeroed counters).
 // Start and stop events ride on the dispatch itself (its completion signal): no marker packets around it.
 static void launch_stream(ffs_stream* s, const ThresholdArgs& a, uint32_t n_frames, hipEvent_t start, hipEvent_t stop, hipStream_t st = nullptr) {
-    const dim3 grid = stream_grid(a, n_frames);
-    if (!st) st = s->st;
-    if (s->ctx->pixel_bytes == 4 && a.dense_mask) hipExtLaunchKernelGGL((k_stream_u32<2, true>), grid, dim3(64), 0, st, start, stop, 0, a);
-    else if (s->ctx->pixel_bytes == 4 && s->ctx->tune.rows_ahead >= 3) hipExtLaunchKernelGGL((k_stream_u32<3, false>), grid, dim3(64), 0, st, start, stop, 0, a);
-    else if (s->ctx->pixel_bytes == 4) hipExtLaunchKernelGGL((k_stream_u32<2, false>), grid, dim3(64), 0, st, start, stop, 0, a);
-    else if (a.dense_mask) hipExtLaunchKernelGGL((k_stream_u16<2, false, true>), grid, dim3(64), 0, st, start, stop, 0, a);
-    else if (s->ctx->tune.rows_ahead == 3) hipExtLaunchKernelGGL((k_stream_u16<3, false, false>), grid, dim3(64), 0, st, start, stop, 0, a);
-    else if (s->ctx->tune.rows_ahead >= 4) hipExtLaunchKernelGGL((k_stream_u16<4, false, false>), grid, dim3(64), 0, st, start, stop, 0, a);
-    else hipExtLaunchKernelGGL((k_stream_u16<2, false, false>), grid, dim3(64), 0, st, start, stop, 0, a);
+    hipExtLaunchKernelGGL(stream_kernel(s->ctx, a.dense_mask != 0, false), stream_grid(a, n_frames), dim3(64), 0, st ? st : s->st, start, stop, 0, a);
 }
 // The general-window kernel (kernels_window.hpp): windows other than 3,3, or every window with tuning "window_kernel" = 1.  The
 // standard algorithm on the plane paths only (no wave logs: those belong to k_stream_u16); the cross-check path (threshold_path 2)
@@ -240,8 +243,7 @@ static void launch_ext_first(ffs_stream* s, const ThresholdArgs& a, uint32_t n_f
         // (both are usually clean already: the plane was cleared behind the previous batch's sparse launch, which also zeroed the counts)
         if (!plane_clean) (void)hipMemsetAsync(a.dplane, 0, (size_t)n_frames * a.plane_frame_stride, s->st);
         if (!counts_clean) (void)hipMemsetAsync(a.tile_counts, 0, tile_counts_bytes(s), s->st);
-        if (a.dense_mask) hipExtLaunchKernelGGL((k_stream_u16<2, true, true>), stream_grid(a, n_frames), dim3(64), 0, s->st, start, stop, 0, a);
-        else hipExtLaunchKernelGGL((k_stream_u16<2, true, false>), stream_grid(a, n_frames), dim3(64), 0, s->st, start, stop, 0, a);
+        hipExtLaunchKernelGGL(stream_kernel(s->ctx, a.dense_mask != 0, true), stream_grid(a, n_frames), dim3(64), 0, s->st, start, stop, 0, a);
         if (fix_here) hipLaunchKernelGGL((k_bright_fix<uint16_t, true>), dim3(32), dim3(256), 0, s->st, a);
         return;
     }
@@ -295,10 +297,10 @@ int ensure_extended_buffers(ffs_stream* s) {
 // Wave logs for this launch (tuning "strong_log"): the 16-bit standard path on a context with sparse streams, a geometry
 // kernels_chain.hpp's merge holds (at most twelve strips per frame).  Allocates the logs for the launch's waves on first use
 // and puts them into `a`; false: the plane.
-bool wave_logs_for(ffs_stream* s, ThresholdArgs& a, uint32_t n_frames) {
+bool wave_logs_for(ffs_stream* s, ThresholdArgs& a, uint32_t n_frames, const Rerun& how) {
     ffs_ctx* c = s->ctx;
     const Layout& L = c->L;
-    if (!(c->tune.strong_log != 0 && !a.bright_to_plane && !s->log_off && !s->plane_once && s->st2 != s->st && c->chain_ok
+    if (!(c->tune.strong_log != 0 && !a.bright_to_plane && !s->log_off && !how.plane && s->st2 != s->st && c->chain_ok
           && s->batch_params.algorithm != FFS_ALGO_DISPERSION_EXTENDED && c->n_tiles <= kChainMaxTiles && L.H <= kChainMaxRows
           && (uint32_t)a.gpf / (uint32_t)kSOwned + 2u <= 16u && a.band_rows <= 1024 && L.W <= 65535))
         return false;
@@ -309,7 +311,7 @@ bool wave_logs_for(ffs_stream* s, ThresholdArgs& a, uint32_t n_frames) {
         // idle here -- submit refuses a busy one, and a re-run inside ffs_wait comes after the batch's last event -- so nothing of
         // its own has to be waited for if it does happen: a tuning change between batches.)
         for (uint32_t nf = 1; nf <= s->max_batch; ++nf) {
-            const ThresholdArgs t = make_threshold_args(s, a.image, a.pitch, a.frame_stride, nf);
+            const ThresholdArgs t = make_threshold_args(s, a.image, a.pitch, a.frame_stride, nf, how);
             waves = std::max(waves, stream_log_slots(t, nf));
         }
         if (s->d_wlog) {
@@ -335,12 +337,14 @@ bool wave_logs_for(ffs_stream* s, ThresholdArgs& a, uint32_t n_frames) {
     return true;
 }
 
-void bench_launch_dense(ffs_stream* s, const ThresholdArgs& a, uint32_t n_frames, hipEvent_t start, hipEvent_t stop) {
-    if (s->batch_params.algorithm == FFS_ALGO_DISPERSION_EXTENDED) launch_ext_first(s, a, n_frames, start, stop);
+// The threshold stage where all of it runs in s->st (ffs_internal.hpp): the dense kernel ...
+void launch_dense_kernel(ffs_stream* s, const ThresholdArgs& a, uint32_t n_frames, hipEvent_t start, hipEvent_t stop, bool plane_clean, bool counts_clean) {
+    if (s->batch_params.algorithm == FFS_ALGO_DISPERSION_EXTENDED) launch_ext_first(s, a, n_frames, start, stop, true, plane_clean, counts_clean);
     else if (window_kernel_for(s, a)) launch_window(s, a, n_frames, start, stop);
     else launch_stream(s, a, n_frames, start, stop);
 }
-void bench_launch_rest(ffs_stream* s, const ThresholdArgs& a, uint32_t n_frames) {
+// ... and what follows it
+void launch_dense_rest(ffs_stream* s, const ThresholdArgs& a, uint32_t n_frames) {
     if (s->batch_params.algorithm == FFS_ALGO_DISPERSION_EXTENDED) launch_ext_rest(s, a, n_frames, s->st);
     else if (window_kernel_for(s, a)) return;   // (it decides every pixel itself)
     else if (a.bright_to_plane) launch_exact(s, a, n_frames, s->st);
@@ -375,19 +379,24 @@ __global__ void k_dummy_spin(uint32_t ticks, uint32_t* sink) {
 
 // The sparse stage in small workgroups (kernels_band.hpp, tuning "sparse_bands"): can this launch geometry take it, and are the
 // buffers between its two kernels there (allocated once, for the most bands any batch of this stream can have).
-static int band_split(const ThresholdArgs& a) { return (std::max(a.band_rows, a.band_rows2) + kBandSplitRows - 1) / kBandSplitRows; }
-static bool band_stage_for(ffs_stream* s, const ThresholdArgs& a, uint32_t n_frames) {
+struct BandSplit { int sub = 1, sub_rows = 0; };   // a band of the streaming launch as `sub` bands of the sparse stage, each of at most sub_rows rows
+static BandSplit band_split(const ThresholdArgs& a) {
+    const int rows = std::max(a.band_rows, a.band_rows2), sub = (rows + kBandSplitRows - 1) / kBandSplitRows;
+    return {sub, (rows + sub - 1) / sub};
+}
+static bool band_stage_for(ffs_stream* s, const ThresholdArgs& a, uint32_t n_frames, const Rerun& how) {
     ffs_ctx* c = s->ctx;
     const uint32_t strips = (uint32_t)a.gpf / (uint32_t)kSOwned + 2u;   // strips a frame's groups can touch
-    const int sub = band_split(a), sub_rows = (std::max(a.band_rows, a.band_rows2) + sub - 1) / sub;
+    const BandSplit split = band_split(a);
+    const int sub = split.sub, sub_rows = split.sub_rows;
     if (sub_rows > kBandMaxRows || (uint32_t)sub_rows * std::min(strips, 16u) > (uint32_t)kBandCw || a.n_bands * sub > kMergeMaxBands || c->L.W > 65535)
         return false;
     const uint32_t need = n_frames * (uint32_t)(a.n_bands * sub);
     if (need > s->band_slots) {
         uint32_t slots = need;
         for (uint32_t nf = 1; nf <= s->max_batch; ++nf) {   // (sized once: hipFree synchronises the device -- see wave_logs_for)
-            const ThresholdArgs t = make_threshold_args(s, a.image, a.pitch, a.frame_stride, nf);
-            slots = std::max(slots, nf * (uint32_t)(t.n_bands * band_split(t)));
+            const ThresholdArgs t = make_threshold_args(s, a.image, a.pitch, a.frame_stride, nf, how);
+            slots = std::max(slots, nf * (uint32_t)(t.n_bands * band_split(t).sub));
         }
         if (s->d_band_hdr) {
             (void)hipFree(s->d_band_hdr); (void)hipFree(s->d_band_acc); (void)hipFree(s->d_band_seam);
@@ -406,47 +415,148 @@ static bool band_stage_for(ffs_stream* s, const ThresholdArgs& a, uint32_t n_fra
 }
 
 // ---- one batch ------------------------------------------------------------------------------------------------------
-int enqueue_batch(ffs_stream* s, const void* d_img, size_t pitch, size_t fstride, uint32_t n, const ffs_params* snapshot) {
+// enqueue_batch() reads top to bottom: plan_batch() takes every decision of the batch, once, into a BatchPlan; reset_for_batch()
+// clears what earlier batches left behind; launch_threshold_stage() enqueues the dense kernels and makes the batch's sparse stream
+// wait for them; launch_sparse_stage() enqueues compaction -> connected components -> records behind that, and the batch's last
+// event.  The three steps that launch branch on the plan and decide nothing again.
+
+// (a step that failed has left its text in the context's error: its code is passed on)
+#define FFS_TRY(expr)                    \
+    do {                                 \
+        const int rc_ = (expr);          \
+        if (rc_ != FFS_OK) return rc_;   \
+    } while (0)
+
+struct BatchPlan {
+    uint32_t n = 0;                   // frames of the batch
+    bool wait_upload = false;         // the frames are in place behind ev[1] (upload / decode stream): waited for in the dense stream this batch's first kernel takes
+    bool counts_were_clean = false;   // the per-tile counts were zero before this batch's resets (the extended first pass then leaves out its own fill)
+    // The extended algorithm (first pass -> erosion -> final pass).  Every other batch is "streamed": the plane the sparse stage
+    // reads was produced by a streaming kernel into a zeroed plane (and is zeroed again by the compaction); path 0 also keeps the
+    // occupancy bitmap in step with it
+    bool ext = false;
+    bool ext_sparse_erode = false;    // ... whose signal-region plane is cleared behind the previous batch together with the first-pass plane (ext_sparse_erode())
+    bool window = false;              // the general-window kernel (kernels_window.hpp) decides every pixel itself: no bright-window list, no fix-up, no wave logs
+    bool list_path = false;           // a streaming kernel that hands its bright windows to k_bright_fix on a list (threshold path 0)
+    bool aside = false;               // the context has sparse streams: the dense stream holds streaming kernels only
+    bool will_chain = false;          // the whole sparse stage in one launch (k_frame_chain, or k_band_cc + k_frame_merge: `banded`); false: the four grid-wide kernels
+    bool runs_ok = false;             // ... and its run-based instantiation can take frames beyond the LDS forest of pixels
+    bool dense_batch = false;         // the stream's previous batch held a frame beyond that forest
+    bool use_log = false;             // the streaming kernel writes wave logs (ta_launch has them) and the one launch merges them: no plane, no counters, no bright list
+    bool runs_launch = false;         // the one launch is k_frame_chain's run-based instantiation
+    bool need_lists = false;          // somebody reads the strong-pixel lists of this batch
+    bool banded = false;              // the one launch is k_band_cc + k_frame_merge, `band` says how the streaming launch's bands are split for it
+    bool chain_first = false;         // the one launch does the bright-window fix-up and the next streaming kernel waits for its start
+    bool want_dense_bytes = false;    // the byte mask of this batch is produced
+    ThresholdArgs ta{};               // the threshold stage's arguments ...
+    ThresholdArgs ta_launch{};        // ... and with the wave logs, for the streaming kernel and the one launch that reads them (== ta without logs)
+    BandSplit band;
+    uint32_t path_bits = 0;           // FFS_PATH_*: what ffs_stream_last_path reports for this batch
+};
+
+// Reads the stream, its context and tuning, the batch's parameters (s->batch_params) and the previous batch's counts; `how`: what a
+// re-run overrides.  Changes nothing of the stream but what is allocated on first use (wave logs, the band stage's buffers).
+static BatchPlan plan_batch(ffs_stream* s, const void* d_img, size_t pitch, size_t fstride, uint32_t n, const Rerun& how) {
     ffs_ctx* c = s->ctx;
     const Layout& L = c->L;
-    s->batch_params = snapshot ? *snapshot : c->params;
     const ffs_params& p = s->batch_params;
-    s->cur_img = d_img;
-    s->cur_pitch = pitch;
-    s->cur_fstride = fstride;
-    const bool ext = p.algorithm == FFS_ALGO_DISPERSION_EXTENDED;
-
-    (void)hipGetLastError();  // drop any stale error state: the check below is for OUR launches
-    const bool wait_upload = s->st_up != s->st && !s->dev_input;   // the frames are in place behind ev[1] (upload / decode stream): waited for below,
-                                                                    // in the dense stream this batch's first kernel takes
-    bool ext_plane_clean = false;
-    if (ext) {
-        const int rc = ensure_extended_buffers(s);
-        if (rc != FFS_OK) return rc;
-        std::swap(s->d_dplane, s->d_dplane2);   // this batch's planes: the ones cleared behind the previous batch (d_dplane2 / d_eplane2 keep that batch's)
-        std::swap(s->d_eplane, s->d_eplane2);
-        ext_plane_clean = s->dplane2_clean;
-        s->ext_e_clean = s->dplane2_clean && s->eplane2_clean && c->tune.ext_erode != 0 && c->tune.ext_e_sparse;
-        s->dplane2_clean = false;
-        s->eplane2_clean = false;
-    } else {
-        s->ext_e_clean = false;
+    BatchPlan P;
+    P.n = n;
+    P.wait_upload = s->st_up != s->st && !s->dev_input;
+    P.counts_were_clean = !s->counts_dirty;
+    P.ext = p.algorithm == FFS_ALGO_DISPERSION_EXTENDED;
+    P.ext_sparse_erode = ext_sparse_erode(c->tune);
+    P.ta = make_threshold_args(s, d_img, pitch, fstride, n, how);
+    P.window = !P.ext && window_kernel_for(s, P.ta);
+    P.list_path = !P.ext && !P.ta.bright_to_plane && !P.window;
+    // (the byte mask: zero-filled by the streaming kernels only when asked for; the exact stages always produce it)
+    P.want_dense_bytes = P.window ? (p.want_strong_mask || c->tune.dense_mask)
+                                  : (P.list_path || (P.ext && ext_stream_first(P.ta))) ? P.ta.dense_mask != 0 : true;
+    // The whole sparse stage in one launch, one workgroup per frame (kernels_chain.hpp) ...
+    const bool can_chain = c->tune.sparse_stage >= 2 && L.H <= 65535 && c->chain_ok && s->direct_recs && s->h_counts_dev
+                           && c->n_tiles <= kChainMaxTiles && L.H <= kChainMaxRows;
+    // ... as long as the frames' strong pixels fit its LDS forest.  A frame beyond that runs the same stages on global arrays
+    // inside its one workgroup (2.8 ms for 32 frames of 61 k strong pixels, the extended algorithm on the bench frames),
+    // where the four grid-wide kernels spread the work over the machine: the path of this batch follows what the stream's
+    // previous batch held (data that is dense stays dense; a single dense frame costs one slow batch).
+    // Denser frames of 16-bit pixels stay in the one launch while their RUNS fit LDS (kernels_chain.hpp, the RUNS instantiation:
+    // 61 k strong pixels are 12 k runs on the bench frames of the extended algorithm); a frame with more runs than that raises
+    // flag 16, ffs_wait() runs the batch again through the grid-wide kernels and the stream stays with them for dense batches.
+    P.runs_ok = c->pixel_bytes == 2 && L.W <= kChainRunMaxW && c->tune.chain_runs != 0 && !s->runs_overflowed;
+    if (can_chain && c->tune.sparse_stage == 2 && s->n_frames > 0) {
+        uint32_t prev_max = 0;
+        for (uint32_t f = 0; f < s->n_frames; ++f) prev_max = std::max(prev_max, s->h_counts[f]);
+        P.dense_batch = prev_max > (uint32_t)kChainLdsEntries;
     }
-    const bool counts_were_clean = !s->counts_dirty;
-    const ThresholdArgs ta = make_threshold_args(s, d_img, pitch, fstride, n);
-    // "streamed": the plane the sparse stage reads was produced by a streaming kernel into a zeroed plane (and is zeroed
-    // again by the compaction); path 0 also keeps the occupancy bitmap in step with it
-    const bool streamed = !ext;
-    // the general-window kernel (kernels_window.hpp) decides every pixel itself: no bright-window list, no fix-up, no wave logs
-    const bool window = streamed && window_kernel_for(s, ta);
-    const bool list_path = streamed && !ta.bright_to_plane && !window;
-    bool dense_resets = false;   // fills went into the stream's own dense stream: this batch's kernel has to follow them there
-    if (wait_upload && ext) HIP_TRY(c, hipStreamWaitEvent(s->st, s->ev[1], 0));
-    if (streamed && s->bits_dirty) {  // (another algorithm or a failed batch left bits behind)
+    P.will_chain = can_chain && (!P.dense_batch || P.runs_ok) && !how.grid;
+    // Wave logs instead of the plane (tuning "strong_log"): the standard 16-bit path, sparse stage in the one launch, frames
+    // that fit its LDS forest.  The streaming kernel then leaves plane, counters, occupancy bitmap and bright list alone.
+    P.ta_launch = P.ta;
+    P.use_log = P.list_path && P.will_chain && !P.dense_batch && wave_logs_for(s, P.ta_launch, n, how);
+#ifdef FFS_EXPERIMENTS
+    if (c->tune.exp.chain_skip) P.will_chain = false;   // (use_log stays what it was with the one launch)
+#endif
+    // (the launch that merges wave logs and the run-based launch of dense frames can do without the lists)
+    P.runs_launch = P.will_chain && !P.use_log && P.runs_ok && (P.dense_batch || c->tune.chain_runs == 2);
+    P.aside = !P.ext && s->st2 != s->st;
+    const int depth = c->inflight.load() + (s->busy ? 0 : 1);
+    // The sparse stage in small workgroups (kernels_band.hpp): wave logs, nobody reads the pixel lists or the byte mask, a geometry
+    // its LDS plan holds, and the stream's recent batches did not overflow that plan.
+    P.need_lists = p.want_strong_list || c->tune.device_lists == 1 || (c->tune.device_lists == 2 && g_live_stacks.load() > 0);
+    // By pipeline depth (tuning "sparse_bands" = 1): its two launches each become ready behind a streaming kernel that is already
+    // being dispatched, so a batch's results are two steps away -- hidden with four batches in flight (101 k against 95.6 k frames/s),
+    // not with two or three (79 k / 89 k against 88 k / 95 k for the one-workgroup launch with its head start); alone in flight the
+    // band waves win again (58 k against 53 k: nothing to wait behind).  profiles/r05n_bands_by_pipeline_depth.log
+    // A context with four or more streams is a pipeline that FILLS through depths two and three (the start of a run, of a timed
+    // region): there the band launches win at every depth (+1.2 % on the driver-style line, profiles/r05zo_tune_ab.log).
+    const bool depth_ok = c->tune.sparse_bands >= 2 || depth >= 4 || depth <= 1 || c->n_streams_made >= 4;
+    P.banded = P.use_log && c->tune.sparse_bands != 0 && depth_ok && !P.need_lists && !P.ta.dense_mask && !how.no_bands && s->band_backoff == 0
+               && band_stage_for(s, P.ta_launch, n, how);
+    if (P.banded) P.band = band_split(P.ta_launch);
+    // chain_first: the one launch, one workgroup per frame, of a list-path batch on a context with sparse streams ...
+    // ... which then also does the bright-window fix-up, and whose workgroups (a whole CU each) should get their CUs
+    // BEFORE the next batch's streaming kernel floods the dispatcher: that kernel waits for this launch to have STARTED.
+    // (Without it a batch's sparse launch sits out the whole next streaming kernel: 0.35 ms more latency per batch.)
+    // Only while few batches are in flight: with a deep pipeline the latency is hidden anyway, the wait costs the dense
+    // stream ~15 us per batch and the fix-up inside the one-workgroup-per-frame launch ~25 us of its CUs (4 batches in
+    // flight: 0.369-0.377 against 0.353 ms per step; 2 in flight: 0.385 against 0.523).
+    // (band waves fit wherever a streaming wave has left: they need no head start)
+    P.chain_first = P.list_path && P.aside && P.will_chain && !P.banded && c->tune.chain_first > 0 && depth <= c->tune.chain_first;
+    P.path_bits = (P.use_log ? FFS_PATH_WAVE_LOGS : 0u) | (P.will_chain && !P.banded ? FFS_PATH_FRAME_CHAIN : 0u) | (P.banded ? FFS_PATH_BANDS : 0u)
+                  | (P.runs_launch ? FFS_PATH_RUNS : 0u) | (!P.will_chain ? FFS_PATH_GRID_KERNELS : 0u) | (P.ext ? FFS_PATH_EXTENDED : 0u)
+                  | (P.window ? FFS_PATH_WINDOW : 0u);
+    return P;
+}
+
+// Extended algorithm: this batch's planes are the ones cleared behind the previous batch (d_dplane2 / d_eplane2 keep that batch's).
+// plane_clean: the first-pass plane is zero already.
+static int take_extended_planes(ffs_stream* s, bool& plane_clean) {
+    plane_clean = false;
+    s->ext_e_clean = false;
+    if (s->batch_params.algorithm != FFS_ALGO_DISPERSION_EXTENDED) return FFS_OK;
+    FFS_TRY(ensure_extended_buffers(s));
+    std::swap(s->d_dplane, s->d_dplane2);
+    std::swap(s->d_eplane, s->d_eplane2);
+    plane_clean = s->dplane2_clean;
+    s->ext_e_clean = s->dplane2_clean && s->eplane2_clean && ext_sparse_erode(s->ctx->tune);
+    s->dplane2_clean = false;
+    s->eplane2_clean = false;
+    return FFS_OK;
+}
+
+// What an earlier batch left behind and this one needs zero, filled in the stream's own dense stream.  dense_resets: there were
+// such fills, and this batch's kernel has to follow them there.
+static int reset_for_batch(ffs_stream* s, const BatchPlan& plan, bool& dense_resets) {
+    ffs_ctx* c = s->ctx;
+    const Layout& L = c->L;
+    dense_resets = false;
+    // (the extended algorithm waits for its frames ahead of all its fills; every other path where its first kernel goes: launch_threshold_stage)
+    if (plan.wait_upload && plan.ext) HIP_TRY(c, hipStreamWaitEvent(s->st, s->ev[1], 0));
+    if (!plan.ext && s->bits_dirty) {  // (another algorithm or a failed batch left bits behind)
         HIP_TRY(c, hipMemsetAsync(s->d_bits, 0, (size_t)s->max_batch * L.plane_frame_stride, s->st));
         dense_resets = true;
     }
-    if (streamed && s->counts_dirty) {
+    if (!plan.ext && s->counts_dirty) {
         HIP_TRY(c, hipMemsetAsync(s->d_tile_counts, 0, tile_counts_bytes(s), s->st));
         dense_resets = true;
     }
@@ -457,165 +567,137 @@ int enqueue_batch(ffs_stream* s, const void* d_img, size_t pitch, size_t fstride
     }
     s->counts_dirty = true;
     s->bits_dirty = true;  // until every launch of this batch is enqueued (a failure in between leaves bits behind)
-    // The whole sparse stage in one launch, one workgroup per frame (kernels_chain.hpp) ...
-    bool will_chain = c->tune.sparse_stage >= 2 && L.H <= 65535 && c->chain_ok && s->direct_recs && s->h_counts_dev
-                      && c->n_tiles <= kChainMaxTiles && L.H <= kChainMaxRows;
-    // ... as long as the frames' strong pixels fit its LDS forest.  A frame beyond that runs the same stages on global arrays
-    // inside its one workgroup (2.8 ms for 32 frames of 61 k strong pixels, the extended algorithm on the bench frames),
-    // where the four grid-wide kernels spread the work over the machine: the path of this batch follows what the stream's
-    // previous batch held (data that is dense stays dense; a single dense frame costs one slow batch).
-    // Denser frames of 16-bit pixels stay in the one launch while their RUNS fit LDS (kernels_chain.hpp, the RUNS instantiation:
-    // 61 k strong pixels are 12 k runs on the bench frames of the extended algorithm); a frame with more runs than that raises
-    // flag 16, ffs_wait() runs the batch again through the grid-wide kernels and the stream stays with them for dense batches.
-    const bool runs_ok = c->pixel_bytes == 2 && L.W <= kChainRunMaxW && c->tune.chain_runs != 0 && !s->runs_overflowed;
-    bool dense_batch = false;
-    if (will_chain && c->tune.sparse_stage == 2 && s->n_frames > 0) {
-        uint32_t prev_max = 0;
-        for (uint32_t f = 0; f < s->n_frames; ++f) prev_max = std::max(prev_max, s->h_counts[f]);
-        dense_batch = prev_max > (uint32_t)kChainLdsEntries;
-        if (dense_batch && !runs_ok) will_chain = false;
+    return FFS_OK;
+}
+
+// ---- ... its threshold stage ----------------------------------------------------------------------------------------
+// What the arms of launch_threshold_stage share.  The frames are in place: waited for in the stream the batch's first kernel takes ...
+static int wait_for_upload(ffs_stream* s, const BatchPlan& plan, hipStream_t st) {
+    if (plan.wait_upload) HIP_TRY(s->ctx, hipStreamWaitEvent(st, s->ev[1], 0));
+    return FFS_OK;
+}
+// ... and the stage's output is: ev[2], recorded behind the stage's kernels in s->st unless it rode on a dispatch, and waited for by
+// the batch's sparse stream
+static int sparse_stream_follows(ffs_stream* s, bool ev2_on_dispatch) {
+    if (!ev2_on_dispatch) HIP_TRY(s->ctx, hipEventRecord(s->ev[2], s->st));
+    if (s->st2 != s->st) HIP_TRY(s->ctx, hipStreamWaitEvent(s->st2, s->ev[2], 0));
+    return FFS_OK;
+}
+
+// Wave-log path with a deep pipeline: the context's two dense HIP streams take the streaming kernels alternately (ffs_internal.hpp,
+// "dense_overlap"): this launch waits for the value the PREVIOUS launch's last workgroup wrote as it started, not for that
+// kernel's end, and writes its own.  Everything that must precede the kernel (the upload's event) goes into the same stream.
+// launched = false: not on this device (the caller launches as without the tuning).
+static int launch_stream_overlapped(ffs_stream* s, const BatchPlan& plan, hipEvent_t ev_start, bool& launched) {
+    ffs_ctx* c = s->ctx;
+    launched = false;
+    std::lock_guard<std::mutex> dense_lock(c->dense_mu);   // (several threads submit to one context: a launch's number, stream and wait are one step)
+    if (!c->dense_st2) {   // the partner stream and the hand-over word: made on first use (nothing of this exists in a context that never asks)
+        int lo = 0, hi = 0, can = 0;
+        bool ok = hipDeviceGetAttribute(&can, hipDeviceAttributeCanUseStreamWaitValue, c->device) == hipSuccess && can
+                  && hipExtMallocWithFlags(reinterpret_cast<void**>(&c->d_handoff), 8, hipMallocSignalMemory) == hipSuccess;
+        ok = ok && hipMemsetAsync(c->d_handoff, 0, 8, c->up_st) == hipSuccess && hipStreamSynchronize(c->up_st) == hipSuccess;
+        ok = ok && hipDeviceGetStreamPriorityRange(&lo, &hi) == hipSuccess
+             && hipStreamCreateWithPriority(&c->dense_st2, hipStreamNonBlocking, (lo + hi) / 2) == hipSuccess;
+        if (!ok) {
+            (void)hipGetLastError();
+            if (c->d_handoff) (void)hipFree(c->d_handoff);
+            c->d_handoff = nullptr;
+            c->dense_st2 = nullptr;
+            c->tune.dense_overlap = 0;   // (not on this device)
+            return FFS_OK;
+        }
     }
-    if (s->force_grid) will_chain = false;
-    // Wave logs instead of the plane (tuning "strong_log"): the standard 16-bit path, sparse stage in the one launch, frames
-    // that fit its LDS forest.  The streaming kernel then leaves plane, counters, occupancy bitmap and bright list alone.
-    ThresholdArgs ta_launch = ta;
-    const bool use_log = list_path && will_chain && !dense_batch && wave_logs_for(s, ta_launch, n);
-#ifdef FFS_EXPERIMENTS
-    if (c->tune.exp.chain_skip) will_chain = false;
-#endif
-    // ... which then also does the bright-window fix-up, and whose workgroups (a whole CU each) should get their CUs
-    // BEFORE the next batch's streaming kernel floods the dispatcher: that kernel waits for this launch to have STARTED.
-    // (Without it a batch's sparse launch sits out the whole next streaming kernel: 0.35 ms more latency per batch.)
-    // Only while few batches are in flight: with a deep pipeline the latency is hidden anyway, the wait costs the dense
-    // stream ~15 us per batch and the fix-up inside the one-workgroup-per-frame launch ~25 us of its CUs (4 batches in
-    // flight: 0.369-0.377 against 0.353 ms per step; 2 in flight: 0.385 against 0.523).
-    const bool aside = streamed && s->st2 != s->st;   // the context has sparse streams: the dense stream holds streaming kernels only
-    const int depth = c->inflight.load() + (s->busy ? 0 : 1);
-    // The sparse stage in small workgroups (kernels_band.hpp): wave logs, nobody reads the pixel lists or the byte mask, a geometry
-    // its LDS plan holds, and the stream's recent batches did not overflow that plan.
-    const bool need_lists = p.want_strong_list || c->tune.device_lists == 1 || (c->tune.device_lists == 2 && g_live_stacks.load() > 0);
-    // By pipeline depth (tuning "sparse_bands" = 1): its two launches each become ready behind a streaming kernel that is already
-    // being dispatched, so a batch's results are two steps away -- hidden with four batches in flight (101 k against 95.6 k frames/s),
-    // not with two or three (79 k / 89 k against 88 k / 95 k for the one-workgroup launch with its head start); alone in flight the
-    // band waves win again (58 k against 53 k: nothing to wait behind).  profiles/r05n_bands_by_pipeline_depth.log
-    // A context with four or more streams is a pipeline that FILLS through depths two and three (the start of a run, of a timed
-    // region): there the band launches win at every depth (+1.2 % on the driver-style line, profiles/r05zo_tune_ab.log).
-    const bool depth_ok = c->tune.sparse_bands >= 2 || depth >= 4 || depth <= 1 || c->n_streams_made >= 4;
-    const bool banded = use_log && c->tune.sparse_bands != 0 && depth_ok && !need_lists && !ta.dense_mask && !s->bands_once_off && s->band_backoff == 0
-                        && band_stage_for(s, ta_launch, n);
-    if (use_log && s->band_backoff > 0 && !s->bands_once_off) --s->band_backoff;
-    s->band_mode = banded;
-    // (band waves fit wherever a streaming wave has left: they need no head start)
-    const bool chain_first = list_path && aside && will_chain && !banded && c->tune.chain_first > 0 && depth <= c->tune.chain_first;
-    if (chain_first) {
+    const uint32_t seq = ++c->handoff_seq;
+    const int which = (int)(seq & 1u);
+    hipStream_t dst = which ? c->dense_st2 : c->dense_st;
+    FFS_TRY(wait_for_upload(s, plan, dst));
+    if (c->handoff_last >= 0 && c->handoff_last != which)
+        HIP_TRY(c, hipStreamWaitValue32(dst, c->d_handoff, seq - 1, hipStreamWaitValueGte, 0xFFFFFFFFu));
+    ThresholdArgs a = plan.ta_launch;
+    a.handoff = c->d_handoff;
+    a.handoff_seq = seq;
+    launch_stream(s, a, plan.n, ev_start, s->ev[2], dst);
+    c->handoff_last = which;
+    launched = true;
+    return FFS_OK;
+}
+
+static int launch_threshold_stage(ffs_stream* s, const BatchPlan& plan, bool dense_resets, bool ext_plane_clean) {
+    ffs_ctx* c = s->ctx;
+    const Layout& L = c->L;
+    const ThresholdArgs& ta = plan.ta;
+    const uint32_t n = plan.n;
+    if (plan.chain_first) {
         std::lock_guard<std::mutex> lock(c->stream_mu);   // (the newest start event cannot be re-recorded between the two lines)
         const int slot = c->chain_ev_newest.load();
         if (slot >= 0) HIP_TRY(c, hipStreamWaitEvent(s->st, c->chain_ev[slot], 0));
     }
     hipEvent_t ev_start = nullptr;
     if (s->ev1_pending) { ev_start = s->ev[1]; s->ev1_pending = false; }
-    if (ext && s->st2 != s->st && c->tune.ext_rest_aside) {
+    if (plan.ext && s->st2 != s->st && c->tune.ext_rest_aside) {
         // The dense stream carries the first pass alone; erosion and the final pass -- a latency-bound gather over the signal
         // region that keeps the vector units half busy -- go to the batch's sparse stream, ahead of its sparse launch, and run
         // BESIDE the next batch's first pass (an issue-bound stream of the whole frame) instead of between two of them.
-        if (ext_stream_first(ta)) {   // (the first pass's stop event rides on its dispatch; the bright-window fix-up goes aside too)
-            launch_ext_first(s, ta, n, ev_start, s->ev[2], false, ext_plane_clean, counts_were_clean);
-            HIP_TRY(c, hipStreamWaitEvent(s->st2, s->ev[2], 0));
-            hipLaunchKernelGGL((k_bright_fix<uint16_t, true>), dim3(32), dim3(256), 0, s->st2, ta);
-        } else {
-            launch_ext_first(s, ta, n, ev_start, nullptr);
-            HIP_TRY(c, hipEventRecord(s->ev[2], s->st));
-            HIP_TRY(c, hipStreamWaitEvent(s->st2, s->ev[2], 0));
-        }
+        const bool streams = ext_stream_first(ta);   // (the first pass's stop event rides on its dispatch; the bright-window fix-up goes aside too)
+        launch_ext_first(s, ta, n, ev_start, streams ? s->ev[2] : nullptr, false, ext_plane_clean, plan.counts_were_clean);
+        FFS_TRY(sparse_stream_follows(s, streams));
+        if (streams) hipLaunchKernelGGL((k_bright_fix<uint16_t, true>), dim3(32), dim3(256), 0, s->st2, ta);
         launch_ext_rest(s, ta, n, s->st2);
-    } else if (ext) {
-        launch_ext_first(s, ta, n, ev_start, nullptr, true, ext_plane_clean, counts_were_clean);
-        launch_ext_rest(s, ta, n, s->st);
-        HIP_TRY(c, hipEventRecord(s->ev[2], s->st));
-        if (s->st2 != s->st) HIP_TRY(c, hipStreamWaitEvent(s->st2, s->ev[2], 0));
-    } else if (window) {
+    } else if (plan.window) {
         // The plane, the per-tile counts, the byte mask when it is asked for and the occupancy bitmap when the one-launch sparse stage
         // reads it: what that stage reads after k_exact
         ThresholdArgs tw = ta;
-        tw.dense_mask = (p.want_strong_mask || c->tune.dense_mask) ? 1 : 0;
-        tw.occ = (c->tune.occupancy_bitmap && will_chain) ? s->d_occ : nullptr;
-        if (wait_upload) HIP_TRY(c, hipStreamWaitEvent(s->st, s->ev[1], 0));
+        tw.dense_mask = plan.want_dense_bytes ? 1 : 0;
+        tw.occ = (c->tune.occupancy_bitmap && plan.will_chain) ? s->d_occ : nullptr;
+        FFS_TRY(wait_for_upload(s, plan, s->st));
         launch_window(s, tw, n, ev_start, s->ev[2]);
-        if (s->st2 != s->st) HIP_TRY(c, hipStreamWaitEvent(s->st2, s->ev[2], 0));
-    } else if (list_path && aside) {
+        FFS_TRY(sparse_stream_follows(s, true));
+    } else if (plan.list_path && plan.aside) {
         // the bright-window fix-up goes to the sparse stream (or into the sparse launch itself: chain_first; with wave logs the
         // sparse launch decides those pixels as it reads the logs)
-        // Wave-log path with a deep pipeline: the context's two dense HIP streams take the streaming kernels alternately (ffs_internal.hpp,
-        // "dense_overlap"): this launch waits for the value the PREVIOUS launch's last workgroup wrote as it started, not for that
-        // kernel's end, and writes its own.  Everything that must precede the kernel (the upload's event) goes into the same stream.
-        bool overlap = use_log && !chain_first && !dense_resets && c->tune.dense_overlap != 0 && s->st == c->dense_st;
-        std::unique_lock<std::mutex> dense_lock(c->dense_mu, std::defer_lock);   // (several threads submit to one context: a launch's number, stream and wait are one step)
-        if (overlap) {
-            dense_lock.lock();
-            if (!c->dense_st2) {   // the partner stream and the hand-over word: made on first use (nothing of this exists in a context that never asks)
-                int lo = 0, hi = 0, can = 0;
-                bool ok = hipDeviceGetAttribute(&can, hipDeviceAttributeCanUseStreamWaitValue, c->device) == hipSuccess && can
-                          && hipExtMallocWithFlags(reinterpret_cast<void**>(&c->d_handoff), 8, hipMallocSignalMemory) == hipSuccess;
-                ok = ok && hipMemsetAsync(c->d_handoff, 0, 8, c->up_st) == hipSuccess && hipStreamSynchronize(c->up_st) == hipSuccess;
-                ok = ok && hipDeviceGetStreamPriorityRange(&lo, &hi) == hipSuccess
-                     && hipStreamCreateWithPriority(&c->dense_st2, hipStreamNonBlocking, (lo + hi) / 2) == hipSuccess;
-                if (!ok) {
-                    (void)hipGetLastError();
-                    if (c->d_handoff) (void)hipFree(c->d_handoff);
-                    c->d_handoff = nullptr;
-                    c->dense_st2 = nullptr;
-                    c->tune.dense_overlap = 0;   // (not on this device)
-                    overlap = false;
-                    dense_lock.unlock();
-                }
-            }
+        bool launched = false;
+        if (plan.use_log && !plan.chain_first && !dense_resets && c->tune.dense_overlap != 0 && s->st == c->dense_st)
+            FFS_TRY(launch_stream_overlapped(s, plan, ev_start, launched));
+        if (!launched) {
+            FFS_TRY(wait_for_upload(s, plan, s->st));
+            launch_stream(s, plan.ta_launch, n, ev_start, s->ev[2]);
         }
-        if (overlap) {
-            const uint32_t seq = ++c->handoff_seq;
-            const int which = (int)(seq & 1u);
-            hipStream_t dst = which ? c->dense_st2 : c->dense_st;
-            if (wait_upload) HIP_TRY(c, hipStreamWaitEvent(dst, s->ev[1], 0));
-            if (c->handoff_last >= 0 && c->handoff_last != which)
-                HIP_TRY(c, hipStreamWaitValue32(dst, c->d_handoff, seq - 1, hipStreamWaitValueGte, 0xFFFFFFFFu));
-            ta_launch.handoff = c->d_handoff;
-            ta_launch.handoff_seq = seq;
-            launch_stream(s, ta_launch, n, ev_start, s->ev[2], dst);
-            c->handoff_last = which;
-        } else {
-            if (wait_upload) HIP_TRY(c, hipStreamWaitEvent(s->st, s->ev[1], 0));
-            launch_stream(s, ta_launch, n, ev_start, s->ev[2]);
-        }
-        HIP_TRY(c, hipStreamWaitEvent(s->st2, s->ev[2], 0));
-        if (!chain_first && !use_log) launch_bright_fix(s, ta, s->st2);
-    } else if (ta.bright_to_plane == 2) {
+        FFS_TRY(sparse_stream_follows(s, true));
+        if (!plan.chain_first && !plan.use_log) launch_bright_fix(s, ta, s->st2);
+    } else if (!plan.ext && ta.bright_to_plane == 2) {
         // the cross-check path of `spotfinder --validate` (tuning "threshold_path" = 2): no streaming kernel, no screen, no LDS
         // queue -- the plane starts as the valid-pixel mask, so k_exact gathers the window of EVERY valid pixel from memory and
         // applies the oracle's predicate to 64-bit sums (exact_strong).  Shares nothing with the hot path but that predicate.
-        if (wait_upload) HIP_TRY(c, hipStreamWaitEvent(s->st, s->ev[1], 0));
+        FFS_TRY(wait_for_upload(s, plan, s->st));
         if (ev_start) HIP_TRY(c, hipEventRecord(ev_start, s->st));
         HIP_TRY(c, hipMemsetAsync(s->d_sbytes, 0, (size_t)n * L.bytes_frame_stride, s->st));
         for (uint32_t f = 0; f < n; ++f)
             HIP_TRY(c, hipMemcpyAsync(s->d_bits + (size_t)f * L.plane_frame_stride, c->d_maskbits, L.plane_frame_stride, hipMemcpyDeviceToDevice, s->st));
         launch_exact(s, ta, n, s->st);
-        HIP_TRY(c, hipEventRecord(s->ev[2], s->st));
-        if (s->st2 != s->st) HIP_TRY(c, hipStreamWaitEvent(s->st2, s->ev[2], 0));
+        FFS_TRY(sparse_stream_follows(s, false));
     } else {
-        if (wait_upload) HIP_TRY(c, hipStreamWaitEvent(s->st, s->ev[1], 0));
-        launch_stream(s, ta, n, ev_start, nullptr);
-        if (list_path) launch_bright_fix(s, ta, s->st);
-        else launch_exact(s, ta, n, s->st);
-        HIP_TRY(c, hipEventRecord(s->ev[2], s->st));
-        if (s->st2 != s->st) HIP_TRY(c, hipStreamWaitEvent(s->st2, s->ev[2], 0));
+        // the whole stage in the dense stream: the streaming kernel + k_bright_fix (path 0 on a context without sparse streams) or
+        // + k_exact (path 1); the extended algorithm's first pass + erosion + final pass
+        if (!plan.ext) FFS_TRY(wait_for_upload(s, plan, s->st));   // (extended: waited for already, reset_for_batch)
+        launch_dense_kernel(s, ta, n, ev_start, nullptr, ext_plane_clean, plan.counts_were_clean);
+        launch_dense_rest(s, ta, n);
+        FFS_TRY(sparse_stream_follows(s, false));
     }
     HIP_TRY(c, hipGetLastError());
+    return FFS_OK;
+}
 
+// ---- ... and its sparse stage ---------------------------------------------------------------------------------------
+static CclArgs make_ccl_args(const ffs_stream* s, const BatchPlan& plan) {
+    const ffs_ctx* c = s->ctx;
+    const Layout& L = c->L;
     CclArgs ca{};
-    ca.image = d_img;
-    ca.frame_stride = fstride;
-    ca.pitch = (uint32_t)pitch;
+    ca.image = plan.ta.image;
+    ca.frame_stride = plan.ta.frame_stride;
+    ca.pitch = plan.ta.pitch;
     ca.bits = s->d_bits;
-    ca.clear_bits = streamed ? 1 : 0;
-    s->bits_cleared = ca.clear_bits != 0;
+    ca.clear_bits = plan.ext ? 0 : 1;
     ca.tile_counts = s->d_tile_counts;
     ca.num_strong = s->d_num_strong;
     ca.row_off = s->d_row_off;
@@ -638,21 +720,18 @@ int enqueue_batch(ffs_stream* s, const void* d_img, size_t pitch, size_t fstride
     ca.bytes_frame_stride = L.bytes_frame_stride;
     ca.acc2 = s->d_acc2;
     ca.summary = s->d_summary;
-    // (the byte mask: zero-filled by the streaming kernels only when asked for; the exact stages always produce it)
-    ca.dense_bytes = ((list_path || (ext && ext_stream_first(ta))) ? ta.dense_mask : 1) ? 1 : 0;
-    if (window) ca.dense_bytes = (p.want_strong_mask || c->tune.dense_mask) ? 1 : 0;   // (as launched above)
-    ca.need_lists = need_lists ? 1 : 0;
-    // (the launch that merges wave logs and the run-based launch of dense frames can do without the lists)
-    const bool runs_launch = will_chain && !use_log && c->pixel_bytes == 2 && runs_ok && (dense_batch || c->tune.chain_runs == 2);
-    s->lists_valid = !(use_log || runs_launch) || ca.need_lists != 0;
-    s->dense_valid = ca.dense_bytes != 0;
+    ca.dense_bytes = plan.want_dense_bytes ? 1 : 0;
+    ca.need_lists = plan.need_lists ? 1 : 0;
     ca.occ = s->d_occ;
     ca.occ_frame_words = occ_frame_words(L);
     ca.occ_spr = L.mpitch / 16;
     // only the streaming kernels and their fix-up keep the bitmap (path 1: a superset of the final plane, which is fine)
-    ca.use_occ = (c->tune.occupancy_bitmap && ta.bright_to_plane != 2) ? 1 : 0;   // (kept by the streaming kernels, their fix-up and the extended algorithm's final pass)
-    s->occ_dirty = !(ca.use_occ && will_chain);      // nobody consumes (and clears) the bits this batch sets
-
+    ca.use_occ = (c->tune.occupancy_bitmap && plan.ta.bright_to_plane != 2) ? 1 : 0;   // (kept by the streaming kernels, their fix-up and the extended algorithm's final pass)
+    return ca;
+}
+static SegArgs make_seg_args(const ffs_stream* s, const BatchPlan& plan) {
+    const ffs_ctx* c = s->ctx;
+    const Layout& L = c->L;
     SegArgs sa{};
     sa.list_k = s->d_list_k;
     sa.list_i = s->d_list_i;
@@ -666,83 +745,98 @@ int enqueue_batch(ffs_stream* s, const void* d_img, size_t pitch, size_t fstride
     sa.H = (uint32_t)L.H;
     sa.row_off = s->d_row_off;
     sa.n_slices = 1;
-    sa.min_spot_size = p.min_spot_size;
-    sa.max_sep = p.max_peak_centroid_separation;
+    sa.min_spot_size = s->batch_params.min_spot_size;
+    sa.max_sep = s->batch_params.max_peak_centroid_separation;
     sa.summary = s->d_summary;
     sa.acc2 = s->d_acc2;
     sa.zero_counts = s->d_tile_counts;
     sa.zero_per_seg = (uint32_t)c->n_tiles;
     sa.zero_word = s->d_tile_counts + tile_counts_bytes(s) / 4 - 1;
+    return sa;
+}
 
-    s->chain_mode = will_chain;
-    s->path_bits = (use_log ? FFS_PATH_WAVE_LOGS : 0u) | (will_chain && !banded ? FFS_PATH_FRAME_CHAIN : 0u) | (banded ? FFS_PATH_BANDS : 0u)
-                   | (runs_launch ? FFS_PATH_RUNS : 0u) | (!will_chain ? FFS_PATH_GRID_KERNELS : 0u) | (ext ? FFS_PATH_EXTENDED : 0u)
-                   | (window ? FFS_PATH_WINDOW : 0u);
-    if (s->chain_mode) {
-        ChainArgs A{};
-        A.c = ca;
-        A.s = sa;
-        A.s.recs = s->h_recs_dev;
-        A.h_counts = s->h_counts_dev;
-        A.max_batch = (uint32_t)s->max_batch;
-        A.rec_stride = s->max_comp;
+// every launch of the batch is enqueued: what it leaves of plane and counts, and the batch is in flight
+static int finish_enqueue(ffs_stream* s, uint32_t n, bool bits_dirty, bool counts_dirty) {
+    s->bits_dirty = bits_dirty;
+    s->counts_dirty = counts_dirty;
+    mark_busy(s);
+    s->n_frames = n;
+    return FFS_OK;
+}
+
+using ChainKernel = void (*)(ChainArgs);
+static ChainKernel frame_chain_kernel(const BatchPlan& plan, int pixel_bytes) {
+    if (plan.use_log) return pixel_bytes == 2 ? k_frame_chain<uint16_t, false, true> : k_frame_chain<uint32_t, false, true>;
+    if (plan.runs_launch) return k_frame_chain<uint16_t, true>;   // (runs_ok: 16-bit pixels)
+    return pixel_bytes == 2 ? k_frame_chain<uint16_t> : k_frame_chain<uint32_t>;
+}
+
+// The one launch (plan.will_chain): k_frame_chain, a workgroup per frame, or -- banded -- k_band_cc + k_frame_merge.  Counters and
+// records go straight to the host: one event behind it.
+static int launch_one_launch_stage(ffs_stream* s, const BatchPlan& plan, const CclArgs& ca, const SegArgs& sa) {
+    ffs_ctx* c = s->ctx;
+    const uint32_t n = plan.n;
+    ChainArgs A{};
+    A.c = ca;
+    A.s = sa;
+    A.s.recs = s->h_recs_dev;
+    A.h_counts = s->h_counts_dev;
+    A.max_batch = (uint32_t)s->max_batch;
+    A.rec_stride = s->max_comp;
 #ifdef FFS_EXPERIMENTS
-        A.stop_after = c->tune.exp.chain_stop;
-        if (std::getenv("FFS_EXP_CHAIN_TS")) {
-            if (!s->h_phase_ts && hipHostMalloc(reinterpret_cast<void**>(&s->h_phase_ts), (size_t)s->max_batch * 64, hipHostMallocDefault) == hipSuccess) {
-                std::memset(s->h_phase_ts, 0, (size_t)s->max_batch * 64);
-                (void)hipHostGetDevicePointer(reinterpret_cast<void**>(&s->h_phase_ts_dev), s->h_phase_ts, 0);
-            }
-            A.phase_ts = s->h_phase_ts_dev;
+    A.stop_after = c->tune.exp.chain_stop;
+    if (std::getenv("FFS_EXP_CHAIN_TS")) {
+        if (!s->h_phase_ts && hipHostMalloc(reinterpret_cast<void**>(&s->h_phase_ts), (size_t)s->max_batch * 64, hipHostMallocDefault) == hipSuccess) {
+            std::memset(s->h_phase_ts, 0, (size_t)s->max_batch * 64);
+            (void)hipHostGetDevicePointer(reinterpret_cast<void**>(&s->h_phase_ts_dev), s->h_phase_ts, 0);
         }
-#endif
-        A.t = ta_launch;
-        A.fix_bright = (chain_first && !use_log) ? 1 : 0;
-        A.fix_done = s->d_tile_counts + tile_counts_bytes(s) / 4 - 2;
-        A.runs_ok = runs_ok ? (c->tune.chain_runs == 2 ? 2 : 1) : 0;
-        {
-            // the launch's start event belongs to the context (ffs_internal.hpp); published under the lock the waiting side takes
-            std::lock_guard<std::mutex> lock(c->stream_mu);
-            const int slot = (int)(c->chain_ev_next.fetch_add(1) % ffs_ctx::kChainEvents);
-            if (banded) {
-                BandArgs BA{};
-                BA.A = A;
-                BA.hdr = s->d_band_hdr;
-                BA.acc = reinterpret_cast<ChainAcc*>(s->d_band_acc);
-                BA.seam = s->d_band_seam;
-                BA.sub = band_split(ta_launch);
-                BA.sub_rows = (std::max(ta_launch.band_rows, ta_launch.band_rows2) + BA.sub - 1) / BA.sub;
-                const dim3 gb((unsigned)(ta_launch.n_bands * BA.sub), n);
-                if (c->pixel_bytes == 2) hipExtLaunchKernelGGL(k_band_cc<uint16_t>, gb, dim3(64), 0, s->st2, c->chain_ev[slot], nullptr, 0, BA);
-                else hipExtLaunchKernelGGL(k_band_cc<uint32_t>, gb, dim3(64), 0, s->st2, c->chain_ev[slot], nullptr, 0, BA);
-                hipLaunchKernelGGL(k_frame_merge, dim3(n), dim3(kMergeThreads), 0, s->st2, BA);
-            }
-            else if (use_log && c->pixel_bytes == 2) hipExtLaunchKernelGGL((k_frame_chain<uint16_t, false, true>), dim3(n), dim3(kChainThreads), kChainDynBytes, s->st2, c->chain_ev[slot], nullptr, 0, A);
-            else if (use_log) hipExtLaunchKernelGGL((k_frame_chain<uint32_t, false, true>), dim3(n), dim3(kChainThreads), kChainDynBytes, s->st2, c->chain_ev[slot], nullptr, 0, A);
-            else if (c->pixel_bytes == 2 && runs_ok && (dense_batch || c->tune.chain_runs == 2)) hipExtLaunchKernelGGL((k_frame_chain<uint16_t, true>), dim3(n), dim3(kChainThreads), kChainDynBytes, s->st2, c->chain_ev[slot], nullptr, 0, A);
-            else if (c->pixel_bytes == 2) hipExtLaunchKernelGGL(k_frame_chain<uint16_t>, dim3(n), dim3(kChainThreads), kChainDynBytes, s->st2, c->chain_ev[slot], nullptr, 0, A);
-            else hipExtLaunchKernelGGL(k_frame_chain<uint32_t>, dim3(n), dim3(kChainThreads), kChainDynBytes, s->st2, c->chain_ev[slot], nullptr, 0, A);
-            if (aside) c->chain_ev_newest.store(slot);
-        }
-        HIP_TRY(c, hipGetLastError());
-        if (ext && ext_stream_first(ta) && s->st2 != s->st) {
-            // the plane the previous batch used (nobody reads it any more) is cleared here, beside the dense kernels, for the next batch
-            // (with the strip erosion the signal-region plane behind it too: one fill, the two are one allocation)
-            HIP_TRY(c, hipMemsetAsync(s->d_dplane2, 0, (size_t)s->max_batch * L.plane_frame_stride * (c->tune.ext_erode != 0 && c->tune.ext_e_sparse ? 2u : 1u), s->st2));
-            s->dplane2_clean = true;
-            s->eplane2_clean = c->tune.ext_erode != 0 && c->tune.ext_e_sparse;
-        }
-        HIP_TRY(c, hipEventRecord(s->ev[4], s->st2));
-        s->ev3_is_ev4 = true;
-        s->spec_recs_copied = (uint64_t)s->max_batch * s->max_comp;
-        s->bits_dirty = !streamed;
-        s->counts_dirty = false;
-        mark_busy(s);
-        s->n_frames = n;
-        return FFS_OK;
+        A.phase_ts = s->h_phase_ts_dev;
     }
-    // the same stages as four grid-wide kernels (frames taller than k_frame_chain's LDS plan, records not written to the
-    // host directly, tuning "sparse_stage" = 1)
+#endif
+    A.t = plan.ta_launch;
+    A.fix_bright = (plan.chain_first && !plan.use_log) ? 1 : 0;
+    A.fix_done = s->d_tile_counts + tile_counts_bytes(s) / 4 - 2;
+    A.runs_ok = plan.runs_ok ? (c->tune.chain_runs == 2 ? 2 : 1) : 0;
+    {
+        // the launch's start event belongs to the context (ffs_internal.hpp); published under the lock the waiting side takes
+        std::lock_guard<std::mutex> lock(c->stream_mu);
+        const int slot = (int)(c->chain_ev_next.fetch_add(1) % ffs_ctx::kChainEvents);
+        if (plan.banded) {
+            BandArgs BA{};
+            BA.A = A;
+            BA.hdr = s->d_band_hdr;
+            BA.acc = reinterpret_cast<ChainAcc*>(s->d_band_acc);
+            BA.seam = s->d_band_seam;
+            BA.sub = plan.band.sub;
+            BA.sub_rows = plan.band.sub_rows;
+            const dim3 gb((unsigned)(plan.ta_launch.n_bands * BA.sub), n);
+            if (c->pixel_bytes == 2) hipExtLaunchKernelGGL(k_band_cc<uint16_t>, gb, dim3(64), 0, s->st2, c->chain_ev[slot], nullptr, 0, BA);
+            else hipExtLaunchKernelGGL(k_band_cc<uint32_t>, gb, dim3(64), 0, s->st2, c->chain_ev[slot], nullptr, 0, BA);
+            hipLaunchKernelGGL(k_frame_merge, dim3(n), dim3(kMergeThreads), 0, s->st2, BA);
+        } else {
+            hipExtLaunchKernelGGL(frame_chain_kernel(plan, c->pixel_bytes), dim3(n), dim3(kChainThreads), kChainDynBytes, s->st2, c->chain_ev[slot], nullptr, 0, A);
+        }
+        if (plan.aside) c->chain_ev_newest.store(slot);
+    }
+    HIP_TRY(c, hipGetLastError());
+    if (plan.ext && ext_stream_first(plan.ta) && s->st2 != s->st) {
+        // the plane the previous batch used (nobody reads it any more) is cleared here, beside the dense kernels, for the next batch
+        // (with the strip erosion the signal-region plane behind it too: one fill, the two are one allocation)
+        HIP_TRY(c, hipMemsetAsync(s->d_dplane2, 0, (size_t)s->max_batch * c->L.plane_frame_stride * (plan.ext_sparse_erode ? 2u : 1u), s->st2));
+        s->dplane2_clean = true;
+        s->eplane2_clean = plan.ext_sparse_erode;
+    }
+    HIP_TRY(c, hipEventRecord(s->ev[4], s->st2));
+    s->ev3_is_ev4 = true;
+    s->spec_recs_copied = (uint64_t)s->max_batch * s->max_comp;
+    return finish_enqueue(s, n, plan.ext, false);
+}
+
+// the same stages as four grid-wide kernels (frames taller than k_frame_chain's LDS plan, records not written to the
+// host directly, tuning "sparse_stage" = 1)
+static int launch_grid_stage(ffs_stream* s, const BatchPlan& plan, const CclArgs& ca, SegArgs sa) {
+    ffs_ctx* c = s->ctx;
+    const uint32_t n = plan.n;
     bool skip_sparse = false;
 #ifdef FFS_EXPERIMENTS
     if (c->tune.exp.chain_skip) {
@@ -777,11 +871,41 @@ int enqueue_batch(ffs_stream* s, const void* d_img, size_t pitch, size_t fstride
         HIP_TRY(c, hipMemcpyAsync(s->h_recs, s->d_recs, s->spec_recs_copied * sizeof(WireRec2), hipMemcpyDeviceToHost, s->st2));
     }
     HIP_TRY(c, hipEventRecord(s->ev[4], s->st2));
-    s->bits_dirty = !streamed || skip_sparse;  // the compaction of a streamed batch leaves the plane all zero again
-    s->counts_dirty = skip_sparse;  // k_union cleared the counts of the frames of this batch (all the streaming kernel touched)
-    mark_busy(s);
-    s->n_frames = n;
-    return FFS_OK;
+    // the compaction of a streamed batch leaves the plane all zero again; k_union cleared the counts of the frames of this batch (all
+    // the streaming kernel touched)
+    return finish_enqueue(s, n, plan.ext || skip_sparse, skip_sparse);
+}
+
+static int launch_sparse_stage(ffs_stream* s, const BatchPlan& plan) {
+    const CclArgs ca = make_ccl_args(s, plan);
+    const SegArgs sa = make_seg_args(s, plan);
+    // what the batch leaves on the device, for ffs_wait and the accessors
+    s->bits_cleared = ca.clear_bits != 0;
+    s->lists_valid = !(plan.use_log || plan.runs_launch) || plan.need_lists;
+    s->dense_valid = plan.want_dense_bytes;
+    s->occ_dirty = !(ca.use_occ && plan.will_chain);      // nobody consumes (and clears) the bits this batch sets
+    s->chain_mode = plan.will_chain;
+    s->path_bits = plan.path_bits;
+    return plan.will_chain ? launch_one_launch_stage(s, plan, ca, sa) : launch_grid_stage(s, plan, ca, sa);
+}
+
+int enqueue_batch(ffs_stream* s, const void* d_img, size_t pitch, size_t fstride, uint32_t n, const ffs_params* snapshot, const Rerun& how) {
+    s->batch_params = snapshot ? *snapshot : s->ctx->params;
+    s->cur_img = d_img;
+    s->cur_pitch = pitch;
+    s->cur_fstride = fstride;
+    (void)hipGetLastError();  // drop any stale error state: the checks below are for OUR launches
+    bool ext_plane_clean = false;
+    FFS_TRY(take_extended_planes(s, ext_plane_clean));
+    const BatchPlan plan = plan_batch(s, d_img, pitch, fstride, n, how);
+    // (the one thing planning changes in what the stream remembers: a batch that could take bands brings the stream one step back to
+    // them after a band overflowed their plan -- ffs_wait.hip sets the 32)
+    if (plan.use_log && s->band_backoff > 0 && !how.no_bands) --s->band_backoff;
+    s->band_mode = plan.banded;
+    bool dense_resets = false;
+    FFS_TRY(reset_for_batch(s, plan, dense_resets));
+    FFS_TRY(launch_threshold_stage(s, plan, dense_resets, ext_plane_clean));
+    return launch_sparse_stage(s, plan);
 }
 
 extern "C" int ffs_submit_device(ffs_stream* s, const void* device_pixels, size_t pitch, size_t fstride,

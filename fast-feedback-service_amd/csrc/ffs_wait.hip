@@ -286,6 +286,15 @@ void ahead_stop(ffs_ctx* c, bool destroy) {
     }
 }
 
+// A plan did not hold the batch (an overflow flag of its kernels): the same frames and parameters again, enqueued with what `how`
+// overrides, and waited for in the caller's place.
+static int rerun_batch(ffs_stream* s, const Rerun& how, const ffs_frame_result** results, uint32_t* n_results) {
+    const int rc = enqueue_batch(s, s->cur_img, s->cur_pitch, s->cur_fstride, s->n_frames, &s->batch_params, how);
+    if (rc != FFS_OK) return rc;
+    ++s->reruns;
+    return ffs_wait_impl(s, results, n_results);
+}
+
 int ffs_wait_impl(ffs_stream* s, const ffs_frame_result** results, uint32_t* n_results) {
     if (!s) return FFS_ERR_INVALID;
     ffs_ctx* c = s->ctx;
@@ -359,24 +368,14 @@ int ffs_wait_impl(ffs_stream* s, const ffs_frame_result** results, uint32_t* n_r
             // more bright-window pixels than the list k_stream_u16 hands to k_bright_fix holds (a batch of
             // saturated frames): run the batch again with those pixels marked in the plane as candidates for the exact kernel
             // (threshold path 1; the extended algorithm: its plain first pass), which has no such list
-            s->force_path = 1;
-            int rc = enqueue_batch(s, s->cur_img, s->cur_pitch, s->cur_fstride, s->n_frames, &s->batch_params);
-            s->force_path = -1;
-            if (rc != FFS_OK) return rc;
-            ++s->reruns;
-            return ffs_wait_impl(s, results, n_results);
+            return rerun_batch(s, Rerun{.threshold_path = 1}, results, n_results);
         }
         if ((overflow & 128u) && !(overflow & 32u)) {
             // a band of a frame beyond the plan of the small-workgroup sparse stage (kernels_band.hpp: strong pixels, log entries,
             // components or seam pixels of ONE band): the batch again through the one-workgroup launch, and so the stream's next batches
             // (data that is dense stays dense)
-            s->bands_once_off = true;
             s->band_backoff = 32;
-            int rc = enqueue_batch(s, s->cur_img, s->cur_pitch, s->cur_fstride, s->n_frames, &s->batch_params);
-            s->bands_once_off = false;
-            if (rc != FFS_OK) return rc;
-            ++s->reruns;
-            return ffs_wait_impl(s, results, n_results);
+            return rerun_batch(s, Rerun{.no_bands = true}, results, n_results);
         }
         if (overflow & (32u | 64u)) {
             // the wave logs could not serve a frame of the batch: the batch again through the plane.  A wave with more strong groups
@@ -384,23 +383,13 @@ int ffs_wait_impl(ffs_stream* s, const ffs_frame_result** results, uint32_t* n_r
             // forest (64): only this batch -- the next one follows what this one held (dense data takes the plane by itself,
             // and the logs are back when the data is sparse again)
             if (overflow & 32u) s->log_off = true;
-            s->plane_once = true;
-            int rc = enqueue_batch(s, s->cur_img, s->cur_pitch, s->cur_fstride, s->n_frames, &s->batch_params);
-            s->plane_once = false;
-            if (rc != FFS_OK) return rc;
-            ++s->reruns;
-            return ffs_wait_impl(s, results, n_results);
+            return rerun_batch(s, Rerun{.plane = true}, results, n_results);
         }
         if (overflow & 16u) {
             // a dense frame with more runs than the one-launch sparse stage holds in LDS (kernels_chain.hpp): the batch again, its
             // sparse stage as the four grid-wide kernels; the stream's later dense batches go there directly
             s->runs_overflowed = true;
-            s->force_grid = true;
-            int rc = enqueue_batch(s, s->cur_img, s->cur_pitch, s->cur_fstride, s->n_frames, &s->batch_params);
-            s->force_grid = false;
-            if (rc != FFS_OK) return rc;
-            ++s->reruns;
-            return ffs_wait_impl(s, results, n_results);
+            return rerun_batch(s, Rerun{.grid = true}, results, n_results);
         }
         // A frame with more strong pixels than the stream's lists hold (flag 1) or more components than its
         // record buffers (flag 2) -- an ice ring, the direct beam.  The reference has no such limit (std::map of
