@@ -1174,7 +1174,7 @@ static int ffs_submit_compressed_impl(ffs_stream* s, const void* const* chunks, 
     // helper thread, so that the caller gets its thread back while the index is built; ffs_wait joins it.
     s->first_id = first_frame_id;
     s->reruns = 0;
-    s->n_frames = n_frames;
+    // (s->n_frames stays the PREVIOUS batch's until enqueue_batch has planned this one: plan_batch reads that batch's counts with it)
     mark_busy(s);
     s->job_rc = FFS_OK;
     s->job_err.clear();

@@ -278,6 +278,7 @@ class Stream:
         h = C.c_void_p()
         ctx._check(self._lib.ffs_stream_create(ctx._h, C.byref(h)))
         self._h = h
+        self._batch_wants = (False, False)
 
     def host_buffer(self) -> np.ndarray:
         """The stream's pinned staging area as a (max_batch, H, W) array."""
@@ -308,6 +309,7 @@ class Stream:
         """chunks: bitshuffle-LZ4 chunks (bytes / uint8 arrays, 12-byte header included), one per frame."""
         self._keep, ptrs, sizes = self._chunk_args(chunks)
         self.ctx._check(self._lib.ffs_submit_compressed(self._h, ptrs, sizes, len(self._keep), first_frame_id))
+        self._snapshot()
 
     def process_compressed(self, chunks, first_frame_id: int = 0):
         self.submit_compressed(chunks, first_frame_id)
@@ -329,11 +331,18 @@ class Stream:
         assert f.shape[1:] == (self.ctx.H, self.ctx.W), f.shape
         self._keep = f
         self.ctx._check(self._lib.ffs_submit(self._h, f.ctypes.data_as(C.c_void_p), f.shape[0], first_frame_id))
+        self._snapshot()
 
     def submit_device(self, dev_ptr: int, pitch_bytes: int, frame_stride_bytes: int, n_frames: int,
                       first_frame_id: int = 0):
         self.ctx._check(self._lib.ffs_submit_device(self._h, C.c_void_p(dev_ptr), pitch_bytes,
                                                     frame_stride_bytes, n_frames, first_frame_id))
+        self._snapshot()
+
+    def _snapshot(self):
+        """The library takes the batch's parameters at submit: so does wait() for the outputs it hands back (the context's
+        parameters may have changed for another stream's batch by then)."""
+        self._batch_wants = (bool(self.ctx.params.want_reflections), bool(self.ctx.params.want_strong_list))
 
     def wait(self, copy: bool = True) -> list[FrameResult]:
         """copy=False: the box / reflection arrays are views of the library's buffers, valid until the
@@ -354,8 +363,7 @@ class Stream:
             return a.copy() if copy else a
         boxes, refls = arr(bp, nb.value, BOX_DT), arr(rp, nr.value, REFL_DT)
         self.last_batch_boxes, self.last_batch_reflections = boxes, refls   # whole-batch arrays
-        want_refl = bool(self.ctx.params.want_reflections)
-        want_list = bool(self.ctx.params.want_strong_list)
+        want_refl, want_list = self._batch_wants
         out = []
         W, H = self.ctx.W, self.ctx.H
         b0 = r0 = 0

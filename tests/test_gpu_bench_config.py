@@ -17,7 +17,7 @@ import pytest
 import torch  # noqa: F401  (before libffs_hip.so is loaded: torch brings its own copy of the HIP runtime, and two runtimes in one
 #                            process cannot both have the GPU -- bench.py imports torch first for the same reason)
 
-from util import assert_frame_matches_oracle, oracle_frame
+from util import _resident, assert_frame_matches_oracle, oracle_frame
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -25,16 +25,6 @@ sys.path.insert(0, ROOT)
 pytestmark = pytest.mark.gpu
 
 CASES = [("eiger16m", "dispersion"), ("eiger16m", "dispersion_extended"), ("jungfrau9m", "dispersion")]
-
-
-def _resident(ctx, frames):
-    """The frames in the library's pitched device layout, as bench.py keeps them (torch: device memory only)."""
-    import torch
-    pitch, fstride = ctx.device_layout()
-    B, H, W = frames.shape
-    host = np.zeros((B, H, pitch // frames.dtype.itemsize), frames.dtype)
-    host[:, :, :W] = frames
-    return torch.from_numpy(host.view(np.uint8).reshape(-1)).to("cuda:0"), pitch, fstride
 
 
 def _pipeline(streams, ptr, pitch, fstride, B, steps, check):

@@ -3,7 +3,7 @@ chunked path of the exact kernel), capacity overflow errors, extreme shapes."""
 import numpy as np
 import pytest
 
-from util import assert_frame_matches_oracle, make_frame
+from util import _blob_frame, assert_frame_matches_oracle, make_frame
 
 pytestmark = pytest.mark.gpu
 
@@ -324,19 +324,6 @@ def test_random_shapes_and_densities(ffs, dtype):
         for fr, img in zip(res, frames):
             assert_frame_matches_oracle(fr, img, mask, min_spot_size=mss, max_sep=sep)
         st.close()
-
-
-def _blob_frame(W, H, seed, n_blobs, rmin=3, rmax=7):
-    """Fat spots on a quiet background: many strong pixels in few runs (what the extended algorithm's final mask looks like)."""
-    rng = np.random.default_rng(seed)
-    img = rng.poisson(1.0, (H, W)).astype(np.uint16)
-    yy, xx = np.mgrid[0:H, 0:W]
-    for _ in range(n_blobs):
-        cy, cx, r = rng.integers(0, H), rng.integers(0, W), rng.integers(rmin, rmax + 1)
-        y0, y1, x0, x1 = max(cy - r, 0), min(cy + r + 1, H), max(cx - r, 0), min(cx + r + 1, W)
-        sel = (yy[y0:y1, x0:x1] - cy) ** 2 + (xx[y0:y1, x0:x1] - cx) ** 2 <= r * r
-        img[y0:y1, x0:x1][sel] = rng.integers(200, 4000, sel.sum()).astype(np.uint16)
-    return img
 
 
 @pytest.mark.parametrize("want_list", [1, 0])

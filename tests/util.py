@@ -65,3 +65,26 @@ def assert_frame_matches_oracle(fr, img, mask, min_spot_size=3, max_sep=2.0, str
         assert fr.n_filtered_size == refl.n_filtered_size
         assert fr.n_filtered_sep == refl.n_filtered_sep
     return strong, cc, refl
+
+
+def _blob_frame(W, H, seed, n_blobs, rmin=3, rmax=7):
+    """Fat spots on a quiet background: many strong pixels in few runs (what the extended algorithm's final mask looks like)."""
+    rng = np.random.default_rng(seed)
+    img = rng.poisson(1.0, (H, W)).astype(np.uint16)
+    yy, xx = np.mgrid[0:H, 0:W]
+    for _ in range(n_blobs):
+        cy, cx, r = rng.integers(0, H), rng.integers(0, W), rng.integers(rmin, rmax + 1)
+        y0, y1, x0, x1 = max(cy - r, 0), min(cy + r + 1, H), max(cx - r, 0), min(cx + r + 1, W)
+        sel = (yy[y0:y1, x0:x1] - cy) ** 2 + (xx[y0:y1, x0:x1] - cx) ** 2 <= r * r
+        img[y0:y1, x0:x1][sel] = rng.integers(200, 4000, sel.sum()).astype(np.uint16)
+    return img
+
+
+def _resident(ctx, frames):
+    """The frames in the library's pitched device layout, as bench.py keeps them (torch: device memory only)."""
+    import torch
+    pitch, fstride = ctx.device_layout()
+    B, H, W = frames.shape
+    host = np.zeros((B, H, pitch // frames.dtype.itemsize), frames.dtype)
+    host[:, :, :W] = frames
+    return torch.from_numpy(host.view(np.uint8).reshape(-1)).to("cuda:0"), pitch, fstride

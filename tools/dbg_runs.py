@@ -5,11 +5,7 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "fast-feedback-service_amd", "python")); sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
 import ffs_amd
-from util import oracle_frame, make_frame
-src = open(os.path.join(ROOT, "tests", "test_gpu_edge_paths.py")).read()
-ns = {}
-exec("import numpy as np\n" + src[src.index("def _blob_frame"):src.index("@pytest.mark.parametrize(\"chain_runs\"")], ns)
-_blob_frame = ns["_blob_frame"]
+from util import _blob_frame, oracle_frame, make_frame
 W, H = 1000, 700
 a = _blob_frame(W, H, 1, 500)
 b = _blob_frame(W, H, 2, 420)
