@@ -613,9 +613,8 @@ int stream_create_sized(ffs_ctx* c, uint32_t max_batch, uint32_t cap, uint32_t m
         const size_t o_img = carve(B * L.frame_stride), o_bits = carve(B * L.plane_frame_stride), o_sbytes = carve(B * L.bytes_frame_stride);
         const size_t o_counts = carve(tile_counts_bytes(s)), o_occ = carve(B * (size_t)occ_frame_words(L) * 4);
         const size_t o_bright = carve((size_t)kBrightCap * sizeof(uint2));
-        // per-frame counters in the layout of h_counts, so that one copy brings them all back:
-        // [B] strong pixels | [B] components | [B][8] summary | [1] overflow / error flag
-        const size_t o_ns = carve((B * 10 + 1) * 4), o_row = carve(B * (size_t)(L.H + 1) * 4);
+        // the counter block (ffs_device.h: counts_*_at), laid out as h_counts is so that one copy brings it back
+        const size_t o_ns = carve(counts_device_words(B) * 4), o_row = carve(B * (size_t)(L.H + 1) * 4);
         const size_t o_k = carve(B * (size_t)s->cap * 4), o_i = carve(B * (size_t)s->cap * 4), o_par = carve(B * (size_t)s->cap * 4);
         const size_t o_acc = carve(B * (size_t)s->cap * sizeof(CompAcc2)), o_roots = carve(B * (size_t)(s->cap / 512 + 1) * 4);
         const size_t o_recs = carve(B * (size_t)s->max_comp * sizeof(WireRec2));
@@ -628,9 +627,9 @@ int stream_create_sized(ffs_ctx* c, uint32_t max_batch, uint32_t cap, uint32_t m
         s->d_occ = reinterpret_cast<uint32_t*>(base + o_occ);
         s->d_bright = reinterpret_cast<uint2*>(base + o_bright);
         s->d_num_strong = reinterpret_cast<uint32_t*>(base + o_ns);
-        s->d_n_comp = s->d_num_strong + B;
-        s->d_summary = s->d_num_strong + 2 * B;
-        s->d_overflow = s->d_num_strong + 10 * B;
+        s->d_n_comp = s->d_num_strong + counts_comp_at(B);
+        s->d_summary = s->d_num_strong + counts_summary_at(B);
+        s->d_overflow = s->d_num_strong + counts_status_at(B);
         s->d_row_off = reinterpret_cast<uint32_t*>(base + o_row);
         s->d_list_k = reinterpret_cast<uint32_t*>(base + o_k);
         s->d_list_i = reinterpret_cast<uint32_t*>(base + o_i);
@@ -645,8 +644,8 @@ int stream_create_sized(ffs_ctx* c, uint32_t max_batch, uint32_t cap, uint32_t m
 #endif
     }
     // (the pinned staging area for frames / chunks is allocated on first use: ensure_host_staging)
-    STREAM_TRY(hipHostMalloc(reinterpret_cast<void**>(&s->h_counts), (B * 11 + 1) * 4, hipHostMallocDefault));  // (+ [B] per-frame flags, k_frame_chain)
-    std::memset(s->h_counts, 0, (B * 11 + 1) * 4);
+    STREAM_TRY(hipHostMalloc(reinterpret_cast<void**>(&s->h_counts), counts_host_words(B) * 4, hipHostMallocDefault));
+    std::memset(s->h_counts, 0, counts_host_words(B) * 4);
     STREAM_TRY(hipHostMalloc(reinterpret_cast<void**>(&s->h_recs), B * (size_t)s->max_comp * sizeof(WireRec2),
                              hipHostMallocDefault));
     // The sparse kernels write the (few MB of) records and the counters straight into these pinned, device-visible

@@ -102,7 +102,7 @@ struct ThresholdArgs {
     uint32_t* bright_n;        // [1] pixels handed to k_bright_fix (window sum >= 65536)
     uint2* bright_list;        // [bright_cap] (frame << 16 | x, y)
     uint32_t bright_cap;
-    uint32_t* overflow;        // status word: 8 = the bright-window list overflowed
+    uint32_t* overflow;        // status word: kOvfBrightList when the bright-window list overflowed
     // occupancy of the strong plane, one bit per 16-byte segment (128 pixels) of a plane row: set by whoever sets a plane
     // bit in a one-kernel batch, read and cleared by k_frame_chain, which then loads only the segments that hold something
     uint32_t* occ;             // [n][occ_frame_words]
@@ -147,6 +147,35 @@ __host__ __device__ inline uint32_t log_slot(const ThresholdArgs& a, uint32_t y,
     return (y * (uint32_t)a.n_bands + band) * (uint32_t)a.n_strips + strip;
 }
 
+// ---- what a batch tells the host when a plan did not hold it: the overflow flags -----------------------------------------
+// Bits of a batch's status word (the block's status word, or a frame's flag word when the sparse stage was one launch per frame).
+// ffs_wait.hip (decide_recovery) has their precedence; DESIGN.md section 3.4d has the table.
+constexpr uint32_t kOvfStrongCap = 1u;    // a frame holds more strong pixels than `cap` (compaction, one-launch stages' tail): that frame again on a one-frame stream
+constexpr uint32_t kOvfCompCap = 2u;      // a frame holds more components than `max_comp` (k_finalize_roots, one-launch stages' tail): that frame again on a one-frame stream
+constexpr uint32_t kOvfCorruptLz4 = 4u;   // an LZ4 block did not decode to its block size (kernels_decode.hpp): the wait fails, FFS_ERR_INVALID
+constexpr uint32_t kOvfBrightList = 8u;   // the bright-window list overflowed (k_bright_fix, k_frame_chain phase B): the batch again, threshold path 1
+constexpr uint32_t kOvfRuns = 16u;        // a frame's runs are beyond the one launch's LDS (k_frame_chain<RUNS>): the batch again through the grid-wide kernels, and so the stream's later dense batches
+constexpr uint32_t kOvfWaveLog = 32u;     // a wave log or the list of undecided pixels overflowed (k_frame_chain<LOG>, k_band_cc): the batch again through the plane, and the stream stays with it
+constexpr uint32_t kOvfLdsForest = 64u;   // a frame beyond the LDS forest met on the log path (k_frame_chain<LOG>): this batch again through the plane
+constexpr uint32_t kOvfBandPlan = 128u;   // a band beyond the band stage's plan (k_band_cc, k_frame_merge): the batch again through k_frame_chain, bands off for 32 batches
+// A different field: why a component is no reflection (filter_reflections), WireRec2::npx_flags >> 30 and ReflOut::flags
+constexpr uint32_t kRecTooSmall = 1u;     // fewer pixels than min_spot_size
+constexpr uint32_t kRecTooSpread = 2u;    // peak further than max_sep from the centre of mass
+
+// ---- the counter block of a stream (B = max_batch) -------------------------------------------------------------------------
+// [B] strong pixels | [B] components | [B][kSummaryWords] summary | [1] status word | [B] per-frame flag words, as 32-bit words.
+// The device block ends behind the status word (one copy brings it back); the pinned host block also has the per-frame flag
+// words, which the one-launch sparse stages write themselves -- such a batch's status is their OR (ffs_wait.hip: batch_overflow).
+constexpr int kSummaryWords = 8;
+constexpr uint32_t kSumBoxes = 0, kSumStrongFiltered = 1, kSumReflections = 2, kSumFilteredSize = 3, kSumFilteredSep = 4;   // slots of a frame's summary
+__host__ __device__ constexpr size_t counts_strong_at(size_t) { return 0; }
+__host__ __device__ constexpr size_t counts_comp_at(size_t B) { return B; }
+__host__ __device__ constexpr size_t counts_summary_at(size_t B) { return 2 * B; }
+__host__ __device__ constexpr size_t counts_status_at(size_t B) { return (2 + kSummaryWords) * B; }
+__host__ __device__ constexpr size_t counts_frame_flags_at(size_t B) { return counts_status_at(B) + 1; }
+__host__ __device__ constexpr size_t counts_device_words(size_t B) { return counts_status_at(B) + 1; }
+__host__ __device__ constexpr size_t counts_host_words(size_t B) { return counts_frame_flags_at(B) + B; }
+
 // ---- strong-pixel lists and connected components -------------------------------------------------
 // 2D only (round 2): the accumulator of a component sits at the list index of its ROOT (its smallest
 // member, always the first pixel of a horizontal run), so no pass has to number the components before
@@ -183,7 +212,7 @@ struct CclArgs {
     uint32_t* parent;          // [n][cap]
     uint32_t* comp_id;         // [n][cap] component number of each ROOT entry
     uint32_t* n_comp;          // [n]
-    uint32_t* overflow;        // [1] set if any frame exceeded cap / max_comp
+    uint32_t* overflow;        // [1] status word: kOvfStrongCap / kOvfCompCap when a frame exceeded cap / max_comp
     int W, H, pitch_px;
     uint32_t mpitch;
     uint64_t plane_frame_stride;

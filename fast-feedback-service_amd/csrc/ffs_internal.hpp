@@ -241,8 +241,7 @@ struct ffs_stream {
     uint8_t* d_band_acc = nullptr;
     uint32_t* d_band_seam = nullptr;
     uint32_t band_slots = 0;                 // (frame, band) pairs the three buffers hold
-    uint32_t band_backoff = 0;               // batches this stream still sends through k_frame_chain after a band overflowed its plan (flag 128: dense data)
-    bool band_mode = false;                  // this batch's sparse stage is k_band_cc + k_frame_merge
+    uint32_t band_backoff = 0;               // batches this stream still sends through k_frame_chain after a band overflowed its plan (kOvfBandPlan: dense data)
     uint32_t path_bits = 0;                  // which launches the last batch took (ffs_stream_last_path)
     uint32_t reruns = 0;                     // times ffs_wait ran the last batch again (a plan that did not hold it)
     bool runs_overflowed = false;            // a frame's runs overflowed the one launch: dense batches of this stream take the grid-wide sparse kernels
@@ -298,7 +297,7 @@ struct ffs_stream {
     size_t h_img_bytes = 0;
     PinnedBuf h_img_buf;           // ... and how it was obtained
     size_t d_comp_bytes = 0;
-    uint32_t* h_counts = nullptr;  // [max_batch] num_strong | [max_batch] n_comp | [max_batch*8] summary | [1] overflow | [max_batch] per-frame flags
+    uint32_t* h_counts = nullptr;  // the counter block (layout: ffs_device.h, counts_*_at; counts_host_words(max_batch) words)
     ReflOut* h_recs = nullptr;
     uint32_t* d_occ = nullptr;     // [max_batch][occ_frame_words] occupancy of the strong plane (one bit per 16-byte segment)
     uint32_t* h_counts_dev = nullptr;  // device-side address of h_counts (k_frame_chain writes the counters itself)
@@ -353,6 +352,14 @@ struct OverflowFrame {
     std::vector<uint32_t> k, inten;
 };
 
+// the re-run of frame `f` among a batch's overflow frames, or null (`ovf` may be null: a batch assembled ahead of its wait has none)
+static inline const OverflowFrame* overflow_frame(const std::vector<OverflowFrame>* ovf, uint32_t f) {
+    if (ovf)
+        for (const OverflowFrame& o : *ovf)
+            if (o.frame == f) return &o;
+    return nullptr;
+}
+
 // ---- no exception crosses the C ABI -----------------------------------------------------------------------
 // The entry points that grow std::vectors (results, staging tables, masks) run inside a catch-all: an
 // allocation failure or a length error becomes FFS_ERR_NOMEM with its text in ffs_last_error, instead of
@@ -387,7 +394,7 @@ static int guarded(ffs_ctx* c, F&& body) {
 struct Rerun {
     int threshold_path = -1;   // >= 0: the threshold path of this enqueue (bright-list overflow -> 1)
     bool plane = false;        // takes the plane (a batch the wave logs could not serve)
-    bool no_bands = false;     // takes k_frame_chain (the batch that raised flag 128)
+    bool no_bands = false;     // takes k_frame_chain (the batch that raised kOvfBandPlan)
     bool grid = false;         // takes the grid-wide sparse kernels (a frame's runs overflowed the one launch)
 };
 // extended algorithm: the strip erosion stores only the non-zero words of a signal-region plane that was cleared behind the previous batch

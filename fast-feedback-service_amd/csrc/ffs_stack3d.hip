@@ -471,12 +471,6 @@ extern "C" int ffs_multi_gather_rows(ffs_stream* const* streams, uint32_t n_stre
     return guarded(streams[root]->ctx, [&] { return multi_gather_rows_impl(streams, n_streams, root, rows4_out, cap, n_rows); });
 }
 
-static const OverflowFrame* overflow_of(const ffs_stream* s, uint32_t f) {
-    for (const OverflowFrame& q : s->ovf)
-        if (q.frame == f) return &q;
-    return nullptr;
-}
-
 // Lists of a batch processed on ANOTHER context (same detector geometry, usually another GPU) into this stack: packed end
 // to end on the source device, then one transfer per array.  Frames that overflowed the stream's lists were re-run on the
 // stream's one-frame stream and have their lists on the host (as for a local batch): those go up from there.
@@ -506,7 +500,7 @@ static int stack3d_add_batch_remote(ffs_stack3d* st, ffs_stream* s, uint64_t pac
     }
     uint32_t at = 0;
     for (uint32_t f = 0; f < nf; ++f) {
-        const uint32_t n = overflow_of(s, f) ? 0u : s->results[f].num_strong_pixels;
+        const uint32_t n = overflow_frame(&s->ovf, f) ? 0u : s->results[f].num_strong_pixels;
         s->h_pack_tab[f] = StackSlice{0u, at, n, 0u};
         at += n;
     }
@@ -572,7 +566,7 @@ static int stack3d_add_batch_impl(ffs_stack3d* st, ffs_stream* s) {
     for (uint32_t f = 0; f < nf; ++f) more += s->results[f].num_strong_pixels;
     for (uint32_t f = 0; f < nf; ++f) {
         // a frame that did not fit the stream's lists was re-run on its one-frame stream: its list is on the host, if kept
-        const OverflowFrame* o = overflow_of(s, f);
+        const OverflowFrame* o = overflow_frame(&s->ovf, f);
         if (o && s->results[f].num_strong_pixels && o->k.size() != s->results[f].num_strong_pixels) {
             c->err = "ffs_stack3d_add_batch: a frame overflowed the stream's lists; set want_strong_list (or a larger "
                      "max_strong_per_frame) for rotation sweeps";
@@ -604,13 +598,13 @@ static int stack3d_add_batch_impl(ffs_stack3d* st, ffs_stream* s) {
         // packed frames must be contiguous in the stack: overflow frames' entries are placed behind them
         uint64_t a2 = st->arrived;
         for (uint32_t f = 0; f < nf; ++f)
-            if (!overflow_of(s, f)) { dst[f] = a2; a2 += s->results[f].num_strong_pixels; }
+            if (!overflow_frame(&s->ovf, f)) { dst[f] = a2; a2 += s->results[f].num_strong_pixels; }
         packed = a2 - st->arrived;
         for (uint32_t f = 0; f < nf; ++f)
-            if (overflow_of(s, f)) { dst[f] = a2; a2 += s->results[f].num_strong_pixels; }
+            if (overflow_frame(&s->ovf, f)) { dst[f] = a2; a2 += s->results[f].num_strong_pixels; }
     }
     for (uint32_t f = 0; f < nf; ++f) {
-        const OverflowFrame* o = overflow_of(s, f);
+        const OverflowFrame* o = overflow_frame(&s->ovf, f);
         const uint32_t n = s->results[f].num_strong_pixels;
         if (o && n) {
             STK_TRY(c, hipMemcpyAsync(st->a_k.p + dst[f], o->k.data(), (size_t)n * 4, hipMemcpyHostToDevice, up_st));
@@ -655,7 +649,7 @@ static int stack3d_add_batch_impl(ffs_stack3d* st, ffs_stream* s) {
     StackSlice* d_tab = st->d_ring.p + (size_t)slot * st->ring_stride;
     for (uint32_t f = 0; f < nf; ++f) {
         const ffs_frame_result& r = s->results[f];
-        h_tab[f] = StackSlice{0u, (uint32_t)dst[f], overflow_of(s, f) ? 0u : r.num_strong_pixels, 0u};
+        h_tab[f] = StackSlice{0u, (uint32_t)dst[f], overflow_frame(&s->ovf, f) ? 0u : r.num_strong_pixels, 0u};
         st->slices[r.frame_id] = ffs_stack3d::Slice{(uint32_t)dst[f], r.num_strong_pixels};
     }
     if (biggest) {
@@ -794,8 +788,8 @@ static int stack3d_finish_impl(ffs_stack3d* st, const ffs_reflection** reflectio
         std::vector<int32_t> kept_index(n_calc, -1);
         for (uint32_t q = 0; q < n_calc; ++q) {
             const ReflOut& r = recs[q];
-            if (r.flags & 1u) ++fs;
-            else if (r.flags & 2u) ++fp;
+            if (r.flags & kRecTooSmall) ++fs;
+            else if (r.flags & kRecTooSpread) ++fp;
             else {
                 ffs_reflection o;
                 std::memcpy(&o, &r, sizeof(o));

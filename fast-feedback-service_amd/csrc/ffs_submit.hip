@@ -481,11 +481,11 @@ static BatchPlan plan_batch(ffs_stream* s, const void* d_img, size_t pitch, size
     // previous batch held (data that is dense stays dense; a single dense frame costs one slow batch).
     // Denser frames of 16-bit pixels stay in the one launch while their RUNS fit LDS (kernels_chain.hpp, the RUNS instantiation:
     // 61 k strong pixels are 12 k runs on the bench frames of the extended algorithm); a frame with more runs than that raises
-    // flag 16, ffs_wait() runs the batch again through the grid-wide kernels and the stream stays with them for dense batches.
+    // kOvfRuns, ffs_wait() runs the batch again through the grid-wide kernels and the stream stays with them for dense batches.
     P.runs_ok = c->pixel_bytes == 2 && L.W <= kChainRunMaxW && c->tune.chain_runs != 0 && !s->runs_overflowed;
     if (can_chain && c->tune.sparse_stage == 2 && s->n_frames > 0) {
         uint32_t prev_max = 0;
-        for (uint32_t f = 0; f < s->n_frames; ++f) prev_max = std::max(prev_max, s->h_counts[f]);
+        for (uint32_t f = 0; f < s->n_frames; ++f) prev_max = std::max(prev_max, s->h_counts[counts_strong_at(s->max_batch) + f]);
         P.dense_batch = prev_max > (uint32_t)kChainLdsEntries;
     }
     P.will_chain = can_chain && (!P.dense_batch || P.runs_ok) && !how.grid;
@@ -863,7 +863,7 @@ static int launch_grid_stage(ffs_stream* s, const BatchPlan& plan, const CclArgs
 
     // small counts first; ffs_wait() sizes the record copy from them
     const size_t B = s->max_batch;
-    HIP_TRY(c, hipMemcpyAsync(s->h_counts, s->d_num_strong, (B * 10 + 1) * 4, hipMemcpyDeviceToHost, s->st2));
+    HIP_TRY(c, hipMemcpyAsync(s->h_counts, s->d_num_strong, counts_device_words(B) * 4, hipMemcpyDeviceToHost, s->st2));
     if (s->direct_recs) {
         s->spec_recs_copied = (uint64_t)B * s->max_comp;  // everything is on the host already
     } else {
@@ -899,9 +899,8 @@ int enqueue_batch(ffs_stream* s, const void* d_img, size_t pitch, size_t fstride
     FFS_TRY(take_extended_planes(s, ext_plane_clean));
     const BatchPlan plan = plan_batch(s, d_img, pitch, fstride, n, how);
     // (the one thing planning changes in what the stream remembers: a batch that could take bands brings the stream one step back to
-    // them after a band overflowed their plan -- ffs_wait.hip sets the 32)
+    // them after a band overflowed their plan -- ffs_wait.hip, decide_recovery, sets the 32)
     if (plan.use_log && s->band_backoff > 0 && !how.no_bands) --s->band_backoff;
-    s->band_mode = plan.banded;
     bool dense_resets = false;
     FFS_TRY(reset_for_batch(s, plan, dense_resets));
     FFS_TRY(launch_threshold_stage(s, plan, dense_resets, ext_plane_clean));
@@ -1247,7 +1246,7 @@ extern "C" int ffs_decode_only(ffs_stream* s, const void* const* chunks, const s
         const size_t row = (size_t)L.W * c->pixel_bytes;
         HIP_TRY(c, hipMemcpy2D(host_out, row, s->d_img, L.pitch, row, (size_t)L.H * n_frames, hipMemcpyDeviceToHost));
     }
-    if (flag & 4u) {
+    if (flag & kOvfCorruptLz4) {
         HIP_TRY(c, hipMemset(s->d_overflow, 0, 4));
         c->err = "corrupt bitshuffle-LZ4 chunk: an LZ4 block did not decode to its block size";
         return FFS_ERR_INVALID;

@@ -13,6 +13,102 @@ static int ensure_list_host(ffs_stream* s) {
     return FFS_OK;
 }
 
+// Where each frame's boxes / reflections / records lie follows from the per-frame summaries the sparse stage wrote (boxes =
+// summary[kSumBoxes], reflections = summary[kSumReflections]; a frame that was re-run on the one-frame stream: what that run
+// returned), so the frames can be assembled independently -- by the caller and the context's helper threads (AssemblyPool) when
+// the batch is large.  box_at / refl_at: [n + 1] (the last entry: the batch's totals), rec_at: [n].
+static void place_frames(const ffs_stream* s, const std::vector<OverflowFrame>* ovf, std::vector<size_t>& box_at, std::vector<size_t>& refl_at,
+                         std::vector<size_t>& rec_at) {
+    const uint32_t n = s->n_frames;
+    const size_t B = s->max_batch;
+    const uint32_t* h_nc = s->h_counts + counts_comp_at(B);
+    const uint32_t* h_sm = s->h_counts + counts_summary_at(B);
+    const bool want_refl = s->batch_params.want_reflections != 0;
+    size_t nb = 0, nr = 0, at = 0;
+    for (uint32_t f = 0; f < n; ++f) {
+        box_at[f] = nb;
+        refl_at[f] = nr;
+        const uint32_t nc = std::min<uint32_t>(h_nc[f], s->max_comp);
+        rec_at[f] = s->chain_mode ? (size_t)f * s->max_comp : at;   // k_frame_chain: every frame has its own record area
+        at += nc;
+        if (const OverflowFrame* o = overflow_frame(ovf, f)) {
+            nb += o->boxes.size();
+            nr += want_refl ? o->refls.size() : 0;
+        } else {
+            nb += h_sm[(size_t)f * kSummaryWords + kSumBoxes];
+            nr += want_refl ? h_sm[(size_t)f * kSummaryWords + kSumReflections] : 0;
+        }
+    }
+    box_at[n] = nb;
+    refl_at[n] = nr;
+}
+
+// The context's helper threads for large batches, started on first use; null: none to be had (the wait assembles on its own)
+static AssemblyPool* assembly_pool(ffs_ctx* c) {
+    AssemblyPool* pool = c->assembly.load(std::memory_order_acquire);
+    if (pool || process_exiting()) return pool;
+    std::lock_guard<std::mutex> lock(c->stream_mu);
+    pool = c->assembly.load(std::memory_order_acquire);
+    if (pool) return pool;
+    pool = new (std::nothrow) AssemblyPool();
+    if (pool) {
+        try {
+            pool->start(std::max(1, std::min(31, c->tune.assembly_threads)));
+        } catch (...) {   // (no more threads to be had: whatever did start is joined, and this wait assembles on its own)
+            delete pool;
+            pool = nullptr;
+        }
+    }
+    if (pool) c->assembly.store(pool, std::memory_order_release);   // (published with its members built and its threads started)
+    return pool;
+}
+
+// The per-frame results of the batch: counts from the counter block, pointers into the arrays just assembled (and into the
+// stream's list and mask copies); a frame that was re-run on the one-frame stream reports what that run returned.
+static void fill_frame_results(ffs_stream* s, const std::vector<OverflowFrame>* ovf, const std::vector<size_t>& box_at, const std::vector<size_t>& refl_at,
+                               std::vector<ffs_frame_result>& out_results, std::vector<ffs_box>& out_boxes, std::vector<ffs_reflection>& out_refls) {
+    const uint32_t n = s->n_frames;
+    const size_t B = s->max_batch;
+    const Layout& L = s->ctx->L;
+    const ffs_params& p = s->batch_params;
+    const uint32_t* h_ns = s->h_counts + counts_strong_at(B);
+    const uint32_t* h_nc = s->h_counts + counts_comp_at(B);
+    const uint32_t* h_sm = s->h_counts + counts_summary_at(B);
+    for (uint32_t f = 0; f < n; ++f) {
+        ffs_frame_result& r = out_results[f];
+        const uint32_t* sm = h_sm + (size_t)f * kSummaryWords;
+        r.frame_id = s->first_id + f;
+        r.num_strong_pixels = h_ns[f];
+        r.num_strong_pixels_filtered = sm[kSumStrongFiltered];
+        r.n_components = h_nc[f];
+        r.n_boxes = sm[kSumBoxes];
+        r.boxes = out_boxes.data() + box_at[f];
+        r.n_reflections = p.want_reflections ? sm[kSumReflections] : 0;
+        r.reflections = p.want_reflections ? out_refls.data() + refl_at[f] : nullptr;
+        r.n_filtered_size = sm[kSumFilteredSize];
+        r.n_filtered_sep = sm[kSumFilteredSep];
+        if (p.want_strong_list) {
+            r.strong_k = s->h_list_k ? s->h_list_k + (size_t)f * s->cap : nullptr;
+            r.strong_intensity = s->h_list_i ? s->h_list_i + (size_t)f * s->cap : nullptr;
+        }
+        if (p.want_strong_mask) r.strong_mask = s->h_mask + (size_t)f * L.W * L.H;
+        if (const OverflowFrame* o = overflow_frame(ovf, f)) {
+            const ffs_frame_result& b = o->res;
+            r.num_strong_pixels = b.num_strong_pixels;
+            r.num_strong_pixels_filtered = b.num_strong_pixels_filtered;
+            r.n_components = b.n_components;
+            r.n_boxes = b.n_boxes;
+            r.n_reflections = p.want_reflections ? b.n_reflections : 0;
+            r.n_filtered_size = b.n_filtered_size;
+            r.n_filtered_sep = b.n_filtered_sep;
+            if (p.want_strong_list) {
+                r.strong_k = o->k.data();
+                r.strong_intensity = o->inten.data();
+            }
+        }
+    }
+}
+
 // Turns the batch's wire records and summaries (pinned host memory, complete) into the arrays ffs_wait hands out.  Runs on the
 // caller's thread inside ffs_wait, or ahead of it on the context's AheadThread (then into the stream's *_n arrays).
 // `ovf`: the frames of this batch that were run again on the one-frame stream (only ffs_wait's own path has any).
@@ -20,18 +116,8 @@ static int assemble_batch(ffs_stream* s, uint64_t total_recs, const std::vector<
                           std::vector<ffs_box>& out_boxes, std::vector<ffs_reflection>& out_refls, std::vector<float>& out_centres) {
     ffs_ctx* c = s->ctx;
     const uint32_t n = s->n_frames;
-    const size_t B = s->max_batch;
-    const Layout& L = c->L;
     const ffs_params& p = s->batch_params;
-    const uint32_t* h_ns = s->h_counts;
-    const uint32_t* h_nc = s->h_counts + B;
-    const uint32_t* h_sm = s->h_counts + 2 * B;
-    auto overflow_frame = [&](uint32_t f) -> const OverflowFrame* {
-        if (ovf)
-            for (const OverflowFrame& o : *ovf)
-                if (o.frame == f) return &o;
-        return nullptr;
-    };
+    const uint32_t* h_nc = s->h_counts + counts_comp_at(s->max_batch);
     // assemble: boxes = components surviving the min-size filter (connected_components.cc:122-135),
     // reflections = components surviving filter_reflections (:207-236); both keep label order.
     // (written through raw pointers into arrays sized for the worst case: 45 000 records per batch of the bench frames, and the
@@ -39,29 +125,8 @@ static int assemble_batch(ffs_stream* s, uint64_t total_recs, const std::vector<
     out_results.assign(n, ffs_frame_result{});
     const uint32_t min_size = p.min_spot_size;
     const bool want_refl = p.want_reflections != 0;
-    // Where each frame's boxes / reflections / records lie follows from the per-frame summaries the sparse stage wrote (boxes =
-    // summary[0], reflections = summary[2]; a frame that was re-run on the one-frame stream: what that run returned), so the
-    // frames can be assembled independently -- by the caller and the context's helper threads (AssemblyPool) when the batch is large.
     std::vector<size_t> box_at(n + 1), refl_at(n + 1), rec_at(n);
-    {
-        size_t nb = 0, nr = 0, at = 0;
-        for (uint32_t f = 0; f < n; ++f) {
-            box_at[f] = nb;
-            refl_at[f] = nr;
-            const uint32_t nc = std::min<uint32_t>(h_nc[f], s->max_comp);
-            rec_at[f] = s->chain_mode ? (size_t)f * s->max_comp : at;   // k_frame_chain: every frame has its own record area
-            at += nc;
-            if (const OverflowFrame* o = overflow_frame(f)) {
-                nb += o->boxes.size();
-                nr += want_refl ? o->refls.size() : 0;
-            } else {
-                nb += h_sm[(size_t)f * 8 + 0];
-                nr += want_refl ? h_sm[(size_t)f * 8 + 2] : 0;
-            }
-        }
-        box_at[n] = nb;
-        refl_at[n] = nr;
-    }
+    place_frames(s, ovf, box_at, refl_at, rec_at);
     out_boxes.resize(box_at[n]);
     out_refls.resize(refl_at[n]);
     // the centres as (frame id, x, y, z) rows, written while each record is in hand: ffs_stream_spot_centres hands them out with one
@@ -77,7 +142,7 @@ static int assemble_batch(ffs_stream* s, uint64_t total_recs, const std::vector<
         const uint32_t id_bits = (uint32_t)((uint64_t)(s->first_id + f) & 0xFFFFFFFFull);   // (a bit pattern: as a float VALUE ids collide from 2^24 on)
         float id_lane;
         std::memcpy(&id_lane, &id_bits, 4);
-        if (const OverflowFrame* o = overflow_frame(f)) {  // re-run on the one-frame stream: its cut records are skipped
+        if (const OverflowFrame* o = overflow_frame(ovf, f)) {  // re-run on the one-frame stream: its cut records are skipped
             for (const ffs_box& b : o->boxes) bo[nbx++] = b;
             if (want_refl)
                 for (const ffs_reflection& r : o->refls) {
@@ -113,27 +178,9 @@ static int assemble_batch(ffs_stream* s, uint64_t total_recs, const std::vector<
         }
         if (nbx != box_end || nrf != refl_end) consistent = false;
     };
-    // assemble: boxes = components surviving the min-size filter (connected_components.cc:122-135),
-    // reflections = components surviving filter_reflections (:207-236); both keep label order.
     bool pooled = false;
     if (total_recs >= 8192 && n >= 4) {
-        AssemblyPool* pool = c->assembly.load(std::memory_order_acquire);
-        if (!pool && !process_exiting()) {
-            std::lock_guard<std::mutex> lock(c->stream_mu);
-            pool = c->assembly.load(std::memory_order_acquire);
-            if (!pool) {
-                pool = new (std::nothrow) AssemblyPool();
-                if (pool) {
-                    try {
-                        pool->start(std::max(1, std::min(31, c->tune.assembly_threads)));
-                    } catch (...) {   // (no more threads to be had: whatever did start is joined, and this wait assembles on its own)
-                        delete pool;
-                        pool = nullptr;
-                    }
-                }
-                if (pool) c->assembly.store(pool, std::memory_order_release);   // (published with its members built and its threads started)
-            }
-        }
+        AssemblyPool* pool = assembly_pool(c);
         if (pool && pool->owner.try_lock()) {   // (another stream's wait has the helpers: assemble here)
             pool->run(n, assemble);
             pool->owner.unlock();
@@ -143,40 +190,18 @@ static int assemble_batch(ffs_stream* s, uint64_t total_recs, const std::vector<
     if (!pooled)
         for (uint32_t f = 0; f < n; ++f) assemble(f);
     if (!consistent.load()) return FFS_ERR_DEVICE;   // (the caller words the error: this may run on the context's own thread)
-    for (uint32_t f = 0; f < n; ++f) {
-        ffs_frame_result& r = out_results[f];
-        const uint32_t* sm = h_sm + (size_t)f * 8;
-        r.frame_id = s->first_id + f;
-        r.num_strong_pixels = h_ns[f];
-        r.num_strong_pixels_filtered = sm[1];
-        r.n_components = h_nc[f];
-        r.n_boxes = sm[0];
-        r.boxes = out_boxes.data() + box_at[f];
-        r.n_reflections = p.want_reflections ? sm[2] : 0;
-        r.reflections = p.want_reflections ? out_refls.data() + refl_at[f] : nullptr;
-        r.n_filtered_size = sm[3];
-        r.n_filtered_sep = sm[4];
-        if (p.want_strong_list) {
-            r.strong_k = s->h_list_k ? s->h_list_k + (size_t)f * s->cap : nullptr;
-            r.strong_intensity = s->h_list_i ? s->h_list_i + (size_t)f * s->cap : nullptr;
-        }
-        if (p.want_strong_mask) r.strong_mask = s->h_mask + (size_t)f * L.W * L.H;
-        if (const OverflowFrame* o = overflow_frame(f)) {
-            const ffs_frame_result& b = o->res;
-            r.num_strong_pixels = b.num_strong_pixels;
-            r.num_strong_pixels_filtered = b.num_strong_pixels_filtered;
-            r.n_components = b.n_components;
-            r.n_boxes = b.n_boxes;
-            r.n_reflections = p.want_reflections ? b.n_reflections : 0;
-            r.n_filtered_size = b.n_filtered_size;
-            r.n_filtered_sep = b.n_filtered_sep;
-            if (p.want_strong_list) {
-                r.strong_k = o->k.data();
-                r.strong_intensity = o->inten.data();
-            }
-        }
-    }
+    fill_frame_results(s, ovf, box_at, refl_at, out_results, out_boxes, out_refls);
     return FFS_OK;
+}
+
+// The status word of the stream's batch (ffs_device.h: kOvf*), complete behind the batch's last event.  The one-launch sparse stages
+// write a flag word per frame: the batch's status is their OR; otherwise it is the block's status word.
+static uint32_t batch_overflow(const ffs_stream* s) {
+    const size_t B = s->max_batch;
+    if (!s->chain_mode) return s->h_counts[counts_status_at(B)];
+    uint32_t overflow = 0;
+    for (uint32_t f = 0; f < s->n_frames; ++f) overflow |= s->h_counts[counts_frame_flags_at(B) + f];
+    return overflow;
 }
 
 // ---- assembly ahead of ffs_wait (ffs_internal.hpp: AheadThread) ------------------------------------------------------------------
@@ -196,16 +221,10 @@ static void ahead_main(ffs_ctx* c) {
         try {
             const ffs_params& p = s->batch_params;
             if (hipEventSynchronize(s->ev[4]) == hipSuccess && !p.want_strong_list && !p.want_strong_mask && s->direct_recs) {
-                const uint32_t n = s->n_frames;
-                const size_t B = s->max_batch;
-                uint32_t overflow = s->h_counts[10 * B];
-                if (s->chain_mode) {
-                    overflow = 0;
-                    for (uint32_t f = 0; f < n; ++f) overflow |= s->h_counts[10 * B + 1 + f];
-                }
-                if (overflow == 0) {
+                if (batch_overflow(s) == 0) {
+                    const uint32_t* h_nc = s->h_counts + counts_comp_at(s->max_batch);
                     uint64_t total_recs = 0;
-                    for (uint32_t f = 0; f < n; ++f) total_recs += std::min<uint32_t>(s->h_counts[B + f], s->max_comp);
+                    for (uint32_t f = 0; f < s->n_frames; ++f) total_recs += std::min<uint32_t>(h_nc[f], s->max_comp);
                     if (assemble_batch(s, total_recs, nullptr, s->results_n, s->boxes_n, s->refls_n, s->centres_n) == FFS_OK) verdict = 2;
                 }
             } else {
@@ -295,173 +314,174 @@ static int rerun_batch(ffs_stream* s, const Rerun& how, const ffs_frame_result**
     return ffs_wait_impl(s, results, n_results);
 }
 
-int ffs_wait_impl(ffs_stream* s, const ffs_frame_result** results, uint32_t* n_results) {
-    if (!s) return FFS_ERR_INVALID;
-    ffs_ctx* c = s->ctx;
-    if (!s->busy) {
-        c->err = "ffs_wait: nothing submitted";
-        return FFS_ERR_INVALID;
+// What ffs_wait does about a batch whose status word is not zero (ffs_device.h: kOvf*): the precedence of the whole recovery
+// protocol.  A re-run of the batch comes with what the stream remembers beyond it (band_backoff, log_off, runs_overflowed), set here.
+struct Recovery {
+    enum Kind { kFail, kRerunBatch, kRerunFrames } kind;
+    Rerun how;   // kRerunBatch: what the enqueue overrides
+};
+static Recovery decide_recovery(ffs_stream* s, uint32_t overflow) {
+    if (overflow & kOvfCorruptLz4) {
+        s->ctx->err = "corrupt bitshuffle-LZ4 chunk: an LZ4 block did not decode to its block size";
+        return {Recovery::kFail, {}};
     }
-    HIP_TRY(c, hipSetDevice(c->device));
-    if (s->job.joinable()) {
-        s->job.join();
-        if (s->job_rc != FFS_OK) {
-            (void)hipStreamSynchronize(s->st_up);
-            mark_idle(s);
-            c->err = s->job_err;
-            return s->job_rc;
+    if (overflow & kOvfBrightList) {
+        // more bright-window pixels than the list k_stream_u16 hands to k_bright_fix holds (a batch of
+        // saturated frames): run the batch again with those pixels marked in the plane as candidates for the exact kernel
+        // (threshold path 1; the extended algorithm: its plain first pass), which has no such list
+        return {Recovery::kRerunBatch, Rerun{.threshold_path = 1}};
+    }
+    if ((overflow & kOvfBandPlan) && !(overflow & kOvfWaveLog)) {
+        // a band of a frame beyond the plan of the small-workgroup sparse stage (kernels_band.hpp: strong pixels, log entries,
+        // components or seam pixels of ONE band): the batch again through the one-workgroup launch, and so the stream's next batches
+        // (data that is dense stays dense)
+        s->band_backoff = 32;
+        return {Recovery::kRerunBatch, Rerun{.no_bands = true}};
+    }
+    if (overflow & (kOvfWaveLog | kOvfLdsForest)) {
+        // the wave logs could not serve a frame of the batch: the batch again through the plane.  A wave with more strong groups
+        // than its log holds (kOvfWaveLog): the stream stays with the plane.  A frame with more strong pixels than the one launch's
+        // LDS forest (kOvfLdsForest): only this batch -- the next one follows what this one held (dense data takes the plane by
+        // itself, and the logs are back when the data is sparse again)
+        if (overflow & kOvfWaveLog) s->log_off = true;
+        return {Recovery::kRerunBatch, Rerun{.plane = true}};
+    }
+    if (overflow & kOvfRuns) {
+        // a dense frame with more runs than the one-launch sparse stage holds in LDS (kernels_chain.hpp): the batch again, its
+        // sparse stage as the four grid-wide kernels; the stream's later dense batches go there directly
+        s->runs_overflowed = true;
+        return {Recovery::kRerunBatch, Rerun{.grid = true}};
+    }
+    // kOvfStrongCap / kOvfCompCap: only some frames did not fit; the others are complete
+    return {Recovery::kRerunFrames, {}};
+}
+
+// A frame with more strong pixels than the stream's lists hold (kOvfStrongCap) or more components than its record buffers
+// (kOvfCompCap) -- an ice ring, the direct beam.  The reference has no such limit (std::map of signals,
+// connected_components.cc:24-32), so neither may the drop-in: the other frames of the batch are complete (lists and records are
+// per frame), and each frame that did not fit is run again on its own on a one-frame stream with room for it (kept for the next
+// time).  Their results go into s->ovf.
+static int rerun_overflow_frames(ffs_stream* s) {
+    ffs_ctx* c = s->ctx;
+    const Layout& L = c->L;
+    const size_t B = s->max_batch;
+    const uint32_t* h_ns = s->h_counts + counts_strong_at(B);
+    const uint32_t* h_nc = s->h_counts + counts_comp_at(B);
+    for (uint32_t f = 0; f < s->n_frames; ++f) {
+        if (h_ns[f] <= s->cap && h_nc[f] <= s->max_comp) continue;
+        uint64_t need_cap = std::max<uint64_t>(h_ns[f], s->cap);
+        uint64_t need_comp = h_ns[f] > s->cap ? need_cap : std::max<uint64_t>(h_nc[f], s->max_comp);  // list truncated: count unknown
+        for (int attempt = 0;; ++attempt) {
+            if (s->big && (s->big->cap < need_cap || s->big->max_comp < need_comp)) {
+                stream_destroy_internal(s->big);
+                s->big = nullptr;
+            }
+            if (!s->big) {
+                const uint64_t npx = (uint64_t)L.W * L.H;
+                const uint32_t bc = (uint32_t)std::min<uint64_t>(npx, need_cap + need_cap / 4 + 1024);
+                const uint32_t bm = (uint32_t)std::min<uint64_t>(bc, need_comp + need_comp / 4 + 1024);
+                int rc = stream_create_sized(c, 1, bc, bm, &s->big);
+                if (rc != FFS_OK) return rc;  // a real out-of-memory
+            }
+            ffs_stream* b = s->big;
+            const uint8_t* img = static_cast<const uint8_t*>(s->cur_img) + (size_t)f * s->cur_fstride;
+            b->first_id = s->first_id + f;
+            b->dev_input = true;
+            b->ev1_pending = true;
+            // (the frame's strong-pixel list comes back to the host whenever somebody may read it: the caller, or a 3D stack
+            // that is alive -- ffs_stack3d_add_batch takes an overflow frame's list from here, tuning "device_lists")
+            ffs_params bp = s->batch_params;
+            if (c->tune.device_lists == 1 || (c->tune.device_lists == 2 && g_live_stacks.load() > 0)) bp.want_strong_list = 1;
+            int rc = enqueue_batch(b, img, s->cur_pitch, s->cur_fstride, 1, &bp);
+            if (rc != FFS_OK) return rc;
+            HIP_TRY(c, hipEventSynchronize(b->ev[4]));
+            if (batch_overflow(b) & (kOvfStrongCap | kOvfCompCap)) {  // only the component count can still be short (it was a guess while the list was cut)
+                (void)hipMemsetAsync(b->d_overflow, 0, 4, b->st2);
+                (void)hipStreamSynchronize(b->st2);
+                mark_idle(b);
+                b->bits_dirty = true;
+                need_cap = std::max<uint64_t>(need_cap, b->h_counts[counts_strong_at(b->max_batch)]);
+                need_comp = std::max<uint64_t>(need_comp * 2, b->h_counts[counts_comp_at(b->max_batch)]);
+                if (attempt >= 4) {
+                    c->err = "a frame still overflows its one-frame stream";
+                    return FFS_ERR_OVERFLOW;
+                }
+                continue;
+            }
+            const ffs_frame_result* br = nullptr;
+            uint32_t bn = 0;
+            rc = ffs_wait_impl(b, &br, &bn);
+            if (rc != FFS_OK) return rc;
+            s->ovf.emplace_back();
+            OverflowFrame& o = s->ovf.back();
+            o.frame = f;
+            o.res = br[0];
+            o.boxes.assign(br[0].boxes, br[0].boxes + br[0].n_boxes);
+            if (br[0].reflections) o.refls.assign(br[0].reflections, br[0].reflections + br[0].n_reflections);
+            if (br[0].strong_k) {
+                o.k.assign(br[0].strong_k, br[0].strong_k + br[0].num_strong_pixels);
+                o.inten.assign(br[0].strong_intensity, br[0].strong_intensity + br[0].num_strong_pixels);
+            }
+            break;
         }
     }
-    if (ahead_take(s) == 2) {
-        // the context's own thread has assembled this batch behind its last event: its arrays become the stream's
-        s->results.swap(s->results_n);
-        s->boxes.swap(s->boxes_n);
-        s->refls.swap(s->refls_n);
-        s->centres.swap(s->centres_n);
-        // the arrays handed back now take the NEXT batch: sized (and their pages touched) here, once, rather than by the assembly
-        // thread in the middle of a run (a stream's second batch paid 0.5 ms of first-touch page faults for its 7 MB)
-        if (s->boxes_n.size() < s->boxes.size()) s->boxes_n.resize(s->boxes.size());
-        if (s->refls_n.size() < s->refls.size()) s->refls_n.resize(s->refls.size());
-        if (s->centres_n.size() < s->centres.size()) s->centres_n.resize(s->centres.size());
-        s->ovf.clear();
-        mark_idle(s);
-        s->timing_last = s->ev[4];
-        s->timings_stale = true;
-        if (results) *results = s->results.data();
-        if (n_results) *n_results = s->n_frames;
-        return FFS_OK;
+    return FFS_OK;
+}
+
+// Step 1: a batch submitted compressed has a helper thread that indexes the chunks' blocks and enqueues the launches
+// (ffs_submit_compressed); the wait joins it and hands on what it could not do.
+static int join_compressed_job(ffs_stream* s) {
+    if (!s->job.joinable()) return FFS_OK;
+    s->job.join();
+    if (s->job_rc == FFS_OK) return FFS_OK;
+    (void)hipStreamSynchronize(s->st_up);
+    mark_idle(s);
+    s->ctx->err = s->job_err;
+    return s->job_rc;
+}
+
+// Step 2: the context's own thread has assembled this batch behind its last event (a batch with no overflow and no list or mask
+// copies): its arrays become the stream's.  false: nothing was assembled ahead, the wait does the work.
+static bool take_ahead_result(ffs_stream* s) {
+    if (ahead_take(s) != 2) return false;
+    s->results.swap(s->results_n);
+    s->boxes.swap(s->boxes_n);
+    s->refls.swap(s->refls_n);
+    s->centres.swap(s->centres_n);
+    // the arrays handed back now take the NEXT batch: sized (and their pages touched) here, once, rather than by the assembly
+    // thread in the middle of a run (a stream's second batch paid 0.5 ms of first-touch page faults for its 7 MB)
+    if (s->boxes_n.size() < s->boxes.size()) s->boxes_n.resize(s->boxes.size());
+    if (s->refls_n.size() < s->refls.size()) s->refls_n.resize(s->refls.size());
+    if (s->centres_n.size() < s->centres.size()) s->centres_n.resize(s->centres.size());
+    s->ovf.clear();
+    mark_idle(s);
+    s->timing_last = s->ev[4];
+    s->timings_stale = true;
+    return true;
+}
+
+#ifdef FFS_EXPERIMENTS
+// phase durations of this batch's sparse launch, averaged over its frames (100 MHz counter)
+static void sum_phase_times(ffs_stream* s) {
+    if (!s->h_phase_ts || !s->chain_mode) return;
+    for (uint32_t f = 0; f < s->n_frames; ++f) {
+        const unsigned long long* t = s->h_phase_ts + (size_t)f * 8;
+        if (t[6] <= t[0]) continue;
+        for (int k = 0; k < 6; ++k) s->phase_sum[k] += (double)(t[k + 1] - t[k]) * 0.01;
+        s->phase_sum[6] += (double)(t[6] - t[0]) * 0.01;
+        ++s->phase_n;
     }
-    HIP_TRY(c, hipEventSynchronize(s->ev[4]));
+}
+#endif
+
+// Step 5: what the batch's last event did not bring to the host -- records beyond the speculative copy, the strong-pixel lists,
+// the byte masks -- copied in the sparse stream behind ev[5] and waited for.  `total_recs`: records of the batch; `max_ns`: the
+// longest list among its frames.
+static int second_phase_copies(ffs_stream* s, uint64_t total_recs, uint32_t max_ns) {
+    ffs_ctx* c = s->ctx;
     const uint32_t n = s->n_frames;
-    const size_t B = s->max_batch;
     const Layout& L = c->L;
     const ffs_params& p = s->batch_params;
-    const uint32_t* h_ns = s->h_counts;
-    const uint32_t* h_nc = s->h_counts + B;
-    uint32_t overflow = s->h_counts[10 * B];
-    if (s->chain_mode) {  // k_frame_chain: one flag word per frame
-        overflow = 0;
-        for (uint32_t f = 0; f < n; ++f) overflow |= s->h_counts[10 * B + 1 + f];
-    }
-    mark_idle(s);
-#ifdef FFS_EXPERIMENTS
-    if (s->h_phase_ts && s->chain_mode) {   // phase durations of this batch's sparse launch, averaged over its frames (100 MHz counter)
-        for (uint32_t f = 0; f < n; ++f) {
-            const unsigned long long* t = s->h_phase_ts + (size_t)f * 8;
-            if (t[6] <= t[0]) continue;
-            for (int k = 0; k < 6; ++k) s->phase_sum[k] += (double)(t[k + 1] - t[k]) * 0.01;
-            s->phase_sum[6] += (double)(t[6] - t[0]) * 0.01;
-            ++s->phase_n;
-        }
-    }
-#endif
-    s->ovf.clear();
-    if (overflow) {
-        s->bits_dirty = true;
-        (void)hipMemsetAsync(s->d_overflow, 0, 4, s->st2);
-        (void)hipStreamSynchronize(s->st2);
-        if (overflow & 4u) {
-            c->err = "corrupt bitshuffle-LZ4 chunk: an LZ4 block did not decode to its block size";
-            return FFS_ERR_INVALID;
-        }
-        if (overflow & 8u) {
-            // more bright-window pixels than the list k_stream_u16 hands to k_bright_fix holds (a batch of
-            // saturated frames): run the batch again with those pixels marked in the plane as candidates for the exact kernel
-            // (threshold path 1; the extended algorithm: its plain first pass), which has no such list
-            return rerun_batch(s, Rerun{.threshold_path = 1}, results, n_results);
-        }
-        if ((overflow & 128u) && !(overflow & 32u)) {
-            // a band of a frame beyond the plan of the small-workgroup sparse stage (kernels_band.hpp: strong pixels, log entries,
-            // components or seam pixels of ONE band): the batch again through the one-workgroup launch, and so the stream's next batches
-            // (data that is dense stays dense)
-            s->band_backoff = 32;
-            return rerun_batch(s, Rerun{.no_bands = true}, results, n_results);
-        }
-        if (overflow & (32u | 64u)) {
-            // the wave logs could not serve a frame of the batch: the batch again through the plane.  A wave with more strong groups
-            // than its log holds (32): the stream stays with the plane.  A frame with more strong pixels than the one launch's LDS
-            // forest (64): only this batch -- the next one follows what this one held (dense data takes the plane by itself,
-            // and the logs are back when the data is sparse again)
-            if (overflow & 32u) s->log_off = true;
-            return rerun_batch(s, Rerun{.plane = true}, results, n_results);
-        }
-        if (overflow & 16u) {
-            // a dense frame with more runs than the one-launch sparse stage holds in LDS (kernels_chain.hpp): the batch again, its
-            // sparse stage as the four grid-wide kernels; the stream's later dense batches go there directly
-            s->runs_overflowed = true;
-            return rerun_batch(s, Rerun{.grid = true}, results, n_results);
-        }
-        // A frame with more strong pixels than the stream's lists hold (flag 1) or more components than its
-        // record buffers (flag 2) -- an ice ring, the direct beam.  The reference has no such limit (std::map of
-        // signals, connected_components.cc:24-32), so neither may the drop-in: the other frames of the batch are
-        // complete (lists and records are per frame), and each frame that did not fit is run again on its own on
-        // a one-frame stream with room for it (kept for the next time).
-        for (uint32_t f = 0; f < n; ++f) {
-            if (h_ns[f] <= s->cap && h_nc[f] <= s->max_comp) continue;
-            uint64_t need_cap = std::max<uint64_t>(h_ns[f], s->cap);
-            uint64_t need_comp = h_ns[f] > s->cap ? need_cap : std::max<uint64_t>(h_nc[f], s->max_comp);  // list truncated: count unknown
-            for (int attempt = 0;; ++attempt) {
-                if (s->big && (s->big->cap < need_cap || s->big->max_comp < need_comp)) {
-                    stream_destroy_internal(s->big);
-                    s->big = nullptr;
-                }
-                if (!s->big) {
-                    const uint64_t npx = (uint64_t)L.W * L.H;
-                    const uint32_t bc = (uint32_t)std::min<uint64_t>(npx, need_cap + need_cap / 4 + 1024);
-                    const uint32_t bm = (uint32_t)std::min<uint64_t>(bc, need_comp + need_comp / 4 + 1024);
-                    int rc = stream_create_sized(c, 1, bc, bm, &s->big);
-                    if (rc != FFS_OK) return rc;  // a real out-of-memory
-                }
-                ffs_stream* b = s->big;
-                const uint8_t* img = static_cast<const uint8_t*>(s->cur_img) + (size_t)f * s->cur_fstride;
-                b->first_id = s->first_id + f;
-                b->dev_input = true;
-                b->ev1_pending = true;
-                // (the frame's strong-pixel list comes back to the host whenever somebody may read it: the caller, or a 3D stack
-                // that is alive -- ffs_stack3d_add_batch takes an overflow frame's list from here, tuning "device_lists")
-                ffs_params bp = s->batch_params;
-                if (c->tune.device_lists == 1 || (c->tune.device_lists == 2 && g_live_stacks.load() > 0)) bp.want_strong_list = 1;
-                int rc = enqueue_batch(b, img, s->cur_pitch, s->cur_fstride, 1, &bp);
-                if (rc != FFS_OK) return rc;
-                HIP_TRY(c, hipEventSynchronize(b->ev[4]));
-                const uint32_t b_ovf = b->chain_mode ? b->h_counts[10 * (size_t)b->max_batch + 1] : b->h_counts[10 * (size_t)b->max_batch];
-                if (b_ovf & 3u) {  // only the component count can still be short (it was a guess while the list was cut)
-                    (void)hipMemsetAsync(b->d_overflow, 0, 4, b->st2);
-                    (void)hipStreamSynchronize(b->st2);
-                    mark_idle(b);
-                    b->bits_dirty = true;
-                    need_cap = std::max<uint64_t>(need_cap, b->h_counts[0]);
-                    need_comp = std::max<uint64_t>(need_comp * 2, b->h_counts[b->max_batch]);
-                    if (attempt >= 4) {
-                        c->err = "a frame still overflows its one-frame stream";
-                        return FFS_ERR_OVERFLOW;
-                    }
-                    continue;
-                }
-                const ffs_frame_result* br = nullptr;
-                uint32_t bn = 0;
-                rc = ffs_wait_impl(b, &br, &bn);
-                if (rc != FFS_OK) return rc;
-                s->ovf.emplace_back();
-                OverflowFrame& o = s->ovf.back();
-                o.frame = f;
-                o.res = br[0];
-                o.boxes.assign(br[0].boxes, br[0].boxes + br[0].n_boxes);
-                if (br[0].reflections) o.refls.assign(br[0].reflections, br[0].reflections + br[0].n_reflections);
-                if (br[0].strong_k) {
-                    o.k.assign(br[0].strong_k, br[0].strong_k + br[0].num_strong_pixels);
-                    o.inten.assign(br[0].strong_intensity, br[0].strong_intensity + br[0].num_strong_pixels);
-                }
-                break;
-            }
-        }
-    }
-    uint64_t total_recs = 0;
-    uint32_t max_ns = 0;
-    for (uint32_t f = 0; f < n; ++f) {
-        total_recs += std::min<uint32_t>(h_nc[f], s->max_comp);  // (the kernels never write more than max_comp per frame)
-        max_ns = std::max(max_ns, std::min<uint32_t>(h_ns[f], s->cap));
-    }
     bool second_phase = false;
     if (total_recs > s->spec_recs_copied) {  // more records than the speculative copy brought: fetch the rest
         const size_t rb = sizeof(WireRec2);
@@ -484,7 +504,7 @@ int ffs_wait_impl(ffs_stream* s, const ffs_frame_result** results, uint32_t* n_r
     if (p.want_strong_mask) {
         second_phase = true;
         if (!s->h_mask)
-            HIP_TRY(c, hipHostMalloc(reinterpret_cast<void**>(&s->h_mask), B * (size_t)L.W * L.H, hipHostMallocDefault));
+            HIP_TRY(c, hipHostMalloc(reinterpret_cast<void**>(&s->h_mask), (size_t)s->max_batch * L.W * L.H, hipHostMallocDefault));
         // the reference's full-mask D2H (spotfinder.cc:887-894), all frames of the batch in one 2D copy
         HIP_TRY(c, hipMemcpy2DAsync(s->h_mask, L.W, s->d_sbytes, L.bpitch, L.W, (size_t)L.H * n,
                                     hipMemcpyDeviceToHost, s->st2));
@@ -499,16 +519,61 @@ int ffs_wait_impl(ffs_stream* s, const ffs_frame_result** results, uint32_t* n_r
     // batch that the last wait of a run pays on the clock)
     s->timing_last = last;
     s->timings_stale = true;
+    return FFS_OK;
+}
 
-    {
-        const int rc = assemble_batch(s, total_recs, &s->ovf, s->results, s->boxes, s->refls, s->centres);
+// ffs_wait, top to bottom: (1) join the compressed-input job, (2) take the result assembled ahead if there is one; otherwise (3) wait
+// for the batch's last event and read its status, (4) recover from an overflow, (5) issue the second-phase copies, (6) assemble.
+int ffs_wait_impl(ffs_stream* s, const ffs_frame_result** results, uint32_t* n_results) {
+    if (!s) return FFS_ERR_INVALID;
+    ffs_ctx* c = s->ctx;
+    if (!s->busy) {
+        c->err = "ffs_wait: nothing submitted";
+        return FFS_ERR_INVALID;
+    }
+    HIP_TRY(c, hipSetDevice(c->device));
+    int rc = join_compressed_job(s);
+    if (rc != FFS_OK) return rc;
+    if (!take_ahead_result(s)) {
+        // Step 3: behind the batch's last event its counters, flags and (speculatively copied or directly written) records are on the host.
+        HIP_TRY(c, hipEventSynchronize(s->ev[4]));
+        const uint32_t overflow = batch_overflow(s);
+        mark_idle(s);
+#ifdef FFS_EXPERIMENTS
+        sum_phase_times(s);
+#endif
+        s->ovf.clear();
+        // Step 4: a plan did not hold the batch.  The planes may hold bits of the abandoned launches and the status word is cleared
+        // before anything runs again; then the wait fails, or hands over to the wait of the batch's re-run (which counts in
+        // `reruns`), or runs the frames that did not fit again one by one and goes on with the batch as it is.
+        if (overflow) {
+            s->bits_dirty = true;
+            (void)hipMemsetAsync(s->d_overflow, 0, 4, s->st2);
+            (void)hipStreamSynchronize(s->st2);
+            const Recovery r = decide_recovery(s, overflow);
+            if (r.kind == Recovery::kFail) return FFS_ERR_INVALID;
+            if (r.kind == Recovery::kRerunBatch) return rerun_batch(s, r.how, results, n_results);
+            rc = rerun_overflow_frames(s);
+            if (rc != FFS_OK) return rc;
+        }
+        const size_t B = s->max_batch;
+        uint64_t total_recs = 0;
+        uint32_t max_ns = 0;
+        for (uint32_t f = 0; f < s->n_frames; ++f) {
+            total_recs += std::min<uint32_t>(s->h_counts[counts_comp_at(B) + f], s->max_comp);  // (the kernels never write more than max_comp per frame)
+            max_ns = std::max(max_ns, std::min<uint32_t>(s->h_counts[counts_strong_at(B) + f], s->cap));
+        }
+        rc = second_phase_copies(s, total_recs, max_ns);
+        if (rc != FFS_OK) return rc;
+        // Step 6: the wire records and summaries become the arrays the accessors hand out.
+        rc = assemble_batch(s, total_recs, &s->ovf, s->results, s->boxes, s->refls, s->centres);
         if (rc != FFS_OK) {
             c->err = "ffs_wait: the records of a frame do not match its summary counts";
             return rc;
         }
     }
     if (results) *results = s->results.data();
-    if (n_results) *n_results = n;
+    if (n_results) *n_results = s->n_frames;
     return FFS_OK;
 }
 
@@ -591,7 +656,7 @@ extern "C" int ffs_stream_debug_bitplane(ffs_stream* s, uint32_t frame, int whic
     }
     if (which == 0 && s->bits_cleared && !s->dense_valid) {
         // the compaction consumed (and cleared) the plane and nobody asked for the byte mask: the strong-pixel list has them
-        const uint32_t ns = std::min<uint32_t>(s->h_counts[frame], s->cap);
+        const uint32_t ns = std::min<uint32_t>(s->h_counts[counts_strong_at(s->max_batch) + frame], s->cap);
         std::vector<uint32_t> ks(ns);
         if (ns) HIP_TRY(c, hipMemcpy(ks.data(), s->d_list_k + (size_t)frame * s->cap, (size_t)ns * 4, hipMemcpyDeviceToHost));
         std::memset(host_out, 0, (size_t)L.W * L.H);

@@ -20,7 +20,7 @@
 //
 // Scope: batches whose strong pixels travel in wave logs and whose lists nobody reads (need_lists == 0, no byte mask) -- the hot
 // path's default.  A band the plan below cannot hold (more than kBandPx strong pixels, kBandEntries log entries, kBandCompStride
-// components; a seam row with more than kBandSeamCap strong pixels) raises flag 128: ffs_wait runs the batch again through
+// components; a seam row with more than kBandSeamCap strong pixels) raises kOvfBandPlan: ffs_wait runs the batch again through
 // k_frame_chain and the stream stays there for a while (dense data).
 #pragma once
 #include "kernels_chain.hpp"
@@ -89,7 +89,7 @@ __global__ __launch_bounds__(64) void k_band_cc(const BandArgs B) {
     const size_t slot = (size_t)frame * (size_t)gridDim.x + (size_t)blockIdx.x;
 
     FFS_STOP_AFTER(B.A, 10);   // (timing experiments: 10 = both kernels return at once, 11 = the merge does, 12 / 13 = the band wave after its entries / the placement)
-    if (lane == 0) s_flag = (rows > (uint32_t)kBandMaxRows || rows * l_ns > (uint32_t)kBandCw) ? 128u : 0u;   // (the host checks the geometry too)
+    if (lane == 0) s_flag = (rows > (uint32_t)kBandMaxRows || rows * l_ns > (uint32_t)kBandCw) ? kOvfBandPlan : 0u;   // (the host checks the geometry too)
     for (uint32_t i = lane; i < min(rows * l_ns, (uint32_t)kBandCw); i += 64) s_cw[i] = 0;
     for (uint32_t i = lane; i < kBandEntries; i += 64) s_par[i] = 0;   // (phase M's per-entry results)
     __syncthreads();
@@ -98,12 +98,12 @@ __global__ __launch_bounds__(64) void k_band_cc(const BandArgs B) {
     uint32_t cnt = 0;
     if ((uint32_t)lane < l_ns && rows != 0) {
         cnt = T.wlog_n[wave0 + (uint32_t)lane];
-        if (cnt > (uint32_t)kWlogCap) { atomicOr(&s_flag, 32u); cnt = (uint32_t)kWlogCap; }
+        if (cnt > (uint32_t)kWlogCap) { atomicOr(&s_flag, kOvfWaveLog); cnt = (uint32_t)kWlogCap; }
     }
     const uint32_t incl0 = wave_inclusive_scan(cnt);
     if (lane < 16) s_lst[lane] = incl0 - cnt;
     const uint32_t nb = (uint32_t)__builtin_amdgcn_readlane((int)incl0, 63);
-    if (nb > (uint32_t)kBandEntries) atomicOr(&s_flag, 128u);
+    if (nb > (uint32_t)kBandEntries) atomicOr(&s_flag, kOvfBandPlan);
     __syncthreads();
     uint32_t n = 0, ncomp = 0, n_top = 0, n_bot = 0;
     if (s_flag == 0 && nb != 0) {
@@ -164,7 +164,7 @@ __global__ __launch_bounds__(64) void k_band_cc(const BandArgs B) {
                     ++q;
                 }
             }
-            if (nm > (uint32_t)kBandItems) atomicOr(&s_flag, 128u);
+            if (nm > (uint32_t)kBandItems) atomicOr(&s_flag, kOvfBandPlan);
             if (nm != 0) {   // wave-uniform
                 __syncthreads();
                 for (uint32_t i = lane; i < min(nm, (uint32_t)kBandItems); i += 64) {
@@ -204,7 +204,7 @@ __global__ __launch_bounds__(64) void k_band_cc(const BandArgs B) {
             }
             if (lane == 0) { s_row[rows] = n; s_row[rows + 1] = n; }
         }
-        if (n > (uint32_t)kBandPx) atomicOr(&s_flag, 128u);
+        if (n > (uint32_t)kBandPx) atomicOr(&s_flag, kOvfBandPlan);
         __syncthreads();
 
         if (s_flag == 0 && n != 0) {
@@ -332,7 +332,7 @@ __global__ __launch_bounds__(64) void k_band_cc(const BandArgs B) {
                 const uint32_t i = i0 + k;
                 if (i < i1) s_id[i] = (uint16_t)s_par[s_id[i]];
             }
-            if (ncomp > (uint32_t)kBandCompStride) atomicOr(&s_flag, 128u);
+            if (ncomp > (uint32_t)kBandCompStride) atomicOr(&s_flag, kOvfBandPlan);
             __syncthreads();
 
             if (s_flag == 0) {
@@ -381,7 +381,7 @@ __global__ __launch_bounds__(64) void k_band_cc(const BandArgs B) {
                 // ---- the seams: the strong pixels of the band's first and last row, with their component ----------------------------
                 n_top = s_row[1] - s_row[0];
                 n_bot = s_row[rows] - s_row[rows - 1];
-                if (n_top > (uint32_t)kBandSeamCap || n_bot > (uint32_t)kBandSeamCap) atomicOr(&s_flag, 128u);
+                if (n_top > (uint32_t)kBandSeamCap || n_bot > (uint32_t)kBandSeamCap) atomicOr(&s_flag, kOvfBandPlan);
                 uint32_t* seam = B.seam + slot * 2 * kBandSeamCap;
                 for (uint32_t j = lane; j < min(n_top, (uint32_t)kBandSeamCap); j += 64) seam[j] = (uint32_t)s_x[j] | ((uint32_t)s_id[j] << 16);
                 const uint32_t bb = s_row[rows - 1];
@@ -407,7 +407,7 @@ __global__ __launch_bounds__(kMergeThreads) void k_frame_merge(const BandArgs B)
     __shared__ uint16_t s_l2id[kMergeCap];          // label -> band component (the root with that label)
     __shared__ uint32_t s_touched[kMergeCap / 32];  // roots that members were folded into (their accumulators were changed by atomics)
     __shared__ uint32_t s_wave[kMergeThreads / 64];
-    __shared__ uint32_t s_sm[8];
+    __shared__ uint32_t s_sm[kSummaryWords];
     __shared__ uint32_t s_tot[2];   // strong pixels, flags
     __shared__ __align__(16) uint32_t s_out[kMergeLabels * kMergeThreads * (sizeof(WireRec2) / 4)];
     __shared__ __align__(16) uint32_t s_seam[kMergeMaxBands * 2 * kMergeSeamLds];   // the first pixels of every seam row (first row, last row per band)
@@ -423,7 +423,7 @@ __global__ __launch_bounds__(kMergeThreads) void k_frame_merge(const BandArgs B)
     FFS_STOP_AFTER(A, 11);
     FFS_STOP_AFTER(A, 12);
     FFS_STOP_AFTER(A, 13);
-    if (tid < 8) s_sm[tid] = 0;
+    if (tid < kSummaryWords) s_sm[tid] = 0;
     if (tid < 2) s_tot[tid] = 0;
     for (int i = tid; i < kMergeCap / 32; i += kMergeThreads) s_touched[i] = 0;
     __syncthreads();
@@ -443,7 +443,7 @@ __global__ __launch_bounds__(kMergeThreads) void k_frame_merge(const BandArgs B)
     __syncthreads();
     const uint32_t total = s_tot[0];
     uint32_t flags = s_tot[1];
-    if (NB > (uint32_t)kMergeCap) flags |= 128u;
+    if (NB > (uint32_t)kMergeCap) flags |= kOvfBandPlan;
     FFS_PHASE_TS(A, 1);
     uint32_t before = 0;
 
@@ -570,21 +570,7 @@ __global__ __launch_bounds__(kMergeThreads) void k_frame_merge(const BandArgs B)
     __syncthreads();
     FFS_PHASE_TS(A, 5);
     FFS_PHASE_TS(A, 6);
-    if (tid == 0) {
-        uint32_t fl = *a.overflow | flags;
-        if (total > a.cap) fl |= 1u;
-        if (before > sa.max_comp) fl |= 2u;
-        a.num_strong[frame] = total;
-        a.n_comp[frame] = before;
-        const size_t Bn = A.max_batch;
-        A.h_counts[frame] = total;
-        A.h_counts[Bn + frame] = before;
-        A.h_counts[10 * Bn + 1 + frame] = fl;
-    }
-    if (tid < 8) {
-        a.summary[(uint64_t)frame * 8 + tid] = s_sm[tid];
-        A.h_counts[2 * (size_t)A.max_batch + (size_t)frame * 8 + tid] = s_sm[tid];
-    }
+    publish_frame_counters(A, frame, tid, total, before, flags, s_sm);
 }
 
 }  // namespace ffsamd

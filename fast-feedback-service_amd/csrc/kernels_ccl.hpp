@@ -178,11 +178,11 @@ __global__ __launch_bounds__(64) void k_emit_list_w(const CclArgs a) {
         const uint32_t total = tile_base + count;
         a.num_strong[frame] = total;
         (a.row_off + (uint64_t)frame * (a.H + 1))[a.H] = min(total, a.cap);
-        if (total > a.cap) atomicOr(a.overflow, 1u);
+        if (total > a.cap) atomicOr(a.overflow, kOvfStrongCap);
     }
     if (tile == 0 && a.acc2) {  // counters the root-indexed reduction adds into
         if (lane == 0) a.n_comp[frame] = 0;
-        if (lane < 8) a.summary[(uint64_t)frame * 8 + lane] = 0;
+        if (lane < kSummaryWords) a.summary[(uint64_t)frame * kSummaryWords + lane] = 0;
     }
     emit_tile_w<PixelT>(a, frame, tile, tile_base, count, wv, s_g, s_w, s_rows, lane);
 }
@@ -316,12 +316,12 @@ __global__ __launch_bounds__(256) void k_finalize_roots(const SegArgs a) {
     const uint32_t* parent = a.parent + (uint64_t)seg * a.seg_stride;
     const CompAcc2* acc = a.acc2 + (uint64_t)seg * a.seg_stride;
     const uint32_t* croots = a.chunk_roots + (uint64_t)seg * a.chunks_max;
-    uint32_t* sm = a.summary + (uint64_t)seg * 8;
+    uint32_t* sm = a.summary + (uint64_t)seg * kSummaryWords;
     if (tid == 0) {
         uint32_t b = 0;
         for (int q = 0; q < seg; ++q) b += min(a.n_comp[q], a.max_comp);
         s_base = b;
-        if (blockIdx.x == 0 && a.n_comp[seg] > a.max_comp) atomicOr(a.overflow, 2u);
+        if (blockIdx.x == 0 && a.n_comp[seg] > a.max_comp) atomicOr(a.overflow, kOvfCompCap);
     }
     for (uint32_t c = blockIdx.x; c < chunks; c += gridDim.x) {
         {   // roots in the chunks before this one
@@ -366,8 +366,8 @@ __global__ __launch_bounds__(256) void k_finalize_roots(const SegArgs a) {
             const float pcd = (float)__builtin_sqrt((double)s2);
             uint32_t flags = 0;
             // filter_reflections(): size first, then separation (connected_components.cc:207-236)
-            if (a.min_spot_size > 0 && r.num_pixels < a.min_spot_size) flags |= 1u;
-            else if (a.max_sep > 0.0f && pcd > a.max_sep) flags |= 2u;
+            if (a.min_spot_size > 0 && r.num_pixels < a.min_spot_size) flags |= kRecTooSmall;
+            else if (a.max_sep > 0.0f && pcd > a.max_sep) flags |= kRecTooSpread;
             WireRec2 o;
             o.x_min = (uint16_t)r.x_min; o.x_max = (uint16_t)r.x_max; o.y_min = (uint16_t)r.y_min; o.y_max = (uint16_t)r.y_max;
             o.npx_flags = r.num_pixels | (flags << 30);
@@ -379,12 +379,12 @@ __global__ __launch_bounds__(256) void k_finalize_roots(const SegArgs a) {
             *reinterpret_cast<WireRec2*>(&s_out[slot * (sizeof(WireRec2) / 4)]) = o;
             // generate_boxes() filter (connected_components.cc:122-138)
             if (a.min_spot_size == 0 || r.num_pixels >= a.min_spot_size) {
-                atomicAdd(&sm[0], 1u);
-                atomicAdd(&sm[1], r.num_pixels);
+                atomicAdd(&sm[kSumBoxes], 1u);
+                atomicAdd(&sm[kSumStrongFiltered], r.num_pixels);
             }
-            if (flags == 0) atomicAdd(&sm[2], 1u);
-            if (flags & 1u) atomicAdd(&sm[3], 1u);
-            if (flags & 2u) atomicAdd(&sm[4], 1u);
+            if (flags == 0) atomicAdd(&sm[kSumReflections], 1u);
+            if (flags & kRecTooSmall) atomicAdd(&sm[kSumFilteredSize], 1u);
+            if (flags & kRecTooSpread) atomicAdd(&sm[kSumFilteredSep], 1u);
         }
         __syncthreads();
         {

@@ -91,7 +91,7 @@ static_assert(kChainMaxRows < 8192, "run descriptor");
 struct ChainArgs {
     CclArgs c;
     SegArgs s;
-    uint32_t* h_counts;     // pinned host block (device address): [B] strong pixels, [B] components, [B][8] summary, [1] unused, [B] flags
+    uint32_t* h_counts;     // the stream's pinned counter block (device address; layout: ffs_device.h, counts_*_at): this launch writes all but its status word
     uint32_t max_batch;     // B
     uint32_t rec_stride;    // records between the frames' record areas (= max_comp)
     ThresholdArgs t;        // for the bright-window fix-up (fix_bright != 0): what k_bright_fix does, by this launch
@@ -101,6 +101,29 @@ struct ChainArgs {
     int runs_ok;            // 1: frames beyond kChainLdsEntries strong pixels take the run-based phases (16-bit pixels, W <= kChainRunMaxW); 2: every frame
     unsigned long long* phase_ts;   // (timing experiments) [frames][8] device timestamps at the phase boundaries, or null
 };
+
+// The tail of the one-launch sparse stages (k_frame_chain, k_frame_merge), after a __syncthreads(): a frame's counters to the device
+// block (for the other consumers of the lists) and to the pinned host block, with the frame's flag word, for ffs_wait().
+// `raised`: what the launch itself raised for the frame; the status word holds what the dense stages did (corrupt chunk, bright list).
+__device__ __forceinline__ void publish_frame_counters(const ChainArgs& A, int frame, int tid, uint32_t total, uint32_t comps, uint32_t raised,
+                                                       const uint32_t* s_sm) {
+    const CclArgs& a = A.c;
+    if (tid == 0) {
+        uint32_t flags = *a.overflow | raised;
+        if (total > a.cap) flags |= kOvfStrongCap;
+        if (comps > A.s.max_comp) flags |= kOvfCompCap;
+        a.num_strong[frame] = total;
+        a.n_comp[frame] = comps;
+        const size_t B = A.max_batch;   // (read inside each branch, as the kernels did: hoisted, their register allocation moves)
+        A.h_counts[counts_strong_at(B) + frame] = total;
+        A.h_counts[counts_comp_at(B) + frame] = comps;
+        A.h_counts[counts_frame_flags_at(B) + frame] = flags;
+    }
+    if (tid < kSummaryWords) {
+        a.summary[(uint64_t)frame * kSummaryWords + tid] = s_sm[tid];
+        A.h_counts[counts_summary_at(A.max_batch) + (size_t)frame * kSummaryWords + tid] = s_sm[tid];
+    }
+}
 
 __device__ __forceinline__ void chain_record(const SegArgs& sa, uint32_t W, uint32_t num_pixels, unsigned long long sum_i,
                                              unsigned long long sum_xi, unsigned long long sum_yi, uint32_t x_min, uint32_t x_max,
@@ -120,8 +143,8 @@ __device__ __forceinline__ void chain_record(const SegArgs& sa, uint32_t W, uint
     const float pcd = (float)__builtin_sqrt((double)s2);
     uint32_t flags = 0;
     // filter_reflections(): size first, then separation (connected_components.cc:207-236)
-    if (sa.min_spot_size > 0 && num_pixels < sa.min_spot_size) flags |= 1u;
-    else if (sa.max_sep > 0.0f && pcd > sa.max_sep) flags |= 2u;
+    if (sa.min_spot_size > 0 && num_pixels < sa.min_spot_size) flags |= kRecTooSmall;
+    else if (sa.max_sep > 0.0f && pcd > sa.max_sep) flags |= kRecTooSpread;
     o.x_min = (uint16_t)x_min; o.x_max = (uint16_t)x_max; o.y_min = (uint16_t)y_min; o.y_max = (uint16_t)y_max;
     o.npx_flags = num_pixels | (flags << 30);
     o.com_x = com_x; o.com_y = com_y;
@@ -131,12 +154,12 @@ __device__ __forceinline__ void chain_record(const SegArgs& sa, uint32_t W, uint
     o.sum_intensity = sum_i;
     // generate_boxes() filter (connected_components.cc:122-138)
     if (sa.min_spot_size == 0 || num_pixels >= sa.min_spot_size) {
-        atomicAdd(&s_sm[0], 1u);
-        atomicAdd(&s_sm[1], num_pixels);
+        atomicAdd(&s_sm[kSumBoxes], 1u);
+        atomicAdd(&s_sm[kSumStrongFiltered], num_pixels);
     }
-    if (flags == 0) atomicAdd(&s_sm[2], 1u);
-    if (flags & 1u) atomicAdd(&s_sm[3], 1u);
-    if (flags & 2u) atomicAdd(&s_sm[4], 1u);
+    if (flags == 0) atomicAdd(&s_sm[kSumReflections], 1u);
+    if (flags & kRecTooSmall) atomicAdd(&s_sm[kSumFilteredSize], 1u);
+    if (flags & kRecTooSpread) atomicAdd(&s_sm[kSumFilteredSep], 1u);
 }
 
 // RUNS: the instantiation that also holds the run-based phases for frames beyond kChainLdsEntries strong pixels (launched when
@@ -154,7 +177,7 @@ __global__ __launch_bounds__(kChainThreads) void k_frame_chain(const ChainArgs A
     uint8_t* s_big = reinterpret_cast<uint8_t*>(s_row + (kChainMaxRows + 1));
     __shared__ uint32_t s_wave[kChainWaves];
     __shared__ uint32_t s_wrun[kChainWaves];   // runs listed by each wave (run-based phases)
-    __shared__ uint32_t s_sm[8];
+    __shared__ uint32_t s_sm[kSummaryWords];
     __shared__ uint32_t s_flag;   // flags raised by any thread of the block (LOG)
     __shared__ uint32_t s_nmaybe;   // LOG: undecided pixels listed
     __shared__ uint32_t s_lst[kChainWaves][16];   // LOG: per chain wave, where each strip's entries start in the band's row of entries
@@ -191,7 +214,7 @@ __global__ __launch_bounds__(kChainThreads) void k_frame_chain(const ChainArgs A
             // the last workgroup through with the list empties it for the next batch (the host re-runs a batch whose list overflowed)
             const uint32_t before_me = atomicAdd(A.fix_done, 1u);
             if (before_me + 1 == gridDim.x) {
-                if (listed > t.bright_cap) bright_flag = 8u;
+                if (listed > t.bright_cap) bright_flag = kOvfBrightList;
                 *t.bright_n = 0;
                 *A.fix_done = 0;
             }
@@ -213,7 +236,7 @@ __global__ __launch_bounds__(kChainThreads) void k_frame_chain(const ChainArgs A
             if (frame == 0 && sa.zero_word && !A.fix_bright) *sa.zero_word = 0;
         }
     }
-    if (tid < 8) s_sm[tid] = 0;
+    if (tid < kSummaryWords) s_sm[tid] = 0;
     if (tid == 0) { s_flag = 0; s_nmaybe = 0; }
     if (tid < kChainWaves) s_wrun[tid] = 0;
     for (int y = tid; y <= a.H; y += kChainThreads) s_row[y] = 0;
@@ -222,7 +245,7 @@ __global__ __launch_bounds__(kChainThreads) void k_frame_chain(const ChainArgs A
     bool in_lds = n <= (uint32_t)kChainLdsEntries;
     // denser: runs instead of pixels where the frame allows it (block-uniform)
     const bool runs = !LOG && RUNS && sizeof(PixelT) == 2 && A.runs_ok != 0 && (!in_lds || A.runs_ok == 2);
-    uint32_t run_flag = 0;   // 16: more runs than the LDS plan holds; 32: a wave log (or the list of undecided pixels) overflowed; 64: a frame beyond
+    uint32_t run_flag = 0;   // kOvfRuns: more runs than the LDS plan holds; kOvfWaveLog: a wave log (or the list of undecided pixels) overflowed; kOvfLdsForest: a frame beyond
                              // the LDS forest met in the wave logs (the host runs the batch again another way)
     FFS_STOP_AFTER(A, 1);
     FFS_PHASE_TS(A, 1);
@@ -262,7 +285,7 @@ __global__ __launch_bounds__(kChainThreads) void k_frame_chain(const ChainArgs A
         uint32_t c = 0;
         if ((uint32_t)lane < l_ns) {
             c = T.wlog_n[log_wave(band, (uint32_t)lane)];
-            if (c > (uint32_t)kWlogCap) { atomicOr(&s_flag, 32u); c = (uint32_t)kWlogCap; }   // (a wave wanted more than its log holds)
+            if (c > (uint32_t)kWlogCap) { atomicOr(&s_flag, kOvfWaveLog); c = (uint32_t)kWlogCap; }   // (a wave wanted more than its log holds)
         }
         const uint32_t incl = wave_inclusive_scan(c);
         __builtin_amdgcn_wave_barrier();
@@ -335,7 +358,7 @@ __global__ __launch_bounds__(kChainThreads) void k_frame_chain(const ChainArgs A
         __syncthreads();
         {
             const uint32_t nm = s_nmaybe;
-            if (nm > kMaybeCap && tid == 0) atomicOr(&s_flag, 32u);
+            if (nm > kMaybeCap && tid == 0) atomicOr(&s_flag, kOvfWaveLog);
             for (uint32_t i = tid; i < min(nm, kMaybeCap); i += kChainThreads) {
                 const uint32_t it = s_maybe[i];
                 uint2* ent = T.wlog + (uint64_t)log_wave((int)(it >> 16), (it >> 12) & 15u) * kWlogCap + ((it >> 3) & 0x1FFu);
@@ -643,9 +666,9 @@ __global__ __launch_bounds__(kChainThreads) void k_frame_chain(const ChainArgs A
     if constexpr (LOG) {
         // ---- L2: the list in raster order.  Per band (one chain wave each): pixels per (row, strip) -> where each strip's part
         // of each row starts -> every entry's pixels placed (a segmented scan over the 64 entries of a chunk of a log).  The
-        // column numbers go straight into LDS (phase X has nothing left to do).  Frames beyond the LDS forest: flag 32.
+        // column numbers go straight into LDS (phase X has nothing left to do).  Frames beyond the LDS forest: kOvfLdsForest.
         run_flag |= s_flag;
-        if (!in_lds) run_flag |= 64u;   // (a frame beyond the LDS forest: this batch again through the plane; logs again when the data is sparse again)
+        if (!in_lds) run_flag |= kOvfLdsForest;   // (a frame beyond the LDS forest: this batch again through the plane; logs again when the data is sparse again)
         if (run_flag == 0 && total != 0) {
             constexpr int kMaxStrips = 16;
             uint16_t* s_x = reinterpret_cast<uint16_t*>(s_dyn + kChainStageOff);
@@ -959,7 +982,7 @@ __global__ __launch_bounds__(kChainThreads) void k_frame_chain(const ChainArgs A
         const uint32_t nr = s_row[a.H];
         uint32_t* s_rd = spar + kChainRunCap;   // descriptors: y << 19 | x0 << 5 | (len - 1)
         if (nr > (uint32_t)kChainRunCap) {
-            run_flag = 16u;
+            run_flag = kOvfRuns;
         } else {
             // ---- X': descriptors into LDS in list order (wave after wave), the forest's singletons, the pixel values
             {
@@ -1195,22 +1218,8 @@ __global__ __launch_bounds__(kChainThreads) void k_frame_chain(const ChainArgs A
 
     // ---- counters: device copies for the other consumers of the lists, host copies for ffs_wait() --------------
     __syncthreads();
-    if (tid == 0) {
-        uint32_t flags = *a.overflow | bright_flag | run_flag;   // what the dense stages raised (corrupt chunk; bright-list overflow)
-        if (total > a.cap) flags |= 1u;
-        if (before > sa.max_comp) flags |= 2u;
-        a.num_strong[frame] = total;
-        a.n_comp[frame] = before;
-        const size_t B = A.max_batch;
-        FFS_PHASE_TS(A, 6);
-        A.h_counts[frame] = total;
-        A.h_counts[B + frame] = before;
-        A.h_counts[10 * B + 1 + frame] = flags;
-    }
-    if (tid < 8) {
-        a.summary[(uint64_t)frame * 8 + tid] = s_sm[tid];
-        A.h_counts[2 * (size_t)A.max_batch + (size_t)frame * 8 + tid] = s_sm[tid];
-    }
+    FFS_PHASE_TS(A, 6);
+    publish_frame_counters(A, frame, tid, total, before, bright_flag | run_flag, s_sm);
 }
 template __global__ void k_frame_chain<uint16_t, false>(const ChainArgs);
 template __global__ void k_frame_chain<uint16_t, true>(const ChainArgs);

@@ -43,7 +43,7 @@ struct DecodeArgs {
     uint32_t block_elems;       // elements per full block
     uint32_t last_block_elems;  // elements in the last LZ4 block (multiple of 8)
     uint32_t tail_elems;        // raw leftover elements (< 8)
-    uint32_t* error;            // |= 4 on a malformed chunk
+    uint32_t* error;            // the stream's status word: kOvfCorruptLz4 on a malformed chunk
 };
 
 // 8 bytes of LDS starting at byte `pos`, wave-uniform (in scalar registers)
@@ -129,7 +129,7 @@ __global__ __launch_bounds__(64) void k_bshuf_lz4_decode(const DecodeArgs a) {
     if (blk == a.blocks_per_frame) {
         // raw tail: fewer than 8 elements, copied as they are
         if (a.tail_elems == 0) return;
-        if (clen != a.tail_elems * ES) { if (lane == 0) atomicOr(a.error, 4u); return; }
+        if (clen != a.tail_elems * ES) { if (lane == 0) atomicOr(a.error, kOvfCorruptLz4); return; }
         if (lane < (int)a.tail_elems) {
             uint32_t v = 0;
             for (int k = 0; k < ES; ++k) v |= (uint32_t)a.comp[(uint64_t)off + (uint32_t)lane * ES + k] << (8 * k);
@@ -220,7 +220,7 @@ __global__ __launch_bounds__(64) void k_bshuf_lz4_decode(const DecodeArgs a) {
     if (op != out_bytes) bad = true;
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_s_waitcnt(0);
-    if (bad && lane == 0) atomicOr(a.error, 4u);
+    if (bad && lane == 0) atomicOr(a.error, kOvfCorruptLz4);
 
     // ---- 3. bit-unshuffle: lane g rebuilds elements 8g .. 8g+7 from byte g of every plane and stores them
     const uint32_t row_bytes = n_elems / 8;  // bytes per plane

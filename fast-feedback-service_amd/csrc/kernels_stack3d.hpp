@@ -158,13 +158,13 @@ __global__ __launch_bounds__(256) void k_finalize_roots3d(const SegArgs a) {
             o.peak_centroid_distance = (float)__builtin_sqrt((double)s2);
             uint32_t flags = 0;
             // filter_reflections(): size first, then separation (connected_components.cc:207-236)
-            if (a.min_spot_size > 0 && r.num_pixels < a.min_spot_size) flags |= 1u;
-            else if (a.max_sep > 0.0f && o.peak_centroid_distance > a.max_sep) flags |= 2u;
+            if (a.min_spot_size > 0 && r.num_pixels < a.min_spot_size) flags |= kRecTooSmall;
+            else if (a.max_sep > 0.0f && o.peak_centroid_distance > a.max_sep) flags |= kRecTooSpread;
             o.flags = flags;
             recs[cidx] = o;
-            if (flags == 0) atomicAdd(&sm[2], 1u);
-            if (flags & 1u) atomicAdd(&sm[3], 1u);
-            if (flags & 2u) atomicAdd(&sm[4], 1u);
+            if (flags == 0) atomicAdd(&sm[kSumReflections], 1u);
+            if (flags & kRecTooSmall) atomicAdd(&sm[kSumFilteredSize], 1u);
+            if (flags & kRecTooSpread) atomicAdd(&sm[kSumFilteredSep], 1u);
         }
         __syncthreads();
     }
