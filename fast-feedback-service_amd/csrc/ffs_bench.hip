@@ -24,7 +24,8 @@ extern "C" int ffs_bench_threshold(ffs_stream* s, const void* device_pixels, siz
         if (rc != FFS_OK) return rc;
     }
     s->ext_e_clean = false;
-    ThresholdArgs ta = make_threshold_args(s, device_pixels, pitch, fstride, n_frames, Rerun{});
+    const StreamGeometry geo = batch_stream_geometry(s, fstride, n_frames);
+    ThresholdArgs ta = make_threshold_args(s, device_pixels, pitch, fstride, n_frames, geo, Rerun{});
     if (!ext && !win_default(c->params) && !window_kernel_for(s, ta)) {
         // (threshold_path 2 at another window: the batch has no dense kernel, k_exact_w gathers every pixel -- nothing here to time)
         c->err = "ffs_bench_threshold: threshold_path 2 with a window other than 3,3 has no dense kernel to time";
@@ -32,7 +33,7 @@ extern "C" int ffs_bench_threshold(ffs_stream* s, const void* device_pixels, siz
     }
     const bool e_sparse = ext && ext_sparse_erode(c->tune);   // (the hot path clears the signal-region plane behind the previous batch)
     ta.eplane_clean = e_sparse ? 1 : 0;
-    if (!ext) (void)wave_logs_for(s, ta, n_frames, Rerun{});   // (the kernel as the hot path launches it)
+    if (!ext) (void)wave_logs_for(s, ta, geo, Rerun{});   // (the kernel as the hot path launches it)
     const Layout& L = c->L;
     std::vector<hipEvent_t> ev(4 * (size_t)iters, nullptr);
     auto cleanup = [&]() { for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e); };
@@ -51,7 +52,7 @@ extern "C" int ffs_bench_threshold(ffs_stream* s, const void* device_pixels, siz
         if (err == hipSuccess) err = hipMemsetAsync(s->d_occ, 0, (size_t)s->max_batch * occ_frame_words(L) * 4, s->st);
         if (err == hipSuccess && e_sparse) err = hipMemsetAsync(s->d_eplane, 0, (size_t)s->max_batch * L.plane_frame_stride, s->st);
         if (err != hipSuccess) break;
-        launch_dense_kernel(s, ta, n_frames, ev[4 * i], ev[4 * i + 1]);
+        launch_dense_kernel(s, ta, geo, n_frames, ev[4 * i], ev[4 * i + 1]);
         err = hipEventRecord(ev[4 * i + 2], s->st);
         launch_dense_rest(s, ta, n_frames);
         if (err == hipSuccess) err = hipEventRecord(ev[4 * i + 3], s->st);

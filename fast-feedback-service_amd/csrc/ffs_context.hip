@@ -158,16 +158,8 @@ extern "C" int ffs_ctx_create(int device, uint32_t width, uint32_t height, int p
 #endif
     c->pixel_bytes = pixel_bytes;
     c->max_batch = max_batch;
-    Layout& L = c->L;
-    L.W = (int)width;
-    L.H = (int)height;
-    L.pitch_px = round_up((int)width, 128);  // byte-mask rows start on 128-byte lines
-    L.pitch = (uint32_t)L.pitch_px * (uint32_t)pixel_bytes;
-    L.mpitch = (uint32_t)L.pitch_px / 8;
-    L.bpitch = (uint32_t)L.pitch_px;
-    L.frame_stride = (uint64_t)L.pitch * height;
-    L.plane_frame_stride = (uint64_t)L.mpitch * height;
-    L.bytes_frame_stride = (uint64_t)L.bpitch * height;
+    c->L = default_layout(width, height, pixel_bytes);
+    const Layout& L = c->L;
     if (L.frame_stride >= (1ull << 32)) {
         g_create_error = "frame larger than 4 GiB";
         delete c;
@@ -186,7 +178,7 @@ extern "C" int ffs_ctx_create(int device, uint32_t width, uint32_t height, int p
     }
     hipError_t e = hipMalloc(&c->d_maskbits, L.plane_frame_stride + 256);
     // one dword per lane group of 16 bytes of pixels: 8 pixels (16-bit) or 4 pixels (32-bit)
-    if (e == hipSuccess) e = hipMalloc(&c->d_ginfo, (size_t)(L.H + kInfoExtraRows) * ((size_t)L.pitch_px * pixel_bytes / 4) + 256);
+    if (e == hipSuccess) e = hipMalloc(&c->d_ginfo, (size_t)(L.H + kInfoExtraRows) * ginfo_pitch(L, pixel_bytes) + 256);
     if (e == hipSuccess) e = hipMalloc(&c->d_mmap, (size_t)L.H * L.pitch_px + 256);
     if (e != hipSuccess) {
         g_create_error = std::string("hipMalloc(mask): ") + hipGetErrorString(e);
@@ -332,7 +324,7 @@ static void ctx_destroy_internal(ffs_ctx* c) {
 // The tables of the one-kernel threshold path depend on the mask alone: rebuilt whenever it changes.
 static int rebuild_mask_tables(ffs_ctx* c) {
     const Layout& L = c->L;
-    const uint32_t gpitch = (uint32_t)L.pitch_px * (uint32_t)c->pixel_bytes / 4;
+    const uint32_t gpitch = ginfo_pitch(L, c->pixel_bytes);
     HIP_TRY(c, hipMemset(c->d_ginfo, 0, (size_t)(L.H + kInfoExtraRows) * gpitch));
     const int groups = L.pitch_px / (c->pixel_bytes == 2 ? 8 : 4);
     (void)hipGetLastError();  // drop any stale error state: the check below is for this launch
@@ -435,7 +427,7 @@ extern "C" int ffs_ctx_device_layout(const ffs_ctx* c, size_t* pitch, size_t* fs
     return FFS_OK;
 }
 
-// ---- tuning (ffs_internal.hpp: Tuning) -------------------------------------------------------------------------
+// ---- tuning (tuning.hpp: Tuning) -----------------------------------------------------------------------------------
 extern "C" int ffs_ctx_set_tuning(ffs_ctx* c, const char* key, long long value) {
     if (!c || !key) return FFS_ERR_INVALID;
     Tuning& t = c->tune;

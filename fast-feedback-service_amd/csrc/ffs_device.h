@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "launch_geometry.hpp"
+
 // Timing experiments (phases switched off, kernels stopped half way: results are wrong when used) exist only in builds
 // with -DFFS_EXPERIMENTS (make experiments -> libffs_hip_exp.so, for tools/); the product library has none of them.
 #ifdef FFS_EXPERIMENTS
@@ -18,35 +20,8 @@
 
 namespace ffsamd {
 
-// ---- frame layout in HBM ---------------------------------------------------------------------
-// Pixels:      [frame][y][pitch_px] of PixelT, rows `pitch` bytes apart (multiple of 128 B).
-// Bit planes:  [frame][y][mpitch] bytes, 1 bit per pixel, LSB first (bit x&7 of byte x>>3);
-//              bits for x >= W are always 0.  Used for: valid-pixel mask (one plane per
-//              context, frame-invariant), candidate plane, strong plane (candidate plane
-//              filtered in place).
-// Byte mask:   [frame][y][bpitch] bytes 0/1 -- the reference kernel's result_strong layout
-//              (spotfinder/kernels/thresholding.cu:233), kept as the drop-in contract.
-struct Layout {
-    int W, H;
-    int pitch_px;        // multiple of 64, >= W
-    uint32_t pitch;      // bytes per pixel row (default layout)
-    uint32_t mpitch;     // bytes per bit-plane row  = pitch_px / 8
-    uint32_t bpitch;     // bytes per byte-mask row  = pitch_px
-    uint64_t frame_stride;       // bytes between frames (default layout)
-    uint64_t plane_frame_stride; // bytes between frames of a bit plane = H * mpitch
-    uint64_t bytes_frame_stride; // bytes between frames of the byte mask = H * bpitch
-};
-
-// ---- streaming threshold kernels: geometry (kernels_stream.hpp) ---------------------------------------
-// One wave64 marches down a column strip; a lane holds 16 bytes of a pixel row (8 pixels of 16 bits, 4 of 32).
-// Lanes 0 and 63 are halo (their windows are incomplete), lanes 1..62 own output.
-constexpr int kSOwned = 62;
-// first row of band b for a (split, rows, rows2) geometry -- see ThresholdArgs::band_split
-__host__ __device__ inline int band_first_row(int band, int band_rows, int band_rows2, int band_split) {
-    return band < band_split ? band * band_rows : band_split * band_rows + (band - band_split) * band_rows2;
-}
-// General-window kernel (kernels_window.hpp): a lane holds one eight-pixel group (16 / 32 bytes) of a row; lanes 1..62 own output
-constexpr int kWinOwned = 62;
+// The frame layout in HBM (Layout), the geometry constants of the kernels (kSOwned, kWinOwned, ...) and the unit map as plain integers
+// (band_first_row, stream_unit_of, log_slot_of) are in launch_geometry.hpp, which has no HIP in it.
 constexpr int kInfoExtraRows = 3;    // ginfo row y carries the mask bits of row y and the window counts of row y - 3
 
 // Exact-stage tiles: one 256-thread workgroup per 8 rows.
@@ -129,22 +104,15 @@ struct ThresholdArgs {
     float w_kS, w_kB;          // its float32 screens: nsig_s^2 (1 - 2^-16), nsig_b^2 (1 - 2^-16); 0 = screen off
 };
 
-// The streaming launch's units.  A unit = one wave = one band of one strip; units are numbered band after band (u = band * n_strips +
-// strip) and dealt to the eight XCDs in eight contiguous chunks (workgroup b runs on XCD b % 8): the strips of a band -- neighbours that
-// share halo columns and, frame after frame, the same rows of the mask tables -- share an L2, and ANY number of bands is balanced over
-// the XCDs.  (Rounds 1-5 dealt the bands round-robin, band = xcd + 8 k, which wanted a multiple of eight bands; the chunks measure
-// 0.5-1 % faster on the same box, profiles/r06e_map_variants.log.)
-__host__ __device__ inline uint32_t stream_units(const ThresholdArgs& a) { return (uint32_t)a.n_bands * (uint32_t)a.n_strips; }
-__host__ __device__ inline uint32_t stream_chunk(const ThresholdArgs& a) { return (stream_units(a) + 7u) / 8u; }   // units per XCD; grid.x = 8 chunks
+// The streaming launch's units (launch_geometry.hpp has the map: stream_unit_of, log_slot_of), for the arguments of a launch
+__host__ __device__ inline uint32_t stream_units(const ThresholdArgs& a) { return stream_units_of(a.n_bands, a.n_strips); }
+__host__ __device__ inline uint32_t stream_chunk(const ThresholdArgs& a) { return stream_chunk_of(a.n_bands, a.n_strips); }   // units per XCD; grid.x = 8 chunks
 __device__ __forceinline__ bool stream_unit(const ThresholdArgs& a, uint32_t bid, int& strip, int& band) {
-    const uint32_t u = (bid & 7u) * stream_chunk(a) + (bid >> 3);
-    band = (int)(u / (uint32_t)a.n_strips);
-    strip = (int)(u - (uint32_t)band * (uint32_t)a.n_strips);
-    return u < stream_units(a);
+    return stream_unit_of(bid, a.n_bands, a.n_strips, strip, band);
 }
-// where the log of (super row y, band, strip) lies in wlog / wlog_n / wpix: the strips of a band side by side
+// where the log of (super row y, band, strip) lies in wlog / wlog_n / wpix
 __host__ __device__ inline uint32_t log_slot(const ThresholdArgs& a, uint32_t y, uint32_t band, uint32_t strip) {
-    return (y * (uint32_t)a.n_bands + band) * (uint32_t)a.n_strips + strip;
+    return log_slot_of(a.n_bands, a.n_strips, y, band, strip);
 }
 
 // ---- what a batch tells the host when a plan did not hold it: the overflow flags -----------------------------------------

@@ -1,6 +1,6 @@
-// ffs_submit.hip -- everything that puts a batch on the device: launch geometry, the launches of the threshold stage
-// and of the sparse stage (compaction -> connected components -> records), the submit entry points and compressed
-// input.  All kernels of the hot path are included here and nowhere else (see ffs_internal.hpp).
+// ffs_submit.hip -- everything that puts a batch on the device: the threshold stage's arguments (their launch geometry comes from
+// launch_geometry.hpp), the launches of the threshold stage and of the sparse stage (compaction -> connected components -> records),
+// the submit entry points and compressed input.  All kernels of the hot path are included here and nowhere else (see ffs_internal.hpp).
 //
 // Reference: the per-frame section of spotfinder/spotfinder.cc:751-1008 (H2D, kernel launch wrapper
 // spotfinder/spotfinder.cu:148-189, D2H of the mask, host connected components).
@@ -24,11 +24,11 @@ bool chain_prepare_device() {   // more than 64 KB of dynamic LDS has to be aske
     return e1 == hipSuccess && e2 == hipSuccess && e3 == hipSuccess && e4 == hipSuccess && e5 == hipSuccess;
 }
 
-ThresholdArgs make_threshold_args(ffs_stream* s, const void* img, size_t pitch, size_t fstride, uint32_t n_frames, const Rerun& how) {
+// ---- the threshold stage's arguments: buffers and pitches, the predicate's constants, the launch geometry ------------------
+static void set_buffers(ThresholdArgs& a, const ffs_stream* s, const void* img, size_t pitch, size_t fstride, const Rerun& how) {
     const ffs_ctx* c = s->ctx;
     const Layout& L = c->L;
     const ffs_params& p = s->batch_params;
-    ThresholdArgs a{};
     a.image = img;
     a.frame_stride = fstride;
     a.pitch = (uint32_t)pitch;
@@ -44,23 +44,6 @@ ThresholdArgs make_threshold_args(ffs_stream* s, const void* img, size_t pitch, 
     a.plane_frame_stride = L.plane_frame_stride;
     a.bytes_frame_stride = L.bytes_frame_stride;
     a.n_tiles = c->n_tiles;
-    a.kS = (float)(p.nsig_s * p.nsig_s * (1.0 - 1.0 / 65536.0));
-    a.kB = (float)(p.nsig_b * (1.0 - 1.0 / 1048576.0));
-    a.min_count = p.min_count;
-    a.nsig_b = p.nsig_b;
-    a.nsig_s = p.nsig_s;
-    a.nsig_b2 = p.nsig_b * p.nsig_b;
-    a.nsig_s2 = p.nsig_s * p.nsig_s;
-    a.threshold = p.threshold;
-    a.max_valid = p.max_valid;
-    {
-        const double b2 = p.nsig_b * p.nsig_b, s2 = p.nsig_s * p.nsig_s;
-        a.int_pred = (b2 == std::floor(b2) && s2 == std::floor(s2) && b2 <= 1024.0 && s2 <= 1024.0 && p.threshold < 2147483648.0
-                      && std::sqrt(b2) == p.nsig_b && std::sqrt(s2) == p.nsig_s) ? 1 : 0;   // (integer nsig: the squares are exact)
-        a.ib2 = a.int_pred ? (uint32_t)b2 : 0u;
-        a.is2 = a.int_pred ? (uint32_t)s2 : 0u;
-        a.thr_floor = a.int_pred ? (uint32_t)std::floor(p.threshold) : 0u;
-    }
     // bright windows (sum p >= 65536; 32-bit pixels >= 2^24): onto the list k_bright_fix works off, or -- tuning
     // "threshold_path" = 1, and whenever that list overflowed (ffs_wait re-runs the batch) -- into the plane as candidates
     a.bright_to_plane = how.threshold_path >= 0 ? how.threshold_path : c->tune.threshold_path;
@@ -83,91 +66,69 @@ ThresholdArgs make_threshold_args(ffs_stream* s, const void* img, size_t pitch, 
     a.dbg_prio = c->tune.stream_prio;
     a.ginfo = c->d_ginfo;
     a.mmap = c->d_mmap;
-    a.gpitch = (uint32_t)L.pitch_px * (uint32_t)c->pixel_bytes / 4;
-    a.gpf = c->pixel_bytes == 2 ? (L.W + 7) / 8 : (L.W + 3) / 4;
-    a.n_frames = (int)n_frames;
-    {   // Streaming kernels: frames side by side in one super row, as many as keep every buffer of the group below 2 GiB.
-        // Bands: enough waves to fill the 256 CUs several times over, bands no shorter than 72 rows (the 6-row warm-up of
-        // every band stays below 8 %).  The default stays a multiple of eight bands (what rounds 1-4's round-robin map, band = xcd + 8 k,
-        // needed: with 29 bands three XCDs had a band less to do than the others, 511 us per 32 Eiger frames against 430-440 with 48
-        // or 56); the unit map of round 5 (ffs_device.h, stream_unit) balances any number -- tuning "stream_bands".
-        const uint64_t per_frame = std::max<uint64_t>(fstride, L.bytes_frame_stride);
-        a.group_frames = (int)std::max<uint64_t>(1, std::min<uint64_t>(n_frames, ((1ull << 31) - 1) / per_frame));
-        a.group_frames = std::min(a.group_frames, c->tune.frames_per_group);
-        const int n_groups = ((int)n_frames + a.group_frames - 1) / a.group_frames;
-        const long long lanes = (long long)a.group_frames * (a.gpf + 1);
-        const long long lines = (long long)a.group_frames * (L.bpitch / 128);  // byte-mask lines to zero per row
-        const int lines_per_wave = c->pixel_bytes == 2 ? 4 : 2;  // a wave zero-fills 512 / 256 bytes of the byte mask per row
-        a.n_strips = (int)std::max<long long>((lanes + kSOwned - 1) / kSOwned, (lines + lines_per_wave - 1) / lines_per_wave);
-        const long long per_band = std::max<long long>(1, (long long)a.n_strips * n_groups);
-        long long nb = std::max<long long>(1, std::min<long long>(c->tune.target_waves / per_band, L.H / 72));
-        if (nb >= 8) nb = nb / 8 * 8;
-        // tuning "stream_bands" > 0: that many bands (any number: the unit map balances the XCDs)
-        if (c->tune.stream_bands > 0) nb = std::max<long long>(1, std::min<long long>(c->tune.stream_bands, L.H / 8));
-        a.band_rows = (int)std::min<long long>(1024, (L.H + nb - 1) / nb);
-        a.n_bands = (L.H + a.band_rows - 1) / a.band_rows;
-        a.band_rows2 = a.band_rows;
-        a.band_split = a.n_bands;
-        // Tapered bands (tuning "band_taper" = t per cent, 0 = off): the last two bands of every XCD are t % as tall as the others.
-        // The waves of a launch all take about the same time and there are 3-4 times as many of them as the machine has slots, so
-        // the last round leaves slots idle; handed out last and short, the final waves fill that tail with less work each.
-        const int taper = c->tune.band_taper;
-        if (taper > 0 && taper < 100 && nb >= 32 && nb % 8 == 0 && a.n_bands == (int)nb) {
-            const int K = (int)nb / 8;                       // bands per XCD
-            const int K2 = 2, K1 = K - K2;
-            // 8 (K1 h1 + K2 h2) >= H with h2 = taper h1 / 100
-            const double h1f = (double)L.H / (8.0 * (K1 + K2 * taper / 100.0));
-            int h1 = std::min(1024, (int)std::ceil(h1f));
-            int h2 = (int)std::ceil((L.H / 8.0 - (double)K1 * h1) / K2);
-            while (h2 < 24) { --h1; h2 = (int)std::ceil((L.H / 8.0 - (double)K1 * h1) / K2); }
-            if (h1 >= h2 && h2 >= 24 && 8 * (K1 * h1 + K2 * h2) >= L.H && 8 * K1 * h1 < L.H) {
-                a.band_rows = h1;
-                a.band_rows2 = h2;
-                a.band_split = 8 * K1;
-                a.n_bands = a.band_split + (L.H - a.band_split * h1 + h2 - 1) / h2;
-            }
-        }
-    }
-    a.kx = win_half(p.kernel_half_x);
-    a.ky = win_half(p.kernel_half_y);
-    {   // the general-window kernel: strips of 62 owned eight-pixel groups; bands at least 6 windows tall (the 2ky + 1 warm-up rows
-        // of a band stay below a sixth of its rows), as many as fill the machine about four times over
-        const int g8 = (L.W + 7) / 8;
-        a.w_strips = (g8 + kWinOwned - 1) / kWinOwned;
-        const long long per_band = std::max<long long>(1, (long long)a.w_strips * n_frames);
-        const int min_rows = std::max(32, 6 * (2 * a.ky + 1));
-        const long long nb = std::max<long long>(1, std::min<long long>(16384 / per_band, std::max(1, L.H / min_rows)));
-        a.w_band_rows = (int)((L.H + nb - 1) / nb + 7) / 8 * 8;
-        a.w_bands = (L.H + a.w_band_rows - 1) / a.w_band_rows;
-        // (only where the float32 arithmetic of the screens can neither overflow nor lose its margin: DESIGN.md section 3.3b)
-        a.w_kS = (std::isfinite(p.nsig_s) && p.nsig_s <= 1024.0) ? (float)(p.nsig_s * p.nsig_s * (1.0 - 1.0 / 65536.0)) : 0.0f;
-        a.w_kB = (std::isfinite(p.nsig_b) && p.nsig_b <= 1024.0) ? (float)(p.nsig_b * p.nsig_b * (1.0 - 1.0 / 65536.0)) : 0.0f;
-    }
+    a.gpitch = ginfo_pitch(L, c->pixel_bytes);
+    a.gpf = groups_per_row(L, c->pixel_bytes);
     a.dplane = s->d_dplane;
     a.eplane = s->d_eplane;
     a.eplane_clean = s->ext_e_clean ? 1 : 0;
-    a.ext_flavour = p.extended_flavour;
     a.ext_variant = (c->pixel_bytes == 2 && how.threshold_path < 0) ? c->tune.ext_first_pass : 0;
-    a.ext_strips = (L.pitch_px + kExtOwnedPx - 1) / kExtOwnedPx;
-    {   // one pixel per lane: bands of 64..256 rows keep the 6-row warm-up below 10 %
-        const long long ext_target = 8192;
-        long long er = ((long long)L.H * a.ext_strips * n_frames + 4 * ext_target - 1) / (4 * ext_target);
-        er = std::max<long long>(64, std::min<long long>(er, 256));
-        a.ext_band_rows = (int)er;
-        a.ext_bands = (L.H + a.ext_band_rows - 1) / a.ext_band_rows;
+}
+static void set_predicate(ThresholdArgs& a, const ffs_params& p) {
+    a.kS = (float)(p.nsig_s * p.nsig_s * (1.0 - 1.0 / 65536.0));
+    a.kB = (float)(p.nsig_b * (1.0 - 1.0 / 1048576.0));
+    a.min_count = p.min_count;
+    a.nsig_b = p.nsig_b;
+    a.nsig_s = p.nsig_s;
+    a.nsig_b2 = p.nsig_b * p.nsig_b;
+    a.nsig_s2 = p.nsig_s * p.nsig_s;
+    a.threshold = p.threshold;
+    a.max_valid = p.max_valid;
+    {
+        const double b2 = p.nsig_b * p.nsig_b, s2 = p.nsig_s * p.nsig_s;
+        a.int_pred = (b2 == std::floor(b2) && s2 == std::floor(s2) && b2 <= 1024.0 && s2 <= 1024.0 && p.threshold < 2147483648.0
+                      && std::sqrt(b2) == p.nsig_b && std::sqrt(s2) == p.nsig_s) ? 1 : 0;   // (integer nsig: the squares are exact)
+        a.ib2 = a.int_pred ? (uint32_t)b2 : 0u;
+        a.is2 = a.int_pred ? (uint32_t)s2 : 0u;
+        a.thr_floor = a.int_pred ? (uint32_t)std::floor(p.threshold) : 0u;
     }
+    a.kx = win_half(p.kernel_half_x);
+    a.ky = win_half(p.kernel_half_y);
+    // the general-window kernel's float32 screens
+    // (only where the float32 arithmetic of the screens can neither overflow nor lose its margin: DESIGN.md section 3.3b)
+    a.w_kS = (std::isfinite(p.nsig_s) && p.nsig_s <= 1024.0) ? (float)(p.nsig_s * p.nsig_s * (1.0 - 1.0 / 65536.0)) : 0.0f;
+    a.w_kB = (std::isfinite(p.nsig_b) && p.nsig_b <= 1024.0) ? (float)(p.nsig_b * p.nsig_b * (1.0 - 1.0 / 65536.0)) : 0.0f;
+    a.ext_flavour = p.extended_flavour;
+}
+// (launch_geometry.hpp computes them; the super rows of the streaming launch, g.n_groups, are its grid's y and no argument)
+static void set_geometry(ThresholdArgs& a, uint32_t n_frames, const StreamGeometry& g, const WindowGeometry& w, const ExtGeometry& e) {
+    a.n_frames = (int)n_frames;
+    a.group_frames = g.group_frames;
+    a.n_strips = g.n_strips;
+    a.n_bands = g.n_bands;
+    a.band_rows = g.band_rows;
+    a.band_rows2 = g.band_rows2;
+    a.band_split = g.band_split;
+    a.w_strips = w.w_strips;
+    a.w_band_rows = w.w_band_rows;
+    a.w_bands = w.w_bands;
+    a.ext_strips = e.ext_strips;
+    a.ext_band_rows = e.ext_band_rows;
+    a.ext_bands = e.ext_bands;
+}
+StreamGeometry batch_stream_geometry(const ffs_stream* s, size_t fstride, uint32_t n_frames) {
+    return stream_geometry(s->ctx->L, s->ctx->pixel_bytes, fstride, n_frames, s->ctx->tune);
+}
+ThresholdArgs make_threshold_args(ffs_stream* s, const void* img, size_t pitch, size_t fstride, uint32_t n_frames, const StreamGeometry& g, const Rerun& how) {
+    ThresholdArgs a{};
+    set_buffers(a, s, img, pitch, fstride, how);
+    set_predicate(a, s->batch_params);
+    set_geometry(a, n_frames, g, window_geometry(s->ctx->L, n_frames, a.ky), ext_geometry(s->ctx->L, n_frames));
     return a;
 }
 
 // ---- the threshold stage's launches -----------------------------------------------------------------------------
-static dim3 stream_grid(const ThresholdArgs& a, uint32_t n_frames) {
-    const unsigned n_groups = (n_frames + (unsigned)a.group_frames - 1) / (unsigned)a.group_frames;
-    return dim3(8u * stream_chunk(a), n_groups);   // (the units in eight equal chunks, one per XCD: ffs_device.h, stream_unit)
-}
-// logs of a launch: one per (super row, band, strip) -- log_slot()
-static size_t stream_log_slots(const ThresholdArgs& a, uint32_t n_frames) {
-    const unsigned n_groups = (n_frames + (unsigned)a.group_frames - 1) / (unsigned)a.group_frames;
-    return (size_t)n_groups * (size_t)a.n_bands * (size_t)a.n_strips;
+static dim3 stream_grid(const ThresholdArgs& a, const StreamGeometry& g) {
+    return dim3(8u * stream_chunk(a), (unsigned)g.n_groups);   // (the units in eight equal chunks, one per XCD: launch_geometry.hpp, stream_unit_of)
 }
 
 // The instantiation of the streaming kernels a launch takes.  Rows of loads a wave keeps in flight: tuning "rows_ahead", within what
@@ -183,8 +144,8 @@ static StreamKernel stream_kernel(const ffs_ctx* c, bool dense_mask, bool extend
 }
 // The whole standard threshold in one kernel: final strong plane + per-tile counts (atomics into zeroed counters).
 // Start and stop events ride on the dispatch itself (its completion signal): no marker packets around it.
-static void launch_stream(ffs_stream* s, const ThresholdArgs& a, uint32_t n_frames, hipEvent_t start, hipEvent_t stop, hipStream_t st = nullptr) {
-    hipExtLaunchKernelGGL(stream_kernel(s->ctx, a.dense_mask != 0, false), stream_grid(a, n_frames), dim3(64), 0, st ? st : s->st, start, stop, 0, a);
+static void launch_stream(ffs_stream* s, const ThresholdArgs& a, const StreamGeometry& g, hipEvent_t start, hipEvent_t stop, hipStream_t st = nullptr) {
+    hipExtLaunchKernelGGL(stream_kernel(s->ctx, a.dense_mask != 0, false), stream_grid(a, g), dim3(64), 0, st ? st : s->st, start, stop, 0, a);
 }
 // The general-window kernel (kernels_window.hpp): windows other than 3,3, or every window with tuning "window_kernel" = 1.  The
 // standard algorithm on the plane paths only (no wave logs: those belong to k_stream_u16); the cross-check path (threshold_path 2)
@@ -236,14 +197,14 @@ static void launch_exact(ffs_stream* s, const ThresholdArgs& a, uint32_t n_frame
 // when the bright-window list of a batch overflowed).
 static bool ext_stream_first(const ThresholdArgs& a) { return a.ext_variant >= 2; }
 
-static void launch_ext_first(ffs_stream* s, const ThresholdArgs& a, uint32_t n_frames, hipEvent_t start, hipEvent_t stop, bool fix_here = true,
+static void launch_ext_first(ffs_stream* s, const ThresholdArgs& a, const StreamGeometry& g, uint32_t n_frames, hipEvent_t start, hipEvent_t stop, bool fix_here = true,
                              bool plane_clean = false, bool counts_clean = false) {
     if (ext_stream_first(a)) {
         // the kernel writes the non-zero bytes of the first-pass plane; the bright-list count sits behind the tile counts
         // (both are usually clean already: the plane was cleared behind the previous batch's sparse launch, which also zeroed the counts)
         if (!plane_clean) (void)hipMemsetAsync(a.dplane, 0, (size_t)n_frames * a.plane_frame_stride, s->st);
         if (!counts_clean) (void)hipMemsetAsync(a.tile_counts, 0, tile_counts_bytes(s), s->st);
-        hipExtLaunchKernelGGL(stream_kernel(s->ctx, a.dense_mask != 0, true), stream_grid(a, n_frames), dim3(64), 0, s->st, start, stop, 0, a);
+        hipExtLaunchKernelGGL(stream_kernel(s->ctx, a.dense_mask != 0, true), stream_grid(a, g), dim3(64), 0, s->st, start, stop, 0, a);
         if (fix_here) hipLaunchKernelGGL((k_bright_fix<uint16_t, true>), dim3(32), dim3(256), 0, s->st, a);
         return;
     }
@@ -294,43 +255,46 @@ int ensure_extended_buffers(ffs_stream* s) {
     return FFS_OK;
 }
 
-// Wave logs for this launch (tuning "strong_log"): the 16-bit standard path on a context with sparse streams, a geometry
-// kernels_chain.hpp's merge holds (at most twelve strips per frame).  Allocates the logs for the launch's waves on first use
-// and puts them into `a`; false: the plane.
-bool wave_logs_for(ffs_stream* s, ThresholdArgs& a, uint32_t n_frames, const Rerun& how) {
-    ffs_ctx* c = s->ctx;
+// Wave logs (tuning "strong_log"): the 16-bit standard path on a context with sparse streams, a geometry kernels_chain.hpp's merge holds
+// (at most twelve strips per frame) -- can this batch take them?
+static bool wave_logs_possible(const ffs_stream* s, const ThresholdArgs& a, const Rerun& how) {
+    const ffs_ctx* c = s->ctx;
     const Layout& L = c->L;
-    if (!(c->tune.strong_log != 0 && !a.bright_to_plane && !s->log_off && !how.plane && s->st2 != s->st && c->chain_ok
-          && s->batch_params.algorithm != FFS_ALGO_DISPERSION_EXTENDED && c->n_tiles <= kChainMaxTiles && L.H <= kChainMaxRows
-          && (uint32_t)a.gpf / (uint32_t)kSOwned + 2u <= 16u && a.band_rows <= 1024 && L.W <= 65535))
-        return false;
-    size_t waves = stream_log_slots(a, n_frames);
-    if (waves > s->wlog_waves) {
-        // Sized ONCE, for the largest launch any batch of this stream can make (1 .. max_batch frames), so that a batch of another
-        // size never re-allocates: hipFree synchronises the whole device, i.e. every other worker's batches in flight.  (A stream is
-        // idle here -- submit refuses a busy one, and a re-run inside ffs_wait comes after the batch's last event -- so nothing of
-        // its own has to be waited for if it does happen: a tuning change between batches.)
-        for (uint32_t nf = 1; nf <= s->max_batch; ++nf) {
-            const ThresholdArgs t = make_threshold_args(s, a.image, a.pitch, a.frame_stride, nf, how);
-            waves = std::max(waves, stream_log_slots(t, nf));
-        }
-        if (s->d_wlog) {
-            (void)hipFree(s->d_wlog);
-            (void)hipFree(s->d_wlog_n);
-            (void)hipFree(s->d_wpix);
-            s->d_wlog = nullptr;
-            s->d_wlog_n = nullptr;
-            s->d_wpix = nullptr;
-        }
-        s->wlog_waves = 0;
-        if (hipMalloc(reinterpret_cast<void**>(&s->d_wlog), waves * kWlogCap * sizeof(uint2)) != hipSuccess
-            || hipMalloc(reinterpret_cast<void**>(&s->d_wpix), waves * kWlogCap * sizeof(uint4)) != hipSuccess
-            || hipMalloc(reinterpret_cast<void**>(&s->d_wlog_n), waves * 4) != hipSuccess) {
-            (void)hipGetLastError();
-            return false;
-        }
-        s->wlog_waves = waves;
+    return c->tune.strong_log != 0 && !a.bright_to_plane && !s->log_off && !how.plane && s->st2 != s->st && c->chain_ok
+           && s->batch_params.algorithm != FFS_ALGO_DISPERSION_EXTENDED && c->n_tiles <= kChainMaxTiles && L.H <= kChainMaxRows
+           && strips_per_frame(L, c->pixel_bytes) <= 16u && a.band_rows <= 1024 && L.W <= 65535;
+}
+// The stream's logs hold `slots` waves: allocated on first use; false: no memory for them.
+static bool ensure_wave_logs(ffs_stream* s, size_t slots) {
+    if (slots <= s->wlog_waves) return true;
+    if (s->d_wlog) {
+        (void)hipFree(s->d_wlog);
+        (void)hipFree(s->d_wlog_n);
+        (void)hipFree(s->d_wpix);
+        s->d_wlog = nullptr;
+        s->d_wlog_n = nullptr;
+        s->d_wpix = nullptr;
     }
+    s->wlog_waves = 0;
+    if (hipMalloc(reinterpret_cast<void**>(&s->d_wlog), slots * kWlogCap * sizeof(uint2)) != hipSuccess
+        || hipMalloc(reinterpret_cast<void**>(&s->d_wpix), slots * kWlogCap * sizeof(uint4)) != hipSuccess
+        || hipMalloc(reinterpret_cast<void**>(&s->d_wlog_n), slots * 4) != hipSuccess) {
+        (void)hipGetLastError();
+        return false;
+    }
+    s->wlog_waves = slots;
+    return true;
+}
+// Wave logs for this launch: allocates them on first use and puts them into `a`; false: the plane.
+bool wave_logs_for(ffs_stream* s, ThresholdArgs& a, const StreamGeometry& g, const Rerun& how) {
+    if (!wave_logs_possible(s, a, how)) return false;
+    size_t slots = stream_log_slots(g);
+    // Sized ONCE, for the largest launch any batch of this stream can make (1 .. max_batch frames), so that a batch of another
+    // size never re-allocates: hipFree synchronises the whole device, i.e. every other worker's batches in flight.  (A stream is
+    // idle here -- submit refuses a busy one, and a re-run inside ffs_wait comes after the batch's last event -- so nothing of
+    // its own has to be waited for if it does happen: a tuning change between batches.)
+    if (slots > s->wlog_waves) slots = std::max(slots, max_stream_log_slots(s->ctx->L, s->ctx->pixel_bytes, a.frame_stride, s->max_batch, s->ctx->tune));
+    if (!ensure_wave_logs(s, slots)) return false;
     a.wlog = s->d_wlog;
     a.wlog_n = s->d_wlog_n;
     a.wpix = s->d_wpix;
@@ -338,10 +302,10 @@ bool wave_logs_for(ffs_stream* s, ThresholdArgs& a, uint32_t n_frames, const Rer
 }
 
 // The threshold stage where all of it runs in s->st (ffs_internal.hpp): the dense kernel ...
-void launch_dense_kernel(ffs_stream* s, const ThresholdArgs& a, uint32_t n_frames, hipEvent_t start, hipEvent_t stop, bool plane_clean, bool counts_clean) {
-    if (s->batch_params.algorithm == FFS_ALGO_DISPERSION_EXTENDED) launch_ext_first(s, a, n_frames, start, stop, true, plane_clean, counts_clean);
+void launch_dense_kernel(ffs_stream* s, const ThresholdArgs& a, const StreamGeometry& g, uint32_t n_frames, hipEvent_t start, hipEvent_t stop, bool plane_clean, bool counts_clean) {
+    if (s->batch_params.algorithm == FFS_ALGO_DISPERSION_EXTENDED) launch_ext_first(s, a, g, n_frames, start, stop, true, plane_clean, counts_clean);
     else if (window_kernel_for(s, a)) launch_window(s, a, n_frames, start, stop);
-    else launch_stream(s, a, n_frames, start, stop);
+    else launch_stream(s, a, g, start, stop);
 }
 // ... and what follows it
 void launch_dense_rest(ffs_stream* s, const ThresholdArgs& a, uint32_t n_frames) {
@@ -379,39 +343,30 @@ __global__ void k_dummy_spin(uint32_t ticks, uint32_t* sink) {
 
 // The sparse stage in small workgroups (kernels_band.hpp, tuning "sparse_bands"): can this launch geometry take it, and are the
 // buffers between its two kernels there (allocated once, for the most bands any batch of this stream can have).
-struct BandSplit { int sub = 1, sub_rows = 0; };   // a band of the streaming launch as `sub` bands of the sparse stage, each of at most sub_rows rows
-static BandSplit band_split(const ThresholdArgs& a) {
-    const int rows = std::max(a.band_rows, a.band_rows2), sub = (rows + kBandSplitRows - 1) / kBandSplitRows;
-    return {sub, (rows + sub - 1) / sub};
-}
-static bool band_stage_for(ffs_stream* s, const ThresholdArgs& a, uint32_t n_frames, const Rerun& how) {
-    ffs_ctx* c = s->ctx;
-    const uint32_t strips = (uint32_t)a.gpf / (uint32_t)kSOwned + 2u;   // strips a frame's groups can touch
-    const BandSplit split = band_split(a);
-    const int sub = split.sub, sub_rows = split.sub_rows;
-    if (sub_rows > kBandMaxRows || (uint32_t)sub_rows * std::min(strips, 16u) > (uint32_t)kBandCw || a.n_bands * sub > kMergeMaxBands || c->L.W > 65535)
-        return false;
-    const uint32_t need = n_frames * (uint32_t)(a.n_bands * sub);
-    if (need > s->band_slots) {
-        uint32_t slots = need;
-        for (uint32_t nf = 1; nf <= s->max_batch; ++nf) {   // (sized once: hipFree synchronises the device -- see wave_logs_for)
-            const ThresholdArgs t = make_threshold_args(s, a.image, a.pitch, a.frame_stride, nf, how);
-            slots = std::max(slots, nf * (uint32_t)(t.n_bands * band_split(t).sub));
-        }
-        if (s->d_band_hdr) {
-            (void)hipFree(s->d_band_hdr); (void)hipFree(s->d_band_acc); (void)hipFree(s->d_band_seam);
-            s->d_band_hdr = nullptr; s->d_band_acc = nullptr; s->d_band_seam = nullptr;
-        }
-        s->band_slots = 0;
-        if (hipMalloc(reinterpret_cast<void**>(&s->d_band_hdr), (size_t)slots * sizeof(uint4)) != hipSuccess
-            || hipMalloc(reinterpret_cast<void**>(&s->d_band_acc), (size_t)slots * kBandCompStride * sizeof(ChainAcc)) != hipSuccess
-            || hipMalloc(reinterpret_cast<void**>(&s->d_band_seam), (size_t)slots * 2 * kBandSeamCap * 4) != hipSuccess) {
-            (void)hipGetLastError();
-            return false;
-        }
-        s->band_slots = slots;
+// The three buffers hold `slots` (frame, band) pairs; false: no memory for them.
+static bool ensure_band_buffers(ffs_stream* s, uint32_t slots) {
+    if (slots <= s->band_slots) return true;
+    if (s->d_band_hdr) {
+        (void)hipFree(s->d_band_hdr); (void)hipFree(s->d_band_acc); (void)hipFree(s->d_band_seam);
+        s->d_band_hdr = nullptr; s->d_band_acc = nullptr; s->d_band_seam = nullptr;
     }
+    s->band_slots = 0;
+    if (hipMalloc(reinterpret_cast<void**>(&s->d_band_hdr), (size_t)slots * sizeof(uint4)) != hipSuccess
+        || hipMalloc(reinterpret_cast<void**>(&s->d_band_acc), (size_t)slots * kBandCompStride * sizeof(ChainAcc)) != hipSuccess
+        || hipMalloc(reinterpret_cast<void**>(&s->d_band_seam), (size_t)slots * 2 * kBandSeamCap * 4) != hipSuccess) {
+        (void)hipGetLastError();
+        return false;
+    }
+    s->band_slots = slots;
     return true;
+}
+static bool band_stage_for(ffs_stream* s, const StreamGeometry& g, size_t fstride, uint32_t n_frames) {
+    const ffs_ctx* c = s->ctx;
+    if (!band_plan_holds(g, c->L, c->pixel_bytes)) return false;
+    uint32_t slots = band_slots(g, n_frames);
+    // (sized once: hipFree synchronises the device -- see wave_logs_for)
+    if (slots > s->band_slots) slots = std::max(slots, max_band_slots(c->L, c->pixel_bytes, fstride, s->max_batch, c->tune));
+    return ensure_band_buffers(s, slots);
 }
 
 // ---- one batch ------------------------------------------------------------------------------------------------------
@@ -448,6 +403,7 @@ struct BatchPlan {
     bool banded = false;              // the one launch is k_band_cc + k_frame_merge, `band` says how the streaming launch's bands are split for it
     bool chain_first = false;         // the one launch does the bright-window fix-up and the next streaming kernel waits for its start
     bool want_dense_bytes = false;    // the byte mask of this batch is produced
+    StreamGeometry geo{};             // the streaming launch's geometry: super rows, strips, bands (launch_geometry.hpp)
     ThresholdArgs ta{};               // the threshold stage's arguments ...
     ThresholdArgs ta_launch{};        // ... and with the wave logs, for the streaming kernel and the one launch that reads them (== ta without logs)
     BandSplit band;
@@ -466,7 +422,8 @@ static BatchPlan plan_batch(ffs_stream* s, const void* d_img, size_t pitch, size
     P.counts_were_clean = !s->counts_dirty;
     P.ext = p.algorithm == FFS_ALGO_DISPERSION_EXTENDED;
     P.ext_sparse_erode = ext_sparse_erode(c->tune);
-    P.ta = make_threshold_args(s, d_img, pitch, fstride, n, how);
+    P.geo = batch_stream_geometry(s, fstride, n);
+    P.ta = make_threshold_args(s, d_img, pitch, fstride, n, P.geo, how);
     P.window = !P.ext && window_kernel_for(s, P.ta);
     P.list_path = !P.ext && !P.ta.bright_to_plane && !P.window;
     // (the byte mask: zero-filled by the streaming kernels only when asked for; the exact stages always produce it)
@@ -492,7 +449,7 @@ static BatchPlan plan_batch(ffs_stream* s, const void* d_img, size_t pitch, size
     // Wave logs instead of the plane (tuning "strong_log"): the standard 16-bit path, sparse stage in the one launch, frames
     // that fit its LDS forest.  The streaming kernel then leaves plane, counters, occupancy bitmap and bright list alone.
     P.ta_launch = P.ta;
-    P.use_log = P.list_path && P.will_chain && !P.dense_batch && wave_logs_for(s, P.ta_launch, n, how);
+    P.use_log = P.list_path && P.will_chain && !P.dense_batch && wave_logs_for(s, P.ta_launch, P.geo, how);
 #ifdef FFS_EXPERIMENTS
     if (c->tune.exp.chain_skip) P.will_chain = false;   // (use_log stays what it was with the one launch)
 #endif
@@ -511,8 +468,8 @@ static BatchPlan plan_batch(ffs_stream* s, const void* d_img, size_t pitch, size
     // region): there the band launches win at every depth (+1.2 % on the driver-style line, profiles/r05zo_tune_ab.log).
     const bool depth_ok = c->tune.sparse_bands >= 2 || depth >= 4 || depth <= 1 || c->n_streams_made >= 4;
     P.banded = P.use_log && c->tune.sparse_bands != 0 && depth_ok && !P.need_lists && !P.ta.dense_mask && !how.no_bands && s->band_backoff == 0
-               && band_stage_for(s, P.ta_launch, n, how);
-    if (P.banded) P.band = band_split(P.ta_launch);
+               && band_stage_for(s, P.geo, fstride, n);
+    if (P.banded) P.band = band_split(P.geo);
     // chain_first: the one launch, one workgroup per frame, of a list-path batch on a context with sparse streams ...
     // ... which then also does the bright-window fix-up, and whose workgroups (a whole CU each) should get their CUs
     // BEFORE the next batch's streaming kernel floods the dispatcher: that kernel waits for this launch to have STARTED.
@@ -617,7 +574,7 @@ static int launch_stream_overlapped(ffs_stream* s, const BatchPlan& plan, hipEve
     ThresholdArgs a = plan.ta_launch;
     a.handoff = c->d_handoff;
     a.handoff_seq = seq;
-    launch_stream(s, a, plan.n, ev_start, s->ev[2], dst);
+    launch_stream(s, a, plan.geo, ev_start, s->ev[2], dst);
     c->handoff_last = which;
     launched = true;
     return FFS_OK;
@@ -640,7 +597,7 @@ static int launch_threshold_stage(ffs_stream* s, const BatchPlan& plan, bool den
         // region that keeps the vector units half busy -- go to the batch's sparse stream, ahead of its sparse launch, and run
         // BESIDE the next batch's first pass (an issue-bound stream of the whole frame) instead of between two of them.
         const bool streams = ext_stream_first(ta);   // (the first pass's stop event rides on its dispatch; the bright-window fix-up goes aside too)
-        launch_ext_first(s, ta, n, ev_start, streams ? s->ev[2] : nullptr, false, ext_plane_clean, plan.counts_were_clean);
+        launch_ext_first(s, ta, plan.geo, n, ev_start, streams ? s->ev[2] : nullptr, false, ext_plane_clean, plan.counts_were_clean);
         FFS_TRY(sparse_stream_follows(s, streams));
         if (streams) hipLaunchKernelGGL((k_bright_fix<uint16_t, true>), dim3(32), dim3(256), 0, s->st2, ta);
         launch_ext_rest(s, ta, n, s->st2);
@@ -661,7 +618,7 @@ static int launch_threshold_stage(ffs_stream* s, const BatchPlan& plan, bool den
             FFS_TRY(launch_stream_overlapped(s, plan, ev_start, launched));
         if (!launched) {
             FFS_TRY(wait_for_upload(s, plan, s->st));
-            launch_stream(s, plan.ta_launch, n, ev_start, s->ev[2]);
+            launch_stream(s, plan.ta_launch, plan.geo, ev_start, s->ev[2]);
         }
         FFS_TRY(sparse_stream_follows(s, true));
         if (!plan.chain_first && !plan.use_log) launch_bright_fix(s, ta, s->st2);
@@ -680,7 +637,7 @@ static int launch_threshold_stage(ffs_stream* s, const BatchPlan& plan, bool den
         // the whole stage in the dense stream: the streaming kernel + k_bright_fix (path 0 on a context without sparse streams) or
         // + k_exact (path 1); the extended algorithm's first pass + erosion + final pass
         if (!plan.ext) FFS_TRY(wait_for_upload(s, plan, s->st));   // (extended: waited for already, reset_for_batch)
-        launch_dense_kernel(s, ta, n, ev_start, nullptr, ext_plane_clean, plan.counts_were_clean);
+        launch_dense_kernel(s, ta, plan.geo, n, ev_start, nullptr, ext_plane_clean, plan.counts_were_clean);
         launch_dense_rest(s, ta, n);
         FFS_TRY(sparse_stream_follows(s, false));
     }

@@ -27,18 +27,15 @@
 
 namespace ffsamd {
 
-constexpr int kBandMaxRows = 128;       // rows of a band (the streaming kernel's geometry: 72-80 for Eiger frames)
 constexpr int kBandChunks = 8;          // chunks of 64 log entries held in registers
 constexpr int kBandEntries = 64 * kBandChunks;
 constexpr int kBandPx = 768;            // strong pixels of one band of one frame (the bench frames: 320 +- 70)
 constexpr int kBandPer = kBandPx / 64;  // consecutive list entries per lane in the forest phases
-constexpr int kBandCw = 1024;           // (row, strip) counters: rows * strips of the frame
 constexpr int kBandSlots = 64;          // components accumulated in LDS at a time
 constexpr int kBandCompStride = 256;    // components of a band handed to the merge (accumulator slots per band)
 constexpr int kBandSeamCap = 256;       // strong pixels of a band's first / last row handed to the merge
 constexpr int kBandItems = (kBandPx - kBandEntries) / 2;   // undecided pixels of a band: two words each behind the per-entry results, in the forest's LDS (free then)
 constexpr int kMergeThreads = 256;
-constexpr int kMergeMaxBands = 128;
 constexpr int kMergeCap = 4096;         // band components of a frame whose forest fits the merge's LDS
 constexpr int kMergeSeamLds = 8;        // strong pixels of a seam row the merge stages in LDS (longer rows: walked in global memory)
 constexpr int kMergeLabels = 2;         // labels per thread and round of the record phase
@@ -46,7 +43,6 @@ constexpr int kMergePer = kMergeCap / kMergeThreads;
 static_assert(sizeof(ChainAcc) == 56 && kBandSlots * (int)sizeof(ChainAcc) <= kBandCw * 4, "the accumulators take the counters' LDS");
 static_assert(kBandEntries + 2 * kBandItems <= kBandPx && kBandMaxRows % 2 == 0, "LDS plan");
 
-constexpr int kBandSplitRows = 96;      // a streaming band taller than this is cut into sub-bands of equal height, a wave each
 struct BandArgs {
     ChainArgs A;
     int sub, sub_rows;   // sub-bands per streaming band (1: the band itself), rows of each (large batches have taller bands: fewer, longer

@@ -25,7 +25,6 @@
 
 namespace ffsamd {
 
-constexpr int kExtOwnedPx = 56;    // lanes 4..59 of a wave own output
 constexpr int kExtLaneOffset = 4;  // lane l sits on x = 56 * strip - 4 + l
 
 template <typename PixelT>
