@@ -126,6 +126,7 @@ constexpr uint32_t kOvfRuns = 16u;        // a frame's runs are beyond the one l
 constexpr uint32_t kOvfWaveLog = 32u;     // a wave log or the list of undecided pixels overflowed (k_frame_chain<LOG>, k_band_cc): the batch again through the plane, and the stream stays with it
 constexpr uint32_t kOvfLdsForest = 64u;   // a frame beyond the LDS forest met on the log path (k_frame_chain<LOG>): this batch again through the plane
 constexpr uint32_t kOvfBandPlan = 128u;   // a band beyond the band stage's plan (k_band_cc, k_frame_merge): the batch again through k_frame_chain, bands off for 32 batches
+constexpr uint32_t kOvfCorruptByteOffset = 256u;   // a byte-offset chunk holds fewer than W * H elements (kernels_byteoffset.hpp): the wait fails, FFS_ERR_INVALID
 // A different field: why a component is no reflection (filter_reflections), WireRec2::npx_flags >> 30 and ReflOut::flags
 constexpr uint32_t kRecTooSmall = 1u;     // fewer pixels than min_spot_size
 constexpr uint32_t kRecTooSpread = 2u;    // peak further than max_sep from the centre of mass

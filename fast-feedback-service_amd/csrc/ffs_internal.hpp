@@ -217,6 +217,12 @@ struct ffs_stream {
     uint8_t* d_comp = nullptr;                         // compressed chunks (allocated on first use)
     uint2 *d_tab = nullptr, *h_tab = nullptr;          // per-block (offset, length) tables
     uint32_t dec_blocks = 0, dec_last = 0, dec_tail = 0, dec_block_elems = 0;
+    // CBF byte-offset decode (kernels_byteoffset.hpp), allocated on the codec's first use: the frame table (device and pinned host,
+    // a BoFrame per frame) and the three summary tables, which hold bo_tiles_cap tiles and follow the staged bytes as d_comp does
+    uint4 *d_bo_frames = nullptr, *h_bo_frames = nullptr;
+    uint2 *d_bo_lane = nullptr, *d_bo_map = nullptr;
+    uint4* d_bo_state = nullptr;
+    size_t bo_tiles_cap = 0;
     // Without direct records: copied back speculatively with the counts (one wait instead of two): room for the most
     // records per frame seen so far on this stream, +25 %; ffs_wait fetches the rest if a batch exceeds it.
     uint32_t spec_recs_per_frame = 256;

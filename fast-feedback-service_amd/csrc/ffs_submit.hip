@@ -12,6 +12,7 @@
 #include "kernels_chain.hpp"
 #include "kernels_band.hpp"
 #include "kernels_decode.hpp"
+#include "kernels_byteoffset.hpp"
 #include "kernels_window.hpp"
 
 bool chain_prepare_device() {   // more than 64 KB of dynamic LDS has to be asked for, per device
@@ -944,26 +945,34 @@ static inline uint32_t be32(const uint8_t* p) {
 // Step 1 (caller's thread): validates the headers, places the chunks in the pinned staging buffer
 // (unless they already are there) and starts their copy to the device.  Fills base[] = offset of every
 // chunk in the staging / device buffer.
-static int stage_chunks(ffs_stream* s, const void* const* chunks, const size_t* chunk_bytes, uint32_t n,
+static int stage_chunks(ffs_stream* s, int codec, const void* const* chunks, const size_t* chunk_bytes, uint32_t n,
                         std::vector<size_t>& base) {
     ffs_ctx* c = s->ctx;
     const Layout& L = c->L;
-    int rc = ensure_decode_buffers(s);
+    int rc = codec == FFS_CODEC_BYTE_OFFSET ? FFS_OK : ensure_decode_buffers(s);
     if (rc != FFS_OK) return rc;
     const size_t es = c->pixel_bytes, raw_bytes = (size_t)L.W * L.H * es;
     uint32_t in_place = 0;
     for (uint32_t f = 0; f < n; ++f) {
-        if (!chunks[f] || chunk_bytes[f] < 12) {
-            c->err = "ffs_submit_compressed: a chunk is shorter than its 12-byte header";
-            return FFS_ERR_INVALID;
-        }
         const uint8_t* p = static_cast<const uint8_t*>(chunks[f]);
-        uint64_t total = 0;
-        for (int i = 0; i < 8; ++i) total = (total << 8) | p[i];
-        if (total != raw_bytes) {
-            c->err = "ffs_submit_compressed: chunk header says " + std::to_string(total) + " bytes, the context's frames have "
-                     + std::to_string(raw_bytes);
-            return FFS_ERR_INVALID;
+        if (codec == FFS_CODEC_BYTE_OFFSET) {   // (no header; every element takes at least one byte)
+            if (!p || chunk_bytes[f] < (size_t)L.W * L.H) {
+                c->err = "ffs_submit_encoded: a byte-offset chunk of " + std::to_string(p ? chunk_bytes[f] : 0) + " bytes cannot hold a frame of "
+                         + std::to_string((size_t)L.W * L.H) + " pixels";
+                return FFS_ERR_INVALID;
+            }
+        } else {
+            if (!p || chunk_bytes[f] < 12) {
+                c->err = "ffs_submit_compressed: a chunk is shorter than its 12-byte header";
+                return FFS_ERR_INVALID;
+            }
+            uint64_t total = 0;
+            for (int i = 0; i < 8; ++i) total = (total << 8) | p[i];
+            if (total != raw_bytes) {
+                c->err = "ffs_submit_compressed: chunk header says " + std::to_string(total) + " bytes, the context's frames have "
+                         + std::to_string(raw_bytes);
+                return FFS_ERR_INVALID;
+            }
         }
         if (p >= s->h_img && p + chunk_bytes[f] <= s->h_img + s->h_img_bytes) ++in_place;
     }
@@ -1108,8 +1117,89 @@ static void launch_decode(ffs_stream* s, uint32_t n, hipStream_t st) {
     else hipLaunchKernelGGL(k_bshuf_lz4_decode<4>, grid, dim3(64), 0, st, da);
 }
 
-static int ffs_submit_compressed_impl(ffs_stream* s, const void* const* chunks, const size_t* chunk_bytes,
-                                     uint32_t n_frames, int64_t first_frame_id) {
+// ---- CBF byte-offset chunks (kernels_byteoffset.hpp) ----
+// Step 1 of a byte-offset batch, on the caller's thread after stage_chunks: the frame table (where every chunk lies, how much of it is
+// parsed, where its tiles lie in the summary tables) and the tables themselves, allocated on the codec's first use on the stream and
+// regrown with the staged bytes.  max_tiles: the launches' grid.
+static int prepare_byte_offset(ffs_stream* s, const std::vector<size_t>& base, const size_t* chunk_bytes, uint32_t n, uint32_t& max_tiles) {
+    ffs_ctx* c = s->ctx;
+    if (!s->d_bo_frames) {
+        if (dmalloc(&s->d_bo_frames, (size_t)s->max_batch * sizeof(uint4)) != hipSuccess
+            || hipHostMalloc(reinterpret_cast<void**>(&s->h_bo_frames), (size_t)s->max_batch * sizeof(uint4), hipHostMallocDefault) != hipSuccess) {
+            (void)hipGetLastError();
+            c->err = "allocation of the byte-offset frame table failed";
+            return FFS_ERR_NOMEM;
+        }
+    }
+    static_assert(sizeof(BoFrame) == sizeof(uint4), "the frame table is allocated as uint4");
+    BoFrame* fr = reinterpret_cast<BoFrame*>(s->h_bo_frames);
+    const uint64_t most = 7ull * c->L.W * c->L.H;   // (seven bytes per element at the most: nothing behind that is ever parsed)
+    size_t tiles = 0;
+    max_tiles = 0;
+    for (uint32_t f = 0; f < n; ++f) {
+        fr[f].base = (uint32_t)base[f];
+        fr[f].end = (uint32_t)std::min<uint64_t>(chunk_bytes[f], most);
+        fr[f].tile0 = (uint32_t)tiles;
+        fr[f].total = 0;
+        tiles += bo_tiles(fr[f].end);
+        max_tiles = std::max(max_tiles, bo_tiles(fr[f].end));
+    }
+    if (tiles > s->bo_tiles_cap) {
+        // (the stream is idle, but its last decode may still read the tables on a decode-only path: they are freed behind both streams)
+        if (s->d_bo_lane) {
+            HIP_TRY(c, hipStreamSynchronize(s->st_up));
+            HIP_TRY(c, hipStreamSynchronize(s->st));
+        }
+        (void)hipFree(s->d_bo_lane); (void)hipFree(s->d_bo_map); (void)hipFree(s->d_bo_state);
+        s->d_bo_lane = nullptr; s->d_bo_map = nullptr; s->d_bo_state = nullptr;
+        s->bo_tiles_cap = 0;
+        const size_t want = tiles + tiles / 4 + 16;
+        if (dmalloc(&s->d_bo_lane, want * 7 * 64 * sizeof(uint2)) != hipSuccess || dmalloc(&s->d_bo_map, want * 7 * sizeof(uint2)) != hipSuccess
+            || dmalloc(&s->d_bo_state, want * sizeof(uint4)) != hipSuccess) {
+            (void)hipGetLastError();
+            c->err = "allocation of the byte-offset summary tables failed";
+            return FFS_ERR_NOMEM;
+        }
+        s->bo_tiles_cap = want;
+    }
+    return FFS_OK;
+}
+
+// The three launches of a byte-offset batch (summarise, compose, emit), behind the copy of the frame table, all in `st`.
+static hipError_t launch_byte_offset(ffs_stream* s, uint32_t n, uint32_t max_tiles, hipStream_t st, bool table = true) {
+    ffs_ctx* c = s->ctx;
+    if (table) {
+        const hipError_t e = hipMemcpyAsync(s->d_bo_frames, s->h_bo_frames, (size_t)n * sizeof(uint4), hipMemcpyHostToDevice, st);
+        if (e != hipSuccess) return e;
+    }
+    BoArgs a{};
+    a.comp = s->d_comp;
+    a.frames = reinterpret_cast<BoFrame*>(s->d_bo_frames);
+    a.lane_pre = s->d_bo_lane;
+    a.tile_map = s->d_bo_map;
+    a.tile_state = s->d_bo_state;
+    a.image = s->d_img;
+    a.frame_stride = c->L.frame_stride;
+    a.pitch = (uint32_t)c->L.pitch;
+    a.W = (uint32_t)c->L.W;
+    a.H = (uint32_t)c->L.H;
+    a.error = s->d_overflow;
+    const dim3 grid(max_tiles, n);
+    hipLaunchKernelGGL(k_bo_summarise, grid, dim3(64), 0, st, a);
+    hipLaunchKernelGGL(k_bo_compose, dim3(n), dim3(64), 0, st, a);
+    if (c->pixel_bytes == 2) hipLaunchKernelGGL(k_bo_emit<uint16_t>, grid, dim3(64), 0, st, a);
+    else hipLaunchKernelGGL(k_bo_emit<uint32_t>, grid, dim3(64), 0, st, a);
+    return hipGetLastError();
+}
+
+static bool codec_known(ffs_ctx* c, int codec, const char* who) {
+    if (codec == FFS_CODEC_BSLZ4 || codec == FFS_CODEC_BYTE_OFFSET) return true;
+    c->err = std::string(who) + ": unknown codec " + std::to_string(codec);
+    return false;
+}
+
+static int ffs_submit_encoded_impl(ffs_stream* s, int codec, const void* const* chunks, const size_t* chunk_bytes,
+                                   uint32_t n_frames, int64_t first_frame_id) {
     if (!s || !chunks || !chunk_bytes) return FFS_ERR_INVALID;
     ffs_ctx* c = s->ctx;
     if (s->busy) {
@@ -1120,12 +1210,21 @@ static int ffs_submit_compressed_impl(ffs_stream* s, const void* const* chunks, 
         c->err = "n_frames must be in 1..max_batch";
         return FFS_ERR_INVALID;
     }
+    if (!codec_known(c, codec, "ffs_submit_encoded")) return FFS_ERR_INVALID;
     HIP_TRY(c, hipSetDevice(c->device));
     s->dev_input = false;
     HIP_TRY(c, hipEventRecord(s->ev[0], s->st_up));
     std::vector<size_t> base;
-    int rc = stage_chunks(s, chunks, chunk_bytes, n_frames, base);
+    int rc = stage_chunks(s, codec, chunks, chunk_bytes, n_frames, base);
     if (rc != FFS_OK) return rc;
+    uint32_t bo_max_tiles = 0;   // (byte-offset chunks need no index: the tables are sized here, the helper thread only launches)
+    if (codec == FFS_CODEC_BYTE_OFFSET) {
+        rc = prepare_byte_offset(s, base, chunk_bytes, n_frames, bo_max_tiles);
+        if (rc != FFS_OK) {
+            (void)hipStreamSynchronize(s->st_up);   // (the chunks' copy reads the staging buffer the caller gets back)
+            return rc;
+        }
+    }
     // The rest -- block index, table copy, decode kernel and the hot path's launches -- is enqueued by a
     // helper thread, so that the caller gets its thread back while the index is built; ffs_wait joins it.
     s->first_id = first_frame_id;
@@ -1136,7 +1235,7 @@ static int ffs_submit_compressed_impl(ffs_stream* s, const void* const* chunks, 
     s->job_err.clear();
     const ffs_params snap = c->params;
     std::vector<size_t> sizes(chunk_bytes, chunk_bytes + n_frames);
-    s->job = std::thread([s, c, snap, n_frames, base = std::move(base), sizes = std::move(sizes)]() {
+    s->job = std::thread([s, c, snap, n_frames, codec, bo_max_tiles, base = std::move(base), sizes = std::move(sizes)]() {
         if (hipSetDevice(c->device) != hipSuccess) {
             s->job_rc = FFS_ERR_DEVICE;
             s->job_err = "hipSetDevice failed on the stream's helper thread";
@@ -1144,12 +1243,16 @@ static int ffs_submit_compressed_impl(ffs_stream* s, const void* const* chunks, 
         }
         // the decode kernel runs with the dense kernels (in their order), behind the copies of its input
         hipStream_t dst = c->tune.decode_in_dense_stream ? s->st : s->st_up;
-        int r = index_blocks(s, base, sizes, s->job_err, dst);
+        int r = codec == FFS_CODEC_BYTE_OFFSET ? FFS_OK : index_blocks(s, base, sizes, s->job_err, dst);
         if (r == FFS_OK) {
             (void)hipGetLastError();
             hipError_t e = hipSuccess;
             if (dst != s->st_up) e = hipStreamWaitEvent(dst, s->ev[6], 0);
-            launch_decode(s, n_frames, dst);
+            if (codec == FFS_CODEC_BYTE_OFFSET) {
+                if (e == hipSuccess) e = launch_byte_offset(s, n_frames, bo_max_tiles, dst);
+            } else {
+                launch_decode(s, n_frames, dst);
+            }
             if (e == hipSuccess) e = hipGetLastError();
             if (e == hipSuccess) e = hipEventRecord(s->ev[1], dst);
             if (e != hipSuccess) {
@@ -1167,19 +1270,24 @@ static int ffs_submit_compressed_impl(ffs_stream* s, const void* const* chunks, 
     return FFS_OK;
 }
 
-extern "C" int ffs_decode_only(ffs_stream* s, const void* const* chunks, const size_t* chunk_bytes, uint32_t n_frames,
-                               uint32_t iters, float* ms_decode, void* host_out) {
+extern "C" int ffs_decode_only_encoded(ffs_stream* s, int codec, const void* const* chunks, const size_t* chunk_bytes, uint32_t n_frames,
+                                       uint32_t iters, float* ms_decode, void* host_out) {
     if (!s || !chunks || !chunk_bytes || iters == 0) return FFS_ERR_INVALID;
     ffs_ctx* c = s->ctx;
     if (s->busy || n_frames == 0 || n_frames > s->max_batch) {
         c->err = "ffs_decode_only: stream busy or n_frames out of range";
         return FFS_ERR_INVALID;
     }
+    if (!codec_known(c, codec, "ffs_decode_only_encoded")) return FFS_ERR_INVALID;
     const Layout& L = c->L;
     HIP_TRY(c, hipSetDevice(c->device));
     std::vector<size_t> base;
-    int rc = stage_chunks(s, chunks, chunk_bytes, n_frames, base);
-    if (rc == FFS_OK) {
+    int rc = stage_chunks(s, codec, chunks, chunk_bytes, n_frames, base);
+    uint32_t bo_max_tiles = 0;
+    if (rc == FFS_OK && codec == FFS_CODEC_BYTE_OFFSET) {
+        rc = prepare_byte_offset(s, base, chunk_bytes, n_frames, bo_max_tiles);
+        if (rc == FFS_OK) HIP_TRY(c, hipMemcpyAsync(s->d_bo_frames, s->h_bo_frames, (size_t)n_frames * sizeof(uint4), hipMemcpyHostToDevice, s->st_up));
+    } else if (rc == FFS_OK) {
         std::string err;
         rc = index_blocks(s, base, std::vector<size_t>(chunk_bytes, chunk_bytes + n_frames), err, s->st_up);
         if (rc != FFS_OK) c->err = err;
@@ -1190,7 +1298,10 @@ extern "C" int ffs_decode_only(ffs_stream* s, const void* const* chunks, const s
     }
     (void)hipGetLastError();
     HIP_TRY(c, hipEventRecord(s->ev[0], s->st_up));
-    for (uint32_t i = 0; i < iters; ++i) launch_decode(s, n_frames, s->st_up);
+    for (uint32_t i = 0; i < iters; ++i) {
+        if (codec == FFS_CODEC_BYTE_OFFSET) HIP_TRY(c, launch_byte_offset(s, n_frames, bo_max_tiles, s->st_up, false));
+        else launch_decode(s, n_frames, s->st_up);
+    }
     HIP_TRY(c, hipEventRecord(s->ev[1], s->st_up));
     HIP_TRY(c, hipGetLastError());
     uint32_t flag = 0;
@@ -1203,16 +1314,26 @@ extern "C" int ffs_decode_only(ffs_stream* s, const void* const* chunks, const s
         const size_t row = (size_t)L.W * c->pixel_bytes;
         HIP_TRY(c, hipMemcpy2D(host_out, row, s->d_img, L.pitch, row, (size_t)L.H * n_frames, hipMemcpyDeviceToHost));
     }
-    if (flag & kOvfCorruptLz4) {
+    if (flag & (kOvfCorruptLz4 | kOvfCorruptByteOffset)) {
         HIP_TRY(c, hipMemset(s->d_overflow, 0, 4));
-        c->err = "corrupt bitshuffle-LZ4 chunk: an LZ4 block did not decode to its block size";
+        c->err = (flag & kOvfCorruptLz4) ? "corrupt bitshuffle-LZ4 chunk: an LZ4 block did not decode to its block size"
+                                         : "corrupt byte-offset chunk: it holds fewer elements than the frame has pixels";
         return FFS_ERR_INVALID;
     }
     return FFS_OK;
+}
+extern "C" int ffs_decode_only(ffs_stream* s, const void* const* chunks, const size_t* chunk_bytes, uint32_t n_frames,
+                               uint32_t iters, float* ms_decode, void* host_out) {
+    return ffs_decode_only_encoded(s, FFS_CODEC_BSLZ4, chunks, chunk_bytes, n_frames, iters, ms_decode, host_out);
 }
 
 extern "C" int ffs_submit_compressed(ffs_stream* s, const void* const* chunks, const size_t* chunk_bytes,
                                      uint32_t n_frames, int64_t first_frame_id) {
     if (!s || !stream_handle_ok(s)) return FFS_ERR_INVALID;
-    return guarded(s->ctx, [&] { return ffs_submit_compressed_impl(s, chunks, chunk_bytes, n_frames, first_frame_id); });
+    return guarded(s->ctx, [&] { return ffs_submit_encoded_impl(s, FFS_CODEC_BSLZ4, chunks, chunk_bytes, n_frames, first_frame_id); });
+}
+extern "C" int ffs_submit_encoded(ffs_stream* s, int codec, const void* const* chunks, const size_t* chunk_bytes,
+                                  uint32_t n_frames, int64_t first_frame_id) {
+    if (!s || !stream_handle_ok(s)) return FFS_ERR_INVALID;
+    return guarded(s->ctx, [&] { return ffs_submit_encoded_impl(s, codec, chunks, chunk_bytes, n_frames, first_frame_id); });
 }

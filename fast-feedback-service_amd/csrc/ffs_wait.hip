@@ -325,6 +325,10 @@ static Recovery decide_recovery(ffs_stream* s, uint32_t overflow) {
         s->ctx->err = "corrupt bitshuffle-LZ4 chunk: an LZ4 block did not decode to its block size";
         return {Recovery::kFail, {}};
     }
+    if (overflow & kOvfCorruptByteOffset) {
+        s->ctx->err = "corrupt byte-offset chunk: it holds fewer elements than the frame has pixels";
+        return {Recovery::kFail, {}};
+    }
     if (overflow & kOvfBrightList) {
         // more bright-window pixels than the list k_stream_u16 hands to k_bright_fix holds (a batch of
         // saturated frames): run the batch again with those pixels marked in the plane as candidates for the exact kernel

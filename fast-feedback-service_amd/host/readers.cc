@@ -159,7 +159,10 @@ class CBFRead : public Reader {
         const size_t at = data.find(marker);
         if (at == std::string::npos) return {dst.data(), 0};
         const size_t start = at + marker.size(), n = data.size() - start;
-        if (n > dst.size()) return {dst.data(), 0};
+        if (n > dst.size()) {   // a cut read fills its buffer, as a read() of the other sources does: the driver sees it by its size
+            std::memcpy(dst.data(), data.data() + start, dst.size());
+            return dst;
+        }
         std::memcpy(dst.data(), data.data() + start, n);
         return {dst.data(), n};
     }

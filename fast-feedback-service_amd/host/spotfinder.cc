@@ -97,7 +97,7 @@ static void usage() {
       "--read-only: (diagnostic) read every chunk into the staging areas and submit nothing\n"
       "environment, A/B only: FFS_SHM_PLAIN_READ=1 -- /dev/shm chunks by read() straight into the staging area instead of\n"
       "              through a cache-resident bounce buffer and non-temporal stores\n"
-      "--cpu-decode: decompress bitshuffle-LZ4 chunks on the worker thread (the reference's way) instead\n"
+      "--cpu-decode: decompress the frames' chunks (bitshuffle-LZ4, CBF byte-offset) on the worker thread (the reference's way) instead\n"
       "              of sending them to the GPU as they are\n"
       "FILE: NXmx .nxs/.h5 (needs an HDF5 build), a /dev/shm directory, a ####.cbf template, or\n"
       "      synth:<eiger16m|jungfrau9m|plumbing1k|sweep16m|tiny|tinysweep>[:n_images[:seed]]\n");
@@ -521,9 +521,11 @@ int main(int argc, char** argv) {
     stamp("frame source opened, header read");
 
     // ---- device context -------------------------------------------------------------------------------
-    // bitshuffle-LZ4 chunks go to the GPU as they are (read straight into the pinned staging area) unless the pixels are
-    // needed on the host (--writeout) or --cpu-decode asks for the reference's way
-    const bool gpu_decode = reader.get_raw_chunk_compression() == Reader::BITSHUFFLE_LZ4 && !args.cpu_decode && !args.writeout;
+    // bitshuffle-LZ4 chunks and CBF byte-offset sections go to the GPU as they are (read straight into the pinned staging area)
+    // unless the pixels are needed on the host (--writeout) or --cpu-decode asks for the reference's way
+    const bool byte_offset = reader.get_raw_chunk_compression() == Reader::BYTE_OFFSET_32;
+    const bool gpu_decode = (reader.get_raw_chunk_compression() == Reader::BITSHUFFLE_LZ4 || byte_offset) && !args.cpu_decode && !args.writeout;
+    const int codec = byte_offset ? FFS_CODEC_BYTE_OFFSET : FFS_CODEC_BSLZ4;
     // frames per GPU batch.  Chunks: 16 for long runs (120 MB of staging per batch for Eiger-16M: the threshold kernels are tuned
     // for 16-32 frames and PCIe, not the GPU, is the limit), 8 for runs below 2048 images per GPU -- a stream's device buffers
     // (37 MB per frame of the batch) are prepared by the driver on FIRST USE at ~60 GB/s, so four assemblies of 16 frames cost a
@@ -1035,11 +1037,11 @@ int main(int argc, char** argv) {
                         A.spill[i].assign(p, p + A.chunk_len[i]);
                         A.chunk_ptr[i] = A.spill[i].data();
                     }
-            const int sub = gpu_decode ? ffs_submit_compressed(A.s, A.chunk_ptr.data(), A.chunk_len.data(), n, first)
+            const int sub = gpu_decode ? ffs_submit_encoded(A.s, codec, A.chunk_ptr.data(), A.chunk_len.data(), n, first)
                                        : ffs_submit(A.s, A.host, n, first);
             if (sub != FFS_OK) { fail("", G.ctx); return false; }
             if (A.v) {   // the same input through the validation context
-                const int vsub = gpu_decode ? ffs_submit_compressed(A.v, A.chunk_ptr.data(), A.chunk_len.data(), n, first)
+                const int vsub = gpu_decode ? ffs_submit_encoded(A.v, codec, A.chunk_ptr.data(), A.chunk_len.data(), n, first)
                                             : ffs_submit(A.v, A.host, n, first);
                 if (vsub != FFS_OK) { fail("validation pass: ", G.vctx); return false; }
             }
@@ -1096,7 +1098,8 @@ int main(int argc, char** argv) {
         if (node_known[di]) (void)pthread_setaffinity_np(pthread_self(), sizeof(cpu_set_t), &node_cpus[di]);
         // scratch: a chunk whose size nobody knows yet; chunks the CPU decodes.  NOT value-initialised: a vector of this size
         // zero-fills 72 MB (10 ms of page faults on the clock, for a chunk of 7 MB)
-        const size_t raw_bytes = frame_bytes * (bytes_per_pixel == 2 ? 2 : 1) + 4096;
+        // (a byte-offset section: seven bytes per pixel at the most -- what a read cuts off behind that is never parsed)
+        const size_t raw_bytes = byte_offset ? (size_t)7 * width * height + 4096 : frame_bytes * (bytes_per_pixel == 2 ? 2 : 1) + 4096;
         std::unique_ptr<uint8_t[]> raw;
         auto scratch = [&]() -> std::span<uint8_t> {
             if (!raw) raw.reset(new uint8_t[raw_bytes]);
@@ -1280,7 +1283,7 @@ int main(int argc, char** argv) {
         // How many of the -n threads read.  The reference needs one thread per frame in flight because its threads decompress
         // (service.py passes --threads 40); here a reader only moves chunks from the frame source into pinned memory, and eight
         // per GPU saturate PCIe (tools/cli_profile.sh) -- beyond that they contend for the page cache's locks.  Threads that
-        // decompress on the host (--cpu-decode, CBF, --writeout) are all used.
+        // decompress on the host (--cpu-decode, --writeout) are all used.
         uint32_t n_workers = args.threads;
         if (gpu_decode && !args.all_threads) n_workers = std::min<uint32_t>(n_workers, 8 * n_dev);
         n_workers = std::max(n_workers, n_dev);

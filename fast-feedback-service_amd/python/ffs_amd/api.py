@@ -74,6 +74,9 @@ _FRAME_RESULT_DT = np.dtype({"names": ["frame_id", "num_strong_pixels", "num_str
                                          ("frame_id", "num_strong_pixels", "num_strong_pixels_filtered", "n_components", "n_boxes", "n_reflections")],
                              "itemsize": C.sizeof(_FrameResult)})
 
+CODEC_BSLZ4 = 0         # FFS_CODEC_*: what Stream.submit_encoded / decode_only take
+CODEC_BYTE_OFFSET = 1
+
 # every symbol include/ffs_hip.h declares (tests check the library exports them all)
 EXPORTS = [
     "ffs_default_params", "ffs_device_count", "ffs_device_name", "ffs_device_total_mem",
@@ -81,7 +84,7 @@ EXPORTS = [
     "ffs_ctx_apply_resolution_mask", "ffs_ctx_get_mask", "ffs_ctx_set_params",
     "ffs_stream_create", "ffs_stream_destroy", "ffs_stream_host_buffer", "ffs_submit",
     "ffs_submit_device", "ffs_ctx_device_layout", "ffs_wait", "ffs_stream_batch_arrays", "ffs_stream_timings",
-    "ffs_submit_compressed", "ffs_decode_only", "ffs_stream_spot_centres", "ffs_bench_threshold", "ffs_bench_hbm", "ffs_stream_debug_planes", "ffs_stream_debug_bitplane", "ffs_selftest_sqrt", "ffs_stack3d_create",
+    "ffs_submit_compressed", "ffs_decode_only", "ffs_submit_encoded", "ffs_decode_only_encoded", "ffs_stream_spot_centres", "ffs_bench_threshold", "ffs_bench_hbm", "ffs_stream_debug_planes", "ffs_stream_debug_bitplane", "ffs_selftest_sqrt", "ffs_stack3d_create",
     "ffs_stack3d_destroy", "ffs_stack3d_add_batch", "ffs_stack3d_add_slice", "ffs_stack3d_finish", "ffs_stack3d_signals", "ffs_stack3d_last_finish_ms", "ffs_multi_init", "ffs_multi_transport",
     "ffs_ctx_set_tuning", "ffs_bench_pipeline", "ffs_device_numa_node", "ffs_stream_reserve_host", "ffs_stream_last_path", "ffs_multi_gather_rows",
 ]
@@ -134,6 +137,9 @@ def load_library():
         L.ffs_submit_compressed.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int64]
         L.ffs_decode_only.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32,
                                       C.POINTER(C.c_float), C.c_void_p]
+        L.ffs_submit_encoded.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int64]
+        L.ffs_decode_only_encoded.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32,
+                                              C.POINTER(C.c_float), C.c_void_p]
         L.ffs_stack3d_signals.argtypes = [C.c_void_p] * 7
         L.ffs_stream_debug_bitplane.argtypes = [C.c_void_p, C.c_uint32, C.c_int, C.c_void_p]
         L.ffs_selftest_sqrt.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.POINTER(C.c_uint64)]
@@ -315,13 +321,24 @@ class Stream:
         self.submit_compressed(chunks, first_frame_id)
         return self.wait()
 
-    def decode_only(self, chunks, iters: int = 1, want_frames: bool = True):
-        """GPU decode alone: (average ms per launch, decoded frames or None)."""
+    def submit_encoded(self, chunks, codec: int, first_frame_id: int = 0):
+        """chunks: one per frame, in `codec` (CODEC_BSLZ4: as submit_compressed; CODEC_BYTE_OFFSET: a CBF binary section, the
+        bytes behind its marker)."""
+        self._keep, ptrs, sizes = self._chunk_args(chunks)
+        self.ctx._check(self._lib.ffs_submit_encoded(self._h, codec, ptrs, sizes, len(self._keep), first_frame_id))
+        self._snapshot()
+
+    def process_encoded(self, chunks, codec: int, first_frame_id: int = 0):
+        self.submit_encoded(chunks, codec, first_frame_id)
+        return self.wait()
+
+    def decode_only(self, chunks, iters: int = 1, want_frames: bool = True, codec: int = CODEC_BSLZ4):
+        """GPU decode alone: (average ms per decode -- one launch, byte-offset: its three --, decoded frames or None)."""
         keep, ptrs, sizes = self._chunk_args(chunks)
         ms = C.c_float()
         out = np.empty((len(keep), self.ctx.H, self.ctx.W), self.ctx.dtype) if want_frames else None
-        self.ctx._check(self._lib.ffs_decode_only(self._h, ptrs, sizes, len(keep), iters, C.byref(ms),
-                                                  out.ctypes.data_as(C.c_void_p) if want_frames else None))
+        self.ctx._check(self._lib.ffs_decode_only_encoded(self._h, codec, ptrs, sizes, len(keep), iters, C.byref(ms),
+                                                          out.ctypes.data_as(C.c_void_p) if want_frames else None))
         return ms.value, out
 
     def submit(self, frames: np.ndarray, first_frame_id: int = 0):

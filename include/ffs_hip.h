@@ -274,6 +274,25 @@ int ffs_submit_compressed(ffs_stream *s, const void *const *chunks, const size_t
 int ffs_decode_only(ffs_stream *s, const void *const *chunks, const size_t *chunk_bytes,
                     uint32_t n_frames, uint32_t iters, float *ms_decode, void *host_out);
 
+/* The two entries above for any codec of the frames' chunks.
+ * FFS_CODEC_BSLZ4: exactly ffs_submit_compressed / ffs_decode_only.
+ * FFS_CODEC_BYTE_OFFSET: miniCBF (Pilatus) frames.  chunks[i] is the binary section as it lies in the file -- everything behind the
+ * 0c 1a 04 d5 marker to the end of the file, what CBFRead::get_raw_chunk returns: no header, and bytes behind the last element
+ * (padding, the MIME trailer), which are ignored -- and is decoded on the GPU into the context's pixel type: replaces
+ * decompress_byte_offset on the reading thread (cbfread.hpp:49-106, called from CBFRead::get_image) and the upload of the raw
+ * frame (spotfinder.cc:846-862).  Placement as for ffs_submit_compressed (anywhere, or all of them inside the stream's host
+ * buffer).  A chunk shorter than width*height bytes cannot hold a frame and is refused here (FFS_ERR_INVALID, "byte-offset ...");
+ * a chunk that ends before its last element is reported by ffs_wait / ffs_decode_only_encoded (FFS_ERR_INVALID, "corrupt
+ * byte-offset chunk"), its missing pixels are zeros.  Any other codec: FFS_ERR_INVALID. */
+#define FFS_CODEC_BSLZ4 0        /* what ffs_submit_compressed / ffs_decode_only take */
+#define FFS_CODEC_BYTE_OFFSET 1  /* CBF byte-offset, cbfread.hpp:49-106; chunk = bytes after the binary marker */
+int ffs_submit_encoded(ffs_stream *s, int codec, const void *const *chunks, const size_t *chunk_bytes,
+                       uint32_t n_frames, int64_t first_frame_id);
+/* ffs_decode_only for any codec (byte-offset: the three decode launches of kernels_byteoffset.hpp are timed together) --
+ * the GPU's side of what cbfread.hpp:49-106 does per frame. */
+int ffs_decode_only_encoded(ffs_stream *s, int codec, const void *const *chunks, const size_t *chunk_bytes,
+                            uint32_t n_frames, uint32_t iters, float *ms_decode, void *host_out);
+
 /* (ffs_wait turns the batch's records into the arrays below; for large batches the frames are spread over the calling thread and
  * three helper threads that belong to the context -- created on first use, joined by ffs_ctx_destroy.) */
 int ffs_wait(ffs_stream *s, const ffs_frame_result **results, uint32_t *n_results);
