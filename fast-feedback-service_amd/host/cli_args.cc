@@ -1,0 +1,178 @@
+// cli_args.cc -- see cli_args.hpp
+#include "cli_args.hpp"
+
+#include <algorithm>
+#include <cstdio>
+#include <cstdlib>
+#include <filesystem>
+#include <fstream>
+#include <sstream>
+
+#include "ffs_hip.h"
+
+namespace fs = std::filesystem;
+
+namespace ffshost {
+
+void usage() {
+    std::printf(
+      "Usage: spotfinder [-h] [--version] [-v] [-d DEVICE] [--list-devices] [--sample | FILE.nxs]\n"
+      "                  [-n NUM] [--validate] [--images NUM] [--writeout] [--min-spot-size N]\n"
+      "                  [--min-spot-size-3d N] [--max-peak-centroid-separation N] [--start-index N]\n"
+      "                  [-t S] [-fd FD] [-a ALGO] [--dmin MIN D] [--dmax MAX D] [-w \xce\xbb] [--detector JSON]\n"
+      "                  [-h5] [--output-for-index] [--batch N] [--cpu-decode] [--strict-dtype]\n"
+      "                  [--max-valid trusted|none|N] [--min-count N] [--kernel-size N | NX,NY]\n"
+      "                  [--devices D0,D1,... | --gpus N] [--no-numa-pinning] [--single-buffer] [--all-threads] [--read-only] [--clean-exit]\n"
+      "--max-valid: a centre pixel above this value is never strong (the reference's kernels test it against the\n"
+      "              data set's trusted maximum).  trusted (default) = the frame source's trusted-range maximum when it is\n"
+      "              below the pixel type's maximum, none = no test (the CPU baseline's behaviour), N = this value\n"
+      "--min-count: valid pixels a window needs (default 2, the CPU baseline's; the reference's kernels use 3)\n"
+      "--kernel-size: half-size of the dispersion window, both axes (N) or along x and y (NX,NY), each 1..7 (default 3:\n"
+      "              the 7x7 window; DIALS spotfinder.threshold.dispersion.kernel_size).  Not with -a dispersion_extended\n"
+      "--validate:  every image is also decided by an independent path (every valid pixel's window gathered from memory,\n"
+      "              no streaming kernel) and the two strong-pixel masks are compared: Match / Mismatch per image\n"
+      "--devices / --gpus: one context and worker pool per GPU, all pulling frames from the one queue\n"
+      "              (-n threads are dealt round-robin to the GPUs, at least one each); rotation sweeps send\n"
+      "              their strong-pixel lists to the first GPU's 3D stack (RCCL over xGMI, else peer copies)\n"
+      "--all-threads: every one of the -n threads reads (default: at most eight per GPU when chunks are decoded there)\n"
+      "--gather host|rccl: with several GPUs and --output-for-index, where the spot centres of a round of batches (one per GPU) are\n"
+      "              collected: read from each context's host arrays (default: seven times cheaper inside one process), or gathered\n"
+      "              over RCCL to the first GPU (counts by all-gather, rows by send / recv, one copy to the host)\n"
+      "--clean-exit: destroy streams and contexts and let the runtime tear itself down before the process ends (default: the\n"
+      "              process leaves as soon as its last result is out -- a request's wall time ends there)\n"
+      "--batch N:   frames per GPU batch (default 16 chunks / 4 decoded frames); a batch is filled by all readers of its GPU\n"
+      "--single-buffer: one batch per GPU at a time (default: four of chunks / three of decoded frames, filled while the others are on the GPU)\n"
+      "--read-only: (diagnostic) read every chunk into the staging areas and submit nothing\n"
+      "environment, A/B only: FFS_SHM_PLAIN_READ=1 -- /dev/shm chunks by read() straight into the staging area instead of\n"
+      "              through a cache-resident bounce buffer and non-temporal stores\n"
+      "--cpu-decode: decompress the frames' chunks (bitshuffle-LZ4, CBF byte-offset) on the worker thread (the reference's way) instead\n"
+      "              of sending them to the GPU as they are\n"
+      "FILE: NXmx .nxs/.h5 (needs an HDF5 build), a /dev/shm directory, a ####.cbf template, or\n"
+      "      synth:<eiger16m|jungfrau9m|plumbing1k|sweep16m|tiny|tinysweep>[:n_images[:seed]]\n");
+}
+
+[[noreturn]] void arg_error(const std::string& m) {  // arg_parser.cc:72-77
+    std::printf("Error: %s\n", m.c_str());
+    usage();
+    std::exit(1);
+}
+
+static void list_devices() {  // cuda_arg_parser.cc:39-53
+    const int n = ffs_device_count();
+    for (int i = 0; i < n; ++i) {
+        char name[256];
+        ffs_device_name(i, name, sizeof name);
+        std::printf("%d: %s\n", i, name);
+    }
+    std::exit(0);
+}
+
+Args parse_args(int argc, char** argv) {
+    std::vector<std::string> a(argv + 1, argv + argc);
+    if (fs::exists("common.args")) {  // arg_parser.cc:57-71
+        std::ifstream f("common.args");
+        std::string line;
+        while (std::getline(f, line))
+            if (!line.empty() && std::find(a.begin(), a.end(), line) == a.end()) a.push_back(line);
+    }
+    Args r;
+    if (const char* e = std::getenv("SPOTFINDER_TIMEOUT")) {  // spotfinder.cc:293-301
+        try { r.timeout = std::stof(e); } catch (...) { std::printf("Ignoring invalid SPOTFINDER_TIMEOUT value: %s\n", e); }
+    }
+    auto need = [&a](size_t& i, const std::string& flag) -> const std::string& {
+        if (i + 1 >= a.size()) arg_error("Too few arguments for '" + flag + "'.");
+        return a[++i];
+    };
+    auto u32 = [](const std::string& v, const std::string& flag) {
+        try { size_t used; long long x = std::stoll(v, &used); if (used != v.size() || x < 0) throw 1; return (uint32_t)x; }
+        catch (...) { arg_error("pattern not found for '" + flag + "': " + v); }
+    };
+    auto f32 = [](const std::string& v, const std::string& flag) {
+        try { size_t used; float x = std::stof(v, &used); if (used != v.size()) throw 1; return x; }
+        catch (...) { arg_error("pattern not found for '" + flag + "': " + v); }
+    };
+    for (size_t i = 0; i < a.size(); ++i) {
+        const std::string& s = a[i];
+        if (s == "-h" || s == "--help") { usage(); std::exit(0); }
+        else if (s == "--version") { std::printf("%s\n", FFS_VERSION); std::exit(0); }
+        else if (s == "-v" || s == "--verbose") r.verbose = true;
+        else if (s == "--list-devices") list_devices();
+        else if (s == "-d" || s == "--device") r.device = (int)u32(need(i, s), s);
+        else if (s == "--sample") r.sample = true;
+        else if (s == "-n" || s == "--threads") r.threads = u32(need(i, s), s);
+        else if (s == "--validate") r.validate = true;
+        else if (s == "--images") { r.images = u32(need(i, s), s); r.images_set = true; }
+        else if (s == "--writeout") r.writeout = true;
+        else if (s == "--min-spot-size") r.min_spot_size = u32(need(i, s), s);
+        else if (s == "--min-spot-size-3d") r.min_spot_size_3d = u32(need(i, s), s);
+        else if (s == "--max-peak-centroid-separation") r.max_sep = f32(need(i, s), s);
+        else if (s == "--start-index") r.start_index = u32(need(i, s), s);
+        else if (s == "-t" || s == "--timeout") r.timeout = f32(need(i, s), s);
+        else if (s == "-fd" || s == "--pipe_fd") r.pipe_fd = std::stoi(need(i, s));
+        else if (s == "-a" || s == "--algorithm") r.algorithm = need(i, s);
+        else if (s == "--cpu-decode") r.cpu_decode = true;
+        else if (s == "--dmin") r.dmin = f32(need(i, s), s);
+        else if (s == "--dmax") r.dmax = f32(need(i, s), s);
+        else if (s == "-w" || s == "--wavelength" || s == "-\xce\xbb") { r.wavelength = f32(need(i, s), s); r.wavelength_set = true; }
+        else if (s == "--detector") { r.detector_json = need(i, s); r.detector_set = true; }
+        else if (s == "-h5" || s == "--save-h5") r.save_h5 = true;
+        else if (s == "--output-for-index") r.output_for_index = true;
+        else if (s == "--batch") r.batch = u32(need(i, s), s);
+        else if (s == "--assemblies") r.assemblies = u32(need(i, s), s);   // batches in flight per GPU (tuning; default below)
+        else if (s == "--slot-margin") r.slot_margin = f32(need(i, s), s);  // per cent of head room per chunk slot (tuning)
+        else if (s == "--gpus") { const uint32_t n = u32(need(i, s), s); r.devices.clear(); for (uint32_t d = 0; d < n; ++d) r.devices.push_back((int)d); }
+        else if (s == "--devices") {
+            r.devices.clear();
+            std::stringstream ss(need(i, s));
+            std::string tok;
+            while (std::getline(ss, tok, ',')) r.devices.push_back((int)u32(tok, s));
+        }
+        else if (s == "--gather") { r.gather = need(i, s); if (r.gather != "host" && r.gather != "rccl") arg_error("--gather takes host or rccl"); }
+        else if (s == "--strict-dtype") r.strict_dtype = true;
+        else if (s == "--max-valid") {
+            r.max_valid = need(i, s);
+            if (r.max_valid != "trusted" && r.max_valid != "none") (void)u32(r.max_valid, s);
+        }
+        else if (s == "--kernel-size") {
+            const std::string& v = need(i, s);
+            const size_t comma = v.find(',');
+            auto half = [&u32, &s, &v](const std::string& t) {
+                const uint32_t k = u32(t, s);
+                if (k < 1 || k > 7) arg_error("--kernel-size takes half-sizes 1..7: " + v);
+                return (int)k;
+            };
+            if (comma == std::string::npos) r.kernel_half_x = r.kernel_half_y = half(v);
+            else {
+                r.kernel_half_x = half(v.substr(0, comma));
+                r.kernel_half_y = half(v.substr(comma + 1));
+            }
+        }
+        else if (s == "--min-count") { r.min_count = u32(need(i, s), s); if (r.min_count < 2) arg_error("--min-count must be at least 2"); }
+        else if (s == "--no-numa-pinning") r.no_numa_pinning = true;
+        else if (s == "--single-buffer") r.single_buffer = true;
+        else if (s == "--read-only") r.read_only = true;   // diagnostic: frames are read into the staging buffers and not submitted
+        else if (s == "--all-threads") r.all_threads = true;
+        else if (s == "--clean-exit") r.clean_exit = true;
+        else if (!s.empty() && s[0] == '-' && s.size() > 1) arg_error("Unknown argument: " + s);
+        else if (r.file.empty()) r.file = s;
+        else arg_error("Maximum number of positional arguments exceeded");
+    }
+    const bool implicit_sample = std::getenv("H5READ_IMPLICIT_SAMPLE") != nullptr;  // spotfinder.cc:268-283
+    if (r.sample && !r.file.empty()) arg_error("Argument 'FILE.nxs' not allowed with '--sample'");
+    if (!r.sample && r.file.empty() && !implicit_sample) arg_error("One of the arguments '--sample' or 'FILE.nxs' is required");
+    if (r.file.empty()) r.sample = true;
+    std::string lower = r.algorithm;   // DispersionAlgorithm, spotfinder.cc:180-203
+    std::transform(lower.begin(), lower.end(), lower.begin(), [](unsigned char ch) { return (char)std::tolower(ch); });
+    if (lower == "dispersion") r.algo = FFS_ALGO_DISPERSION;
+    else if (lower == "dispersion_extended") {
+        if (r.kernel_half_x != 3 || r.kernel_half_y != 3)
+            arg_error("--kernel-size other than 3 is not available with the dispersion_extended algorithm");
+        r.algo = FFS_ALGO_DISPERSION_EXTENDED;
+    } else {
+        std::printf("Error: Invalid algorithm specified\n");
+        std::exit(1);
+    }
+    return r;
+}
+
+}  // namespace ffshost

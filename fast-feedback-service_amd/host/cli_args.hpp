@@ -1,0 +1,36 @@
+// cli_args.hpp -- the spotfinder driver's command line (spotfinder.cc:291-398, src/ffs/arg_parser.cc, src/ffs/cuda_arg_parser.cc)
+#pragma once
+#include <cstdint>
+#include <string>
+#include <vector>
+
+#ifndef FFS_VERSION
+#define FFS_VERSION "ffs-mi355x 0.1 (gfx950)"
+#endif
+
+namespace ffshost {
+
+struct Args {
+    std::string file;
+    bool sample = false, validate = false, writeout = false, save_h5 = false, output_for_index = false;
+    bool verbose = false, strict_dtype = false;
+    uint32_t threads = 1, images = 0, min_spot_size = 3, min_spot_size_3d = 3, start_index = 0, batch = 0, assemblies = 0;
+    bool images_set = false, wavelength_set = false, detector_set = false;
+    float max_sep = 2.0f, timeout = 30.0f, dmin = -1.f, dmax = -1.f, wavelength = 0.f, slot_margin = 2.0f;
+    int pipe_fd = -1, device = 0;
+    std::vector<int> devices;  // --devices / --gpus: the frame queue is dealt to all of them
+    std::string algorithm = "dispersion", detector_json, gather = "host";
+    int algo = 0;   // FFS_ALGO_*: `algorithm`, lower-cased and checked by parse_args
+    std::string max_valid = "trusted";   // trusted | none | N
+    uint32_t min_count = 2;
+    int kernel_half_x = 3, kernel_half_y = 3;   // --kernel-size
+    bool cpu_decode = false, no_numa_pinning = false, single_buffer = false, all_threads = false, read_only = false, clean_exit = false;
+};
+
+void usage();
+[[noreturn]] void arg_error(const std::string& m);   // "Error: ...", the usage text, exit code 1
+// Exits by itself for -h, --version, --list-devices and on every error (usage errors: arg_error; an algorithm
+// that does not exist: "Error: Invalid algorithm specified", exit code 1).
+Args parse_args(int argc, char** argv);
+
+}  // namespace ffshost
