@@ -416,7 +416,27 @@ extern "C" int ffs_ctx_set_params(ffs_ctx* c, const ffs_params* p) {
         c->err = "ffs_ctx_set_params: unknown algorithm / extended_flavour";
         return FFS_ERR_INVALID;
     }
+    if (p->extended_flavour == 1 && c->max_valid_scope == FFS_MAX_VALID_WINDOW) {
+        c->err = "ffs_ctx_set_params: extended_flavour 1 cannot be combined with the window scope of max_valid (ffs_ctx_set_max_valid_scope): "
+                 "the device-flavour erosion skips masked neighbours by the static mask";
+        return FFS_ERR_INVALID;
+    }
     c->params = *p;
+    return FFS_OK;
+}
+
+extern "C" int ffs_ctx_set_max_valid_scope(ffs_ctx* c, int scope) {
+    if (!c) return FFS_ERR_INVALID;
+    if (scope != FFS_MAX_VALID_CENTRE && scope != FFS_MAX_VALID_WINDOW) {
+        c->err = "ffs_ctx_set_max_valid_scope: scope must be FFS_MAX_VALID_CENTRE (0) or FFS_MAX_VALID_WINDOW (1)";
+        return FFS_ERR_INVALID;
+    }
+    if (scope == FFS_MAX_VALID_WINDOW && c->params.extended_flavour == 1) {
+        c->err = "ffs_ctx_set_max_valid_scope: the window scope cannot be combined with extended_flavour 1: the device-flavour erosion "
+                 "skips masked neighbours by the static mask";
+        return FFS_ERR_INVALID;
+    }
+    c->max_valid_scope = scope;
     return FFS_OK;
 }
 

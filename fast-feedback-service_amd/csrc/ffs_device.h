@@ -33,6 +33,12 @@ struct ThresholdArgs {
     const void* image;         // device pixels
     uint64_t frame_stride;     // bytes
     uint32_t pitch;            // bytes
+    // The neighbour limit, exclusive (ffs_ctx_set_max_valid_scope): a pixel p >= nb_limit is left out of the
+    // count and the sums of every window.  Centre scope: 2^24, the oracle's rule for 32-bit pixels (standalone.cc:78,90), and no kernel
+    // of 16-bit pixels reads it.  Window scope with max_valid >= 0: min(max_valid, 2^24 - 1) + 1 (16-bit pixels: at most 65536), read
+    // by the general-window kernel, k_ext_first, and the TRUSTED instantiations of the gathered predicates.  (It fills the four bytes
+    // of padding between `pitch` and `maskbits`.)
+    uint32_t nb_limit;
     const uint8_t* maskbits;   // valid-pixel bit plane [H][mpitch]
     uint8_t* bits;             // candidate / strong bit planes [n][H][mpitch]
     uint8_t* strong_bytes;     // byte masks [n][H][bpitch]

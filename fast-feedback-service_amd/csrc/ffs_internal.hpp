@@ -119,6 +119,7 @@ struct ffs_ctx {
     uint32_t max_comp = 0;  // components per frame
     int n_tiles = 0;
     ffs_params params{};
+    int max_valid_scope = FFS_MAX_VALID_CENTRE;   // ffs_ctx_set_max_valid_scope: kept across ffs_ctx_set_params, snapshot per batch with the parameters
     uint8_t* d_maskbits = nullptr;
     uint8_t* d_ginfo = nullptr;  // per-group mask bits + window-count bounds (kernels_stream.hpp)
     uint8_t* d_mmap = nullptr;   // per-pixel window counts
@@ -266,6 +267,7 @@ struct ffs_stream {
     const void* cur_img = nullptr;
     size_t cur_pitch = 0, cur_fstride = 0;
     ffs_params batch_params{};
+    int batch_scope = FFS_MAX_VALID_CENTRE;   // ... and the scope of max_valid the batch was submitted under (re-runs inside ffs_wait keep it)
     float timings[5] = {0, 0, 0, 0, 0};
     bool timings_stale = false;              // the stage times of the last batch are still in its events (ffs_stream_timings reads them out)
     hipEvent_t timing_last = nullptr;
@@ -333,6 +335,11 @@ static int guarded(ffs_ctx* c, F&& body) {
     } while (0)
 
 // ---- small helpers ------------------------------------------------------------------------------------------
+// What a batch is computed with: the context's parameters and its scope of max_valid as they were at submit.
+struct ParamSnapshot {
+    ffs_params params;
+    int max_valid_scope;
+};
 // What ffs_wait asks of the enqueue that runs a batch AGAIN because a plan did not hold it (ffs_wait.hip, rerun_batch); the default
 // is a normal batch.  An argument of that one call: what a stream remembers beyond it (log_off, runs_overflowed, band_backoff) is
 // in ffs_stream.
@@ -398,7 +405,7 @@ StreamGeometry batch_stream_geometry(const ffs_stream* s, size_t fstride, uint32
 ThresholdArgs make_threshold_args(ffs_stream* s, const void* img, size_t pitch, size_t fstride, uint32_t n_frames, const StreamGeometry& g, const Rerun& how);
 int check_layout(ffs_stream* s, size_t pitch, size_t fstride, uint32_t n_frames);
 int ensure_extended_buffers(ffs_stream* s);
-int enqueue_batch(ffs_stream* s, const void* d_img, size_t pitch, size_t fstride, uint32_t n, const ffs_params* snapshot = nullptr,
+int enqueue_batch(ffs_stream* s, const void* d_img, size_t pitch, size_t fstride, uint32_t n, const ParamSnapshot* snapshot = nullptr,
                   const Rerun& how = Rerun{});
 extern std::atomic<int> g_live_stacks;   // 3D stacks alive in the process (ffs_stack3d.hip)
 bool wave_logs_for(ffs_stream* s, ThresholdArgs& a, const StreamGeometry& g, const Rerun& how);

@@ -26,6 +26,8 @@ bool chain_prepare_device() {   // more than 64 KB of dynamic LDS has to be aske
 }
 
 // ---- the threshold stage's arguments: buffers and pitches, the predicate's constants, the launch geometry ------------------
+// The window scope of max_valid is on for this batch (ffs_ctx_set_max_valid_scope; without a max_valid the scope changes nothing)
+static bool trusted_window(const ffs_stream* s) { return s->batch_scope == FFS_MAX_VALID_WINDOW && s->batch_params.max_valid >= 0; }
 static void set_buffers(ThresholdArgs& a, const ffs_stream* s, const void* img, size_t pitch, size_t fstride, const Rerun& how) {
     const ffs_ctx* c = s->ctx;
     const Layout& L = c->L;
@@ -72,9 +74,12 @@ static void set_buffers(ThresholdArgs& a, const ffs_stream* s, const void* img, 
     a.dplane = s->d_dplane;
     a.eplane = s->d_eplane;
     a.eplane_clean = s->ext_e_clean ? 1 : 0;
-    a.ext_variant = (c->pixel_bytes == 2 && how.threshold_path < 0) ? c->tune.ext_first_pass : 0;
+    // (the streaming first pass reads the mask tables, which know nothing of a frame's pixels: the window scope of max_valid takes k_ext_first)
+    a.ext_variant = (c->pixel_bytes == 2 && how.threshold_path < 0 && !trusted_window(s)) ? c->tune.ext_first_pass : 0;
 }
-static void set_predicate(ThresholdArgs& a, const ffs_params& p) {
+static void set_predicate(ThresholdArgs& a, const ffs_params& p, bool trusted) {
+    // (exclusive; the oracle's < 2^24 rule for 32-bit pixels holds on top of max_valid, and 16-bit pixels never reach it)
+    a.nb_limit = trusted ? (uint32_t)std::min<long long>(p.max_valid, (1ll << 24) - 1) + 1u : 1u << 24;
     a.kS = (float)(p.nsig_s * p.nsig_s * (1.0 - 1.0 / 65536.0));
     a.kB = (float)(p.nsig_b * (1.0 - 1.0 / 1048576.0));
     a.min_count = p.min_count;
@@ -122,7 +127,7 @@ StreamGeometry batch_stream_geometry(const ffs_stream* s, size_t fstride, uint32
 ThresholdArgs make_threshold_args(ffs_stream* s, const void* img, size_t pitch, size_t fstride, uint32_t n_frames, const StreamGeometry& g, const Rerun& how) {
     ThresholdArgs a{};
     set_buffers(a, s, img, pitch, fstride, how);
-    set_predicate(a, s->batch_params);
+    set_predicate(a, s->batch_params, trusted_window(s));
     set_geometry(a, n_frames, g, window_geometry(s->ctx->L, n_frames, a.ky), ext_geometry(s->ctx->L, n_frames));
     return a;
 }
@@ -148,30 +153,32 @@ static StreamKernel stream_kernel(const ffs_ctx* c, bool dense_mask, bool extend
 static void launch_stream(ffs_stream* s, const ThresholdArgs& a, const StreamGeometry& g, hipEvent_t start, hipEvent_t stop, hipStream_t st = nullptr) {
     hipExtLaunchKernelGGL(stream_kernel(s->ctx, a.dense_mask != 0, false), stream_grid(a, g), dim3(64), 0, st ? st : s->st, start, stop, 0, a);
 }
-// The general-window kernel (kernels_window.hpp): windows other than 3,3, or every window with tuning "window_kernel" = 1.  The
+// The general-window kernel (kernels_window.hpp): windows other than 3,3, or every window with tuning "window_kernel" = 1 or under the
+// window scope of max_valid (the streaming kernels' screens rest on counts that depend on the mask alone: DESIGN.md section 3.3c).  The
 // standard algorithm on the plane paths only (no wave logs: those belong to k_stream_u16); the cross-check path (threshold_path 2)
 // keeps its gather.
 bool window_kernel_for(const ffs_stream* s, const ThresholdArgs& a) {
     return s->batch_params.algorithm == FFS_ALGO_DISPERSION && a.bright_to_plane != 2
-           && (!win_default(s->batch_params) || s->ctx->tune.window_kernel == 1);
+           && (!win_default(s->batch_params) || s->ctx->tune.window_kernel == 1 || trusted_window(s));
 }
-template <typename PixelT>
+template <typename PixelT, bool TRUSTED = false>
 static void launch_window_t(const ThresholdArgs& a, dim3 grid, hipStream_t st, hipEvent_t start, hipEvent_t stop) {
     const size_t lds = win_ring_bytes((int)sizeof(PixelT), a.ky);
     switch (a.kx) {
-        case 1: hipExtLaunchKernelGGL((k_window<PixelT, 1>), grid, dim3(64), lds, st, start, stop, 0, a); break;
-        case 2: hipExtLaunchKernelGGL((k_window<PixelT, 2>), grid, dim3(64), lds, st, start, stop, 0, a); break;
-        case 3: hipExtLaunchKernelGGL((k_window<PixelT, 3>), grid, dim3(64), lds, st, start, stop, 0, a); break;
-        case 4: hipExtLaunchKernelGGL((k_window<PixelT, 4>), grid, dim3(64), lds, st, start, stop, 0, a); break;
-        case 5: hipExtLaunchKernelGGL((k_window<PixelT, 5>), grid, dim3(64), lds, st, start, stop, 0, a); break;
-        case 6: hipExtLaunchKernelGGL((k_window<PixelT, 6>), grid, dim3(64), lds, st, start, stop, 0, a); break;
-        default: hipExtLaunchKernelGGL((k_window<PixelT, 7>), grid, dim3(64), lds, st, start, stop, 0, a); break;
+        case 1: hipExtLaunchKernelGGL((k_window<PixelT, 1, TRUSTED>), grid, dim3(64), lds, st, start, stop, 0, a); break;
+        case 2: hipExtLaunchKernelGGL((k_window<PixelT, 2, TRUSTED>), grid, dim3(64), lds, st, start, stop, 0, a); break;
+        case 3: hipExtLaunchKernelGGL((k_window<PixelT, 3, TRUSTED>), grid, dim3(64), lds, st, start, stop, 0, a); break;
+        case 4: hipExtLaunchKernelGGL((k_window<PixelT, 4, TRUSTED>), grid, dim3(64), lds, st, start, stop, 0, a); break;
+        case 5: hipExtLaunchKernelGGL((k_window<PixelT, 5, TRUSTED>), grid, dim3(64), lds, st, start, stop, 0, a); break;
+        case 6: hipExtLaunchKernelGGL((k_window<PixelT, 6, TRUSTED>), grid, dim3(64), lds, st, start, stop, 0, a); break;
+        default: hipExtLaunchKernelGGL((k_window<PixelT, 7, TRUSTED>), grid, dim3(64), lds, st, start, stop, 0, a); break;
     }
 }
 static void launch_window(ffs_stream* s, const ThresholdArgs& a, uint32_t n_frames, hipEvent_t start, hipEvent_t stop, hipStream_t st = nullptr) {
     const dim3 grid((unsigned)(a.w_strips * a.w_bands), n_frames);
     if (!st) st = s->st;
-    if (s->ctx->pixel_bytes == 4) launch_window_t<uint32_t>(a, grid, st, start, stop);
+    if (s->ctx->pixel_bytes == 4) launch_window_t<uint32_t>(a, grid, st, start, stop);   // (the neighbour limit is its argument)
+    else if (trusted_window(s)) launch_window_t<uint16_t, true>(a, grid, st, start, stop);
     else launch_window_t<uint16_t>(a, grid, st, start, stop);
 }
 static void launch_bright_fix(ffs_stream* s, const ThresholdArgs& a, hipStream_t st) {
@@ -182,12 +189,17 @@ static void launch_bright_fix(ffs_stream* s, const ThresholdArgs& a, hipStream_t
 // predicate; rewrites the plane, the per-tile counts and sets the byte mask's 1s
 static void launch_exact(ffs_stream* s, const ThresholdArgs& a, uint32_t n_frames, hipStream_t st) {
     const dim3 grid((unsigned)a.n_tiles, n_frames);
+    const bool u32 = s->ctx->pixel_bytes == 4, trusted = trusted_window(s);   // (trusted: the cross-check path, the only one that gets here with it)
     if (a.kx != 3 || a.ky != 3) {   // (the runtime-window gather: exact_strong_w)
-        if (s->ctx->pixel_bytes == 4) hipLaunchKernelGGL(k_exact_w<uint32_t>, grid, dim3(256), 0, st, a);
+        if (trusted && u32) hipLaunchKernelGGL((k_exact_w<uint32_t, true>), grid, dim3(256), 0, st, a);
+        else if (trusted) hipLaunchKernelGGL((k_exact_w<uint16_t, true>), grid, dim3(256), 0, st, a);
+        else if (u32) hipLaunchKernelGGL(k_exact_w<uint32_t>, grid, dim3(256), 0, st, a);
         else hipLaunchKernelGGL(k_exact_w<uint16_t>, grid, dim3(256), 0, st, a);
         return;
     }
-    if (s->ctx->pixel_bytes == 4) hipLaunchKernelGGL(k_exact<uint32_t>, grid, dim3(256), 0, st, a);
+    if (trusted && u32) hipLaunchKernelGGL((k_exact<uint32_t, true>), grid, dim3(256), 0, st, a);
+    else if (trusted) hipLaunchKernelGGL((k_exact<uint16_t, true>), grid, dim3(256), 0, st, a);
+    else if (u32) hipLaunchKernelGGL(k_exact<uint32_t>, grid, dim3(256), 0, st, a);
     else hipLaunchKernelGGL(k_exact<uint16_t>, grid, dim3(256), 0, st, a);
 }
 
@@ -210,17 +222,18 @@ static void launch_ext_first(ffs_stream* s, const ThresholdArgs& a, const Stream
         return;
     }
     dim3 g1((unsigned)(a.ext_strips * a.ext_bands), n_frames);
-    if (s->ctx->pixel_bytes == 2) hipExtLaunchKernelGGL(k_ext_first<uint16_t>, g1, dim3(64), 0, s->st, start, stop, 0, a);
+    if (s->ctx->pixel_bytes == 2 && trusted_window(s)) hipExtLaunchKernelGGL((k_ext_first<uint16_t, true>), g1, dim3(64), 0, s->st, start, stop, 0, a);
+    else if (s->ctx->pixel_bytes == 2) hipExtLaunchKernelGGL(k_ext_first<uint16_t>, g1, dim3(64), 0, s->st, start, stop, 0, a);
     else hipExtLaunchKernelGGL(k_ext_first<uint32_t>, g1, dim3(64), 0, s->st, start, stop, 0, a);
 }
 static void launch_ext_rest(ffs_stream* s, const ThresholdArgs& a, uint32_t n_frames, hipStream_t st) {
-    const bool u16 = s->ctx->pixel_bytes == 2;
+    const bool u16 = s->ctx->pixel_bytes == 2, trusted = trusted_window(s);
     // The byte mask: the streaming kernel zero-filled it if somebody wants it (k_ext_final sets 1s in it either way; without a
     // taker they land in a buffer nobody reads); after k_ext_first it is always produced, so zero it here.
     if (!ext_stream_first(a)) (void)hipMemsetAsync(a.strong_bytes, 0, (size_t)n_frames * a.bytes_frame_stride, st);
     dim3 g3((unsigned)a.n_tiles, n_frames);
     if (u16 && s->ctx->tune.ext_fused) {   // erosion inside the final pass's tiles: one launch, the plane crosses memory once
-        hipLaunchKernelGGL(k_ext_erode_final, g3, dim3(256), (size_t)(kTileRows + 10) * a.mpitch, st, a);
+        hipLaunchKernelGGL(trusted ? k_ext_erode_final_trusted : k_ext_erode_final, g3, dim3(256), (size_t)(kTileRows + 10) * a.mpitch, st, a);
         return;
     }
     const int erode = s->ctx->tune.ext_erode;
@@ -235,7 +248,9 @@ static void launch_ext_rest(ffs_stream* s, const ThresholdArgs& a, uint32_t n_fr
         const unsigned erode_lanes = (a.mpitch / 4) * (unsigned)((a.H + kErodeRows - 1) / kErodeRows);
         hipLaunchKernelGGL(k_ext_erode, dim3((erode_lanes + 255) / 256, n_frames), dim3(256), 0, st, a);
     }
-    if (u16) hipLaunchKernelGGL(k_ext_final<uint16_t>, g3, dim3(256), 0, st, a);
+    if (trusted && u16) hipLaunchKernelGGL(k_ext_final_trusted<uint16_t>, g3, dim3(256), 0, st, a);
+    else if (trusted) hipLaunchKernelGGL(k_ext_final_trusted<uint32_t>, g3, dim3(256), 0, st, a);
+    else if (u16) hipLaunchKernelGGL(k_ext_final<uint16_t>, g3, dim3(256), 0, st, a);
     else hipLaunchKernelGGL(k_ext_final<uint32_t>, g3, dim3(256), 0, st, a);
 }
 
@@ -847,8 +862,9 @@ static int launch_sparse_stage(ffs_stream* s, const BatchPlan& plan) {
     return plan.will_chain ? launch_one_launch_stage(s, plan, ca, sa) : launch_grid_stage(s, plan, ca, sa);
 }
 
-int enqueue_batch(ffs_stream* s, const void* d_img, size_t pitch, size_t fstride, uint32_t n, const ffs_params* snapshot, const Rerun& how) {
-    s->batch_params = snapshot ? *snapshot : s->ctx->params;
+int enqueue_batch(ffs_stream* s, const void* d_img, size_t pitch, size_t fstride, uint32_t n, const ParamSnapshot* snapshot, const Rerun& how) {
+    s->batch_params = snapshot ? snapshot->params : s->ctx->params;
+    s->batch_scope = snapshot ? snapshot->max_valid_scope : s->ctx->max_valid_scope;
     s->cur_img = d_img;
     s->cur_pitch = pitch;
     s->cur_fstride = fstride;
@@ -1233,7 +1249,7 @@ static int ffs_submit_encoded_impl(ffs_stream* s, int codec, const void* const* 
     mark_busy(s);
     s->job_rc = FFS_OK;
     s->job_err.clear();
-    const ffs_params snap = c->params;
+    const ParamSnapshot snap{c->params, c->max_valid_scope};
     std::vector<size_t> sizes(chunk_bytes, chunk_bytes + n_frames);
     s->job = std::thread([s, c, snap, n_frames, codec, bo_max_tiles, base = std::move(base), sizes = std::move(sizes)]() {
         if (hipSetDevice(c->device) != hipSuccess) {

@@ -27,8 +27,12 @@ namespace ffsamd {
 
 constexpr int kExtLaneOffset = 4;  // lane l sits on x = 56 * strip - 4 + l
 
-template <typename PixelT>
+// TRUSTED (16-bit pixels; 32-bit pixels read the same limit as an argument in their one instantiation): the window scope of max_valid,
+// a pixel p >= a.nb_limit is masked for its frame -- out of the window sums here, no background in the final pass, and its own
+// first-pass bit is zero (the centre test below), so it erodes its neighbours like any background pixel.
+template <typename PixelT, bool TRUSTED = false>
 __global__ __launch_bounds__(64) void k_ext_first(const ThresholdArgs a) {
+    static_assert(!TRUSTED || sizeof(PixelT) == 2, "32-bit pixels take the neighbour limit as an argument");
     const int lane = threadIdx.x;
     const int strip = blockIdx.x % a.ext_strips;
     const int band = blockIdx.x / a.ext_strips;
@@ -61,7 +65,7 @@ __global__ __launch_bounds__(64) void k_ext_first(const ThresholdArgs a) {
                 mbit = (a.maskbits[(uint64_t)yin * a.mpitch + (x >> 3)] >> (x & 7)) & 1u;
             }
             // mm = mask && src < 2^24, baseline.cpp:379,391
-            const bool inc = mbit && (sizeof(PixelT) == 2 || p < (1u << 24));
+            const bool inc = mbit && ((sizeof(PixelT) == 2 && !TRUSTED) || p < a.nb_limit);
             const uint32_t pn = inc ? p : 0u, po = ring_p[t];
             cm += (int)inc - (int)((hist >> t) & 1u);
             cx += pn - po;
@@ -125,6 +129,7 @@ __global__ __launch_bounds__(64) void k_ext_first(const ThresholdArgs a) {
 }
 template __global__ void k_ext_first<uint16_t>(const ThresholdArgs);
 template __global__ void k_ext_first<uint32_t>(const ThresholdArgs);
+template __global__ void k_ext_first<uint16_t, true>(const ThresholdArgs);
 
 // One row of the horizontally eroded plane for word column w: row yy of D with "does not erode its neighbours" pixels set (beyond
 // the image width; with the device kernels' rule also masked pixels), eroded horizontally by 2.  `centre` = D's own word.
@@ -254,7 +259,7 @@ template __global__ void k_ext_erode_strips<16, false>(const ThresholdArgs);
 template __global__ void k_ext_erode_strips<16, true>(const ThresholdArgs);
 
 // X3 predicate: baseline.cpp:580-645 for one pixel of the signal region E.
-template <typename PixelT>
+template <typename PixelT, bool TRUSTED>
 __device__ __forceinline__ bool ext_final_strong(const ThresholdArgs& a, const uint8_t* img, const uint32_t* eplane, int e_y0, int x, int y) {
     const int W = a.W, H = a.H;
     const int xs = max(x - 5, 0), xe = min(x + 5, W - 1);  // kernel + 2, clipped (:591-598)
@@ -285,7 +290,14 @@ __device__ __forceinline__ bool ext_final_strong(const ThresholdArgs& a, const u
 #pragma unroll
             for (int q = 0; q < 6; ++q) pw[q] = prow[q];
             // background for the second SAT: valid and not in the signal region (:552-571, :755)
-            const uint32_t inc = ok ? ((uint32_t)((mw & ~ew) >> shb) & cm) : 0u;
+            uint32_t inc = ok ? ((uint32_t)((mw & ~ew) >> shb) & cm) : 0u;
+            if constexpr (TRUSTED) {   // a pixel above max_valid is no background either
+#pragma unroll
+                for (int q = 0; q < 6; ++q) {
+                    if ((pw[q] & 0xFFFFu) >= a.nb_limit) inc &= ~(1u << (2 * q));
+                    if ((pw[q] >> 16) >= a.nb_limit) inc &= ~(2u << (2 * q));
+                }
+            }
             m2 += __popc(inc);
 #pragma unroll
             for (int q = 0; q < 6; ++q) {
@@ -306,7 +318,7 @@ __device__ __forceinline__ bool ext_final_strong(const ThresholdArgs& a, const u
                 const int q = __ffs(inc) - 1;
                 inc &= inc - 1;
                 const uint32_t p = prow[q];
-                if (p < (1u << 24)) {  // compute_sat's BIG, :379,391
+                if (TRUSTED ? p < a.nb_limit : p < (1u << 24)) {  // compute_sat's BIG, :379,391
                     m2 += 1;
                     x2 += p;
                 }
@@ -337,6 +349,7 @@ __device__ __forceinline__ uint32_t quad_sum(uint32_t v) {
     v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x4E, 0xf, 0xf, true);   // quad_perm [2,3,0,1]
     return v;
 }
+template <bool TRUSTED>
 __device__ __forceinline__ bool ext_final_strong4(const ThresholdArgs& a, const uint8_t* img, const uint32_t* eplane, int e_y0, int x0, int y, int sub) {
     const int H = a.H;
     const int dpr = (int)(a.mpitch >> 2);
@@ -368,11 +381,14 @@ __device__ __forceinline__ bool ext_final_strong4(const ThresholdArgs& a, const 
         }
         pw[8] = *reinterpret_cast<const uint32_t*>(prow + 32);
         // background for the second SAT: valid and not in the signal region (:552-571, :755)
-        const uint32_t inc = ok ? (uint32_t)((mw & ~ew) >> shb) & 0xFFFFFu : 0u;
+        uint32_t inc = ok ? (uint32_t)((mw & ~ew) >> shb) & 0xFFFFFu : 0u;
 #pragma unroll
         for (int j = 0; j < 14; ++j) {
             const int k = 3 + j;
             const uint32_t p = (k & 1) ? pw[k >> 1] >> 16 : pw[k >> 1] & 0xFFFFu;
+            if constexpr (TRUSTED) {   // a pixel above max_valid is no background either (the windows read block columns 3 .. 16 only)
+                if (p >= a.nb_limit) inc &= ~(1u << k);
+            }
             c[j] += ((inc >> k) & 1u) ? p : 0u;
         }
 #pragma unroll
@@ -409,7 +425,14 @@ template <typename PixelT>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7, 7))) void k_ext_final(const ThresholdArgs a) { exact_tile<PixelT, 256, kExactListCap, sizeof(PixelT) == 2 ? 2 : 1>(a); }
 template __global__ void k_ext_final<uint16_t>(const ThresholdArgs);
 template __global__ void k_ext_final<uint32_t>(const ThresholdArgs);
+// the same under the window scope of max_valid (no waves-per-SIMD request: with the quad variant's compares the compiler takes 104
+// VGPRs, four workgroups a CU, and spills nothing -- held to seven it spills 42 VGPRs, to six 28)
+template <typename PixelT>
+__global__ __launch_bounds__(256) void k_ext_final_trusted(const ThresholdArgs a) { exact_tile<PixelT, 256, kExactListCap, sizeof(PixelT) == 2 ? 2 : 1, false, true>(a); }
+template __global__ void k_ext_final_trusted<uint16_t>(const ThresholdArgs);
+template __global__ void k_ext_final_trusted<uint32_t>(const ThresholdArgs);
 // erosion + final pass in one launch (16-bit pixels; dynamic LDS: 18 rows of the plane = 18 * mpitch bytes)
 __global__ __launch_bounds__(256) void k_ext_erode_final(const ThresholdArgs a) { exact_tile<uint16_t, 256, kExactListCap, 3>(a); }
+__global__ __launch_bounds__(256) void k_ext_erode_final_trusted(const ThresholdArgs a) { exact_tile<uint16_t, 256, kExactListCap, 3, false, true>(a); }
 
 }  // namespace ffsamd

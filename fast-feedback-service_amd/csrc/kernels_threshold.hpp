@@ -63,7 +63,14 @@ __device__ __forceinline__ bool exact_decide(const ThresholdArgs& a, uint32_t m,
 // All seven window rows (pixels and mask bits) are requested before any is used, so a candidate
 // costs one memory round trip, not seven.
 // DISP_ONLY: the extended algorithm's first pass (baseline.cpp:468-473) -- same sums, a > c alone.
-template <typename PixelT, bool DISP_ONLY = false>
+// TRUSTED (here and in exact_strong_w): the window scope of max_valid -- a neighbour counts when p < a.nb_limit, for either pixel
+// type (ffs_device.h); only the cross-check path instantiates it, the hot path's callers compile to what they were.
+template <typename PixelT, bool TRUSTED>
+__device__ __forceinline__ bool neighbour_counts(const ThresholdArgs& a, uint32_t p) {
+    if constexpr (TRUSTED) return p < a.nb_limit;
+    else return sizeof(PixelT) == 2 || p < (1u << 24);   // mm = mask && src < 2^24, standalone.cc:78,90
+}
+template <typename PixelT, bool DISP_ONLY = false, bool TRUSTED = false>
 __device__ bool exact_strong(const ThresholdArgs& a, const uint8_t* img, int x, int y) {
     const int W = a.W, H = a.H;
     const int xs = max(x - 3, 0), xe = min(x + 3, W - 1);  // window clipped to the image, :126-130
@@ -112,8 +119,7 @@ __device__ bool exact_strong(const ThresholdArgs& a, const uint8_t* img, int x, 
         }
 #pragma unroll
         for (int q = 0; q < 8; ++q) {
-            // mm = mask && src < 2^24, standalone.cc:78,90
-            const bool inc = ((bits >> q) & 1u) && (sizeof(PixelT) == 2 || p[q] < (1u << 24));
+            const bool inc = ((bits >> q) & 1u) && neighbour_counts<PixelT, TRUSTED>(a, p[q]);
             const uint32_t pv = inc ? p[q] : 0u;
             m += inc ? 1u : 0u;
             sx += pv;
@@ -127,7 +133,7 @@ __device__ bool exact_strong(const ThresholdArgs& a, const uint8_t* img, int x, 
 // exact_strong at the runtime window (2 a.kx + 1) x (2 a.ky + 1), kx, ky in 1..7: what k_exact<., true> gathers on the cross-check
 // path (tuning "threshold_path" = 2) for windows other than 3,3.  Row after row (at most 15), 16 pixels from an even column cover
 // the (<= 15 wide) window row; 64-bit sums, the same predicate.  Shares nothing with kernels_window.hpp but exact_decide.
-template <typename PixelT>
+template <typename PixelT, bool TRUSTED = false>
 __device__ bool exact_strong_w(const ThresholdArgs& a, const uint8_t* img, int x, int y) {
     const int W = a.W, H = a.H;
     const int xs = max(x - a.kx, 0), xe = min(x + a.kx, W - 1);  // window clipped to the image, :126-130
@@ -166,7 +172,7 @@ __device__ bool exact_strong_w(const ThresholdArgs& a, const uint8_t* img, int x
         }
 #pragma unroll
         for (int q = 0; q < 16; ++q) {
-            const bool inc = ((bits >> q) & 1u) && (sizeof(PixelT) == 2 || p[q] < (1u << 24));
+            const bool inc = ((bits >> q) & 1u) && neighbour_counts<PixelT, TRUSTED>(a, p[q]);
             const uint32_t pv = inc ? p[q] : 0u;
             m += inc ? 1u : 0u;
             sx += pv;
@@ -241,8 +247,9 @@ __device__ __forceinline__ bool exact_strong_lite(const ThresholdArgs& a, const 
 // extended algorithm's final test (kernels_extended.hpp)
 // (the signal-region plane E: `eplane` = the frame's plane in global memory, row 0 first, rows `edpr` dwords apart; MODE 3 passes
 // the tile's rows of it in LDS instead -- row `e_y0` first)
-template <typename PixelT>
+template <typename PixelT, bool TRUSTED = false>
 __device__ __forceinline__ bool ext_final_strong(const ThresholdArgs& a, const uint8_t* img, const uint32_t* eplane, int e_y0, int x, int y);
+template <bool TRUSTED = false>
 __device__ __forceinline__ bool ext_final_strong4(const ThresholdArgs& a, const uint8_t* img, const uint32_t* eplane, int e_y0, int x0, int y, int sub);
 // 5 x 5 erosion of the first-pass plane D, one row of one 32-pixel word column: see kernels_extended.hpp
 __device__ __forceinline__ uint32_t ext_erode_hrow(const ThresholdArgs& a, const uint32_t* dp, const uint32_t* mp, int dpr, int w, int yy,
@@ -258,7 +265,8 @@ __device__ __forceinline__ uint32_t ext_erode_hrow(const ThresholdArgs& a, const
 //         of E to a.eplane (for --writeout / ffs_stream_debug_bitplane) and takes every window's E bits from LDS: one launch and a
 //         round trip of the plane less than k_ext_erode + MODE 2.
 // WIN (MODE 0 only): the runtime window of exact_strong_w instead of the 7x7 one.
-template <typename PixelT, int NT, int LISTCAP, int MODE = 0, bool WIN = false>
+// TRUSTED: the predicates' instantiations for the window scope of max_valid (neighbours p >= a.nb_limit are left out).
+template <typename PixelT, int NT, int LISTCAP, int MODE = 0, bool WIN = false, bool TRUSTED = false>
 __device__ __forceinline__ void exact_tile(const ThresholdArgs& a) {
     // The stage is latency-bound (sparse gathers).  Measured dead ends: a smaller LDS footprint
     // (more tiles resident) and one-wave workgroups both made it slower.  Round 4, extended algorithm (MODE 2, profiles/r04r_ext_final_*):
@@ -365,8 +373,8 @@ __device__ __forceinline__ void exact_tile(const ThresholdArgs& a) {
                 const int y = y0 + row;
                 const bool want = (s_words[g] >> (bit + (uint32_t)sub)) & 1u;   // (only this lane ever changes this bit)
                 bool strong;
-                if (x >= 8 && x + 12 <= a.pitch_px) strong = ext_final_strong4(a, img, esrc, e_y0, x, y, sub);   // (quad-uniform branch)
-                else strong = want && ext_final_strong<PixelT>(a, img, esrc, e_y0, x + sub, y);                   // next to the frame's left or right edge
+                if (x >= 8 && x + 12 <= a.pitch_px) strong = ext_final_strong4<TRUSTED>(a, img, esrc, e_y0, x, y, sub);   // (quad-uniform branch)
+                else strong = want && ext_final_strong<PixelT, TRUSTED>(a, img, esrc, e_y0, x + sub, y);                   // next to the frame's left or right edge
                 if (want) {
                     if (strong) sbytes[(uint64_t)y * a.bpitch + x + sub] = 1;
                     else atomicAnd(&s_words[g], ~(1u << (bit + (uint32_t)sub)));
@@ -381,9 +389,9 @@ __device__ __forceinline__ void exact_tile(const ThresholdArgs& a) {
             const int x = (int)((g - row * dpr) * 32u + bit);
             const int y = y0 + row;
             bool strong;
-            if constexpr (MODE == 1) strong = ext_final_strong<PixelT>(a, img, esrc, e_y0, x, y);
-            else if constexpr (WIN) strong = exact_strong_w<PixelT>(a, img, x, y);
-            else strong = exact_strong<PixelT>(a, img, x, y);
+            if constexpr (MODE == 1) strong = ext_final_strong<PixelT, TRUSTED>(a, img, esrc, e_y0, x, y);
+            else if constexpr (WIN) strong = exact_strong_w<PixelT, TRUSTED>(a, img, x, y);
+            else strong = exact_strong<PixelT, false, TRUSTED>(a, img, x, y);
             if (strong) {
                 sbytes[(uint64_t)y * a.bpitch + x] = 1;
             } else {
@@ -441,15 +449,19 @@ __device__ __forceinline__ void exact_tile(const ThresholdArgs& a) {
 
 // NB: __launch_bounds__ must be a literal here -- with a template parameter hipcc 7.2 silently
 // dropped it (default 1024-thread bound -> 178 VGPRs + scratch, kernel 2x slower).
-template <typename PixelT>
-__global__ __launch_bounds__(256) void k_exact(const ThresholdArgs a) { exact_tile<PixelT, 256, kExactListCap>(a); }
+template <typename PixelT, bool TRUSTED = false>
+__global__ __launch_bounds__(256) void k_exact(const ThresholdArgs a) { exact_tile<PixelT, 256, kExactListCap, 0, false, TRUSTED>(a); }
 template __global__ void k_exact<uint16_t>(const ThresholdArgs);
 template __global__ void k_exact<uint32_t>(const ThresholdArgs);
+template __global__ void k_exact<uint16_t, true>(const ThresholdArgs);
+template __global__ void k_exact<uint32_t, true>(const ThresholdArgs);
 // the same at the runtime window (a.kx, a.ky): windows other than 3,3 on the cross-check path (threshold_path 2)
-template <typename PixelT>
-__global__ __launch_bounds__(256) void k_exact_w(const ThresholdArgs a) { exact_tile<PixelT, 256, kExactListCap, 0, true>(a); }
+template <typename PixelT, bool TRUSTED = false>
+__global__ __launch_bounds__(256) void k_exact_w(const ThresholdArgs a) { exact_tile<PixelT, 256, kExactListCap, 0, true, TRUSTED>(a); }
 template __global__ void k_exact_w<uint16_t>(const ThresholdArgs);
 template __global__ void k_exact_w<uint32_t>(const ThresholdArgs);
+template __global__ void k_exact_w<uint16_t, true>(const ThresholdArgs);
+template __global__ void k_exact_w<uint32_t, true>(const ThresholdArgs);
 // Inclusive prefix sum over the 64 lanes in six DPP adds (row_shr 1/2/4/8 inside the rows of 16, then row_bcast:15 and
 // row_bcast:31 carry the row totals on) instead of six ds_bpermute round trips.
 __device__ __forceinline__ uint32_t wave_inclusive_scan(uint32_t v) {

@@ -12,6 +12,10 @@
 //   16-bit pixels: m << 24 | sum p in one dword (sum p <= 225 * 65535 < 2^24, m <= 225), sum p^2 in 64 bits;
 //   32-bit pixels: sum p in a dword (< 225 * 2^24 <= 2^32), m << 56 | sum p^2 in 64 bits (sum p^2 < 225 * 2^48 < 2^56);
 // m and the sums count the valid neighbours, and for 32-bit pixels only those below 2^24 (standalone.cc:78,90; exact_strong).
+// Neighbour limit (ThresholdArgs.nb_limit, exclusive): with ffs_ctx_set_max_valid_scope(FFS_MAX_VALID_WINDOW) a pixel above max_valid
+// is masked for its frame -- out of m and both sums of every window.  32-bit pixels: the 2^24 above IS that argument (2^24 under the
+// centre scope, min(max_valid, 2^24 - 1) + 1 under the window scope), the same compare.  16-bit pixels: the TRUSTED instantiations
+// carry the compare; the others are the code they were.  The sums are over a subset of the window, so every bound above holds.
 // Every pixel is then decided by exact_decide -- the oracle's float64 predicate, operation for operation -- behind screens that
 // are proven supersets (win_signal, win_rest).  Output: what the sparse stage reads after k_exact -- the strong bit plane, per-tile counts,
 // the occupancy bitmap when the sparse launch reads it (a.occ != nullptr), the byte mask when somebody asked for it.
@@ -55,13 +59,13 @@ __device__ __forceinline__ void win_unpack(const WinRow<PixelT>& r, uint32_t (&p
 }
 
 // column sums += (SUB: -=) one row's contribution
-template <typename PixelT, bool SUB>
-__device__ __forceinline__ void win_columns(uint32_t (&cs)[8], uint64_t (&cq)[8], const WinRow<PixelT>& r) {
+template <typename PixelT, bool SUB, bool TRUSTED>
+__device__ __forceinline__ void win_columns(uint32_t (&cs)[8], uint64_t (&cq)[8], const WinRow<PixelT>& r, uint32_t limit) {
     uint32_t p[8];
     win_unpack<PixelT>(r, p);
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
-        const bool v = ((r.mb >> j) & 1u) && (sizeof(PixelT) == 2 || p[j] < (1u << 24));
+        const bool v = ((r.mb >> j) & 1u) && ((sizeof(PixelT) == 2 && !TRUSTED) || p[j] < limit);
         const uint32_t pv = v ? p[j] : 0u;
         uint32_t ds;
         uint64_t dq = (uint64_t)pv * pv;
@@ -117,9 +121,11 @@ __host__ __device__ inline size_t win_ring_bytes(int pixel_bytes, int ky) {
     return (size_t)(2 * ky + 2) * 64 * (pixel_bytes == 2 ? 20 : 36);
 }
 
-template <typename PixelT, int KX>
+template <typename PixelT, int KX, bool TRUSTED = false>
 __global__ __launch_bounds__(64) void k_window(const ThresholdArgs a) {
     static_assert(KX >= 1 && KX <= 7, "window half-width 1..7");
+    static_assert(!TRUSTED || sizeof(PixelT) == 2, "32-bit pixels take the neighbour limit as an argument: one instantiation");
+    const uint32_t limit = a.nb_limit;
     const int lane = (int)threadIdx.x;
     const int strip = (int)(blockIdx.x % (uint32_t)a.w_strips), band = (int)(blockIdx.x / (uint32_t)a.w_strips);
     const int frame = (int)blockIdx.y;
@@ -165,7 +171,7 @@ __global__ __launch_bounds__(64) void k_window(const ThresholdArgs a) {
     for (int r = max(0, y0 - 1 - ky); r <= min(a.H - 1, y0 - 1 + ky); ++r) {
         const WinRow<PixelT> w = win_load<PixelT>(a, img, r, g, g_ok);
         put(r, w);
-        win_columns<PixelT, false>(cs, cq, w);
+        win_columns<PixelT, false, TRUSTED>(cs, cq, w, limit);
     }
 
     uint8_t* plane = a.bits + (uint64_t)frame * a.plane_frame_stride;
@@ -179,8 +185,8 @@ __global__ __launch_bounds__(64) void k_window(const ThresholdArgs a) {
         const WinRow<PixelT> l = get(y - ky - 1);
         const WinRow<PixelT> c = get(y);
         put(y + ky, e);   // (2ky + 2 slots: neither the leaving nor the centre row shares its slot)
-        win_columns<PixelT, false>(cs, cq, e);
-        win_columns<PixelT, true>(cs, cq, l);
+        win_columns<PixelT, false, TRUSTED>(cs, cq, e, limit);
+        win_columns<PixelT, true, TRUSTED>(cs, cq, l, limit);
 
         // the kx columns on each side from the neighbouring lanes
         uint32_t ls[KX], rs[KX];
@@ -211,7 +217,8 @@ __global__ __launch_bounds__(64) void k_window(const ThresholdArgs a) {
             uint64_t sy;
             if constexpr (sizeof(PixelT) == 2) { m = ws >> 24; sx = ws & 0xFFFFFFu; sy = wq; }
             else { m = (uint32_t)(wq >> 56); sx = ws; sy = wq & ((1ull << 56) - 1ull); }
-            const bool sig = win_signal<PixelT>(a, m, sx, p[j], (c.mb >> j) & 1u);
+            // (a centre above max_valid is never strong: exact_decide refuses it; the TRUSTED kernels -- limit = max_valid + 1 -- know it here)
+            const bool sig = win_signal<PixelT>(a, m, sx, p[j], ((c.mb >> j) & 1u) && (!TRUSTED || p[j] < limit));
             // (wave-uniform: at most pixel positions no lane of the wave has a candidate, and the rest is skipped)
             if (__ballot(sig) != 0ull) {
                 if (sig && win_rest<PixelT>(a, m, sx, sy, p[j])) sb |= 1u << j;

@@ -21,11 +21,15 @@ void usage() {
       "                  [--min-spot-size-3d N] [--max-peak-centroid-separation N] [--start-index N]\n"
       "                  [-t S] [-fd FD] [-a ALGO] [--dmin MIN D] [--dmax MAX D] [-w \xce\xbb] [--detector JSON]\n"
       "                  [-h5] [--output-for-index] [--batch N] [--cpu-decode] [--strict-dtype]\n"
-      "                  [--max-valid trusted|none|N] [--min-count N] [--kernel-size N | NX,NY]\n"
+      "                  [--max-valid trusted|none|N] [--max-valid-scope centre|window] [--min-count N] [--kernel-size N | NX,NY]\n"
       "                  [--devices D0,D1,... | --gpus N] [--no-numa-pinning] [--single-buffer] [--all-threads] [--read-only] [--clean-exit]\n"
       "--max-valid: a centre pixel above this value is never strong (the reference's kernels test it against the\n"
       "              data set's trusted maximum).  trusted (default) = the frame source's trusted-range maximum when it is\n"
       "              below the pixel type's maximum, none = no test (the CPU baseline's behaviour), N = this value\n"
+      "--max-valid-scope: centre (default) = only a centre pixel above --max-valid is refused, and it still counts as a neighbour in\n"
+      "              every window around it (the reference's kernels); window = such a pixel is masked for its frame, left out of\n"
+      "              every window's count and sums, as the per-image mask of the DIALS pipeline does (the general-window kernel at every\n"
+      "              --kernel-size; not with the device flavour of dispersion_extended)\n"
       "--min-count: valid pixels a window needs (default 2, the CPU baseline's; the reference's kernels use 3)\n"
       "--kernel-size: half-size of the dispersion window, both axes (N) or along x and y (NX,NY), each 1..7 (default 3:\n"
       "              the 7x7 window; DIALS spotfinder.threshold.dispersion.kernel_size).  Not with -a dispersion_extended\n"
@@ -132,6 +136,12 @@ Args parse_args(int argc, char** argv) {
         else if (s == "--max-valid") {
             r.max_valid = need(i, s);
             if (r.max_valid != "trusted" && r.max_valid != "none") (void)u32(r.max_valid, s);
+        }
+        else if (s == "--max-valid-scope") {
+            const std::string& v = need(i, s);
+            if (v == "centre") r.max_valid_scope = FFS_MAX_VALID_CENTRE;
+            else if (v == "window") r.max_valid_scope = FFS_MAX_VALID_WINDOW;
+            else arg_error("--max-valid-scope takes centre or window: " + v);
         }
         else if (s == "--kernel-size") {
             const std::string& v = need(i, s);

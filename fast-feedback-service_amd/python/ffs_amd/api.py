@@ -74,6 +74,8 @@ _FRAME_RESULT_DT = np.dtype({"names": ["frame_id", "num_strong_pixels", "num_str
                                          ("frame_id", "num_strong_pixels", "num_strong_pixels_filtered", "n_components", "n_boxes", "n_reflections")],
                              "itemsize": C.sizeof(_FrameResult)})
 
+MAX_VALID_CENTRE, MAX_VALID_WINDOW = 0, 1   # FFS_MAX_VALID_*: what Context.set_max_valid_scope takes ("centre" / "window")
+
 CODEC_BSLZ4 = 0         # FFS_CODEC_*: what Stream.submit_encoded / decode_only take
 CODEC_BYTE_OFFSET = 1
 
@@ -87,6 +89,7 @@ EXPORTS = [
     "ffs_submit_compressed", "ffs_decode_only", "ffs_submit_encoded", "ffs_decode_only_encoded", "ffs_stream_spot_centres", "ffs_bench_threshold", "ffs_bench_hbm", "ffs_stream_debug_planes", "ffs_stream_debug_bitplane", "ffs_selftest_sqrt", "ffs_stack3d_create",
     "ffs_stack3d_destroy", "ffs_stack3d_add_batch", "ffs_stack3d_add_slice", "ffs_stack3d_finish", "ffs_stack3d_signals", "ffs_stack3d_last_finish_ms", "ffs_multi_init", "ffs_multi_transport",
     "ffs_ctx_set_tuning", "ffs_bench_pipeline", "ffs_device_numa_node", "ffs_stream_reserve_host", "ffs_stream_last_path", "ffs_multi_gather_rows",
+    "ffs_ctx_set_max_valid_scope",
 ]
 
 _lib = None
@@ -110,6 +113,7 @@ def load_library():
         L.ffs_ctx_get_mask.argtypes = [C.c_void_p, C.c_void_p]
         L.ffs_ctx_set_params.argtypes = [C.c_void_p, C.POINTER(Params)]
         L.ffs_ctx_set_tuning.argtypes = [C.c_void_p, C.c_char_p, C.c_longlong]
+        L.ffs_ctx_set_max_valid_scope.argtypes = [C.c_void_p, C.c_int]
         L.ffs_bench_pipeline.argtypes = [C.POINTER(C.c_void_p), C.c_uint32, C.c_void_p, C.c_size_t, C.c_size_t, C.c_uint32,
                                          C.c_uint32, C.c_int64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
         L.ffs_device_numa_node.argtypes = [C.c_int]
@@ -246,6 +250,17 @@ class Context:
                 raise AttributeError(k)
             setattr(self.params, k, v)
         self._check(self._lib.ffs_ctx_set_params(self._h, C.byref(self.params)))
+
+    def set_max_valid_scope(self, scope):
+        """ffs_ctx_set_max_valid_scope: "centre" (default: only a centre pixel above max_valid is refused, the reference kernels'
+        behaviour) or "window" (such a pixel is masked for its frame: out of every window's count and sums); or the constants
+        MAX_VALID_CENTRE / MAX_VALID_WINDOW.  Kept across set_params; a batch takes it as it is at submit."""
+        if isinstance(scope, str):
+            names = {"centre": MAX_VALID_CENTRE, "window": MAX_VALID_WINDOW}
+            if scope not in names:
+                raise ValueError(f"max_valid scope must be 'centre' or 'window', not {scope!r}")
+            scope = names[scope]
+        self._check(self._lib.ffs_ctx_set_max_valid_scope(self._h, int(scope)))
 
     def set_tuning(self, **kw):
         """ffs_ctx_set_tuning: A/B partners, fall-backs and capacities (same results either way); see include/ffs_hip.h."""

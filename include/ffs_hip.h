@@ -166,6 +166,22 @@ int ffs_ctx_get_mask(ffs_ctx *ctx, uint8_t *host_mask);
 
 int ffs_ctx_set_params(ffs_ctx *ctx, const ffs_params *p);
 
+/* The scope of ffs_params.max_valid.  Replaces nothing in the reference's kernels: there a pixel above the trusted maximum is
+ * only never strong itself (thresholding.cu:208-215) and still counts as a neighbour in every window it falls into.  What it
+ * stands in for is the per-image mask of the DIALS pipeline (built by dxtbx from the trusted range), which excludes such a pixel
+ * before the threshold sees it.
+ *   FFS_MAX_VALID_CENTRE (0, default): the reference kernels' behaviour -- only the centre pixel is tested.
+ *   FFS_MAX_VALID_WINDOW (1): a pixel p > max_valid is masked for its frame -- left out of the count and both sums of every
+ *     window, and never strong: the result is the oracle's on the mask `mask & (img <= max_valid)` (for 32-bit pixels the
+ *     oracle's p < 2^24 rule holds on top).  Such a batch takes the general-window kernel at every window (FFS_PATH_WINDOW).
+ *     With max_valid < 0 the scope changes nothing.
+ * Per context; kept across ffs_ctx_set_params; like the parameters a batch takes it as it is at submit.  FFS_ERR_INVALID, state
+ * unchanged: any other value; FFS_MAX_VALID_WINDOW together with extended_flavour 1, whichever call comes second (the device
+ * flavour's erosion skips masked neighbours by the static mask, and the reference's kernels have no per-frame mask to copy). */
+#define FFS_MAX_VALID_CENTRE 0
+#define FFS_MAX_VALID_WINDOW 1
+int ffs_ctx_set_max_valid_scope(ffs_ctx *ctx, int scope);
+
 /* Selects between paths that give the SAME results (A/B partners, fall-backs, capacities that tests shrink) --
  * per context, never through the environment; nothing here can change a result.  Keys (default):
  *   "threshold_path"   (0) 0 = windows the streaming kernel cannot vouch for go onto a list (fix-up kernel),
