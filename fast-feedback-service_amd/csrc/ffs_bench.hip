@@ -19,6 +19,7 @@ extern "C" int ffs_bench_threshold(ffs_stream* s, const void* device_pixels, siz
     HIP_TRY(c, hipSetDevice(c->device));
     s->batch_params = c->params;
     s->batch_scope = c->max_valid_scope;
+    s->batch_gain = c->gain;
     const bool ext = c->params.algorithm == FFS_ALGO_DISPERSION_EXTENDED;
     if (ext) {
         rc = ensure_extended_buffers(s);

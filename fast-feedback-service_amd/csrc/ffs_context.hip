@@ -421,7 +421,27 @@ extern "C" int ffs_ctx_set_params(ffs_ctx* c, const ffs_params* p) {
                  "the device-flavour erosion skips masked neighbours by the static mask";
         return FFS_ERR_INVALID;
     }
+    if (p->extended_flavour == 1 && c->gain > 0.0) {
+        c->err = "ffs_ctx_set_params: extended_flavour 1 cannot be combined with a detector gain (ffs_ctx_set_gain): "
+                 "the reference's device kernels, which that flavour copies, have no gain";
+        return FFS_ERR_INVALID;
+    }
     c->params = *p;
+    return FFS_OK;
+}
+
+extern "C" int ffs_ctx_set_gain(ffs_ctx* c, double gain) {
+    if (!c) return FFS_ERR_INVALID;
+    if (!std::isfinite(gain) || gain < 0.0) {
+        c->err = "ffs_ctx_set_gain: the gain must be finite and >= 0 (0 = off: pixel values are photon counts)";
+        return FFS_ERR_INVALID;
+    }
+    if (gain > 0.0 && c->params.extended_flavour == 1) {
+        c->err = "ffs_ctx_set_gain: a detector gain cannot be combined with extended_flavour 1: the reference's device kernels, "
+                 "which that flavour copies, have no gain";
+        return FFS_ERR_INVALID;
+    }
+    c->gain = gain;
     return FFS_OK;
 }
 

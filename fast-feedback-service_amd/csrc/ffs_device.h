@@ -108,6 +108,11 @@ struct ThresholdArgs {
     int kx, ky;
     int w_strips, w_band_rows, w_bands;   // general-window kernel: a wave per (strip of 62 eight-pixel groups, band of rows, frame)
     float w_kS, w_kB;          // its float32 screens: nsig_s^2 (1 - 2^-16), nsig_b^2 (1 - 2^-16); 0 = screen off
+                               // (a gain batch: w_kS carries the gain, gain nsig_s^2 (1 - 2^-16) -- DESIGN.md section 3.3d)
+    // the detector gain (ffs_ctx_set_gain): 0 = off; > 0 = the GAIN instantiations decide with the variance
+    // gain * mean (baseline.cpp:241-247, :539-543, :709-715).  No other kernel reads these.
+    double gain;
+    float g_gain, g_nb;        // float32 screen of a > c under gain: (float)gain and (float)nsig_b; g_gain = 0 = screen off
 };
 
 // The streaming launch's units (launch_geometry.hpp has the map: stream_unit_of, log_slot_of), for the arguments of a launch

@@ -120,6 +120,7 @@ struct ffs_ctx {
     int n_tiles = 0;
     ffs_params params{};
     int max_valid_scope = FFS_MAX_VALID_CENTRE;   // ffs_ctx_set_max_valid_scope: kept across ffs_ctx_set_params, snapshot per batch with the parameters
+    double gain = 0.0;                            // ffs_ctx_set_gain (0 = off): kept and snapshot the same way
     uint8_t* d_maskbits = nullptr;
     uint8_t* d_ginfo = nullptr;  // per-group mask bits + window-count bounds (kernels_stream.hpp)
     uint8_t* d_mmap = nullptr;   // per-pixel window counts
@@ -268,6 +269,7 @@ struct ffs_stream {
     size_t cur_pitch = 0, cur_fstride = 0;
     ffs_params batch_params{};
     int batch_scope = FFS_MAX_VALID_CENTRE;   // ... and the scope of max_valid the batch was submitted under (re-runs inside ffs_wait keep it)
+    double batch_gain = 0.0;                  // ... and the detector gain
     float timings[5] = {0, 0, 0, 0, 0};
     bool timings_stale = false;              // the stage times of the last batch are still in its events (ffs_stream_timings reads them out)
     hipEvent_t timing_last = nullptr;
@@ -335,10 +337,11 @@ static int guarded(ffs_ctx* c, F&& body) {
     } while (0)
 
 // ---- small helpers ------------------------------------------------------------------------------------------
-// What a batch is computed with: the context's parameters and its scope of max_valid as they were at submit.
+// What a batch is computed with: the context's parameters, its scope of max_valid and its detector gain as they were at submit.
 struct ParamSnapshot {
     ffs_params params;
     int max_valid_scope;
+    double gain;
 };
 // What ffs_wait asks of the enqueue that runs a batch AGAIN because a plan did not hold it (ffs_wait.hip, rerun_batch); the default
 // is a normal batch.  An argument of that one call: what a stream remembers beyond it (log_off, runs_overflowed, band_backoff) is

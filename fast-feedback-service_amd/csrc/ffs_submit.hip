@@ -28,6 +28,8 @@ bool chain_prepare_device() {   // more than 64 KB of dynamic LDS has to be aske
 // ---- the threshold stage's arguments: buffers and pitches, the predicate's constants, the launch geometry ------------------
 // The window scope of max_valid is on for this batch (ffs_ctx_set_max_valid_scope; without a max_valid the scope changes nothing)
 static bool trusted_window(const ffs_stream* s) { return s->batch_scope == FFS_MAX_VALID_WINDOW && s->batch_params.max_valid >= 0; }
+// A detector gain is set for this batch (ffs_ctx_set_gain): the GAIN instantiations of the kernels decide it
+static bool gain_on(const ffs_stream* s) { return s->batch_gain > 0.0; }
 static void set_buffers(ThresholdArgs& a, const ffs_stream* s, const void* img, size_t pitch, size_t fstride, const Rerun& how) {
     const ffs_ctx* c = s->ctx;
     const Layout& L = c->L;
@@ -74,10 +76,11 @@ static void set_buffers(ThresholdArgs& a, const ffs_stream* s, const void* img, 
     a.dplane = s->d_dplane;
     a.eplane = s->d_eplane;
     a.eplane_clean = s->ext_e_clean ? 1 : 0;
-    // (the streaming first pass reads the mask tables, which know nothing of a frame's pixels: the window scope of max_valid takes k_ext_first)
-    a.ext_variant = (c->pixel_bytes == 2 && how.threshold_path < 0 && !trusted_window(s)) ? c->tune.ext_first_pass : 0;
+    // (the streaming first pass reads the mask tables, which know nothing of a frame's pixels: the window scope of max_valid takes k_ext_first;
+    // so does a gain batch -- the streaming kernels' screens are proven for the photon-count predicate only)
+    a.ext_variant = (c->pixel_bytes == 2 && how.threshold_path < 0 && !trusted_window(s) && !gain_on(s)) ? c->tune.ext_first_pass : 0;
 }
-static void set_predicate(ThresholdArgs& a, const ffs_params& p, bool trusted) {
+static void set_predicate(ThresholdArgs& a, const ffs_params& p, bool trusted, double gain) {
     // (exclusive; the oracle's < 2^24 rule for 32-bit pixels holds on top of max_valid, and 16-bit pixels never reach it)
     a.nb_limit = trusted ? (uint32_t)std::min<long long>(p.max_valid, (1ll << 24) - 1) + 1u : 1u << 24;
     a.kS = (float)(p.nsig_s * p.nsig_s * (1.0 - 1.0 / 65536.0));
@@ -104,6 +107,23 @@ static void set_predicate(ThresholdArgs& a, const ffs_params& p, bool trusted) {
     a.w_kS = (std::isfinite(p.nsig_s) && p.nsig_s <= 1024.0) ? (float)(p.nsig_s * p.nsig_s * (1.0 - 1.0 / 65536.0)) : 0.0f;
     a.w_kB = (std::isfinite(p.nsig_b) && p.nsig_b <= 1024.0) ? (float)(p.nsig_b * p.nsig_b * (1.0 - 1.0 / 65536.0)) : 0.0f;
     a.ext_flavour = p.extended_flavour;
+    // The detector gain and what the float32 screens of the GAIN kernels take: the signal screen is win_signal's
+    // own with the gain inside its constant; the dispersion screen takes the gain and nsig_b as floats.  Outside the range the proofs
+    // cover (the float32 products must stay normal numbers) a screen is off and float64 decides.
+    a.gain = gain;
+    a.g_gain = 0.0f;
+    a.g_nb = 0.0f;
+    if (gain > 0.0) {
+        const bool in_range = gain >= 0x1p-60 && gain <= 0x1p60;
+        if (!in_range) a.w_kS = 0.0f;
+        else if (a.w_kS != 0.0f) a.w_kS = (float)(gain * (p.nsig_s * p.nsig_s) * (1.0 - 1.0 / 65536.0));
+        // (a constant near the bottom of float32's normal range rounds by more than the margin: nsig_s has no lower bound of its own)
+        if (a.w_kS < 0x1p-100f) a.w_kS = 0.0f;
+        if (in_range && std::isfinite(p.nsig_b) && p.nsig_b <= 1024.0 && (p.nsig_b == 0.0 || p.nsig_b >= 0x1p-60)) {
+            a.g_gain = (float)gain;
+            a.g_nb = (float)p.nsig_b;
+        }
+    }
 }
 // (launch_geometry.hpp computes them; the super rows of the streaming launch, g.n_groups, are its grid's y and no argument)
 static void set_geometry(ThresholdArgs& a, uint32_t n_frames, const StreamGeometry& g, const WindowGeometry& w, const ExtGeometry& e) {
@@ -127,7 +147,7 @@ StreamGeometry batch_stream_geometry(const ffs_stream* s, size_t fstride, uint32
 ThresholdArgs make_threshold_args(ffs_stream* s, const void* img, size_t pitch, size_t fstride, uint32_t n_frames, const StreamGeometry& g, const Rerun& how) {
     ThresholdArgs a{};
     set_buffers(a, s, img, pitch, fstride, how);
-    set_predicate(a, s->batch_params, trusted_window(s));
+    set_predicate(a, s->batch_params, trusted_window(s), s->batch_gain);
     set_geometry(a, n_frames, g, window_geometry(s->ctx->L, n_frames, a.ky), ext_geometry(s->ctx->L, n_frames));
     return a;
 }
@@ -153,31 +173,34 @@ static StreamKernel stream_kernel(const ffs_ctx* c, bool dense_mask, bool extend
 static void launch_stream(ffs_stream* s, const ThresholdArgs& a, const StreamGeometry& g, hipEvent_t start, hipEvent_t stop, hipStream_t st = nullptr) {
     hipExtLaunchKernelGGL(stream_kernel(s->ctx, a.dense_mask != 0, false), stream_grid(a, g), dim3(64), 0, st ? st : s->st, start, stop, 0, a);
 }
-// The general-window kernel (kernels_window.hpp): windows other than 3,3, or every window with tuning "window_kernel" = 1 or under the
-// window scope of max_valid (the streaming kernels' screens rest on counts that depend on the mask alone: DESIGN.md section 3.3c).  The
+// The general-window kernel (kernels_window.hpp): windows other than 3,3, or every window with tuning "window_kernel" = 1, under the
+// window scope of max_valid (the streaming kernels' screens rest on counts that depend on the mask alone: DESIGN.md section 3.3c) or
+// with a detector gain (their screens are proven for the photon-count predicate: section 3.3d).  The
 // standard algorithm on the plane paths only (no wave logs: those belong to k_stream_u16); the cross-check path (threshold_path 2)
 // keeps its gather.
 bool window_kernel_for(const ffs_stream* s, const ThresholdArgs& a) {
     return s->batch_params.algorithm == FFS_ALGO_DISPERSION && a.bright_to_plane != 2
-           && (!win_default(s->batch_params) || s->ctx->tune.window_kernel == 1 || trusted_window(s));
+           && (!win_default(s->batch_params) || s->ctx->tune.window_kernel == 1 || trusted_window(s) || gain_on(s));
 }
-template <typename PixelT, bool TRUSTED = false>
+template <typename PixelT, bool TRUSTED = false, bool GAIN = false>
 static void launch_window_t(const ThresholdArgs& a, dim3 grid, hipStream_t st, hipEvent_t start, hipEvent_t stop) {
     const size_t lds = win_ring_bytes((int)sizeof(PixelT), a.ky);
     switch (a.kx) {
-        case 1: hipExtLaunchKernelGGL((k_window<PixelT, 1, TRUSTED>), grid, dim3(64), lds, st, start, stop, 0, a); break;
-        case 2: hipExtLaunchKernelGGL((k_window<PixelT, 2, TRUSTED>), grid, dim3(64), lds, st, start, stop, 0, a); break;
-        case 3: hipExtLaunchKernelGGL((k_window<PixelT, 3, TRUSTED>), grid, dim3(64), lds, st, start, stop, 0, a); break;
-        case 4: hipExtLaunchKernelGGL((k_window<PixelT, 4, TRUSTED>), grid, dim3(64), lds, st, start, stop, 0, a); break;
-        case 5: hipExtLaunchKernelGGL((k_window<PixelT, 5, TRUSTED>), grid, dim3(64), lds, st, start, stop, 0, a); break;
-        case 6: hipExtLaunchKernelGGL((k_window<PixelT, 6, TRUSTED>), grid, dim3(64), lds, st, start, stop, 0, a); break;
-        default: hipExtLaunchKernelGGL((k_window<PixelT, 7, TRUSTED>), grid, dim3(64), lds, st, start, stop, 0, a); break;
+        case 1: hipExtLaunchKernelGGL((k_window<PixelT, 1, TRUSTED, GAIN>), grid, dim3(64), lds, st, start, stop, 0, a); break;
+        case 2: hipExtLaunchKernelGGL((k_window<PixelT, 2, TRUSTED, GAIN>), grid, dim3(64), lds, st, start, stop, 0, a); break;
+        case 3: hipExtLaunchKernelGGL((k_window<PixelT, 3, TRUSTED, GAIN>), grid, dim3(64), lds, st, start, stop, 0, a); break;
+        case 4: hipExtLaunchKernelGGL((k_window<PixelT, 4, TRUSTED, GAIN>), grid, dim3(64), lds, st, start, stop, 0, a); break;
+        case 5: hipExtLaunchKernelGGL((k_window<PixelT, 5, TRUSTED, GAIN>), grid, dim3(64), lds, st, start, stop, 0, a); break;
+        case 6: hipExtLaunchKernelGGL((k_window<PixelT, 6, TRUSTED, GAIN>), grid, dim3(64), lds, st, start, stop, 0, a); break;
+        default: hipExtLaunchKernelGGL((k_window<PixelT, 7, TRUSTED, GAIN>), grid, dim3(64), lds, st, start, stop, 0, a); break;
     }
 }
 static void launch_window(ffs_stream* s, const ThresholdArgs& a, uint32_t n_frames, hipEvent_t start, hipEvent_t stop, hipStream_t st = nullptr) {
     const dim3 grid((unsigned)(a.w_strips * a.w_bands), n_frames);
     if (!st) st = s->st;
-    if (s->ctx->pixel_bytes == 4) launch_window_t<uint32_t>(a, grid, st, start, stop);   // (the neighbour limit is its argument)
+    if (gain_on(s) && s->ctx->pixel_bytes == 4) launch_window_t<uint32_t, false, true>(a, grid, st, start, stop);
+    else if (gain_on(s)) launch_window_t<uint16_t, true, true>(a, grid, st, start, stop);   // (centre scope: the limit is 2^24, beyond every pixel)
+    else if (s->ctx->pixel_bytes == 4) launch_window_t<uint32_t>(a, grid, st, start, stop);   // (the neighbour limit is its argument)
     else if (trusted_window(s)) launch_window_t<uint16_t, true>(a, grid, st, start, stop);
     else launch_window_t<uint16_t>(a, grid, st, start, stop);
 }
@@ -190,14 +213,19 @@ static void launch_bright_fix(ffs_stream* s, const ThresholdArgs& a, hipStream_t
 static void launch_exact(ffs_stream* s, const ThresholdArgs& a, uint32_t n_frames, hipStream_t st) {
     const dim3 grid((unsigned)a.n_tiles, n_frames);
     const bool u32 = s->ctx->pixel_bytes == 4, trusted = trusted_window(s);   // (trusted: the cross-check path, the only one that gets here with it)
+    const bool gain = gain_on(s);                                              // (and so with a gain)
     if (a.kx != 3 || a.ky != 3) {   // (the runtime-window gather: exact_strong_w)
-        if (trusted && u32) hipLaunchKernelGGL((k_exact_w<uint32_t, true>), grid, dim3(256), 0, st, a);
+        if (gain && u32) hipLaunchKernelGGL((k_exact_w<uint32_t, true, true>), grid, dim3(256), 0, st, a);
+        else if (gain) hipLaunchKernelGGL((k_exact_w<uint16_t, true, true>), grid, dim3(256), 0, st, a);
+        else if (trusted && u32) hipLaunchKernelGGL((k_exact_w<uint32_t, true>), grid, dim3(256), 0, st, a);
         else if (trusted) hipLaunchKernelGGL((k_exact_w<uint16_t, true>), grid, dim3(256), 0, st, a);
         else if (u32) hipLaunchKernelGGL(k_exact_w<uint32_t>, grid, dim3(256), 0, st, a);
         else hipLaunchKernelGGL(k_exact_w<uint16_t>, grid, dim3(256), 0, st, a);
         return;
     }
-    if (trusted && u32) hipLaunchKernelGGL((k_exact<uint32_t, true>), grid, dim3(256), 0, st, a);
+    if (gain && u32) hipLaunchKernelGGL((k_exact<uint32_t, true, true>), grid, dim3(256), 0, st, a);
+    else if (gain) hipLaunchKernelGGL((k_exact<uint16_t, true, true>), grid, dim3(256), 0, st, a);
+    else if (trusted && u32) hipLaunchKernelGGL((k_exact<uint32_t, true>), grid, dim3(256), 0, st, a);
     else if (trusted) hipLaunchKernelGGL((k_exact<uint16_t, true>), grid, dim3(256), 0, st, a);
     else if (u32) hipLaunchKernelGGL(k_exact<uint32_t>, grid, dim3(256), 0, st, a);
     else hipLaunchKernelGGL(k_exact<uint16_t>, grid, dim3(256), 0, st, a);
@@ -222,17 +250,20 @@ static void launch_ext_first(ffs_stream* s, const ThresholdArgs& a, const Stream
         return;
     }
     dim3 g1((unsigned)(a.ext_strips * a.ext_bands), n_frames);
-    if (s->ctx->pixel_bytes == 2 && trusted_window(s)) hipExtLaunchKernelGGL((k_ext_first<uint16_t, true>), g1, dim3(64), 0, s->st, start, stop, 0, a);
+    if (gain_on(s) && s->ctx->pixel_bytes == 2) hipExtLaunchKernelGGL((k_ext_first<uint16_t, true, true>), g1, dim3(64), 0, s->st, start, stop, 0, a);
+    else if (gain_on(s)) hipExtLaunchKernelGGL((k_ext_first<uint32_t, false, true>), g1, dim3(64), 0, s->st, start, stop, 0, a);
+    else if (s->ctx->pixel_bytes == 2 && trusted_window(s)) hipExtLaunchKernelGGL((k_ext_first<uint16_t, true>), g1, dim3(64), 0, s->st, start, stop, 0, a);
     else if (s->ctx->pixel_bytes == 2) hipExtLaunchKernelGGL(k_ext_first<uint16_t>, g1, dim3(64), 0, s->st, start, stop, 0, a);
     else hipExtLaunchKernelGGL(k_ext_first<uint32_t>, g1, dim3(64), 0, s->st, start, stop, 0, a);
 }
 static void launch_ext_rest(ffs_stream* s, const ThresholdArgs& a, uint32_t n_frames, hipStream_t st) {
-    const bool u16 = s->ctx->pixel_bytes == 2, trusted = trusted_window(s);
+    const bool u16 = s->ctx->pixel_bytes == 2, trusted = trusted_window(s), gain = gain_on(s);
     // The byte mask: the streaming kernel zero-filled it if somebody wants it (k_ext_final sets 1s in it either way; without a
     // taker they land in a buffer nobody reads); after k_ext_first it is always produced, so zero it here.
     if (!ext_stream_first(a)) (void)hipMemsetAsync(a.strong_bytes, 0, (size_t)n_frames * a.bytes_frame_stride, st);
     dim3 g3((unsigned)a.n_tiles, n_frames);
-    if (u16 && s->ctx->tune.ext_fused) {   // erosion inside the final pass's tiles: one launch, the plane crosses memory once
+    // (a gain batch has no fused kernel: erosion + final pass below)
+    if (u16 && s->ctx->tune.ext_fused && !gain) {   // erosion inside the final pass's tiles: one launch, the plane crosses memory once
         hipLaunchKernelGGL(trusted ? k_ext_erode_final_trusted : k_ext_erode_final, g3, dim3(256), (size_t)(kTileRows + 10) * a.mpitch, st, a);
         return;
     }
@@ -248,7 +279,9 @@ static void launch_ext_rest(ffs_stream* s, const ThresholdArgs& a, uint32_t n_fr
         const unsigned erode_lanes = (a.mpitch / 4) * (unsigned)((a.H + kErodeRows - 1) / kErodeRows);
         hipLaunchKernelGGL(k_ext_erode, dim3((erode_lanes + 255) / 256, n_frames), dim3(256), 0, st, a);
     }
-    if (trusted && u16) hipLaunchKernelGGL(k_ext_final_trusted<uint16_t>, g3, dim3(256), 0, st, a);
+    if (gain && u16) hipLaunchKernelGGL(k_ext_final_gain<uint16_t>, g3, dim3(256), 0, st, a);
+    else if (gain) hipLaunchKernelGGL(k_ext_final_gain<uint32_t>, g3, dim3(256), 0, st, a);
+    else if (trusted && u16) hipLaunchKernelGGL(k_ext_final_trusted<uint16_t>, g3, dim3(256), 0, st, a);
     else if (trusted) hipLaunchKernelGGL(k_ext_final_trusted<uint32_t>, g3, dim3(256), 0, st, a);
     else if (u16) hipLaunchKernelGGL(k_ext_final<uint16_t>, g3, dim3(256), 0, st, a);
     else hipLaunchKernelGGL(k_ext_final<uint32_t>, g3, dim3(256), 0, st, a);
@@ -865,6 +898,7 @@ static int launch_sparse_stage(ffs_stream* s, const BatchPlan& plan) {
 int enqueue_batch(ffs_stream* s, const void* d_img, size_t pitch, size_t fstride, uint32_t n, const ParamSnapshot* snapshot, const Rerun& how) {
     s->batch_params = snapshot ? snapshot->params : s->ctx->params;
     s->batch_scope = snapshot ? snapshot->max_valid_scope : s->ctx->max_valid_scope;
+    s->batch_gain = snapshot ? snapshot->gain : s->ctx->gain;
     s->cur_img = d_img;
     s->cur_pitch = pitch;
     s->cur_fstride = fstride;
@@ -1249,7 +1283,7 @@ static int ffs_submit_encoded_impl(ffs_stream* s, int codec, const void* const* 
     mark_busy(s);
     s->job_rc = FFS_OK;
     s->job_err.clear();
-    const ParamSnapshot snap{c->params, c->max_valid_scope};
+    const ParamSnapshot snap{c->params, c->max_valid_scope, c->gain};
     std::vector<size_t> sizes(chunk_bytes, chunk_bytes + n_frames);
     s->job = std::thread([s, c, snap, n_frames, codec, bo_max_tiles, base = std::move(base), sizes = std::move(sizes)]() {
         if (hipSetDevice(c->device) != hipSuccess) {

@@ -308,7 +308,7 @@ void ahead_stop(ffs_ctx* c, bool destroy) {
 // A plan did not hold the batch (an overflow flag of its kernels): the same frames and parameters again, enqueued with what `how`
 // overrides, and waited for in the caller's place.
 static int rerun_batch(ffs_stream* s, const Rerun& how, const ffs_frame_result** results, uint32_t* n_results) {
-    const ParamSnapshot snap{s->batch_params, s->batch_scope};
+    const ParamSnapshot snap{s->batch_params, s->batch_scope, s->batch_gain};
     const int rc = enqueue_batch(s, s->cur_img, s->cur_pitch, s->cur_fstride, s->n_frames, &snap, how);
     if (rc != FFS_OK) return rc;
     ++s->reruns;
@@ -395,7 +395,7 @@ static int rerun_overflow_frames(ffs_stream* s) {
             b->ev1_pending = true;
             // (the frame's strong-pixel list comes back to the host whenever somebody may read it: the caller, or a 3D stack
             // that is alive -- ffs_stack3d_add_batch takes an overflow frame's list from here, tuning "device_lists")
-            ParamSnapshot bp{s->batch_params, s->batch_scope};
+            ParamSnapshot bp{s->batch_params, s->batch_scope, s->batch_gain};
             if (c->tune.device_lists == 1 || (c->tune.device_lists == 2 && g_live_stacks.load() > 0)) bp.params.want_strong_list = 1;
             int rc = enqueue_batch(b, img, s->cur_pitch, s->cur_fstride, 1, &bp);
             if (rc != FFS_OK) return rc;

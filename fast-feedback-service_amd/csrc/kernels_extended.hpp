@@ -30,9 +30,12 @@ constexpr int kExtLaneOffset = 4;  // lane l sits on x = 56 * strip - 4 + l
 // TRUSTED (16-bit pixels; 32-bit pixels read the same limit as an argument in their one instantiation): the window scope of max_valid,
 // a pixel p >= a.nb_limit is masked for its frame -- out of the window sums here, no background in the final pass, and its own
 // first-pass bit is zero (the centre test below), so it erodes its neighbours like any background pixel.
-template <typename PixelT, bool TRUSTED = false>
+// GAIN (ffs_ctx_set_gain): a = m y - x^2 and c = (gain x)((m - 1) + nsig_b sqrt(2 (m - 1))), baseline.cpp:539-543 (DESIGN.md section
+// 3.3d); the 16-bit instantiation carries the neighbour-limit compare, as every gain kernel does.
+template <typename PixelT, bool TRUSTED = false, bool GAIN = false>
 __global__ __launch_bounds__(64) void k_ext_first(const ThresholdArgs a) {
     static_assert(!TRUSTED || sizeof(PixelT) == 2, "32-bit pixels take the neighbour limit as an argument");
+    static_assert(!GAIN || TRUSTED || sizeof(PixelT) == 4, "the gain kernels always carry the neighbour-limit compare");
     const int lane = threadIdx.x;
     const int strip = blockIdx.x % a.ext_strips;
     const int band = blockIdx.x / a.ext_strips;
@@ -98,21 +101,33 @@ __global__ __launch_bounds__(64) void k_ext_first(const ThresholdArgs a) {
             bool d_bit = false;
             // baseline.cpp:469 (mask[k] && m >= min_count && x >= 0)
             if (centre_mask && m >= a.min_count) {
-                // exact integers: a = m y - x^2 - x (m - 1)
-                const long long ai = (long long)((unsigned long long)m * wy) - (long long)((unsigned long long)wx * wx)
-                                     - (long long)((unsigned long long)wx * (unsigned)(m - 1));
-                // float32 screen with allowance: all roundings together stay below 2^-21 relative
-                const float af = (float)ai;
-                const float cf = (float)wx * (a.kB * __builtin_sqrtf(2.0f * (float)(m - 1)));
-                if (ai > 0 && af >= cf * (1.0f - 3.8146973e-06f)) {
-                    // :470-472, each operation rounded separately (contraction is off)
-                    const double md = (double)m, xd = (double)wx, yd = (double)wy;
-                    const double t0 = md * yd;
-                    const double t1 = xd * xd;
-                    const double t2 = xd * (md - 1.0);
-                    const double av = (t0 - t1) - t2;
-                    const double cv = (xd * a.nsig_b) * __builtin_sqrt(2.0 * (md - 1.0));
-                    d_bit = av > cv;
+                if constexpr (GAIN) {
+                    // exact integers: a = m y - x^2 (m y < 49 * 49 * 2^48 and x^2 < (49 * 2^24)^2: int64 holds them)
+                    const long long ai = (long long)((unsigned long long)m * wy) - (long long)((unsigned long long)wx * wx);
+                    if (!gain_disp_rejects(a, ai, wx, (uint32_t)m)) {
+                        // :540-542, each operation rounded separately (contraction is off)
+                        const double md = (double)m, xd = (double)wx, yd = (double)wy;
+                        const double av = md * yd - xd * xd;
+                        const double cv = (a.gain * xd) * ((md - 1.0) + a.nsig_b * __builtin_sqrt(2.0 * (md - 1.0)));
+                        d_bit = av > cv;
+                    }
+                } else {
+                    // exact integers: a = m y - x^2 - x (m - 1)
+                    const long long ai = (long long)((unsigned long long)m * wy) - (long long)((unsigned long long)wx * wx)
+                                         - (long long)((unsigned long long)wx * (unsigned)(m - 1));
+                    // float32 screen with allowance: all roundings together stay below 2^-21 relative
+                    const float af = (float)ai;
+                    const float cf = (float)wx * (a.kB * __builtin_sqrtf(2.0f * (float)(m - 1)));
+                    if (ai > 0 && af >= cf * (1.0f - 3.8146973e-06f)) {
+                        // :470-472, each operation rounded separately (contraction is off)
+                        const double md = (double)m, xd = (double)wx, yd = (double)wy;
+                        const double t0 = md * yd;
+                        const double t1 = xd * xd;
+                        const double t2 = xd * (md - 1.0);
+                        const double av = (t0 - t1) - t2;
+                        const double cv = (xd * a.nsig_b) * __builtin_sqrt(2.0 * (md - 1.0));
+                        d_bit = av > cv;
+                    }
                 }
                 if (a.max_valid >= 0) {  // device kernels only, thresholding.cu:318-325
                     const uint32_t pc = reinterpret_cast<const PixelT*>(img + (uint64_t)(yin - 3) * a.pitch)[x];
@@ -130,6 +145,8 @@ __global__ __launch_bounds__(64) void k_ext_first(const ThresholdArgs a) {
 template __global__ void k_ext_first<uint16_t>(const ThresholdArgs);
 template __global__ void k_ext_first<uint32_t>(const ThresholdArgs);
 template __global__ void k_ext_first<uint16_t, true>(const ThresholdArgs);
+template __global__ void k_ext_first<uint16_t, true, true>(const ThresholdArgs);
+template __global__ void k_ext_first<uint32_t, false, true>(const ThresholdArgs);
 
 // One row of the horizontally eroded plane for word column w: row yy of D with "does not erode its neighbours" pixels set (beyond
 // the image width; with the device kernels' rule also masked pixels), eroded horizontally by 2.  `centre` = D's own word.
@@ -259,7 +276,7 @@ template __global__ void k_ext_erode_strips<16, false>(const ThresholdArgs);
 template __global__ void k_ext_erode_strips<16, true>(const ThresholdArgs);
 
 // X3 predicate: baseline.cpp:580-645 for one pixel of the signal region E.
-template <typename PixelT, bool TRUSTED>
+template <typename PixelT, bool TRUSTED, bool GAIN>
 __device__ __forceinline__ bool ext_final_strong(const ThresholdArgs& a, const uint8_t* img, const uint32_t* eplane, int e_y0, int x, int y) {
     const int W = a.W, H = a.H;
     const int xs = max(x - 5, 0), xe = min(x + 5, W - 1);  // kernel + 2, clipped (:591-598)
@@ -331,7 +348,9 @@ __device__ __forceinline__ bool ext_final_strong(const ThresholdArgs& a, const u
     const double src = (double)pc;
     const double mean = m2 >= 2 ? (double)x2 / (double)m2 : 0.0;        // :640
     const bool global_mask = src > a.threshold;
-    const bool local_mask = src >= (mean + a.nsig_s * __builtin_sqrt(mean));
+    bool local_mask;
+    if constexpr (GAIN) local_mask = src >= (mean + a.nsig_s * __builtin_sqrt(a.gain * mean));   // :713-714
+    else local_mask = src >= (mean + a.nsig_s * __builtin_sqrt(mean));
     return global_mask && local_mask;
 }
 
@@ -349,7 +368,7 @@ __device__ __forceinline__ uint32_t quad_sum(uint32_t v) {
     v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x4E, 0xf, 0xf, true);   // quad_perm [2,3,0,1]
     return v;
 }
-template <bool TRUSTED>
+template <bool TRUSTED, bool GAIN>
 __device__ __forceinline__ bool ext_final_strong4(const ThresholdArgs& a, const uint8_t* img, const uint32_t* eplane, int e_y0, int x0, int y, int sub) {
     const int H = a.H;
     const int dpr = (int)(a.mpitch >> 2);
@@ -415,7 +434,8 @@ __device__ __forceinline__ bool ext_final_strong4(const ThresholdArgs& a, const 
     if (a.max_valid >= 0 && (long long)pc > a.max_valid) return false;  // thresholding.cu:440-441
     const double src = (double)pc;
     const double mean = m >= 2 ? (double)x2 / (double)m : 0.0;          // :640
-    return src > a.threshold && src >= (mean + a.nsig_s * __builtin_sqrt(mean));
+    if constexpr (GAIN) return src > a.threshold && src >= (mean + a.nsig_s * __builtin_sqrt(a.gain * mean));   // :713-714
+    else return src > a.threshold && src >= (mean + a.nsig_s * __builtin_sqrt(mean));
 }
 
 // (16-bit pixels: four pixels per quad of lanes, MODE 2 of the tile skeleton; 32-bit pixels: one pixel per lane)
@@ -431,6 +451,12 @@ template <typename PixelT>
 __global__ __launch_bounds__(256) void k_ext_final_trusted(const ThresholdArgs a) { exact_tile<PixelT, 256, kExactListCap, sizeof(PixelT) == 2 ? 2 : 1, false, true>(a); }
 template __global__ void k_ext_final_trusted<uint16_t>(const ThresholdArgs);
 template __global__ void k_ext_final_trusted<uint32_t>(const ThresholdArgs);
+// the same with the gain in the local test (ffs_ctx_set_gain; MODE 2 for 16-bit pixels, MODE 1 for 32-bit ones); like every gain kernel
+// it carries the neighbour-limit compare.  A gain batch has no fused erosion: tuning "ext_fused" falls back to erosion + this.
+template <typename PixelT>
+__global__ __launch_bounds__(256) void k_ext_final_gain(const ThresholdArgs a) { exact_tile<PixelT, 256, kExactListCap, sizeof(PixelT) == 2 ? 2 : 1, false, true, true>(a); }
+template __global__ void k_ext_final_gain<uint16_t>(const ThresholdArgs);
+template __global__ void k_ext_final_gain<uint32_t>(const ThresholdArgs);
 // erosion + final pass in one launch (16-bit pixels; dynamic LDS: 18 rows of the plane = 18 * mpitch bytes)
 __global__ __launch_bounds__(256) void k_ext_erode_final(const ThresholdArgs a) { exact_tile<uint16_t, 256, kExactListCap, 3>(a); }
 __global__ __launch_bounds__(256) void k_ext_erode_final_trusted(const ThresholdArgs a) { exact_tile<uint16_t, 256, kExactListCap, 3, false, true>(a); }

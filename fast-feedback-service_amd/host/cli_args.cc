@@ -22,6 +22,7 @@ void usage() {
       "                  [-t S] [-fd FD] [-a ALGO] [--dmin MIN D] [--dmax MAX D] [-w \xce\xbb] [--detector JSON]\n"
       "                  [-h5] [--output-for-index] [--batch N] [--cpu-decode] [--strict-dtype]\n"
       "                  [--max-valid trusted|none|N] [--max-valid-scope centre|window] [--min-count N] [--kernel-size N | NX,NY]\n"
+      "                  [--gain G]\n"
       "                  [--devices D0,D1,... | --gpus N] [--no-numa-pinning] [--single-buffer] [--all-threads] [--read-only] [--clean-exit]\n"
       "--max-valid: a centre pixel above this value is never strong (the reference's kernels test it against the\n"
       "              data set's trusted maximum).  trusted (default) = the frame source's trusted-range maximum when it is\n"
@@ -33,6 +34,9 @@ void usage() {
       "--min-count: valid pixels a window needs (default 2, the CPU baseline's; the reference's kernels use 3)\n"
       "--kernel-size: half-size of the dispersion window, both axes (N) or along x and y (NX,NY), each 1..7 (default 3:\n"
       "              the 7x7 window; DIALS spotfinder.threshold.dispersion.kernel_size).  Not with -a dispersion_extended\n"
+      "--gain:      the detector gain G > 0 of the dispersion tests, for frames in ADU or keV whose background variance is G x mean,\n"
+      "              not mean (DIALS spotfinder.threshold.dispersion.gain; default: none, pixel values are photon counts).  The\n"
+      "              general-window kernel at every --kernel-size; also with -a dispersion_extended\n"
       "--validate:  every image is also decided by an independent path (every valid pixel's window gathered from memory,\n"
       "              no streaming kernel) and the two strong-pixel masks are compared: Match / Mismatch per image\n"
       "--devices / --gpus: one context and worker pool per GPU, all pulling frames from the one queue\n"
@@ -156,6 +160,12 @@ Args parse_args(int argc, char** argv) {
                 r.kernel_half_x = half(v.substr(0, comma));
                 r.kernel_half_y = half(v.substr(comma + 1));
             }
+        }
+        else if (s == "--gain") {
+            const std::string& v = need(i, s);
+            try { size_t used; r.gain = std::stod(v, &used); if (used != v.size()) throw 1; }
+            catch (...) { arg_error("pattern not found for '" + s + "': " + v); }
+            if (!(r.gain > 0.0) || r.gain > 1.7976931348623157e308) arg_error("--gain takes a finite number above 0: " + v);
         }
         else if (s == "--min-count") { r.min_count = u32(need(i, s), s); if (r.min_count < 2) arg_error("--min-count must be at least 2"); }
         else if (s == "--no-numa-pinning") r.no_numa_pinning = true;

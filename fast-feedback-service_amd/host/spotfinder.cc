@@ -367,7 +367,7 @@ static ffs_params make_params(const Args& args, bool rotation, int64_t max_valid
 // pixel is gathered from memory (tuning "threshold_path" = 2; the extended algorithm: its plain one-pixel-per-lane first
 // pass and the grid-wide sparse kernels) -- and the two strong-pixel masks are compared image by image.
 static bool create_validation_contexts(const std::vector<int>& devices, const std::vector<ffs_ctx*>& ctxs, const FrameShape& shape, uint32_t batch,
-                                       const ffs_params& prm, int max_valid_scope, std::vector<ffs_ctx*>& vctxs) {
+                                       const ffs_params& prm, int max_valid_scope, double gain, std::vector<ffs_ctx*>& vctxs) {
     for (size_t di = 0; di < devices.size(); ++di) {
         if (!create_context(devices[di], shape, batch, &vctxs[di])) return false;
         ffs_ctx* v = vctxs[di];
@@ -380,6 +380,7 @@ static bool create_validation_contexts(const std::vector<int>& devices, const st
         FFS_CHECK(v, ffs_ctx_set_mask(v, m.data()));
         FFS_CHECK(v, ffs_ctx_set_params(v, &prm));
         FFS_CHECK(v, ffs_ctx_set_max_valid_scope(v, max_valid_scope));
+        FFS_CHECK(v, ffs_ctx_set_gain(v, gain));
     }
     std::printf("Validation: every image is also decided by the gather path (every valid pixel's window summed from memory)\n");
     return true;
@@ -802,11 +803,13 @@ int main(int argc, char** argv) {
     for (ffs_ctx* cx : ctxs) {
         FFS_CHECK(cx, ffs_ctx_set_params(cx, &prm));
         FFS_CHECK(cx, ffs_ctx_set_max_valid_scope(cx, args.max_valid_scope));
+        FFS_CHECK(cx, ffs_ctx_set_gain(cx, args.gain));
     }
     if (max_valid >= 0 && args.max_valid_scope == FFS_MAX_VALID_WINDOW)
         std::printf("Trusted range: pixels above %lld are masked for their frame (window scope: out of every window's sums, and not spots)\n", (long long)max_valid);
     else if (max_valid >= 0) std::printf("Trusted range: centre pixels above %lld are not spots\n", (long long)max_valid);
-    if (args.validate && !create_validation_contexts(devices, ctxs, shape, batch, prm, args.max_valid_scope, vctxs)) return 1;
+    if (args.gain > 0.0) std::printf("Detector gain: %g (a background window's variance is taken as gain x mean)\n", args.gain);
+    if (args.validate && !create_validation_contexts(devices, ctxs, shape, batch, prm, args.max_valid_scope, args.gain, vctxs)) return 1;
     if (args.save_h5 && !h5_supported()) {
         std::printf("Error: --save-h5 needs an HDF5-enabled build\n");
         return 1;

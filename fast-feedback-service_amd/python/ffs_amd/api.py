@@ -89,7 +89,7 @@ EXPORTS = [
     "ffs_submit_compressed", "ffs_decode_only", "ffs_submit_encoded", "ffs_decode_only_encoded", "ffs_stream_spot_centres", "ffs_bench_threshold", "ffs_bench_hbm", "ffs_stream_debug_planes", "ffs_stream_debug_bitplane", "ffs_selftest_sqrt", "ffs_stack3d_create",
     "ffs_stack3d_destroy", "ffs_stack3d_add_batch", "ffs_stack3d_add_slice", "ffs_stack3d_finish", "ffs_stack3d_signals", "ffs_stack3d_last_finish_ms", "ffs_multi_init", "ffs_multi_transport",
     "ffs_ctx_set_tuning", "ffs_bench_pipeline", "ffs_device_numa_node", "ffs_stream_reserve_host", "ffs_stream_last_path", "ffs_multi_gather_rows",
-    "ffs_ctx_set_max_valid_scope",
+    "ffs_ctx_set_max_valid_scope", "ffs_ctx_set_gain",
 ]
 
 _lib = None
@@ -114,6 +114,7 @@ def load_library():
         L.ffs_ctx_set_params.argtypes = [C.c_void_p, C.POINTER(Params)]
         L.ffs_ctx_set_tuning.argtypes = [C.c_void_p, C.c_char_p, C.c_longlong]
         L.ffs_ctx_set_max_valid_scope.argtypes = [C.c_void_p, C.c_int]
+        L.ffs_ctx_set_gain.argtypes = [C.c_void_p, C.c_double]
         L.ffs_bench_pipeline.argtypes = [C.POINTER(C.c_void_p), C.c_uint32, C.c_void_p, C.c_size_t, C.c_size_t, C.c_uint32,
                                          C.c_uint32, C.c_int64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
         L.ffs_device_numa_node.argtypes = [C.c_int]
@@ -261,6 +262,13 @@ class Context:
                 raise ValueError(f"max_valid scope must be 'centre' or 'window', not {scope!r}")
             scope = names[scope]
         self._check(self._lib.ffs_ctx_set_max_valid_scope(self._h, int(scope)))
+
+    def set_gain(self, gain):
+        """ffs_ctx_set_gain: the detector gain of the dispersion tests (DIALS spotfinder.threshold.dispersion.gain) -- a background
+        window's variance is gain * mean.  0 = off (photon counts, the default); any finite g > 0 selects the gain form of
+        baseline.cpp (the general-window kernel at every window).  Kept across set_params; a batch takes it as it is at submit.
+        Refused (FfsError, state unchanged): negative, NaN, infinite; g > 0 with extended_flavour 1."""
+        self._check(self._lib.ffs_ctx_set_gain(self._h, float(gain)))
 
     def set_tuning(self, **kw):
         """ffs_ctx_set_tuning: A/B partners, fall-backs and capacities (same results either way); see include/ffs_hip.h."""

@@ -182,6 +182,24 @@ int ffs_ctx_set_params(ffs_ctx *ctx, const ffs_params *p);
 #define FFS_MAX_VALID_WINDOW 1
 int ffs_ctx_set_max_valid_scope(ffs_ctx *ctx, int scope);
 
+/* The detector gain of both dispersion tests: DIALS spotfinder.threshold.dispersion.gain, as one scalar per context.  The tests
+ * assume that a background window's variance equals its mean (photon counts); a detector that delivers ADU or keV (Jungfrau, CCDs,
+ * any integrating detector) has variance = gain * mean.  The arithmetic is the reference's threshold_w_gain of
+ * baseline/spotfinder/baseline.cpp with a constant gain map; the reference's GPU kernels and standalone.cc have no gain.
+ *   0 (default): off -- the same kernels, paths and results as before, bit for bit.
+ *   g > 0 (1.0 included): with the window sums m, x, y counted as without a gain and converted once to float64, each operation
+ *     rounded separately in this order --
+ *       standard algorithm (baseline.cpp:241-247):  a = m*y - x*x;  b = m*p - x;
+ *         c = (g*x) * ((m - 1) + nsig_b*sqrt(2*(m - 1)));  d = nsig_s*sqrt((g*x)*m);  strong = a > c && b > d
+ *       extended algorithm, flavour 0: first pass a > c with the same a and c (:539-543); erosion unchanged; final pass
+ *         p >= mean + nsig_s*sqrt(g*mean) (:709-715).
+ *     A gain batch of the standard algorithm takes the general-window kernel at every window (FFS_PATH_WINDOW); the extended
+ *     algorithm takes its plain first pass.  Composes with every kernel_half_x / _y and with FFS_MAX_VALID_WINDOW.
+ * Per context; kept across ffs_ctx_set_params; like the parameters a batch takes it as it is at submit.  FFS_ERR_INVALID, state
+ * unchanged (ffs_last_error has the text): a negative, NaN or infinite gain; a gain > 0 together with extended_flavour 1,
+ * whichever call comes second (that flavour copies the reference's device kernels, which have no gain). */
+int ffs_ctx_set_gain(ffs_ctx *ctx, double gain);
+
 /* Selects between paths that give the SAME results (A/B partners, fall-backs, capacities that tests shrink) --
  * per context, never through the environment; nothing here can change a result.  Keys (default):
  *   "threshold_path"   (0) 0 = windows the streaming kernel cannot vouch for go onto a list (fix-up kernel),
