@@ -17,18 +17,17 @@ extern "C" int ffs_bench_threshold(ffs_stream* s, const void* device_pixels, siz
     int rc = check_layout(s, pitch, fstride, n_frames);
     if (rc != FFS_OK) return rc;
     HIP_TRY(c, hipSetDevice(c->device));
-    s->batch_params = c->params;
-    s->batch_scope = c->max_valid_scope;
-    s->batch_gain = c->gain;
-    const bool ext = c->params.algorithm == FFS_ALGO_DISPERSION_EXTENDED;
+    s->batch = snapshot_of(c);
+    const ThresholdRoute route = batch_route(s, Rerun{});
+    const bool ext = route.ext();
     if (ext) {
         rc = ensure_extended_buffers(s);
         if (rc != FFS_OK) return rc;
     }
     s->ext_e_clean = false;
     const StreamGeometry geo = batch_stream_geometry(s, fstride, n_frames);
-    ThresholdArgs ta = make_threshold_args(s, device_pixels, pitch, fstride, n_frames, geo, Rerun{});
-    if (!ext && !win_default(c->params) && !window_kernel_for(s, ta)) {
+    ThresholdArgs ta = make_threshold_args(s, device_pixels, pitch, fstride, n_frames, geo, route);
+    if (!route.has_dense_kernel()) {
         // (threshold_path 2 at another window: the batch has no dense kernel, k_exact_w gathers every pixel -- nothing here to time)
         c->err = "ffs_bench_threshold: threshold_path 2 with a window other than 3,3 has no dense kernel to time";
         return FFS_ERR_INVALID;
@@ -54,9 +53,9 @@ extern "C" int ffs_bench_threshold(ffs_stream* s, const void* device_pixels, siz
         if (err == hipSuccess) err = hipMemsetAsync(s->d_occ, 0, (size_t)s->max_batch * occ_frame_words(L) * 4, s->st);
         if (err == hipSuccess && e_sparse) err = hipMemsetAsync(s->d_eplane, 0, (size_t)s->max_batch * L.plane_frame_stride, s->st);
         if (err != hipSuccess) break;
-        launch_dense_kernel(s, ta, geo, n_frames, ev[4 * i], ev[4 * i + 1]);
+        launch_dense_kernel(s, route, ta, geo, n_frames, ev[4 * i], ev[4 * i + 1]);
         err = hipEventRecord(ev[4 * i + 2], s->st);
-        launch_dense_rest(s, ta, n_frames);
+        launch_dense_rest(s, route, ta, n_frames);
         if (err == hipSuccess) err = hipEventRecord(ev[4 * i + 3], s->st);
         if (err == hipSuccess) err = hipGetLastError();
     }

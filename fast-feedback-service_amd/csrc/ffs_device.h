@@ -4,6 +4,7 @@
 #include <stdint.h>
 
 #include "launch_geometry.hpp"
+#include "threshold_route.hpp"
 
 // Timing experiments (phases switched off, kernels stopped half way: results are wrong when used) exist only in builds
 // with -DFFS_EXPERIMENTS (make experiments -> libffs_hip_exp.so, for tools/); the product library has none of them.
@@ -36,7 +37,7 @@ struct ThresholdArgs {
     // The neighbour limit, exclusive (ffs_ctx_set_max_valid_scope): a pixel p >= nb_limit is left out of the
     // count and the sums of every window.  Centre scope: 2^24, the oracle's rule for 32-bit pixels (standalone.cc:78,90), and no kernel
     // of 16-bit pixels reads it.  Window scope with max_valid >= 0: min(max_valid, 2^24 - 1) + 1 (16-bit pixels: at most 65536), read
-    // by the general-window kernel, k_ext_first, and the TRUSTED instantiations of the gathered predicates.  (It fills the four bytes
+    // by the general-window kernel, k_ext_first, and the gathered predicates' instantiations that carry the compare (threshold_route.hpp).  (It fills the four bytes
     // of padding between `pitch` and `maskbits`.)
     uint32_t nb_limit;
     const uint8_t* maskbits;   // valid-pixel bit plane [H][mpitch]
@@ -71,7 +72,7 @@ struct ThresholdArgs {
     int eplane_clean;          // the signal-region plane is all zero (cleared behind the previous batch): the erosion stores its non-zero words only
     int ext_strips, ext_band_rows, ext_bands;
     int ext_flavour;           // 0 = baseline.cpp rules, 1 = device-kernel rules
-    int ext_variant;           // first pass, 16-bit pixels: 2 = streaming kernel (k_stream_u16<true>), 0 = k_ext_first
+    int ext_variant;           // first pass, 16-bit pixels: 2 = streaming kernel (k_stream_u16<true>), 0 = k_ext_first (host side only: ThresholdRoute)
     // one-kernel threshold for 16-bit pixels (kernels_stream.hpp)
     const uint8_t* ginfo;      // [H + 3][gpitch] one dword per 8-pixel group: mask bits | min count << 8 | max count << 16
     const uint8_t* mmap;       // [H][pitch_px] 7x7 window count of every pixel
@@ -109,7 +110,7 @@ struct ThresholdArgs {
     int w_strips, w_band_rows, w_bands;   // general-window kernel: a wave per (strip of 62 eight-pixel groups, band of rows, frame)
     float w_kS, w_kB;          // its float32 screens: nsig_s^2 (1 - 2^-16), nsig_b^2 (1 - 2^-16); 0 = screen off
                                // (a gain batch: w_kS carries the gain, gain nsig_s^2 (1 - 2^-16) -- DESIGN.md section 3.3d)
-    // the detector gain (ffs_ctx_set_gain): 0 = off; > 0 = the GAIN instantiations decide with the variance
+    // the detector gain (ffs_ctx_set_gain): 0 = off; > 0 = the gain instantiations decide with the variance
     // gain * mean (baseline.cpp:241-247, :539-543, :709-715).  No other kernel reads these.
     double gain;
     float g_gain, g_nb;        // float32 screen of a > c under gain: (float)gain and (float)nsig_b; g_gain = 0 = screen off

@@ -2,7 +2,7 @@
 // include/ffs_hip.h, error plumbing, and the few functions one unit calls in another.  Host side only; the kernels
 // live in kernels_*.hpp, each included by exactly one unit:
 //   ffs_context.hip  contexts, masks (kernels_mask.hpp), tuning, streams
-//   ffs_submit.hip   one batch (enqueue_batch: plan_batch decides its path once, a BatchPlan with the launch geometry; then the resets,
+//   ffs_submit.hip   one batch (enqueue_batch: plan_batch decides its path once, a BatchPlan with the launch geometry and the threshold route; then the resets,
 //                    the threshold stage and the sparse stage are launched from that plan), submit entry points, compressed input
 //                    (kernels_stream / threshold / extended / window / ccl / chain / band / decode)
 //   ffs_wait.hip     ffs_wait: overflow re-runs (rerun_batch: the same batch again with a Rerun override), result assembly,
@@ -12,6 +12,8 @@
 // Without HIP, shared with the kernels through ffs_device.h and compiled by a plain C++ test (tests/launch_geometry_check.cc):
 //   launch_geometry.hpp  the frame layout, the launch geometry of the threshold stage (super rows, strips, bands; wave logs and band
 //                        slots a launch needs) and the unit map the kernels invert
+//   threshold_route.hpp  the predicate's variants, which instantiation of a kernel family serves one, and a batch's route through the
+//                        threshold stage (tests/threshold_route_check.cc)
 //   tuning.hpp           struct Tuning
 // No exception leaves the library (guarded()).
 #pragma once
@@ -38,6 +40,7 @@
 
 #include "ffs_hip.h"
 #include "ffs_device.h"
+#include "threshold_route.hpp"
 #include "tuning.hpp"
 
 using namespace ffsamd;
@@ -62,6 +65,14 @@ struct ThreadError {
 // ---- tuning: struct Tuning, tuning.hpp ---------------------------------------------------------------------------
 
 struct ffs_stack3d;
+
+// What a batch is computed with: the context's parameters, its scope of max_valid and its detector gain as they were at submit (re-runs
+// inside ffs_wait keep them).  A new per-batch setting is a new field here.
+struct ParamSnapshot {
+    ffs_params params{};
+    int max_valid_scope = FFS_MAX_VALID_CENTRE;
+    double gain = 0.0;
+};
 
 // A few helper threads per context for ffs_wait's result assembly (wire records -> boxes, reflections, centre rows): one thread
 // moves a batch's 7 MB (45 000 components of 32 Eiger frames) in 0.21 ms -- two thirds of the time the GPU takes for the batch, and
@@ -267,9 +278,7 @@ struct ffs_stream {
     int64_t first_id = 0;
     const void* cur_img = nullptr;
     size_t cur_pitch = 0, cur_fstride = 0;
-    ffs_params batch_params{};
-    int batch_scope = FFS_MAX_VALID_CENTRE;   // ... and the scope of max_valid the batch was submitted under (re-runs inside ffs_wait keep it)
-    double batch_gain = 0.0;                  // ... and the detector gain
+    ParamSnapshot batch;
     float timings[5] = {0, 0, 0, 0, 0};
     bool timings_stale = false;              // the stage times of the last batch are still in its events (ffs_stream_timings reads them out)
     hipEvent_t timing_last = nullptr;
@@ -337,12 +346,7 @@ static int guarded(ffs_ctx* c, F&& body) {
     } while (0)
 
 // ---- small helpers ------------------------------------------------------------------------------------------
-// What a batch is computed with: the context's parameters, its scope of max_valid and its detector gain as they were at submit.
-struct ParamSnapshot {
-    ffs_params params;
-    int max_valid_scope;
-    double gain;
-};
+static inline ParamSnapshot snapshot_of(const ffs_ctx* c) { return ParamSnapshot{c->params, c->max_valid_scope, c->gain}; }
 // What ffs_wait asks of the enqueue that runs a batch AGAIN because a plan did not hold it (ffs_wait.hip, rerun_batch); the default
 // is a normal batch.  An argument of that one call: what a stream remembers beyond it (log_off, runs_overflowed, band_backoff) is
 // in ffs_stream.
@@ -405,7 +409,9 @@ size_t default_staging_bytes(const ffs_stream* s);      // max_batch raw frames 
 // ffs_submit.hip
 bool chain_prepare_device();   // asks for k_frame_chain's dynamic LDS on the current device; false: use the four kernels
 StreamGeometry batch_stream_geometry(const ffs_stream* s, size_t fstride, uint32_t n_frames);   // launch_geometry.hpp's, for a batch of this stream
-ThresholdArgs make_threshold_args(ffs_stream* s, const void* img, size_t pitch, size_t fstride, uint32_t n_frames, const StreamGeometry& g, const Rerun& how);
+ThresholdRoute batch_route(const ffs_stream* s, const Rerun& how);   // threshold_route.hpp's, for the stream's batch (s->batch) and what a re-run overrides
+ThresholdArgs make_threshold_args(ffs_stream* s, const void* img, size_t pitch, size_t fstride, uint32_t n_frames, const StreamGeometry& g,
+                                  const ThresholdRoute& route);
 int check_layout(ffs_stream* s, size_t pitch, size_t fstride, uint32_t n_frames);
 int ensure_extended_buffers(ffs_stream* s);
 int enqueue_batch(ffs_stream* s, const void* d_img, size_t pitch, size_t fstride, uint32_t n, const ParamSnapshot* snapshot = nullptr,
@@ -415,10 +421,9 @@ bool wave_logs_for(ffs_stream* s, ThresholdArgs& a, const StreamGeometry& g, con
 // The threshold stage where all of it runs in s->st, in its two steps: the dense kernel, with HIP events on the dispatch itself (either
 // may be null), and the kernels that follow it (k_bright_fix / k_exact; extended: erosion + final pass; none behind the general-window
 // kernel or with wave logs).  What enqueue_batch launches for such a batch, and what ffs_bench_threshold times.
-void launch_dense_kernel(ffs_stream* s, const ThresholdArgs& a, const StreamGeometry& g, uint32_t n_frames, hipEvent_t start, hipEvent_t stop,
-                         bool plane_clean = false, bool counts_clean = false);
-void launch_dense_rest(ffs_stream* s, const ThresholdArgs& a, uint32_t n_frames);
-bool window_kernel_for(const ffs_stream* s, const ThresholdArgs& a);   // this batch's threshold stage is the general-window kernel
+void launch_dense_kernel(ffs_stream* s, const ThresholdRoute& route, const ThresholdArgs& a, const StreamGeometry& g, uint32_t n_frames, hipEvent_t start,
+                         hipEvent_t stop, bool plane_clean = false, bool counts_clean = false);
+void launch_dense_rest(ffs_stream* s, const ThresholdRoute& route, const ThresholdArgs& a, uint32_t n_frames);
 // ffs_wait.hip
 int ffs_wait_impl(ffs_stream* s, const ffs_frame_result** results, uint32_t* n_results);
 void ahead_register(ffs_stream* s);   // the batch just enqueued may be assembled ahead of its ffs_wait

@@ -26,14 +26,15 @@ bool chain_prepare_device() {   // more than 64 KB of dynamic LDS has to be aske
 }
 
 // ---- the threshold stage's arguments: buffers and pitches, the predicate's constants, the launch geometry ------------------
-// The window scope of max_valid is on for this batch (ffs_ctx_set_max_valid_scope; without a max_valid the scope changes nothing)
-static bool trusted_window(const ffs_stream* s) { return s->batch_scope == FFS_MAX_VALID_WINDOW && s->batch_params.max_valid >= 0; }
-// A detector gain is set for this batch (ffs_ctx_set_gain): the GAIN instantiations of the kernels decide it
-static bool gain_on(const ffs_stream* s) { return s->batch_gain > 0.0; }
-static void set_buffers(ThresholdArgs& a, const ffs_stream* s, const void* img, size_t pitch, size_t fstride, const Rerun& how) {
+ThresholdRoute batch_route(const ffs_stream* s, const Rerun& how) {
+    const ParamSnapshot& b = s->batch;
+    return threshold_route(b.params.algorithm, s->ctx->pixel_bytes, win_default(b.params), b.max_valid_scope, b.params.max_valid, b.gain, how.threshold_path,
+                           s->ctx->tune);
+}
+static void set_buffers(ThresholdArgs& a, const ffs_stream* s, const void* img, size_t pitch, size_t fstride, const ThresholdRoute& route) {
     const ffs_ctx* c = s->ctx;
     const Layout& L = c->L;
-    const ffs_params& p = s->batch_params;
+    const ffs_params& p = s->batch.params;
     a.image = img;
     a.frame_stride = fstride;
     a.pitch = (uint32_t)pitch;
@@ -49,9 +50,8 @@ static void set_buffers(ThresholdArgs& a, const ffs_stream* s, const void* img, 
     a.plane_frame_stride = L.plane_frame_stride;
     a.bytes_frame_stride = L.bytes_frame_stride;
     a.n_tiles = c->n_tiles;
-    // bright windows (sum p >= 65536; 32-bit pixels >= 2^24): onto the list k_bright_fix works off, or -- tuning
-    // "threshold_path" = 1, and whenever that list overflowed (ffs_wait re-runs the batch) -- into the plane as candidates
-    a.bright_to_plane = how.threshold_path >= 0 ? how.threshold_path : c->tune.threshold_path;
+    // bright windows (sum p >= 65536; 32-bit pixels >= 2^24): onto the list k_bright_fix works off, or into the plane as candidates
+    a.bright_to_plane = route.bright_to_plane;
     a.overflow = s->d_overflow;
     a.bright_n = s->d_tile_counts + tile_counts_bytes(s) / 4 - 1;
     a.bright_list = s->d_bright;
@@ -76,9 +76,7 @@ static void set_buffers(ThresholdArgs& a, const ffs_stream* s, const void* img, 
     a.dplane = s->d_dplane;
     a.eplane = s->d_eplane;
     a.eplane_clean = s->ext_e_clean ? 1 : 0;
-    // (the streaming first pass reads the mask tables, which know nothing of a frame's pixels: the window scope of max_valid takes k_ext_first;
-    // so does a gain batch -- the streaming kernels' screens are proven for the photon-count predicate only)
-    a.ext_variant = (c->pixel_bytes == 2 && how.threshold_path < 0 && !trusted_window(s) && !gain_on(s)) ? c->tune.ext_first_pass : 0;
+    a.ext_variant = route.ext_variant;
 }
 static void set_predicate(ThresholdArgs& a, const ffs_params& p, bool trusted, double gain) {
     // (exclusive; the oracle's < 2^24 rule for 32-bit pixels holds on top of max_valid, and 16-bit pixels never reach it)
@@ -107,7 +105,7 @@ static void set_predicate(ThresholdArgs& a, const ffs_params& p, bool trusted, d
     a.w_kS = (std::isfinite(p.nsig_s) && p.nsig_s <= 1024.0) ? (float)(p.nsig_s * p.nsig_s * (1.0 - 1.0 / 65536.0)) : 0.0f;
     a.w_kB = (std::isfinite(p.nsig_b) && p.nsig_b <= 1024.0) ? (float)(p.nsig_b * p.nsig_b * (1.0 - 1.0 / 65536.0)) : 0.0f;
     a.ext_flavour = p.extended_flavour;
-    // The detector gain and what the float32 screens of the GAIN kernels take: the signal screen is win_signal's
+    // The detector gain and what the float32 screens of the gain kernels take: the signal screen is win_signal's
     // own with the gain inside its constant; the dispersion screen takes the gain and nsig_b as floats.  Outside the range the proofs
     // cover (the float32 products must stay normal numbers) a screen is off and float64 decides.
     a.gain = gain;
@@ -144,10 +142,11 @@ static void set_geometry(ThresholdArgs& a, uint32_t n_frames, const StreamGeomet
 StreamGeometry batch_stream_geometry(const ffs_stream* s, size_t fstride, uint32_t n_frames) {
     return stream_geometry(s->ctx->L, s->ctx->pixel_bytes, fstride, n_frames, s->ctx->tune);
 }
-ThresholdArgs make_threshold_args(ffs_stream* s, const void* img, size_t pitch, size_t fstride, uint32_t n_frames, const StreamGeometry& g, const Rerun& how) {
+ThresholdArgs make_threshold_args(ffs_stream* s, const void* img, size_t pitch, size_t fstride, uint32_t n_frames, const StreamGeometry& g,
+                                  const ThresholdRoute& route) {
     ThresholdArgs a{};
-    set_buffers(a, s, img, pitch, fstride, how);
-    set_predicate(a, s->batch_params, trusted_window(s), s->batch_gain);
+    set_buffers(a, s, img, pitch, fstride, route);
+    set_predicate(a, s->batch.params, route.window_scope, s->batch.gain);
     set_geometry(a, n_frames, g, window_geometry(s->ctx->L, n_frames, a.ky), ext_geometry(s->ctx->L, n_frames));
     return a;
 }
@@ -173,36 +172,46 @@ static StreamKernel stream_kernel(const ffs_ctx* c, bool dense_mask, bool extend
 static void launch_stream(ffs_stream* s, const ThresholdArgs& a, const StreamGeometry& g, hipEvent_t start, hipEvent_t stop, hipStream_t st = nullptr) {
     hipExtLaunchKernelGGL(stream_kernel(s->ctx, a.dense_mask != 0, false), stream_grid(a, g), dim3(64), 0, st ? st : s->st, start, stop, 0, a);
 }
-// The general-window kernel (kernels_window.hpp): windows other than 3,3, or every window with tuning "window_kernel" = 1, under the
-// window scope of max_valid (the streaming kernels' screens rest on counts that depend on the mask alone: DESIGN.md section 3.3c) or
-// with a detector gain (their screens are proven for the photon-count predicate: section 3.3d).  The
-// standard algorithm on the plane paths only (no wave logs: those belong to k_stream_u16); the cross-check path (threshold_path 2)
-// keeps its gather.
-bool window_kernel_for(const ffs_stream* s, const ThresholdArgs& a) {
-    return s->batch_params.algorithm == FFS_ALGO_DISPERSION && a.bright_to_plane != 2
-           && (!win_default(s->batch_params) || s->ctx->tune.window_kernel == 1 || trusted_window(s) || gain_on(s));
+// The instantiation of a kernel family a launch takes: (pixel_bytes, variant) as compile-time tags, handed to `launch`, which names the
+// kernel with them.  (`of` folds the variant as threshold_route.hpp's rule says, so no instantiation exists twice.)
+template <typename PixelT, Predicate V>
+struct KernelTag {
+    using pixel = PixelT;
+    static constexpr Predicate of(KernelFamily f) { return instantiated_as(f, sizeof(PixelT), V); }
+};
+template <Predicate V, typename Launch>
+static void with_pixel_tag(int pixel_bytes, Launch& launch) {
+    if (pixel_bytes == 4) launch(KernelTag<uint32_t, V>{});
+    else launch(KernelTag<uint16_t, V>{});
 }
-template <typename PixelT, bool TRUSTED = false, bool GAIN = false>
+template <typename Launch>
+static void with_kernel_tag(int pixel_bytes, Predicate v, Launch&& launch) {
+    if (v == Predicate::kGain) with_pixel_tag<Predicate::kGain>(pixel_bytes, launch);
+    else if (v == Predicate::kWindowScope) with_pixel_tag<Predicate::kWindowScope>(pixel_bytes, launch);
+    else with_pixel_tag<Predicate::kPhotonCount>(pixel_bytes, launch);
+}
+
+// The general-window kernel (kernels_window.hpp), where the route says so (ThresholdStage::kWindow).  The standard algorithm on the plane
+// paths only (no wave logs: those belong to k_stream_u16); the cross-check path (threshold_path 2) keeps its gather.
+template <typename PixelT, Predicate V>
 static void launch_window_t(const ThresholdArgs& a, dim3 grid, hipStream_t st, hipEvent_t start, hipEvent_t stop) {
     const size_t lds = win_ring_bytes((int)sizeof(PixelT), a.ky);
     switch (a.kx) {
-        case 1: hipExtLaunchKernelGGL((k_window<PixelT, 1, TRUSTED, GAIN>), grid, dim3(64), lds, st, start, stop, 0, a); break;
-        case 2: hipExtLaunchKernelGGL((k_window<PixelT, 2, TRUSTED, GAIN>), grid, dim3(64), lds, st, start, stop, 0, a); break;
-        case 3: hipExtLaunchKernelGGL((k_window<PixelT, 3, TRUSTED, GAIN>), grid, dim3(64), lds, st, start, stop, 0, a); break;
-        case 4: hipExtLaunchKernelGGL((k_window<PixelT, 4, TRUSTED, GAIN>), grid, dim3(64), lds, st, start, stop, 0, a); break;
-        case 5: hipExtLaunchKernelGGL((k_window<PixelT, 5, TRUSTED, GAIN>), grid, dim3(64), lds, st, start, stop, 0, a); break;
-        case 6: hipExtLaunchKernelGGL((k_window<PixelT, 6, TRUSTED, GAIN>), grid, dim3(64), lds, st, start, stop, 0, a); break;
-        default: hipExtLaunchKernelGGL((k_window<PixelT, 7, TRUSTED, GAIN>), grid, dim3(64), lds, st, start, stop, 0, a); break;
+        case 1: hipExtLaunchKernelGGL((k_window<PixelT, 1, V>), grid, dim3(64), lds, st, start, stop, 0, a); break;
+        case 2: hipExtLaunchKernelGGL((k_window<PixelT, 2, V>), grid, dim3(64), lds, st, start, stop, 0, a); break;
+        case 3: hipExtLaunchKernelGGL((k_window<PixelT, 3, V>), grid, dim3(64), lds, st, start, stop, 0, a); break;
+        case 4: hipExtLaunchKernelGGL((k_window<PixelT, 4, V>), grid, dim3(64), lds, st, start, stop, 0, a); break;
+        case 5: hipExtLaunchKernelGGL((k_window<PixelT, 5, V>), grid, dim3(64), lds, st, start, stop, 0, a); break;
+        case 6: hipExtLaunchKernelGGL((k_window<PixelT, 6, V>), grid, dim3(64), lds, st, start, stop, 0, a); break;
+        default: hipExtLaunchKernelGGL((k_window<PixelT, 7, V>), grid, dim3(64), lds, st, start, stop, 0, a); break;
     }
 }
-static void launch_window(ffs_stream* s, const ThresholdArgs& a, uint32_t n_frames, hipEvent_t start, hipEvent_t stop, hipStream_t st = nullptr) {
+static void launch_window(ffs_stream* s, const ThresholdRoute& route, const ThresholdArgs& a, uint32_t n_frames, hipEvent_t start, hipEvent_t stop) {
     const dim3 grid((unsigned)(a.w_strips * a.w_bands), n_frames);
-    if (!st) st = s->st;
-    if (gain_on(s) && s->ctx->pixel_bytes == 4) launch_window_t<uint32_t, false, true>(a, grid, st, start, stop);
-    else if (gain_on(s)) launch_window_t<uint16_t, true, true>(a, grid, st, start, stop);   // (centre scope: the limit is 2^24, beyond every pixel)
-    else if (s->ctx->pixel_bytes == 4) launch_window_t<uint32_t>(a, grid, st, start, stop);   // (the neighbour limit is its argument)
-    else if (trusted_window(s)) launch_window_t<uint16_t, true>(a, grid, st, start, stop);
-    else launch_window_t<uint16_t>(a, grid, st, start, stop);
+    with_kernel_tag(s->ctx->pixel_bytes, route.variant, [&](auto tag) {
+        using T = decltype(tag);
+        launch_window_t<typename T::pixel, T::of(KernelFamily::kWindow)>(a, grid, s->st, start, stop);
+    });
 }
 static void launch_bright_fix(ffs_stream* s, const ThresholdArgs& a, hipStream_t st) {
     if (s->ctx->pixel_bytes == 4) hipLaunchKernelGGL(k_bright_fix<uint32_t>, dim3(32), dim3(256), 0, st, a);
@@ -210,37 +219,24 @@ static void launch_bright_fix(ffs_stream* s, const ThresholdArgs& a, hipStream_t
 }
 // path 1: every pixel marked in the plane (decided strong pixels and bright-window candidates alike) takes the gathered
 // predicate; rewrites the plane, the per-tile counts and sets the byte mask's 1s
-static void launch_exact(ffs_stream* s, const ThresholdArgs& a, uint32_t n_frames, hipStream_t st) {
+static void launch_exact(ffs_stream* s, const ThresholdRoute& route, const ThresholdArgs& a, uint32_t n_frames, hipStream_t st) {
     const dim3 grid((unsigned)a.n_tiles, n_frames);
-    const bool u32 = s->ctx->pixel_bytes == 4, trusted = trusted_window(s);   // (trusted: the cross-check path, the only one that gets here with it)
-    const bool gain = gain_on(s);                                              // (and so with a gain)
-    if (a.kx != 3 || a.ky != 3) {   // (the runtime-window gather: exact_strong_w)
-        if (gain && u32) hipLaunchKernelGGL((k_exact_w<uint32_t, true, true>), grid, dim3(256), 0, st, a);
-        else if (gain) hipLaunchKernelGGL((k_exact_w<uint16_t, true, true>), grid, dim3(256), 0, st, a);
-        else if (trusted && u32) hipLaunchKernelGGL((k_exact_w<uint32_t, true>), grid, dim3(256), 0, st, a);
-        else if (trusted) hipLaunchKernelGGL((k_exact_w<uint16_t, true>), grid, dim3(256), 0, st, a);
-        else if (u32) hipLaunchKernelGGL(k_exact_w<uint32_t>, grid, dim3(256), 0, st, a);
-        else hipLaunchKernelGGL(k_exact_w<uint16_t>, grid, dim3(256), 0, st, a);
-        return;
-    }
-    if (gain && u32) hipLaunchKernelGGL((k_exact<uint32_t, true, true>), grid, dim3(256), 0, st, a);
-    else if (gain) hipLaunchKernelGGL((k_exact<uint16_t, true, true>), grid, dim3(256), 0, st, a);
-    else if (trusted && u32) hipLaunchKernelGGL((k_exact<uint32_t, true>), grid, dim3(256), 0, st, a);
-    else if (trusted) hipLaunchKernelGGL((k_exact<uint16_t, true>), grid, dim3(256), 0, st, a);
-    else if (u32) hipLaunchKernelGGL(k_exact<uint32_t>, grid, dim3(256), 0, st, a);
-    else hipLaunchKernelGGL(k_exact<uint16_t>, grid, dim3(256), 0, st, a);
+    // (a variant other than photon-count: the cross-check path, the only one that gets here with it)
+    with_kernel_tag(s->ctx->pixel_bytes, route.variant, [&](auto tag) {
+        using T = decltype(tag);
+        if (route.window_3x3) hipLaunchKernelGGL((k_exact<typename T::pixel, T::of(KernelFamily::kExact)>), grid, dim3(256), 0, st, a);
+        else hipLaunchKernelGGL((k_exact_w<typename T::pixel, T::of(KernelFamily::kExact)>), grid, dim3(256), 0, st, a);   // (the runtime-window gather: exact_strong_w)
+    });
 }
 
 // Extended dispersion: first pass -> erosion -> final threshold (kernels_extended.hpp).  Leaves the strong plane in
 // a.bits, the byte mask and the per-tile counts as the exact stage does.  First pass, 16-bit pixels: the streaming kernel
 // in its extended mode decides it exactly in its drain (ext_variant 2, default); k_ext_first is the plain one-pixel-
 // per-lane kernel that computes the same plane directly (32-bit pixels, tuning "ext_first_pass" = 0, and the fall-back
-// when the bright-window list of a batch overflowed).
-static bool ext_stream_first(const ThresholdArgs& a) { return a.ext_variant >= 2; }
-
-static void launch_ext_first(ffs_stream* s, const ThresholdArgs& a, const StreamGeometry& g, uint32_t n_frames, hipEvent_t start, hipEvent_t stop, bool fix_here = true,
+// when the bright-window list of a batch overflowed): ThresholdRoute::ext_streams_first.
+static void launch_ext_first(ffs_stream* s, const ThresholdRoute& route, const ThresholdArgs& a, const StreamGeometry& g, uint32_t n_frames, hipEvent_t start, hipEvent_t stop, bool fix_here = true,
                              bool plane_clean = false, bool counts_clean = false) {
-    if (ext_stream_first(a)) {
+    if (route.ext_streams_first()) {
         // the kernel writes the non-zero bytes of the first-pass plane; the bright-list count sits behind the tile counts
         // (both are usually clean already: the plane was cleared behind the previous batch's sparse launch, which also zeroed the counts)
         if (!plane_clean) (void)hipMemsetAsync(a.dplane, 0, (size_t)n_frames * a.plane_frame_stride, s->st);
@@ -250,21 +246,19 @@ static void launch_ext_first(ffs_stream* s, const ThresholdArgs& a, const Stream
         return;
     }
     dim3 g1((unsigned)(a.ext_strips * a.ext_bands), n_frames);
-    if (gain_on(s) && s->ctx->pixel_bytes == 2) hipExtLaunchKernelGGL((k_ext_first<uint16_t, true, true>), g1, dim3(64), 0, s->st, start, stop, 0, a);
-    else if (gain_on(s)) hipExtLaunchKernelGGL((k_ext_first<uint32_t, false, true>), g1, dim3(64), 0, s->st, start, stop, 0, a);
-    else if (s->ctx->pixel_bytes == 2 && trusted_window(s)) hipExtLaunchKernelGGL((k_ext_first<uint16_t, true>), g1, dim3(64), 0, s->st, start, stop, 0, a);
-    else if (s->ctx->pixel_bytes == 2) hipExtLaunchKernelGGL(k_ext_first<uint16_t>, g1, dim3(64), 0, s->st, start, stop, 0, a);
-    else hipExtLaunchKernelGGL(k_ext_first<uint32_t>, g1, dim3(64), 0, s->st, start, stop, 0, a);
+    with_kernel_tag(s->ctx->pixel_bytes, route.variant, [&](auto tag) {
+        using T = decltype(tag);
+        hipExtLaunchKernelGGL((k_ext_first<typename T::pixel, T::of(KernelFamily::kExtFirst)>), g1, dim3(64), 0, s->st, start, stop, 0, a);
+    });
 }
-static void launch_ext_rest(ffs_stream* s, const ThresholdArgs& a, uint32_t n_frames, hipStream_t st) {
-    const bool u16 = s->ctx->pixel_bytes == 2, trusted = trusted_window(s), gain = gain_on(s);
+static void launch_ext_rest(ffs_stream* s, const ThresholdRoute& route, const ThresholdArgs& a, uint32_t n_frames, hipStream_t st) {
     // The byte mask: the streaming kernel zero-filled it if somebody wants it (k_ext_final sets 1s in it either way; without a
     // taker they land in a buffer nobody reads); after k_ext_first it is always produced, so zero it here.
-    if (!ext_stream_first(a)) (void)hipMemsetAsync(a.strong_bytes, 0, (size_t)n_frames * a.bytes_frame_stride, st);
+    if (!route.ext_streams_first()) (void)hipMemsetAsync(a.strong_bytes, 0, (size_t)n_frames * a.bytes_frame_stride, st);
     dim3 g3((unsigned)a.n_tiles, n_frames);
-    // (a gain batch has no fused kernel: erosion + final pass below)
-    if (u16 && s->ctx->tune.ext_fused && !gain) {   // erosion inside the final pass's tiles: one launch, the plane crosses memory once
-        hipLaunchKernelGGL(trusted ? k_ext_erode_final_trusted : k_ext_erode_final, g3, dim3(256), (size_t)(kTileRows + 10) * a.mpitch, st, a);
+    if (route.ext_fused) {   // erosion inside the final pass's tiles: one launch, the plane crosses memory once (16-bit pixels, no gain)
+        hipLaunchKernelGGL(route.variant == Predicate::kWindowScope ? k_ext_erode_final<Predicate::kWindowScope> : k_ext_erode_final<Predicate::kPhotonCount>, g3,
+                           dim3(256), (size_t)(kTileRows + 10) * a.mpitch, st, a);
         return;
     }
     const int erode = s->ctx->tune.ext_erode;
@@ -279,12 +273,10 @@ static void launch_ext_rest(ffs_stream* s, const ThresholdArgs& a, uint32_t n_fr
         const unsigned erode_lanes = (a.mpitch / 4) * (unsigned)((a.H + kErodeRows - 1) / kErodeRows);
         hipLaunchKernelGGL(k_ext_erode, dim3((erode_lanes + 255) / 256, n_frames), dim3(256), 0, st, a);
     }
-    if (gain && u16) hipLaunchKernelGGL(k_ext_final_gain<uint16_t>, g3, dim3(256), 0, st, a);
-    else if (gain) hipLaunchKernelGGL(k_ext_final_gain<uint32_t>, g3, dim3(256), 0, st, a);
-    else if (trusted && u16) hipLaunchKernelGGL(k_ext_final_trusted<uint16_t>, g3, dim3(256), 0, st, a);
-    else if (trusted) hipLaunchKernelGGL(k_ext_final_trusted<uint32_t>, g3, dim3(256), 0, st, a);
-    else if (u16) hipLaunchKernelGGL(k_ext_final<uint16_t>, g3, dim3(256), 0, st, a);
-    else hipLaunchKernelGGL(k_ext_final<uint32_t>, g3, dim3(256), 0, st, a);
+    with_kernel_tag(s->ctx->pixel_bytes, route.variant, [&](auto tag) {
+        using T = decltype(tag);
+        hipLaunchKernelGGL((k_ext_final<typename T::pixel, T::of(KernelFamily::kExtFinal)>), g3, dim3(256), 0, st, a);
+    });
 }
 
 int ensure_extended_buffers(ffs_stream* s) {
@@ -310,7 +302,7 @@ static bool wave_logs_possible(const ffs_stream* s, const ThresholdArgs& a, cons
     const ffs_ctx* c = s->ctx;
     const Layout& L = c->L;
     return c->tune.strong_log != 0 && !a.bright_to_plane && !s->log_off && !how.plane && s->st2 != s->st && c->chain_ok
-           && s->batch_params.algorithm != FFS_ALGO_DISPERSION_EXTENDED && c->n_tiles <= kChainMaxTiles && L.H <= kChainMaxRows
+           && s->batch.params.algorithm != FFS_ALGO_DISPERSION_EXTENDED && c->n_tiles <= kChainMaxTiles && L.H <= kChainMaxRows
            && strips_per_frame(L, c->pixel_bytes) <= 16u && a.band_rows <= 1024 && L.W <= 65535;
 }
 // The stream's logs hold `slots` waves: allocated on first use; false: no memory for them.
@@ -351,16 +343,17 @@ bool wave_logs_for(ffs_stream* s, ThresholdArgs& a, const StreamGeometry& g, con
 }
 
 // The threshold stage where all of it runs in s->st (ffs_internal.hpp): the dense kernel ...
-void launch_dense_kernel(ffs_stream* s, const ThresholdArgs& a, const StreamGeometry& g, uint32_t n_frames, hipEvent_t start, hipEvent_t stop, bool plane_clean, bool counts_clean) {
-    if (s->batch_params.algorithm == FFS_ALGO_DISPERSION_EXTENDED) launch_ext_first(s, a, g, n_frames, start, stop, true, plane_clean, counts_clean);
-    else if (window_kernel_for(s, a)) launch_window(s, a, n_frames, start, stop);
+void launch_dense_kernel(ffs_stream* s, const ThresholdRoute& route, const ThresholdArgs& a, const StreamGeometry& g, uint32_t n_frames, hipEvent_t start,
+                         hipEvent_t stop, bool plane_clean, bool counts_clean) {
+    if (route.ext()) launch_ext_first(s, route, a, g, n_frames, start, stop, true, plane_clean, counts_clean);
+    else if (route.stage == ThresholdStage::kWindow) launch_window(s, route, a, n_frames, start, stop);
     else launch_stream(s, a, g, start, stop);
 }
 // ... and what follows it
-void launch_dense_rest(ffs_stream* s, const ThresholdArgs& a, uint32_t n_frames) {
-    if (s->batch_params.algorithm == FFS_ALGO_DISPERSION_EXTENDED) launch_ext_rest(s, a, n_frames, s->st);
-    else if (window_kernel_for(s, a)) return;   // (it decides every pixel itself)
-    else if (a.bright_to_plane) launch_exact(s, a, n_frames, s->st);
+void launch_dense_rest(ffs_stream* s, const ThresholdRoute& route, const ThresholdArgs& a, uint32_t n_frames) {
+    if (route.ext()) launch_ext_rest(s, route, a, n_frames, s->st);
+    else if (route.stage == ThresholdStage::kWindow) return;   // (it decides every pixel itself)
+    else if (route.bright_to_plane) launch_exact(s, route, a, n_frames, s->st);
     else if (!a.wlog) launch_bright_fix(s, a, s->st);   // (with wave logs the sparse launch decides the bright windows)
 }
 
@@ -452,6 +445,7 @@ struct BatchPlan {
     bool banded = false;              // the one launch is k_band_cc + k_frame_merge, `band` says how the streaming launch's bands are split for it
     bool chain_first = false;         // the one launch does the bright-window fix-up and the next streaming kernel waits for its start
     bool want_dense_bytes = false;    // the byte mask of this batch is produced
+    ThresholdRoute route{};           // which threshold stage and which form of the predicate (threshold_route.hpp)
     StreamGeometry geo{};             // the streaming launch's geometry: super rows, strips, bands (launch_geometry.hpp)
     ThresholdArgs ta{};               // the threshold stage's arguments ...
     ThresholdArgs ta_launch{};        // ... and with the wave logs, for the streaming kernel and the one launch that reads them (== ta without logs)
@@ -459,25 +453,26 @@ struct BatchPlan {
     uint32_t path_bits = 0;           // FFS_PATH_*: what ffs_stream_last_path reports for this batch
 };
 
-// Reads the stream, its context and tuning, the batch's parameters (s->batch_params) and the previous batch's counts; `how`: what a
+// Reads the stream, its context and tuning, the batch's settings (s->batch) and the previous batch's counts; `how`: what a
 // re-run overrides.  Changes nothing of the stream but what is allocated on first use (wave logs, the band stage's buffers).
 static BatchPlan plan_batch(ffs_stream* s, const void* d_img, size_t pitch, size_t fstride, uint32_t n, const Rerun& how) {
     ffs_ctx* c = s->ctx;
     const Layout& L = c->L;
-    const ffs_params& p = s->batch_params;
+    const ffs_params& p = s->batch.params;
     BatchPlan P;
     P.n = n;
     P.wait_upload = s->st_up != s->st && !s->dev_input;
     P.counts_were_clean = !s->counts_dirty;
-    P.ext = p.algorithm == FFS_ALGO_DISPERSION_EXTENDED;
+    P.route = batch_route(s, how);
+    P.ext = P.route.ext();
     P.ext_sparse_erode = ext_sparse_erode(c->tune);
     P.geo = batch_stream_geometry(s, fstride, n);
-    P.ta = make_threshold_args(s, d_img, pitch, fstride, n, P.geo, how);
-    P.window = !P.ext && window_kernel_for(s, P.ta);
-    P.list_path = !P.ext && !P.ta.bright_to_plane && !P.window;
+    P.ta = make_threshold_args(s, d_img, pitch, fstride, n, P.geo, P.route);
+    P.window = P.route.stage == ThresholdStage::kWindow;
+    P.list_path = P.route.stage == ThresholdStage::kStreamList;
     // (the byte mask: zero-filled by the streaming kernels only when asked for; the exact stages always produce it)
     P.want_dense_bytes = P.window ? (p.want_strong_mask || c->tune.dense_mask)
-                                  : (P.list_path || (P.ext && ext_stream_first(P.ta))) ? P.ta.dense_mask != 0 : true;
+                                  : (P.list_path || (P.ext && P.route.ext_streams_first())) ? P.ta.dense_mask != 0 : true;
     // The whole sparse stage in one launch, one workgroup per frame (kernels_chain.hpp) ...
     const bool can_chain = c->tune.sparse_stage >= 2 && L.H <= 65535 && c->chain_ok && s->direct_recs && s->h_counts_dev
                            && c->n_tiles <= kChainMaxTiles && L.H <= kChainMaxRows;
@@ -539,7 +534,7 @@ static BatchPlan plan_batch(ffs_stream* s, const void* d_img, size_t pitch, size
 static int take_extended_planes(ffs_stream* s, bool& plane_clean) {
     plane_clean = false;
     s->ext_e_clean = false;
-    if (s->batch_params.algorithm != FFS_ALGO_DISPERSION_EXTENDED) return FFS_OK;
+    if (s->batch.params.algorithm != FFS_ALGO_DISPERSION_EXTENDED) return FFS_OK;
     FFS_TRY(ensure_extended_buffers(s));
     std::swap(s->d_dplane, s->d_dplane2);
     std::swap(s->d_eplane, s->d_eplane2);
@@ -645,11 +640,11 @@ static int launch_threshold_stage(ffs_stream* s, const BatchPlan& plan, bool den
         // The dense stream carries the first pass alone; erosion and the final pass -- a latency-bound gather over the signal
         // region that keeps the vector units half busy -- go to the batch's sparse stream, ahead of its sparse launch, and run
         // BESIDE the next batch's first pass (an issue-bound stream of the whole frame) instead of between two of them.
-        const bool streams = ext_stream_first(ta);   // (the first pass's stop event rides on its dispatch; the bright-window fix-up goes aside too)
-        launch_ext_first(s, ta, plan.geo, n, ev_start, streams ? s->ev[2] : nullptr, false, ext_plane_clean, plan.counts_were_clean);
+        const bool streams = plan.route.ext_streams_first();   // (the first pass's stop event rides on its dispatch; the bright-window fix-up goes aside too)
+        launch_ext_first(s, plan.route, ta, plan.geo, n, ev_start, streams ? s->ev[2] : nullptr, false, ext_plane_clean, plan.counts_were_clean);
         FFS_TRY(sparse_stream_follows(s, streams));
         if (streams) hipLaunchKernelGGL((k_bright_fix<uint16_t, true>), dim3(32), dim3(256), 0, s->st2, ta);
-        launch_ext_rest(s, ta, n, s->st2);
+        launch_ext_rest(s, plan.route, ta, n, s->st2);
     } else if (plan.window) {
         // The plane, the per-tile counts, the byte mask when it is asked for and the occupancy bitmap when the one-launch sparse stage
         // reads it: what that stage reads after k_exact
@@ -657,7 +652,7 @@ static int launch_threshold_stage(ffs_stream* s, const BatchPlan& plan, bool den
         tw.dense_mask = plan.want_dense_bytes ? 1 : 0;
         tw.occ = (c->tune.occupancy_bitmap && plan.will_chain) ? s->d_occ : nullptr;
         FFS_TRY(wait_for_upload(s, plan, s->st));
-        launch_window(s, tw, n, ev_start, s->ev[2]);
+        launch_window(s, plan.route, tw, n, ev_start, s->ev[2]);
         FFS_TRY(sparse_stream_follows(s, true));
     } else if (plan.list_path && plan.aside) {
         // the bright-window fix-up goes to the sparse stream (or into the sparse launch itself: chain_first; with wave logs the
@@ -671,7 +666,7 @@ static int launch_threshold_stage(ffs_stream* s, const BatchPlan& plan, bool den
         }
         FFS_TRY(sparse_stream_follows(s, true));
         if (!plan.chain_first && !plan.use_log) launch_bright_fix(s, ta, s->st2);
-    } else if (!plan.ext && ta.bright_to_plane == 2) {
+    } else if (plan.route.stage == ThresholdStage::kCrossCheck) {
         // the cross-check path of `spotfinder --validate` (tuning "threshold_path" = 2): no streaming kernel, no screen, no LDS
         // queue -- the plane starts as the valid-pixel mask, so k_exact gathers the window of EVERY valid pixel from memory and
         // applies the oracle's predicate to 64-bit sums (exact_strong).  Shares nothing with the hot path but that predicate.
@@ -680,14 +675,14 @@ static int launch_threshold_stage(ffs_stream* s, const BatchPlan& plan, bool den
         HIP_TRY(c, hipMemsetAsync(s->d_sbytes, 0, (size_t)n * L.bytes_frame_stride, s->st));
         for (uint32_t f = 0; f < n; ++f)
             HIP_TRY(c, hipMemcpyAsync(s->d_bits + (size_t)f * L.plane_frame_stride, c->d_maskbits, L.plane_frame_stride, hipMemcpyDeviceToDevice, s->st));
-        launch_exact(s, ta, n, s->st);
+        launch_exact(s, plan.route, ta, n, s->st);
         FFS_TRY(sparse_stream_follows(s, false));
     } else {
         // the whole stage in the dense stream: the streaming kernel + k_bright_fix (path 0 on a context without sparse streams) or
         // + k_exact (path 1); the extended algorithm's first pass + erosion + final pass
         if (!plan.ext) FFS_TRY(wait_for_upload(s, plan, s->st));   // (extended: waited for already, reset_for_batch)
-        launch_dense_kernel(s, ta, plan.geo, n, ev_start, nullptr, ext_plane_clean, plan.counts_were_clean);
-        launch_dense_rest(s, ta, n);
+        launch_dense_kernel(s, plan.route, ta, plan.geo, n, ev_start, nullptr, ext_plane_clean, plan.counts_were_clean);
+        launch_dense_rest(s, plan.route, ta, n);
         FFS_TRY(sparse_stream_follows(s, false));
     }
     HIP_TRY(c, hipGetLastError());
@@ -751,8 +746,8 @@ static SegArgs make_seg_args(const ffs_stream* s, const BatchPlan& plan) {
     sa.H = (uint32_t)L.H;
     sa.row_off = s->d_row_off;
     sa.n_slices = 1;
-    sa.min_spot_size = s->batch_params.min_spot_size;
-    sa.max_sep = s->batch_params.max_peak_centroid_separation;
+    sa.min_spot_size = s->batch.params.min_spot_size;
+    sa.max_sep = s->batch.params.max_peak_centroid_separation;
     sa.summary = s->d_summary;
     sa.acc2 = s->d_acc2;
     sa.zero_counts = s->d_tile_counts;
@@ -825,7 +820,7 @@ static int launch_one_launch_stage(ffs_stream* s, const BatchPlan& plan, const C
         if (plan.aside) c->chain_ev_newest.store(slot);
     }
     HIP_TRY(c, hipGetLastError());
-    if (plan.ext && ext_stream_first(plan.ta) && s->st2 != s->st) {
+    if (plan.ext && plan.route.ext_streams_first() && s->st2 != s->st) {
         // the plane the previous batch used (nobody reads it any more) is cleared here, beside the dense kernels, for the next batch
         // (with the strip erosion the signal-region plane behind it too: one fill, the two are one allocation)
         HIP_TRY(c, hipMemsetAsync(s->d_dplane2, 0, (size_t)s->max_batch * c->L.plane_frame_stride * (plan.ext_sparse_erode ? 2u : 1u), s->st2));
@@ -896,9 +891,7 @@ static int launch_sparse_stage(ffs_stream* s, const BatchPlan& plan) {
 }
 
 int enqueue_batch(ffs_stream* s, const void* d_img, size_t pitch, size_t fstride, uint32_t n, const ParamSnapshot* snapshot, const Rerun& how) {
-    s->batch_params = snapshot ? snapshot->params : s->ctx->params;
-    s->batch_scope = snapshot ? snapshot->max_valid_scope : s->ctx->max_valid_scope;
-    s->batch_gain = snapshot ? snapshot->gain : s->ctx->gain;
+    s->batch = snapshot ? *snapshot : snapshot_of(s->ctx);
     s->cur_img = d_img;
     s->cur_pitch = pitch;
     s->cur_fstride = fstride;
@@ -1283,7 +1276,7 @@ static int ffs_submit_encoded_impl(ffs_stream* s, int codec, const void* const* 
     mark_busy(s);
     s->job_rc = FFS_OK;
     s->job_err.clear();
-    const ParamSnapshot snap{c->params, c->max_valid_scope, c->gain};
+    const ParamSnapshot snap = snapshot_of(c);
     std::vector<size_t> sizes(chunk_bytes, chunk_bytes + n_frames);
     s->job = std::thread([s, c, snap, n_frames, codec, bo_max_tiles, base = std::move(base), sizes = std::move(sizes)]() {
         if (hipSetDevice(c->device) != hipSuccess) {

@@ -23,7 +23,7 @@ static void place_frames(const ffs_stream* s, const std::vector<OverflowFrame>* 
     const size_t B = s->max_batch;
     const uint32_t* h_nc = s->h_counts + counts_comp_at(B);
     const uint32_t* h_sm = s->h_counts + counts_summary_at(B);
-    const bool want_refl = s->batch_params.want_reflections != 0;
+    const bool want_refl = s->batch.params.want_reflections != 0;
     size_t nb = 0, nr = 0, at = 0;
     for (uint32_t f = 0; f < n; ++f) {
         box_at[f] = nb;
@@ -70,7 +70,7 @@ static void fill_frame_results(ffs_stream* s, const std::vector<OverflowFrame>* 
     const uint32_t n = s->n_frames;
     const size_t B = s->max_batch;
     const Layout& L = s->ctx->L;
-    const ffs_params& p = s->batch_params;
+    const ffs_params& p = s->batch.params;
     const uint32_t* h_ns = s->h_counts + counts_strong_at(B);
     const uint32_t* h_nc = s->h_counts + counts_comp_at(B);
     const uint32_t* h_sm = s->h_counts + counts_summary_at(B);
@@ -116,7 +116,7 @@ static int assemble_batch(ffs_stream* s, uint64_t total_recs, const std::vector<
                           std::vector<ffs_box>& out_boxes, std::vector<ffs_reflection>& out_refls, std::vector<float>& out_centres) {
     ffs_ctx* c = s->ctx;
     const uint32_t n = s->n_frames;
-    const ffs_params& p = s->batch_params;
+    const ffs_params& p = s->batch.params;
     const uint32_t* h_nc = s->h_counts + counts_comp_at(s->max_batch);
     // assemble: boxes = components surviving the min-size filter (connected_components.cc:122-135),
     // reflections = components surviving filter_reflections (:207-236); both keep label order.
@@ -219,7 +219,7 @@ static void ahead_main(ffs_ctx* c) {
         }
         int verdict = 3;
         try {
-            const ffs_params& p = s->batch_params;
+            const ffs_params& p = s->batch.params;
             if (hipEventSynchronize(s->ev[4]) == hipSuccess && !p.want_strong_list && !p.want_strong_mask && s->direct_recs) {
                 if (batch_overflow(s) == 0) {
                     const uint32_t* h_nc = s->h_counts + counts_comp_at(s->max_batch);
@@ -308,7 +308,7 @@ void ahead_stop(ffs_ctx* c, bool destroy) {
 // A plan did not hold the batch (an overflow flag of its kernels): the same frames and parameters again, enqueued with what `how`
 // overrides, and waited for in the caller's place.
 static int rerun_batch(ffs_stream* s, const Rerun& how, const ffs_frame_result** results, uint32_t* n_results) {
-    const ParamSnapshot snap{s->batch_params, s->batch_scope, s->batch_gain};
+    const ParamSnapshot snap = s->batch;
     const int rc = enqueue_batch(s, s->cur_img, s->cur_pitch, s->cur_fstride, s->n_frames, &snap, how);
     if (rc != FFS_OK) return rc;
     ++s->reruns;
@@ -395,7 +395,7 @@ static int rerun_overflow_frames(ffs_stream* s) {
             b->ev1_pending = true;
             // (the frame's strong-pixel list comes back to the host whenever somebody may read it: the caller, or a 3D stack
             // that is alive -- ffs_stack3d_add_batch takes an overflow frame's list from here, tuning "device_lists")
-            ParamSnapshot bp{s->batch_params, s->batch_scope, s->batch_gain};
+            ParamSnapshot bp = s->batch;
             if (c->tune.device_lists == 1 || (c->tune.device_lists == 2 && g_live_stacks.load() > 0)) bp.params.want_strong_list = 1;
             int rc = enqueue_batch(b, img, s->cur_pitch, s->cur_fstride, 1, &bp);
             if (rc != FFS_OK) return rc;
@@ -486,7 +486,7 @@ static int second_phase_copies(ffs_stream* s, uint64_t total_recs, uint32_t max_
     ffs_ctx* c = s->ctx;
     const uint32_t n = s->n_frames;
     const Layout& L = c->L;
-    const ffs_params& p = s->batch_params;
+    const ffs_params& p = s->batch.params;
     bool second_phase = false;
     if (total_recs > s->spec_recs_copied) {  // more records than the speculative copy brought: fetch the rest
         const size_t rb = sizeof(WireRec2);

@@ -27,15 +27,12 @@ namespace ffsamd {
 
 constexpr int kExtLaneOffset = 4;  // lane l sits on x = 56 * strip - 4 + l
 
-// TRUSTED (16-bit pixels; 32-bit pixels read the same limit as an argument in their one instantiation): the window scope of max_valid,
-// a pixel p >= a.nb_limit is masked for its frame -- out of the window sums here, no background in the final pass, and its own
-// first-pass bit is zero (the centre test below), so it erodes its neighbours like any background pixel.
-// GAIN (ffs_ctx_set_gain): a = m y - x^2 and c = (gain x)((m - 1) + nsig_b sqrt(2 (m - 1))), baseline.cpp:539-543 (DESIGN.md section
-// 3.3d); the 16-bit instantiation carries the neighbour-limit compare, as every gain kernel does.
-template <typename PixelT, bool TRUSTED = false, bool GAIN = false>
+// V: the predicate's variant (threshold_route.hpp).  A pixel the neighbour limit leaves out has a zero first-pass
+// bit of its own (the centre test below), so it erodes its neighbours like any background pixel (section 3.3c); the gain form is
+// baseline.cpp:539-543 (section 3.3d).
+template <typename PixelT, Predicate V = Predicate::kPhotonCount>
 __global__ __launch_bounds__(64) void k_ext_first(const ThresholdArgs a) {
-    static_assert(!TRUSTED || sizeof(PixelT) == 2, "32-bit pixels take the neighbour limit as an argument");
-    static_assert(!GAIN || TRUSTED || sizeof(PixelT) == 4, "the gain kernels always carry the neighbour-limit compare");
+    constexpr bool TRUSTED = compares_limit(KernelFamily::kExtFirst, sizeof(PixelT), V), GAIN = gain_form(V);
     const int lane = threadIdx.x;
     const int strip = blockIdx.x % a.ext_strips;
     const int band = blockIdx.x / a.ext_strips;
@@ -142,11 +139,6 @@ __global__ __launch_bounds__(64) void k_ext_first(const ThresholdArgs a) {
         }
     }
 }
-template __global__ void k_ext_first<uint16_t>(const ThresholdArgs);
-template __global__ void k_ext_first<uint32_t>(const ThresholdArgs);
-template __global__ void k_ext_first<uint16_t, true>(const ThresholdArgs);
-template __global__ void k_ext_first<uint16_t, true, true>(const ThresholdArgs);
-template __global__ void k_ext_first<uint32_t, false, true>(const ThresholdArgs);
 
 // One row of the horizontally eroded plane for word column w: row yy of D with "does not erode its neighbours" pixels set (beyond
 // the image width; with the device kernels' rule also masked pixels), eroded horizontally by 2.  `centre` = D's own word.
@@ -276,8 +268,9 @@ template __global__ void k_ext_erode_strips<16, false>(const ThresholdArgs);
 template __global__ void k_ext_erode_strips<16, true>(const ThresholdArgs);
 
 // X3 predicate: baseline.cpp:580-645 for one pixel of the signal region E.
-template <typename PixelT, bool TRUSTED, bool GAIN>
+template <typename PixelT, Predicate V>
 __device__ __forceinline__ bool ext_final_strong(const ThresholdArgs& a, const uint8_t* img, const uint32_t* eplane, int e_y0, int x, int y) {
+    constexpr bool TRUSTED = compares_limit(KernelFamily::kExtFinal, sizeof(PixelT), V), GAIN = gain_form(V);
     const int W = a.W, H = a.H;
     const int xs = max(x - 5, 0), xe = min(x + 5, W - 1);  // kernel + 2, clipped (:591-598)
     const int ncol = xe - xs + 1;
@@ -368,8 +361,9 @@ __device__ __forceinline__ uint32_t quad_sum(uint32_t v) {
     v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x4E, 0xf, 0xf, true);   // quad_perm [2,3,0,1]
     return v;
 }
-template <bool TRUSTED, bool GAIN>
+template <Predicate V>
 __device__ __forceinline__ bool ext_final_strong4(const ThresholdArgs& a, const uint8_t* img, const uint32_t* eplane, int e_y0, int x0, int y, int sub) {
+    constexpr bool TRUSTED = compares_limit(KernelFamily::kExtFinal, 2, V), GAIN = gain_form(V);
     const int H = a.H;
     const int dpr = (int)(a.mpitch >> 2);
     const int bx = x0 - 8;                         // block column 0; a multiple of 4
@@ -441,24 +435,17 @@ __device__ __forceinline__ bool ext_final_strong4(const ThresholdArgs& a, const 
 // (16-bit pixels: four pixels per quad of lanes, MODE 2 of the tile skeleton; 32-bit pixels: one pixel per lane)
 // (seven workgroups a CU: 72 VGPRs without a vector spill where the compiler took 80 for six; 186-187 against 189-190 us with the erosion,
 // profiles/r04x_ext_final_7_waves_per_simd_ab.txt -- eight need 64 VGPRs and spill: +40 us)
-template <typename PixelT>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7, 7))) void k_ext_final(const ThresholdArgs a) { exact_tile<PixelT, 256, kExactListCap, sizeof(PixelT) == 2 ? 2 : 1>(a); }
-template __global__ void k_ext_final<uint16_t>(const ThresholdArgs);
-template __global__ void k_ext_final<uint32_t>(const ThresholdArgs);
-// the same under the window scope of max_valid (no waves-per-SIMD request: with the quad variant's compares the compiler takes 104
-// VGPRs, four workgroups a CU, and spills nothing -- held to seven it spills 42 VGPRs, to six 28)
-template <typename PixelT>
-__global__ __launch_bounds__(256) void k_ext_final_trusted(const ThresholdArgs a) { exact_tile<PixelT, 256, kExactListCap, sizeof(PixelT) == 2 ? 2 : 1, false, true>(a); }
-template __global__ void k_ext_final_trusted<uint16_t>(const ThresholdArgs);
-template __global__ void k_ext_final_trusted<uint32_t>(const ThresholdArgs);
-// the same with the gain in the local test (ffs_ctx_set_gain; MODE 2 for 16-bit pixels, MODE 1 for 32-bit ones); like every gain kernel
-// it carries the neighbour-limit compare.  A gain batch has no fused erosion: tuning "ext_fused" falls back to erosion + this.
-template <typename PixelT>
-__global__ __launch_bounds__(256) void k_ext_final_gain(const ThresholdArgs a) { exact_tile<PixelT, 256, kExactListCap, sizeof(PixelT) == 2 ? 2 : 1, false, true, true>(a); }
-template __global__ void k_ext_final_gain<uint16_t>(const ThresholdArgs);
-template __global__ void k_ext_final_gain<uint32_t>(const ThresholdArgs);
+// Templated on the predicate's variant.  A gain batch has no fused erosion: tuning "ext_fused" falls back to erosion + k_ext_final.
+template <typename PixelT, Predicate V>
+__global__ __launch_bounds__(256) void k_ext_final(const ThresholdArgs a) { exact_tile<PixelT, 256, kExactListCap, sizeof(PixelT) == 2 ? 2 : 1, false, V>(a); }
+// (photon-count is defined on its own for its occupancy attribute: with the other variants' compares the compiler takes 104 VGPRs, four
+// workgroups a CU, and spills nothing -- held to seven waves it spills 42 VGPRs, to six 28)
+#define FFS_EXT_FINAL_7 template <> __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7, 7))) void
+FFS_EXT_FINAL_7 k_ext_final<uint16_t, Predicate::kPhotonCount>(const ThresholdArgs a) { exact_tile<uint16_t, 256, kExactListCap, 2>(a); }
+FFS_EXT_FINAL_7 k_ext_final<uint32_t, Predicate::kPhotonCount>(const ThresholdArgs a) { exact_tile<uint32_t, 256, kExactListCap, 1>(a); }
+#undef FFS_EXT_FINAL_7
 // erosion + final pass in one launch (16-bit pixels; dynamic LDS: 18 rows of the plane = 18 * mpitch bytes)
-__global__ __launch_bounds__(256) void k_ext_erode_final(const ThresholdArgs a) { exact_tile<uint16_t, 256, kExactListCap, 3>(a); }
-__global__ __launch_bounds__(256) void k_ext_erode_final_trusted(const ThresholdArgs a) { exact_tile<uint16_t, 256, kExactListCap, 3, false, true>(a); }
+template <Predicate V>
+__global__ __launch_bounds__(256) void k_ext_erode_final(const ThresholdArgs a) { exact_tile<uint16_t, 256, kExactListCap, 3, false, V>(a); }
 
 }  // namespace ffsamd

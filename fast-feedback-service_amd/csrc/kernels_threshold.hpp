@@ -40,16 +40,16 @@ constexpr int kQCap = 64;        // lane-group queue entries per wave of the str
 // ================================================================================================
 
 // The oracle's predicate on a window's exact sums (standalone.cc:165-170), shared by the gathered forms below.
-// GAIN: the variance of a background window is a.gain * mean, not mean (ffs_ctx_set_gain; baseline.cpp:241-247 with a scalar gain,
-// the extended first pass :539-543 has its own kernel, k_ext_first: no gathered form) -- every operation rounded separately, in the order of the C++ text.
-template <bool DISP_ONLY, bool GAIN = false>
+// V: the predicate's variant (threshold_route.hpp); its gain form is baseline.cpp:241-247 with a scalar gain, every
+// operation rounded separately, in the order of the C++ text (the extended first pass, :539-543, has its own kernel and no gathered form).
+template <bool DISP_ONLY, Predicate V = Predicate::kPhotonCount>
 __device__ __forceinline__ bool exact_decide(const ThresholdArgs& a, uint32_t m, unsigned long long sx, unsigned long long sy, uint32_t pc, bool centre_valid) {
     // :165  mask[k] && m >= min_count && x >= 0 && src[k] > threshold
     const double src = (double)pc;
     if (!(centre_valid && (int)m >= a.min_count && (DISP_ONLY || src > a.threshold))) return false;
     if (a.max_valid >= 0 && (long long)pc > a.max_valid) return false;  // GPU reference only, thresholding.cu:208-215
     const double md = (double)m, xd = (double)sx, yd = (double)sy;
-    if constexpr (GAIN) {
+    if constexpr (gain_form(V)) {
         static_assert(!DISP_ONLY, "no gain batch gathers the extended first pass (k_bright_fix<., true> follows the streaming kernel only)");
         const double gx = a.gain * xd;
         const double av = md * yd - xd * xd;                                                         // :242
@@ -87,16 +87,13 @@ __device__ __forceinline__ bool gain_disp_rejects(const ThresholdArgs& a, long l
 // All seven window rows (pixels and mask bits) are requested before any is used, so a candidate
 // costs one memory round trip, not seven.
 // DISP_ONLY: the extended algorithm's first pass (baseline.cpp:468-473) -- same sums, a > c alone.
-// TRUSTED (here and in exact_strong_w): the window scope of max_valid -- a neighbour counts when p < a.nb_limit, for either pixel
-// type (ffs_device.h); only the cross-check path instantiates it, the hot path's callers compile to what they were.
-// GAIN (here, in exact_strong_w and exact_tile): exact_decide's gain form; such an instantiation always carries the neighbour-limit
-// compare (2^24 under the centre scope: no pixel of either type that the oracle counts reaches it).
-template <typename PixelT, bool TRUSTED>
+// V (here, in exact_strong_w and exact_tile): the predicate's variant; only the cross-check path instantiates another than photon-count.
+template <typename PixelT, Predicate V>
 __device__ __forceinline__ bool neighbour_counts(const ThresholdArgs& a, uint32_t p) {
-    if constexpr (TRUSTED) return p < a.nb_limit;
+    if constexpr (compares_limit(KernelFamily::kExact, sizeof(PixelT), V)) return p < a.nb_limit;
     else return sizeof(PixelT) == 2 || p < (1u << 24);   // mm = mask && src < 2^24, standalone.cc:78,90
 }
-template <typename PixelT, bool DISP_ONLY = false, bool TRUSTED = false, bool GAIN = false>
+template <typename PixelT, bool DISP_ONLY = false, Predicate V = Predicate::kPhotonCount>
 __device__ bool exact_strong(const ThresholdArgs& a, const uint8_t* img, int x, int y) {
     const int W = a.W, H = a.H;
     const int xs = max(x - 3, 0), xe = min(x + 3, W - 1);  // window clipped to the image, :126-130
@@ -145,7 +142,7 @@ __device__ bool exact_strong(const ThresholdArgs& a, const uint8_t* img, int x, 
         }
 #pragma unroll
         for (int q = 0; q < 8; ++q) {
-            const bool inc = ((bits >> q) & 1u) && neighbour_counts<PixelT, TRUSTED>(a, p[q]);
+            const bool inc = ((bits >> q) & 1u) && neighbour_counts<PixelT, V>(a, p[q]);
             const uint32_t pv = inc ? p[q] : 0u;
             m += inc ? 1u : 0u;
             sx += pv;
@@ -153,13 +150,13 @@ __device__ bool exact_strong(const ThresholdArgs& a, const uint8_t* img, int x, 
         }
     }
 
-    return exact_decide<DISP_ONLY, GAIN>(a, m, sx, sy, pc, centre_valid);
+    return exact_decide<DISP_ONLY, V>(a, m, sx, sy, pc, centre_valid);
 }
 
 // exact_strong at the runtime window (2 a.kx + 1) x (2 a.ky + 1), kx, ky in 1..7: what k_exact<., true> gathers on the cross-check
 // path (tuning "threshold_path" = 2) for windows other than 3,3.  Row after row (at most 15), 16 pixels from an even column cover
 // the (<= 15 wide) window row; 64-bit sums, the same predicate.  Shares nothing with kernels_window.hpp but exact_decide.
-template <typename PixelT, bool TRUSTED = false, bool GAIN = false>
+template <typename PixelT, Predicate V = Predicate::kPhotonCount>
 __device__ bool exact_strong_w(const ThresholdArgs& a, const uint8_t* img, int x, int y) {
     const int W = a.W, H = a.H;
     const int xs = max(x - a.kx, 0), xe = min(x + a.kx, W - 1);  // window clipped to the image, :126-130
@@ -198,14 +195,14 @@ __device__ bool exact_strong_w(const ThresholdArgs& a, const uint8_t* img, int x
         }
 #pragma unroll
         for (int q = 0; q < 16; ++q) {
-            const bool inc = ((bits >> q) & 1u) && neighbour_counts<PixelT, TRUSTED>(a, p[q]);
+            const bool inc = ((bits >> q) & 1u) && neighbour_counts<PixelT, V>(a, p[q]);
             const uint32_t pv = inc ? p[q] : 0u;
             m += inc ? 1u : 0u;
             sx += pv;
             sy += (unsigned long long)pv * pv;
         }
     }
-    return exact_decide<false, GAIN>(a, m, sx, sy, pc, centre_valid);
+    return exact_decide<false, V>(a, m, sx, sy, pc, centre_valid);
 }
 
 // The same decision from the same sums with HALF the registers: the window's rows come in two batches (four, then three) -- two
@@ -273,9 +270,9 @@ __device__ __forceinline__ bool exact_strong_lite(const ThresholdArgs& a, const 
 // extended algorithm's final test (kernels_extended.hpp)
 // (the signal-region plane E: `eplane` = the frame's plane in global memory, row 0 first, rows `edpr` dwords apart; MODE 3 passes
 // the tile's rows of it in LDS instead -- row `e_y0` first)
-template <typename PixelT, bool TRUSTED = false, bool GAIN = false>
+template <typename PixelT, Predicate V = Predicate::kPhotonCount>
 __device__ __forceinline__ bool ext_final_strong(const ThresholdArgs& a, const uint8_t* img, const uint32_t* eplane, int e_y0, int x, int y);
-template <bool TRUSTED = false, bool GAIN = false>
+template <Predicate V = Predicate::kPhotonCount>
 __device__ __forceinline__ bool ext_final_strong4(const ThresholdArgs& a, const uint8_t* img, const uint32_t* eplane, int e_y0, int x0, int y, int sub);
 // 5 x 5 erosion of the first-pass plane D, one row of one 32-pixel word column: see kernels_extended.hpp
 __device__ __forceinline__ uint32_t ext_erode_hrow(const ThresholdArgs& a, const uint32_t* dp, const uint32_t* mp, int dpr, int w, int yy,
@@ -291,9 +288,8 @@ __device__ __forceinline__ uint32_t ext_erode_hrow(const ThresholdArgs& a, const
 //         of E to a.eplane (for --writeout / ffs_stream_debug_bitplane) and takes every window's E bits from LDS: one launch and a
 //         round trip of the plane less than k_ext_erode + MODE 2.
 // WIN (MODE 0 only): the runtime window of exact_strong_w instead of the 7x7 one.
-// TRUSTED: the predicates' instantiations for the window scope of max_valid (neighbours p >= a.nb_limit are left out).
-// GAIN: the predicates' gain forms (ffs_ctx_set_gain); instantiated with TRUSTED only.
-template <typename PixelT, int NT, int LISTCAP, int MODE = 0, bool WIN = false, bool TRUSTED = false, bool GAIN = false>
+// V: the variant the predicates are instantiated with.
+template <typename PixelT, int NT, int LISTCAP, int MODE = 0, bool WIN = false, Predicate V = Predicate::kPhotonCount>
 __device__ __forceinline__ void exact_tile(const ThresholdArgs& a) {
     // The stage is latency-bound (sparse gathers).  Measured dead ends: a smaller LDS footprint
     // (more tiles resident) and one-wave workgroups both made it slower.  Round 4, extended algorithm (MODE 2, profiles/r04r_ext_final_*):
@@ -400,8 +396,8 @@ __device__ __forceinline__ void exact_tile(const ThresholdArgs& a) {
                 const int y = y0 + row;
                 const bool want = (s_words[g] >> (bit + (uint32_t)sub)) & 1u;   // (only this lane ever changes this bit)
                 bool strong;
-                if (x >= 8 && x + 12 <= a.pitch_px) strong = ext_final_strong4<TRUSTED, GAIN>(a, img, esrc, e_y0, x, y, sub);   // (quad-uniform branch)
-                else strong = want && ext_final_strong<PixelT, TRUSTED, GAIN>(a, img, esrc, e_y0, x + sub, y);                   // next to the frame's left or right edge
+                if (x >= 8 && x + 12 <= a.pitch_px) strong = ext_final_strong4<V>(a, img, esrc, e_y0, x, y, sub);   // (quad-uniform branch)
+                else strong = want && ext_final_strong<PixelT, V>(a, img, esrc, e_y0, x + sub, y);                   // next to the frame's left or right edge
                 if (want) {
                     if (strong) sbytes[(uint64_t)y * a.bpitch + x + sub] = 1;
                     else atomicAnd(&s_words[g], ~(1u << (bit + (uint32_t)sub)));
@@ -416,9 +412,9 @@ __device__ __forceinline__ void exact_tile(const ThresholdArgs& a) {
             const int x = (int)((g - row * dpr) * 32u + bit);
             const int y = y0 + row;
             bool strong;
-            if constexpr (MODE == 1) strong = ext_final_strong<PixelT, TRUSTED, GAIN>(a, img, esrc, e_y0, x, y);
-            else if constexpr (WIN) strong = exact_strong_w<PixelT, TRUSTED, GAIN>(a, img, x, y);
-            else strong = exact_strong<PixelT, false, TRUSTED, GAIN>(a, img, x, y);
+            if constexpr (MODE == 1) strong = ext_final_strong<PixelT, V>(a, img, esrc, e_y0, x, y);
+            else if constexpr (WIN) strong = exact_strong_w<PixelT, V>(a, img, x, y);
+            else strong = exact_strong<PixelT, false, V>(a, img, x, y);
             if (strong) {
                 sbytes[(uint64_t)y * a.bpitch + x] = 1;
             } else {
@@ -476,23 +472,14 @@ __device__ __forceinline__ void exact_tile(const ThresholdArgs& a) {
 
 // NB: __launch_bounds__ must be a literal here -- with a template parameter hipcc 7.2 silently
 // dropped it (default 1024-thread bound -> 178 VGPRs + scratch, kernel 2x slower).
-template <typename PixelT, bool TRUSTED = false, bool GAIN = false>
-__global__ __launch_bounds__(256) void k_exact(const ThresholdArgs a) { exact_tile<PixelT, 256, kExactListCap, 0, false, TRUSTED, GAIN>(a); }
+template <typename PixelT, Predicate V = Predicate::kPhotonCount>
+__global__ __launch_bounds__(256) void k_exact(const ThresholdArgs a) { exact_tile<PixelT, 256, kExactListCap, 0, false, V>(a); }
+// (instantiated here, ahead of the other users of exact_strong: where they are instantiated decides what the compiler inlines)
 template __global__ void k_exact<uint16_t>(const ThresholdArgs);
 template __global__ void k_exact<uint32_t>(const ThresholdArgs);
-template __global__ void k_exact<uint16_t, true>(const ThresholdArgs);
-template __global__ void k_exact<uint32_t, true>(const ThresholdArgs);
-template __global__ void k_exact<uint16_t, true, true>(const ThresholdArgs);
-template __global__ void k_exact<uint32_t, true, true>(const ThresholdArgs);
 // the same at the runtime window (a.kx, a.ky): windows other than 3,3 on the cross-check path (threshold_path 2)
-template <typename PixelT, bool TRUSTED = false, bool GAIN = false>
-__global__ __launch_bounds__(256) void k_exact_w(const ThresholdArgs a) { exact_tile<PixelT, 256, kExactListCap, 0, true, TRUSTED, GAIN>(a); }
-template __global__ void k_exact_w<uint16_t>(const ThresholdArgs);
-template __global__ void k_exact_w<uint32_t>(const ThresholdArgs);
-template __global__ void k_exact_w<uint16_t, true>(const ThresholdArgs);
-template __global__ void k_exact_w<uint32_t, true>(const ThresholdArgs);
-template __global__ void k_exact_w<uint16_t, true, true>(const ThresholdArgs);
-template __global__ void k_exact_w<uint32_t, true, true>(const ThresholdArgs);
+template <typename PixelT, Predicate V = Predicate::kPhotonCount>
+__global__ __launch_bounds__(256) void k_exact_w(const ThresholdArgs a) { exact_tile<PixelT, 256, kExactListCap, 0, true, V>(a); }
 // Inclusive prefix sum over the 64 lanes in six DPP adds (row_shr 1/2/4/8 inside the rows of 16, then row_bcast:15 and
 // row_bcast:31 carry the row totals on) instead of six ds_bpermute round trips.
 __device__ __forceinline__ uint32_t wave_inclusive_scan(uint32_t v) {

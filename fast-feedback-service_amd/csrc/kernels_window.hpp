@@ -14,11 +14,10 @@
 // m and the sums count the valid neighbours, and for 32-bit pixels only those below 2^24 (standalone.cc:78,90; exact_strong).
 // Neighbour limit (ThresholdArgs.nb_limit, exclusive): with ffs_ctx_set_max_valid_scope(FFS_MAX_VALID_WINDOW) a pixel above max_valid
 // is masked for its frame -- out of m and both sums of every window.  32-bit pixels: the 2^24 above IS that argument (2^24 under the
-// centre scope, min(max_valid, 2^24 - 1) + 1 under the window scope), the same compare.  16-bit pixels: the TRUSTED instantiations
-// carry the compare; the others are the code they were.  The sums are over a subset of the window, so every bound above holds.
-// Gain (ffs_ctx_set_gain): the GAIN instantiations decide with exact_decide's gain form (baseline.cpp:241-247);
-// they always carry the neighbour-limit compare, so there are 7 + 7 of them.  Their screens: win_signal is the same code with the gain
-// inside w_kS; win_rest takes the gain form's a = m*y - x^2 and c (gain_disp_rejects).
+// centre scope, min(max_valid, 2^24 - 1) + 1 under the window scope), the same compare.  16-bit pixels: which instantiations carry the
+// compare is threshold_route.hpp's rule.  The sums are over a subset of the window, so every bound above holds.
+// The gain variant's screens: win_signal is the same code with the gain inside w_kS; win_rest takes the gain form's a = m*y - x^2 and c
+// (gain_disp_rejects).
 // Every pixel is then decided by exact_decide -- the oracle's float64 predicate, operation for operation -- behind screens that
 // are proven supersets (win_signal, win_rest).  Output: what the sparse stage reads after k_exact -- the strong bit plane, per-tile counts,
 // the occupancy bitmap when the sparse launch reads it (a.occ != nullptr), the byte mask when somebody asked for it.
@@ -62,8 +61,9 @@ __device__ __forceinline__ void win_unpack(const WinRow<PixelT>& r, uint32_t (&p
 }
 
 // column sums += (SUB: -=) one row's contribution
-template <typename PixelT, bool SUB, bool TRUSTED>
+template <typename PixelT, bool SUB, Predicate V>
 __device__ __forceinline__ void win_columns(uint32_t (&cs)[8], uint64_t (&cq)[8], const WinRow<PixelT>& r, uint32_t limit) {
+    constexpr bool TRUSTED = compares_limit(KernelFamily::kWindow, sizeof(PixelT), V);
     uint32_t p[8];
     win_unpack<PixelT>(r, p);
 #pragma unroll
@@ -108,15 +108,15 @@ __device__ __forceinline__ bool win_signal(const ThresholdArgs& a, uint32_t m, u
 }
 // win_rest, only where win_signal passed: (16-bit pixels) av = m*y - x^2 - x(m-1) is an exact integer in float64 and cv >= 0, so
 // av <= 0 decides "no", and the float32 square test rejects av < cv; then the oracle's float64 predicate itself.
-// GAIN: d = nsig_s sqrt((gain x) m), so win_signal's test holds with w_kS = gain nsig_s^2 (1 - 2^-16) (set_predicate); here a and c take
-// their gain forms: gain_disp_rejects.
-template <typename PixelT, bool GAIN = false>
+// The gain variant: d = nsig_s sqrt((gain x) m), so win_signal's test holds with w_kS = gain nsig_s^2 (1 - 2^-16) (set_predicate); here a
+// and c take their gain forms: gain_disp_rejects.
+template <typename PixelT, Predicate V>
 __device__ __forceinline__ bool win_rest(const ThresholdArgs& a, uint32_t m, uint32_t sx, uint64_t sy, uint32_t pc) {
-    if constexpr (GAIN) {
+    if constexpr (gain_form(V)) {
         if constexpr (sizeof(PixelT) == 2) {   // (m*y < 225 * 225 * 2^32 and x^2 < 2^48: int64 holds them)
             if (gain_disp_rejects(a, (long long)m * (long long)sy - (long long)sx * (long long)sx, sx, m)) return false;
         }
-        return exact_decide<false, true>(a, m, sx, sy, pc, true);
+        return exact_decide<false, V>(a, m, sx, sy, pc, true);
     }
     if constexpr (sizeof(PixelT) == 2) {
         const long long A = (long long)m * (long long)sy - (long long)sx * (long long)sx - (long long)sx * (long long)(m - 1u);
@@ -132,11 +132,10 @@ __host__ __device__ inline size_t win_ring_bytes(int pixel_bytes, int ky) {
     return (size_t)(2 * ky + 2) * 64 * (pixel_bytes == 2 ? 20 : 36);
 }
 
-template <typename PixelT, int KX, bool TRUSTED = false, bool GAIN = false>
+template <typename PixelT, int KX, Predicate V = Predicate::kPhotonCount>
 __global__ __launch_bounds__(64) void k_window(const ThresholdArgs a) {
     static_assert(KX >= 1 && KX <= 7, "window half-width 1..7");
-    static_assert(!TRUSTED || sizeof(PixelT) == 2, "32-bit pixels take the neighbour limit as an argument: one instantiation");
-    static_assert(!GAIN || TRUSTED || sizeof(PixelT) == 4, "the gain kernels always carry the neighbour-limit compare");
+    constexpr bool TRUSTED = compares_limit(KernelFamily::kWindow, sizeof(PixelT), V);
     const uint32_t limit = a.nb_limit;
     const int lane = (int)threadIdx.x;
     const int strip = (int)(blockIdx.x % (uint32_t)a.w_strips), band = (int)(blockIdx.x / (uint32_t)a.w_strips);
@@ -183,7 +182,7 @@ __global__ __launch_bounds__(64) void k_window(const ThresholdArgs a) {
     for (int r = max(0, y0 - 1 - ky); r <= min(a.H - 1, y0 - 1 + ky); ++r) {
         const WinRow<PixelT> w = win_load<PixelT>(a, img, r, g, g_ok);
         put(r, w);
-        win_columns<PixelT, false, TRUSTED>(cs, cq, w, limit);
+        win_columns<PixelT, false, V>(cs, cq, w, limit);
     }
 
     uint8_t* plane = a.bits + (uint64_t)frame * a.plane_frame_stride;
@@ -197,8 +196,8 @@ __global__ __launch_bounds__(64) void k_window(const ThresholdArgs a) {
         const WinRow<PixelT> l = get(y - ky - 1);
         const WinRow<PixelT> c = get(y);
         put(y + ky, e);   // (2ky + 2 slots: neither the leaving nor the centre row shares its slot)
-        win_columns<PixelT, false, TRUSTED>(cs, cq, e, limit);
-        win_columns<PixelT, true, TRUSTED>(cs, cq, l, limit);
+        win_columns<PixelT, false, V>(cs, cq, e, limit);
+        win_columns<PixelT, true, V>(cs, cq, l, limit);
 
         // the kx columns on each side from the neighbouring lanes
         uint32_t ls[KX], rs[KX];
@@ -233,7 +232,7 @@ __global__ __launch_bounds__(64) void k_window(const ThresholdArgs a) {
             const bool sig = win_signal<PixelT>(a, m, sx, p[j], ((c.mb >> j) & 1u) && (!TRUSTED || p[j] < limit));
             // (wave-uniform: at most pixel positions no lane of the wave has a candidate, and the rest is skipped)
             if (__ballot(sig) != 0ull) {
-                if (sig && win_rest<PixelT, GAIN>(a, m, sx, sy, p[j])) sb |= 1u << j;
+                if (sig && win_rest<PixelT, V>(a, m, sx, sy, p[j])) sb |= 1u << j;
             }
         }
         if (!own) sb = 0u;   // (bits of x >= W: their mask bits are 0, never strong)
