@@ -309,6 +309,7 @@ static void ctx_destroy_internal(ffs_ctx* c) {
         delete pool;            // joins the helpers
     }
     if (c->d_maskbits) (void)hipFree(c->d_maskbits);
+    if (c->d_gain_map) (void)hipFree(c->d_gain_map);
     if (c->d_ginfo) (void)hipFree(c->d_ginfo);
     if (c->d_mmap) (void)hipFree(c->d_mmap);
     if (c->dense_st) (void)hipStreamDestroy(c->dense_st);
@@ -426,6 +427,11 @@ extern "C" int ffs_ctx_set_params(ffs_ctx* c, const ffs_params* p) {
                  "the reference's device kernels, which that flavour copies, have no gain";
         return FFS_ERR_INVALID;
     }
+    if (p->extended_flavour == 1 && c->has_gain_map) {
+        c->err = "ffs_ctx_set_params: extended_flavour 1 cannot be combined with a gain map (ffs_ctx_set_gain_map): "
+                 "the reference's device kernels, which that flavour copies, have no gain";
+        return FFS_ERR_INVALID;
+    }
     c->params = *p;
     return FFS_OK;
 }
@@ -441,8 +447,69 @@ extern "C" int ffs_ctx_set_gain(ffs_ctx* c, double gain) {
                  "which that flavour copies, have no gain";
         return FFS_ERR_INVALID;
     }
+    if (gain > 0.0 && c->has_gain_map) {
+        c->err = "ffs_ctx_set_gain: a gain map is set (ffs_ctx_set_gain_map): drop it with ffs_ctx_set_gain_map(ctx, NULL) first";
+        return FFS_ERR_INVALID;
+    }
     c->gain = gain;
     return FFS_OK;
+}
+
+// The per-pixel gain map.  Everything is checked before anything changes; the device copy is written only while no
+// batch of the context is in flight, so a batch and its re-runs inside ffs_wait read the map they were submitted with.
+static int ffs_ctx_set_gain_map_impl(ffs_ctx* c, const float* host_gain) {
+    if (!host_gain) {   // (the device buffer stays: a batch in flight was routed at submit and goes on reading the map it was submitted with)
+        c->has_gain_map = false;
+        return FFS_OK;
+    }
+    if (c->inflight.load() > 0) {
+        c->err = "ffs_ctx_set_gain_map: a batch of this context is in flight (ffs_wait for it first): a batch keeps the map it was submitted with";
+        return FFS_ERR_INVALID;
+    }
+    if (c->gain > 0.0) {
+        c->err = "ffs_ctx_set_gain_map: a scalar gain is set (ffs_ctx_set_gain): switch it off with ffs_ctx_set_gain(ctx, 0) first";
+        return FFS_ERR_INVALID;
+    }
+    if (c->params.extended_flavour == 1) {
+        c->err = "ffs_ctx_set_gain_map: a gain map cannot be combined with extended_flavour 1: the reference's device kernels, "
+                 "which that flavour copies, have no gain";
+        return FFS_ERR_INVALID;
+    }
+    const Layout& L = c->L;
+    const size_t n = (size_t)L.W * L.H;
+    float lo = host_gain[0], hi = host_gain[0];
+    for (size_t i = 0; i < n; ++i) {
+        const float g = host_gain[i];
+        if (!(g >= 0x1p-60f && g <= 0x1p60f)) {   // (false for a NaN)
+            c->err = "ffs_ctx_set_gain_map: entry " + std::to_string(i) + " (x = " + std::to_string(i % (size_t)L.W) + ", y = " + std::to_string(i / (size_t)L.W)
+                     + ") is " + std::to_string(g) + ": every entry must be finite and in [2^-60, 2^60], under masked pixels too";
+            return FFS_ERR_INVALID;
+        }
+        lo = std::min(lo, g);
+        hi = std::max(hi, g);
+    }
+    // rows of pitch_px entries, addressed like the pixel rows; the entries beyond W (whose pixels no mask bit covers) are 1
+    std::vector<float> rows((size_t)L.pitch_px * L.H, 1.0f);
+    for (int y = 0; y < L.H; ++y) std::memcpy(rows.data() + (size_t)y * L.pitch_px, host_gain + (size_t)y * L.W, (size_t)L.W * sizeof(float));
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (!c->d_gain_map) {
+        float* d = nullptr;
+        if (hipMalloc(&d, rows.size() * sizeof(float)) != hipSuccess) {
+            (void)hipGetLastError();
+            c->err = "ffs_ctx_set_gain_map: hipMalloc(gain map) failed";
+            return FFS_ERR_NOMEM;
+        }
+        c->d_gain_map = d;
+    }
+    HIP_TRY(c, hipMemcpy(c->d_gain_map, rows.data(), rows.size() * sizeof(float), hipMemcpyHostToDevice));
+    c->gain_map_min = lo;
+    c->gain_map_max = hi;
+    c->has_gain_map = true;
+    return FFS_OK;
+}
+extern "C" int ffs_ctx_set_gain_map(ffs_ctx* c, const float* host_gain) {
+    if (!c) return FFS_ERR_INVALID;
+    return guarded(c, [&] { return ffs_ctx_set_gain_map_impl(c, host_gain); });
 }
 
 extern "C" int ffs_ctx_set_max_valid_scope(ffs_ctx* c, int scope) {

@@ -114,7 +114,16 @@ struct ThresholdArgs {
     // gain * mean (baseline.cpp:241-247, :539-543, :709-715).  No other kernel reads these.
     double gain;
     float g_gain, g_nb;        // float32 screen of a > c under gain: (float)gain and (float)nsig_b; g_gain = 0 = screen off
+    // the per-pixel gain map (ffs_ctx_set_gain_map): float32 rows of pitch_px entries, gm_pitch bytes apart; only the
+    // kGainMap instantiations read it, each pixel's decision with the entry of its CENTRE (baseline.cpp:244-245, :541, :714).  Such a batch
+    // has gain = 0, w_kS without a gain inside (the kernel multiplies by the pixel's) and g_gain unused; g_nb = 0 = nsig_b outside the screen's range.
+    const float* gain_map;
+    uint32_t gm_pitch;
 };
+// the gain-map entry of pixel (x, y), 0 <= x < pitch_px
+__device__ __forceinline__ float gain_at(const ThresholdArgs& a, int x, int y) {
+    return *reinterpret_cast<const float*>(reinterpret_cast<const uint8_t*>(a.gain_map) + (uint64_t)y * a.gm_pitch + (uint64_t)x * 4u);
+}
 
 // The streaming launch's units (launch_geometry.hpp has the map: stream_unit_of, log_slot_of), for the arguments of a launch
 __host__ __device__ inline uint32_t stream_units(const ThresholdArgs& a) { return stream_units_of(a.n_bands, a.n_strips); }

@@ -67,11 +67,13 @@ struct ThreadError {
 struct ffs_stack3d;
 
 // What a batch is computed with: the context's parameters, its scope of max_valid and its detector gain as they were at submit (re-runs
-// inside ffs_wait keep them).  A new per-batch setting is a new field here.
+// inside ffs_wait keep them).  A new per-batch setting is a new field here.  gain_map: the context had a gain map at submit -- the route's
+// input; the map itself is a property of the context like the mask, and cannot change while a batch is in flight (ffs_ctx_set_gain_map).
 struct ParamSnapshot {
     ffs_params params{};
     int max_valid_scope = FFS_MAX_VALID_CENTRE;
     double gain = 0.0;
+    bool gain_map = false;
 };
 
 // A few helper threads per context for ffs_wait's result assembly (wire records -> boxes, reflections, centre rows): one thread
@@ -132,6 +134,11 @@ struct ffs_ctx {
     ffs_params params{};
     int max_valid_scope = FFS_MAX_VALID_CENTRE;   // ffs_ctx_set_max_valid_scope: kept across ffs_ctx_set_params, snapshot per batch with the parameters
     double gain = 0.0;                            // ffs_ctx_set_gain (0 = off): kept and snapshot the same way
+    // ffs_ctx_set_gain_map: [H][pitch_px] float32, allocated at the first set and kept (entries beyond W are 1); has_gain_map says whether it
+    // is in force, gain_map_min / _max are the extremes of its W * H entries (what the screens' per-batch switches are decided from)
+    float* d_gain_map = nullptr;
+    bool has_gain_map = false;
+    float gain_map_min = 0.0f, gain_map_max = 0.0f;
     uint8_t* d_maskbits = nullptr;
     uint8_t* d_ginfo = nullptr;  // per-group mask bits + window-count bounds (kernels_stream.hpp)
     uint8_t* d_mmap = nullptr;   // per-pixel window counts
@@ -346,7 +353,7 @@ static int guarded(ffs_ctx* c, F&& body) {
     } while (0)
 
 // ---- small helpers ------------------------------------------------------------------------------------------
-static inline ParamSnapshot snapshot_of(const ffs_ctx* c) { return ParamSnapshot{c->params, c->max_valid_scope, c->gain}; }
+static inline ParamSnapshot snapshot_of(const ffs_ctx* c) { return ParamSnapshot{c->params, c->max_valid_scope, c->gain, c->has_gain_map}; }
 // What ffs_wait asks of the enqueue that runs a batch AGAIN because a plan did not hold it (ffs_wait.hip, rerun_batch); the default
 // is a normal batch.  An argument of that one call: what a stream remembers beyond it (log_off, runs_overflowed, band_backoff) is
 // in ffs_stream.

@@ -29,7 +29,7 @@ bool chain_prepare_device() {   // more than 64 KB of dynamic LDS has to be aske
 ThresholdRoute batch_route(const ffs_stream* s, const Rerun& how) {
     const ParamSnapshot& b = s->batch;
     return threshold_route(b.params.algorithm, s->ctx->pixel_bytes, win_default(b.params), b.max_valid_scope, b.params.max_valid, b.gain, how.threshold_path,
-                           s->ctx->tune);
+                           s->ctx->tune, b.gain_map);
 }
 static void set_buffers(ThresholdArgs& a, const ffs_stream* s, const void* img, size_t pitch, size_t fstride, const ThresholdRoute& route) {
     const ffs_ctx* c = s->ctx;
@@ -78,7 +78,7 @@ static void set_buffers(ThresholdArgs& a, const ffs_stream* s, const void* img, 
     a.eplane_clean = s->ext_e_clean ? 1 : 0;
     a.ext_variant = route.ext_variant;
 }
-static void set_predicate(ThresholdArgs& a, const ffs_params& p, bool trusted, double gain) {
+static void set_predicate(ThresholdArgs& a, const ffs_params& p, bool trusted, double gain, const ffs_ctx* map_of) {
     // (exclusive; the oracle's < 2^24 rule for 32-bit pixels holds on top of max_valid, and 16-bit pixels never reach it)
     a.nb_limit = trusted ? (uint32_t)std::min<long long>(p.max_valid, (1ll << 24) - 1) + 1u : 1u << 24;
     a.kS = (float)(p.nsig_s * p.nsig_s * (1.0 - 1.0 / 65536.0));
@@ -122,6 +122,18 @@ static void set_predicate(ThresholdArgs& a, const ffs_params& p, bool trusted, d
             a.g_nb = (float)p.nsig_b;
         }
     }
+    // The gain map: the kernels multiply w_kS -- still nsig_s^2 (1 - 2^-16) here, nsig_s <= 1024 or 0 -- by the
+    // pixel's own gain, so the smallest product any pixel forms, with the map's minimum, must be a normal float32 with its 24 bits (the
+    // largest is below 2^80); and the dispersion screen takes the pixel's gain, always in range, so only nsig_b can switch its
+    // square-root term off (g_nb = 0: cf = g x (m - 1), never above c).
+    a.gain_map = nullptr;
+    a.gm_pitch = 0;
+    if (map_of) {
+        a.gain_map = map_of->d_gain_map;
+        a.gm_pitch = (uint32_t)map_of->L.pitch_px * 4u;
+        if (map_of->gain_map_min * a.w_kS < 0x1p-100f) a.w_kS = 0.0f;
+        if (std::isfinite(p.nsig_b) && p.nsig_b <= 1024.0 && p.nsig_b >= 0x1p-60) a.g_nb = (float)p.nsig_b;
+    }
 }
 // (launch_geometry.hpp computes them; the super rows of the streaming launch, g.n_groups, are its grid's y and no argument)
 static void set_geometry(ThresholdArgs& a, uint32_t n_frames, const StreamGeometry& g, const WindowGeometry& w, const ExtGeometry& e) {
@@ -146,7 +158,7 @@ ThresholdArgs make_threshold_args(ffs_stream* s, const void* img, size_t pitch, 
                                   const ThresholdRoute& route) {
     ThresholdArgs a{};
     set_buffers(a, s, img, pitch, fstride, route);
-    set_predicate(a, s->batch.params, route.window_scope, s->batch.gain);
+    set_predicate(a, s->batch.params, route.window_scope, s->batch.gain, s->batch.gain_map ? s->ctx : nullptr);
     set_geometry(a, n_frames, g, window_geometry(s->ctx->L, n_frames, a.ky), ext_geometry(s->ctx->L, n_frames));
     return a;
 }
@@ -186,7 +198,8 @@ static void with_pixel_tag(int pixel_bytes, Launch& launch) {
 }
 template <typename Launch>
 static void with_kernel_tag(int pixel_bytes, Predicate v, Launch&& launch) {
-    if (v == Predicate::kGain) with_pixel_tag<Predicate::kGain>(pixel_bytes, launch);
+    if (v == Predicate::kGainMap) with_pixel_tag<Predicate::kGainMap>(pixel_bytes, launch);
+    else if (v == Predicate::kGain) with_pixel_tag<Predicate::kGain>(pixel_bytes, launch);
     else if (v == Predicate::kWindowScope) with_pixel_tag<Predicate::kWindowScope>(pixel_bytes, launch);
     else with_pixel_tag<Predicate::kPhotonCount>(pixel_bytes, launch);
 }

@@ -101,11 +101,15 @@ __global__ __launch_bounds__(64) void k_ext_first(const ThresholdArgs a) {
                 if constexpr (GAIN) {
                     // exact integers: a = m y - x^2 (m y < 49 * 49 * 2^48 and x^2 < (49 * 2^24)^2: int64 holds them)
                     const long long ai = (long long)((unsigned long long)m * wy) - (long long)((unsigned long long)wx * wx);
-                    if (!gain_disp_rejects(a, ai, wx, (uint32_t)m)) {
+                    // (map variant: the lane's own centre pixel (x, yin - 3), a valid pixel of the frame here -- four bytes a lane, coalesced along x)
+                    float g_f = a.g_gain;
+                    if constexpr (gain_from_map(V)) g_f = gain_at(a, x, yin - 3);
+                    if (!gain_disp_rejects(a, g_f, ai, wx, (uint32_t)m)) {
                         // :540-542, each operation rounded separately (contraction is off)
                         const double md = (double)m, xd = (double)wx, yd = (double)wy;
                         const double av = md * yd - xd * xd;
-                        const double cv = (a.gain * xd) * ((md - 1.0) + a.nsig_b * __builtin_sqrt(2.0 * (md - 1.0)));
+                        const double gd = gain_from_map(V) ? (double)g_f : a.gain;
+                        const double cv = (gd * xd) * ((md - 1.0) + a.nsig_b * __builtin_sqrt(2.0 * (md - 1.0)));
                         d_bit = av > cv;
                     }
                 } else {
@@ -342,7 +346,10 @@ __device__ __forceinline__ bool ext_final_strong(const ThresholdArgs& a, const u
     const double mean = m2 >= 2 ? (double)x2 / (double)m2 : 0.0;        // :640
     const bool global_mask = src > a.threshold;
     bool local_mask;
-    if constexpr (GAIN) local_mask = src >= (mean + a.nsig_s * __builtin_sqrt(a.gain * mean));   // :713-714
+    if constexpr (gain_from_map(V)) {   // (the centre's entry, :714, read only where the float64 test is reached)
+        if (!global_mask) return false;
+        local_mask = src >= (mean + a.nsig_s * __builtin_sqrt((double)gain_at(a, x, y) * mean));
+    } else if constexpr (GAIN) local_mask = src >= (mean + a.nsig_s * __builtin_sqrt(a.gain * mean));   // :713-714
     else local_mask = src >= (mean + a.nsig_s * __builtin_sqrt(mean));
     return global_mask && local_mask;
 }
@@ -428,7 +435,10 @@ __device__ __forceinline__ bool ext_final_strong4(const ThresholdArgs& a, const 
     if (a.max_valid >= 0 && (long long)pc > a.max_valid) return false;  // thresholding.cu:440-441
     const double src = (double)pc;
     const double mean = m >= 2 ? (double)x2 / (double)m : 0.0;          // :640
-    if constexpr (GAIN) return src > a.threshold && src >= (mean + a.nsig_s * __builtin_sqrt(a.gain * mean));   // :713-714
+    if constexpr (gain_from_map(V)) {   // (pixel x0 + sub < pitch_px of row y: its own entry, read only where the float64 test is reached)
+        if (!(src > a.threshold)) return false;
+        return src >= (mean + a.nsig_s * __builtin_sqrt((double)gain_at(a, x0 + sub, y) * mean));
+    } else if constexpr (GAIN) return src > a.threshold && src >= (mean + a.nsig_s * __builtin_sqrt(a.gain * mean));   // :713-714
     else return src > a.threshold && src >= (mean + a.nsig_s * __builtin_sqrt(mean));
 }
 

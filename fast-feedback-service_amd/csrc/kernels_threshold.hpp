@@ -42,8 +42,10 @@ constexpr int kQCap = 64;        // lane-group queue entries per wave of the str
 // The oracle's predicate on a window's exact sums (standalone.cc:165-170), shared by the gathered forms below.
 // V: the predicate's variant (threshold_route.hpp); its gain form is baseline.cpp:241-247 with a scalar gain, every
 // operation rounded separately, in the order of the C++ text (the extended first pass, :539-543, has its own kernel and no gathered form).
+// g_centre: the map variant's gain (the centre pixel's map entry, widened to float64 exactly: gain[k] of :244-245); no other variant reads it.
 template <bool DISP_ONLY, Predicate V = Predicate::kPhotonCount>
-__device__ __forceinline__ bool exact_decide(const ThresholdArgs& a, uint32_t m, unsigned long long sx, unsigned long long sy, uint32_t pc, bool centre_valid) {
+__device__ __forceinline__ bool exact_decide(const ThresholdArgs& a, uint32_t m, unsigned long long sx, unsigned long long sy, uint32_t pc, bool centre_valid,
+                                             double g_centre = 0.0) {
     // :165  mask[k] && m >= min_count && x >= 0 && src[k] > threshold
     const double src = (double)pc;
     if (!(centre_valid && (int)m >= a.min_count && (DISP_ONLY || src > a.threshold))) return false;
@@ -51,7 +53,9 @@ __device__ __forceinline__ bool exact_decide(const ThresholdArgs& a, uint32_t m,
     const double md = (double)m, xd = (double)sx, yd = (double)sy;
     if constexpr (gain_form(V)) {
         static_assert(!DISP_ONLY, "no gain batch gathers the extended first pass (k_bright_fix<., true> follows the streaming kernel only)");
-        const double gx = a.gain * xd;
+        double gx;
+        if constexpr (gain_from_map(V)) gx = g_centre * xd;
+        else gx = a.gain * xd;
         const double av = md * yd - xd * xd;                                                         // :242
         const double cv = gx * ((md - 1.0) + a.nsig_b * __builtin_sqrt(2.0 * (md - 1.0)));           // :244
         const double bv = md * src - xd;                                                             // :243
@@ -76,11 +80,21 @@ __device__ __forceinline__ bool exact_decide(const ThresholdArgs& a, uint32_t m,
 // and a sum), each at most 2^-23 relative, stay below 2^-20 together, and the float64 c is within 2^-50 of the real one -- a margin
 // of 2^-18 holds both.  g_gain = 0 (the gain outside [2^-60, 2^60], or nsig_b outside [0, 1024]: ffs_submit.hip) makes cf = 0 and the
 // screen passes everything with A > 0 on to float64.
-__device__ __forceinline__ bool gain_disp_rejects(const ThresholdArgs& a, long long A, uint32_t sx, uint32_t m) {
+// g_f: a.g_gain, or the map variant's centre entry -- itself a float32, so no rounding, and always inside [2^-60, 2^60]; there nsig_b outside
+// its range makes g_nb = 0, which leaves cf = g x (m - 1) <= c (section 3.3f).
+__device__ __forceinline__ bool gain_disp_rejects(const ThresholdArgs& a, float g_f, long long A, uint32_t sx, uint32_t m) {
     if (A <= 0) return true;
     const float fm1 = (float)(m - 1u);
-    const float cf = (a.g_gain * (float)sx) * (fm1 + a.g_nb * __builtin_sqrtf(2.0f * fm1));
+    const float cf = (g_f * (float)sx) * (fm1 + a.g_nb * __builtin_sqrtf(2.0f * fm1));
     return !((float)A >= cf * (1.0f - 3.8146973e-06f));
+}
+
+// The map variant's gain for the gathered predicates, loaded only where the float64 test will read it (`reaches`: exact_decide's first two
+// conditions; (x, y) is then a valid pixel of the frame).  Every other variant: nothing is loaded.
+template <Predicate V>
+__device__ __forceinline__ double centre_gain(const ThresholdArgs& a, int x, int y, bool reaches) {
+    if constexpr (gain_from_map(V)) return reaches ? (double)gain_at(a, x, y) : 1.0;
+    else return 0.0;
 }
 
 // Exact integer window sums + the oracle predicate, standalone.cc:113-174 operation for operation.
@@ -150,7 +164,7 @@ __device__ bool exact_strong(const ThresholdArgs& a, const uint8_t* img, int x, 
         }
     }
 
-    return exact_decide<DISP_ONLY, V>(a, m, sx, sy, pc, centre_valid);
+    return exact_decide<DISP_ONLY, V>(a, m, sx, sy, pc, centre_valid, centre_gain<V>(a, x, y, centre_valid && (int)m >= a.min_count));
 }
 
 // exact_strong at the runtime window (2 a.kx + 1) x (2 a.ky + 1), kx, ky in 1..7: what k_exact<., true> gathers on the cross-check
@@ -202,7 +216,7 @@ __device__ bool exact_strong_w(const ThresholdArgs& a, const uint8_t* img, int x
             sy += (unsigned long long)pv * pv;
         }
     }
-    return exact_decide<false, V>(a, m, sx, sy, pc, centre_valid);
+    return exact_decide<false, V>(a, m, sx, sy, pc, centre_valid, centre_gain<V>(a, x, y, centre_valid && (int)m >= a.min_count));
 }
 
 // The same decision from the same sums with HALF the registers: the window's rows come in two batches (four, then three) -- two

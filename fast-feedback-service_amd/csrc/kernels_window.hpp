@@ -17,7 +17,8 @@
 // centre scope, min(max_valid, 2^24 - 1) + 1 under the window scope), the same compare.  16-bit pixels: which instantiations carry the
 // compare is threshold_route.hpp's rule.  The sums are over a subset of the window, so every bound above holds.
 // The gain variant's screens: win_signal is the same code with the gain inside w_kS; win_rest takes the gain form's a = m*y - x^2 and c
-// (gain_disp_rejects).
+// (gain_disp_rejects).  The map variant (kGainMap): the same two with the gain of the pixel itself, which the lane
+// loads with its centre row's group (win_gain).
 // Every pixel is then decided by exact_decide -- the oracle's float64 predicate, operation for operation -- behind screens that
 // are proven supersets (win_signal, win_rest).  Output: what the sparse stage reads after k_exact -- the strong bit plane, per-tile counts,
 // the occupancy bitmap when the sparse launch reads it (a.occ != nullptr), the byte mask when somebody asked for it.
@@ -60,6 +61,29 @@ __device__ __forceinline__ void win_unpack(const WinRow<PixelT>& r, uint32_t (&p
     }
 }
 
+// (map variant) the gain-map entries of a lane's group in row y, 0 <= y < H: 32 bytes a lane, the access pattern of a row of 32-bit pixels.
+// A group outside the row gets 1.0 (it owns no output).  Every other variant: nothing is loaded.
+struct WinGain {
+    float4 lo, hi;
+    __device__ __forceinline__ float at(int j) const {
+        return j == 0 ? lo.x : j == 1 ? lo.y : j == 2 ? lo.z : j == 3 ? lo.w : j == 4 ? hi.x : j == 5 ? hi.y : j == 6 ? hi.z : hi.w;
+    }
+};
+template <Predicate V>
+__device__ __forceinline__ WinGain win_gain(const ThresholdArgs& a, int y, int g, bool g_ok) {
+    WinGain r;
+    r.lo = make_float4(1.0f, 1.0f, 1.0f, 1.0f);
+    r.hi = r.lo;
+    if constexpr (gain_from_map(V)) {
+        if (g_ok && y < a.H) {
+            const uint8_t* gp = reinterpret_cast<const uint8_t*>(a.gain_map) + (uint64_t)y * a.gm_pitch + (uint64_t)g * 32u;
+            r.lo = *reinterpret_cast<const float4*>(gp);
+            r.hi = *reinterpret_cast<const float4*>(gp + 16);
+        }
+    }
+    return r;
+}
+
 // column sums += (SUB: -=) one row's contribution
 template <typename PixelT, bool SUB, Predicate V>
 __device__ __forceinline__ void win_columns(uint32_t (&cs)[8], uint64_t (&cq)[8], const WinRow<PixelT>& r, uint32_t limit) {
@@ -91,8 +115,9 @@ __device__ __forceinline__ uint64_t from_right64(uint64_t v) {
 // win_signal, every pixel: the centre's mask bit, m >= min_count, and the signal test.  bv = m*p - x is an exact integer in float64
 // and dv >= 0 (nsig_s >= 0), so bv <= 0 decides "no"; a float32 square test with a 2^-16 margin rejects bv < dv.  For 16-bit pixels
 // m*p and x are below 2^24: B is an int32 and exact as a float.
+// kS: a.w_kS, or the map variant's per-pixel product g_f * a.w_kS.
 template <typename PixelT>
-__device__ __forceinline__ bool win_signal(const ThresholdArgs& a, uint32_t m, uint32_t sx, uint32_t pc, bool centre_valid) {
+__device__ __forceinline__ bool win_signal(const ThresholdArgs& a, float kS, uint32_t m, uint32_t sx, uint32_t pc, bool centre_valid) {
     if (!(centre_valid && (int)m >= a.min_count)) return false;
     float fB;
     if constexpr (sizeof(PixelT) == 2) {
@@ -104,19 +129,20 @@ __device__ __forceinline__ bool win_signal(const ThresholdArgs& a, uint32_t m, u
         if (B <= 0) return false;
         fB = (float)B;
     }
-    return !(fB * fB < (a.w_kS * (float)sx) * (float)m);
+    return !(fB * fB < (kS * (float)sx) * (float)m);
 }
 // win_rest, only where win_signal passed: (16-bit pixels) av = m*y - x^2 - x(m-1) is an exact integer in float64 and cv >= 0, so
 // av <= 0 decides "no", and the float32 square test rejects av < cv; then the oracle's float64 predicate itself.
 // The gain variant: d = nsig_s sqrt((gain x) m), so win_signal's test holds with w_kS = gain nsig_s^2 (1 - 2^-16) (set_predicate); here a
 // and c take their gain forms: gain_disp_rejects.
+// g_f: the map variant's gain of this pixel (kernels_threshold.hpp: gain_disp_rejects, exact_decide); unused otherwise.
 template <typename PixelT, Predicate V>
-__device__ __forceinline__ bool win_rest(const ThresholdArgs& a, uint32_t m, uint32_t sx, uint64_t sy, uint32_t pc) {
+__device__ __forceinline__ bool win_rest(const ThresholdArgs& a, uint32_t m, uint32_t sx, uint64_t sy, uint32_t pc, float g_f) {
     if constexpr (gain_form(V)) {
         if constexpr (sizeof(PixelT) == 2) {   // (m*y < 225 * 225 * 2^32 and x^2 < 2^48: int64 holds them)
-            if (gain_disp_rejects(a, (long long)m * (long long)sy - (long long)sx * (long long)sx, sx, m)) return false;
+            if (gain_disp_rejects(a, gain_from_map(V) ? g_f : a.g_gain, (long long)m * (long long)sy - (long long)sx * (long long)sx, sx, m)) return false;
         }
-        return exact_decide<false, V>(a, m, sx, sy, pc, true);
+        return exact_decide<false, V>(a, m, sx, sy, pc, true, (double)g_f);
     }
     if constexpr (sizeof(PixelT) == 2) {
         const long long A = (long long)m * (long long)sy - (long long)sx * (long long)sx - (long long)sx * (long long)(m - 1u);
@@ -190,9 +216,15 @@ __global__ __launch_bounds__(64) void k_window(const ThresholdArgs a) {
     uint32_t cnt = 0;
     // the entering row comes from memory, loaded one step ahead; leaving and centre rows from the ring
     WinRow<PixelT> e = win_load<PixelT>(a, img, y0 + ky, g, g_ok);
+    // (map variant) the gains of the lane's eight centre pixels, loaded one step ahead as the entering row is; the map is shared by the frames
+    [[maybe_unused]] WinGain gc = win_gain<V>(a, y0, g, g_ok);
     for (int y = y0; y < y1; ++y) {
         WinRow<PixelT> e2 = e;
-        if (y + 1 < y1) e2 = win_load<PixelT>(a, img, y + 1 + ky, g, g_ok);
+        [[maybe_unused]] WinGain gc2 = gc;
+        if (y + 1 < y1) {
+            e2 = win_load<PixelT>(a, img, y + 1 + ky, g, g_ok);
+            gc2 = win_gain<V>(a, y + 1, g, g_ok);
+        }
         const WinRow<PixelT> l = get(y - ky - 1);
         const WinRow<PixelT> c = get(y);
         put(y + ky, e);   // (2ky + 2 slots: neither the leaving nor the centre row shares its slot)
@@ -229,10 +261,12 @@ __global__ __launch_bounds__(64) void k_window(const ThresholdArgs a) {
             if constexpr (sizeof(PixelT) == 2) { m = ws >> 24; sx = ws & 0xFFFFFFu; sy = wq; }
             else { m = (uint32_t)(wq >> 56); sx = ws; sy = wq & ((1ull << 56) - 1ull); }
             // (a centre above max_valid is never strong: exact_decide refuses it; the TRUSTED kernels -- limit = max_valid + 1 -- know it here)
-            const bool sig = win_signal<PixelT>(a, m, sx, p[j], ((c.mb >> j) & 1u) && (!TRUSTED || p[j] < limit));
+            float g_f = 0.0f, kS = a.w_kS;
+            if constexpr (gain_from_map(V)) { g_f = gc.at(j); kS = g_f * a.w_kS; }
+            const bool sig = win_signal<PixelT>(a, kS, m, sx, p[j], ((c.mb >> j) & 1u) && (!TRUSTED || p[j] < limit));
             // (wave-uniform: at most pixel positions no lane of the wave has a candidate, and the rest is skipped)
             if (__ballot(sig) != 0ull) {
-                if (sig && win_rest<PixelT, V>(a, m, sx, sy, p[j])) sb |= 1u << j;
+                if (sig && win_rest<PixelT, V>(a, m, sx, sy, p[j], g_f)) sb |= 1u << j;
             }
         }
         if (!own) sb = 0u;   // (bits of x >= W: their mask bits are 0, never strong)
@@ -259,6 +293,7 @@ __global__ __launch_bounds__(64) void k_window(const ThresholdArgs a) {
             cnt = 0u;
         }
         e = e2;
+        gc = gc2;
     }
 }
 

@@ -15,6 +15,7 @@ enum class Predicate : int {
     kPhotonCount = 0,   // the oracle's predicate: variance = mean; max_valid tests the centre pixel alone
     kWindowScope = 1,   // ... and a pixel p >= ThresholdArgs.nb_limit leaves every window (ffs_ctx_set_max_valid_scope)
     kGain = 2,          // variance = gain * mean (ffs_ctx_set_gain, section 3.3d); carries the neighbour limit too (2^24 under the centre scope)
+    kGainMap = 3,       // kGain with the gain of the CENTRE pixel read from a float32 map (ffs_ctx_set_gain_map, section 3.3f); the limit as kGain
 };
 // The kernels templated on it: k_exact and k_exact_w, k_ext_final, k_ext_erode_final, k_window, k_ext_first
 enum class KernelFamily : int { kExact, kExtFinal, kExtFused, kWindow, kExtFirst };
@@ -31,7 +32,8 @@ constexpr Predicate instantiated_as(KernelFamily f, size_t pixel_bytes, Predicat
 constexpr bool compares_limit(KernelFamily f, size_t pixel_bytes, Predicate v) {
     return v != Predicate::kPhotonCount && !limit_is_argument(f, pixel_bytes);
 }
-constexpr bool gain_form(Predicate v) { return v == Predicate::kGain; }
+constexpr bool gain_form(Predicate v) { return v == Predicate::kGain || v == Predicate::kGainMap; }
+constexpr bool gain_from_map(Predicate v) { return v == Predicate::kGainMap; }   // g is ThresholdArgs.gain_map at the centre, not ThresholdArgs.gain
 
 // ---- a batch's route through the threshold stage -------------------------------------------------------------------
 enum class ThresholdStage : int {
@@ -55,11 +57,12 @@ struct ThresholdRoute {
 };
 
 // rerun_threshold_path: Rerun::threshold_path (< 0: none); the tuning's threshold_path, window_kernel, ext_first_pass and ext_fused are read
+// gain_map: a per-pixel gain map is set (exclusive with gain > 0: ffs_ctx_set_gain_map)
 inline ThresholdRoute threshold_route(int algorithm, int pixel_bytes, bool window_3x3, int scope, long long max_valid, double gain,
-                                      int rerun_threshold_path, const Tuning& t) {
+                                      int rerun_threshold_path, const Tuning& t, bool gain_map = false) {
     ThresholdRoute r;
     r.window_scope = scope == FFS_MAX_VALID_WINDOW && max_valid >= 0;   // (without a max_valid the scope changes nothing)
-    r.variant = gain > 0.0 ? Predicate::kGain : r.window_scope ? Predicate::kWindowScope : Predicate::kPhotonCount;
+    r.variant = gain_map ? Predicate::kGainMap : gain > 0.0 ? Predicate::kGain : r.window_scope ? Predicate::kWindowScope : Predicate::kPhotonCount;
     r.window_3x3 = window_3x3;
     const bool photon = r.variant == Predicate::kPhotonCount;
     // bright windows: onto the list, or -- tuning "threshold_path" = 1, and whenever that list overflowed -- into the plane as candidates
@@ -69,7 +72,7 @@ inline ThresholdRoute threshold_route(int algorithm, int pixel_bytes, bool windo
     r.ext_variant = (pixel_bytes == 2 && rerun_threshold_path < 0 && photon) ? t.ext_first_pass : 0;
     if (algorithm == FFS_ALGO_DISPERSION_EXTENDED) {
         r.stage = ThresholdStage::kExtended;
-        r.ext_fused = pixel_bytes == 2 && t.ext_fused != 0 && r.variant != Predicate::kGain;   // (a gain batch has no fused kernel)
+        r.ext_fused = pixel_bytes == 2 && t.ext_fused != 0 && !gain_form(r.variant);   // (a gain batch has no fused kernel)
     } else if (r.bright_to_plane == 2) {
         r.stage = ThresholdStage::kCrossCheck;
     } else if (!window_3x3 || t.window_kernel == 1 || !photon) {

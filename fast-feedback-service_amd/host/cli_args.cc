@@ -22,7 +22,7 @@ void usage() {
       "                  [-t S] [-fd FD] [-a ALGO] [--dmin MIN D] [--dmax MAX D] [-w \xce\xbb] [--detector JSON]\n"
       "                  [-h5] [--output-for-index] [--batch N] [--cpu-decode] [--strict-dtype]\n"
       "                  [--max-valid trusted|none|N] [--max-valid-scope centre|window] [--min-count N] [--kernel-size N | NX,NY]\n"
-      "                  [--gain G]\n"
+      "                  [--gain G] [--gain-map FILE]\n"
       "                  [--devices D0,D1,... | --gpus N] [--no-numa-pinning] [--single-buffer] [--all-threads] [--read-only] [--clean-exit]\n"
       "--max-valid: a centre pixel above this value is never strong (the reference's kernels test it against the\n"
       "              data set's trusted maximum).  trusted (default) = the frame source's trusted-range maximum when it is\n"
@@ -37,6 +37,10 @@ void usage() {
       "--gain:      the detector gain G > 0 of the dispersion tests, for frames in ADU or keV whose background variance is G x mean,\n"
       "              not mean (DIALS spotfinder.threshold.dispersion.gain; default: none, pixel values are photon counts).  The\n"
       "              general-window kernel at every --kernel-size; also with -a dispersion_extended\n"
+      "--gain-map:  the detector gain per pixel, for detectors whose modules or gain stages do not share one gain (DIALS\n"
+      "              spotfinder.lookup.gain_map): FILE holds exactly width x height float32 values, little-endian, row-major, nothing\n"
+      "              else; every value finite and in [2^-60, 2^60], under masked pixels too.  Each pixel is decided with the --gain\n"
+      "              arithmetic and its own value.  Not together with --gain\n"
       "--validate:  every image is also decided by an independent path (every valid pixel's window gathered from memory,\n"
       "              no streaming kernel) and the two strong-pixel masks are compared: Match / Mismatch per image\n"
       "--devices / --gpus: one context and worker pool per GPU, all pulling frames from the one queue\n"
@@ -167,6 +171,10 @@ Args parse_args(int argc, char** argv) {
             catch (...) { arg_error("pattern not found for '" + s + "': " + v); }
             if (!(r.gain > 0.0) || r.gain > 1.7976931348623157e308) arg_error("--gain takes a finite number above 0: " + v);
         }
+        else if (s == "--gain-map") {
+            r.gain_map = need(i, s);
+            if (r.gain_map.empty() || !fs::is_regular_file(r.gain_map)) arg_error("--gain-map: no such file: " + r.gain_map);
+        }
         else if (s == "--min-count") { r.min_count = u32(need(i, s), s); if (r.min_count < 2) arg_error("--min-count must be at least 2"); }
         else if (s == "--no-numa-pinning") r.no_numa_pinning = true;
         else if (s == "--single-buffer") r.single_buffer = true;
@@ -181,6 +189,7 @@ Args parse_args(int argc, char** argv) {
     if (r.sample && !r.file.empty()) arg_error("Argument 'FILE.nxs' not allowed with '--sample'");
     if (!r.sample && r.file.empty() && !implicit_sample) arg_error("One of the arguments '--sample' or 'FILE.nxs' is required");
     if (r.file.empty()) r.sample = true;
+    if (r.gain > 0.0 && !r.gain_map.empty()) arg_error("--gain and --gain-map exclude each other: a constant map is the scalar gain");
     std::string lower = r.algorithm;   // DispersionAlgorithm, spotfinder.cc:180-203
     std::transform(lower.begin(), lower.end(), lower.begin(), [](unsigned char ch) { return (char)std::tolower(ch); });
     if (lower == "dispersion") r.algo = FFS_ALGO_DISPERSION;

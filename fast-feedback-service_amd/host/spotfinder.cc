@@ -182,13 +182,43 @@ static int open_reader(const Args& args, const std::atomic<bool>& give_up, std::
 // The frame source is opened (header, the 72 MB pixel mask of an Eiger-16M stream directory: 35 ms) on a helper thread WHILE this
 // one initialises the HIP runtime (70-160 ms): nothing in it needs the GPU, and a request's latency is the wall time of the process
 // (DESIGN.md section 5b).  It prints only when it has to wait for its files or fails.  -> 0, or the process's exit code
-static int open_source_beside_runtime(const Args& args, Stamps& stamp, std::unique_ptr<Reader>& reader) {
+// --gain-map FILE: exactly width x height float32 values, little-endian (the byte order of every host this driver is built for), row-major;
+// every value inside what ffs_ctx_set_gain_map accepts.  Anything else is a usage error.  Empty: no map was asked for.
+static std::vector<float> read_gain_map(const Args& args, uint32_t width, uint32_t height) {
+    std::vector<float> map;
+    if (args.gain_map.empty()) return map;
+    const size_t n = (size_t)width * height;
+    std::ifstream f(args.gain_map, std::ios::binary | std::ios::ate);
+    if (!f) arg_error("--gain-map: cannot open " + args.gain_map);
+    const std::streamoff bytes = f.tellg();
+    if (bytes < 0 || (uint64_t)bytes != (uint64_t)n * sizeof(float))
+        arg_error("--gain-map: " + args.gain_map + " holds " + std::to_string((long long)bytes) + " bytes, the " + std::to_string(width) + " x "
+                  + std::to_string(height) + " float32 values of this detector are " + std::to_string(n * sizeof(float)));
+    map.resize(n);
+    f.seekg(0);
+    if (!f.read(reinterpret_cast<char*>(map.data()), bytes)) arg_error("--gain-map: cannot read " + args.gain_map);
+    for (size_t i = 0; i < n; ++i)
+        if (!(map[i] >= 0x1p-60f && map[i] <= 0x1p60f))   // (false for a NaN)
+            arg_error("--gain-map: value " + std::to_string(i) + " of " + args.gain_map + " is " + std::to_string(map[i])
+                      + ": every value must be finite and in [2^-60, 2^60]");
+    return map;
+}
+
+// (--gain-map: the file is held against the frame source's shape as soon as the source is open, ahead of the verdict on the devices -- a
+// usage error is reported as one wherever the driver runs)
+static int open_source_beside_runtime(const Args& args, Stamps& stamp, std::unique_ptr<Reader>& reader, std::vector<float>& gain_map) {
     int reader_rc = 0;
     std::atomic<bool> give_up{false};
     JoinedThread reader_holder;
     reader_holder.th = std::thread([&args, &give_up, &reader, &reader_rc] { reader_rc = open_reader(args, give_up, reader); });
     stamp("arguments parsed");
-    if (ffs_device_count() < 1) {  // cuda_arg_parser.cc:56-61
+    const int n_devices = ffs_device_count();
+    if (!args.gain_map.empty()) {
+        reader_holder.th.join();
+        if (reader_rc != 0) return reader_rc;
+        gain_map = read_gain_map(args, (uint32_t)reader->image_shape()[1], (uint32_t)reader->image_shape()[0]);
+    }
+    if (n_devices < 1) {  // cuda_arg_parser.cc:56-61
         give_up.store(true);
         std::printf("\033[1;31mError: Could not select GPU device\033[0m\n");
         return 1;
@@ -201,7 +231,7 @@ static int open_source_beside_runtime(const Args& args, Stamps& stamp, std::uniq
         return 1;
     }
     std::printf("Using %s\n", name);
-    reader_holder.th.join();
+    if (reader_holder.th.joinable()) reader_holder.th.join();
     if (reader_rc != 0) return reader_rc;
     stamp("frame source opened (beside the runtime's initialisation)");
     return 0;
@@ -367,7 +397,8 @@ static ffs_params make_params(const Args& args, bool rotation, int64_t max_valid
 // pixel is gathered from memory (tuning "threshold_path" = 2; the extended algorithm: its plain one-pixel-per-lane first
 // pass and the grid-wide sparse kernels) -- and the two strong-pixel masks are compared image by image.
 static bool create_validation_contexts(const std::vector<int>& devices, const std::vector<ffs_ctx*>& ctxs, const FrameShape& shape, uint32_t batch,
-                                       const ffs_params& prm, int max_valid_scope, double gain, std::vector<ffs_ctx*>& vctxs) {
+                                       const ffs_params& prm, int max_valid_scope, double gain, const std::vector<float>& gain_map,
+                                       std::vector<ffs_ctx*>& vctxs) {
     for (size_t di = 0; di < devices.size(); ++di) {
         if (!create_context(devices[di], shape, batch, &vctxs[di])) return false;
         ffs_ctx* v = vctxs[di];
@@ -381,6 +412,7 @@ static bool create_validation_contexts(const std::vector<int>& devices, const st
         FFS_CHECK(v, ffs_ctx_set_params(v, &prm));
         FFS_CHECK(v, ffs_ctx_set_max_valid_scope(v, max_valid_scope));
         FFS_CHECK(v, ffs_ctx_set_gain(v, gain));
+        if (!gain_map.empty()) FFS_CHECK(v, ffs_ctx_set_gain_map(v, gain_map.data()));
     }
     std::printf("Validation: every image is also decided by the gather path (every valid pixel's window summed from memory)\n");
     return true;
@@ -740,7 +772,8 @@ int main(int argc, char** argv) {
         return 1;
     }
     std::unique_ptr<Reader> reader_ptr;
-    if (const int rc = open_source_beside_runtime(args, stamp, reader_ptr)) return rc;
+    std::vector<float> gain_map;   // --gain-map: width x height values, checked; empty: none
+    if (const int rc = open_source_beside_runtime(args, stamp, reader_ptr, gain_map)) return rc;
     Reader& reader = *reader_ptr;
 
     FrameShape shape;
@@ -804,12 +837,16 @@ int main(int argc, char** argv) {
         FFS_CHECK(cx, ffs_ctx_set_params(cx, &prm));
         FFS_CHECK(cx, ffs_ctx_set_max_valid_scope(cx, args.max_valid_scope));
         FFS_CHECK(cx, ffs_ctx_set_gain(cx, args.gain));
+        if (!gain_map.empty()) FFS_CHECK(cx, ffs_ctx_set_gain_map(cx, gain_map.data()));
     }
     if (max_valid >= 0 && args.max_valid_scope == FFS_MAX_VALID_WINDOW)
         std::printf("Trusted range: pixels above %lld are masked for their frame (window scope: out of every window's sums, and not spots)\n", (long long)max_valid);
     else if (max_valid >= 0) std::printf("Trusted range: centre pixels above %lld are not spots\n", (long long)max_valid);
     if (args.gain > 0.0) std::printf("Detector gain: %g (a background window's variance is taken as gain x mean)\n", args.gain);
-    if (args.validate && !create_validation_contexts(devices, ctxs, shape, batch, prm, args.max_valid_scope, args.gain, vctxs)) return 1;
+    if (!gain_map.empty())
+        std::printf("Detector gain map: %s (%g .. %g)\n", args.gain_map.c_str(), (double)*std::min_element(gain_map.begin(), gain_map.end()),
+                    (double)*std::max_element(gain_map.begin(), gain_map.end()));
+    if (args.validate && !create_validation_contexts(devices, ctxs, shape, batch, prm, args.max_valid_scope, args.gain, gain_map, vctxs)) return 1;
     if (args.save_h5 && !h5_supported()) {
         std::printf("Error: --save-h5 needs an HDF5-enabled build\n");
         return 1;

@@ -89,7 +89,7 @@ EXPORTS = [
     "ffs_submit_compressed", "ffs_decode_only", "ffs_submit_encoded", "ffs_decode_only_encoded", "ffs_stream_spot_centres", "ffs_bench_threshold", "ffs_bench_hbm", "ffs_stream_debug_planes", "ffs_stream_debug_bitplane", "ffs_selftest_sqrt", "ffs_stack3d_create",
     "ffs_stack3d_destroy", "ffs_stack3d_add_batch", "ffs_stack3d_add_slice", "ffs_stack3d_finish", "ffs_stack3d_signals", "ffs_stack3d_last_finish_ms", "ffs_multi_init", "ffs_multi_transport",
     "ffs_ctx_set_tuning", "ffs_bench_pipeline", "ffs_device_numa_node", "ffs_stream_reserve_host", "ffs_stream_last_path", "ffs_multi_gather_rows",
-    "ffs_ctx_set_max_valid_scope", "ffs_ctx_set_gain",
+    "ffs_ctx_set_max_valid_scope", "ffs_ctx_set_gain", "ffs_ctx_set_gain_map",
 ]
 
 _lib = None
@@ -115,6 +115,7 @@ def load_library():
         L.ffs_ctx_set_tuning.argtypes = [C.c_void_p, C.c_char_p, C.c_longlong]
         L.ffs_ctx_set_max_valid_scope.argtypes = [C.c_void_p, C.c_int]
         L.ffs_ctx_set_gain.argtypes = [C.c_void_p, C.c_double]
+        L.ffs_ctx_set_gain_map.argtypes = [C.c_void_p, C.c_void_p]
         L.ffs_bench_pipeline.argtypes = [C.POINTER(C.c_void_p), C.c_uint32, C.c_void_p, C.c_size_t, C.c_size_t, C.c_uint32,
                                          C.c_uint32, C.c_int64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
         L.ffs_device_numa_node.argtypes = [C.c_int]
@@ -269,6 +270,20 @@ class Context:
         baseline.cpp (the general-window kernel at every window).  Kept across set_params; a batch takes it as it is at submit.
         Refused (FfsError, state unchanged): negative, NaN, infinite; g > 0 with extended_flavour 1."""
         self._check(self._lib.ffs_ctx_set_gain(self._h, float(gain)))
+
+    def set_gain_map(self, gain_map: np.ndarray | None):
+        """ffs_ctx_set_gain_map: the detector gain per pixel (DIALS spotfinder.lookup.gain_map), an H x W array converted to
+        C-contiguous float32, or None for no map.  The arithmetic of set_gain with the gain of the pixel being decided (the window's
+        centre).  A property of the context like the mask: kept across set_params.  Refused (FfsError, state unchanged): an entry
+        that is not finite or outside [2^-60, 2^60]; with a scalar gain > 0 set; with extended_flavour 1; while a batch is in
+        flight.  A wrong shape is a ValueError."""
+        if gain_map is None:
+            self._check(self._lib.ffs_ctx_set_gain_map(self._h, None))
+            return
+        g = np.ascontiguousarray(gain_map, dtype=np.float32)
+        if g.shape != (self.H, self.W):
+            raise ValueError(f"the gain map must have shape (H, W) = {(self.H, self.W)}, not {g.shape}")
+        self._check(self._lib.ffs_ctx_set_gain_map(self._h, g.ctypes.data_as(C.c_void_p)))
 
     def set_tuning(self, **kw):
         """ffs_ctx_set_tuning: A/B partners, fall-backs and capacities (same results either way); see include/ffs_hip.h."""

@@ -200,6 +200,29 @@ int ffs_ctx_set_max_valid_scope(ffs_ctx *ctx, int scope);
  * whichever call comes second (that flavour copies the reference's device kernels, which have no gain). */
 int ffs_ctx_set_gain(ffs_ctx *ctx, double gain);
 
+/* The detector gain per pixel: DIALS spotfinder.lookup.gain_map, for detectors whose modules, tapers or gain stages do not share one
+ * gain.  The reference's threshold_w_gain (baseline/spotfinder/baseline.cpp) takes a gain ARRAY and reads the entry of the centre
+ * pixel: gain[k] at :244-245 (standard algorithm), :541 (extended first pass), :714 (extended final pass).
+ *   host_gain: W*H float32, row-major, dense; copied before the call returns.  NULL = no map (the default).
+ *   The arithmetic is exactly that of ffs_ctx_set_gain above, with g = (double)host_gain[y*W + x] of the pixel (x, y) being decided --
+ *   the window's CENTRE, never a neighbour's entry.  Window sums, erosion, min_count, threshold and max_valid under both scopes are
+ *   what they are without a gain.  The map is float32 because the kernels read it once per pixel and frame and no calibration carries
+ *   more than 24 bits; the widening to float64 is exact, so a constant map of value c gives bit for bit the results of
+ *   ffs_ctx_set_gain(ctx, (double)(float)c).
+ *   A map batch takes the paths a gain batch takes: FFS_PATH_WINDOW at every window, the extended algorithm's plain first pass,
+ *   erosion + final pass under tuning "ext_fused", the gather under "threshold_path" 2.  Composes with every kernel_half_x / _y and
+ *   with FFS_MAX_VALID_WINDOW.  With no map and gain 0 everything is as before: kernels, paths and results.
+ * A property of the context like the mask, not a per-batch snapshot: kept across ffs_ctx_set_params, and it cannot change under a
+ * batch.  FFS_ERR_INVALID, state unchanged (ffs_last_error has the text):
+ *   - an entry that is not finite or not in [2^-60, 2^60] (zero, negative, NaN, infinite): the text names the index of the first
+ *     one.  Entries under masked pixels are checked like all others: replace zeros or NaNs in detector gaps first;
+ *   - a map while any stream of the context has a batch between submit and ffs_wait (NULL is accepted then too: the batch in
+ *     flight and its re-runs inside ffs_wait go on with the map they were submitted with, which stays on the device);
+ *   - a map while a gain > 0 is set, and ffs_ctx_set_gain(g > 0) while a map is set: the two are exclusive
+ *     (ffs_ctx_set_gain(ctx, 0) and ffs_ctx_set_gain_map(ctx, NULL) are always accepted otherwise);
+ *   - a map together with extended_flavour 1, whichever call comes second, as for the scalar. */
+int ffs_ctx_set_gain_map(ffs_ctx *ctx, const float *host_gain);
+
 /* Selects between paths that give the SAME results (A/B partners, fall-backs, capacities that tests shrink) --
  * per context, never through the environment; nothing here can change a result.  Keys (default):
  *   "threshold_path"   (0) 0 = windows the streaming kernel cannot vouch for go onto a list (fix-up kernel),

@@ -9,7 +9,11 @@ photon frames, so that the strong sets, and with them the screens' loads, are co
 move some decisions (every row reports its own strong_pixels_per_frame).  One context per row, all in one process, the rows measured
 in alternating rounds.  One JSON line per row; the gain row's first frames are also held to tests/gain_oracle.py.
 
-A checkout from before the setter has no gain rows: run there (same box, alternating with this one) the other rows are the
+The gain-map rows (ffs_ctx_set_gain_map: k_window_gain_map, extended_gain_map) reuse the scalar gain rows' frames in ADU and their
+workloads, under a map of eight vertical stripes of gains around 2.5 (2.15 .. 2.85, mean 2.5) that the 32 frames of a batch share:
+what the per-pixel load costs is the difference to the scalar row of the same run.  Held to tests/gain_map_oracle.py.
+
+A checkout from before a setter has no rows of its kind: run there (same box, alternating with this one) the other rows are the
 parent's figures.
 
   python3 tools/gain_cost.py --rounds 5 --iters 10 > profiles/...jsonl
@@ -27,20 +31,37 @@ sys.path.insert(0, ROOT)
 import numpy as np  # noqa: E402
 
 GAIN = 2.5
-ROWS = ["k_window_forced_gain0", "k_window_gain", "k_stream_gain0", "extended_default_gain0", "extended_first0_gain0", "extended_gain"]
+ROWS = ["k_window_forced_gain0", "k_window_gain", "k_window_gain_map", "k_stream_gain0", "extended_default_gain0", "extended_first0_gain0",
+        "extended_gain", "extended_gain_map"]
+STRIPES = [2.15, 2.25, 2.35, 2.45, 2.55, 2.65, 2.75, 2.85]
 
 
-def oracle_match(W, H, dt, adu_frames, mask, n_check, extended):
+def stripe_map(W, H):
+    """Eight vertical stripes of equal width (the last takes the remainder), float32."""
+    g = np.empty((H, W), np.float32)
+    for i, v in enumerate(STRIPES):
+        g[:, i * (W // 8):(W if i == 7 else (i + 1) * (W // 8))] = v
+    return g
+
+
+def oracle_match(W, H, dt, adu_frames, mask, n_check, extended, gain_map=None):
     import ffs_amd
     import gain_oracle as G
     c = ffs_amd.Context(W, H, dt, max_batch=n_check)
     c.set_mask(mask)
     c.set_params(want_strong_list=1, algorithm=ffs_amd.ALGO_DISPERSION_EXTENDED if extended else ffs_amd.ALGO_DISPERSION)
-    c.set_gain(GAIN)
+    if gain_map is None:
+        c.set_gain(GAIN)
+    else:
+        import gain_map_oracle as M
+        c.set_gain_map(gain_map)
     res = c.stream().process(np.ascontiguousarray(adu_frames[:n_check]))
     ok = True
     for r, img in zip(res, adu_frames[:n_check]):
-        want = G.dispersion_extended_gain(img, mask, GAIN)[0] if extended else G.dispersion_gain(img, mask, GAIN)
+        if gain_map is not None:
+            want = M.dispersion_extended_gain_map(img, mask, gain_map)[0] if extended else M.dispersion_gain_map(img, mask, gain_map)
+        else:
+            want = G.dispersion_extended_gain(img, mask, GAIN)[0] if extended else G.dispersion_gain(img, mask, GAIN)
         k = np.flatnonzero(want.reshape(-1))
         ok = ok and r.num_strong_pixels == len(k) and np.array_equal(r.strong_k.astype(np.int64), k)
     c.close()
@@ -55,10 +76,11 @@ def run_workload(workload, args):
     frames, mask = make_inputs(workload, args.frames, 0)
     adu_frames = np.minimum(np.rint(frames.astype(np.float64) * GAIN), np.iinfo(dt).max).astype(dt)   # (a saturated pixel stays one)
     B = args.batch
-    have_gain = hasattr(ffs_amd.Context, "set_gain")
+    have_gain, have_map = hasattr(ffs_amd.Context, "set_gain"), hasattr(ffs_amd.Context, "set_gain_map")
+    gmap = stripe_map(W, H)
     ctxs = {}
     for kind in ROWS:
-        if kind.endswith("_gain") and not have_gain:
+        if (kind.endswith("_gain") and not have_gain) or (kind.endswith("_gain_map") and not have_map):
             continue
         c = ffs_amd.Context(W, H, dt, max_batch=B)
         c.set_mask(mask)
@@ -69,6 +91,8 @@ def run_workload(workload, args):
         c.set_params(algorithm=ffs_amd.ALGO_DISPERSION_EXTENDED if kind.startswith("extended") else ffs_amd.ALGO_DISPERSION)
         if kind.endswith("_gain"):
             c.set_gain(GAIN)
+        if kind.endswith("_gain_map"):
+            c.set_gain_map(gmap)
         ctxs[kind] = (c, c.stream())
     c0 = next(iter(ctxs.values()))[0]
     pitch, fstride = c0.device_layout()
@@ -80,11 +104,15 @@ def run_workload(workload, args):
         return torch.from_numpy(host.view(np.uint8).reshape(-1)).cuda()
 
     d_photons, d_adu = resident(frames), resident(adu_frames)
+
+    def in_adu(key):
+        return key.endswith("_gain") or key.endswith("_gain_map")
+
     times = {key: [] for key in ctxs}
     rest = {key: [] for key in ctxs}
     for _ in range(args.rounds):                 # alternating: every row once per round
         for key, (c, st) in ctxs.items():
-            d = d_adu if key.endswith("_gain") else d_photons
+            d = d_adu if in_adu(key) else d_photons
             a, b = st.bench_threshold(d.data_ptr(), pitch, fstride, B, args.iters)
             times[key].append(a)
             rest[key].append(b)
@@ -92,11 +120,11 @@ def run_workload(workload, args):
     for key, (c, st) in ctxs.items():
         ms = statistics.median(times[key])
         match = None
-        if key.endswith("_gain") and args.check > 0:
-            match = oracle_match(W, H, dt, adu_frames, mask, args.check, key.startswith("extended"))
-        src = adu_frames if key.endswith("_gain") else frames
+        if in_adu(key) and args.check > 0:
+            match = oracle_match(W, H, dt, adu_frames, mask, args.check, key.startswith("extended"), gmap if key.endswith("_gain_map") else None)
+        src = adu_frames if in_adu(key) else frames
         strong = float(np.mean([r.num_strong_pixels for r in st.process(np.ascontiguousarray(src[:2]))]))   # (what the row's frames hold)
-        print(json.dumps({"workload": workload, "kernel": key, "gain": GAIN if key.endswith("_gain") else 0, "batch": B, "unique_frames": len(frames),
+        print(json.dumps({"workload": workload, "kernel": key, "gain": GAIN if key.endswith("_gain") else "map" if key.endswith("_gain_map") else 0, "batch": B, "unique_frames": len(frames),
                           "strong_pixels_per_frame": strong,
                           "launches_per_round": args.iters, "label": args.label, "ms_per_launch": round(ms, 4),
                           "ms_rounds": [round(t, 4) for t in times[key]], "ms_rest": round(statistics.median(rest[key]), 4),
