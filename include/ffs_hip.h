@@ -437,12 +437,20 @@ void ffs_stack3d_destroy(ffs_stack3d *st);
 /* Adds the strong pixels of every frame of the stream's last completed batch, keyed by frame_id
  * (the reference keys its rotation_slices map by image number, spotfinder.cc:913-918). */
 int ffs_stack3d_add_batch(ffs_stack3d *st, ffs_stream *s);
-/* Adds one slice from host memory (k ascending) -- what a gather from other GPUs delivers. */
+/* Adds one slice from host memory (k ascending) -- what a gather from other GPUs delivers.
+ * A frame id added twice: the later list counts.  Intensities are expected to be at least 1, as
+ * every list the threshold produces is: for a strong pixel of intensity 0 the reference's peak
+ * search (which starts from numeric_limits<double>::min()) and the packed maximum used here
+ * (which starts from 0) legitimately disagree about the peak. */
 int ffs_stack3d_add_slice(ffs_stack3d *st, int64_t frame_id, const uint32_t *k,
                           const uint32_t *intensity, uint32_t n);
 /* Orders slices by frame_id (std::map order, spotfinder.cc:1105-1108), z = rank, runs the 3D
  * union-find on the device, filters with min_spot_size_3d / max_peak_centroid_separation.
- * reflections are in label order; n_calculated = "Calculated {} spots". */
+ * reflections are in label order; n_calculated = "Calculated {} spots".
+ * Centroids are bit-exact with the reference while sum (2c+1) * I < 2^53 per component and axis
+ * (c = x, y or z; the sums are kept as 64-bit integers, the reference adds (c + 0.5) * I in
+ * double, exact while its partial sums stay below 2^52): beyond that the reference's own result
+ * depends on its summation order. */
 int ffs_stack3d_finish(ffs_stack3d *st, const ffs_reflection **reflections,
                        uint32_t *n_reflections, uint32_t *n_calculated,
                        uint32_t *n_filtered_size, uint32_t *n_filtered_sep);

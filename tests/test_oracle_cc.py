@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 from scipy import ndimage
 
+from cc_shapes import _helix_components
 from oracle import oracle as O
 
 
@@ -138,40 +139,6 @@ def test_partition_matches_scipy_label_3d(seed):
     assert r.n_calculated == n
     sizes = sorted(int((lab == i).sum()) for i in range(1, n + 1))
     assert sorted(int(x) for x in r.reflections["num_pixels"]) == sizes
-
-
-def _helix_components(vol):
-    """Independent formulation of the reference's graph INCLUDING its row-wrap edge: strong pixels of each slice
-    as a 1D sequence (linear index k = y W + x), edges k -- k+1 (no row-end check, connected_components.cc:62-70),
-    k -- k+W, and the same k in the next slice (:352-370); components by scipy's sparse-graph labelling; numbered
-    in order of their smallest (z, k) vertex (Boost's DFS discovery order over ascending vertex ids)."""
-    from scipy.sparse import coo_matrix
-    from scipy.sparse.csgraph import connected_components
-    Z, H, W = vol.shape
-    flat = vol.reshape(Z, H * W) != 0
-    ids = -np.ones((Z, H * W), np.int64)
-    n = 0
-    for z in range(Z):
-        on = np.flatnonzero(flat[z])
-        ids[z, on] = np.arange(n, n + len(on))
-        n += len(on)
-    src, dst = [], []
-    for z in range(Z):
-        a = ids[z]
-        for step in (1, W):                        # k+1 joins (W-1, y) with (0, y+1) too
-            both = (a[:-step] >= 0) & (a[step:] >= 0)
-            src.append(a[:-step][both]); dst.append(a[step:][both])
-        if z + 1 < Z:
-            both = (a >= 0) & (ids[z + 1] >= 0)
-            src.append(a[both]); dst.append(ids[z + 1][both])
-    src, dst = np.concatenate(src), np.concatenate(dst)
-    g = coo_matrix((np.ones(len(src), np.int8), (src, dst)), shape=(n, n))
-    _, lab = connected_components(g, directed=False)
-    first = np.full(lab.max() + 1 if n else 0, n, np.int64)
-    np.minimum.at(first, lab, np.arange(n))
-    order = np.argsort(first)                      # label order = order of the smallest vertex
-    rank = np.empty_like(order); rank[order] = np.arange(len(order))
-    return ids, rank[lab] if n else lab
 
 
 @pytest.mark.parametrize("seed", range(10))
