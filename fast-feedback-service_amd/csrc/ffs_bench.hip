@@ -82,6 +82,53 @@ extern "C" int ffs_bench_threshold(ffs_stream* s, const void* device_pixels, siz
     return FFS_OK;
 }
 
+// Average duration of the radial profile of one batch (kernels_radial.hpp: k_radial + k_radial_sum) over `iters` runs on resident frames,
+// launched alone: the start event rides on the first dispatch, the stop event on the second.  Needs a bin map on the context; the
+// profiles go to the host buffer the stream's next batch would write, so what the last ffs_wait handed out stays as it is.
+extern "C" int ffs_bench_radial(ffs_stream* s, const void* device_pixels, size_t pitch, size_t fstride, uint32_t n_frames, uint32_t iters, float* ms) {
+    if (!s || !device_pixels || iters == 0 || !stream_handle_ok(s)) return FFS_ERR_INVALID;
+    ffs_ctx* c = s->ctx;
+    if (s->busy) {
+        c->err = "stream busy";
+        return FFS_ERR_INVALID;
+    }
+    if (c->radial_bins == 0) {
+        c->err = "ffs_bench_radial: the context has no bin map (ffs_ctx_set_radial_bins)";
+        return FFS_ERR_INVALID;
+    }
+    int rc = check_layout(s, pitch, fstride, n_frames);
+    if (rc != FFS_OK) return rc;
+    HIP_TRY(c, hipSetDevice(c->device));
+    s->batch = snapshot_of(c);
+    rc = radial_ensure_buffers(s, s->batch.radial_bins);
+    if (rc != FFS_OK) return rc;
+    std::vector<hipEvent_t> ev(2 * (size_t)iters, nullptr);
+    auto cleanup = [&]() { for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e); };
+    for (auto& e : ev)
+        if (hipEventCreate(&e) != hipSuccess) {
+            cleanup();
+            c->err = "hipEventCreate failed";
+            return FFS_ERR_DEVICE;
+        }
+    (void)hipGetLastError();
+    for (uint32_t i = 0; i < iters && rc == FFS_OK; ++i) rc = radial_launch(s, device_pixels, pitch, fstride, n_frames, s->st, ev[2 * i], ev[2 * i + 1]);
+    hipError_t err = hipStreamSynchronize(s->st);
+    double t = 0;
+    for (uint32_t i = 0; i < iters && rc == FFS_OK && err == hipSuccess; ++i) {
+        float a = 0;
+        err = hipEventElapsedTime(&a, ev[2 * i], ev[2 * i + 1]);
+        t += a;
+    }
+    cleanup();
+    if (rc != FFS_OK) return rc;
+    if (err != hipSuccess) {
+        c->err = std::string("ffs_bench_radial: ") + hipGetErrorString(err);
+        return FFS_ERR_DEVICE;
+    }
+    if (ms) *ms = (float)(t / iters);
+    return FFS_OK;
+}
+
 // The submit / wait loop bench.py runs in Python for one GPU, natively: `steps` batches of device-resident frames through
 // `n_streams` streams of one context, all in flight.  For drivers with one host thread per GPU (bench.py --single-process):
 // no interpreter lock is held while it runs.  Sums over all frames: boxes (spots after the size filter) and strong pixels.

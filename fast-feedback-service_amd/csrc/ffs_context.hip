@@ -310,6 +310,7 @@ static void ctx_destroy_internal(ffs_ctx* c) {
     }
     if (c->d_maskbits) (void)hipFree(c->d_maskbits);
     if (c->d_gain_map) (void)hipFree(c->d_gain_map);
+    if (c->d_radial_map) (void)hipFree(c->d_radial_map);
     if (c->d_ginfo) (void)hipFree(c->d_ginfo);
     if (c->d_mmap) (void)hipFree(c->d_mmap);
     if (c->dense_st) (void)hipStreamDestroy(c->dense_st);
@@ -512,6 +513,58 @@ extern "C" int ffs_ctx_set_gain_map(ffs_ctx* c, const float* host_gain) {
     return guarded(c, [&] { return ffs_ctx_set_gain_map_impl(c, host_gain); });
 }
 
+// The bin map of the radial profile.  Everything is checked before anything changes; like the gain map, the device
+// copy is written only while no batch of the context is in flight, and NULL only switches the map off (a batch in flight took its bins at
+// submit and its profile kernels read the device copy, which stays).
+static int ffs_ctx_set_radial_bins_impl(ffs_ctx* c, const uint16_t* bin_of_pixel, uint32_t n_bins) {
+    if (!bin_of_pixel) {
+        c->radial_bins = 0;
+        return FFS_OK;
+    }
+    if (n_bins < 1 || n_bins > 1024) {
+        c->err = "ffs_ctx_set_radial_bins: n_bins must be in 1..1024, got " + std::to_string(n_bins);
+        return FFS_ERR_INVALID;
+    }
+    if (c->inflight.load() > 0) {
+        c->err = "ffs_ctx_set_radial_bins: a batch of this context is in flight (ffs_wait for it first): a batch keeps the map it was submitted with";
+        return FFS_ERR_INVALID;
+    }
+    const Layout& L = c->L;
+    const size_t n = (size_t)L.W * L.H;
+    for (size_t i = 0; i < n; ++i)
+        if (bin_of_pixel[i] >= n_bins && bin_of_pixel[i] != 0xFFFFu) {
+            c->err = "ffs_ctx_set_radial_bins: entry " + std::to_string(i) + " (x = " + std::to_string(i % (size_t)L.W) + ", y = " + std::to_string(i / (size_t)L.W)
+                     + ") is " + std::to_string(bin_of_pixel[i]) + ": every entry must be below n_bins = " + std::to_string(n_bins) + " or 0xFFFF (in no bin)";
+            return FFS_ERR_INVALID;
+        }
+    // rows of pitch_px entries, addressed like the pixel rows; the entries beyond W are in no bin
+    std::vector<uint16_t> rows((size_t)L.pitch_px * L.H, (uint16_t)0xFFFFu);
+    for (int y = 0; y < L.H; ++y) std::memcpy(rows.data() + (size_t)y * L.pitch_px, bin_of_pixel + (size_t)y * L.W, (size_t)L.W * sizeof(uint16_t));
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (!c->d_radial_map) {
+        uint16_t* d = nullptr;
+        if (hipMalloc(reinterpret_cast<void**>(&d), rows.size() * (sizeof(uint16_t) + 1)) != hipSuccess) {
+            (void)hipGetLastError();
+            c->err = "ffs_ctx_set_radial_bins: hipMalloc(bin map) failed";
+            return FFS_ERR_NOMEM;
+        }
+        c->d_radial_map = d;
+        c->d_radial_map8 = reinterpret_cast<uint8_t*>(d + rows.size());
+    }
+    HIP_TRY(c, hipMemcpy(c->d_radial_map, rows.data(), rows.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
+    if (n_bins <= 255) {   // the one-byte form (tuning "radial_map8"): what a batch's launch takes is decided from n_bins and the tuning alone
+        std::vector<uint8_t> rows8(rows.size());
+        for (size_t i = 0; i < rows.size(); ++i) rows8[i] = (uint8_t)rows[i];   // (0xFFFF -> 0xFF; every other entry is below 255)
+        HIP_TRY(c, hipMemcpy(c->d_radial_map8, rows8.data(), rows8.size(), hipMemcpyHostToDevice));
+    }
+    c->radial_bins = n_bins;
+    return FFS_OK;
+}
+extern "C" int ffs_ctx_set_radial_bins(ffs_ctx* c, const uint16_t* bin_of_pixel, uint32_t n_bins) {
+    if (!c) return FFS_ERR_INVALID;
+    return guarded(c, [&] { return ffs_ctx_set_radial_bins_impl(c, bin_of_pixel, n_bins); });
+}
+
 extern "C" int ffs_ctx_set_max_valid_scope(ffs_ctx* c, int scope) {
     if (!c) return FFS_ERR_INVALID;
     if (scope != FFS_MAX_VALID_CENTRE && scope != FFS_MAX_VALID_WINDOW) {
@@ -543,6 +596,8 @@ extern "C" int ffs_ctx_set_tuning(ffs_ctx* c, const char* key, long long value) 
     bool ok = true;
     if (k == "threshold_path") { if ((ok = in(0, 2))) t.threshold_path = (int)value; }
     else if (k == "window_kernel") { if ((ok = in(0, 1))) t.window_kernel = (int)value; }
+    else if (k == "radial_stream") { if ((ok = in(0, 1))) t.radial_stream = (int)value; }
+    else if (k == "radial_map8") { if ((ok = in(0, 1))) t.radial_map8 = (int)value; }
     else if (k == "ext_first_pass") { if ((ok = value == 0 || value == 2)) t.ext_first_pass = (int)value; }
     else if (k == "sparse_stage") { if ((ok = in(1, 3))) t.sparse_stage = (int)value; }
     else if (k == "device_lists") { if ((ok = in(0, 2))) t.device_lists = (int)value; }
@@ -628,6 +683,7 @@ void stream_destroy_internal(ffs_stream* s) {
     if (s->st) (void)hipStreamSynchronize(s->st);
     if (s->st_shared && s->ctx->dense_st2) (void)hipStreamSynchronize(s->ctx->dense_st2);   // (the dense stream's partner may hold this stream's kernel)
     if (s->st2 && s->st2 != s->st) { (void)hipStreamSynchronize(s->st2); if (!s->st2_shared) (void)hipStreamDestroy(s->st2); }
+    radial_free(s);
     // (d_n_comp, d_summary and d_overflow live inside the d_num_strong allocation)
     if (s->h_pack_tab) (void)hipHostFree(s->h_pack_tab);
     // (the stream's device buffers are one slab; what is allocated on first use is freed by itself)

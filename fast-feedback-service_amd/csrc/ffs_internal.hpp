@@ -74,6 +74,7 @@ struct ParamSnapshot {
     int max_valid_scope = FFS_MAX_VALID_CENTRE;
     double gain = 0.0;
     bool gain_map = false;
+    uint32_t radial_bins = 0;   // bins of the context's radial bin map at submit (0: no map): the batch computes a profile over that many bins
 };
 
 // A few helper threads per context for ffs_wait's result assembly (wire records -> boxes, reflections, centre rows): one thread
@@ -139,6 +140,11 @@ struct ffs_ctx {
     float* d_gain_map = nullptr;
     bool has_gain_map = false;
     float gain_map_min = 0.0f, gain_map_max = 0.0f;
+    // ffs_ctx_set_radial_bins: [H][pitch_px] uint16 bin entries, allocated at the first set and kept (entries beyond W
+    // are 0xFFFF); radial_bins says whether a map is in force and how many bins it has (0 = none).  Like the gain map it cannot change under a batch.
+    uint16_t* d_radial_map = nullptr;
+    uint8_t* d_radial_map8 = nullptr;   // the same rows in one byte an entry (0xFF: in no bin), behind the two-byte rows in the same allocation; written for maps of at most 255 bins
+    uint32_t radial_bins = 0;
     uint8_t* d_maskbits = nullptr;
     uint8_t* d_ginfo = nullptr;  // per-group mask bits + window-count bounds (kernels_stream.hpp)
     uint8_t* d_mmap = nullptr;   // per-pixel window counts
@@ -279,6 +285,21 @@ struct ffs_stream {
     bool occ_dirty = false;     // the occupancy bitmap may hold bits nobody will consume
     uint32_t *h_list_k = nullptr, *h_list_i = nullptr;
     uint8_t* h_mask = nullptr;
+    // The radial profile (kernels_radial.hpp) of a batch whose snapshot has radial_bins (ParamSnapshot).  radial_todo: set by the submit entry
+    // points -- the batch's first enqueue launches the profile and clears it, the re-runs inside ffs_wait find it off; radial_pending: a batch
+    // is in flight whose profile (or the lack of one) ffs_wait has not handed out yet (set once its launches are enqueued).  The bands' partials
+    // live on the device; the results are written straight into one of two pinned host buffers that take turns, so the profile ffs_wait handed
+    // out stays readable while the next batch is in flight.  All allocated on first use and re-sized when a later map has more bins (a host
+    // buffer somebody may still read is retired, and freed at the next wait).
+    bool radial_todo = false, radial_pending = false;
+    uint8_t* d_radial_part = nullptr;
+    size_t radial_part_entries = 0;          // (frame, band, bin) triples the partials hold
+    uint8_t *h_radial[2] = {nullptr, nullptr}, *h_radial_dev[2] = {nullptr, nullptr};
+    uint32_t h_radial_bins = 0;              // bins per frame the two host buffers hold
+    int radial_turn = 0;                     // the host buffer the next batch writes
+    std::vector<uint8_t*> radial_retired;
+    const uint8_t* radial_out = nullptr;     // what ffs_stream_radial_profile reads: the last waited batch's buffer, bins (0: no profile) and frames
+    uint32_t radial_out_bins = 0, radial_out_frames = 0;
     // state of the batch in flight
     bool busy = false;
     uint32_t n_frames = 0;
@@ -353,7 +374,7 @@ static int guarded(ffs_ctx* c, F&& body) {
     } while (0)
 
 // ---- small helpers ------------------------------------------------------------------------------------------
-static inline ParamSnapshot snapshot_of(const ffs_ctx* c) { return ParamSnapshot{c->params, c->max_valid_scope, c->gain, c->has_gain_map}; }
+static inline ParamSnapshot snapshot_of(const ffs_ctx* c) { return ParamSnapshot{c->params, c->max_valid_scope, c->gain, c->has_gain_map, c->radial_bins}; }
 // What ffs_wait asks of the enqueue that runs a batch AGAIN because a plan did not hold it (ffs_wait.hip, rerun_batch); the default
 // is a normal batch.  An argument of that one call: what a stream remembers beyond it (log_off, runs_overflowed, band_backoff) is
 // in ffs_stream.
@@ -431,6 +452,13 @@ bool wave_logs_for(ffs_stream* s, ThresholdArgs& a, const StreamGeometry& g, con
 void launch_dense_kernel(ffs_stream* s, const ThresholdRoute& route, const ThresholdArgs& a, const StreamGeometry& g, uint32_t n_frames, hipEvent_t start,
                          hipEvent_t stop, bool plane_clean = false, bool counts_clean = false);
 void launch_dense_rest(ffs_stream* s, const ThresholdRoute& route, const ThresholdArgs& a, uint32_t n_frames);
+// The radial profile: ensure makes room for the profiles of this stream's batches under a map of `bins` bins (no batch of the stream in flight);
+// launch puts the two kernels into `st` for frames that are in place there, over s->batch.radial_bins bins, writing the host buffer whose turn
+// it is (start / stop: events on the two dispatches, either may be null); publish is ffs_wait's side.
+int radial_ensure_buffers(ffs_stream* s, uint32_t bins);
+int radial_launch(ffs_stream* s, const void* d_img, size_t pitch, size_t fstride, uint32_t n_frames, hipStream_t st, hipEvent_t start, hipEvent_t stop);
+void radial_publish(ffs_stream* s);
+void radial_free(ffs_stream* s);
 // ffs_wait.hip
 int ffs_wait_impl(ffs_stream* s, const ffs_frame_result** results, uint32_t* n_results);
 void ahead_register(ffs_stream* s);   // the batch just enqueued may be assembled ahead of its ffs_wait

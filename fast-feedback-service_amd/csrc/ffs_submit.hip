@@ -14,6 +14,7 @@
 #include "kernels_decode.hpp"
 #include "kernels_byteoffset.hpp"
 #include "kernels_window.hpp"
+#include "kernels_radial.hpp"
 
 bool chain_prepare_device() {   // more than 64 KB of dynamic LDS has to be asked for, per device
     const hipError_t e1 = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_frame_chain<uint16_t>), hipFuncAttributeMaxDynamicSharedMemorySize, kChainDynBytes);
@@ -775,9 +776,141 @@ static int finish_enqueue(ffs_stream* s, uint32_t n, bool bits_dirty, bool count
     s->counts_dirty = counts_dirty;
     mark_busy(s);
     s->n_frames = n;
+    s->radial_pending = true;   // (the batch is in flight: its wait hands out its profile, or that it has none)
     return FFS_OK;
 }
 
+// ---- the radial profile (kernels_radial.hpp) -----------------------------------------------------------------
+// Few fat workgroups over contiguous row bands: about 2048 workgroups a launch (eight per CU) and at most 64 bands a frame, which bounds
+// the partials at 64 x n_bins x 20 B a frame -- 1.3 MB at 1024 bins, under 4 % of an Eiger frame.
+constexpr uint32_t kRadialTargetGroups = 2048, kRadialMaxBands = 64;
+static void radial_bands(const Layout& L, uint32_t n_frames, uint32_t& n_bands, uint32_t& band_rows) {
+    const uint32_t want = std::clamp<uint32_t>((kRadialTargetGroups + n_frames - 1) / n_frames, 1u, std::min<uint32_t>((uint32_t)L.H, kRadialMaxBands));
+    band_rows = ((uint32_t)L.H + want - 1) / want;
+    n_bands = ((uint32_t)L.H + band_rows - 1) / band_rows;
+}
+// bytes of a result buffer: sums, sums of squares, counts, [max_batch][bins] each
+static inline size_t radial_host_bytes(const ffs_stream* s, uint32_t bins) { return (size_t)s->max_batch * bins * 20u; }
+
+void radial_free(ffs_stream* s) {
+    if (s->d_radial_part) (void)hipFree(s->d_radial_part);
+    for (uint8_t* p : s->h_radial)
+        if (p) (void)hipHostFree(p);
+    for (uint8_t* p : s->radial_retired) (void)hipHostFree(p);
+    s->d_radial_part = nullptr;
+    s->h_radial[0] = s->h_radial[1] = nullptr;
+    s->radial_retired.clear();
+    s->radial_part_entries = 0;
+    s->h_radial_bins = 0;
+}
+
+// Room for the profile of a batch of up to max_batch frames under a map of `bins` bins.  Only on a stream with no batch in flight.
+int radial_ensure_buffers(ffs_stream* s, uint32_t bins) {
+    ffs_ctx* c = s->ctx;
+    size_t slots = 0;   // the most (frame, band) pairs a batch of this stream can have
+    for (uint32_t nf = 1; nf <= s->max_batch; ++nf) {
+        uint32_t nb = 0, rows = 0;
+        radial_bands(c->L, nf, nb, rows);
+        slots = std::max(slots, (size_t)nf * nb);
+    }
+    if (slots * bins > s->radial_part_entries) {
+        if (s->d_radial_part) (void)hipFree(s->d_radial_part);
+        s->d_radial_part = nullptr;
+        s->radial_part_entries = 0;
+        if (hipMalloc(reinterpret_cast<void**>(&s->d_radial_part), slots * bins * 20u) != hipSuccess) {
+            (void)hipGetLastError();
+            c->err = "radial profile: hipMalloc(partials) failed";
+            return FFS_ERR_NOMEM;
+        }
+        s->radial_part_entries = slots * bins;
+    }
+    if (bins > s->h_radial_bins) {
+        // (the buffer the last wait handed out may still be read: it is freed at the next wait; the other one nobody reads)
+        for (int i = 0; i < 2; ++i) {
+            if (!s->h_radial[i]) continue;
+            if (s->h_radial[i] == s->radial_out) s->radial_retired.push_back(s->h_radial[i]);
+            else (void)hipHostFree(s->h_radial[i]);
+            s->h_radial[i] = nullptr;
+        }
+        s->h_radial_bins = 0;
+        for (int i = 0; i < 2; ++i) {
+            if (hipHostMalloc(reinterpret_cast<void**>(&s->h_radial[i]), radial_host_bytes(s, bins), hipHostMallocDefault) != hipSuccess
+                || hipHostGetDevicePointer(reinterpret_cast<void**>(&s->h_radial_dev[i]), s->h_radial[i], 0) != hipSuccess) {
+                (void)hipGetLastError();
+                c->err = "radial profile: hipHostMalloc(results) failed";
+                return FFS_ERR_NOMEM;
+            }
+        }
+        s->h_radial_bins = bins;
+    }
+    return FFS_OK;
+}
+
+int radial_launch(ffs_stream* s, const void* d_img, size_t pitch, size_t fstride, uint32_t n_frames, hipStream_t st, hipEvent_t start, hipEvent_t stop) {
+    ffs_ctx* c = s->ctx;
+    const Layout& L = c->L;
+    const uint32_t bins = s->batch.radial_bins;
+    const size_t B = s->max_batch;
+    RadialArgs a{};
+    a.image = d_img;
+    a.frame_stride = fstride;
+    a.pitch = (uint32_t)pitch;
+    a.maskbits = c->d_maskbits;
+    a.mpitch = L.mpitch;
+    a.bins = c->d_radial_map;
+    a.bin_pitch = (uint32_t)L.pitch_px;
+    a.W = L.W;
+    a.H = L.H;
+    a.n_bins = bins;
+    radial_bands(L, n_frames, a.n_bands, a.band_rows);
+    // (max_valid under both of its scopes, and the oracle's neighbour rule for 32-bit pixels: what set_predicate calls nb_limit under the window scope)
+    const long long mv = s->batch.params.max_valid;
+    a.limit = mv >= 0 ? (uint32_t)std::min<long long>(mv, (1ll << 24) - 1) + 1u : 1u << 24;
+    const size_t part = s->radial_part_entries;
+    a.p_sum = reinterpret_cast<uint64_t*>(s->d_radial_part);
+    a.p_sq = a.p_sum + part;
+    a.p_count = reinterpret_cast<uint32_t*>(a.p_sq + part);
+    uint8_t* out = s->h_radial_dev[s->radial_turn];
+    a.r_sum = reinterpret_cast<uint64_t*>(out);
+    a.r_sq = a.r_sum + B * bins;
+    a.r_count = reinterpret_cast<uint32_t*>(a.r_sq + B * bins);
+    if ((size_t)n_frames * a.n_bands * bins > part || bins > s->h_radial_bins || !a.bins) {
+        c->err = "radial profile: the stream's buffers do not hold this batch";
+        return FFS_ERR_INVALID;
+    }
+    const dim3 grid(n_frames, a.n_bands);
+    // (the one-byte form of the map: tuning "radial_map8", for maps of at most 255 bins -- ffs_ctx_set_radial_bins keeps both forms then)
+    a.bins8 = (c->tune.radial_map8 && bins <= 255) ? c->d_radial_map8 : nullptr;
+    using RadialKernel = void (*)(RadialArgs);
+    const RadialKernel k = c->pixel_bytes == 2 ? (a.bins8 ? k_radial<uint16_t, true> : k_radial<uint16_t, false>)
+                                               : (a.bins8 ? k_radial<uint32_t, true> : k_radial<uint32_t, false>);
+    hipExtLaunchKernelGGL(k, grid, dim3(kRadialThreads), radial_lds_bytes(bins), st, start, nullptr, 0, a);
+    hipExtLaunchKernelGGL(k_radial_sum, dim3((bins + 255) / 256, n_frames), dim3(256), 0, st, nullptr, stop, 0, a);
+    HIP_TRY(c, hipGetLastError());
+    return FFS_OK;
+}
+
+// The batch's profile, once: launched by the batch's first enqueue (radial_todo: the re-runs of ffs_wait find it off), for frames that are in
+// place in `st`.  Where: tuning "radial_stream".  0 (default): in the batch's SPARSE stream behind the sparse launch and ahead of the batch's
+// last event -- the stream has waited for the threshold stage there.  1: in the DENSE stream behind the threshold stage's kernels; the sparse
+// stream then waits for ev[5], recorded behind it, ahead of the batch's last event (ffs_wait records ev[5] anew only after that event).
+static int launch_radial(ffs_stream* s, uint32_t n, hipStream_t st) {
+    s->radial_todo = false;
+    FFS_TRY(radial_ensure_buffers(s, s->batch.radial_bins));   // (first use, or a map with more bins: the stream has no batch in flight yet)
+    return radial_launch(s, s->cur_img, s->cur_pitch, s->cur_fstride, n, st, nullptr, nullptr);
+}
+static inline bool radial_wanted(const ffs_stream* s) { return s->radial_todo && s->batch.radial_bins != 0; }
+static int launch_radial_dense(ffs_stream* s, uint32_t n) {
+    if (!radial_wanted(s) || s->ctx->tune.radial_stream != 1 || s->st2 == s->st || s->ctx->tune.dense_overlap != 0) return FFS_OK;   // (dense_overlap: the stage's kernel may be in the partner stream)
+    FFS_TRY(launch_radial(s, n, s->st));
+    HIP_TRY(s->ctx, hipEventRecord(s->ev[5], s->st));
+    HIP_TRY(s->ctx, hipStreamWaitEvent(s->st2, s->ev[5], 0));
+    return FFS_OK;
+}
+static int launch_radial_stage(ffs_stream* s, uint32_t n) {
+    if (!radial_wanted(s)) return FFS_OK;
+    return launch_radial(s, n, s->st2);
+}
 using ChainKernel = void (*)(ChainArgs);
 static ChainKernel frame_chain_kernel(const BatchPlan& plan, int pixel_bytes) {
     if (plan.use_log) return pixel_bytes == 2 ? k_frame_chain<uint16_t, false, true> : k_frame_chain<uint32_t, false, true>;
@@ -840,6 +973,7 @@ static int launch_one_launch_stage(ffs_stream* s, const BatchPlan& plan, const C
         s->dplane2_clean = true;
         s->eplane2_clean = plan.ext_sparse_erode;
     }
+    FFS_TRY(launch_radial_stage(s, n));
     HIP_TRY(c, hipEventRecord(s->ev[4], s->st2));
     s->ev3_is_ev4 = true;
     s->spec_recs_copied = (uint64_t)s->max_batch * s->max_comp;
@@ -884,6 +1018,7 @@ static int launch_grid_stage(ffs_stream* s, const BatchPlan& plan, const CclArgs
         s->spec_recs_copied = std::min<uint64_t>((uint64_t)s->spec_recs_per_frame * n, (uint64_t)B * s->max_comp);
         HIP_TRY(c, hipMemcpyAsync(s->h_recs, s->d_recs, s->spec_recs_copied * sizeof(WireRec2), hipMemcpyDeviceToHost, s->st2));
     }
+    FFS_TRY(launch_radial_stage(s, n));
     HIP_TRY(c, hipEventRecord(s->ev[4], s->st2));
     // the compaction of a streamed batch leaves the plane all zero again; k_union cleared the counts of the frames of this batch (all
     // the streaming kernel touched)
@@ -899,7 +1034,7 @@ static int launch_sparse_stage(ffs_stream* s, const BatchPlan& plan) {
     s->dense_valid = plan.want_dense_bytes;
     s->occ_dirty = !(ca.use_occ && plan.will_chain);      // nobody consumes (and clears) the bits this batch sets
     s->chain_mode = plan.will_chain;
-    s->path_bits = plan.path_bits;
+    s->path_bits = plan.path_bits | (s->batch.radial_bins ? FFS_PATH_RADIAL : 0u);
     return plan.will_chain ? launch_one_launch_stage(s, plan, ca, sa) : launch_grid_stage(s, plan, ca, sa);
 }
 
@@ -918,6 +1053,7 @@ int enqueue_batch(ffs_stream* s, const void* d_img, size_t pitch, size_t fstride
     bool dense_resets = false;
     FFS_TRY(reset_for_batch(s, plan, dense_resets));
     FFS_TRY(launch_threshold_stage(s, plan, dense_resets, ext_plane_clean));
+    FFS_TRY(launch_radial_dense(s, n));
     return launch_sparse_stage(s, plan);
 }
 
@@ -938,6 +1074,7 @@ extern "C" int ffs_submit_device(ffs_stream* s, const void* device_pixels, size_
     s->ev1_pending = true;
     s->first_id = first_frame_id;
     s->reruns = 0;
+    s->radial_todo = true;
     rc = enqueue_batch(s, device_pixels, pitch, fstride, n_frames);
     if (rc == FFS_OK) ahead_register(s);
     return rc;
@@ -956,6 +1093,7 @@ extern "C" int ffs_submit(ffs_stream* s, const void* host_pixels, uint32_t n_fra
     }
     const Layout& L = c->L;
     HIP_TRY(c, hipSetDevice(c->device));
+    s->radial_todo = true;
     s->dev_input = false;
     HIP_TRY(c, hipEventRecord(s->ev[0], s->st_up));
     // one 2D copy: the default device layout keeps frames contiguous (frame_stride = H * pitch)
@@ -1268,6 +1406,7 @@ static int ffs_submit_encoded_impl(ffs_stream* s, int codec, const void* const* 
     }
     if (!codec_known(c, codec, "ffs_submit_encoded")) return FFS_ERR_INVALID;
     HIP_TRY(c, hipSetDevice(c->device));
+    s->radial_todo = true;
     s->dev_input = false;
     HIP_TRY(c, hipEventRecord(s->ev[0], s->st_up));
     std::vector<size_t> base;

@@ -396,6 +396,7 @@ static int rerun_overflow_frames(ffs_stream* s) {
             // (the frame's strong-pixel list comes back to the host whenever somebody may read it: the caller, or a 3D stack
             // that is alive -- ffs_stack3d_add_batch takes an overflow frame's list from here, tuning "device_lists")
             ParamSnapshot bp = s->batch;
+            bp.radial_bins = 0;   // (the batch's profile was computed by its first enqueue)
             if (c->tune.device_lists == 1 || (c->tune.device_lists == 2 && g_live_stacks.load() > 0)) bp.params.want_strong_list = 1;
             int rc = enqueue_batch(b, img, s->cur_pitch, s->cur_fstride, 1, &bp);
             if (rc != FFS_OK) return rc;
@@ -577,8 +578,46 @@ int ffs_wait_impl(ffs_stream* s, const ffs_frame_result** results, uint32_t* n_r
             return rc;
         }
     }
+    radial_publish(s);
     if (results) *results = s->results.data();
     if (n_results) *n_results = s->n_frames;
+    return FFS_OK;
+}
+
+// The radial profile of the batch this wait returns becomes what ffs_stream_radial_profile reads (once per batch: the wait of a re-run
+// is this same function, and finds nothing pending the second time).  The two host buffers take turns, so the next batch writes the other one.
+void radial_publish(ffs_stream* s) {
+    if (!s->radial_pending) return;
+    s->radial_pending = false;
+    for (uint8_t* p : s->radial_retired) (void)hipHostFree(p);   // (what the previous wait had handed out before the buffers grew)
+    s->radial_retired.clear();
+    s->radial_out = nullptr;
+    if (s->batch.radial_bins) {
+        s->radial_out = s->h_radial[s->radial_turn];
+        s->radial_turn ^= 1;
+    }
+    s->radial_out_bins = s->batch.radial_bins;
+    s->radial_out_frames = s->n_frames;
+}
+
+extern "C" int ffs_stream_radial_profile(ffs_stream* s, uint32_t frame_in_batch, ffs_radial_profile* out) {
+    if (!s || !out || !stream_handle_ok(s)) return FFS_ERR_INVALID;
+    ffs_ctx* c = s->ctx;
+    if (!s->radial_out || s->radial_out_bins == 0) {
+        c->err = "ffs_stream_radial_profile: the last batch ffs_wait returned on this stream was submitted without a bin map (ffs_ctx_set_radial_bins)";
+        return FFS_ERR_INVALID;
+    }
+    if (frame_in_batch >= s->radial_out_frames) {
+        c->err = "ffs_stream_radial_profile: frame_in_batch " + std::to_string(frame_in_batch) + " is out of range: the batch had " + std::to_string(s->radial_out_frames) + " frames";
+        return FFS_ERR_INVALID;
+    }
+    // (the layout k_radial_sum writes: sums, sums of squares, counts, [max_batch][bins] each)
+    const size_t bins = s->radial_out_bins, plane = (size_t)s->max_batch * bins;
+    const uint64_t* sum = reinterpret_cast<const uint64_t*>(s->radial_out);
+    out->n_bins = s->radial_out_bins;
+    out->sum = sum + (size_t)frame_in_batch * bins;
+    out->sum_sq = sum + plane + (size_t)frame_in_batch * bins;
+    out->count = reinterpret_cast<const uint32_t*>(sum + 2 * plane) + (size_t)frame_in_batch * bins;
     return FFS_OK;
 }
 

@@ -65,6 +65,9 @@ struct Tuning {
     int sparse_priority = 0;    // priority of the context's sparse HIP streams: 0 = highest, 1 = lowest, 2 = the dense stream's
     int window_kernel = 0;      // 1: the general-window kernel (kernels_window.hpp) also runs the 7x7 window -- the A/B and cross-check partner
                                 //    of k_stream_u16 / k_stream_u32; 0: only windows other than 3,3 take it
+    int radial_stream = 0;      // the radial profile's two launches (kernels_radial.hpp): 0 = in the batch's sparse stream behind its sparse launch, 1 = in the
+                                //    dense stream behind the threshold stage's kernels (the A/B partner: DESIGN.md section 3.6 has both measurements)
+    int radial_map8 = 0;        // k_radial reads the bin map in one byte an entry where the map has at most 255 bins (1) or always in two (0)
 #ifdef FFS_EXPERIMENTS
     struct Exp {
         int k1_debug = 0, chain_skip = 0, chain_stop = 0, dummy_us = 0, dummy_wg = 32, dummy_threads = 1024, dummy_lds = 0;

@@ -22,7 +22,7 @@ void usage() {
       "                  [-t S] [-fd FD] [-a ALGO] [--dmin MIN D] [--dmax MAX D] [-w \xce\xbb] [--detector JSON]\n"
       "                  [-h5] [--output-for-index] [--batch N] [--cpu-decode] [--strict-dtype]\n"
       "                  [--max-valid trusted|none|N] [--max-valid-scope centre|window] [--min-count N] [--kernel-size N | NX,NY]\n"
-      "                  [--gain G] [--gain-map FILE]\n"
+      "                  [--gain G] [--gain-map FILE] [--radial-bins N]\n"
       "                  [--devices D0,D1,... | --gpus N] [--no-numa-pinning] [--single-buffer] [--all-threads] [--read-only] [--clean-exit]\n"
       "--max-valid: a centre pixel above this value is never strong (the reference's kernels test it against the\n"
       "              data set's trusted maximum).  trusted (default) = the frame source's trusted-range maximum when it is\n"
@@ -41,6 +41,10 @@ void usage() {
       "              spotfinder.lookup.gain_map): FILE holds exactly width x height float32 values, little-endian, row-major, nothing\n"
       "              else; every value finite and in [2^-60, 2^60], under masked pixels too.  Each pixel is decided with the --gain\n"
       "              arithmetic and its own value.  Not together with --gain\n"
+      "--radial-bins: per image, the count, sum and sum of squares of the valid pixels in each of N (1..1024) resolution shells of equal\n"
+      "              width in 1/d^2, from the beam centre to the furthest pixel: the background level and its dispersion per shell, as\n"
+      "              \"radial_count\", \"radial_sum\" and \"radial_sum_sq\" arrays in every image's JSON line (pixels above --max-valid and\n"
+      "              masked pixels, --dmin / --dmax included, are left out).  Needs the detector geometry and the wavelength --dmin needs\n"
       "--validate:  every image is also decided by an independent path (every valid pixel's window gathered from memory,\n"
       "              no streaming kernel) and the two strong-pixel masks are compared: Match / Mismatch per image\n"
       "--devices / --gpus: one context and worker pool per GPU, all pulling frames from the one queue\n"
@@ -174,6 +178,11 @@ Args parse_args(int argc, char** argv) {
         else if (s == "--gain-map") {
             r.gain_map = need(i, s);
             if (r.gain_map.empty() || !fs::is_regular_file(r.gain_map)) arg_error("--gain-map: no such file: " + r.gain_map);
+        }
+        else if (s == "--radial-bins") {
+            const std::string& v = need(i, s);
+            r.radial_bins = u32(v, s);
+            if (r.radial_bins < 1 || r.radial_bins > 1024) arg_error("--radial-bins takes a number of shells in 1..1024: " + v);
         }
         else if (s == "--min-count") { r.min_count = u32(need(i, s), s); if (r.min_count < 2) arg_error("--min-count must be at least 2"); }
         else if (s == "--no-numa-pinning") r.no_numa_pinning = true;

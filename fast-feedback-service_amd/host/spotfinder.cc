@@ -30,6 +30,7 @@
 #include "cli_args.hpp"
 #include "ffs_hip.h"
 #include "minijson.hpp"
+#include "radial_bins.hpp"
 #include "kabsch_space.hpp"
 #include "png_writer.hpp"
 #include "reader.hpp"
@@ -217,6 +218,14 @@ static int open_source_beside_runtime(const Args& args, Stamps& stamp, std::uniq
         reader_holder.th.join();
         if (reader_rc != 0) return reader_rc;
         gain_map = read_gain_map(args, (uint32_t)reader->image_shape()[1], (uint32_t)reader->image_shape()[0]);
+    }
+    if (args.radial_bins) {   // (--radial-bins needs the geometry --dmin needs: without it a usage error, like a bad --gain-map, wherever the driver runs)
+        if (reader_holder.th.joinable()) reader_holder.th.join();
+        if (reader_rc != 0) return reader_rc;
+        const bool detector = args.detector_set || (reader->get_beam_center() && reader->get_pixel_size() && reader->get_detector_distance());
+        const bool wavelength = args.wavelength_set || reader->get_wavelength();
+        if (!detector) arg_error("--radial-bins needs the detector geometry (distance, beam centre, pixel size): the frame source has none, pass --detector");
+        if (!wavelength) arg_error("--radial-bins needs the wavelength: the frame source has none, pass --wavelength");
     }
     if (n_devices < 1) {  // cuda_arg_parser.cc:56-61
         give_up.store(true);
@@ -587,7 +596,7 @@ class BatchReport {
                 std::lock_guard<std::mutex> lock(centers_mutex_);
                 reflection_centers_2d[image_num + args_.start_index] = std::move(coms);
             }
-            if (pipe_) append_json(r, round_rows, json_lines);
+            if (pipe_) append_json(r, batch.stream, i, round_rows, json_lines);
             append_text(r, batch.validation ? &batch.validation[i] : nullptr, batch, text);
         }
         if (pipe_ && !json_lines.empty()) pipe_->send_lines(json_lines);
@@ -598,10 +607,24 @@ class BatchReport {
 
   private:
     // one image's JSON line; keys in alphabetical order, as nlohmann dumps them (:997-1008)
-    void append_json(const ffs_frame_result& r, const float*& round_rows, std::string& json_lines) const {
+    // --radial-bins: the image's profile as three arrays of N integers (behind "num_strong_pixels": the keys stay in alphabetical order)
+    static std::string radial_json(ffs_stream* stream, uint32_t frame_in_batch) {
+        ffs_radial_profile prof{};
+        if (ffs_stream_radial_profile(stream, frame_in_batch, &prof) != FFS_OK) return "";
+        std::string c = ",\"radial_count\":[", s = ",\"radial_sum\":[", q = ",\"radial_sum_sq\":[";
+        for (uint32_t b = 0; b < prof.n_bins; ++b) {
+            const char* sep = b ? "," : "";
+            c += sep + std::to_string(prof.count[b]);
+            s += sep + std::to_string(prof.sum[b]);
+            q += sep + std::to_string(prof.sum_sq[b]);
+        }
+        return c + "]" + s + "]" + q + "]";
+    }
+    void append_json(const ffs_frame_result& r, ffs_stream* stream, uint32_t frame_in_batch, const float*& round_rows, std::string& json_lines) const {
         std::string j = "{\"file\":" + json_escape(args_.file) + ",\"file-number\":" + std::to_string((uint32_t)r.frame_id)
                         + ",\"n_spots_total\":" + std::to_string(r.n_boxes)
                         + ",\"num_strong_pixels\":" + std::to_string(r.num_strong_pixels);
+        if (args_.radial_bins) j += radial_json(stream, frame_in_batch);
         if (args_.output_for_index) {
             j += ",\"spot_centers\":[";
             for (uint32_t qq = 0; qq < r.n_reflections; ++qq) {
@@ -846,6 +869,20 @@ int main(int argc, char** argv) {
     if (!gain_map.empty())
         std::printf("Detector gain map: %s (%g .. %g)\n", args.gain_map.c_str(), (double)*std::min_element(gain_map.begin(), gain_map.end()),
                     (double)*std::max_element(gain_map.begin(), gain_map.end()));
+    if (args.radial_bins) {
+        // N shells of equal width in 1/d^2, built here in float64 (radial_bins.hpp); the library only counts into them
+        const DetectorGeometry& d = ex.detector;
+        const RadialBins shells = radial_bins(RadialGeometry{ex.wavelength, d.distance, d.beam_center_x, d.beam_center_y, d.pixel_size_x, d.pixel_size_y},
+                                              shape.width, shape.height, args.radial_bins);
+        for (ffs_ctx* cx : ctxs) FFS_CHECK(cx, ffs_ctx_set_radial_bins(cx, shells.bin_of_pixel.data(), shells.n_bins));
+        std::string edges;
+        for (uint32_t k = 0; k <= shells.n_bins; ++k) {
+            char buf[32];
+            std::snprintf(buf, sizeof buf, k == 0 ? "inf" : " %.4g", shells.d_edge(k));
+            edges += buf;
+        }
+        std::printf("Radial bins: %u shells, d edges (A): %s\n", shells.n_bins, edges.c_str());
+    }
     if (args.validate && !create_validation_contexts(devices, ctxs, shape, batch, prm, args.max_valid_scope, args.gain, gain_map, vctxs)) return 1;
     if (args.save_h5 && !h5_supported()) {
         std::printf("Error: --save-h5 needs an HDF5-enabled build\n");

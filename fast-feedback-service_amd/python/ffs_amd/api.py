@@ -67,6 +67,13 @@ REFL_DT = np.dtype([("x_min", "<u4"), ("x_max", "<u4"), ("y_min", "<u4"), ("y_ma
                     ("peak_intensity", "<u4"), ("peak_centroid_distance", "<f4"),
                     ("flags", "<u4"), ("sum_intensity", "<u8")])
 assert REFL_DT.itemsize == C.sizeof(_Refl) and BOX_DT.itemsize == C.sizeof(_Box)
+
+
+class _RadialProfile(C.Structure):   # ffs_radial_profile
+    _fields_ = [("n_bins", C.c_uint32), ("count", C.POINTER(C.c_uint32)), ("sum", C.POINTER(C.c_uint64)), ("sum_sq", C.POINTER(C.c_uint64))]
+
+
+RADIAL_NO_BIN = 0xFFFF   # a bin-map entry that is in no bin (Context.set_radial_bins)
 # ffs_frame_result as a numpy record (offsets taken from the ctypes structure: pointers and padding included)
 _FRAME_RESULT_DT = np.dtype({"names": ["frame_id", "num_strong_pixels", "num_strong_pixels_filtered", "n_components", "n_boxes", "n_reflections"],
                              "formats": ["<i8", "<u4", "<u4", "<u4", "<u4", "<u4"],
@@ -90,6 +97,7 @@ EXPORTS = [
     "ffs_stack3d_destroy", "ffs_stack3d_add_batch", "ffs_stack3d_add_slice", "ffs_stack3d_finish", "ffs_stack3d_signals", "ffs_stack3d_last_finish_ms", "ffs_multi_init", "ffs_multi_transport",
     "ffs_ctx_set_tuning", "ffs_bench_pipeline", "ffs_device_numa_node", "ffs_stream_reserve_host", "ffs_stream_last_path", "ffs_multi_gather_rows",
     "ffs_ctx_set_max_valid_scope", "ffs_ctx_set_gain", "ffs_ctx_set_gain_map",
+    "ffs_ctx_set_radial_bins", "ffs_stream_radial_profile", "ffs_bench_radial",
 ]
 
 _lib = None
@@ -116,6 +124,9 @@ def load_library():
         L.ffs_ctx_set_max_valid_scope.argtypes = [C.c_void_p, C.c_int]
         L.ffs_ctx_set_gain.argtypes = [C.c_void_p, C.c_double]
         L.ffs_ctx_set_gain_map.argtypes = [C.c_void_p, C.c_void_p]
+        L.ffs_ctx_set_radial_bins.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
+        L.ffs_stream_radial_profile.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(_RadialProfile)]
+        L.ffs_bench_radial.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_uint32, C.c_uint32, C.POINTER(C.c_float)]
         L.ffs_bench_pipeline.argtypes = [C.POINTER(C.c_void_p), C.c_uint32, C.c_void_p, C.c_size_t, C.c_size_t, C.c_uint32,
                                          C.c_uint32, C.c_int64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
         L.ffs_device_numa_node.argtypes = [C.c_int]
@@ -284,6 +295,27 @@ class Context:
         if g.shape != (self.H, self.W):
             raise ValueError(f"the gain map must have shape (H, W) = {(self.H, self.W)}, not {g.shape}")
         self._check(self._lib.ffs_ctx_set_gain_map(self._h, g.ctypes.data_as(C.c_void_p)))
+
+    def set_radial_bins(self, bins: np.ndarray | None, n_bins=None):
+        """ffs_ctx_set_radial_bins: the bin map of the per-frame radial profile, an H x W array of bin indices (converted to
+        C-contiguous uint16; RADIAL_NO_BIN = 0xFFFF is "in no bin"), or None for no map (the default).  n_bins (1..1024) defaults
+        to max + 1 over the entries other than 0xFFFF (1 when there is none).  A property of the context like the mask: kept across
+        set_params; a batch takes it at submit, and Stream.radial_profile reads its profile after wait().  Refused (FfsError, state
+        unchanged): n_bins outside 1..1024; an entry >= n_bins that is not 0xFFFF; a map while a batch is in flight.  A wrong shape,
+        or an entry that no uint16 holds, is a ValueError."""
+        if bins is None:
+            self._check(self._lib.ffs_ctx_set_radial_bins(self._h, None, 0))
+            return
+        a = np.asarray(bins)
+        if a.shape != (self.H, self.W):
+            raise ValueError(f"the bin map must have shape (H, W) = {(self.H, self.W)}, not {a.shape}")
+        if a.dtype.kind not in "iu" or (a.size and (int(a.min()) < 0 or int(a.max()) > 0xFFFF)):
+            raise ValueError("the bin map must hold integers in 0..65535 (0xFFFF = in no bin)")
+        b = np.ascontiguousarray(a, dtype=np.uint16)
+        if n_bins is None:
+            used = b[b != RADIAL_NO_BIN]
+            n_bins = int(used.max()) + 1 if used.size else 1
+        self._check(self._lib.ffs_ctx_set_radial_bins(self._h, b.ctypes.data_as(C.c_void_p), int(n_bins)))
 
     def set_tuning(self, **kw):
         """ffs_ctx_set_tuning: A/B partners, fall-backs and capacities (same results either way); see include/ffs_hip.h."""
@@ -469,7 +501,7 @@ class Stream:
         self.ctx._check(self._lib.ffs_stream_timings(self._h, t))
         return dict(zip(("h2d", "threshold", "ccl", "d2h", "total"), list(t)))
 
-    PATH_BITS = {"wave_logs": 1, "frame_chain": 2, "bands": 4, "runs": 8, "grid_kernels": 16, "extended": 32, "window": 64}
+    PATH_BITS = {"wave_logs": 1, "frame_chain": 2, "bands": 4, "runs": 8, "grid_kernels": 16, "extended": 32, "window": 64, "radial": 128}
 
     def last_path(self):
         """ffs_stream_last_path: (set of the launches the last batch took, times ffs_wait ran it again)."""
@@ -484,6 +516,21 @@ class Stream:
                                                       frame_stride_bytes, n_frames, iters,
                                                       C.byref(a), C.byref(b)))
         return a.value, b.value
+
+    def radial_profile(self, frame_in_batch: int):
+        """ffs_stream_radial_profile: (count uint32, sum uint64, sum_sq uint64 modulo 2^64), n_bins entries each, of one frame of the
+        last batch wait() returned -- copies.  FfsError when that batch was submitted without a bin map or the frame is out of range."""
+        out = _RadialProfile()
+        self.ctx._check(self._lib.ffs_stream_radial_profile(self._h, int(frame_in_batch), C.byref(out)))
+        n = out.n_bins
+        return (np.ctypeslib.as_array(out.count, (n,)).copy(), np.ctypeslib.as_array(out.sum, (n,)).copy(),
+                np.ctypeslib.as_array(out.sum_sq, (n,)).copy())
+
+    def bench_radial(self, dev_ptr: int, pitch_bytes: int, frame_stride_bytes: int, n_frames: int, iters: int) -> float:
+        """ffs_bench_radial: average ms of one batch's radial profile (its two launches), alone on resident frames."""
+        ms = C.c_float()
+        self.ctx._check(self._lib.ffs_bench_radial(self._h, C.c_void_p(dev_ptr), pitch_bytes, frame_stride_bytes, n_frames, iters, C.byref(ms)))
+        return ms.value
 
     def bench_hbm(self, iters: int = 5):
         """(read-only GB/s, 2:1 read/write GB/s) measured on this stream's buffers (ffs_bench_hbm)."""

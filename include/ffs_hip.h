@@ -223,6 +223,34 @@ int ffs_ctx_set_gain(ffs_ctx *ctx, double gain);
  *   - a map together with extended_flavour 1, whichever call comes second, as for the scalar. */
 int ffs_ctx_set_gain_map(ffs_ctx *ctx, const float *host_gain);
 
+/* The per-frame radial profile: per frame and bin of a caller-defined bin map (resolution shells, usually), how many pixels count, their
+ * sum and their sum of squares -- the background level and its dispersion per shell, what DIALS builds its radial_profile threshold, its
+ * ice-ring filter and its per-image analysis on.  The reference reports nothing of the kind (its per-image output is the strong mask and
+ * the spots, spotfinder/spotfinder.cc:887-933).  Computed on the device from what a batch has there anyway: the pixels, the valid-pixel
+ * mask, max_valid.
+ *   bin_of_pixel: W*H uint16, row-major, dense; copied before the call returns.  An entry is a bin index < n_bins, or 0xFFFF for "in no
+ *   bin".  n_bins: 1..1024.  NULL = no map (the default): every kernel, path and result is as before.
+ *   The caller defines the bins and the library never computes a resolution (the resolution mask works in float32 with atanf / sinf;
+ *   binning on that would make shell membership a rounding question): any geometry works -- several panels; shells equal in 1/d^2, in d
+ *   or in radius; azimuthal sectors.
+ *   A pixel (x, y) of a frame counts into bin b = bin_of_pixel[y*W + x] when all of these hold:
+ *     - b != 0xFFFF;
+ *     - its bit in the context's valid-pixel mask is set -- the mask as it stands at submit, ffs_ctx_apply_resolution_mask included;
+ *     - p <= max_valid when ffs_params.max_valid >= 0, under both scopes of max_valid;
+ *     - for 32-bit pixels, p < 2^24 (the oracle's neighbour rule, standalone.cc:78,90).
+ *   Per frame and bin: count (uint32), sum = the sum of p (uint64), sum_sq = the sum of p*p (uint64, taken modulo 2^64).  sum_sq is exact for
+ *   every 16-bit frame (2^32 * 2^25 < 2^64); it can wrap only for 32-bit frames with more than 65 536 pixels near 2^24 in one bin.
+ *   All three are integers and independent of the order of summation: the result is exact, bit for bit.
+ *   The profile depends on nothing of the threshold stage: algorithm, window, gain, the scope of max_valid beyond the rule above, tuning
+ *   keys, or the path a batch takes (a batch that ffs_wait runs again keeps the profile of its first pass).
+ * A property of the context like the mask and the gain map: kept across ffs_ctx_set_params; a batch takes it as it is at submit.
+ * FFS_ERR_INVALID, state unchanged (ffs_last_error has the text):
+ *   - n_bins outside 1..1024;
+ *   - an entry >= n_bins that is not 0xFFFF: the text names the index of the first one, with its x and y;
+ *   - a map while any stream of the context has a batch between submit and ffs_wait.  As for the gain map, NULL is accepted then too:
+ *     the batch in flight goes on with the map it was submitted with, which stays on the device, and hands out its profile. */
+int ffs_ctx_set_radial_bins(ffs_ctx *ctx, const uint16_t *bin_of_pixel, uint32_t n_bins);
+
 /* Selects between paths that give the SAME results (A/B partners, fall-backs, capacities that tests shrink) --
  * per context, never through the environment; nothing here can change a result.  Keys (default):
  *   "threshold_path"   (0) 0 = windows the streaming kernel cannot vouch for go onto a list (fix-up kernel),
@@ -264,6 +292,12 @@ int ffs_ctx_set_gain_map(ffs_ctx *ctx, const float *host_gain);
  *   "window_kernel"    (0) 0 = the general-window threshold kernel (any kernel_half_x / _y in 1..7, exact sums, the oracle's float64
  *                          predicate) runs only for windows other than 3,3; 1 = it runs for every window, 3,3 included (the A/B and
  *                          cross-check partner of the 7x7 streaming kernels: same results)
+ *   "radial_stream"    (0) the radial profile's two launches (ffs_ctx_set_radial_bins): 0 = in the batch's sparse stream behind its sparse
+ *                          launch, 1 = in the dense stream behind the threshold stage's kernels (measured 11 % slower in the pipeline: the A/B partner).
+ *                          1 is taken as 0 where there is no dense stream to tell from the sparse one ("sched" 0: one HIP stream per
+ *                          ffs_stream) and under "dense_overlap" 1 (the stage's kernel may be in the dense stream's partner)
+ *   "radial_map8"      (0) the radial profile reads a bin map of at most 255 bins in one byte an entry (1) instead of two (0): DESIGN.md section 3.6
+ *                          has the measurement
  *   "assembly_threads" (7: helper threads that build a batch's result arrays; 3, 12 and 15 measure the same): see DESIGN.md.
  *   "band_taper" (0), "ext_rest_aside" (0), "ext_fused" (0): round 4's A/B partners (tapered bands of the streaming kernels;
  *                          extended algorithm: erosion + final pass in the sparse stream / fused into one kernel) -- measured, no
@@ -376,7 +410,20 @@ int ffs_stream_timings(ffs_stream *s, float ms[5]);
 #define FFS_PATH_GRID_KERNELS 16u  /* sparse stage: four grid-wide kernels */
 #define FFS_PATH_EXTENDED 32u      /* extended dispersion */
 #define FFS_PATH_WINDOW 64u        /* the general-window threshold kernel (a window other than 3,3, or tuning "window_kernel" = 1) */
+#define FFS_PATH_RADIAL 128u       /* the batch computed a radial profile (ffs_ctx_set_radial_bins) */
 int ffs_stream_last_path(ffs_stream *s, uint32_t *path_bits, uint32_t *reruns);
+
+/* The radial profile (ffs_ctx_set_radial_bins) of frame `frame_in_batch` of the last batch ffs_wait returned on this stream: n_bins
+ * entries each, complete when ffs_wait returns.  The pointers stay valid until the next ffs_wait on the stream, like the pointers in
+ * ffs_frame_result (the stream's next batch may be in flight meanwhile).  FFS_ERR_INVALID: that batch was submitted without a map;
+ * frame_in_batch is out of range; a dead handle. */
+typedef struct {
+    uint32_t n_bins;
+    const uint32_t *count;
+    const uint64_t *sum;
+    const uint64_t *sum_sq;
+} ffs_radial_profile;
+int ffs_stream_radial_profile(ffs_stream *s, uint32_t frame_in_batch, ffs_radial_profile *out);
 
 /* Centres of mass of the last batch's reflections as rows (frame_id, x, y, z) of float32 -- the
  * payload of `--output-for-index` (spot_centers, spotfinder.cc:919-933,1004-1006), in frame order;
@@ -398,6 +445,11 @@ int ffs_stream_spot_centres(ffs_stream *s, float *rows4, uint32_t cap, uint32_t 
 int ffs_bench_threshold(ffs_stream *s, const void *device_pixels, size_t pitch_bytes,
                         size_t frame_stride_bytes, uint32_t n_frames, uint32_t iters,
                         float *ms_dense, float *ms_rest);
+/* Runs the radial profile (ffs_ctx_set_radial_bins: the context needs a map) alone on device-resident frames, `iters` times, and
+ * returns the average duration of one batch's profile -- its two launches, from HIP events that ride on the dispatches themselves.  The
+ * profile ffs_stream_radial_profile hands out is not touched.  (No counterpart in the reference.) */
+int ffs_bench_radial(ffs_stream *s, const void *device_pixels, size_t pitch_bytes, size_t frame_stride_bytes,
+                     uint32_t n_frames, uint32_t iters, float *ms);
 /* The submit / wait loop of a resident-frames benchmark, natively: `steps` batches of the same device-resident
  * frames through `n_streams` streams of ONE context, all of them in flight (ffs_submit_device / ffs_wait).  For
  * drivers with one host thread per GPU (bench.py --single-process, the threading model of
