@@ -129,6 +129,54 @@ extern "C" int ffs_bench_radial(ffs_stream* s, const void* device_pixels, size_t
     return FFS_OK;
 }
 
+// Average duration of the per-pixel statistics' launch for one batch (kernels_pixstats.hpp) over `iters` runs on resident frames, launched
+// alone in the stream's dense HIP stream.  The accumulators are the context's own, and what they hold afterwards is no statistic of anything.
+extern "C" int ffs_bench_pixel_stats(ffs_stream* s, const void* device_pixels, size_t pitch, size_t fstride, uint32_t n_frames, uint32_t iters, float* ms) {
+    if (!s || !device_pixels || iters == 0 || !stream_handle_ok(s)) return FFS_ERR_INVALID;
+    ffs_ctx* c = s->ctx;
+    if (c->stats_on) {
+        c->err = "ffs_bench_pixel_stats: accumulation is on (ffs_ctx_set_pixel_stats(ctx, FFS_PIXEL_STATS_OFF) first): the measurement leaves the accumulators undefined";
+        return FFS_ERR_INVALID;
+    }
+    if (c->inflight.load() > 0) {
+        c->err = "ffs_bench_pixel_stats: a batch of this context is in flight (ffs_wait for it first)";
+        return FFS_ERR_INVALID;
+    }
+    int rc = check_layout(s, pitch, fstride, n_frames);
+    if (rc != FFS_OK) return rc;
+    rc = pixstats_ensure(c);
+    if (rc != FFS_OK) return rc;
+    std::vector<hipEvent_t> ev(2 * (size_t)iters, nullptr);
+    auto cleanup = [&]() { for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e); };
+    for (auto& e : ev)
+        if (hipEventCreate(&e) != hipSuccess) {
+            cleanup();
+            c->err = "hipEventCreate failed";
+            return FFS_ERR_DEVICE;
+        }
+    (void)hipGetLastError();
+    {
+        std::lock_guard<std::mutex> lock(c->stats_mu);
+        for (uint32_t i = 0; i < iters && rc == FFS_OK; ++i)
+            rc = pixstats_launch(c, device_pixels, pitch, fstride, n_frames, c->params.max_valid, s->st, ev[2 * i], ev[2 * i + 1]);
+    }
+    hipError_t err = hipStreamSynchronize(s->st);
+    double t = 0;
+    for (uint32_t i = 0; i < iters && rc == FFS_OK && err == hipSuccess; ++i) {
+        float a = 0;
+        err = hipEventElapsedTime(&a, ev[2 * i], ev[2 * i + 1]);
+        t += a;
+    }
+    cleanup();
+    if (rc != FFS_OK) return rc;
+    if (err != hipSuccess) {
+        c->err = std::string("ffs_bench_pixel_stats: ") + hipGetErrorString(err);
+        return FFS_ERR_DEVICE;
+    }
+    if (ms) *ms = (float)(t / iters);
+    return FFS_OK;
+}
+
 // The submit / wait loop bench.py runs in Python for one GPU, natively: `steps` batches of device-resident frames through
 // `n_streams` streams of one context, all in flight.  For drivers with one host thread per GPU (bench.py --single-process):
 // no interpreter lock is held while it runs.  Sums over all frames: boxes (spots after the size filter) and strong pixels.

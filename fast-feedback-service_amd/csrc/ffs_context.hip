@@ -311,6 +311,11 @@ static void ctx_destroy_internal(ffs_ctx* c) {
     if (c->d_maskbits) (void)hipFree(c->d_maskbits);
     if (c->d_gain_map) (void)hipFree(c->d_gain_map);
     if (c->d_radial_map) (void)hipFree(c->d_radial_map);
+    if (c->stats_st) {   // (the streams are closed: nothing new comes, what is there is let finish)
+        (void)hipStreamSynchronize(c->stats_st);
+        (void)hipStreamDestroy(c->stats_st);
+    }
+    if (c->d_stats) (void)hipFree(c->d_stats);
     if (c->d_ginfo) (void)hipFree(c->d_ginfo);
     if (c->d_mmap) (void)hipFree(c->d_mmap);
     if (c->dense_st) (void)hipStreamDestroy(c->dense_st);
@@ -565,6 +570,93 @@ extern "C" int ffs_ctx_set_radial_bins(ffs_ctx* c, const uint16_t* bin_of_pixel,
     return guarded(c, [&] { return ffs_ctx_set_radial_bins_impl(c, bin_of_pixel, n_bins); });
 }
 
+// ---- the per-pixel statistics ------------------------------------------------------------------------------------
+int pixstats_ensure(ffs_ctx* c) {
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (!c->stats_st) HIP_TRY(c, hipStreamCreateWithFlags(&c->stats_st, hipStreamNonBlocking));
+    if (!c->d_stats && hipMalloc(reinterpret_cast<void**>(&c->d_stats), pixstats_layout(c).bytes()) != hipSuccess) {
+        (void)hipGetLastError();
+        c->d_stats = nullptr;
+        c->err = "pixel statistics: hipMalloc(accumulators, " + std::to_string(pixstats_layout(c).bytes() >> 20) + " MB) failed";
+        return FFS_ERR_NOMEM;
+    }
+    return FFS_OK;
+}
+
+extern "C" int ffs_ctx_set_pixel_stats(ffs_ctx* c, int mode) {
+    if (!c) return FFS_ERR_INVALID;
+    if (mode != FFS_PIXEL_STATS_OFF && mode != FFS_PIXEL_STATS_START && mode != FFS_PIXEL_STATS_RESUME) {
+        c->err = "ffs_ctx_set_pixel_stats: mode must be FFS_PIXEL_STATS_OFF (0), _START (1) or _RESUME (2), got " + std::to_string(mode);
+        return FFS_ERR_INVALID;
+    }
+    if (mode == FFS_PIXEL_STATS_OFF) {   // (at any time: a batch in flight carries its own "on")
+        c->stats_on = false;
+        return FFS_OK;
+    }
+    if (mode == FFS_PIXEL_STATS_RESUME && c->stats_started) {
+        c->stats_on = true;
+        return FFS_OK;
+    }
+    if (c->inflight.load() > 0) {
+        c->err = "ffs_ctx_set_pixel_stats: a batch of this context is in flight (ffs_wait for it first): a start zeroes the accumulators";
+        return FFS_ERR_INVALID;
+    }
+    if (const int rc = pixstats_ensure(c); rc != FFS_OK) return rc;
+    HIP_TRY(c, hipMemsetAsync(c->d_stats, 0, pixstats_layout(c).bytes(), c->stats_st));
+    HIP_TRY(c, hipStreamSynchronize(c->stats_st));
+    std::lock_guard<std::mutex> lock(c->stats_mu);
+    c->stats_frames = 0;
+    c->stats_started = true;
+    c->stats_on = true;
+    return FFS_OK;
+}
+
+// Everything is checked before anything is copied.  No batch is in flight, so every launch lies ahead of an event some ffs_wait has seen
+// -- the streams are synchronised all the same, for a batch whose wait failed -- and the planes are copied one at a time and un-interleaved.
+static int ffs_ctx_get_pixel_stats_impl(ffs_ctx* c, ffs_pixel_stats* out) {
+    if (!c->stats_started) {
+        c->err = "ffs_ctx_get_pixel_stats: no statistics yet (ffs_ctx_set_pixel_stats(ctx, FFS_PIXEL_STATS_START) first)";
+        return FFS_ERR_INVALID;
+    }
+    if (c->inflight.load() > 0) {
+        c->err = "ffs_ctx_get_pixel_stats: a batch of this context is in flight (ffs_wait for it first)";
+        return FFS_ERR_INVALID;
+    }
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipStreamSynchronize(c->stats_st));
+    if (c->dense_st) HIP_TRY(c, hipStreamSynchronize(c->dense_st));
+    const PixStatsLayout P = pixstats_layout(c);
+    const size_t W = (size_t)c->L.W, H = (size_t)c->L.H;
+    std::vector<uint64_t> plane;
+    auto fetch = [&](size_t offset, size_t bytes, uint32_t entry_bytes, void* dst) -> int {
+        if (!dst) return FFS_OK;
+        plane.resize(bytes / 8);
+        HIP_TRY(c, hipMemcpy(plane.data(), c->d_stats + offset, bytes, hipMemcpyDeviceToHost));
+        for (size_t y = 0; y < H; ++y)
+            for (size_t x = 0; x < W; ++x) {
+                const size_t at = P.entry((uint32_t)(y * P.groups + x / P.px), (uint32_t)(x % P.px), entry_bytes);
+                if (entry_bytes == 4) static_cast<uint32_t*>(dst)[y * W + x] = reinterpret_cast<const uint32_t*>(plane.data())[at];
+                else static_cast<uint64_t*>(dst)[y * W + x] = plane[at];
+            }
+        return FFS_OK;
+    };
+    if (const int rc = fetch(0, P.plane32, 4, out->count); rc != FFS_OK) return rc;
+    if (const int rc = fetch(P.plane32, P.plane32, 4, out->max); rc != FFS_OK) return rc;
+    if (const int rc = fetch(2 * P.plane32, P.plane64, 8, out->sum); rc != FFS_OK) return rc;
+    if (const int rc = fetch(2 * P.plane32 + P.plane64, P.plane64, 8, out->sum_sq); rc != FFS_OK) return rc;
+    std::lock_guard<std::mutex> lock(c->stats_mu);
+    out->n_frames = c->stats_frames;
+    return FFS_OK;
+}
+extern "C" int ffs_ctx_get_pixel_stats(ffs_ctx* c, ffs_pixel_stats* out) {
+    if (!c) return FFS_ERR_INVALID;
+    if (!out) {
+        c->err = "ffs_ctx_get_pixel_stats: out is NULL";
+        return FFS_ERR_INVALID;
+    }
+    return guarded(c, [&] { return ffs_ctx_get_pixel_stats_impl(c, out); });
+}
+
 extern "C" int ffs_ctx_set_max_valid_scope(ffs_ctx* c, int scope) {
     if (!c) return FFS_ERR_INVALID;
     if (scope != FFS_MAX_VALID_CENTRE && scope != FFS_MAX_VALID_WINDOW) {
@@ -598,6 +690,10 @@ extern "C" int ffs_ctx_set_tuning(ffs_ctx* c, const char* key, long long value) 
     else if (k == "window_kernel") { if ((ok = in(0, 1))) t.window_kernel = (int)value; }
     else if (k == "radial_stream") { if ((ok = in(0, 1))) t.radial_stream = (int)value; }
     else if (k == "radial_map8") { if ((ok = in(0, 1))) t.radial_map8 = (int)value; }
+    else if (k == "stats_stream") {
+        // (launches in the context's own stream and launches in the dense stream are not ordered among each other: the key moves only while nothing is in flight)
+        if ((ok = in(0, 1) && c->inflight.load() == 0)) t.stats_stream = (int)value;
+    }
     else if (k == "ext_first_pass") { if ((ok = value == 0 || value == 2)) t.ext_first_pass = (int)value; }
     else if (k == "sparse_stage") { if ((ok = in(1, 3))) t.sparse_stage = (int)value; }
     else if (k == "device_lists") { if ((ok = in(0, 2))) t.device_lists = (int)value; }
@@ -645,7 +741,7 @@ extern "C" int ffs_ctx_set_tuning(ffs_ctx* c, const char* key, long long value) 
         return FFS_ERR_INVALID;
     }
     if (!ok) {
-        c->err = "ffs_ctx_set_tuning: value out of range for '" + k + "' (sched / direct_records: before the first stream is created)";
+        c->err = "ffs_ctx_set_tuning: value out of range for '" + k + "' (sched / direct_records: before the first stream is created; stats_stream: while no batch is in flight)";
         return FFS_ERR_INVALID;
     }
     return FFS_OK;
@@ -684,6 +780,7 @@ void stream_destroy_internal(ffs_stream* s) {
     if (s->st_shared && s->ctx->dense_st2) (void)hipStreamSynchronize(s->ctx->dense_st2);   // (the dense stream's partner may hold this stream's kernel)
     if (s->st2 && s->st2 != s->st) { (void)hipStreamSynchronize(s->st2); if (!s->st2_shared) (void)hipStreamDestroy(s->st2); }
     radial_free(s);
+    if (s->ev_stats) (void)hipEventDestroy(s->ev_stats);   // (the sparse stream, synchronised above, waited for it)
     // (d_n_comp, d_summary and d_overflow live inside the d_num_strong allocation)
     if (s->h_pack_tab) (void)hipHostFree(s->h_pack_tab);
     // (the stream's device buffers are one slab; what is allocated on first use is freed by itself)

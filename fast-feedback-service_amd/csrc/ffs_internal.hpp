@@ -75,6 +75,7 @@ struct ParamSnapshot {
     double gain = 0.0;
     bool gain_map = false;
     uint32_t radial_bins = 0;   // bins of the context's radial bin map at submit (0: no map): the batch computes a profile over that many bins
+    bool pixel_stats = false;   // ffs_ctx_set_pixel_stats was on at submit: the batch's frames are folded into the context's per-pixel statistics, once
 };
 
 // A few helper threads per context for ffs_wait's result assembly (wire records -> boxes, reflections, centre rows): one thread
@@ -145,6 +146,16 @@ struct ffs_ctx {
     uint16_t* d_radial_map = nullptr;
     uint8_t* d_radial_map8 = nullptr;   // the same rows in one byte an entry (0xFF: in no bin), behind the two-byte rows in the same allocation; written for maps of at most 255 bins
     uint32_t radial_bins = 0;
+    // ffs_ctx_set_pixel_stats: the four accumulator planes are one allocation, made at the first start and kept (count,
+    // max, sum, sum of squares, in that order; laid out in tiles: PixStatsLayout below).  stats_on: batches submitted from now on are folded in;
+    // stats_started: there has been a start, ffs_ctx_get_pixel_stats has something to hand out.  stats_st: the context's own HIP stream for the
+    // launches (tuning "stats_stream" 0), made with the accumulators.  stats_mu: one launch at a time is put behind the previous one --
+    // distinct ffs_streams are driven from distinct threads -- and adds its frames to stats_frames.
+    uint8_t* d_stats = nullptr;
+    bool stats_on = false, stats_started = false;
+    uint64_t stats_frames = 0;
+    hipStream_t stats_st = nullptr;
+    std::mutex stats_mu;
     uint8_t* d_maskbits = nullptr;
     uint8_t* d_ginfo = nullptr;  // per-group mask bits + window-count bounds (kernels_stream.hpp)
     uint8_t* d_mmap = nullptr;   // per-pixel window counts
@@ -300,6 +311,11 @@ struct ffs_stream {
     std::vector<uint8_t*> radial_retired;
     const uint8_t* radial_out = nullptr;     // what ffs_stream_radial_profile reads: the last waited batch's buffer, bins (0: no profile) and frames
     uint32_t radial_out_bins = 0, radial_out_frames = 0;
+    // The per-pixel statistics (kernels_pixstats.hpp) of a batch whose snapshot has pixel_stats.  stats_todo: set by the submit entry points --
+    // the batch's first enqueue launches the kernel and clears it, the re-runs inside ffs_wait find it off; stats_join: that launch is not in
+    // the batch's sparse stream, which waits for ev_stats (recorded behind it, made on first use) ahead of the batch's last event.
+    bool stats_todo = false, stats_join = false;
+    hipEvent_t ev_stats = nullptr;
     // state of the batch in flight
     bool busy = false;
     uint32_t n_frames = 0;
@@ -374,7 +390,30 @@ static int guarded(ffs_ctx* c, F&& body) {
     } while (0)
 
 // ---- small helpers ------------------------------------------------------------------------------------------
-static inline ParamSnapshot snapshot_of(const ffs_ctx* c) { return ParamSnapshot{c->params, c->max_valid_scope, c->gain, c->has_gain_map, c->radial_bins}; }
+static inline ParamSnapshot snapshot_of(const ffs_ctx* c) { return ParamSnapshot{c->params, c->max_valid_scope, c->gain, c->has_gain_map, c->radial_bins, c->stats_on}; }
+// Where the per-pixel statistics lie (kernels_pixstats.hpp has the why): a lane owns px = 16 / pixel_bytes pixels of a row, lanes are numbered
+// row by row, sixty-four of them are a tile, and in every plane a lane's entries are chunks of 16 B, chunk k of lane l of tile t at
+// 16 B x ((t * chunks + k) * 64 + l).
+struct PixStatsLayout {
+    uint32_t px = 0, groups = 0, n_lanes = 0;
+    size_t plane32 = 0, plane64 = 0;   // bytes of a plane of 32-bit entries (count, max) and of 64-bit entries (sum, sum of squares)
+    size_t bytes() const { return 2 * plane32 + 2 * plane64; }
+    // entry j (0 .. px - 1) of lane i in a plane of entry_bytes-byte entries, counted in entries
+    size_t entry(uint32_t i, uint32_t j, uint32_t entry_bytes) const {
+        const uint32_t per_chunk = 16u / entry_bytes, chunks = px / per_chunk;
+        return (((size_t)(i >> 6) * chunks + j / per_chunk) * 64u + (i & 63u)) * per_chunk + j % per_chunk;
+    }
+};
+static inline PixStatsLayout pixstats_layout(const ffs_ctx* c) {
+    PixStatsLayout p;
+    p.px = 16u / (uint32_t)c->pixel_bytes;
+    p.groups = ((uint32_t)c->L.W + p.px - 1) / p.px;
+    p.n_lanes = p.groups * (uint32_t)c->L.H;
+    const size_t tiles = ((size_t)p.n_lanes + 63) / 64;
+    p.plane32 = tiles * 64 * p.px * 4;
+    p.plane64 = tiles * 64 * p.px * 8;
+    return p;
+}
 // What ffs_wait asks of the enqueue that runs a batch AGAIN because a plan did not hold it (ffs_wait.hip, rerun_batch); the default
 // is a normal batch.  An argument of that one call: what a stream remembers beyond it (log_off, runs_overflowed, band_backoff) is
 // in ffs_stream.
@@ -459,6 +498,12 @@ int radial_ensure_buffers(ffs_stream* s, uint32_t bins);
 int radial_launch(ffs_stream* s, const void* d_img, size_t pitch, size_t fstride, uint32_t n_frames, hipStream_t st, hipEvent_t start, hipEvent_t stop);
 void radial_publish(ffs_stream* s);
 void radial_free(ffs_stream* s);
+// The per-pixel statistics: the kernel over n_frames frames that are in place in `st`, into the context's accumulators (which exist), with the
+// limit of `max_valid`; start / stop ride on the first and the last dispatch (either may be null).  The caller keeps two launches apart.
+int pixstats_launch(ffs_ctx* c, const void* d_img, size_t pitch, size_t fstride, uint32_t n_frames, long long max_valid, hipStream_t st, hipEvent_t start,
+                    hipEvent_t stop);
+// ffs_context.hip
+int pixstats_ensure(ffs_ctx* c);   // the accumulators and the context's stream, made on first use (contents undefined)
 // ffs_wait.hip
 int ffs_wait_impl(ffs_stream* s, const ffs_frame_result** results, uint32_t* n_results);
 void ahead_register(ffs_stream* s);   // the batch just enqueued may be assembled ahead of its ffs_wait

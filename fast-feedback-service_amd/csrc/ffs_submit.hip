@@ -15,6 +15,7 @@
 #include "kernels_byteoffset.hpp"
 #include "kernels_window.hpp"
 #include "kernels_radial.hpp"
+#include "kernels_pixstats.hpp"
 
 bool chain_prepare_device() {   // more than 64 KB of dynamic LDS has to be asked for, per device
     const hipError_t e1 = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_frame_chain<uint16_t>), hipFuncAttributeMaxDynamicSharedMemorySize, kChainDynBytes);
@@ -911,6 +912,71 @@ static int launch_radial_stage(ffs_stream* s, uint32_t n) {
     if (!radial_wanted(s)) return FFS_OK;
     return launch_radial(s, n, s->st2);
 }
+// ---- the per-pixel statistics (kernels_pixstats.hpp) -----------------------------------------------------------
+int pixstats_launch(ffs_ctx* c, const void* d_img, size_t pitch, size_t fstride, uint32_t n_frames, long long max_valid, hipStream_t st, hipEvent_t start,
+                    hipEvent_t stop) {
+    const PixStatsLayout P = pixstats_layout(c);
+    if (!c->d_stats || n_frames == 0) {
+        c->err = "pixel statistics: the context has no accumulators";
+        return FFS_ERR_INVALID;
+    }
+    PixStatsArgs a{};
+    a.frame_stride = fstride;
+    a.pitch = (uint32_t)pitch;
+    a.groups = P.groups;
+    a.n_lanes = P.n_lanes;
+    // (max_valid under both of its scopes, and p < 2^24 for 32-bit pixels: RadialArgs::limit)
+    a.limit = max_valid >= 0 ? (uint32_t)std::min<long long>(max_valid, (1ll << 24) - 1) + 1u : 1u << 24;
+    a.count = reinterpret_cast<uint4*>(c->d_stats);
+    a.max = reinterpret_cast<uint4*>(c->d_stats + P.plane32);
+    a.sum = reinterpret_cast<uint4*>(c->d_stats + 2 * P.plane32);
+    a.sum_sq = reinterpret_cast<uint4*>(c->d_stats + 2 * P.plane32 + P.plane64);
+    const dim3 grid((P.n_lanes + kPixStatsThreads - 1) / kPixStatsThreads);
+    // (one launch holds at most kPixStatsMaxFrames frames -- the 16-bit kernel's 32-bit sums; a longer batch is several, one behind the other)
+    for (uint32_t f0 = 0; f0 < n_frames; f0 += kPixStatsMaxFrames) {
+        a.image = static_cast<const uint8_t*>(d_img) + (size_t)f0 * fstride;
+        a.n_frames = std::min(n_frames - f0, kPixStatsMaxFrames);
+        const bool first = f0 == 0, last = n_frames - f0 <= kPixStatsMaxFrames;
+        if (c->pixel_bytes == 2) hipExtLaunchKernelGGL(k_pixel_stats<uint16_t>, grid, dim3(kPixStatsThreads), 0, st, first ? start : nullptr, last ? stop : nullptr, 0, a);
+        else hipExtLaunchKernelGGL(k_pixel_stats<uint32_t>, grid, dim3(kPixStatsThreads), 0, st, first ? start : nullptr, last ? stop : nullptr, 0, a);
+    }
+    HIP_TRY(c, hipGetLastError());
+    return FFS_OK;
+}
+
+// The batch's frames into the context's statistics, once: launched by the batch's first enqueue (stats_todo: the re-runs of ffs_wait find it
+// off).  The accumulators belong to the context and every launch reads, adds and writes them whole, so two launches must never overlap,
+// whichever ffs_streams and threads they come from.  Where: tuning "stats_stream".
+//   0: the context's own HIP stream, in which launches follow one another.  It waits for the event behind which the frames are in place --
+//      ev[1], recorded behind the upload or the decode; resident frames (ffs_submit_device) are in place as they come -- so the kernel may run
+//      beside the batch's threshold stage, and the dense stream gets no packet of ours.
+//   1: the batch's dense stream behind the threshold stage's kernels.  Only where that is ONE stream for the whole context: not under
+//      "sched" 0 (a HIP stream per ffs_stream) and not under "dense_overlap" 1 (the stage's kernel may be in the partner stream); 0 is taken there.
+// Either way ev_stats is recorded behind the launch and the batch's sparse stream waits for it ahead of the batch's last event
+// (join_pixel_stats): the frames stay valid until ffs_wait returns, and every waited batch is in what ffs_ctx_get_pixel_stats copies.
+// stats_mu makes wait, launch, record and the frame count one step.
+static int launch_pixel_stats(ffs_stream* s, uint32_t n) {
+    if (!s->stats_todo) return FFS_OK;
+    s->stats_todo = false;
+    if (!s->batch.pixel_stats) return FFS_OK;
+    ffs_ctx* c = s->ctx;
+    if (!s->ev_stats) HIP_TRY(c, hipEventCreateWithFlags(&s->ev_stats, hipEventDisableTiming));
+    const bool dense = c->tune.stats_stream == 1 && s->st2 != s->st && c->tune.dense_overlap == 0;
+    std::lock_guard<std::mutex> lock(c->stats_mu);
+    hipStream_t st = dense ? s->st : c->stats_st;
+    if (!dense && !s->dev_input) HIP_TRY(c, hipStreamWaitEvent(st, s->ev[1], 0));
+    FFS_TRY(pixstats_launch(c, s->cur_img, s->cur_pitch, s->cur_fstride, n, s->batch.params.max_valid, st, nullptr, nullptr));
+    HIP_TRY(c, hipEventRecord(s->ev_stats, st));
+    c->stats_frames += n;
+    s->stats_join = true;
+    return FFS_OK;
+}
+static int join_pixel_stats(ffs_stream* s) {
+    if (!s->stats_join) return FFS_OK;
+    s->stats_join = false;
+    HIP_TRY(s->ctx, hipStreamWaitEvent(s->st2, s->ev_stats, 0));
+    return FFS_OK;
+}
 using ChainKernel = void (*)(ChainArgs);
 static ChainKernel frame_chain_kernel(const BatchPlan& plan, int pixel_bytes) {
     if (plan.use_log) return pixel_bytes == 2 ? k_frame_chain<uint16_t, false, true> : k_frame_chain<uint32_t, false, true>;
@@ -974,6 +1040,7 @@ static int launch_one_launch_stage(ffs_stream* s, const BatchPlan& plan, const C
         s->eplane2_clean = plan.ext_sparse_erode;
     }
     FFS_TRY(launch_radial_stage(s, n));
+    FFS_TRY(join_pixel_stats(s));
     HIP_TRY(c, hipEventRecord(s->ev[4], s->st2));
     s->ev3_is_ev4 = true;
     s->spec_recs_copied = (uint64_t)s->max_batch * s->max_comp;
@@ -1019,6 +1086,7 @@ static int launch_grid_stage(ffs_stream* s, const BatchPlan& plan, const CclArgs
         HIP_TRY(c, hipMemcpyAsync(s->h_recs, s->d_recs, s->spec_recs_copied * sizeof(WireRec2), hipMemcpyDeviceToHost, s->st2));
     }
     FFS_TRY(launch_radial_stage(s, n));
+    FFS_TRY(join_pixel_stats(s));
     HIP_TRY(c, hipEventRecord(s->ev[4], s->st2));
     // the compaction of a streamed batch leaves the plane all zero again; k_union cleared the counts of the frames of this batch (all
     // the streaming kernel touched)
@@ -1034,7 +1102,7 @@ static int launch_sparse_stage(ffs_stream* s, const BatchPlan& plan) {
     s->dense_valid = plan.want_dense_bytes;
     s->occ_dirty = !(ca.use_occ && plan.will_chain);      // nobody consumes (and clears) the bits this batch sets
     s->chain_mode = plan.will_chain;
-    s->path_bits = plan.path_bits | (s->batch.radial_bins ? FFS_PATH_RADIAL : 0u);
+    s->path_bits = plan.path_bits | (s->batch.radial_bins ? FFS_PATH_RADIAL : 0u) | (s->batch.pixel_stats ? FFS_PATH_PIXEL_STATS : 0u);
     return plan.will_chain ? launch_one_launch_stage(s, plan, ca, sa) : launch_grid_stage(s, plan, ca, sa);
 }
 
@@ -1054,6 +1122,7 @@ int enqueue_batch(ffs_stream* s, const void* d_img, size_t pitch, size_t fstride
     FFS_TRY(reset_for_batch(s, plan, dense_resets));
     FFS_TRY(launch_threshold_stage(s, plan, dense_resets, ext_plane_clean));
     FFS_TRY(launch_radial_dense(s, n));
+    FFS_TRY(launch_pixel_stats(s, n));
     return launch_sparse_stage(s, plan);
 }
 
@@ -1075,6 +1144,7 @@ extern "C" int ffs_submit_device(ffs_stream* s, const void* device_pixels, size_
     s->first_id = first_frame_id;
     s->reruns = 0;
     s->radial_todo = true;
+    s->stats_todo = true;
     rc = enqueue_batch(s, device_pixels, pitch, fstride, n_frames);
     if (rc == FFS_OK) ahead_register(s);
     return rc;
@@ -1094,6 +1164,7 @@ extern "C" int ffs_submit(ffs_stream* s, const void* host_pixels, uint32_t n_fra
     const Layout& L = c->L;
     HIP_TRY(c, hipSetDevice(c->device));
     s->radial_todo = true;
+    s->stats_todo = true;
     s->dev_input = false;
     HIP_TRY(c, hipEventRecord(s->ev[0], s->st_up));
     // one 2D copy: the default device layout keeps frames contiguous (frame_stride = H * pitch)
@@ -1407,6 +1478,7 @@ static int ffs_submit_encoded_impl(ffs_stream* s, int codec, const void* const* 
     if (!codec_known(c, codec, "ffs_submit_encoded")) return FFS_ERR_INVALID;
     HIP_TRY(c, hipSetDevice(c->device));
     s->radial_todo = true;
+    s->stats_todo = true;
     s->dev_input = false;
     HIP_TRY(c, hipEventRecord(s->ev[0], s->st_up));
     std::vector<size_t> base;

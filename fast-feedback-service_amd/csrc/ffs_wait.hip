@@ -397,6 +397,7 @@ static int rerun_overflow_frames(ffs_stream* s) {
             // that is alive -- ffs_stack3d_add_batch takes an overflow frame's list from here, tuning "device_lists")
             ParamSnapshot bp = s->batch;
             bp.radial_bins = 0;   // (the batch's profile was computed by its first enqueue)
+            bp.pixel_stats = false;   // (... and its frames were folded into the pixel statistics there)
             if (c->tune.device_lists == 1 || (c->tune.device_lists == 2 && g_live_stacks.load() > 0)) bp.params.want_strong_list = 1;
             int rc = enqueue_batch(b, img, s->cur_pitch, s->cur_fstride, 1, &bp);
             if (rc != FFS_OK) return rc;

@@ -68,6 +68,8 @@ struct Tuning {
     int radial_stream = 0;      // the radial profile's two launches (kernels_radial.hpp): 0 = in the batch's sparse stream behind its sparse launch, 1 = in the
                                 //    dense stream behind the threshold stage's kernels (the A/B partner: DESIGN.md section 3.6 has both measurements)
     int radial_map8 = 0;        // k_radial reads the bin map in one byte an entry where the map has at most 255 bins (1) or always in two (0)
+    int stats_stream = 0;       // the per-pixel statistics' launch (kernels_pixstats.hpp): 0 = in a HIP stream of the context's own, beside the batch's threshold
+                                //    stage, 1 = in the dense stream behind the threshold stage's kernels (the A/B partner: DESIGN.md section 3.7)
 #ifdef FFS_EXPERIMENTS
     struct Exp {
         int k1_debug = 0, chain_skip = 0, chain_stop = 0, dummy_us = 0, dummy_wg = 32, dummy_threads = 1024, dummy_lds = 0;

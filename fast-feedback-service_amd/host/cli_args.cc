@@ -22,7 +22,7 @@ void usage() {
       "                  [-t S] [-fd FD] [-a ALGO] [--dmin MIN D] [--dmax MAX D] [-w \xce\xbb] [--detector JSON]\n"
       "                  [-h5] [--output-for-index] [--batch N] [--cpu-decode] [--strict-dtype]\n"
       "                  [--max-valid trusted|none|N] [--max-valid-scope centre|window] [--min-count N] [--kernel-size N | NX,NY]\n"
-      "                  [--gain G] [--gain-map FILE] [--radial-bins N]\n"
+      "                  [--gain G] [--gain-map FILE] [--radial-bins N] [--pixel-stats PREFIX]\n"
       "                  [--devices D0,D1,... | --gpus N] [--no-numa-pinning] [--single-buffer] [--all-threads] [--read-only] [--clean-exit]\n"
       "--max-valid: a centre pixel above this value is never strong (the reference's kernels test it against the\n"
       "              data set's trusted maximum).  trusted (default) = the frame source's trusted-range maximum when it is\n"
@@ -45,6 +45,12 @@ void usage() {
       "              width in 1/d^2, from the beam centre to the furthest pixel: the background level and its dispersion per shell, as\n"
       "              \"radial_count\", \"radial_sum\" and \"radial_sum_sq\" arrays in every image's JSON line (pixels above --max-valid and\n"
       "              masked pixels, --dmin / --dmax included, are left out).  Needs the detector geometry and the wavelength --dmin needs\n"
+      "--pixel-stats: per pixel over the whole run, in how many images it was at or below --max-valid (32-bit pixels: and below 2^24), the sum\n"
+      "              and the sum of squares of its values there, and the largest of them: what a mask, a gain map (variance / mean of a\n"
+      "              flat run) and the maximum image of a serial run are made from.  Masked pixels are in them.  Written after the last\n"
+      "              image as PREFIX.count.u32, PREFIX.sum.u64, PREFIX.sum_sq.u64 and PREFIX.max.u32: raw little-endian, width x height\n"
+      "              values, row-major, nothing else (the format --gain-map reads).  With several GPUs their statistics are merged: counts\n"
+      "              and sums add, the maximum is the largest\n"
       "--validate:  every image is also decided by an independent path (every valid pixel's window gathered from memory,\n"
       "              no streaming kernel) and the two strong-pixel masks are compared: Match / Mismatch per image\n"
       "--devices / --gpus: one context and worker pool per GPU, all pulling frames from the one queue\n"
@@ -178,6 +184,10 @@ Args parse_args(int argc, char** argv) {
         else if (s == "--gain-map") {
             r.gain_map = need(i, s);
             if (r.gain_map.empty() || !fs::is_regular_file(r.gain_map)) arg_error("--gain-map: no such file: " + r.gain_map);
+        }
+        else if (s == "--pixel-stats") {
+            r.pixel_stats = need(i, s);
+            if (r.pixel_stats.empty()) arg_error("--pixel-stats takes the prefix of the four files it writes");
         }
         else if (s == "--radial-bins") {
             const std::string& v = need(i, s);

@@ -205,6 +205,47 @@ static std::vector<float> read_gain_map(const Args& args, uint32_t width, uint32
     return map;
 }
 
+// --pixel-stats PREFIX, after the last wait: the contexts' statistics merged on the host -- counts and sums add (the sums of squares modulo
+// 2^64, as each context's own), the maximum is the largest -- and written as four raw little-endian files of width x height values.
+static bool write_pixel_stats(const std::string& prefix, const std::vector<ffs_ctx*>& ctxs, uint32_t width, uint32_t height) {
+    const size_t n = (size_t)width * height;
+    std::vector<uint32_t> count(n, 0), max(n, 0), c1, m1;
+    std::vector<uint64_t> sum(n, 0), sum_sq(n, 0), s1, q1;
+    uint64_t frames = 0;
+    for (size_t k = 0; k < ctxs.size(); ++k) {
+        ffs_pixel_stats st{};
+        if (k == 0) {
+            st.count = count.data(); st.sum = sum.data(); st.sum_sq = sum_sq.data(); st.max = max.data();
+        } else {
+            c1.resize(n); m1.resize(n); s1.resize(n); q1.resize(n);
+            st.count = c1.data(); st.sum = s1.data(); st.sum_sq = q1.data(); st.max = m1.data();
+        }
+        FFS_CHECK(ctxs[k], ffs_ctx_get_pixel_stats(ctxs[k], &st));
+        frames += st.n_frames;
+        if (k == 0) continue;
+        for (size_t i = 0; i < n; ++i) {
+            count[i] += c1[i];
+            sum[i] += s1[i];
+            sum_sq[i] += q1[i];
+            max[i] = std::max(max[i], m1[i]);
+        }
+    }
+    auto write = [&](const char* suffix, const void* data, size_t bytes) {
+        const std::string name = prefix + suffix;
+        std::ofstream f(name, std::ios::binary | std::ios::trunc);
+        if (!f || !f.write(static_cast<const char*>(data), (std::streamsize)bytes) || !f.flush()) {
+            std::printf("Error: --pixel-stats: cannot write %s\n", name.c_str());
+            return false;
+        }
+        return true;
+    };
+    if (!write(".count.u32", count.data(), n * 4) || !write(".sum.u64", sum.data(), n * 8) || !write(".sum_sq.u64", sum_sq.data(), n * 8)
+        || !write(".max.u32", max.data(), n * 4))
+        return false;
+    std::printf("Pixel statistics: %llu frames -> %s.{count.u32,sum.u64,sum_sq.u64,max.u32}\n", (unsigned long long)frames, prefix.c_str());
+    return true;
+}
+
 // (--gain-map: the file is held against the frame source's shape as soon as the source is open, ahead of the verdict on the devices -- a
 // usage error is reported as one wherever the driver runs)
 static int open_source_beside_runtime(const Args& args, Stamps& stamp, std::unique_ptr<Reader>& reader, std::vector<float>& gain_map) {
@@ -883,6 +924,9 @@ int main(int argc, char** argv) {
         }
         std::printf("Radial bins: %u shells, d edges (A): %s\n", shells.n_bins, edges.c_str());
     }
+    // --pixel-stats: every context accumulates from its first batch on (the validation contexts see the same frames again, and do not)
+    if (!args.pixel_stats.empty())
+        for (ffs_ctx* cx : ctxs) FFS_CHECK(cx, ffs_ctx_set_pixel_stats(cx, FFS_PIXEL_STATS_START));
     if (args.validate && !create_validation_contexts(devices, ctxs, shape, batch, prm, args.max_valid_scope, args.gain, gain_map, vctxs)) return 1;
     if (args.save_h5 && !h5_supported()) {
         std::printf("Error: --save-h5 needs an HDF5-enabled build\n");
@@ -929,6 +973,7 @@ int main(int argc, char** argv) {
     if (rotation) finish_3d(args, ctx, stack, prm, ex, t_joined);
     else if (args.save_h5) write_2d_h5(report.reflection_centers_2d);
     print_summary(args, shape, pipeline, report, gather.get(), n_dev, all_start, stamp.process_start());
+    if (!args.pixel_stats.empty() && !write_pixel_stats(args.pixel_stats, ctxs, shape.width, shape.height)) return 1;
     pipe.reset();
     exchange.join();
     stamp("timed loop and reports done");

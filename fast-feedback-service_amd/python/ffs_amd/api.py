@@ -74,6 +74,14 @@ class _RadialProfile(C.Structure):   # ffs_radial_profile
 
 
 RADIAL_NO_BIN = 0xFFFF   # a bin-map entry that is in no bin (Context.set_radial_bins)
+
+
+class _PixelStats(C.Structure):   # ffs_pixel_stats
+    _fields_ = [("n_frames", C.c_uint64), ("count", C.POINTER(C.c_uint32)), ("sum", C.POINTER(C.c_uint64)), ("sum_sq", C.POINTER(C.c_uint64)),
+                ("max", C.POINTER(C.c_uint32))]
+
+
+PIXEL_STATS_MODES = {"off": 0, "start": 1, "resume": 2}   # FFS_PIXEL_STATS_OFF / _START / _RESUME
 # ffs_frame_result as a numpy record (offsets taken from the ctypes structure: pointers and padding included)
 _FRAME_RESULT_DT = np.dtype({"names": ["frame_id", "num_strong_pixels", "num_strong_pixels_filtered", "n_components", "n_boxes", "n_reflections"],
                              "formats": ["<i8", "<u4", "<u4", "<u4", "<u4", "<u4"],
@@ -98,6 +106,7 @@ EXPORTS = [
     "ffs_ctx_set_tuning", "ffs_bench_pipeline", "ffs_device_numa_node", "ffs_stream_reserve_host", "ffs_stream_last_path", "ffs_multi_gather_rows",
     "ffs_ctx_set_max_valid_scope", "ffs_ctx_set_gain", "ffs_ctx_set_gain_map",
     "ffs_ctx_set_radial_bins", "ffs_stream_radial_profile", "ffs_bench_radial",
+    "ffs_ctx_set_pixel_stats", "ffs_ctx_get_pixel_stats", "ffs_bench_pixel_stats",
 ]
 
 _lib = None
@@ -127,6 +136,9 @@ def load_library():
         L.ffs_ctx_set_radial_bins.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
         L.ffs_stream_radial_profile.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(_RadialProfile)]
         L.ffs_bench_radial.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_uint32, C.c_uint32, C.POINTER(C.c_float)]
+        L.ffs_ctx_set_pixel_stats.argtypes = [C.c_void_p, C.c_int]
+        L.ffs_ctx_get_pixel_stats.argtypes = [C.c_void_p, C.POINTER(_PixelStats)]
+        L.ffs_bench_pixel_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_uint32, C.c_uint32, C.POINTER(C.c_float)]
         L.ffs_bench_pipeline.argtypes = [C.POINTER(C.c_void_p), C.c_uint32, C.c_void_p, C.c_size_t, C.c_size_t, C.c_uint32,
                                          C.c_uint32, C.c_int64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
         L.ffs_device_numa_node.argtypes = [C.c_int]
@@ -317,6 +329,27 @@ class Context:
             n_bins = int(used.max()) + 1 if used.size else 1
         self._check(self._lib.ffs_ctx_set_radial_bins(self._h, b.ctypes.data_as(C.c_void_p), int(n_bins)))
 
+    def set_pixel_stats(self, mode: str):
+        """ffs_ctx_set_pixel_stats: "start" (zero the per-pixel statistics and accumulate every frame submitted on the context from now
+        on), "off" (stop; the values stay readable; accepted at any time) or "resume" (go on, values kept; a start if there was none).
+        FfsError, state unchanged: "start" while a batch is in flight.  Any other word is a ValueError."""
+        if mode not in PIXEL_STATS_MODES:
+            raise ValueError(f"pixel statistics mode must be one of {sorted(PIXEL_STATS_MODES)}, not {mode!r}")
+        self._check(self._lib.ffs_ctx_set_pixel_stats(self._h, PIXEL_STATS_MODES[mode]))
+
+    def pixel_stats(self, planes=("count", "sum", "sum_sq", "max")):
+        """ffs_ctx_get_pixel_stats: (n_frames, count uint32, sum uint64, sum_sq uint64 modulo 2^64, max uint32), H x W arrays over all frames
+        folded in since the last start; a plane not named in `planes` is None (and is not copied).  FfsError before any start and while a
+        batch is in flight."""
+        out = _PixelStats()
+        arrays = {}
+        for name, dt, ct in (("count", np.uint32, C.c_uint32), ("sum", np.uint64, C.c_uint64), ("sum_sq", np.uint64, C.c_uint64), ("max", np.uint32, C.c_uint32)):
+            if name in planes:
+                arrays[name] = np.zeros((self.H, self.W), dt)
+                setattr(out, name, arrays[name].ctypes.data_as(C.POINTER(ct)))
+        self._check(self._lib.ffs_ctx_get_pixel_stats(self._h, C.byref(out)))
+        return (int(out.n_frames), arrays.get("count"), arrays.get("sum"), arrays.get("sum_sq"), arrays.get("max"))
+
     def set_tuning(self, **kw):
         """ffs_ctx_set_tuning: A/B partners, fall-backs and capacities (same results either way); see include/ffs_hip.h."""
         for k, v in kw.items():
@@ -501,7 +534,7 @@ class Stream:
         self.ctx._check(self._lib.ffs_stream_timings(self._h, t))
         return dict(zip(("h2d", "threshold", "ccl", "d2h", "total"), list(t)))
 
-    PATH_BITS = {"wave_logs": 1, "frame_chain": 2, "bands": 4, "runs": 8, "grid_kernels": 16, "extended": 32, "window": 64, "radial": 128}
+    PATH_BITS = {"wave_logs": 1, "frame_chain": 2, "bands": 4, "runs": 8, "grid_kernels": 16, "extended": 32, "window": 64, "radial": 128, "pixel_stats": 256}
 
     def last_path(self):
         """ffs_stream_last_path: (set of the launches the last batch took, times ffs_wait ran it again)."""
@@ -530,6 +563,13 @@ class Stream:
         """ffs_bench_radial: average ms of one batch's radial profile (its two launches), alone on resident frames."""
         ms = C.c_float()
         self.ctx._check(self._lib.ffs_bench_radial(self._h, C.c_void_p(dev_ptr), pitch_bytes, frame_stride_bytes, n_frames, iters, C.byref(ms)))
+        return ms.value
+
+    def bench_pixel_stats(self, dev_ptr: int, pitch_bytes: int, frame_stride_bytes: int, n_frames: int, iters: int) -> float:
+        """ffs_bench_pixel_stats: average ms of one batch's per-pixel statistics launch, alone on resident frames.  Uses the context's
+        accumulators and leaves them undefined: FfsError while accumulation is on or a batch is in flight."""
+        ms = C.c_float()
+        self.ctx._check(self._lib.ffs_bench_pixel_stats(self._h, C.c_void_p(dev_ptr), pitch_bytes, frame_stride_bytes, n_frames, iters, C.byref(ms)))
         return ms.value
 
     def bench_hbm(self, iters: int = 5):

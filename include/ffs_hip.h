@@ -251,6 +251,56 @@ int ffs_ctx_set_gain_map(ffs_ctx *ctx, const float *host_gain);
  *     the batch in flight goes on with the map it was submitted with, which stays on the device, and hands out its profile. */
 int ffs_ctx_set_radial_bins(ffs_ctx *ctx, const uint16_t *bin_of_pixel, uint32_t n_bins);
 
+/* Per-pixel statistics over a run: count, sum, sum of squares and maximum of every pixel over all frames the context sees -- what a
+ * valid-pixel mask (dead pixels: mean 0; hot pixels: a mean far above the neighbours'), a gain map (variance / mean over a flat run) and
+ * the maximum image of a serial run (the "virtual powder pattern") are made from; dxtbx.image_average produces the same three images on
+ * the host.  The reference has no counterpart.  Accumulated on the device from the frames a batch has there anyway.
+ *   While accumulation is on, every frame of every batch submitted on the context -- through ffs_submit, ffs_submit_device,
+ *   ffs_submit_compressed or ffs_submit_encoded, on any of its streams -- is folded into four W x H accumulators.
+ *   A pixel value p of a frame COUNTS at (x, y) when both of these hold:
+ *     - p <= max_valid when ffs_params.max_valid >= 0 for that batch, under both scopes of max_valid;
+ *     - for 32-bit pixels, p < 2^24 (the rule of the radial profile).
+ *   Unlike the radial profile, the valid-pixel mask plays no part: the statistics are what a mask is made from, so masked pixels are in them.
+ *   Per pixel:
+ *     count  (uint32) the number of frames in which the pixel counted;
+ *     sum    (uint64) the sum of p over those frames;
+ *     sum_sq (uint64) the sum of p*p over them, taken modulo 2^64: it can wrap only for 32-bit pixels, and only after more than 65 536
+ *            frames near 2^24;
+ *     max    (uint32) the largest counted p; 0 when count is 0.
+ *   Per context: n_frames (uint64), the frames folded in since the last start; n_frames - count is how often a pixel was above the limit.
+ *   All of these are integers: the result is bit for bit independent of batch size, stream, order, path and tuning.
+ *   The result is state of the CONTEXT, accumulated across batches and across all of its streams, not an output of a batch.  A batch takes
+ *   the on / off state as it is at submit.  A batch that ffs_wait runs again (all of it, or single frames) counts once.  ffs_decode_only*
+ *   and the ffs_bench_* entries fold nothing in, except ffs_bench_pixel_stats -- and ffs_bench_pipeline, which IS ffs_submit_device and
+ *   ffs_wait in a loop and folds as they do (how the cost of accumulating is measured in the pipeline).  If a batch's ffs_wait fails (a corrupt chunk, say) the
+ *   statistics are undefined: start again.
+ * Modes:
+ *   FFS_PIXEL_STATS_OFF     stop; the accumulated values stay readable.  Accepted at any time: a batch in flight that was submitted
+ *                           under "on" still counts.
+ *   FFS_PIXEL_STATS_START   allocate on first use, zero all four planes and n_frames, on.
+ *   FFS_PIXEL_STATS_RESUME  on, values kept (START if never started).
+ * The accumulators are 24 bytes per pixel (434 MB on Eiger-16M), allocated at the first start and freed with the context; a failed
+ * allocation is FFS_ERR_NOMEM.
+ * FFS_ERR_INVALID, state unchanged (ffs_last_error has the text):
+ *   - any other mode;
+ *   - START (or a RESUME that is one) while any stream of the context has a batch between submit and ffs_wait. */
+#define FFS_PIXEL_STATS_OFF 0
+#define FFS_PIXEL_STATS_START 1
+#define FFS_PIXEL_STATS_RESUME 2
+int ffs_ctx_set_pixel_stats(ffs_ctx *ctx, int mode);
+
+/* Copies the statistics out: each of the four pointers is caller-owned, dense, W*H entries, row-major, and may be NULL (that plane is
+ * not copied); n_frames is always written.  Complete for every batch ffs_wait has returned: FFS_ERR_INVALID, nothing written, before any
+ * start and while any stream of the context has a batch in flight.  Accumulation may be on or off, and stays as it is. */
+typedef struct {
+    uint64_t n_frames;   /* out */
+    uint32_t *count;
+    uint64_t *sum;
+    uint64_t *sum_sq;
+    uint32_t *max;
+} ffs_pixel_stats;
+int ffs_ctx_get_pixel_stats(ffs_ctx *ctx, ffs_pixel_stats *out);
+
 /* Selects between paths that give the SAME results (A/B partners, fall-backs, capacities that tests shrink) --
  * per context, never through the environment; nothing here can change a result.  Keys (default):
  *   "threshold_path"   (0) 0 = windows the streaming kernel cannot vouch for go onto a list (fix-up kernel),
@@ -296,6 +346,10 @@ int ffs_ctx_set_radial_bins(ffs_ctx *ctx, const uint16_t *bin_of_pixel, uint32_t
  *                          launch, 1 = in the dense stream behind the threshold stage's kernels (measured 11 % slower in the pipeline: the A/B partner).
  *                          1 is taken as 0 where there is no dense stream to tell from the sparse one ("sched" 0: one HIP stream per
  *                          ffs_stream) and under "dense_overlap" 1 (the stage's kernel may be in the dense stream's partner)
+ *   "stats_stream"     (0) the per-pixel statistics' launch (ffs_ctx_set_pixel_stats): 0 = in a HIP stream of the context's own, beside the
+ *                          batch's threshold stage, 1 = in the dense stream behind the threshold stage's kernels (the A/B partner).  1 is taken
+ *                          as 0 under "sched" 0 and under "dense_overlap" 1, where the dense stream is not one stream for the whole context.
+ *                          Accepted only while no batch of the context is in flight
  *   "radial_map8"      (0) the radial profile reads a bin map of at most 255 bins in one byte an entry (1) instead of two (0): DESIGN.md section 3.6
  *                          has the measurement
  *   "assembly_threads" (7: helper threads that build a batch's result arrays; 3, 12 and 15 measure the same): see DESIGN.md.
@@ -411,6 +465,7 @@ int ffs_stream_timings(ffs_stream *s, float ms[5]);
 #define FFS_PATH_EXTENDED 32u      /* extended dispersion */
 #define FFS_PATH_WINDOW 64u        /* the general-window threshold kernel (a window other than 3,3, or tuning "window_kernel" = 1) */
 #define FFS_PATH_RADIAL 128u       /* the batch computed a radial profile (ffs_ctx_set_radial_bins) */
+#define FFS_PATH_PIXEL_STATS 256u  /* the batch was folded into the per-pixel statistics (ffs_ctx_set_pixel_stats) */
 int ffs_stream_last_path(ffs_stream *s, uint32_t *path_bits, uint32_t *reruns);
 
 /* The radial profile (ffs_ctx_set_radial_bins) of frame `frame_in_batch` of the last batch ffs_wait returned on this stream: n_bins
@@ -450,6 +505,11 @@ int ffs_bench_threshold(ffs_stream *s, const void *device_pixels, size_t pitch_b
  * profile ffs_stream_radial_profile hands out is not touched.  (No counterpart in the reference.) */
 int ffs_bench_radial(ffs_stream *s, const void *device_pixels, size_t pitch_bytes, size_t frame_stride_bytes,
                      uint32_t n_frames, uint32_t iters, float *ms);
+/* Runs the per-pixel statistics' kernel alone on device-resident frames, `iters` times, and returns the average duration of one batch's
+ * launch from HIP events that ride on the dispatch.  It uses the context's own accumulators (allocated here if need be) and leaves them
+ * undefined: FFS_ERR_INVALID while accumulation is on or a batch of the context is in flight.  (No counterpart in the reference.) */
+int ffs_bench_pixel_stats(ffs_stream *s, const void *device_pixels, size_t pitch_bytes, size_t frame_stride_bytes,
+                          uint32_t n_frames, uint32_t iters, float *ms);
 /* The submit / wait loop of a resident-frames benchmark, natively: `steps` batches of the same device-resident
  * frames through `n_streams` streams of ONE context, all of them in flight (ffs_submit_device / ffs_wait).  For
  * drivers with one host thread per GPU (bench.py --single-process, the threading model of
