@@ -342,7 +342,19 @@ static int rebuild_mask_tables(ffs_ctx* c) {
         hipLaunchKernelGGL(k_build_maps4, dim3((groups + 255) / 256, L.H), dim3(256), 0, 0, c->d_maskbits, L.mpitch, L.W, L.H,
                            L.pitch_px, c->d_mmap, c->d_ginfo, gpitch);
     HIP_TRY(c, hipGetLastError());
+    // ... and the runs of rows without a valid pixel, which the streaming waves trim off their bands' ends: a flag per row from the plane
+    // (the resolution mask is made on the device), H bytes back, the runs on the host.  Once per mask.
+    c->empty_runs = EmptyRuns{};
+    uint8_t* d_flags = nullptr;
+    HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&d_flags), (size_t)L.H));
+    hipLaunchKernelGGL(k_row_flags, dim3((unsigned)L.H), dim3(64), 0, 0, c->d_maskbits, L.mpitch, L.H, d_flags);
+    std::vector<uint8_t> flags((size_t)L.H, 1);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpy(flags.data(), d_flags, flags.size(), hipMemcpyDeviceToHost);
+    (void)hipFree(d_flags);
+    HIP_TRY(c, e);
     HIP_TRY(c, hipDeviceSynchronize());
+    c->empty_runs = empty_runs_of(flags.data(), L.H);
     return FFS_OK;
 }
 

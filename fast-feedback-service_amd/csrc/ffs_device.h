@@ -80,7 +80,6 @@ struct ThresholdArgs {
     int gpf;                   // lane groups per frame row = ceil(W / 8)
     int n_frames;              // frames of this launch
     int group_frames;          // frames laid side by side in one super row (group bytes < 2 GiB)
-    int s_strips, s_band_rows, s_bands;
     uint32_t* bright_n;        // [1] pixels handed to k_bright_fix (window sum >= 65536)
     uint2* bright_list;        // [bright_cap] (frame << 16 | x, y)
     uint32_t bright_cap;
@@ -119,6 +118,10 @@ struct ThresholdArgs {
     // has gain = 0, w_kS without a gain inside (the kernel multiplies by the pixel's) and g_gain unused; g_nb = 0 = nsig_b outside the screen's range.
     const float* gain_map;
     uint32_t gm_pitch;
+    // the runs of rows the mask leaves without a valid pixel (launch_geometry.hpp: empty_runs_of, built with the mask tables): the waves of
+    // the streaming kernels trim them off their band's two ends (trim_band).  By value, so a launch carries the runs of the mask its
+    // tables were built from.
+    EmptyRuns empty_runs;
 };
 // the gain-map entry of pixel (x, y), 0 <= x < pitch_px
 __device__ __forceinline__ float gain_at(const ThresholdArgs& a, int x, int y) {

@@ -159,6 +159,7 @@ struct ffs_ctx {
     uint8_t* d_maskbits = nullptr;
     uint8_t* d_ginfo = nullptr;  // per-group mask bits + window-count bounds (kernels_stream.hpp)
     uint8_t* d_mmap = nullptr;   // per-pixel window counts
+    EmptyRuns empty_runs{};      // the rows the mask leaves empty (launch_geometry.hpp), rebuilt with the two tables above; every launch's arguments carry a copy
     hipStream_t dense_st = nullptr;  // sched 3: the one stream of the dense kernels
     // ... and its partner (tuning "dense_overlap", off: measured slower in the pipeline): the streaming kernels of the wave-log path take
     // the two alternately, each behind a wait for the value the previous launch's last workgroup writes into `d_handoff` (signal

@@ -138,7 +138,8 @@ static void set_predicate(ThresholdArgs& a, const ffs_params& p, bool trusted, d
     }
 }
 // (launch_geometry.hpp computes them; the super rows of the streaming launch, g.n_groups, are its grid's y and no argument)
-static void set_geometry(ThresholdArgs& a, uint32_t n_frames, const StreamGeometry& g, const WindowGeometry& w, const ExtGeometry& e) {
+static void set_geometry(ThresholdArgs& a, uint32_t n_frames, const StreamGeometry& g, const WindowGeometry& w, const ExtGeometry& e, const EmptyRuns& empty) {
+    a.empty_runs = empty;   // (what the streaming waves trim off their bands' ends: the geometry itself does not depend on the mask)
     a.n_frames = (int)n_frames;
     a.group_frames = g.group_frames;
     a.n_strips = g.n_strips;
@@ -161,7 +162,7 @@ ThresholdArgs make_threshold_args(ffs_stream* s, const void* img, size_t pitch, 
     ThresholdArgs a{};
     set_buffers(a, s, img, pitch, fstride, route);
     set_predicate(a, s->batch.params, route.window_scope, s->batch.gain, s->batch.gain_map ? s->ctx : nullptr);
-    set_geometry(a, n_frames, g, window_geometry(s->ctx->L, n_frames, a.ky), ext_geometry(s->ctx->L, n_frames));
+    set_geometry(a, n_frames, g, window_geometry(s->ctx->L, n_frames, a.ky), ext_geometry(s->ctx->L, n_frames), s->ctx->empty_runs);
     return a;
 }
 

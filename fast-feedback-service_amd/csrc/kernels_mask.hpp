@@ -73,6 +73,17 @@ __global__ __launch_bounds__(256) void k_build_maps4(const uint8_t* maskbits, ui
     ginfo[(uint64_t)(y + kInfoExtraRows) * gpitch_bytes + g * 4 + 3] = (uint8_t)own;
 }
 
+// flags[y] = 1 where row y of the valid-pixel plane holds a valid pixel (the plane's bits for x >= W are never set): what the empty-row
+// runs are made from (launch_geometry.hpp, empty_runs_of).  One wave per row; mpitch is a multiple of 16.
+__global__ __launch_bounds__(64) void k_row_flags(const uint8_t* maskbits, uint32_t mpitch, int H, uint8_t* flags) {
+    const int y = blockIdx.x;
+    if (y >= H) return;
+    const uint32_t* row = reinterpret_cast<const uint32_t*>(maskbits + (uint64_t)y * mpitch);
+    uint32_t any = 0;
+    for (uint32_t w = threadIdx.x; w < mpitch / 4; w += 64) any |= row[w];
+    const unsigned long long m = __ballot(any != 0u);
+    if (threadIdx.x == 0) flags[y] = m != 0ull ? 1 : 0;
+}
 
 // Resolution mask: spotfinder/kernels/masking.cu:37-73 (float32 distance / d-spacing), :99-147.
 // One thread per mask byte (8 pixels); only clears bits, as the reference only ever masks.

@@ -179,15 +179,24 @@ __global__ __launch_bounds__(64, 4) void k_stream_u16(const ThresholdArgs a) {
     [[maybe_unused]] const uint32_t slot = log_slot(a, blockIdx.y, (uint32_t)band, (uint32_t)strip);   // where this wave's log lies
     const int f0 = blockIdx.y * a.group_frames;                   // first frame of this super row
     const int nf = min(a.group_frames, a.n_frames - f0);
-    const int yb0 = band_first_row(band, a.band_rows, a.band_rows2, a.band_split);
-    const int yb1 = min(band_first_row(band + 1, a.band_rows, a.band_rows2, a.band_split), a.H);
+    // The band's rows, without the rows at its two ends that the mask leaves empty (launch_geometry.hpp, trim_band: scalar, once per
+    // wave).  The wave loads rows yb0 - 3 .. yb1 + 2 and decides rows yb0 .. yb1 - 1 as before; the rows it no longer runs hold no valid
+    // pixel, so none of them is strong and the windows that reach into them see zeros either way.  DENSE keeps the whole band: it
+    // zero-fills the byte mask row by row, and a row left out would keep the bytes of the batch before.
+    const int band0 = band_first_row(band, a.band_rows, a.band_rows2, a.band_split);
+    const int band1 = min(band_first_row(band + 1, a.band_rows, a.band_rows2, a.band_split), a.H);
+    const BandRows rows = DENSE ? BandRows{band0, band1} : trim_band(a.empty_runs, band0, band1);
+    const int yb0 = rows.yb0, yb1 = rows.yb1;
+    // A band without a valid row (yb0 == yb1): no lane is active, so every load is out of its buffer's range and reads nothing; the wave
+    // falls through its six warm-up rows and writes its empty log's count at the end like any other (k_band_cc reads every slot's).  No
+    // early return: a branch here split the prologue and cost the row loop three more spilled SGPRs.
 
     // lane -> (frame, group) in the super row; group a.gpf of every frame is the empty separator
     const int gsep = a.gpf + 1;
     const int G = strip * kSOwned + lane - 1;
     const int fl = G >= 0 ? G / gsep : 0;
     const int g = G - fl * gsep;
-    const bool active = G >= 0 && fl < nf && g < a.gpf;
+    const bool active = G >= 0 && fl < nf && g < a.gpf && yb0 != yb1;   // (yb0 == yb1: the band has no valid row, the wave loads nothing)
     const bool owned = active && lane >= 1 && lane <= kSOwned;
     const uint32_t my_fg = ((uint32_t)fl << 16) | (uint32_t)g;   // travels with every group this lane queues
 
@@ -719,14 +728,18 @@ __global__ __launch_bounds__(64, 4) void k_stream_u32(const ThresholdArgs a) {
     const uint32_t slot = log_slot(a, blockIdx.y, (uint32_t)band, (uint32_t)strip);
     const int f0 = blockIdx.y * a.group_frames;
     const int nf = min(a.group_frames, a.n_frames - f0);
-    const int yb0 = band_first_row(band, a.band_rows, a.band_rows2, a.band_split);
-    const int yb1 = min(band_first_row(band + 1, a.band_rows, a.band_rows2, a.band_split), a.H);
+    // (the band without the empty rows at its two ends: see k_stream_u16.  `bighist` stays right: it is carried by the ring slots, which
+    // are still filled from row yb0 - 3 on, and a row left out holds no valid pixel, so none >= 2^24 that a window would have to know of)
+    const int band0 = band_first_row(band, a.band_rows, a.band_rows2, a.band_split);
+    const int band1 = min(band_first_row(band + 1, a.band_rows, a.band_rows2, a.band_split), a.H);
+    const BandRows rows = DENSE ? BandRows{band0, band1} : trim_band(a.empty_runs, band0, band1);
+    const int yb0 = rows.yb0, yb1 = rows.yb1;
 
     const int gsep = a.gpf + 1;   // a.gpf = groups of four pixels per frame row
     const int G = strip * kSOwned + lane - 1;
     const int fl = G >= 0 ? G / gsep : 0;
     const int g = G - fl * gsep;
-    const bool active = G >= 0 && fl < nf && g < a.gpf;
+    const bool active = G >= 0 && fl < nf && g < a.gpf && yb0 != yb1;   // (yb0 == yb1: the band has no valid row, the wave loads nothing)
     const bool owned = active && lane >= 1 && lane <= kSOwned;
 
     const rsrc_t r_img = make_rsrc((const uint8_t*)a.image + (uint64_t)f0 * a.frame_stride,

@@ -8,6 +8,7 @@
 
 #include <algorithm>
 #include <cmath>
+#include <utility>
 
 #include "tuning.hpp"
 
@@ -211,6 +212,62 @@ FFS_HD inline bool stream_unit_of(uint32_t bid, int n_bands, int n_strips, int& 
 // where the log of (super row y, band, strip) lies in wlog / wlog_n / wpix: the strips of a band side by side
 FFS_HD inline uint32_t log_slot_of(int n_bands, int n_strips, uint32_t y, uint32_t band, uint32_t strip) {
     return (y * (uint32_t)n_bands + band) * (uint32_t)n_strips + strip;
+}
+
+// ---- the rows a mask leaves empty: what a streaming wave trims off its band's two ends ----------------------------------
+// A row without a valid pixel has no strong pixel (a masked centre never passes the predicate), and to the windows of its neighbours
+// it is a row of zeros whether it is loaded or not.  A wave of the streaming kernels therefore starts at its band's first row WITH a
+// valid pixel and stops behind the last one: the geometry above -- bands, grid, log slots -- stays what it
+// is, the wave only runs fewer rows.  The runs travel by value in the kernel arguments (ThresholdArgs::empty_runs), per launch.
+constexpr int kEmptyRunSlots = 16;
+struct EmptyRuns {
+    uint32_t n;                          // runs kept
+    uint16_t run[kEmptyRunSlots][2];     // (first row, end row), end exclusive; sorted by first row; the slots behind n are (0, 0), which cover nothing
+};
+// The kEmptyRunSlots longest maximal runs of rows with flags[y] == 0, sorted by first row.  Keeping
+// fewer runs than the mask has is always correct: it only trims less.  Frames taller than the 16-bit rows hold: no runs.
+inline EmptyRuns empty_runs_of(const uint8_t* flags, int H) {
+    EmptyRuns r{};
+    if (H > 65535) return r;
+    for (int y = 0; y < H;) {
+        if (flags[y]) { ++y; continue; }
+        int end = y;
+        while (end < H && !flags[end]) ++end;
+        int at = (int)r.n;
+        if (at == kEmptyRunSlots) {   // full: in place of the shortest kept run, where this one is longer
+            at = 0;
+            for (int k = 1; k < kEmptyRunSlots; ++k)
+                if (r.run[k][1] - r.run[k][0] < r.run[at][1] - r.run[at][0]) at = k;
+            if (end - y <= r.run[at][1] - r.run[at][0]) at = -1;
+        } else {
+            ++r.n;
+        }
+        if (at >= 0) { r.run[at][0] = (uint16_t)y; r.run[at][1] = (uint16_t)end; }
+        y = end;
+    }
+    for (int i = 1; i < (int)r.n; ++i)   // by first row (insertion sort: at most 16 entries)
+        for (int k = i; k > 0 && r.run[k][0] < r.run[k - 1][0]; --k) {
+            std::swap(r.run[k][0], r.run[k - 1][0]);
+            std::swap(r.run[k][1], r.run[k - 1][1]);
+        }
+    return r;
+}
+// Rows yb0 .. yb1 - 1 of a band without the kept runs that cover its first and its last row: [yb0', yb1') inside the band, every row
+// of the band with a valid pixel inside it; a band without one gives yb0' == yb1'.  One pass each way: the runs are sorted, so a raised
+// yb0 can only fall into a later run and a lowered yb1 into an earlier one.  Scalar arithmetic on 16 argument words, once per wave.
+struct BandRows { int yb0, yb1; };
+FFS_HD inline BandRows trim_band(const EmptyRuns& r, int yb0, int yb1) {
+    if (yb0 >= yb1) return {yb0, yb1};
+    int lo = yb0, hi = yb1;
+    if (r.n != 0) {   // (a mask without an empty row -- most detectors' -- pays one compare)
+        for (int k = 0; k < kEmptyRunSlots; ++k)
+            if ((int)r.run[k][0] <= lo && lo < (int)r.run[k][1]) lo = (int)r.run[k][1];
+        for (int k = kEmptyRunSlots - 1; k >= 0; --k)
+            if ((int)r.run[k][0] < hi && hi <= (int)r.run[k][1]) hi = (int)r.run[k][0];
+    }
+    lo = lo < yb1 ? lo : yb1;
+    hi = hi > lo ? hi : lo;
+    return {lo, hi};
 }
 
 }  // namespace ffsamd
