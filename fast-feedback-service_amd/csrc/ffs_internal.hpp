@@ -7,6 +7,7 @@
 //                    (kernels_stream / threshold / extended / window / ccl / chain / band / decode)
 //   ffs_wait.hip     ffs_wait: overflow re-runs (rerun_batch: the same batch again with a Rerun override), result assembly,
 //                    result accessors
+//   ffs_spotbg.hip   ffs_stream_spot_backgrounds: the per-spot constant background of the last waited batch (kernels_spotbg.hpp)
 //   ffs_stack3d.hip  rotation sweeps: the device-resident 3D stack and the exchange between GPUs (kernels_stack3d)
 //   ffs_bench.hip    measurement entry points (kernel timings, memory ceiling, native pipeline loop, sqrt self-test)
 // Without HIP, shared with the kernels through ffs_device.h and compiled by a plain C++ test (tests/launch_geometry_check.cc):
@@ -15,6 +16,7 @@
 //   threshold_route.hpp  the predicate's variants, which instantiation of a kernel family serves one, and a batch's route through the
 //                        threshold stage (tests/threshold_route_check.cc)
 //   tuning.hpp           struct Tuning
+//   spot_background_model.hpp  the decisions of the per-spot background: quartile positions, status order, fence (tests/spot_background_check.cc)
 // No exception leaves the library (guarded()).
 #pragma once
 #include <algorithm>
@@ -317,6 +319,17 @@ struct ffs_stream {
     // the batch's sparse stream, which waits for ev_stats (recorded behind it, made on first use) ahead of the batch's last event.
     bool stats_todo = false, stats_join = false;
     hipEvent_t ev_stats = nullptr;
+    // The per-spot backgrounds (ffs_spotbg.hip, kernels_spotbg.hpp), all made by the first ffs_stream_spot_backgrounds
+    // on the stream: a non-blocking HIP stream of the ffs_stream's own with two events around its launch, the boxes of the last batch's
+    // reflections (pinned host, written by the call, and their copy on the device) and the records the kernel writes straight into pinned host
+    // memory -- room for bg_cap reflections each, grown when a batch has more.  waited_ok: the last ffs_wait on the stream returned FFS_OK,
+    // so results / refls / cur_img describe one batch (ffs_wait_impl sets it; ffs_decode_only*, which overwrite the stream's frames, clear it).
+    bool waited_ok = false;
+    hipStream_t bg_st = nullptr;
+    hipEvent_t bg_ev[2] = {nullptr, nullptr};
+    void *h_bg_boxes = nullptr, *d_bg_boxes = nullptr;
+    ffs_spot_background *h_bg_out = nullptr, *h_bg_out_dev = nullptr;
+    uint32_t bg_cap = 0;
     // state of the batch in flight
     bool busy = false;
     uint32_t n_frames = 0;
@@ -510,6 +523,8 @@ int ffs_wait_impl(ffs_stream* s, const ffs_frame_result** results, uint32_t* n_r
 void ahead_register(ffs_stream* s);   // the batch just enqueued may be assembled ahead of its ffs_wait
 int ahead_take(ffs_stream* s);        // waits for the AheadThread to be done with the stream's batch; its verdict (0, 2 or 3), state reset
 void ahead_stop(ffs_ctx* c, bool destroy);   // the thread leaves and is joined (context destroy, process exit)
+// ffs_spotbg.hip
+void spotbg_free(ffs_stream* s);   // the stream's own HIP stream, events and buffers of ffs_stream_spot_backgrounds, if it was ever called
 // ffs_stack3d.hip
 void stack3d_free(ffs_stack3d* st);
 void gather_scratch_free(ffs_stream* s);   // what ffs_multi_gather_rows allocated for the stream, if anything

@@ -1549,6 +1549,7 @@ extern "C" int ffs_decode_only_encoded(ffs_stream* s, int codec, const void* con
     if (!codec_known(c, codec, "ffs_decode_only_encoded")) return FFS_ERR_INVALID;
     const Layout& L = c->L;
     HIP_TRY(c, hipSetDevice(c->device));
+    s->waited_ok = false;   // (the decoded frames replace the last batch's in the stream's image buffer: ffs_stream_spot_backgrounds has nothing to read)
     std::vector<size_t> base;
     int rc = stage_chunks(s, codec, chunks, chunk_bytes, n_frames, base);
     uint32_t bo_max_tiles = 0;

@@ -538,6 +538,7 @@ int ffs_wait_impl(ffs_stream* s, const ffs_frame_result** results, uint32_t* n_r
         c->err = "ffs_wait: nothing submitted";
         return FFS_ERR_INVALID;
     }
+    s->waited_ok = false;   // (until this wait has handed the batch out: ffs_stream_spot_backgrounds reads it)
     HIP_TRY(c, hipSetDevice(c->device));
     int rc = join_compressed_job(s);
     if (rc != FFS_OK) return rc;
@@ -580,6 +581,7 @@ int ffs_wait_impl(ffs_stream* s, const ffs_frame_result** results, uint32_t* n_r
         }
     }
     radial_publish(s);
+    s->waited_ok = true;
     if (results) *results = s->results.data();
     if (n_results) *n_results = s->n_frames;
     return FFS_OK;

@@ -23,6 +23,7 @@ void usage() {
       "                  [-h5] [--output-for-index] [--batch N] [--cpu-decode] [--strict-dtype]\n"
       "                  [--max-valid trusted|none|N] [--max-valid-scope centre|window] [--min-count N] [--kernel-size N | NX,NY]\n"
       "                  [--gain G] [--gain-map FILE] [--radial-bins N] [--pixel-stats PREFIX]\n"
+      "                  [--spot-background B]\n"
       "                  [--devices D0,D1,... | --gpus N] [--no-numa-pinning] [--single-buffer] [--all-threads] [--read-only] [--clean-exit]\n"
       "--max-valid: a centre pixel above this value is never strong (the reference's kernels test it against the\n"
       "              data set's trusted maximum).  trusted (default) = the frame source's trusted-range maximum when it is\n"
@@ -51,6 +52,13 @@ void usage() {
       "              image as PREFIX.count.u32, PREFIX.sum.u64, PREFIX.sum_sq.u64 and PREFIX.max.u32: raw little-endian, width x height\n"
       "              values, row-major, nothing else (the format --gain-map reads).  With several GPUs their statistics are merged: counts\n"
       "              and sums add, the maximum is the largest\n"
+      "--spot-background: per spot, the constant background of the ring of B (1..16) pixels around its bounding box -- the valid pixels of the\n"
+      "              padded box outside the box itself (masked pixels, --dmin / --dmax included, and pixels above --max-valid are left out), an\n"
+      "              integer histogram of 256 bins, Tukey's fence q1 - 1.5 IQR .. q3 + 1.5 IQR, the mean of what is inside -- and the\n"
+      "              background-subtracted intensity: \"spot_background_mean\", \"spot_intensity\" (sum - pixels x mean) and \"spot_variance\"\n"
+      "              arrays in every image's JSON line, one entry per spot left after both filters, null where the ring gives no estimate\n"
+      "              (no valid pixel, more than a quarter of it at or above 256, or a fence that reaches 256), and \"total_intensity\", the sum\n"
+      "              of the image's estimated intensities.  Assumes photon counts (no gain is applied)\n"
       "--validate:  every image is also decided by an independent path (every valid pixel's window gathered from memory,\n"
       "              no streaming kernel) and the two strong-pixel masks are compared: Match / Mismatch per image\n"
       "--devices / --gpus: one context and worker pool per GPU, all pulling frames from the one queue\n"
@@ -188,6 +196,11 @@ Args parse_args(int argc, char** argv) {
         else if (s == "--pixel-stats") {
             r.pixel_stats = need(i, s);
             if (r.pixel_stats.empty()) arg_error("--pixel-stats takes the prefix of the four files it writes");
+        }
+        else if (s == "--spot-background") {
+            const std::string& v = need(i, s);
+            r.spot_background = u32(v, s);
+            if (r.spot_background < 1 || r.spot_background > 16) arg_error("--spot-background takes a border in 1..16: " + v);
         }
         else if (s == "--radial-bins") {
             const std::string& v = need(i, s);

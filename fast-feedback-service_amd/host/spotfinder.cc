@@ -431,6 +431,7 @@ static ffs_params make_params(const Args& args, bool rotation, int64_t max_valid
     prm.min_spot_size_3d = args.min_spot_size_3d;
     prm.max_peak_centroid_separation = args.max_sep;
     prm.want_reflections = (!rotation && (args.save_h5 || args.output_for_index)) ? 1 : 0;
+    if (args.spot_background) prm.want_reflections = 1;   // (the spots whose backgrounds are measured are the reflections left after both filters)
     prm.want_strong_mask = args.writeout ? 1 : 0;
     prm.algorithm = args.algo;
     prm.max_valid = max_valid;
@@ -619,6 +620,16 @@ class BatchReport {
             for (uint32_t i = 0; i < nres; ++i) my_rows += res[i].n_reflections;
             round_rows = gather_->rows_of(batch.gpu, batch.q, batch.stream, my_rows);
         }
+        // --spot-background: the batch's backgrounds, once, between its wait and the stream's next submit (the collector releases the batch's
+        // assembly only after this callback); image i's entries follow image i - 1's, n_reflections each
+        const ffs_spot_background* backgrounds = nullptr;
+        if (args_.spot_background) {
+            uint32_t n_bg = 0;
+            if (ffs_stream_spot_backgrounds(batch.stream, args_.spot_background, &backgrounds, &n_bg, nullptr) != FFS_OK) {
+                std::printf("Error: %s\n", ffs_last_error(ctxs_[batch.gpu]));
+                return false;
+            }
+        }
         // what this batch prints and sends goes out in one piece each (the collector is the one thread between the GPU and a
         // free staging area: a printf and a write per image, into pipes a Python caller drains, were on that path)
         std::string text, json_lines;
@@ -637,7 +648,8 @@ class BatchReport {
                 std::lock_guard<std::mutex> lock(centers_mutex_);
                 reflection_centers_2d[image_num + args_.start_index] = std::move(coms);
             }
-            if (pipe_) append_json(r, batch.stream, i, round_rows, json_lines);
+            if (pipe_) append_json(r, batch.stream, i, round_rows, backgrounds, json_lines);
+            if (backgrounds) backgrounds += r.n_reflections;
             append_text(r, batch.validation ? &batch.validation[i] : nullptr, batch, text);
         }
         if (pipe_ && !json_lines.empty()) pipe_->send_lines(json_lines);
@@ -661,11 +673,36 @@ class BatchReport {
         }
         return c + "]" + s + "]" + q + "]";
     }
-    void append_json(const ffs_frame_result& r, ffs_stream* stream, uint32_t frame_in_batch, const float*& round_rows, std::string& json_lines) const {
+    // --spot-background: a "%.17g" number (it parses back to the same float64), or null where the spot's ring gave no estimate
+    static void append_g17(std::string& j, bool valid, double v) {
+        char buf[40];
+        if (valid) std::snprintf(buf, sizeof buf, "%.17g", v);
+        j += valid ? buf : "null";
+    }
+    void append_json(const ffs_frame_result& r, ffs_stream* stream, uint32_t frame_in_batch, const float*& round_rows, const ffs_spot_background* bg,
+                     std::string& json_lines) const {
         std::string j = "{\"file\":" + json_escape(args_.file) + ",\"file-number\":" + std::to_string((uint32_t)r.frame_id)
                         + ",\"n_spots_total\":" + std::to_string(r.n_boxes)
                         + ",\"num_strong_pixels\":" + std::to_string(r.num_strong_pixels);
         if (args_.radial_bins) j += radial_json(stream, frame_in_batch);
+        // the image's spots in reflection order: intensity = sum - pixels x mean; variance = sum + pixels^2 x mean / inliers (the counts' own
+        // Poisson variance plus that of the estimated mean); the keys stay in alphabetical order around "spot_centers"
+        std::string intensity, variance;
+        double total_intensity = 0.0;
+        if (args_.spot_background) {   // (bg may be null: a batch without a single reflection)
+            j += ",\"spot_background_mean\":[";
+            for (uint32_t qq = 0; qq < r.n_reflections; ++qq) {
+                const bool ok = bg[qq].status == FFS_SPOT_BG_OK;
+                const double sum = (double)r.reflections[qq].sum_intensity, k = (double)r.reflections[qq].num_pixels, mean = bg[qq].mean;
+                const double i_spot = sum - k * mean, v_spot = ok ? sum + k * k * mean / (double)bg[qq].n_inliers : 0.0;
+                if (qq) { j += ","; intensity += ","; variance += ","; }
+                append_g17(j, ok, mean);
+                append_g17(intensity, ok, i_spot);
+                append_g17(variance, ok, v_spot);
+                if (ok) total_intensity += i_spot;
+            }
+            j += "]";
+        }
         if (args_.output_for_index) {
             j += ",\"spot_centers\":[";
             for (uint32_t qq = 0; qq < r.n_reflections; ++qq) {
@@ -679,6 +716,10 @@ class BatchReport {
                 }
             }
             j += "]";
+        }
+        if (args_.spot_background) {
+            j += ",\"spot_intensity\":[" + intensity + "],\"spot_variance\":[" + variance + "],\"total_intensity\":";
+            append_g17(j, true, total_intensity);
         }
         json_lines += j;
         json_lines += "}\n";

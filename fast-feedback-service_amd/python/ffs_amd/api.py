@@ -81,6 +81,18 @@ class _PixelStats(C.Structure):   # ffs_pixel_stats
                 ("max", C.POINTER(C.c_uint32))]
 
 
+class _SpotBackground(C.Structure):   # ffs_spot_background
+    _fields_ = [("n_pixels", C.c_uint32), ("n_overflow", C.c_uint32), ("q1", C.c_int32), ("median", C.c_int32), ("q3", C.c_int32),
+                ("n_inliers", C.c_uint32), ("inlier_sum", C.c_uint64), ("status", C.c_uint32), ("reserved", C.c_uint32), ("mean", C.c_double)]
+
+
+SPOT_BG_DT = np.dtype([("n_pixels", "<u4"), ("n_overflow", "<u4"), ("q1", "<i4"), ("median", "<i4"), ("q3", "<i4"), ("n_inliers", "<u4"),
+                       ("inlier_sum", "<u8"), ("status", "<u4"), ("reserved", "<u4"), ("mean", "<f8")])
+assert SPOT_BG_DT.itemsize == C.sizeof(_SpotBackground) == 48
+# FFS_SPOT_BG_*: the status of a spot's background estimate
+SPOT_BG_OK, SPOT_BG_NO_PIXELS, SPOT_BG_OVERFLOW, SPOT_BG_RANGE, SPOT_BG_NO_INLIERS = 0, 1, 2, 3, 4
+
+
 PIXEL_STATS_MODES = {"off": 0, "start": 1, "resume": 2}   # FFS_PIXEL_STATS_OFF / _START / _RESUME
 # ffs_frame_result as a numpy record (offsets taken from the ctypes structure: pointers and padding included)
 _FRAME_RESULT_DT = np.dtype({"names": ["frame_id", "num_strong_pixels", "num_strong_pixels_filtered", "n_components", "n_boxes", "n_reflections"],
@@ -107,6 +119,7 @@ EXPORTS = [
     "ffs_ctx_set_max_valid_scope", "ffs_ctx_set_gain", "ffs_ctx_set_gain_map",
     "ffs_ctx_set_radial_bins", "ffs_stream_radial_profile", "ffs_bench_radial",
     "ffs_ctx_set_pixel_stats", "ffs_ctx_get_pixel_stats", "ffs_bench_pixel_stats",
+    "ffs_stream_spot_backgrounds",
 ]
 
 _lib = None
@@ -139,6 +152,7 @@ def load_library():
         L.ffs_ctx_set_pixel_stats.argtypes = [C.c_void_p, C.c_int]
         L.ffs_ctx_get_pixel_stats.argtypes = [C.c_void_p, C.POINTER(_PixelStats)]
         L.ffs_bench_pixel_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_uint32, C.c_uint32, C.POINTER(C.c_float)]
+        L.ffs_stream_spot_backgrounds.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_void_p), C.POINTER(C.c_uint32), C.POINTER(C.c_float)]
         L.ffs_bench_pipeline.argtypes = [C.POINTER(C.c_void_p), C.c_uint32, C.c_void_p, C.c_size_t, C.c_size_t, C.c_uint32,
                                          C.c_uint32, C.c_int64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
         L.ffs_device_numa_node.argtypes = [C.c_int]
@@ -559,6 +573,21 @@ class Stream:
         return (np.ctypeslib.as_array(out.count, (n,)).copy(), np.ctypeslib.as_array(out.sum, (n,)).copy(),
                 np.ctypeslib.as_array(out.sum_sq, (n,)).copy())
 
+    def spot_backgrounds(self, border: int = 3, copy: bool = True, want_ms: bool = False):
+        """ffs_stream_spot_backgrounds: the constant background of the ring of `border` (1..16) pixels around every reflection of the last
+        batch wait() returned, as a structured array (SPOT_BG_DT: n_pixels, n_overflow, q1, median, q3, n_inliers, inlier_sum, status,
+        reserved, mean) in the order of last_batch_reflections.  Between wait() and the next submit on this stream; the batch needs
+        want_reflections.  copy=False: a view of the library's buffer, valid until the next call or the next wait().  want_ms: returns
+        (array, the kernel's ms from HIP events).  spot_intensities() turns it into background-subtracted intensities."""
+        p, n, ms = C.c_void_p(), C.c_uint32(), C.c_float()
+        self.ctx._check(self._lib.ffs_stream_spot_backgrounds(self._h, int(border), C.byref(p), C.byref(n), C.byref(ms)))
+        if n.value:
+            a = np.frombuffer((C.c_uint8 * (n.value * SPOT_BG_DT.itemsize)).from_address(p.value), SPOT_BG_DT)
+            a = a.copy() if copy else a
+        else:
+            a = np.zeros(0, SPOT_BG_DT)
+        return (a, ms.value) if want_ms else a
+
     def bench_radial(self, dev_ptr: int, pitch_bytes: int, frame_stride_bytes: int, n_frames: int, iters: int) -> float:
         """ffs_bench_radial: average ms of one batch's radial profile (its two launches), alone on resident frames."""
         ms = C.c_float()
@@ -603,6 +632,21 @@ class Stream:
             self.close()
         except Exception:
             pass
+
+
+def spot_intensities(reflections: np.ndarray, backgrounds: np.ndarray):
+    """Background-subtracted intensities of a batch's reflections (REFL_DT) from their backgrounds (Stream.spot_backgrounds, same order):
+    intensity = sum_intensity - num_pixels * mean, and its variance under Poisson statistics, sum_intensity + num_pixels^2 * mean /
+    n_inliers (the counts' own variance plus that of the estimated mean over the spot's pixels).  Both float64, NaN where status != 0."""
+    assert len(reflections) == len(backgrounds)
+    ok = backgrounds["status"] == SPOT_BG_OK
+    s = reflections["sum_intensity"].astype(np.float64)
+    k = reflections["num_pixels"].astype(np.float64)
+    mean = backgrounds["mean"].astype(np.float64)
+    ni = np.where(ok, backgrounds["n_inliers"], 1).astype(np.float64)
+    intensity = np.where(ok, s - k * mean, np.nan)
+    variance = np.where(ok, s + k * k * mean / ni, np.nan)
+    return intensity, variance
 
 
 def bench_pipeline(streams, dev_ptr: int, pitch_bytes: int, frame_stride_bytes: int, n_frames: int, steps: int,

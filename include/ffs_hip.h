@@ -480,6 +480,67 @@ typedef struct {
 } ffs_radial_profile;
 int ffs_stream_radial_profile(ffs_stream *s, uint32_t frame_in_batch, ffs_radial_profile *out);
 
+/* The per-spot background and what a background-subtracted intensity needs: for every reflection of the last batch ffs_wait returned on
+ * this stream, a constant background level estimated from the ring of pixels around its bounding box, with Tukey's fence against
+ * outliers.  The model is the constant background of the reference's integrator (include/integrator/background.hpp,
+ * tukey_constant_background: an integer histogram of 256 one-count bins and a high tail, quartiles by 1-based position, rejection
+ * outside q1 - 1.5 IQR .. q3 + 1.5 IQR, no estimate when the tail or the fence says the range is too small), restated in integers; it
+ * assumes photon counts, as the reference's header says, and applies no gain.  The reference runs it over a 3D shoebox at integration
+ * time; here it runs over a 2D ring at spot-finding time, on the device, where the pixels are.
+ *   Ring.  For a reflection with bounding box x_min..x_max, y_min..y_max in its frame and a border b in 1..16: the pixels of
+ *   [x_min - b, x_max + b] x [y_min - b, y_max + b], clipped to the image, that lie OUTSIDE the bounding box.  The spot's own box
+ *   contributes nothing (its non-strong tails are not background); a neighbour's strong pixels that fall into the ring stay in it
+ *   (rejecting them is the model's job).
+ *   A ring pixel p is VALID when all of these hold (the rules of the radial profile):
+ *     - its bit in the context's valid-pixel mask is set -- the mask as it stands at the call, ffs_ctx_apply_resolution_mask included;
+ *     - p <= max_valid when the batch's ffs_params.max_valid >= 0, under both scopes of max_valid;
+ *     - for 32-bit pixels, p < 2^24.
+ *   From the valid ring pixels, in integers:
+ *     n_pixels = N, their number; n_overflow = those with p >= 256.
+ *     status, decided in this order:
+ *       FFS_SPOT_BG_NO_PIXELS (1)   N = 0;
+ *       FFS_SPOT_BG_OVERFLOW (2)    4 * n_overflow > N: too much of the ring lies above the histogram;
+ *       otherwise q1, median, q3 = the values at the 1-based sorted positions (N + 3) / 4, (N + 1) / 2, (3 N + 1) / 4 (integer
+ *       division); all three are below 256 then.  With iqr = q3 - q1:
+ *       FFS_SPOT_BG_RANGE (3)       2 * q3 + 3 * iqr >= 512: the upper fence reaches the end of the histogram;
+ *       otherwise the inliers are the pixels with 2 * q1 - 3 * iqr <= 2 * p <= 2 * q3 + 3 * iqr and p < 256; n_inliers is their
+ *       number and inlier_sum their sum;
+ *       FFS_SPOT_BG_NO_INLIERS (4)  there are none.  Cannot be reached once 1-3 are excluded (the bin of q1 is never empty and always
+ *                                   inside the fence); kept for parity with the reference's order of checks;
+ *       FFS_SPOT_BG_OK (0)          else.
+ *     Under status 1 and 2 the quartiles are -1.  Under any non-zero status n_inliers = inlier_sum = 0.
+ *     mean (float64) = (double)inlier_sum / (double)n_inliers, divided on the host; 0 when status != 0.
+ *   Everything up to that division is integer arithmetic: the result is exact, bit for bit, and independent of path, tuning and order.
+ *   A background-subtracted intensity is sum_intensity - num_pixels * mean (the reflection's fields); its variance under Poisson
+ *   statistics is sum_intensity + num_pixels^2 * mean / n_inliers.
+ * One entry is written per reflection of the batch, in the order and with the per-frame slices of ffs_stream_batch_arrays: frame i's slice
+ * starts where frame i-1's ends and is results[i].n_reflections long (the reflections left after both filters).  *out stays valid until
+ * the next call of this function or the next ffs_wait on the stream.  kernel_ms may be NULL; otherwise it receives the kernel's time from
+ * HIP events on its dispatch (0 when nothing was launched).  A batch with no reflections: FFS_OK, *n = 0, nothing is launched.
+ * The call is synchronous -- it launches in a HIP stream of the ffs_stream's own, waits and returns -- and belongs between ffs_wait and the
+ * stream's next submit.  It reads the reflections ffs_wait handed out and the frames where the batch left them, so it sees the final
+ * records whatever path, re-run or one-frame recovery produced them, and:
+ *   - for an ffs_submit_device batch the caller's frames must still be where they were at submit, unchanged;
+ *   - the context's mask must not have been replaced since the batch (the ring is judged by the mask as it stands at the call);
+ *   - ffs_decode_only* on the stream decodes into the stream's frame buffer: after it the call is refused until the next ffs_wait.
+ * FFS_ERR_INVALID (ffs_last_error names the reason): a dead handle; NULL out or n; border outside 1..16; no batch waited on the stream
+ * yet, or the last ffs_wait on it failed; a batch in flight on the stream (its frames replace the last batch's); the last batch was
+ * submitted without want_reflections. */
+#define FFS_SPOT_BG_OK 0u
+#define FFS_SPOT_BG_NO_PIXELS 1u
+#define FFS_SPOT_BG_OVERFLOW 2u
+#define FFS_SPOT_BG_RANGE 3u
+#define FFS_SPOT_BG_NO_INLIERS 4u
+typedef struct {
+    uint32_t n_pixels, n_overflow;
+    int32_t q1, median, q3;
+    uint32_t n_inliers;
+    uint64_t inlier_sum;
+    uint32_t status, reserved;
+    double mean;
+} ffs_spot_background;            /* 48 bytes */
+int ffs_stream_spot_backgrounds(ffs_stream *s, uint32_t border, const ffs_spot_background **out, uint32_t *n, float *kernel_ms);
+
 /* Centres of mass of the last batch's reflections as rows (frame_id, x, y, z) of float32 -- the
  * payload of `--output-for-index` (spot_centers, spotfinder.cc:919-933,1004-1006), in frame order;
  * used to feed a multi-GPU gather without a per-frame loop on the caller's side.  Lane 0 carries the
