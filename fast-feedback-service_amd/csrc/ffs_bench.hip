@@ -3,7 +3,8 @@
 #include "ffs_internal.hpp"
 
 // Average duration of ONE launch of the threshold stage's dense kernel (`ms_dense`) and of what follows it inside the stage
-// (`ms_rest`: k_bright_fix; extended algorithm: erosion + final pass), over `iters` launches.  Every launch runs on the state
+// (`ms_rest`: k_bright_fix; extended algorithm: erosion + final pass; radial-profile threshold: the histogram launch, then the cut and
+// strong launches, whose records go to the host buffer the stream's next batch would write), over `iters` launches.  Every launch runs on the state
 // the hot path gives it -- zeroed per-tile counts and bright-list count, empty plane and occupancy bitmap -- and is timed by
 // start / stop events that ride on its own dispatch, so the resets between launches are outside the measurement.
 extern "C" int ffs_bench_threshold(ffs_stream* s, const void* device_pixels, size_t pitch, size_t fstride,
@@ -34,7 +35,12 @@ extern "C" int ffs_bench_threshold(ffs_stream* s, const void* device_pixels, siz
     }
     const bool e_sparse = ext && ext_sparse_erode(c->tune);   // (the hot path clears the signal-region plane behind the previous batch)
     ta.eplane_clean = e_sparse ? 1 : 0;
-    if (!ext) (void)wave_logs_for(s, ta, geo, Rerun{});   // (the kernel as the hot path launches it)
+    const bool radial = route.stage == ThresholdStage::kRadial;   // (ms_dense: the histogram launch; ms_rest: the cut and strong launches)
+    if (radial) {
+        rc = radthr_ensure_buffers(s);
+        if (rc != FFS_OK) return rc;
+    }
+    if (!ext && !radial) (void)wave_logs_for(s, ta, geo, Rerun{});   // (the kernel as the hot path launches it)
     const Layout& L = c->L;
     std::vector<hipEvent_t> ev(4 * (size_t)iters, nullptr);
     auto cleanup = [&]() { for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e); };

@@ -430,9 +430,19 @@ extern "C" int ffs_ctx_set_params(ffs_ctx* c, const ffs_params* p) {
                  "its erosion and final pass derive from it";
         return FFS_ERR_INVALID;
     }
-    if ((p->algorithm != FFS_ALGO_DISPERSION && p->algorithm != FFS_ALGO_DISPERSION_EXTENDED)
+    if ((p->algorithm != FFS_ALGO_DISPERSION && p->algorithm != FFS_ALGO_DISPERSION_EXTENDED && p->algorithm != FFS_ALGO_RADIAL_PROFILE)
         || (p->extended_flavour != 0 && p->extended_flavour != 1)) {
         c->err = "ffs_ctx_set_params: unknown algorithm / extended_flavour";
+        return FFS_ERR_INVALID;
+    }
+    // (whichever call comes second is refused: ffs_ctx_set_radial_bins has the other half)
+    if (p->algorithm == FFS_ALGO_RADIAL_PROFILE && c->radial_bins == 0) {
+        c->err = "ffs_ctx_set_params: the radial_profile algorithm needs a radial bin map (ffs_ctx_set_radial_bins) and the context has none";
+        return FFS_ERR_INVALID;
+    }
+    if (p->algorithm == FFS_ALGO_RADIAL_PROFILE && c->radial_bins > kRadThrMaxBins) {
+        c->err = "ffs_ctx_set_params: the radial_profile algorithm takes a radial bin map of at most 128 bins and the context's has "
+                 + std::to_string(c->radial_bins);
         return FFS_ERR_INVALID;
     }
     if (p->extended_flavour == 1 && c->max_valid_scope == FFS_MAX_VALID_WINDOW) {
@@ -534,12 +544,21 @@ extern "C" int ffs_ctx_set_gain_map(ffs_ctx* c, const float* host_gain) {
 // copy is written only while no batch of the context is in flight, and NULL only switches the map off (a batch in flight took its bins at
 // submit and its profile kernels read the device copy, which stays).
 static int ffs_ctx_set_radial_bins_impl(ffs_ctx* c, const uint16_t* bin_of_pixel, uint32_t n_bins) {
+    const bool thresholds = c->params.algorithm == FFS_ALGO_RADIAL_PROFILE;   // (ffs_ctx_set_params has the other half of these two)
     if (!bin_of_pixel) {
+        if (thresholds) {
+            c->err = "ffs_ctx_set_radial_bins: the context's parameters say the radial_profile algorithm, which needs the map: set another algorithm first";
+            return FFS_ERR_INVALID;
+        }
         c->radial_bins = 0;
         return FFS_OK;
     }
     if (n_bins < 1 || n_bins > 1024) {
         c->err = "ffs_ctx_set_radial_bins: n_bins must be in 1..1024, got " + std::to_string(n_bins);
+        return FFS_ERR_INVALID;
+    }
+    if (thresholds && n_bins > kRadThrMaxBins) {
+        c->err = "ffs_ctx_set_radial_bins: the context's parameters say the radial_profile algorithm, which takes at most 128 bins, got " + std::to_string(n_bins);
         return FFS_ERR_INVALID;
     }
     if (c->inflight.load() > 0) {
@@ -580,6 +599,16 @@ static int ffs_ctx_set_radial_bins_impl(ffs_ctx* c, const uint16_t* bin_of_pixel
 extern "C" int ffs_ctx_set_radial_bins(ffs_ctx* c, const uint16_t* bin_of_pixel, uint32_t n_bins) {
     if (!c) return FFS_ERR_INVALID;
     return guarded(c, [&] { return ffs_ctx_set_radial_bins_impl(c, bin_of_pixel, n_bins); });
+}
+
+extern "C" int ffs_ctx_set_radial_threshold(ffs_ctx* c, double n_iqr) {
+    if (!c) return FFS_ERR_INVALID;
+    if (!std::isfinite(n_iqr) || n_iqr < 0.0 || n_iqr > kRadThrMaxNIqr) {
+        c->err = "ffs_ctx_set_radial_threshold: n_iqr must be finite and in 0 .. 2^20 (the cutoff median + n_iqr * iqr is a uint32)";
+        return FFS_ERR_INVALID;
+    }
+    c->n_iqr = n_iqr;
+    return FFS_OK;
 }
 
 // ---- the per-pixel statistics ------------------------------------------------------------------------------------
@@ -702,6 +731,8 @@ extern "C" int ffs_ctx_set_tuning(ffs_ctx* c, const char* key, long long value) 
     else if (k == "window_kernel") { if ((ok = in(0, 1))) t.window_kernel = (int)value; }
     else if (k == "radial_stream") { if ((ok = in(0, 1))) t.radial_stream = (int)value; }
     else if (k == "radial_map8") { if ((ok = in(0, 1))) t.radial_map8 = (int)value; }
+    else if (k == "radthr_bands") { if ((ok = in(0, 1 << 30))) t.radthr_bands = (int)value; }
+    else if (k == "radthr_form") { if ((ok = in(0, 2))) t.radthr_form = (int)value; }
     else if (k == "stats_stream") {
         // (launches in the context's own stream and launches in the dense stream are not ordered among each other: the key moves only while nothing is in flight)
         if ((ok = in(0, 1) && c->inflight.load() == 0)) t.stats_stream = (int)value;
@@ -792,6 +823,7 @@ void stream_destroy_internal(ffs_stream* s) {
     if (s->st_shared && s->ctx->dense_st2) (void)hipStreamSynchronize(s->ctx->dense_st2);   // (the dense stream's partner may hold this stream's kernel)
     if (s->st2 && s->st2 != s->st) { (void)hipStreamSynchronize(s->st2); if (!s->st2_shared) (void)hipStreamDestroy(s->st2); }
     radial_free(s);
+    radthr_free(s);
     spotbg_free(s);
     if (s->ev_stats) (void)hipEventDestroy(s->ev_stats);   // (the sparse stream, synchronised above, waited for it)
     // (d_n_comp, d_summary and d_overflow live inside the d_num_strong allocation)

@@ -4,7 +4,7 @@
 //   ffs_context.hip  contexts, masks (kernels_mask.hpp), tuning, streams
 //   ffs_submit.hip   one batch (enqueue_batch: plan_batch decides its path once, a BatchPlan with the launch geometry and the threshold route; then the resets,
 //                    the threshold stage and the sparse stage are launched from that plan), submit entry points, compressed input
-//                    (kernels_stream / threshold / extended / window / ccl / chain / band / decode)
+//                    (kernels_stream / threshold / extended / window / radthr / ccl / chain / band / decode)
 //   ffs_wait.hip     ffs_wait: overflow re-runs (rerun_batch: the same batch again with a Rerun override), result assembly,
 //                    result accessors
 //   ffs_spotbg.hip   ffs_stream_spot_backgrounds: the per-spot constant background of the last waited batch (kernels_spotbg.hpp)
@@ -17,6 +17,8 @@
 //                        threshold stage (tests/threshold_route_check.cc)
 //   tuning.hpp           struct Tuning
 //   spot_background_model.hpp  the decisions of the per-spot background: quartile positions, status order, fence (tests/spot_background_check.cc)
+//   radial_threshold_model.hpp the decisions of the radial-profile threshold (kernels_radthr.hpp, included by ffs_submit.hip): status order and the
+//                        cutoff's two separately rounded operations (tests/radial_threshold_check.cc)
 // No exception leaves the library (guarded()).
 #pragma once
 #include <algorithm>
@@ -42,6 +44,7 @@
 
 #include "ffs_hip.h"
 #include "ffs_device.h"
+#include "radial_threshold_model.hpp"
 #include "threshold_route.hpp"
 #include "tuning.hpp"
 
@@ -78,6 +81,11 @@ struct ParamSnapshot {
     bool gain_map = false;
     uint32_t radial_bins = 0;   // bins of the context's radial bin map at submit (0: no map): the batch computes a profile over that many bins
     bool pixel_stats = false;   // ffs_ctx_set_pixel_stats was on at submit: the batch's frames are folded into the context's per-pixel statistics, once
+    // The radial-profile threshold (FFS_ALGO_RADIAL_PROFILE): the shells of the map at submit when the parameters say that
+    // algorithm, else 0 -- its own field, because a one-frame re-run drops radial_bins (the profile is computed once) and still thresholds by
+    // shell -- and n_iqr (ffs_ctx_set_radial_threshold).  The map itself is the context's, like the gain map.
+    uint32_t radthr_bins = 0;
+    double n_iqr = 6.0;
 };
 
 // A few helper threads per context for ffs_wait's result assembly (wire records -> boxes, reflections, centre rows): one thread
@@ -148,6 +156,7 @@ struct ffs_ctx {
     uint16_t* d_radial_map = nullptr;
     uint8_t* d_radial_map8 = nullptr;   // the same rows in one byte an entry (0xFF: in no bin), behind the two-byte rows in the same allocation; written for maps of at most 255 bins
     uint32_t radial_bins = 0;
+    double n_iqr = 6.0;                           // ffs_ctx_set_radial_threshold: kept across ffs_ctx_set_params, snapshot per batch
     // ffs_ctx_set_pixel_stats: the four accumulator planes are one allocation, made at the first start and kept (count,
     // max, sum, sum of squares, in that order; laid out in tiles: PixStatsLayout below).  stats_on: batches submitted from now on are folded in;
     // stats_started: there has been a start, ffs_ctx_get_pixel_stats has something to hand out.  stats_st: the context's own HIP stream for the
@@ -314,6 +323,15 @@ struct ffs_stream {
     std::vector<uint8_t*> radial_retired;
     const uint8_t* radial_out = nullptr;     // what ffs_stream_radial_profile reads: the last waited batch's buffer, bins (0: no profile) and frames
     uint32_t radial_out_bins = 0, radial_out_frames = 0;
+    // The radial-profile threshold (kernels_radthr.hpp) of a batch whose snapshot has radthr_bins.  All made by the stream's first such batch,
+    // for kRadThrMaxBins shells and max_batch frames: the frames' histograms and cutoffs on the device, and two pinned host buffers of
+    // ffs_radial_shell records that take turns like the profile's (a re-run inside ffs_wait writes the same records into the same buffer).
+    // radthr_out: what ffs_stream_radial_thresholds reads, the last waited batch's buffer (null: that batch ran another algorithm).
+    uint32_t *d_radthr_hist = nullptr, *d_radthr_cut = nullptr;
+    ffs_radial_shell *h_radthr[2] = {nullptr, nullptr}, *h_radthr_dev[2] = {nullptr, nullptr};
+    int radthr_turn = 0;
+    const ffs_radial_shell* radthr_out = nullptr;
+    uint32_t radthr_out_bins = 0, radthr_out_frames = 0;
     // The per-pixel statistics (kernels_pixstats.hpp) of a batch whose snapshot has pixel_stats.  stats_todo: set by the submit entry points --
     // the batch's first enqueue launches the kernel and clears it, the re-runs inside ffs_wait find it off; stats_join: that launch is not in
     // the batch's sparse stream, which waits for ev_stats (recorded behind it, made on first use) ahead of the batch's last event.
@@ -404,7 +422,10 @@ static int guarded(ffs_ctx* c, F&& body) {
     } while (0)
 
 // ---- small helpers ------------------------------------------------------------------------------------------
-static inline ParamSnapshot snapshot_of(const ffs_ctx* c) { return ParamSnapshot{c->params, c->max_valid_scope, c->gain, c->has_gain_map, c->radial_bins, c->stats_on}; }
+static inline ParamSnapshot snapshot_of(const ffs_ctx* c) {
+    return ParamSnapshot{c->params, c->max_valid_scope, c->gain, c->has_gain_map, c->radial_bins, c->stats_on,
+                         c->params.algorithm == FFS_ALGO_RADIAL_PROFILE ? c->radial_bins : 0u, c->n_iqr};
+}
 // Where the per-pixel statistics lie (kernels_pixstats.hpp has the why): a lane owns px = 16 / pixel_bytes pixels of a row, lanes are numbered
 // row by row, sixty-four of them are a tile, and in every plane a lane's entries are chunks of 16 B, chunk k of lane l of tile t at
 // 16 B x ((t * chunks + k) * 64 + l).
@@ -512,6 +533,11 @@ int radial_ensure_buffers(ffs_stream* s, uint32_t bins);
 int radial_launch(ffs_stream* s, const void* d_img, size_t pitch, size_t fstride, uint32_t n_frames, hipStream_t st, hipEvent_t start, hipEvent_t stop);
 void radial_publish(ffs_stream* s);
 void radial_free(ffs_stream* s);
+// The radial-profile threshold (ThresholdStage::kRadial): ensure makes the stream's buffers and asks the device for the histogram's LDS (first
+// use); launch_dense_kernel / launch_dense_rest launch its histogram and its cut + strong kernels; publish is ffs_wait's side.
+int radthr_ensure_buffers(ffs_stream* s);
+void radthr_publish(ffs_stream* s);
+void radthr_free(ffs_stream* s);
 // The per-pixel statistics: the kernel over n_frames frames that are in place in `st`, into the context's accumulators (which exist), with the
 // limit of `max_valid`; start / stop ride on the first and the last dispatch (either may be null).  The caller keeps two launches apart.
 int pixstats_launch(ffs_ctx* c, const void* d_img, size_t pitch, size_t fstride, uint32_t n_frames, long long max_valid, hipStream_t st, hipEvent_t start,

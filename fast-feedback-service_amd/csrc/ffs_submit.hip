@@ -15,6 +15,7 @@
 #include "kernels_byteoffset.hpp"
 #include "kernels_window.hpp"
 #include "kernels_radial.hpp"
+#include "kernels_radthr.hpp"
 #include "kernels_pixstats.hpp"
 
 bool chain_prepare_device() {   // more than 64 KB of dynamic LDS has to be asked for, per device
@@ -358,16 +359,136 @@ bool wave_logs_for(ffs_stream* s, ThresholdArgs& a, const StreamGeometry& g, con
     return true;
 }
 
+// ---- the radial-profile threshold (kernels_radthr.hpp) --------------------------------------------------------
+// The histogram's workgroups hold a whole CU's LDS each, so a launch aims at two per CU and at most 64 bands a frame; tuning "radthr_bands"
+// sets the bands instead (clamped to 1..H).
+constexpr uint32_t kRadThrTargetGroups = 512, kRadThrMaxBands = 64;
+static void radthr_bands(const ffs_ctx* c, uint32_t n_frames, uint32_t& n_bands, uint32_t& band_rows) {
+    const uint32_t H = (uint32_t)c->L.H;
+    const uint32_t want = c->tune.radthr_bands > 0 ? std::clamp<uint32_t>((uint32_t)c->tune.radthr_bands, 1u, H)
+                                                   : std::clamp<uint32_t>((kRadThrTargetGroups + n_frames - 1) / n_frames, 1u, std::min(H, kRadThrMaxBands));
+    band_rows = (H + want - 1) / want;
+    n_bands = (H + band_rows - 1) / band_rows;
+}
+using RadThrKernel = void (*)(RadThrArgs);
+// form: tuning "radthr_form" -- 1 = one LDS add per counting pixel, 2 = a run kept in registers, 0 = the faster of the two as measured
+// (DESIGN.md section 3.9): the run for 16-bit pixels, the plain add for 32-bit
+static RadThrKernel radthr_hist_kernel(int pixel_bytes, int form) {
+    const bool run = form == 0 ? pixel_bytes == 2 : form == 2;
+    return pixel_bytes == 2 ? (run ? k_radthr_hist<uint16_t, true> : k_radthr_hist<uint16_t, false>)
+                            : (run ? k_radthr_hist<uint32_t, true> : k_radthr_hist<uint32_t, false>);
+}
+
+void radthr_free(ffs_stream* s) {
+    if (s->d_radthr_hist) (void)hipFree(s->d_radthr_hist);
+    for (ffs_radial_shell* p : s->h_radthr)
+        if (p) (void)hipHostFree(p);
+    s->d_radthr_hist = s->d_radthr_cut = nullptr;
+    s->h_radthr[0] = s->h_radthr[1] = nullptr;
+    s->radthr_out = nullptr;
+}
+
+// Histograms and cutoffs (one allocation) and the two record buffers, for max_batch frames of kRadThrMaxBins shells: made by the stream's
+// first batch of the algorithm and kept.  A table of more than 64 KB of dynamic LDS has to be asked for, per device (chain_prepare_device):
+// a device that refuses cannot run the algorithm, and says so.
+int radthr_ensure_buffers(ffs_stream* s) {
+    if (s->d_radthr_hist) return FFS_OK;
+    ffs_ctx* c = s->ctx;
+    for (int form = 1; form <= 2; ++form)
+        if (hipFuncSetAttribute(reinterpret_cast<const void*>(radthr_hist_kernel(c->pixel_bytes, form)), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                (int)radthr_lds_bytes(kRadThrMaxBins)) != hipSuccess) {
+            (void)hipGetLastError();
+            c->err = "radial_profile threshold: the device refuses the histogram's " + std::to_string(radthr_lds_bytes(kRadThrMaxBins)) + " bytes of LDS";
+            return FFS_ERR_DEVICE;
+        }
+    const size_t shells = (size_t)s->max_batch * kRadThrMaxBins;
+    uint32_t* d = nullptr;
+    if (hipMalloc(reinterpret_cast<void**>(&d), shells * (kRadThrCounters + 1) * 4u) != hipSuccess) {
+        (void)hipGetLastError();
+        c->err = "radial_profile threshold: hipMalloc(histograms) failed";
+        return FFS_ERR_NOMEM;
+    }
+    for (int i = 0; i < 2; ++i)
+        if (hipHostMalloc(reinterpret_cast<void**>(&s->h_radthr[i]), shells * sizeof(ffs_radial_shell), hipHostMallocDefault) != hipSuccess
+            || hipHostGetDevicePointer(reinterpret_cast<void**>(&s->h_radthr_dev[i]), s->h_radthr[i], 0) != hipSuccess) {
+            (void)hipGetLastError();
+            (void)hipFree(d);
+            for (ffs_radial_shell*& p : s->h_radthr) {
+                if (p) (void)hipHostFree(p);
+                p = nullptr;
+            }
+            c->err = "radial_profile threshold: hipHostMalloc(records) failed";
+            return FFS_ERR_NOMEM;
+        }
+    s->d_radthr_hist = d;
+    s->d_radthr_cut = d + shells * kRadThrCounters;
+    return FFS_OK;
+}
+
+// The stage's arguments from the threshold stage's (buffers, pitches, threshold, what the sparse stage wants) and the batch's snapshot
+static RadThrArgs make_radthr_args(const ffs_stream* s, const ThresholdArgs& t, uint32_t n_frames) {
+    const ffs_ctx* c = s->ctx;
+    RadThrArgs a{};
+    a.in.image = t.image;
+    a.in.frame_stride = t.frame_stride;
+    a.in.pitch = t.pitch;
+    a.in.maskbits = t.maskbits;
+    a.in.mpitch = t.mpitch;
+    a.in.bins = c->d_radial_map;
+    a.in.bin_pitch = (uint32_t)t.pitch_px;
+    a.in.W = t.W;
+    a.in.H = t.H;
+    a.in.n_bins = s->batch.radthr_bins;
+    radthr_bands(c, n_frames, a.in.n_bands, a.in.band_rows);
+    // (max_valid under both of its scopes, and p < 2^24 for 32-bit pixels: the radial profile's limit, radial_launch)
+    a.in.limit = t.max_valid >= 0 ? (uint32_t)std::min<long long>(t.max_valid, (1ll << 24) - 1) + 1u : 1u << 24;
+    a.hist = s->d_radthr_hist;
+    a.cut = s->d_radthr_cut;
+    a.shells = s->h_radthr_dev[s->radthr_turn];
+    a.n_iqr = s->batch.n_iqr;
+    a.threshold = t.threshold;
+    a.bits = t.bits;
+    a.strong_bytes = t.strong_bytes;
+    a.tile_counts = t.tile_counts;
+    a.occ = t.occ;
+    a.occ_frame_words = t.occ_frame_words;
+    a.occ_spr = t.occ_spr;
+    a.bpitch = t.bpitch;
+    a.plane_frame_stride = t.plane_frame_stride;
+    a.bytes_frame_stride = t.bytes_frame_stride;
+    a.n_tiles = t.n_tiles;
+    a.dense_mask = t.dense_mask;
+    a.s_strips = ((uint32_t)(t.W + 7) / 8u + 63u) / 64u;
+    return a;
+}
+// The histogram: the frames' tables are zeroed ahead of the launch, outside its events (radthr_ensure_buffers has run)
+static void launch_radthr_hist(ffs_stream* s, const ThresholdArgs& t, uint32_t n_frames, hipEvent_t start, hipEvent_t stop) {
+    const RadThrArgs a = make_radthr_args(s, t, n_frames);
+    (void)hipMemsetAsync(a.hist, 0, (size_t)n_frames * a.in.n_bins * kRadThrCounters * 4u, s->st);
+    hipExtLaunchKernelGGL(radthr_hist_kernel(s->ctx->pixel_bytes, s->ctx->tune.radthr_form), dim3(n_frames, a.in.n_bands), dim3(kRadThrHistThreads),
+                          radthr_lds_bytes(a.in.n_bins), s->st, start, stop, 0, a);
+}
+// ... and the cutoffs and the strong pixels behind it; `stop` rides on the last dispatch
+static void launch_radthr_rest(ffs_stream* s, const ThresholdArgs& t, uint32_t n_frames, hipEvent_t stop) {
+    const RadThrArgs a = make_radthr_args(s, t, n_frames);
+    hipLaunchKernelGGL(k_radthr_cut, dim3(a.in.n_bins, n_frames), dim3(64), 0, s->st, a);
+    const dim3 grid(a.s_strips * (uint32_t)a.n_tiles, n_frames);
+    if (s->ctx->pixel_bytes == 2) hipExtLaunchKernelGGL(k_radthr_strong<uint16_t>, grid, dim3(64), 0, s->st, nullptr, stop, 0, a);
+    else hipExtLaunchKernelGGL(k_radthr_strong<uint32_t>, grid, dim3(64), 0, s->st, nullptr, stop, 0, a);
+}
+
 // The threshold stage where all of it runs in s->st (ffs_internal.hpp): the dense kernel ...
 void launch_dense_kernel(ffs_stream* s, const ThresholdRoute& route, const ThresholdArgs& a, const StreamGeometry& g, uint32_t n_frames, hipEvent_t start,
                          hipEvent_t stop, bool plane_clean, bool counts_clean) {
     if (route.ext()) launch_ext_first(s, route, a, g, n_frames, start, stop, true, plane_clean, counts_clean);
+    else if (route.stage == ThresholdStage::kRadial) launch_radthr_hist(s, a, n_frames, start, stop);
     else if (route.stage == ThresholdStage::kWindow) launch_window(s, route, a, n_frames, start, stop);
     else launch_stream(s, a, g, start, stop);
 }
 // ... and what follows it
 void launch_dense_rest(ffs_stream* s, const ThresholdRoute& route, const ThresholdArgs& a, uint32_t n_frames) {
     if (route.ext()) launch_ext_rest(s, route, a, n_frames, s->st);
+    else if (route.stage == ThresholdStage::kRadial) launch_radthr_rest(s, a, n_frames, nullptr);
     else if (route.stage == ThresholdStage::kWindow) return;   // (it decides every pixel itself)
     else if (route.bright_to_plane) launch_exact(s, route, a, n_frames, s->st);
     else if (!a.wlog) launch_bright_fix(s, a, s->st);   // (with wave logs the sparse launch decides the bright windows)
@@ -449,6 +570,7 @@ struct BatchPlan {
     // occupancy bitmap in step with it
     bool ext = false;
     bool ext_sparse_erode = false;    // ... whose signal-region plane is cleared behind the previous batch together with the first-pass plane (ext_sparse_erode())
+    bool radial = false;              // the radial-profile threshold (kernels_radthr.hpp) decides every pixel itself, like the general-window kernel: no list, no fix-up, no logs
     bool window = false;              // the general-window kernel (kernels_window.hpp) decides every pixel itself: no bright-window list, no fix-up, no wave logs
     bool list_path = false;           // a streaming kernel that hands its bright windows to k_bright_fix on a list (threshold path 0)
     bool aside = false;               // the context has sparse streams: the dense stream holds streaming kernels only
@@ -485,9 +607,10 @@ static BatchPlan plan_batch(ffs_stream* s, const void* d_img, size_t pitch, size
     P.geo = batch_stream_geometry(s, fstride, n);
     P.ta = make_threshold_args(s, d_img, pitch, fstride, n, P.geo, P.route);
     P.window = P.route.stage == ThresholdStage::kWindow;
+    P.radial = P.route.stage == ThresholdStage::kRadial;
     P.list_path = P.route.stage == ThresholdStage::kStreamList;
     // (the byte mask: zero-filled by the streaming kernels only when asked for; the exact stages always produce it)
-    P.want_dense_bytes = P.window ? (p.want_strong_mask || c->tune.dense_mask)
+    P.want_dense_bytes = (P.window || P.radial) ? (p.want_strong_mask || c->tune.dense_mask)
                                   : (P.list_path || (P.ext && P.route.ext_streams_first())) ? P.ta.dense_mask != 0 : true;
     // The whole sparse stage in one launch, one workgroup per frame (kernels_chain.hpp) ...
     const bool can_chain = c->tune.sparse_stage >= 2 && L.H <= 65535 && c->chain_ok && s->direct_recs && s->h_counts_dev
@@ -541,7 +664,7 @@ static BatchPlan plan_batch(ffs_stream* s, const void* d_img, size_t pitch, size
     P.chain_first = P.list_path && P.aside && P.will_chain && !P.banded && c->tune.chain_first > 0 && depth <= c->tune.chain_first;
     P.path_bits = (P.use_log ? FFS_PATH_WAVE_LOGS : 0u) | (P.will_chain && !P.banded ? FFS_PATH_FRAME_CHAIN : 0u) | (P.banded ? FFS_PATH_BANDS : 0u)
                   | (P.runs_launch ? FFS_PATH_RUNS : 0u) | (!P.will_chain ? FFS_PATH_GRID_KERNELS : 0u) | (P.ext ? FFS_PATH_EXTENDED : 0u)
-                  | (P.window ? FFS_PATH_WINDOW : 0u);
+                  | (P.window ? FFS_PATH_WINDOW : 0u) | (P.radial ? FFS_PATH_RADIAL_THRESHOLD : 0u);
     return P;
 }
 
@@ -669,6 +792,17 @@ static int launch_threshold_stage(ffs_stream* s, const BatchPlan& plan, bool den
         tw.occ = (c->tune.occupancy_bitmap && plan.will_chain) ? s->d_occ : nullptr;
         FFS_TRY(wait_for_upload(s, plan, s->st));
         launch_window(s, plan.route, tw, n, ev_start, s->ev[2]);
+        FFS_TRY(sparse_stream_follows(s, true));
+    } else if (plan.radial) {
+        // The same outputs from the radial-profile threshold's three launches: the histogram (behind the fill that zeroes its tables), the
+        // cutoffs, the strong pixels
+        ThresholdArgs tr = ta;
+        tr.dense_mask = plan.want_dense_bytes ? 1 : 0;
+        tr.occ = (c->tune.occupancy_bitmap && plan.will_chain) ? s->d_occ : nullptr;
+        FFS_TRY(radthr_ensure_buffers(s));
+        FFS_TRY(wait_for_upload(s, plan, s->st));
+        launch_radthr_hist(s, tr, n, ev_start, nullptr);
+        launch_radthr_rest(s, tr, n, s->ev[2]);
         FFS_TRY(sparse_stream_follows(s, true));
     } else if (plan.list_path && plan.aside) {
         // the bright-window fix-up goes to the sparse stream (or into the sparse launch itself: chain_first; with wave logs the

@@ -580,6 +580,7 @@ int ffs_wait_impl(ffs_stream* s, const ffs_frame_result** results, uint32_t* n_r
             return rc;
         }
     }
+    radthr_publish(s);   // (ahead of radial_publish, which ends the batch's "pending")
     radial_publish(s);
     s->waited_ok = true;
     if (results) *results = s->results.data();
@@ -621,6 +622,35 @@ extern "C" int ffs_stream_radial_profile(ffs_stream* s, uint32_t frame_in_batch,
     out->sum = sum + (size_t)frame_in_batch * bins;
     out->sum_sq = sum + plane + (size_t)frame_in_batch * bins;
     out->count = reinterpret_cast<const uint32_t*>(sum + 2 * plane) + (size_t)frame_in_batch * bins;
+    return FFS_OK;
+}
+
+// The records of the radial-profile threshold, the same way and under the same flag (radial_pending: once per batch; a re-run inside ffs_wait
+// computed the same records into the same buffer).  A batch of another algorithm hands out that it has none.
+void radthr_publish(ffs_stream* s) {
+    if (!s->radial_pending) return;
+    s->radthr_out = nullptr;
+    if (s->batch.radthr_bins) {
+        s->radthr_out = s->h_radthr[s->radthr_turn];
+        s->radthr_turn ^= 1;
+    }
+    s->radthr_out_bins = s->batch.radthr_bins;
+    s->radthr_out_frames = s->n_frames;
+}
+
+extern "C" int ffs_stream_radial_thresholds(ffs_stream* s, uint32_t frame_in_batch, const ffs_radial_shell** out, uint32_t* n_bins) {
+    if (!s || !out || !n_bins || !stream_handle_ok(s)) return FFS_ERR_INVALID;
+    ffs_ctx* c = s->ctx;
+    if (!s->radthr_out || s->radthr_out_bins == 0) {
+        c->err = "ffs_stream_radial_thresholds: the last batch ffs_wait returned on this stream did not run the radial_profile algorithm (FFS_ALGO_RADIAL_PROFILE)";
+        return FFS_ERR_INVALID;
+    }
+    if (frame_in_batch >= s->radthr_out_frames) {
+        c->err = "ffs_stream_radial_thresholds: frame_in_batch " + std::to_string(frame_in_batch) + " is out of range: the batch had " + std::to_string(s->radthr_out_frames) + " frames";
+        return FFS_ERR_INVALID;
+    }
+    *out = s->radthr_out + (size_t)frame_in_batch * s->radthr_out_bins;   // (the layout k_radthr_cut writes: [frame][bins of the batch])
+    *n_bins = s->radthr_out_bins;
     return FFS_OK;
 }
 

@@ -1,0 +1,254 @@
+// kernels_radthr.hpp (included by ffs_submit.hip only) -- the radial-profile threshold (FFS_ALGO_RADIAL_PROFILE): a
+// pixel is strong when it stands above median + n_iqr x IQR of its shell of the caller's bin map (ffs_ctx_set_radial_bins, at most 128
+// bins), both taken per frame over a histogram of the shell's counting pixels.  The reference has no counterpart (its algorithms are
+// dispersion and dispersion_extended, spotfinder/spotfinder.cc:338-342); the definition is ffs_hip.h's, modelled on DIALS's radial_profile.
+//
+// Three launches in the dense stream, everything an integer but the cutoff's one product:
+//   k_radthr_hist<PixelT>   grid (frames, bands): a workgroup of sixteen waves streams a band of contiguous rows of one frame with
+//                           kernels_radial.hpp's loads (16 B of pixels, the matching bin entries and mask bits per lane and load, the next
+//                           load in flight) and counts into a table in LDS, n_bins x 257 counters: the values 0 .. 255 and a tail.  The
+//                           table is up to 128.5 KiB -- one workgroup a CU, hence sixteen waves of it -- and its non-zero counters are then
+//                           added to the frame's table in global memory, zeroed ahead of the launch (integers: any order, the same bits).
+//   k_radthr_cut            grid (bins, frames): a wave per (frame, shell) scans the 257 counters, four bins a lane, and decides with
+//                           radial_threshold_model.hpp: N, the quartiles, the status, the cutoff.  The record goes to pinned host memory,
+//                           the cutoff (0xFFFFFFFF under a status other than 0: no pixel passes) to the device array k_radthr_strong reads.
+//   k_radthr_strong<PixelT> grid (strips x tiles, frames): a wave per 64 eight-pixel groups and eight rows (an exact-stage tile) decides
+//                           every pixel -- p > cutoff of its shell, an integer compare, and p > threshold -- and leaves what k_window leaves
+//                           for the sparse stage: the non-zero bytes of a plane that is zero at launch, the occupancy bits, the per-tile
+//                           counts, the byte mask when asked for.
+// How a lane's count meets the table (tuning "radthr_form"): 1, one LDS add per counting pixel under the lane's own exec bit; 2, a run of
+// equal (shell, value) pairs kept in registers, as k_radial keeps its run of equal bins, and added when the pair changes; 0 (default), the
+// one that measured faster for the pixel size -- the run for 16-bit pixels (0.454 against 0.476 ms, 32 Eiger-16M frames, 100 shells), the
+// plain add for 32-bit (0.297 against 0.324 ms, Jungfrau-9M).  DESIGN.md section 3.9 has both.
+#pragma once
+#include "ffs_device.h"
+#include "kernels_radial.hpp"
+#include "kernels_threshold.hpp"
+#include "radial_threshold_model.hpp"
+
+namespace ffsamd {
+
+constexpr int kRadThrHistThreads = 1024;
+constexpr int kRadThrHistWaves = kRadThrHistThreads / 64;
+
+struct RadThrArgs {
+    // what the histogram reads, as the radial profile reads it: image, frame_stride, pitch, maskbits, mpitch, bins, bin_pitch, W, H, n_bins,
+    // n_bands, band_rows, limit (bins8 is null and the profile's partials and results are unused)
+    RadialArgs in;
+    uint32_t* hist;               // [frame][n_bins][kRadThrCounters], zero when k_radthr_hist starts
+    uint32_t* cut;                // [frame][n_bins]: the cutoff, kRadThrNever under a status other than 0
+    ffs_radial_shell* shells;     // [frame][n_bins], pinned host memory
+    double n_iqr, threshold;
+    // what k_radthr_strong writes (ThresholdArgs has the same names)
+    uint8_t* bits;
+    uint8_t* strong_bytes;
+    uint32_t* tile_counts;
+    uint32_t* occ;                // nullptr: nobody reads the occupancy bitmap
+    uint32_t occ_frame_words, occ_spr;
+    uint32_t bpitch;
+    uint64_t plane_frame_stride, bytes_frame_stride;
+    int n_tiles, dense_mask;
+    uint32_t s_strips;            // strips of 64 groups in a row
+};
+
+static inline size_t radthr_lds_bytes(uint32_t n_bins) { return (size_t)n_bins * kRadThrCounters * 4u; }
+
+template <typename PixelT, bool RUN>
+__global__ __launch_bounds__(kRadThrHistThreads) void k_radthr_hist(RadThrArgs a) {
+    constexpr int PX = 16 / (int)sizeof(PixelT);
+    extern __shared__ __attribute__((aligned(16))) uint8_t radthr_smem[];
+    uint32_t* tab = reinterpret_cast<uint32_t*>(radthr_smem);
+    const uint32_t n_tab = a.in.n_bins * (uint32_t)kRadThrCounters;
+    const uint32_t frame = blockIdx.x, band = blockIdx.y;
+    for (uint32_t i = threadIdx.x; i < n_tab; i += kRadThrHistThreads) tab[i] = 0u;
+    __syncthreads();
+
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const uint8_t* img = static_cast<const uint8_t*>(a.in.image) + (uint64_t)frame * a.in.frame_stride;
+    const int y_end = min(a.in.H, (int)((band + 1u) * a.in.band_rows));
+    const int step = 64 * PX;
+    // this wave's loads: rows y, y + 16, ... of the band, each from x = 0 in steps of `step` while x < W (k_radial's order)
+    int y = (int)(band * a.in.band_rows + wave), xw = 0;
+    [[maybe_unused]] uint32_t cur = 0u, cnt = 0u;   // (RUN) the lane's run: a counter's index and how often
+    RadialLoad<PixelT> ld = radial_load<PixelT, false>(a.in, img, y < y_end ? y : a.in.H, xw + (int)lane * PX);
+    while (y < y_end) {
+        int yn = y, xn = xw + step;
+        if (xn >= a.in.W) { xn = 0; yn = y + kRadThrHistWaves; }
+        const RadialLoad<PixelT> nx = radial_load<PixelT, false>(a.in, img, yn < y_end ? yn : a.in.H, xn + (int)lane * PX);
+#pragma unroll
+        for (int j = 0; j < PX; ++j) {
+            uint32_t p, b;
+            if constexpr (PX == 8) {
+                const uint32_t pw = j < 2 ? ld.px.x : j < 4 ? ld.px.y : j < 6 ? ld.px.z : ld.px.w;
+                const uint32_t bw = j < 2 ? ld.bn.x : j < 4 ? ld.bn.y : j < 6 ? ld.bn.z : ld.bn.w;
+                p = (j & 1) ? pw >> 16 : pw & 0xFFFFu;
+                b = (j & 1) ? bw >> 16 : bw & 0xFFFFu;
+            } else {
+                p = j == 0 ? ld.px.x : j == 1 ? ld.px.y : j == 2 ? ld.px.z : ld.px.w;
+                const uint32_t bw = j < 2 ? ld.bn.x : ld.bn.y;
+                b = (j & 1) ? bw >> 16 : bw & 0xFFFFu;
+            }
+            // (the map's entries are below n_bins or kRadialNone: ffs_ctx_set_radial_bins checked them)
+            const bool ok = ((ld.mb >> j) & 1u) && b != kRadialNone && p < a.in.limit;
+            const uint32_t at = b * (uint32_t)kRadThrCounters + min(p, (uint32_t)kRadThrValues);
+            if constexpr (RUN) {
+                if (ok && at != cur) {
+                    if (cnt != 0u) atomicAdd(&tab[cur], cnt);
+                    cur = at;
+                    cnt = 0u;
+                }
+                if (ok) ++cnt;
+            } else {
+                if (ok) atomicAdd(&tab[at], 1u);
+            }
+        }
+        ld = nx;
+        y = yn;
+        xw = xn;
+    }
+    if constexpr (RUN) {
+        if (cnt != 0u) atomicAdd(&tab[cur], cnt);
+    }
+    __syncthreads();
+    uint32_t* out = a.hist + (uint64_t)frame * n_tab;
+    for (uint32_t i = threadIdx.x; i < n_tab; i += kRadThrHistThreads) {
+        const uint32_t v = tab[i];
+        if (v != 0u) atomicAdd(&out[i], v);
+    }
+}
+
+__device__ __forceinline__ int radthr_wave_max(int v) {
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) v = max(v, __shfl_xor(v, d, 64));
+    return v;
+}
+
+__global__ __launch_bounds__(64) void k_radthr_cut(RadThrArgs a) {
+    const uint32_t b = blockIdx.x, frame = blockIdx.y, lane = threadIdx.x;
+    const uint64_t shell = (uint64_t)frame * a.in.n_bins + b;
+    const uint32_t* h = a.hist + shell * (uint32_t)kRadThrCounters;
+    uint32_t c[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) c[k] = h[lane * 4u + (uint32_t)k];
+    const uint32_t n_overflow = h[kRadThrValues];
+    const uint32_t mine = c[0] + c[1] + c[2] + c[3];
+    const uint32_t incl = wave_inclusive_scan(mine);
+    const uint64_t n = (uint64_t)__builtin_amdgcn_readlane((int)incl, 63) + n_overflow;   // (at most W x H: a frame's pixels are counted in 32 bits)
+    const uint32_t status = radthr_status_of_counts(n, n_overflow);
+    int q1 = -1, median = -1, q3 = -1;
+    uint32_t cutoff = 0u;
+    if (status == kRadThrOk) {   // (the same in every lane)
+        const SpotBgPositions pos = spotbg_positions(n);
+        uint64_t cum = incl - mine;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {   // the first value whose cumulative count reaches a position: exactly one (lane, k) each
+            const uint64_t before = cum;
+            cum += c[k];
+            const int v = (int)(lane * 4u) + k;
+            if (before < pos.p25 && cum >= pos.p25) q1 = v;
+            if (before < pos.p50 && cum >= pos.p50) median = v;
+            if (before < pos.p75 && cum >= pos.p75) q3 = v;
+        }
+        q1 = radthr_wave_max(q1);
+        median = radthr_wave_max(median);
+        q3 = radthr_wave_max(q3);
+        cutoff = radthr_cutoff(median, q3 - q1, a.n_iqr);
+    }
+    if (lane == 0u) {
+        ffs_radial_shell r;
+        r.n_pixels = (uint32_t)n;
+        r.n_overflow = n_overflow;
+        r.q1 = q1;
+        r.median = median;
+        r.q3 = q3;
+        r.cutoff = cutoff;
+        r.status = status;
+        r.reserved = 0u;
+        a.shells[shell] = r;
+        a.cut[shell] = status == kRadThrOk ? cutoff : kRadThrNever;
+    }
+}
+
+// One row of a lane's group of eight pixels: the pixels, their bin entries and the valid-pixel mask byte; nothing outside the frame
+template <typename PixelT>
+struct RadThrRow {
+    uint4 p0, p1, bn;
+    uint32_t mb;
+};
+template <typename PixelT>
+__device__ __forceinline__ RadThrRow<PixelT> radthr_row(const RadThrArgs& a, const uint8_t* img, int y, uint32_t g, bool own) {
+    RadThrRow<PixelT> r;
+    r.p0 = make_uint4(0u, 0u, 0u, 0u);
+    r.p1 = r.p0;
+    r.bn = make_uint4(0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu);
+    r.mb = 0u;
+    // (a group that straddles W stays inside the row's pitch_px pixels; what it reads beyond W has no mask bit and no bin)
+    if (own && y < a.in.H) {
+        const uint8_t* rp = img + (uint64_t)y * a.in.pitch + (uint64_t)g * (8u * sizeof(PixelT));
+        r.p0 = *reinterpret_cast<const uint4*>(rp);
+        if constexpr (sizeof(PixelT) == 4) r.p1 = *reinterpret_cast<const uint4*>(rp + 16);
+        r.bn = *reinterpret_cast<const uint4*>(a.in.bins + (uint64_t)y * a.in.bin_pitch + (uint64_t)g * 8u);
+        r.mb = a.in.maskbits[(uint64_t)y * a.in.mpitch + g];
+    }
+    return r;
+}
+
+template <typename PixelT>
+__global__ __launch_bounds__(64) void k_radthr_strong(RadThrArgs a) {
+    __shared__ uint32_t s_cut[kRadThrMaxBins];
+    const uint32_t lane = threadIdx.x;
+    const uint32_t strip = blockIdx.x % a.s_strips, tile = blockIdx.x / a.s_strips, frame = blockIdx.y;
+    for (uint32_t i = lane; i < kRadThrMaxBins; i += 64u) s_cut[i] = i < a.in.n_bins ? a.cut[(uint64_t)frame * a.in.n_bins + i] : kRadThrNever;
+    __syncthreads();
+    const uint32_t g = strip * 64u + lane;              // this lane's group: pixels 8g .. 8g + 7
+    const bool own = (int)(g * 8u) < a.in.W;
+    const int y0 = (int)tile * kTileRows, y1 = min(a.in.H, y0 + kTileRows);
+    const uint8_t* img = static_cast<const uint8_t*>(a.in.image) + (uint64_t)frame * a.in.frame_stride;
+    uint8_t* plane = a.bits + (uint64_t)frame * a.plane_frame_stride;
+    uint8_t* sbytes = a.strong_bytes + (uint64_t)frame * a.bytes_frame_stride;
+    uint32_t cnt = 0u;
+    RadThrRow<PixelT> row = radthr_row<PixelT>(a, img, y0, g, own);
+    for (int y = y0; y < y1; ++y) {
+        const RadThrRow<PixelT> next = radthr_row<PixelT>(a, img, y + 1 < y1 ? y + 1 : a.in.H, g, own);
+        uint32_t p[8];
+        if constexpr (sizeof(PixelT) == 2) {
+            p[0] = row.p0.x & 0xFFFFu; p[1] = row.p0.x >> 16; p[2] = row.p0.y & 0xFFFFu; p[3] = row.p0.y >> 16;
+            p[4] = row.p0.z & 0xFFFFu; p[5] = row.p0.z >> 16; p[6] = row.p0.w & 0xFFFFu; p[7] = row.p0.w >> 16;
+        } else {
+            p[0] = row.p0.x; p[1] = row.p0.y; p[2] = row.p0.z; p[3] = row.p0.w;
+            p[4] = row.p1.x; p[5] = row.p1.y; p[6] = row.p1.z; p[7] = row.p1.w;
+        }
+        uint32_t sb = 0u;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const uint32_t bw = j < 2 ? row.bn.x : j < 4 ? row.bn.y : j < 6 ? row.bn.z : row.bn.w;
+            const uint32_t b = (j & 1) ? bw >> 16 : bw & 0xFFFFu;
+            // (a pixel beyond W has no mask bit: bits at x >= W are never set)
+            const bool counts = ((row.mb >> j) & 1u) && b != kRadialNone && p[j] < a.in.limit;
+            const uint32_t cutoff = s_cut[b & (kRadThrMaxBins - 1u)];
+            if (counts && p[j] > cutoff && (double)p[j] > a.threshold) sb |= 1u << j;
+        }
+        if (sb) {
+            plane[(uint64_t)y * a.in.mpitch + g] = (uint8_t)sb;   // (the plane is all zero when the kernel starts)
+            if (a.occ) {
+                const uint32_t ob = (uint32_t)y * a.occ_spr + (g >> 4);   // the 16-byte segment of the plane row
+                atomicOr(a.occ + (uint64_t)frame * a.occ_frame_words + (ob >> 5), 1u << (ob & 31u));
+            }
+        }
+        if (a.dense_mask && own) {
+            uint2 bytes;
+            bytes.x = (sb & 1u) | ((sb & 2u) << 7) | ((sb & 4u) << 14) | ((sb & 8u) << 21);
+            bytes.y = ((sb >> 4) & 1u) | ((sb & 0x20u) << 3) | ((sb & 0x40u) << 10) | ((sb & 0x80u) << 17);
+            *reinterpret_cast<uint2*>(sbytes + (uint64_t)y * a.bpitch + (uint64_t)g * 8u) = bytes;
+        }
+        cnt += (uint32_t)__popc(sb);
+        row = next;
+    }
+    if (__ballot(cnt != 0u)) {   // the tile's count
+        const uint32_t total = __builtin_amdgcn_readlane(wave_inclusive_scan(cnt), 63);
+        if (lane == 0u) atomicAdd(a.tile_counts + (uint64_t)frame * a.n_tiles + tile, total);
+    }
+}
+
+}  // namespace ffsamd

@@ -42,6 +42,7 @@ enum class ThresholdStage : int {
     kStreamList,    // dispersion, path 0: a streaming kernel, its bright windows on the list k_bright_fix works off
     kStreamExact,   // dispersion, path 1: a streaming kernel, its bright windows marked in the plane k_exact filters
     kExtended,      // first pass -> erosion -> final pass
+    kRadial,        // the radial-profile threshold (FFS_ALGO_RADIAL_PROFILE): histogram -> cutoffs -> strong pixels (kernels_radthr.hpp)
 };
 struct ThresholdRoute {
     ThresholdStage stage = ThresholdStage::kStreamList;
@@ -70,7 +71,12 @@ inline ThresholdRoute threshold_route(int algorithm, int pixel_bytes, bool windo
     // (the streaming kernels' screens rest on the mask tables, which know nothing of a frame's pixels, and are proven for the photon-count
     // predicate: every other variant takes k_window / k_ext_first -- DESIGN.md sections 3.3c, 3.3d)
     r.ext_variant = (pixel_bytes == 2 && rerun_threshold_path < 0 && photon) ? t.ext_first_pass : 0;
-    if (algorithm == FFS_ALGO_DISPERSION_EXTENDED) {
+    if (algorithm == FFS_ALGO_RADIAL_PROFILE) {
+        // whatever the tuning's threshold_path and window_kernel say: the stage has one form, no bright windows and no first pass
+        r.stage = ThresholdStage::kRadial;
+        r.bright_to_plane = 0;
+        r.ext_variant = 0;
+    } else if (algorithm == FFS_ALGO_DISPERSION_EXTENDED) {
         r.stage = ThresholdStage::kExtended;
         r.ext_fused = pixel_bytes == 2 && t.ext_fused != 0 && !gain_form(r.variant);   // (a gain batch has no fused kernel)
     } else if (r.bright_to_plane == 2) {

@@ -70,6 +70,10 @@ struct Tuning {
     int radial_map8 = 0;        // k_radial reads the bin map in one byte an entry where the map has at most 255 bins (1) or always in two (0)
     int stats_stream = 0;       // the per-pixel statistics' launch (kernels_pixstats.hpp): 0 = in a HIP stream of the context's own, beside the batch's threshold
                                 //    stage, 1 = in the dense stream behind the threshold stage's kernels (the A/B partner: DESIGN.md section 3.7)
+    int radthr_bands = 0;       // the radial-profile threshold's histogram launch (kernels_radthr.hpp): 0 = the launch chooses its bands per frame, > 0 = that
+                                //    many, clamped to 1..H (tests put the band seams where they want them)
+    int radthr_form = 0;        // ... and how a lane's counts meet the workgroup's table: 1 = one LDS add per counting pixel, 2 = a run of equal (shell, value)
+                                //    pairs kept in registers, 0 = what measured faster for the pixel size: 2 for 16-bit pixels, 1 for 32-bit
 #ifdef FFS_EXPERIMENTS
     struct Exp {
         int k1_debug = 0, chain_skip = 0, chain_stop = 0, dummy_us = 0, dummy_wg = 32, dummy_threads = 1024, dummy_lds = 0;

@@ -24,6 +24,7 @@ void usage() {
       "                  [--max-valid trusted|none|N] [--max-valid-scope centre|window] [--min-count N] [--kernel-size N | NX,NY]\n"
       "                  [--gain G] [--gain-map FILE] [--radial-bins N] [--pixel-stats PREFIX]\n"
       "                  [--spot-background B]\n"
+      "                  [--n-iqr X]\n"
       "                  [--devices D0,D1,... | --gpus N] [--no-numa-pinning] [--single-buffer] [--all-threads] [--read-only] [--clean-exit]\n"
       "--max-valid: a centre pixel above this value is never strong (the reference's kernels test it against the\n"
       "              data set's trusted maximum).  trusted (default) = the frame source's trusted-range maximum when it is\n"
@@ -46,6 +47,12 @@ void usage() {
       "              width in 1/d^2, from the beam centre to the furthest pixel: the background level and its dispersion per shell, as\n"
       "              \"radial_count\", \"radial_sum\" and \"radial_sum_sq\" arrays in every image's JSON line (pixels above --max-valid and\n"
       "              masked pixels, --dmin / --dmax included, are left out).  Needs the detector geometry and the wavelength --dmin needs\n"
+      "-a radial_profile: a pixel is a spot candidate when it stands above median + X x IQR of its resolution shell, both taken per image from\n"
+      "              the shell's valid pixels (DIALS spotfinder.threshold.algorithm = radial_profile, without its blur): for high or steeply\n"
+      "              radial background, ice and solvent rings.  The shells are --radial-bins's (default 100 here, at most 128); --n-iqr X\n"
+      "              (default 6, 0 .. 2^20).  --min-count, --kernel-size, --gain and --gain-map play no part.  Every image's JSON line gains\n"
+      "              \"radial_median\", \"radial_cutoff\" and \"radial_status\" (0 decided, 1 no pixels, 2 more than a quarter at or above 256: no\n"
+      "              spots in that shell).  Not with --validate\n"
       "--pixel-stats: per pixel over the whole run, in how many images it was at or below --max-valid (32-bit pixels: and below 2^24), the sum\n"
       "              and the sum of squares of its values there, and the largest of them: what a mask, a gain map (variance / mean of a\n"
       "              flat run) and the maximum image of a serial run are made from.  Masked pixels are in them.  Written after the last\n"
@@ -207,6 +214,12 @@ Args parse_args(int argc, char** argv) {
             r.radial_bins = u32(v, s);
             if (r.radial_bins < 1 || r.radial_bins > 1024) arg_error("--radial-bins takes a number of shells in 1..1024: " + v);
         }
+        else if (s == "--n-iqr") {
+            const std::string& v = need(i, s);
+            char* end = nullptr;
+            r.n_iqr = std::strtod(v.c_str(), &end);
+            if (v.empty() || *end || !(r.n_iqr >= 0.0 && r.n_iqr <= 1048576.0)) arg_error("--n-iqr takes a number in 0 .. 2^20: " + v);
+        }
         else if (s == "--min-count") { r.min_count = u32(need(i, s), s); if (r.min_count < 2) arg_error("--min-count must be at least 2"); }
         else if (s == "--no-numa-pinning") r.no_numa_pinning = true;
         else if (s == "--single-buffer") r.single_buffer = true;
@@ -229,6 +242,12 @@ Args parse_args(int argc, char** argv) {
         if (r.kernel_half_x != 3 || r.kernel_half_y != 3)
             arg_error("--kernel-size other than 3 is not available with the dispersion_extended algorithm");
         r.algo = FFS_ALGO_DISPERSION_EXTENDED;
+    } else if (lower == "radial_profile") {
+        // (the shells are --radial-bins's, 100 unless given; the histogram's LDS table holds 128 of them)
+        if (r.radial_bins == 0) r.radial_bins = 100;
+        if (r.radial_bins > 128) arg_error("-a radial_profile takes at most 128 shells (--radial-bins): " + std::to_string(r.radial_bins));
+        if (r.validate) arg_error("--validate is not available with the radial_profile algorithm: the cross-check path is a dispersion path");
+        r.algo = FFS_ALGO_RADIAL_PROFILE;
     } else {
         std::printf("Error: Invalid algorithm specified\n");
         std::exit(1);

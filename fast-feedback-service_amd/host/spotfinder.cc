@@ -661,6 +661,8 @@ class BatchReport {
   private:
     // one image's JSON line; keys in alphabetical order, as nlohmann dumps them (:997-1008)
     // --radial-bins: the image's profile as three arrays of N integers (behind "num_strong_pixels": the keys stay in alphabetical order)
+    // -a radial_profile: what the threshold decided per shell, "radial_cutoff", "radial_median" and "radial_status", between "radial_count" and
+    // "radial_sum" (a batch of another algorithm has none: nothing is added)
     static std::string radial_json(ffs_stream* stream, uint32_t frame_in_batch) {
         ffs_radial_profile prof{};
         if (ffs_stream_radial_profile(stream, frame_in_batch, &prof) != FFS_OK) return "";
@@ -671,7 +673,20 @@ class BatchReport {
             s += sep + std::to_string(prof.sum[b]);
             q += sep + std::to_string(prof.sum_sq[b]);
         }
-        return c + "]" + s + "]" + q + "]";
+        std::string t;
+        const ffs_radial_shell* shells = nullptr;
+        uint32_t n_shells = 0;
+        if (ffs_stream_radial_thresholds(stream, frame_in_batch, &shells, &n_shells) == FFS_OK) {
+            std::string cut = ",\"radial_cutoff\":[", med = ",\"radial_median\":[", status = ",\"radial_status\":[";
+            for (uint32_t b = 0; b < n_shells; ++b) {
+                const char* sep = b ? "," : "";
+                cut += sep + std::to_string(shells[b].cutoff);
+                med += sep + std::to_string(shells[b].median);
+                status += sep + std::to_string(shells[b].status);
+            }
+            t = cut + "]" + med + "]" + status + "]";
+        }
+        return c + "]" + t + s + "]" + q + "]";
     }
     // --spot-background: a "%.17g" number (it parses back to the same float64), or null where the spot's ring gave no estimate
     static void append_g17(std::string& j, bool valid, double v) {
@@ -871,7 +886,7 @@ int main(int argc, char** argv) {
     std::printf("Spotfinder version: %s\n", FFS_VERSION);
     Args args = parse_args(argc, argv);
     stamp.verbose = args.verbose;
-    std::printf("Algorithm: %s\n", args.algo == FFS_ALGO_DISPERSION_EXTENDED ? "Dispersion Extended" : "Dispersion");
+    std::printf("Algorithm: %s\n", args.algo == FFS_ALGO_DISPERSION_EXTENDED ? "Dispersion Extended" : args.algo == FFS_ALGO_RADIAL_PROFILE ? "Radial Profile" : "Dispersion");
     if (args.threads < 1) {
         std::printf("Error: Thread count must be >= 1\n");
         return 1;
@@ -938,8 +953,13 @@ int main(int argc, char** argv) {
     ffs_ctx* ctx = ctxs[0];  // owns the 3D stack; also the context the one-off steps below report from
     upload_masks(ctxs, reader, args, ex, shape);
     const ffs_params prm = make_params(args, rotation, max_valid);
+    // (-a radial_profile is refused while the context has no bin map: the parameters go in with the default algorithm here and again, as they
+    // are, behind the map below)
+    const bool radial_algo = args.algo == FFS_ALGO_RADIAL_PROFILE;
+    ffs_params prm_before_map = prm;
+    if (radial_algo) prm_before_map.algorithm = FFS_ALGO_DISPERSION;
     for (ffs_ctx* cx : ctxs) {
-        FFS_CHECK(cx, ffs_ctx_set_params(cx, &prm));
+        FFS_CHECK(cx, ffs_ctx_set_params(cx, &prm_before_map));
         FFS_CHECK(cx, ffs_ctx_set_max_valid_scope(cx, args.max_valid_scope));
         FFS_CHECK(cx, ffs_ctx_set_gain(cx, args.gain));
         if (!gain_map.empty()) FFS_CHECK(cx, ffs_ctx_set_gain_map(cx, gain_map.data()));
@@ -964,6 +984,13 @@ int main(int argc, char** argv) {
             edges += buf;
         }
         std::printf("Radial bins: %u shells, d edges (A): %s\n", shells.n_bins, edges.c_str());
+    }
+    if (radial_algo) {
+        for (ffs_ctx* cx : ctxs) {
+            FFS_CHECK(cx, ffs_ctx_set_radial_threshold(cx, args.n_iqr));
+            FFS_CHECK(cx, ffs_ctx_set_params(cx, &prm));
+        }
+        std::printf("Radial-profile threshold: a strong pixel stands above median + %g x IQR of its shell\n", args.n_iqr);
     }
     // --pixel-stats: every context accumulates from its first batch on (the validation contexts see the same frames again, and do not)
     if (!args.pixel_stats.empty())

@@ -93,6 +93,14 @@ assert SPOT_BG_DT.itemsize == C.sizeof(_SpotBackground) == 48
 SPOT_BG_OK, SPOT_BG_NO_PIXELS, SPOT_BG_OVERFLOW, SPOT_BG_RANGE, SPOT_BG_NO_INLIERS = 0, 1, 2, 3, 4
 
 
+# ffs_radial_shell: what the radial-profile threshold decided for one (frame, shell) -- Stream.radial_thresholds
+RADIAL_SHELL_DT = np.dtype([("n_pixels", "<u4"), ("n_overflow", "<u4"), ("q1", "<i4"), ("median", "<i4"), ("q3", "<i4"), ("cutoff", "<u4"),
+                            ("status", "<u4"), ("reserved", "<u4")])
+assert RADIAL_SHELL_DT.itemsize == 32
+RADIAL_THR_OK, RADIAL_THR_EMPTY, RADIAL_THR_OVERFLOW = 0, 1, 2   # FFS_RADIAL_THR_*
+ALGO_RADIAL_PROFILE = 2   # FFS_ALGO_RADIAL_PROFILE: Context.set_params(algorithm=...), with a bin map of at most 128 bins set
+
+
 PIXEL_STATS_MODES = {"off": 0, "start": 1, "resume": 2}   # FFS_PIXEL_STATS_OFF / _START / _RESUME
 # ffs_frame_result as a numpy record (offsets taken from the ctypes structure: pointers and padding included)
 _FRAME_RESULT_DT = np.dtype({"names": ["frame_id", "num_strong_pixels", "num_strong_pixels_filtered", "n_components", "n_boxes", "n_reflections"],
@@ -120,6 +128,7 @@ EXPORTS = [
     "ffs_ctx_set_radial_bins", "ffs_stream_radial_profile", "ffs_bench_radial",
     "ffs_ctx_set_pixel_stats", "ffs_ctx_get_pixel_stats", "ffs_bench_pixel_stats",
     "ffs_stream_spot_backgrounds",
+    "ffs_ctx_set_radial_threshold", "ffs_stream_radial_thresholds",
 ]
 
 _lib = None
@@ -149,6 +158,8 @@ def load_library():
         L.ffs_ctx_set_radial_bins.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
         L.ffs_stream_radial_profile.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(_RadialProfile)]
         L.ffs_bench_radial.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_uint32, C.c_uint32, C.POINTER(C.c_float)]
+        L.ffs_ctx_set_radial_threshold.argtypes = [C.c_void_p, C.c_double]
+        L.ffs_stream_radial_thresholds.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_void_p), C.POINTER(C.c_uint32)]
         L.ffs_ctx_set_pixel_stats.argtypes = [C.c_void_p, C.c_int]
         L.ffs_ctx_get_pixel_stats.argtypes = [C.c_void_p, C.POINTER(_PixelStats)]
         L.ffs_bench_pixel_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_uint32, C.c_uint32, C.POINTER(C.c_float)]
@@ -342,6 +353,12 @@ class Context:
             used = b[b != RADIAL_NO_BIN]
             n_bins = int(used.max()) + 1 if used.size else 1
         self._check(self._lib.ffs_ctx_set_radial_bins(self._h, b.ctypes.data_as(C.c_void_p), int(n_bins)))
+
+    def set_radial_threshold(self, n_iqr: float):
+        """ffs_ctx_set_radial_threshold: n_iqr of the radial-profile threshold (set_params(algorithm=ALGO_RADIAL_PROFILE)) -- a pixel is
+        strong above floor(median + n_iqr * iqr) of its shell.  Default 6.  Kept across set_params; a batch takes it as it is at submit.
+        Refused (FfsError, state unchanged): NaN, infinite, below 0 or above 2^20."""
+        self._check(self._lib.ffs_ctx_set_radial_threshold(self._h, float(n_iqr)))
 
     def set_pixel_stats(self, mode: str):
         """ffs_ctx_set_pixel_stats: "start" (zero the per-pixel statistics and accumulate every frame submitted on the context from now
@@ -548,7 +565,8 @@ class Stream:
         self.ctx._check(self._lib.ffs_stream_timings(self._h, t))
         return dict(zip(("h2d", "threshold", "ccl", "d2h", "total"), list(t)))
 
-    PATH_BITS = {"wave_logs": 1, "frame_chain": 2, "bands": 4, "runs": 8, "grid_kernels": 16, "extended": 32, "window": 64, "radial": 128, "pixel_stats": 256}
+    PATH_BITS = {"wave_logs": 1, "frame_chain": 2, "bands": 4, "runs": 8, "grid_kernels": 16, "extended": 32, "window": 64, "radial": 128, "pixel_stats": 256,
+                 "radial_threshold": 512}
 
     def last_path(self):
         """ffs_stream_last_path: (set of the launches the last batch took, times ffs_wait ran it again)."""
@@ -572,6 +590,14 @@ class Stream:
         n = out.n_bins
         return (np.ctypeslib.as_array(out.count, (n,)).copy(), np.ctypeslib.as_array(out.sum, (n,)).copy(),
                 np.ctypeslib.as_array(out.sum_sq, (n,)).copy())
+
+    def radial_thresholds(self, frame_in_batch: int):
+        """ffs_stream_radial_thresholds: what the radial-profile threshold decided per shell of one frame of the last batch wait() returned,
+        as a structured array (RADIAL_SHELL_DT: n_pixels, n_overflow, q1, median, q3, cutoff, status, reserved) of n_bins records -- a
+        copy.  FfsError when that batch ran another algorithm or the frame is out of range."""
+        p, n = C.c_void_p(), C.c_uint32()
+        self.ctx._check(self._lib.ffs_stream_radial_thresholds(self._h, int(frame_in_batch), C.byref(p), C.byref(n)))
+        return np.frombuffer((C.c_uint8 * (n.value * RADIAL_SHELL_DT.itemsize)).from_address(p.value), RADIAL_SHELL_DT).copy()
 
     def spot_backgrounds(self, border: int = 3, copy: bool = True, want_ms: bool = False):
         """ffs_stream_spot_backgrounds: the constant background of the ring of `border` (1..16) pixels around every reflection of the last

@@ -61,7 +61,7 @@ typedef struct {
     int32_t want_strong_mask; /* produce and return the dense W*H byte mask per frame (reference D2H, :887-897); 0 (default): the
                                * strong mask stays a bit plane on the device and only lists / boxes / reflections come back */
     int32_t algorithm;        /* FFS_ALGO_DISPERSION (default) or FFS_ALGO_DISPERSION_EXTENDED:
-                                 `--algorithm`, spotfinder.cc:338-342, 572-590 */
+                                 `--algorithm`, spotfinder.cc:338-342, 572-590; or FFS_ALGO_RADIAL_PROFILE (below) */
     int32_t extended_flavour; /* extended only.  0 = baseline.cpp:730-761 rules (default); 1 = where the
                                  device kernels differ structurally: erosion skips masked neighbours
                                  (erosion.cu:101-105), second pass needs n > 0 (thresholding.cu:472) */
@@ -75,6 +75,25 @@ typedef struct {
 
 #define FFS_ALGO_DISPERSION 0
 #define FFS_ALGO_DISPERSION_EXTENDED 1
+/* The radial-profile threshold: a pixel is strong when it stands far above the background of its shell of the context's radial bin map
+ * (ffs_ctx_set_radial_bins, at most 128 bins here), measured per frame by the shell's median and interquartile range.  The reference has
+ * no counterpart (its `--algorithm` knows the two above, spotfinder/spotfinder.cc:338-342); modelled on DIALS's
+ * spotfinder.threshold.algorithm = radial_profile without its blur, and no parity with DIALS is claimed: this definition is the contract.
+ *   A pixel COUNTS in shell b under the radial profile's rule (ffs_ctx_set_radial_bins): b != 0xFFFF, its valid-pixel mask bit is set (the
+ *   mask as it stands at submit), p <= max_valid when max_valid >= 0 (both scopes), and for 32-bit pixels p < 2^24.
+ *   Per frame and shell, over its N counting pixels, from a histogram of one-count bins 0..255 and a tail: n_overflow = those with p >= 256;
+ *   status FFS_RADIAL_THR_EMPTY when N = 0; otherwise, with the 1-based sorted positions (N+3)/4, (N+1)/2 and (3N+1)/4 (integer division),
+ *   FFS_RADIAL_THR_OVERFLOW when the value at the third position is >= 256 (the position is above N - n_overflow); otherwise
+ *   FFS_RADIAL_THR_OK with q1, median, q3 the values at the three positions, iqr = q3 - q1 and
+ *   cutoff = floor((double)median + n_iqr * (double)iqr), product and sum each rounded to nearest on their own (no fused multiply-add).
+ *   Under the other two statuses the quartiles are -1 and the cutoff is 0.
+ *   A pixel is STRONG when it counts in shell b, b's status is 0, p > cutoff[b] (integers) and (double)p > ffs_params.threshold.
+ *   min_count, nsig_b, nsig_s, kernel_half_x / _y, extended_flavour, the gain, the gain map and the scope of max_valid beyond the
+ *   counting rule play no part (the IQR measures the spread itself); connected components, filters, records, lists, byte mask, 3D stack,
+ *   radial profile, pixel statistics and spot backgrounds of such a batch are what they are for any strong plane.
+ * ffs_ctx_set_params refuses it (FFS_ERR_INVALID) while the context has no bin map or one of more than 128 bins; ffs_ctx_set_radial_bins
+ * refuses NULL and a map of more than 128 bins while the context's parameters say this algorithm.  ffs_params keeps its layout. */
+#define FFS_ALGO_RADIAL_PROFILE 2
 
 void ffs_default_params(ffs_params *p);
 
@@ -251,6 +270,11 @@ int ffs_ctx_set_gain_map(ffs_ctx *ctx, const float *host_gain);
  *     the batch in flight goes on with the map it was submitted with, which stays on the device, and hands out its profile. */
 int ffs_ctx_set_radial_bins(ffs_ctx *ctx, const uint16_t *bin_of_pixel, uint32_t n_bins);
 
+/* n_iqr of the radial-profile threshold (FFS_ALGO_RADIAL_PROFILE): how many interquartile ranges above its shell's median a strong pixel
+ * stands.  Default 6 (DIALS's radial_profile.n_iqr).  Per context, kept across ffs_ctx_set_params; a batch takes it as it is at submit.
+ * FFS_ERR_INVALID, state unchanged: n_iqr is not finite, below 0 or above 2^20 (the cutoff is a uint32).  (No counterpart in the reference.) */
+int ffs_ctx_set_radial_threshold(ffs_ctx *ctx, double n_iqr);
+
 /* Per-pixel statistics over a run: count, sum, sum of squares and maximum of every pixel over all frames the context sees -- what a
  * valid-pixel mask (dead pixels: mean 0; hot pixels: a mean far above the neighbours'), a gain map (variance / mean over a flat run) and
  * the maximum image of a serial run (the "virtual powder pattern") are made from; dxtbx.image_average produces the same three images on
@@ -352,6 +376,11 @@ int ffs_ctx_get_pixel_stats(ffs_ctx *ctx, ffs_pixel_stats *out);
  *                          Accepted only while no batch of the context is in flight
  *   "radial_map8"      (0) the radial profile reads a bin map of at most 255 bins in one byte an entry (1) instead of two (0): DESIGN.md section 3.6
  *                          has the measurement
+ *   "radthr_bands"     (0) the radial-profile threshold's histogram launch: 0 = the launch chooses its bands of rows per frame, > 0 = that many,
+ *                          clamped to 1..H, each ceil(H / bands) rows tall (tests put the band seams where they want them)
+ *   "radthr_form"      (0) ... and how a lane's counts meet the workgroup's table in LDS: 1 = one add per counting pixel, 2 = a run of equal
+ *                          (shell, value) pairs kept in registers, 0 = the one that measured faster for the pixel size (2 for 16-bit
+ *                          pixels, 1 for 32-bit: DESIGN.md section 3.9)
  *   "assembly_threads" (7: helper threads that build a batch's result arrays; 3, 12 and 15 measure the same): see DESIGN.md.
  *   "band_taper" (0), "ext_rest_aside" (0), "ext_fused" (0): round 4's A/B partners (tapered bands of the streaming kernels;
  *                          extended algorithm: erosion + final pass in the sparse stream / fused into one kernel) -- measured, no
@@ -466,6 +495,7 @@ int ffs_stream_timings(ffs_stream *s, float ms[5]);
 #define FFS_PATH_WINDOW 64u        /* the general-window threshold kernel (a window other than 3,3, or tuning "window_kernel" = 1) */
 #define FFS_PATH_RADIAL 128u       /* the batch computed a radial profile (ffs_ctx_set_radial_bins) */
 #define FFS_PATH_PIXEL_STATS 256u  /* the batch was folded into the per-pixel statistics (ffs_ctx_set_pixel_stats) */
+#define FFS_PATH_RADIAL_THRESHOLD 512u /* the radial-profile threshold decided the strong pixels (FFS_ALGO_RADIAL_PROFILE; no counterpart in the reference) */
 int ffs_stream_last_path(ffs_stream *s, uint32_t *path_bits, uint32_t *reruns);
 
 /* The radial profile (ffs_ctx_set_radial_bins) of frame `frame_in_batch` of the last batch ffs_wait returned on this stream: n_bins
@@ -479,6 +509,22 @@ typedef struct {
     const uint64_t *sum_sq;
 } ffs_radial_profile;
 int ffs_stream_radial_profile(ffs_stream *s, uint32_t frame_in_batch, ffs_radial_profile *out);
+
+/* What the radial-profile threshold (FFS_ALGO_RADIAL_PROFILE) decided per shell of frame `frame_in_batch` of the last batch ffs_wait
+ * returned on this stream: *n_bins records, one per bin of the map the batch was submitted with, complete when ffs_wait returns and valid
+ * until the next ffs_wait on the stream (two pinned host buffers take turns, as for the profile).  The fields are FFS_ALGO_RADIAL_PROFILE's.
+ * FFS_ERR_INVALID: that batch did not run this algorithm; frame_in_batch is out of range; a dead handle.  (No counterpart in the
+ * reference: it has no such algorithm.) */
+#define FFS_RADIAL_THR_OK 0u
+#define FFS_RADIAL_THR_EMPTY 1u
+#define FFS_RADIAL_THR_OVERFLOW 2u
+typedef struct {
+    uint32_t n_pixels;            /* N, the shell's counting pixels */
+    uint32_t n_overflow;          /* ... those at or above 256 */
+    int32_t q1, median, q3;       /* -1 under a status other than FFS_RADIAL_THR_OK */
+    uint32_t cutoff, status, reserved;
+} ffs_radial_shell;               /* 32 bytes */
+int ffs_stream_radial_thresholds(ffs_stream *s, uint32_t frame_in_batch, const ffs_radial_shell **out, uint32_t *n_bins);
 
 /* The per-spot background and what a background-subtracted intensity needs: for every reflection of the last batch ffs_wait returned on
  * this stream, a constant background level estimated from the ring of pixels around its bounding box, with Tukey's fence against
