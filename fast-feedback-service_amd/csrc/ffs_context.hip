@@ -540,164 +540,6 @@ extern "C" int ffs_ctx_set_gain_map(ffs_ctx* c, const float* host_gain) {
     return guarded(c, [&] { return ffs_ctx_set_gain_map_impl(c, host_gain); });
 }
 
-// The bin map of the radial profile.  Everything is checked before anything changes; like the gain map, the device
-// copy is written only while no batch of the context is in flight, and NULL only switches the map off (a batch in flight took its bins at
-// submit and its profile kernels read the device copy, which stays).
-static int ffs_ctx_set_radial_bins_impl(ffs_ctx* c, const uint16_t* bin_of_pixel, uint32_t n_bins) {
-    const bool thresholds = c->params.algorithm == FFS_ALGO_RADIAL_PROFILE;   // (ffs_ctx_set_params has the other half of these two)
-    if (!bin_of_pixel) {
-        if (thresholds) {
-            c->err = "ffs_ctx_set_radial_bins: the context's parameters say the radial_profile algorithm, which needs the map: set another algorithm first";
-            return FFS_ERR_INVALID;
-        }
-        c->radial_bins = 0;
-        return FFS_OK;
-    }
-    if (n_bins < 1 || n_bins > 1024) {
-        c->err = "ffs_ctx_set_radial_bins: n_bins must be in 1..1024, got " + std::to_string(n_bins);
-        return FFS_ERR_INVALID;
-    }
-    if (thresholds && n_bins > kRadThrMaxBins) {
-        c->err = "ffs_ctx_set_radial_bins: the context's parameters say the radial_profile algorithm, which takes at most 128 bins, got " + std::to_string(n_bins);
-        return FFS_ERR_INVALID;
-    }
-    if (c->inflight.load() > 0) {
-        c->err = "ffs_ctx_set_radial_bins: a batch of this context is in flight (ffs_wait for it first): a batch keeps the map it was submitted with";
-        return FFS_ERR_INVALID;
-    }
-    const Layout& L = c->L;
-    const size_t n = (size_t)L.W * L.H;
-    for (size_t i = 0; i < n; ++i)
-        if (bin_of_pixel[i] >= n_bins && bin_of_pixel[i] != 0xFFFFu) {
-            c->err = "ffs_ctx_set_radial_bins: entry " + std::to_string(i) + " (x = " + std::to_string(i % (size_t)L.W) + ", y = " + std::to_string(i / (size_t)L.W)
-                     + ") is " + std::to_string(bin_of_pixel[i]) + ": every entry must be below n_bins = " + std::to_string(n_bins) + " or 0xFFFF (in no bin)";
-            return FFS_ERR_INVALID;
-        }
-    // rows of pitch_px entries, addressed like the pixel rows; the entries beyond W are in no bin
-    std::vector<uint16_t> rows((size_t)L.pitch_px * L.H, (uint16_t)0xFFFFu);
-    for (int y = 0; y < L.H; ++y) std::memcpy(rows.data() + (size_t)y * L.pitch_px, bin_of_pixel + (size_t)y * L.W, (size_t)L.W * sizeof(uint16_t));
-    HIP_TRY(c, hipSetDevice(c->device));
-    if (!c->d_radial_map) {
-        uint16_t* d = nullptr;
-        if (hipMalloc(reinterpret_cast<void**>(&d), rows.size() * (sizeof(uint16_t) + 1)) != hipSuccess) {
-            (void)hipGetLastError();
-            c->err = "ffs_ctx_set_radial_bins: hipMalloc(bin map) failed";
-            return FFS_ERR_NOMEM;
-        }
-        c->d_radial_map = d;
-        c->d_radial_map8 = reinterpret_cast<uint8_t*>(d + rows.size());
-    }
-    HIP_TRY(c, hipMemcpy(c->d_radial_map, rows.data(), rows.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
-    if (n_bins <= 255) {   // the one-byte form (tuning "radial_map8"): what a batch's launch takes is decided from n_bins and the tuning alone
-        std::vector<uint8_t> rows8(rows.size());
-        for (size_t i = 0; i < rows.size(); ++i) rows8[i] = (uint8_t)rows[i];   // (0xFFFF -> 0xFF; every other entry is below 255)
-        HIP_TRY(c, hipMemcpy(c->d_radial_map8, rows8.data(), rows8.size(), hipMemcpyHostToDevice));
-    }
-    c->radial_bins = n_bins;
-    return FFS_OK;
-}
-extern "C" int ffs_ctx_set_radial_bins(ffs_ctx* c, const uint16_t* bin_of_pixel, uint32_t n_bins) {
-    if (!c) return FFS_ERR_INVALID;
-    return guarded(c, [&] { return ffs_ctx_set_radial_bins_impl(c, bin_of_pixel, n_bins); });
-}
-
-extern "C" int ffs_ctx_set_radial_threshold(ffs_ctx* c, double n_iqr) {
-    if (!c) return FFS_ERR_INVALID;
-    if (!std::isfinite(n_iqr) || n_iqr < 0.0 || n_iqr > kRadThrMaxNIqr) {
-        c->err = "ffs_ctx_set_radial_threshold: n_iqr must be finite and in 0 .. 2^20 (the cutoff median + n_iqr * iqr is a uint32)";
-        return FFS_ERR_INVALID;
-    }
-    c->n_iqr = n_iqr;
-    return FFS_OK;
-}
-
-// ---- the per-pixel statistics ------------------------------------------------------------------------------------
-int pixstats_ensure(ffs_ctx* c) {
-    HIP_TRY(c, hipSetDevice(c->device));
-    if (!c->stats_st) HIP_TRY(c, hipStreamCreateWithFlags(&c->stats_st, hipStreamNonBlocking));
-    if (!c->d_stats && hipMalloc(reinterpret_cast<void**>(&c->d_stats), pixstats_layout(c).bytes()) != hipSuccess) {
-        (void)hipGetLastError();
-        c->d_stats = nullptr;
-        c->err = "pixel statistics: hipMalloc(accumulators, " + std::to_string(pixstats_layout(c).bytes() >> 20) + " MB) failed";
-        return FFS_ERR_NOMEM;
-    }
-    return FFS_OK;
-}
-
-extern "C" int ffs_ctx_set_pixel_stats(ffs_ctx* c, int mode) {
-    if (!c) return FFS_ERR_INVALID;
-    if (mode != FFS_PIXEL_STATS_OFF && mode != FFS_PIXEL_STATS_START && mode != FFS_PIXEL_STATS_RESUME) {
-        c->err = "ffs_ctx_set_pixel_stats: mode must be FFS_PIXEL_STATS_OFF (0), _START (1) or _RESUME (2), got " + std::to_string(mode);
-        return FFS_ERR_INVALID;
-    }
-    if (mode == FFS_PIXEL_STATS_OFF) {   // (at any time: a batch in flight carries its own "on")
-        c->stats_on = false;
-        return FFS_OK;
-    }
-    if (mode == FFS_PIXEL_STATS_RESUME && c->stats_started) {
-        c->stats_on = true;
-        return FFS_OK;
-    }
-    if (c->inflight.load() > 0) {
-        c->err = "ffs_ctx_set_pixel_stats: a batch of this context is in flight (ffs_wait for it first): a start zeroes the accumulators";
-        return FFS_ERR_INVALID;
-    }
-    if (const int rc = pixstats_ensure(c); rc != FFS_OK) return rc;
-    HIP_TRY(c, hipMemsetAsync(c->d_stats, 0, pixstats_layout(c).bytes(), c->stats_st));
-    HIP_TRY(c, hipStreamSynchronize(c->stats_st));
-    std::lock_guard<std::mutex> lock(c->stats_mu);
-    c->stats_frames = 0;
-    c->stats_started = true;
-    c->stats_on = true;
-    return FFS_OK;
-}
-
-// Everything is checked before anything is copied.  No batch is in flight, so every launch lies ahead of an event some ffs_wait has seen
-// -- the streams are synchronised all the same, for a batch whose wait failed -- and the planes are copied one at a time and un-interleaved.
-static int ffs_ctx_get_pixel_stats_impl(ffs_ctx* c, ffs_pixel_stats* out) {
-    if (!c->stats_started) {
-        c->err = "ffs_ctx_get_pixel_stats: no statistics yet (ffs_ctx_set_pixel_stats(ctx, FFS_PIXEL_STATS_START) first)";
-        return FFS_ERR_INVALID;
-    }
-    if (c->inflight.load() > 0) {
-        c->err = "ffs_ctx_get_pixel_stats: a batch of this context is in flight (ffs_wait for it first)";
-        return FFS_ERR_INVALID;
-    }
-    HIP_TRY(c, hipSetDevice(c->device));
-    HIP_TRY(c, hipStreamSynchronize(c->stats_st));
-    if (c->dense_st) HIP_TRY(c, hipStreamSynchronize(c->dense_st));
-    const PixStatsLayout P = pixstats_layout(c);
-    const size_t W = (size_t)c->L.W, H = (size_t)c->L.H;
-    std::vector<uint64_t> plane;
-    auto fetch = [&](size_t offset, size_t bytes, uint32_t entry_bytes, void* dst) -> int {
-        if (!dst) return FFS_OK;
-        plane.resize(bytes / 8);
-        HIP_TRY(c, hipMemcpy(plane.data(), c->d_stats + offset, bytes, hipMemcpyDeviceToHost));
-        for (size_t y = 0; y < H; ++y)
-            for (size_t x = 0; x < W; ++x) {
-                const size_t at = P.entry((uint32_t)(y * P.groups + x / P.px), (uint32_t)(x % P.px), entry_bytes);
-                if (entry_bytes == 4) static_cast<uint32_t*>(dst)[y * W + x] = reinterpret_cast<const uint32_t*>(plane.data())[at];
-                else static_cast<uint64_t*>(dst)[y * W + x] = plane[at];
-            }
-        return FFS_OK;
-    };
-    if (const int rc = fetch(0, P.plane32, 4, out->count); rc != FFS_OK) return rc;
-    if (const int rc = fetch(P.plane32, P.plane32, 4, out->max); rc != FFS_OK) return rc;
-    if (const int rc = fetch(2 * P.plane32, P.plane64, 8, out->sum); rc != FFS_OK) return rc;
-    if (const int rc = fetch(2 * P.plane32 + P.plane64, P.plane64, 8, out->sum_sq); rc != FFS_OK) return rc;
-    std::lock_guard<std::mutex> lock(c->stats_mu);
-    out->n_frames = c->stats_frames;
-    return FFS_OK;
-}
-extern "C" int ffs_ctx_get_pixel_stats(ffs_ctx* c, ffs_pixel_stats* out) {
-    if (!c) return FFS_ERR_INVALID;
-    if (!out) {
-        c->err = "ffs_ctx_get_pixel_stats: out is NULL";
-        return FFS_ERR_INVALID;
-    }
-    return guarded(c, [&] { return ffs_ctx_get_pixel_stats_impl(c, out); });
-}
-
 extern "C" int ffs_ctx_set_max_valid_scope(ffs_ctx* c, int scope) {
     if (!c) return FFS_ERR_INVALID;
     if (scope != FFS_MAX_VALID_CENTRE && scope != FFS_MAX_VALID_WINDOW) {

@@ -298,5 +298,27 @@ struct ReflOut {
     unsigned long long sum_intensity;
 };
 
+// Inclusive prefix sum over the 64 lanes in six DPP adds (row_shr 1/2/4/8 inside the rows of 16, then row_bcast:15 and
+// row_bcast:31 carry the row totals on) instead of six ds_bpermute round trips.
+__device__ __forceinline__ uint32_t wave_inclusive_scan(uint32_t v) {
+    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xf, 0xf, false);   // row_shr:1
+    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xf, 0xf, false);   // row_shr:2
+    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xf, 0xf, false);   // row_shr:4
+    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x118, 0xf, 0xf, false);   // row_shr:8
+    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x142, 0xa, 0xf, false);   // row_bcast:15 -> rows 1 and 3
+    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x143, 0xc, 0xf, false);   // row_bcast:31 -> rows 2 and 3
+    return v;
+}
+
+// Pixel j of the 16 bytes a lane loaded: PX = 8 pixels of 16 bits or 4 of 32
+template <int PX>
+__device__ __forceinline__ uint32_t lane_pixel(const uint4& v, int j) {
+    if constexpr (PX == 8) {
+        const uint32_t w = j < 2 ? v.x : j < 4 ? v.y : j < 6 ? v.z : v.w;
+        return (j & 1) ? w >> 16 : w & 0xFFFFu;
+    } else {
+        return j == 0 ? v.x : j == 1 ? v.y : j == 2 ? v.z : v.w;
+    }
+}
 
 }  // namespace ffsamd

@@ -4,7 +4,9 @@
 //   ffs_context.hip  contexts, masks (kernels_mask.hpp), tuning, streams
 //   ffs_submit.hip   one batch (enqueue_batch: plan_batch decides its path once, a BatchPlan with the launch geometry and the threshold route; then the resets,
 //                    the threshold stage and the sparse stage are launched from that plan), submit entry points, compressed input
-//                    (kernels_stream / threshold / extended / window / radthr / ccl / chain / band / decode)
+//                    (kernels_stream / threshold / extended / window / ccl / chain / band / decode / byteoffset)
+//   ffs_products.hip the per-frame products, each from its setter to its accessor: the radial profile, the radial-profile threshold, the per-pixel
+//                    statistics (kernels_radial / radthr / pixstats); ffs_submit.hip calls their launches at their places in a batch
 //   ffs_wait.hip     ffs_wait: overflow re-runs (rerun_batch: the same batch again with a Rerun override), result assembly,
 //                    result accessors
 //   ffs_spotbg.hip   ffs_stream_spot_backgrounds: the per-spot constant background of the last waited batch (kernels_spotbg.hpp)
@@ -12,12 +14,12 @@
 //   ffs_bench.hip    measurement entry points (kernel timings, memory ceiling, native pipeline loop, sqrt self-test)
 // Without HIP, shared with the kernels through ffs_device.h and compiled by a plain C++ test (tests/launch_geometry_check.cc):
 //   launch_geometry.hpp  the frame layout, the launch geometry of the threshold stage (super rows, strips, bands; wave logs and band
-//                        slots a launch needs) and the unit map the kernels invert
+//                        slots a launch needs), the unit map the kernels invert, the row bands and the pixel-count rule of the per-frame products
 //   threshold_route.hpp  the predicate's variants, which instantiation of a kernel family serves one, and a batch's route through the
 //                        threshold stage (tests/threshold_route_check.cc)
 //   tuning.hpp           struct Tuning
 //   spot_background_model.hpp  the decisions of the per-spot background: quartile positions, status order, fence (tests/spot_background_check.cc)
-//   radial_threshold_model.hpp the decisions of the radial-profile threshold (kernels_radthr.hpp, included by ffs_submit.hip): status order and the
+//   radial_threshold_model.hpp the decisions of the radial-profile threshold (kernels_radthr.hpp, included by ffs_products.hip): status order and the
 //                        cutoff's two separately rounded operations (tests/radial_threshold_check.cc)
 // No exception leaves the library (guarded()).
 #pragma once
@@ -421,6 +423,13 @@ static int guarded(ffs_ctx* c, F&& body) {
         }                                                                               \
     } while (0)
 
+// (a step that failed has left its text in the context's error: its code is passed on)
+#define FFS_TRY(expr)                    \
+    do {                                 \
+        const int rc_ = (expr);          \
+        if (rc_ != FFS_OK) return rc_;   \
+    } while (0)
+
 // ---- small helpers ------------------------------------------------------------------------------------------
 static inline ParamSnapshot snapshot_of(const ffs_ctx* c) {
     return ParamSnapshot{c->params, c->max_valid_scope, c->gain, c->has_gain_map, c->radial_bins, c->stats_on,
@@ -526,24 +535,30 @@ bool wave_logs_for(ffs_stream* s, ThresholdArgs& a, const StreamGeometry& g, con
 void launch_dense_kernel(ffs_stream* s, const ThresholdRoute& route, const ThresholdArgs& a, const StreamGeometry& g, uint32_t n_frames, hipEvent_t start,
                          hipEvent_t stop, bool plane_clean = false, bool counts_clean = false);
 void launch_dense_rest(ffs_stream* s, const ThresholdRoute& route, const ThresholdArgs& a, uint32_t n_frames);
+// ffs_products.hip
 // The radial profile: ensure makes room for the profiles of this stream's batches under a map of `bins` bins (no batch of the stream in flight);
-// launch puts the two kernels into `st` for frames that are in place there, over s->batch.radial_bins bins, writing the host buffer whose turn
-// it is (start / stop: events on the two dispatches, either may be null); publish is ffs_wait's side.
+// launch puts the two kernels into `st` for frames that are in place there (start / stop: events on the two dispatches, either may be null).
+// launch_radial_dense / _stage: the batch's two places for it, behind the threshold stage's kernels or behind the sparse launch; publish is ffs_wait's side.
 int radial_ensure_buffers(ffs_stream* s, uint32_t bins);
 int radial_launch(ffs_stream* s, const void* d_img, size_t pitch, size_t fstride, uint32_t n_frames, hipStream_t st, hipEvent_t start, hipEvent_t stop);
+int launch_radial_dense(ffs_stream* s, uint32_t n);
+int launch_radial_stage(ffs_stream* s, uint32_t n);
 void radial_publish(ffs_stream* s);
 void radial_free(ffs_stream* s);
 // The radial-profile threshold (ThresholdStage::kRadial): ensure makes the stream's buffers and asks the device for the histogram's LDS (first
-// use); launch_dense_kernel / launch_dense_rest launch its histogram and its cut + strong kernels; publish is ffs_wait's side.
+// use); hist and rest (the cut and strong kernels) launch into s->st from the threshold stage's arguments; publish is ffs_wait's side.
 int radthr_ensure_buffers(ffs_stream* s);
+void launch_radthr_hist(ffs_stream* s, const ThresholdArgs& t, uint32_t n_frames, hipEvent_t start, hipEvent_t stop);
+void launch_radthr_rest(ffs_stream* s, const ThresholdArgs& t, uint32_t n_frames, hipEvent_t stop);
 void radthr_publish(ffs_stream* s);
 void radthr_free(ffs_stream* s);
-// The per-pixel statistics: the kernel over n_frames frames that are in place in `st`, into the context's accumulators (which exist), with the
-// limit of `max_valid`; start / stop ride on the first and the last dispatch (either may be null).  The caller keeps two launches apart.
+// The per-pixel statistics: ensure makes the accumulators and the context's stream on first use; launch puts the kernel over n_frames frames that
+// are in place in `st` (the caller keeps two launches apart).  launch_pixel_stats does that for a batch, once; join_pixel_stats makes its sparse stream wait.
+int pixstats_ensure(ffs_ctx* c);
 int pixstats_launch(ffs_ctx* c, const void* d_img, size_t pitch, size_t fstride, uint32_t n_frames, long long max_valid, hipStream_t st, hipEvent_t start,
                     hipEvent_t stop);
-// ffs_context.hip
-int pixstats_ensure(ffs_ctx* c);   // the accumulators and the context's stream, made on first use (contents undefined)
+int launch_pixel_stats(ffs_stream* s, uint32_t n);
+int join_pixel_stats(ffs_stream* s);
 // ffs_wait.hip
 int ffs_wait_impl(ffs_stream* s, const ffs_frame_result** results, uint32_t* n_results);
 void ahead_register(ffs_stream* s);   // the batch just enqueued may be assembled ahead of its ffs_wait

@@ -126,9 +126,7 @@ static int spot_backgrounds_impl(ffs_stream* s, uint32_t border, const ffs_spot_
     a.mpitch = L.mpitch;
     a.W = L.W;
     a.H = L.H;
-    // (max_valid under both of its scopes, and the p < 2^24 rule of 32-bit pixels: the radial profile's limit)
-    const long long mv = s->batch.params.max_valid;
-    a.limit = mv >= 0 ? (uint32_t)std::min<long long>(mv, (1ll << 24) - 1) + 1u : 1u << 24;
+    a.limit = counting_limit(s->batch.params.max_valid);
     a.border = (int)border;
     a.n = (uint32_t)n;
     a.boxes = static_cast<const SpotBgBox*>(s->d_bg_boxes);

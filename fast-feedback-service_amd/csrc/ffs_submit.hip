@@ -14,9 +14,6 @@
 #include "kernels_decode.hpp"
 #include "kernels_byteoffset.hpp"
 #include "kernels_window.hpp"
-#include "kernels_radial.hpp"
-#include "kernels_radthr.hpp"
-#include "kernels_pixstats.hpp"
 
 bool chain_prepare_device() {   // more than 64 KB of dynamic LDS has to be asked for, per device
     const hipError_t e1 = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_frame_chain<uint16_t>), hipFuncAttributeMaxDynamicSharedMemorySize, kChainDynBytes);
@@ -82,8 +79,7 @@ static void set_buffers(ThresholdArgs& a, const ffs_stream* s, const void* img, 
     a.ext_variant = route.ext_variant;
 }
 static void set_predicate(ThresholdArgs& a, const ffs_params& p, bool trusted, double gain, const ffs_ctx* map_of) {
-    // (exclusive; the oracle's < 2^24 rule for 32-bit pixels holds on top of max_valid, and 16-bit pixels never reach it)
-    a.nb_limit = trusted ? (uint32_t)std::min<long long>(p.max_valid, (1ll << 24) - 1) + 1u : 1u << 24;
+    a.nb_limit = counting_limit(trusted ? p.max_valid : -1);   // (exclusive; trusted: the window scope with a max_valid)
     a.kS = (float)(p.nsig_s * p.nsig_s * (1.0 - 1.0 / 65536.0));
     a.kB = (float)(p.nsig_b * (1.0 - 1.0 / 1048576.0));
     a.min_count = p.min_count;
@@ -359,124 +355,6 @@ bool wave_logs_for(ffs_stream* s, ThresholdArgs& a, const StreamGeometry& g, con
     return true;
 }
 
-// ---- the radial-profile threshold (kernels_radthr.hpp) --------------------------------------------------------
-// The histogram's workgroups hold a whole CU's LDS each, so a launch aims at two per CU and at most 64 bands a frame; tuning "radthr_bands"
-// sets the bands instead (clamped to 1..H).
-constexpr uint32_t kRadThrTargetGroups = 512, kRadThrMaxBands = 64;
-static void radthr_bands(const ffs_ctx* c, uint32_t n_frames, uint32_t& n_bands, uint32_t& band_rows) {
-    const uint32_t H = (uint32_t)c->L.H;
-    const uint32_t want = c->tune.radthr_bands > 0 ? std::clamp<uint32_t>((uint32_t)c->tune.radthr_bands, 1u, H)
-                                                   : std::clamp<uint32_t>((kRadThrTargetGroups + n_frames - 1) / n_frames, 1u, std::min(H, kRadThrMaxBands));
-    band_rows = (H + want - 1) / want;
-    n_bands = (H + band_rows - 1) / band_rows;
-}
-using RadThrKernel = void (*)(RadThrArgs);
-// form: tuning "radthr_form" -- 1 = one LDS add per counting pixel, 2 = a run kept in registers, 0 = the faster of the two as measured
-// (DESIGN.md section 3.9): the run for 16-bit pixels, the plain add for 32-bit
-static RadThrKernel radthr_hist_kernel(int pixel_bytes, int form) {
-    const bool run = form == 0 ? pixel_bytes == 2 : form == 2;
-    return pixel_bytes == 2 ? (run ? k_radthr_hist<uint16_t, true> : k_radthr_hist<uint16_t, false>)
-                            : (run ? k_radthr_hist<uint32_t, true> : k_radthr_hist<uint32_t, false>);
-}
-
-void radthr_free(ffs_stream* s) {
-    if (s->d_radthr_hist) (void)hipFree(s->d_radthr_hist);
-    for (ffs_radial_shell* p : s->h_radthr)
-        if (p) (void)hipHostFree(p);
-    s->d_radthr_hist = s->d_radthr_cut = nullptr;
-    s->h_radthr[0] = s->h_radthr[1] = nullptr;
-    s->radthr_out = nullptr;
-}
-
-// Histograms and cutoffs (one allocation) and the two record buffers, for max_batch frames of kRadThrMaxBins shells: made by the stream's
-// first batch of the algorithm and kept.  A table of more than 64 KB of dynamic LDS has to be asked for, per device (chain_prepare_device):
-// a device that refuses cannot run the algorithm, and says so.
-int radthr_ensure_buffers(ffs_stream* s) {
-    if (s->d_radthr_hist) return FFS_OK;
-    ffs_ctx* c = s->ctx;
-    for (int form = 1; form <= 2; ++form)
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(radthr_hist_kernel(c->pixel_bytes, form)), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)radthr_lds_bytes(kRadThrMaxBins)) != hipSuccess) {
-            (void)hipGetLastError();
-            c->err = "radial_profile threshold: the device refuses the histogram's " + std::to_string(radthr_lds_bytes(kRadThrMaxBins)) + " bytes of LDS";
-            return FFS_ERR_DEVICE;
-        }
-    const size_t shells = (size_t)s->max_batch * kRadThrMaxBins;
-    uint32_t* d = nullptr;
-    if (hipMalloc(reinterpret_cast<void**>(&d), shells * (kRadThrCounters + 1) * 4u) != hipSuccess) {
-        (void)hipGetLastError();
-        c->err = "radial_profile threshold: hipMalloc(histograms) failed";
-        return FFS_ERR_NOMEM;
-    }
-    for (int i = 0; i < 2; ++i)
-        if (hipHostMalloc(reinterpret_cast<void**>(&s->h_radthr[i]), shells * sizeof(ffs_radial_shell), hipHostMallocDefault) != hipSuccess
-            || hipHostGetDevicePointer(reinterpret_cast<void**>(&s->h_radthr_dev[i]), s->h_radthr[i], 0) != hipSuccess) {
-            (void)hipGetLastError();
-            (void)hipFree(d);
-            for (ffs_radial_shell*& p : s->h_radthr) {
-                if (p) (void)hipHostFree(p);
-                p = nullptr;
-            }
-            c->err = "radial_profile threshold: hipHostMalloc(records) failed";
-            return FFS_ERR_NOMEM;
-        }
-    s->d_radthr_hist = d;
-    s->d_radthr_cut = d + shells * kRadThrCounters;
-    return FFS_OK;
-}
-
-// The stage's arguments from the threshold stage's (buffers, pitches, threshold, what the sparse stage wants) and the batch's snapshot
-static RadThrArgs make_radthr_args(const ffs_stream* s, const ThresholdArgs& t, uint32_t n_frames) {
-    const ffs_ctx* c = s->ctx;
-    RadThrArgs a{};
-    a.in.image = t.image;
-    a.in.frame_stride = t.frame_stride;
-    a.in.pitch = t.pitch;
-    a.in.maskbits = t.maskbits;
-    a.in.mpitch = t.mpitch;
-    a.in.bins = c->d_radial_map;
-    a.in.bin_pitch = (uint32_t)t.pitch_px;
-    a.in.W = t.W;
-    a.in.H = t.H;
-    a.in.n_bins = s->batch.radthr_bins;
-    radthr_bands(c, n_frames, a.in.n_bands, a.in.band_rows);
-    // (max_valid under both of its scopes, and p < 2^24 for 32-bit pixels: the radial profile's limit, radial_launch)
-    a.in.limit = t.max_valid >= 0 ? (uint32_t)std::min<long long>(t.max_valid, (1ll << 24) - 1) + 1u : 1u << 24;
-    a.hist = s->d_radthr_hist;
-    a.cut = s->d_radthr_cut;
-    a.shells = s->h_radthr_dev[s->radthr_turn];
-    a.n_iqr = s->batch.n_iqr;
-    a.threshold = t.threshold;
-    a.bits = t.bits;
-    a.strong_bytes = t.strong_bytes;
-    a.tile_counts = t.tile_counts;
-    a.occ = t.occ;
-    a.occ_frame_words = t.occ_frame_words;
-    a.occ_spr = t.occ_spr;
-    a.bpitch = t.bpitch;
-    a.plane_frame_stride = t.plane_frame_stride;
-    a.bytes_frame_stride = t.bytes_frame_stride;
-    a.n_tiles = t.n_tiles;
-    a.dense_mask = t.dense_mask;
-    a.s_strips = ((uint32_t)(t.W + 7) / 8u + 63u) / 64u;
-    return a;
-}
-// The histogram: the frames' tables are zeroed ahead of the launch, outside its events (radthr_ensure_buffers has run)
-static void launch_radthr_hist(ffs_stream* s, const ThresholdArgs& t, uint32_t n_frames, hipEvent_t start, hipEvent_t stop) {
-    const RadThrArgs a = make_radthr_args(s, t, n_frames);
-    (void)hipMemsetAsync(a.hist, 0, (size_t)n_frames * a.in.n_bins * kRadThrCounters * 4u, s->st);
-    hipExtLaunchKernelGGL(radthr_hist_kernel(s->ctx->pixel_bytes, s->ctx->tune.radthr_form), dim3(n_frames, a.in.n_bands), dim3(kRadThrHistThreads),
-                          radthr_lds_bytes(a.in.n_bins), s->st, start, stop, 0, a);
-}
-// ... and the cutoffs and the strong pixels behind it; `stop` rides on the last dispatch
-static void launch_radthr_rest(ffs_stream* s, const ThresholdArgs& t, uint32_t n_frames, hipEvent_t stop) {
-    const RadThrArgs a = make_radthr_args(s, t, n_frames);
-    hipLaunchKernelGGL(k_radthr_cut, dim3(a.in.n_bins, n_frames), dim3(64), 0, s->st, a);
-    const dim3 grid(a.s_strips * (uint32_t)a.n_tiles, n_frames);
-    if (s->ctx->pixel_bytes == 2) hipExtLaunchKernelGGL(k_radthr_strong<uint16_t>, grid, dim3(64), 0, s->st, nullptr, stop, 0, a);
-    else hipExtLaunchKernelGGL(k_radthr_strong<uint32_t>, grid, dim3(64), 0, s->st, nullptr, stop, 0, a);
-}
-
 // The threshold stage where all of it runs in s->st (ffs_internal.hpp): the dense kernel ...
 void launch_dense_kernel(ffs_stream* s, const ThresholdRoute& route, const ThresholdArgs& a, const StreamGeometry& g, uint32_t n_frames, hipEvent_t start,
                          hipEvent_t stop, bool plane_clean, bool counts_clean) {
@@ -553,13 +431,6 @@ static bool band_stage_for(ffs_stream* s, const StreamGeometry& g, size_t fstrid
 // clears what earlier batches left behind; launch_threshold_stage() enqueues the dense kernels and makes the batch's sparse stream
 // wait for them; launch_sparse_stage() enqueues compaction -> connected components -> records behind that, and the batch's last
 // event.  The three steps that launch branch on the plan and decide nothing again.
-
-// (a step that failed has left its text in the context's error: its code is passed on)
-#define FFS_TRY(expr)                    \
-    do {                                 \
-        const int rc_ = (expr);          \
-        if (rc_ != FFS_OK) return rc_;   \
-    } while (0)
 
 struct BatchPlan {
     uint32_t n = 0;                   // frames of the batch
@@ -916,202 +787,6 @@ static int finish_enqueue(ffs_stream* s, uint32_t n, bool bits_dirty, bool count
     return FFS_OK;
 }
 
-// ---- the radial profile (kernels_radial.hpp) -----------------------------------------------------------------
-// Few fat workgroups over contiguous row bands: about 2048 workgroups a launch (eight per CU) and at most 64 bands a frame, which bounds
-// the partials at 64 x n_bins x 20 B a frame -- 1.3 MB at 1024 bins, under 4 % of an Eiger frame.
-constexpr uint32_t kRadialTargetGroups = 2048, kRadialMaxBands = 64;
-static void radial_bands(const Layout& L, uint32_t n_frames, uint32_t& n_bands, uint32_t& band_rows) {
-    const uint32_t want = std::clamp<uint32_t>((kRadialTargetGroups + n_frames - 1) / n_frames, 1u, std::min<uint32_t>((uint32_t)L.H, kRadialMaxBands));
-    band_rows = ((uint32_t)L.H + want - 1) / want;
-    n_bands = ((uint32_t)L.H + band_rows - 1) / band_rows;
-}
-// bytes of a result buffer: sums, sums of squares, counts, [max_batch][bins] each
-static inline size_t radial_host_bytes(const ffs_stream* s, uint32_t bins) { return (size_t)s->max_batch * bins * 20u; }
-
-void radial_free(ffs_stream* s) {
-    if (s->d_radial_part) (void)hipFree(s->d_radial_part);
-    for (uint8_t* p : s->h_radial)
-        if (p) (void)hipHostFree(p);
-    for (uint8_t* p : s->radial_retired) (void)hipHostFree(p);
-    s->d_radial_part = nullptr;
-    s->h_radial[0] = s->h_radial[1] = nullptr;
-    s->radial_retired.clear();
-    s->radial_part_entries = 0;
-    s->h_radial_bins = 0;
-}
-
-// Room for the profile of a batch of up to max_batch frames under a map of `bins` bins.  Only on a stream with no batch in flight.
-int radial_ensure_buffers(ffs_stream* s, uint32_t bins) {
-    ffs_ctx* c = s->ctx;
-    size_t slots = 0;   // the most (frame, band) pairs a batch of this stream can have
-    for (uint32_t nf = 1; nf <= s->max_batch; ++nf) {
-        uint32_t nb = 0, rows = 0;
-        radial_bands(c->L, nf, nb, rows);
-        slots = std::max(slots, (size_t)nf * nb);
-    }
-    if (slots * bins > s->radial_part_entries) {
-        if (s->d_radial_part) (void)hipFree(s->d_radial_part);
-        s->d_radial_part = nullptr;
-        s->radial_part_entries = 0;
-        if (hipMalloc(reinterpret_cast<void**>(&s->d_radial_part), slots * bins * 20u) != hipSuccess) {
-            (void)hipGetLastError();
-            c->err = "radial profile: hipMalloc(partials) failed";
-            return FFS_ERR_NOMEM;
-        }
-        s->radial_part_entries = slots * bins;
-    }
-    if (bins > s->h_radial_bins) {
-        // (the buffer the last wait handed out may still be read: it is freed at the next wait; the other one nobody reads)
-        for (int i = 0; i < 2; ++i) {
-            if (!s->h_radial[i]) continue;
-            if (s->h_radial[i] == s->radial_out) s->radial_retired.push_back(s->h_radial[i]);
-            else (void)hipHostFree(s->h_radial[i]);
-            s->h_radial[i] = nullptr;
-        }
-        s->h_radial_bins = 0;
-        for (int i = 0; i < 2; ++i) {
-            if (hipHostMalloc(reinterpret_cast<void**>(&s->h_radial[i]), radial_host_bytes(s, bins), hipHostMallocDefault) != hipSuccess
-                || hipHostGetDevicePointer(reinterpret_cast<void**>(&s->h_radial_dev[i]), s->h_radial[i], 0) != hipSuccess) {
-                (void)hipGetLastError();
-                c->err = "radial profile: hipHostMalloc(results) failed";
-                return FFS_ERR_NOMEM;
-            }
-        }
-        s->h_radial_bins = bins;
-    }
-    return FFS_OK;
-}
-
-int radial_launch(ffs_stream* s, const void* d_img, size_t pitch, size_t fstride, uint32_t n_frames, hipStream_t st, hipEvent_t start, hipEvent_t stop) {
-    ffs_ctx* c = s->ctx;
-    const Layout& L = c->L;
-    const uint32_t bins = s->batch.radial_bins;
-    const size_t B = s->max_batch;
-    RadialArgs a{};
-    a.image = d_img;
-    a.frame_stride = fstride;
-    a.pitch = (uint32_t)pitch;
-    a.maskbits = c->d_maskbits;
-    a.mpitch = L.mpitch;
-    a.bins = c->d_radial_map;
-    a.bin_pitch = (uint32_t)L.pitch_px;
-    a.W = L.W;
-    a.H = L.H;
-    a.n_bins = bins;
-    radial_bands(L, n_frames, a.n_bands, a.band_rows);
-    // (max_valid under both of its scopes, and the oracle's neighbour rule for 32-bit pixels: what set_predicate calls nb_limit under the window scope)
-    const long long mv = s->batch.params.max_valid;
-    a.limit = mv >= 0 ? (uint32_t)std::min<long long>(mv, (1ll << 24) - 1) + 1u : 1u << 24;
-    const size_t part = s->radial_part_entries;
-    a.p_sum = reinterpret_cast<uint64_t*>(s->d_radial_part);
-    a.p_sq = a.p_sum + part;
-    a.p_count = reinterpret_cast<uint32_t*>(a.p_sq + part);
-    uint8_t* out = s->h_radial_dev[s->radial_turn];
-    a.r_sum = reinterpret_cast<uint64_t*>(out);
-    a.r_sq = a.r_sum + B * bins;
-    a.r_count = reinterpret_cast<uint32_t*>(a.r_sq + B * bins);
-    if ((size_t)n_frames * a.n_bands * bins > part || bins > s->h_radial_bins || !a.bins) {
-        c->err = "radial profile: the stream's buffers do not hold this batch";
-        return FFS_ERR_INVALID;
-    }
-    const dim3 grid(n_frames, a.n_bands);
-    // (the one-byte form of the map: tuning "radial_map8", for maps of at most 255 bins -- ffs_ctx_set_radial_bins keeps both forms then)
-    a.bins8 = (c->tune.radial_map8 && bins <= 255) ? c->d_radial_map8 : nullptr;
-    using RadialKernel = void (*)(RadialArgs);
-    const RadialKernel k = c->pixel_bytes == 2 ? (a.bins8 ? k_radial<uint16_t, true> : k_radial<uint16_t, false>)
-                                               : (a.bins8 ? k_radial<uint32_t, true> : k_radial<uint32_t, false>);
-    hipExtLaunchKernelGGL(k, grid, dim3(kRadialThreads), radial_lds_bytes(bins), st, start, nullptr, 0, a);
-    hipExtLaunchKernelGGL(k_radial_sum, dim3((bins + 255) / 256, n_frames), dim3(256), 0, st, nullptr, stop, 0, a);
-    HIP_TRY(c, hipGetLastError());
-    return FFS_OK;
-}
-
-// The batch's profile, once: launched by the batch's first enqueue (radial_todo: the re-runs of ffs_wait find it off), for frames that are in
-// place in `st`.  Where: tuning "radial_stream".  0 (default): in the batch's SPARSE stream behind the sparse launch and ahead of the batch's
-// last event -- the stream has waited for the threshold stage there.  1: in the DENSE stream behind the threshold stage's kernels; the sparse
-// stream then waits for ev[5], recorded behind it, ahead of the batch's last event (ffs_wait records ev[5] anew only after that event).
-static int launch_radial(ffs_stream* s, uint32_t n, hipStream_t st) {
-    s->radial_todo = false;
-    FFS_TRY(radial_ensure_buffers(s, s->batch.radial_bins));   // (first use, or a map with more bins: the stream has no batch in flight yet)
-    return radial_launch(s, s->cur_img, s->cur_pitch, s->cur_fstride, n, st, nullptr, nullptr);
-}
-static inline bool radial_wanted(const ffs_stream* s) { return s->radial_todo && s->batch.radial_bins != 0; }
-static int launch_radial_dense(ffs_stream* s, uint32_t n) {
-    if (!radial_wanted(s) || s->ctx->tune.radial_stream != 1 || s->st2 == s->st || s->ctx->tune.dense_overlap != 0) return FFS_OK;   // (dense_overlap: the stage's kernel may be in the partner stream)
-    FFS_TRY(launch_radial(s, n, s->st));
-    HIP_TRY(s->ctx, hipEventRecord(s->ev[5], s->st));
-    HIP_TRY(s->ctx, hipStreamWaitEvent(s->st2, s->ev[5], 0));
-    return FFS_OK;
-}
-static int launch_radial_stage(ffs_stream* s, uint32_t n) {
-    if (!radial_wanted(s)) return FFS_OK;
-    return launch_radial(s, n, s->st2);
-}
-// ---- the per-pixel statistics (kernels_pixstats.hpp) -----------------------------------------------------------
-int pixstats_launch(ffs_ctx* c, const void* d_img, size_t pitch, size_t fstride, uint32_t n_frames, long long max_valid, hipStream_t st, hipEvent_t start,
-                    hipEvent_t stop) {
-    const PixStatsLayout P = pixstats_layout(c);
-    if (!c->d_stats || n_frames == 0) {
-        c->err = "pixel statistics: the context has no accumulators";
-        return FFS_ERR_INVALID;
-    }
-    PixStatsArgs a{};
-    a.frame_stride = fstride;
-    a.pitch = (uint32_t)pitch;
-    a.groups = P.groups;
-    a.n_lanes = P.n_lanes;
-    // (max_valid under both of its scopes, and p < 2^24 for 32-bit pixels: RadialArgs::limit)
-    a.limit = max_valid >= 0 ? (uint32_t)std::min<long long>(max_valid, (1ll << 24) - 1) + 1u : 1u << 24;
-    a.count = reinterpret_cast<uint4*>(c->d_stats);
-    a.max = reinterpret_cast<uint4*>(c->d_stats + P.plane32);
-    a.sum = reinterpret_cast<uint4*>(c->d_stats + 2 * P.plane32);
-    a.sum_sq = reinterpret_cast<uint4*>(c->d_stats + 2 * P.plane32 + P.plane64);
-    const dim3 grid((P.n_lanes + kPixStatsThreads - 1) / kPixStatsThreads);
-    // (one launch holds at most kPixStatsMaxFrames frames -- the 16-bit kernel's 32-bit sums; a longer batch is several, one behind the other)
-    for (uint32_t f0 = 0; f0 < n_frames; f0 += kPixStatsMaxFrames) {
-        a.image = static_cast<const uint8_t*>(d_img) + (size_t)f0 * fstride;
-        a.n_frames = std::min(n_frames - f0, kPixStatsMaxFrames);
-        const bool first = f0 == 0, last = n_frames - f0 <= kPixStatsMaxFrames;
-        if (c->pixel_bytes == 2) hipExtLaunchKernelGGL(k_pixel_stats<uint16_t>, grid, dim3(kPixStatsThreads), 0, st, first ? start : nullptr, last ? stop : nullptr, 0, a);
-        else hipExtLaunchKernelGGL(k_pixel_stats<uint32_t>, grid, dim3(kPixStatsThreads), 0, st, first ? start : nullptr, last ? stop : nullptr, 0, a);
-    }
-    HIP_TRY(c, hipGetLastError());
-    return FFS_OK;
-}
-
-// The batch's frames into the context's statistics, once: launched by the batch's first enqueue (stats_todo: the re-runs of ffs_wait find it
-// off).  The accumulators belong to the context and every launch reads, adds and writes them whole, so two launches must never overlap,
-// whichever ffs_streams and threads they come from.  Where: tuning "stats_stream".
-//   0: the context's own HIP stream, in which launches follow one another.  It waits for the event behind which the frames are in place --
-//      ev[1], recorded behind the upload or the decode; resident frames (ffs_submit_device) are in place as they come -- so the kernel may run
-//      beside the batch's threshold stage, and the dense stream gets no packet of ours.
-//   1: the batch's dense stream behind the threshold stage's kernels.  Only where that is ONE stream for the whole context: not under
-//      "sched" 0 (a HIP stream per ffs_stream) and not under "dense_overlap" 1 (the stage's kernel may be in the partner stream); 0 is taken there.
-// Either way ev_stats is recorded behind the launch and the batch's sparse stream waits for it ahead of the batch's last event
-// (join_pixel_stats): the frames stay valid until ffs_wait returns, and every waited batch is in what ffs_ctx_get_pixel_stats copies.
-// stats_mu makes wait, launch, record and the frame count one step.
-static int launch_pixel_stats(ffs_stream* s, uint32_t n) {
-    if (!s->stats_todo) return FFS_OK;
-    s->stats_todo = false;
-    if (!s->batch.pixel_stats) return FFS_OK;
-    ffs_ctx* c = s->ctx;
-    if (!s->ev_stats) HIP_TRY(c, hipEventCreateWithFlags(&s->ev_stats, hipEventDisableTiming));
-    const bool dense = c->tune.stats_stream == 1 && s->st2 != s->st && c->tune.dense_overlap == 0;
-    std::lock_guard<std::mutex> lock(c->stats_mu);
-    hipStream_t st = dense ? s->st : c->stats_st;
-    if (!dense && !s->dev_input) HIP_TRY(c, hipStreamWaitEvent(st, s->ev[1], 0));
-    FFS_TRY(pixstats_launch(c, s->cur_img, s->cur_pitch, s->cur_fstride, n, s->batch.params.max_valid, st, nullptr, nullptr));
-    HIP_TRY(c, hipEventRecord(s->ev_stats, st));
-    c->stats_frames += n;
-    s->stats_join = true;
-    return FFS_OK;
-}
-static int join_pixel_stats(ffs_stream* s) {
-    if (!s->stats_join) return FFS_OK;
-    s->stats_join = false;
-    HIP_TRY(s->ctx, hipStreamWaitEvent(s->st2, s->ev_stats, 0));
-    return FFS_OK;
-}
 using ChainKernel = void (*)(ChainArgs);
 static ChainKernel frame_chain_kernel(const BatchPlan& plan, int pixel_bytes) {
     if (plan.use_log) return pixel_bytes == 2 ? k_frame_chain<uint16_t, false, true> : k_frame_chain<uint32_t, false, true>;

@@ -588,72 +588,6 @@ int ffs_wait_impl(ffs_stream* s, const ffs_frame_result** results, uint32_t* n_r
     return FFS_OK;
 }
 
-// The radial profile of the batch this wait returns becomes what ffs_stream_radial_profile reads (once per batch: the wait of a re-run
-// is this same function, and finds nothing pending the second time).  The two host buffers take turns, so the next batch writes the other one.
-void radial_publish(ffs_stream* s) {
-    if (!s->radial_pending) return;
-    s->radial_pending = false;
-    for (uint8_t* p : s->radial_retired) (void)hipHostFree(p);   // (what the previous wait had handed out before the buffers grew)
-    s->radial_retired.clear();
-    s->radial_out = nullptr;
-    if (s->batch.radial_bins) {
-        s->radial_out = s->h_radial[s->radial_turn];
-        s->radial_turn ^= 1;
-    }
-    s->radial_out_bins = s->batch.radial_bins;
-    s->radial_out_frames = s->n_frames;
-}
-
-extern "C" int ffs_stream_radial_profile(ffs_stream* s, uint32_t frame_in_batch, ffs_radial_profile* out) {
-    if (!s || !out || !stream_handle_ok(s)) return FFS_ERR_INVALID;
-    ffs_ctx* c = s->ctx;
-    if (!s->radial_out || s->radial_out_bins == 0) {
-        c->err = "ffs_stream_radial_profile: the last batch ffs_wait returned on this stream was submitted without a bin map (ffs_ctx_set_radial_bins)";
-        return FFS_ERR_INVALID;
-    }
-    if (frame_in_batch >= s->radial_out_frames) {
-        c->err = "ffs_stream_radial_profile: frame_in_batch " + std::to_string(frame_in_batch) + " is out of range: the batch had " + std::to_string(s->radial_out_frames) + " frames";
-        return FFS_ERR_INVALID;
-    }
-    // (the layout k_radial_sum writes: sums, sums of squares, counts, [max_batch][bins] each)
-    const size_t bins = s->radial_out_bins, plane = (size_t)s->max_batch * bins;
-    const uint64_t* sum = reinterpret_cast<const uint64_t*>(s->radial_out);
-    out->n_bins = s->radial_out_bins;
-    out->sum = sum + (size_t)frame_in_batch * bins;
-    out->sum_sq = sum + plane + (size_t)frame_in_batch * bins;
-    out->count = reinterpret_cast<const uint32_t*>(sum + 2 * plane) + (size_t)frame_in_batch * bins;
-    return FFS_OK;
-}
-
-// The records of the radial-profile threshold, the same way and under the same flag (radial_pending: once per batch; a re-run inside ffs_wait
-// computed the same records into the same buffer).  A batch of another algorithm hands out that it has none.
-void radthr_publish(ffs_stream* s) {
-    if (!s->radial_pending) return;
-    s->radthr_out = nullptr;
-    if (s->batch.radthr_bins) {
-        s->radthr_out = s->h_radthr[s->radthr_turn];
-        s->radthr_turn ^= 1;
-    }
-    s->radthr_out_bins = s->batch.radthr_bins;
-    s->radthr_out_frames = s->n_frames;
-}
-
-extern "C" int ffs_stream_radial_thresholds(ffs_stream* s, uint32_t frame_in_batch, const ffs_radial_shell** out, uint32_t* n_bins) {
-    if (!s || !out || !n_bins || !stream_handle_ok(s)) return FFS_ERR_INVALID;
-    ffs_ctx* c = s->ctx;
-    if (!s->radthr_out || s->radthr_out_bins == 0) {
-        c->err = "ffs_stream_radial_thresholds: the last batch ffs_wait returned on this stream did not run the radial_profile algorithm (FFS_ALGO_RADIAL_PROFILE)";
-        return FFS_ERR_INVALID;
-    }
-    if (frame_in_batch >= s->radthr_out_frames) {
-        c->err = "ffs_stream_radial_thresholds: frame_in_batch " + std::to_string(frame_in_batch) + " is out of range: the batch had " + std::to_string(s->radthr_out_frames) + " frames";
-        return FFS_ERR_INVALID;
-    }
-    *out = s->radthr_out + (size_t)frame_in_batch * s->radthr_out_bins;   // (the layout k_radthr_cut writes: [frame][bins of the batch])
-    *n_bins = s->radthr_out_bins;
-    return FFS_OK;
-}
-
 extern "C" int ffs_stream_batch_arrays(ffs_stream* s, const ffs_box** boxes, uint32_t* n_boxes,
                                        const ffs_reflection** refls, uint32_t* n_refls) {
     if (!s) return FFS_ERR_INVALID;

@@ -1,12 +1,12 @@
-// kernels_pixstats.hpp (included by ffs_submit.hip only) -- the per-pixel statistics over a run (ffs_ctx_set_pixel_stats, DESIGN.md
+// kernels_pixstats.hpp (included by ffs_products.hip only) -- the per-pixel statistics over a run (ffs_ctx_set_pixel_stats, DESIGN.md
 // section 3.7): per pixel, in how many frames it counted, the sum and the sum of squares of its values there, and the largest of them --
-// what a mask, a gain map and a "virtual powder pattern" are made from.  A pixel value counts when p < limit (max_valid + 1 and 2^24,
-// whichever is smaller: RadialArgs::limit, the same rule); the valid-pixel mask plays no part.  The reference has no counterpart.
+// what a mask, a gain map and a "virtual powder pattern" are made from.  A pixel value counts when p < limit (launch_geometry.hpp,
+// counting_limit: the radial profile's rule); the valid-pixel mask plays no part.  The reference has no counterpart.
 //
 // One launch a batch, no atomics: a lane owns 16 B of one pixel row -- PX = 8 or 4 pixels -- and walks the batch's frames at that
 // position, kPixStatsUnroll independent loads in flight, with count, sum, sum of squares and maximum of its PX pixels in registers; then
 // it adds them into the context's accumulators with ONE read-modify-write.  The accumulator traffic is per batch, not per frame.  Two
-// launches on the same accumulators must not overlap: the host serialises them (ffs_submit.hip, launch_pixel_stats).
+// launches on the same accumulators must not overlap: the host serialises them (ffs_products.hip, launch_pixel_stats).
 //
 // The accumulators are laid out for that read-modify-write, not for the caller (ffs_ctx_get_pixel_stats un-interleaves them,
 // pixstats_entry in ffs_internal.hpp is the host's statement of where an entry lies): lanes are numbered row by row, i = y * groups + x / PX, and
@@ -54,13 +54,7 @@ __device__ __forceinline__ void pixstats_fold(PixStatsRegs<PixelT>& r, const uin
     constexpr int PX = PixStatsRegs<PixelT>::PX;
 #pragma unroll
     for (int j = 0; j < PX; ++j) {
-        uint32_t p;
-        if constexpr (PX == 8) {
-            const uint32_t w = j < 2 ? v.x : j < 4 ? v.y : j < 6 ? v.z : v.w;
-            p = (j & 1) ? w >> 16 : w & 0xFFFFu;
-        } else {
-            p = j == 0 ? v.x : j == 1 ? v.y : j == 2 ? v.z : v.w;
-        }
+        const uint32_t p = lane_pixel<PX>(v, j);
         const bool ok = p < limit;
         const uint32_t q = ok ? p : 0u;
         r.cnt[j] += ok ? 1u : 0u;

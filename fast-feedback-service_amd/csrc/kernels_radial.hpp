@@ -1,4 +1,4 @@
-// kernels_radial.hpp (included by ffs_submit.hip only) -- the per-frame radial profile (ffs_ctx_set_radial_bins):
+// kernels_radial.hpp (included by ffs_products.hip only) -- the per-frame radial profile (ffs_ctx_set_radial_bins):
 // per frame and bin of a caller-defined bin map, the count, the sum and the sum of squares of the pixels that the valid-pixel mask,
 // max_valid and (32-bit pixels) the oracle's p < 2^24 rule let through.  The reference has no counterpart (its per-image output is the
 // strong mask, spotfinder/spotfinder.cc:887-933); DIALS builds its radial_profile threshold and its per-image analysis on this quantity.
@@ -29,7 +29,8 @@ constexpr uint32_t kRadialMaxBins = 1024;    // 20 KB of LDS a workgroup
 constexpr int kRadialThreads = 256;
 constexpr int kRadialWaves = kRadialThreads / 64;
 
-struct RadialArgs {
+// What the band walk reads (radial_walk): k_radial's input, and the radial-profile threshold's (kernels_radthr.hpp)
+struct RadialIn {
     const void* image;          // [frame][y][pitch bytes], as the threshold stage reads it
     uint64_t frame_stride;
     uint32_t pitch;
@@ -41,7 +42,10 @@ struct RadialArgs {
     int W, H;
     uint32_t n_bins;
     uint32_t n_bands, band_rows;   // bands of a frame (the grid's y) and the rows of one
-    uint32_t limit;             // a pixel counts when p < limit: max_valid + 1 and 2^24, whichever is smaller
+    uint32_t limit;             // a pixel counts when p < limit (launch_geometry.hpp, counting_limit)
+};
+struct RadialArgs {
+    RadialIn in;
     // partials, [frame][band][n_bins] each, and results, [frame][n_bins] each
     uint64_t *p_sum, *p_sq;
     uint32_t* p_count;
@@ -65,7 +69,7 @@ __device__ __forceinline__ uint32_t radial_widen2(uint32_t b2) {   // two entrie
     return (lo == 0xFFu ? 0xFFFFu : lo) | ((hi == 0xFFu ? 0xFFFFu : hi) << 16);
 }
 template <typename PixelT, bool MAP8>
-__device__ __forceinline__ RadialLoad<PixelT> radial_load(const RadialArgs& a, const uint8_t* img, int y, int x0) {
+__device__ __forceinline__ RadialLoad<PixelT> radial_load(const RadialIn& a, const uint8_t* img, int y, int x0) {
     constexpr int PX = 16 / (int)sizeof(PixelT);
     RadialLoad<PixelT> r;
     r.px = make_uint4(0u, 0u, 0u, 0u);
@@ -146,74 +150,87 @@ __device__ __forceinline__ void radial_flush(uint64_t pending, uint32_t bin, uin
     }
 }
 
+// The rule: a pixel counts when the mask has its bit, the map has it in a bin and its value is below the limit
+__device__ __forceinline__ bool radial_counts(const RadialIn& a, uint32_t mask_bit, uint32_t b, uint32_t p) { return mask_bit && b != kRadialNone && p < a.limit; }
+
+// Entry j of the bin entries a lane has of one load (two entries a word; with 32-bit pixels only the first four exist)
+__device__ __forceinline__ uint32_t radial_bin_entry(const uint4& bn, int j) {
+    const uint32_t bw = j < 2 ? bn.x : j < 4 ? bn.y : j < 6 ? bn.z : bn.w;
+    return (j & 1) ? bw >> 16 : bw & 0xFFFFu;
+}
+
+// The band walk of a workgroup of WAVES waves over band `band` of frame `frame`: wave w takes rows w, w + WAVES, ... of the band, each from
+// x = 0 in steps of 64 x PX pixels while x < W, with the next step's load in flight while this one is counted, and folds every pixel of
+// every load, in that order, into what the lane keeps: run = each(run, p, b, mask_bit) -- value, bin entry, valid-pixel bit; whether the pixel
+// counts is radial_counts of the three.  Returns the lane's last run.  (The run goes in and out BY VALUE and `each` applies the rule itself: a
+// lambda that changed its run through a reference, or was handed the rule's result, compiled to another loop body -- profiles/r23a.)
+template <typename PixelT, bool MAP8, int WAVES, typename Run, typename Each>
+__device__ __forceinline__ Run radial_walk(const RadialIn& a, uint32_t frame, uint32_t band, Run run, Each&& each) {
+    constexpr int PX = 16 / (int)sizeof(PixelT);
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));   // (the row loop below is the same in every lane)
+    const uint8_t* img = static_cast<const uint8_t*>(a.image) + (uint64_t)frame * a.frame_stride;
+    const int y_end = min(a.H, (int)((band + 1u) * a.band_rows));
+    const int step = 64 * PX;                      // pixels of a wave's load
+    int y = (int)(band * a.band_rows + wave), xw = 0;
+    RadialLoad<PixelT> ld = radial_load<PixelT, MAP8>(a, img, y < y_end ? y : a.H, xw + (int)lane * PX);
+    while (y < y_end) {
+        int yn = y, xn = xw + step;
+        if (xn >= a.W) { xn = 0; yn = y + WAVES; }
+        const RadialLoad<PixelT> nx = radial_load<PixelT, MAP8>(a, img, yn < y_end ? yn : a.H, xn + (int)lane * PX);
+#pragma unroll
+        for (int j = 0; j < PX; ++j) {
+            const uint32_t p = lane_pixel<PX>(ld.px, j), b = radial_bin_entry(ld.bn, j);
+            run = each(run, p, b, (ld.mb >> j) & 1u);
+        }
+        ld = nx;
+        y = yn;
+        xw = xn;
+    }
+    return run;
+}
+
+struct RadialRun { uint32_t cur, cnt; uint64_t s, q; };   // a lane's run of equal bins: the bin, count, sum, sum of squares
+
 template <typename PixelT, bool MAP8>
 __global__ __launch_bounds__(kRadialThreads) void k_radial(RadialArgs a) {
-    constexpr int PX = 16 / (int)sizeof(PixelT);
     extern __shared__ __attribute__((aligned(16))) uint8_t radial_smem[];
+    const uint32_t n_bins = a.in.n_bins;
     uint64_t* l_sum = reinterpret_cast<uint64_t*>(radial_smem);
-    uint64_t* l_sq = l_sum + a.n_bins;
-    uint32_t* l_count = reinterpret_cast<uint32_t*>(l_sq + a.n_bins);
+    uint64_t* l_sq = l_sum + n_bins;
+    uint32_t* l_count = reinterpret_cast<uint32_t*>(l_sq + n_bins);
     const uint32_t frame = blockIdx.x, band = blockIdx.y;
-    for (uint32_t i = threadIdx.x; i < a.n_bins; i += kRadialThreads) {
+    for (uint32_t i = threadIdx.x; i < n_bins; i += kRadialThreads) {
         l_sum[i] = 0ull;
         l_sq[i] = 0ull;
         l_count[i] = 0u;
     }
     __syncthreads();
 
-    const uint32_t lane = threadIdx.x & 63u;
-    const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));   // (the row loop below is the same in every lane)
-    const uint8_t* img = static_cast<const uint8_t*>(a.image) + (uint64_t)frame * a.frame_stride;
-    const int y_end = min(a.H, (int)((band + 1u) * a.band_rows));
-    const int step = 64 * PX;                      // pixels of a wave's load
-    // this wave's loads: rows y, y + 4, ... of the band, each from x = 0 in steps of `step` while x < W
-    int y = (int)(band * a.band_rows + wave), xw = 0;
-    uint32_t cur = kRadialNone, cnt = 0u;          // the lane's run
-    uint64_t s = 0ull, q = 0ull;
-    RadialLoad<PixelT> ld = radial_load<PixelT, MAP8>(a, img, y < y_end ? y : a.H, xw + (int)lane * PX);
-    while (y < y_end) {
-        int yn = y, xn = xw + step;
-        if (xn >= a.W) { xn = 0; yn = y + kRadialWaves; }
-        const RadialLoad<PixelT> nx = radial_load<PixelT, MAP8>(a, img, yn < y_end ? yn : a.H, xn + (int)lane * PX);
-#pragma unroll
-        for (int j = 0; j < PX; ++j) {
-            uint32_t p, b;
-            if constexpr (PX == 8) {
-                const uint32_t pw = j < 2 ? ld.px.x : j < 4 ? ld.px.y : j < 6 ? ld.px.z : ld.px.w;
-                const uint32_t bw = j < 2 ? ld.bn.x : j < 4 ? ld.bn.y : j < 6 ? ld.bn.z : ld.bn.w;
-                p = (j & 1) ? pw >> 16 : pw & 0xFFFFu;
-                b = (j & 1) ? bw >> 16 : bw & 0xFFFFu;
-            } else {
-                p = j == 0 ? ld.px.x : j == 1 ? ld.px.y : j == 2 ? ld.px.z : ld.px.w;
-                const uint32_t bw = j < 2 ? ld.bn.x : ld.bn.y;
-                b = (j & 1) ? bw >> 16 : bw & 0xFFFFu;
-            }
-            const bool ok = ((ld.mb >> j) & 1u) && b != kRadialNone && p < a.limit;
-            const bool change = ok && b != cur;
-            if (change) {
-                if (cnt != 0u) radial_add(cur, cnt, s, q, l_sum, l_sq, l_count);
-                cur = b;
-                cnt = 0u;
-                s = 0ull;
-                q = 0ull;
-            }
-            if (ok) {
-                ++cnt;
-                s += p;
-                q += (uint64_t)p * p;
-            }
+    const RadialRun last = radial_walk<PixelT, MAP8, kRadialWaves>(a.in, frame, band, RadialRun{kRadialNone, 0u, 0ull, 0ull}, [&a, l_sum, l_sq, l_count](RadialRun r, uint32_t p, uint32_t b, uint32_t m) {
+        const bool ok = radial_counts(a.in, m, b, p);
+        const bool change = ok && b != r.cur;
+        if (change) {
+            if (r.cnt != 0u) radial_add(r.cur, r.cnt, r.s, r.q, l_sum, l_sq, l_count);
+            r.cur = b;
+            r.cnt = 0u;
+            r.s = 0ull;
+            r.q = 0ull;
         }
-        ld = nx;
-        y = yn;
-        xw = xn;
-    }
+        if (ok) {
+            ++r.cnt;
+            r.s += p;
+            r.q += (uint64_t)p * p;
+        }
+        return r;
+    });
     {
-        const uint64_t pending = __ballot(cnt != 0u);
-        if (pending) radial_flush(pending, cur, cnt, s, q, l_sum, l_sq, l_count);
+        const uint64_t pending = __ballot(last.cnt != 0u);
+        if (pending) radial_flush(pending, last.cur, last.cnt, last.s, last.q, l_sum, l_sq, l_count);
     }
     __syncthreads();
-    const uint64_t base = ((uint64_t)frame * a.n_bands + band) * a.n_bins;
-    for (uint32_t i = threadIdx.x; i < a.n_bins; i += kRadialThreads) {
+    const uint64_t base = ((uint64_t)frame * a.in.n_bands + band) * n_bins;
+    for (uint32_t i = threadIdx.x; i < n_bins; i += kRadialThreads) {
         a.p_sum[base + i] = l_sum[i];
         a.p_sq[base + i] = l_sq[i];
         a.p_count[base + i] = l_count[i];
@@ -222,16 +239,16 @@ __global__ __launch_bounds__(kRadialThreads) void k_radial(RadialArgs a) {
 
 __global__ __launch_bounds__(256) void k_radial_sum(RadialArgs a) {
     const uint32_t b = blockIdx.x * 256u + threadIdx.x, frame = blockIdx.y;
-    if (b >= a.n_bins) return;
+    if (b >= a.in.n_bins) return;
     uint32_t c = 0u;
     uint64_t s = 0ull, q = 0ull;
-    uint64_t at = (uint64_t)frame * a.n_bands * a.n_bins + b;
-    for (uint32_t band = 0; band < a.n_bands; ++band, at += a.n_bins) {
+    uint64_t at = (uint64_t)frame * a.in.n_bands * a.in.n_bins + b;
+    for (uint32_t band = 0; band < a.in.n_bands; ++band, at += a.in.n_bins) {
         c += a.p_count[at];
         s += a.p_sum[at];
         q += a.p_sq[at];
     }
-    const uint64_t out = (uint64_t)frame * a.n_bins + b;
+    const uint64_t out = (uint64_t)frame * a.in.n_bins + b;
     a.r_count[out] = c;
     a.r_sum[out] = s;
     a.r_sq[out] = q;

@@ -1,12 +1,12 @@
-// kernels_radthr.hpp (included by ffs_submit.hip only) -- the radial-profile threshold (FFS_ALGO_RADIAL_PROFILE): a
+// kernels_radthr.hpp (included by ffs_products.hip only) -- the radial-profile threshold (FFS_ALGO_RADIAL_PROFILE): a
 // pixel is strong when it stands above median + n_iqr x IQR of its shell of the caller's bin map (ffs_ctx_set_radial_bins, at most 128
 // bins), both taken per frame over a histogram of the shell's counting pixels.  The reference has no counterpart (its algorithms are
 // dispersion and dispersion_extended, spotfinder/spotfinder.cc:338-342); the definition is ffs_hip.h's, modelled on DIALS's radial_profile.
 //
 // Three launches in the dense stream, everything an integer but the cutoff's one product:
 //   k_radthr_hist<PixelT>   grid (frames, bands): a workgroup of sixteen waves streams a band of contiguous rows of one frame with
-//                           kernels_radial.hpp's loads (16 B of pixels, the matching bin entries and mask bits per lane and load, the next
-//                           load in flight) and counts into a table in LDS, n_bins x 257 counters: the values 0 .. 255 and a tail.  The
+//                           kernels_radial.hpp's band walk (16 B of pixels, the matching bin entries and mask bits per lane and load, the
+//                           next load in flight) and counts into a table in LDS, n_bins x 257 counters: the values 0 .. 255 and a tail.  The
 //                           table is up to 128.5 KiB -- one workgroup a CU, hence sixteen waves of it -- and its non-zero counters are then
 //                           added to the frame's table in global memory, zeroed ahead of the launch (integers: any order, the same bits).
 //   k_radthr_cut            grid (bins, frames): a wave per (frame, shell) scans the 257 counters, four bins a lane, and decides with
@@ -23,7 +23,6 @@
 #pragma once
 #include "ffs_device.h"
 #include "kernels_radial.hpp"
-#include "kernels_threshold.hpp"
 #include "radial_threshold_model.hpp"
 
 namespace ffsamd {
@@ -32,9 +31,7 @@ constexpr int kRadThrHistThreads = 1024;
 constexpr int kRadThrHistWaves = kRadThrHistThreads / 64;
 
 struct RadThrArgs {
-    // what the histogram reads, as the radial profile reads it: image, frame_stride, pitch, maskbits, mpitch, bins, bin_pitch, W, H, n_bins,
-    // n_bands, band_rows, limit (bins8 is null and the profile's partials and results are unused)
-    RadialArgs in;
+    RadialIn in;                  // what the histogram's band walk reads (bins8 is null); k_radthr_strong reads the same frames, map and limit
     uint32_t* hist;               // [frame][n_bins][kRadThrCounters], zero when k_radthr_hist starts
     uint32_t* cut;                // [frame][n_bins]: the cutoff, kRadThrNever under a status other than 0
     ffs_radial_shell* shells;     // [frame][n_bins], pinned host memory
@@ -55,7 +52,6 @@ static inline size_t radthr_lds_bytes(uint32_t n_bins) { return (size_t)n_bins *
 
 template <typename PixelT, bool RUN>
 __global__ __launch_bounds__(kRadThrHistThreads) void k_radthr_hist(RadThrArgs a) {
-    constexpr int PX = 16 / (int)sizeof(PixelT);
     extern __shared__ __attribute__((aligned(16))) uint8_t radthr_smem[];
     uint32_t* tab = reinterpret_cast<uint32_t*>(radthr_smem);
     const uint32_t n_tab = a.in.n_bins * (uint32_t)kRadThrCounters;
@@ -63,52 +59,25 @@ __global__ __launch_bounds__(kRadThrHistThreads) void k_radthr_hist(RadThrArgs a
     for (uint32_t i = threadIdx.x; i < n_tab; i += kRadThrHistThreads) tab[i] = 0u;
     __syncthreads();
 
-    const uint32_t lane = threadIdx.x & 63u;
-    const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const uint8_t* img = static_cast<const uint8_t*>(a.in.image) + (uint64_t)frame * a.in.frame_stride;
-    const int y_end = min(a.in.H, (int)((band + 1u) * a.in.band_rows));
-    const int step = 64 * PX;
-    // this wave's loads: rows y, y + 16, ... of the band, each from x = 0 in steps of `step` while x < W (k_radial's order)
-    int y = (int)(band * a.in.band_rows + wave), xw = 0;
-    [[maybe_unused]] uint32_t cur = 0u, cnt = 0u;   // (RUN) the lane's run: a counter's index and how often
-    RadialLoad<PixelT> ld = radial_load<PixelT, false>(a.in, img, y < y_end ? y : a.in.H, xw + (int)lane * PX);
-    while (y < y_end) {
-        int yn = y, xn = xw + step;
-        if (xn >= a.in.W) { xn = 0; yn = y + kRadThrHistWaves; }
-        const RadialLoad<PixelT> nx = radial_load<PixelT, false>(a.in, img, yn < y_end ? yn : a.in.H, xn + (int)lane * PX);
-#pragma unroll
-        for (int j = 0; j < PX; ++j) {
-            uint32_t p, b;
-            if constexpr (PX == 8) {
-                const uint32_t pw = j < 2 ? ld.px.x : j < 4 ? ld.px.y : j < 6 ? ld.px.z : ld.px.w;
-                const uint32_t bw = j < 2 ? ld.bn.x : j < 4 ? ld.bn.y : j < 6 ? ld.bn.z : ld.bn.w;
-                p = (j & 1) ? pw >> 16 : pw & 0xFFFFu;
-                b = (j & 1) ? bw >> 16 : bw & 0xFFFFu;
-            } else {
-                p = j == 0 ? ld.px.x : j == 1 ? ld.px.y : j == 2 ? ld.px.z : ld.px.w;
-                const uint32_t bw = j < 2 ? ld.bn.x : ld.bn.y;
-                b = (j & 1) ? bw >> 16 : bw & 0xFFFFu;
+    // (RUN) the lane's run: a counter's index (x) and how often (y)
+    const uint2 last = radial_walk<PixelT, false, kRadThrHistWaves>(a.in, frame, band, make_uint2(0u, 0u), [&a, tab](uint2 run, uint32_t p, uint32_t b, uint32_t m) {
+        // (the map's entries are below n_bins or kRadialNone: ffs_ctx_set_radial_bins checked them)
+        const bool ok = radial_counts(a.in, m, b, p);
+        const uint32_t at = b * (uint32_t)kRadThrCounters + min(p, (uint32_t)kRadThrValues);
+        if constexpr (RUN) {
+            if (ok && at != run.x) {
+                if (run.y != 0u) atomicAdd(&tab[run.x], run.y);
+                run.x = at;
+                run.y = 0u;
             }
-            // (the map's entries are below n_bins or kRadialNone: ffs_ctx_set_radial_bins checked them)
-            const bool ok = ((ld.mb >> j) & 1u) && b != kRadialNone && p < a.in.limit;
-            const uint32_t at = b * (uint32_t)kRadThrCounters + min(p, (uint32_t)kRadThrValues);
-            if constexpr (RUN) {
-                if (ok && at != cur) {
-                    if (cnt != 0u) atomicAdd(&tab[cur], cnt);
-                    cur = at;
-                    cnt = 0u;
-                }
-                if (ok) ++cnt;
-            } else {
-                if (ok) atomicAdd(&tab[at], 1u);
-            }
+            if (ok) ++run.y;
+        } else {
+            if (ok) atomicAdd(&tab[at], 1u);
         }
-        ld = nx;
-        y = yn;
-        xw = xn;
-    }
+        return run;
+    });
     if constexpr (RUN) {
-        if (cnt != 0u) atomicAdd(&tab[cur], cnt);
+        if (last.y != 0u) atomicAdd(&tab[last.x], last.y);
     }
     __syncthreads();
     uint32_t* out = a.hist + (uint64_t)frame * n_tab;
@@ -211,23 +180,15 @@ __global__ __launch_bounds__(64) void k_radthr_strong(RadThrArgs a) {
     RadThrRow<PixelT> row = radthr_row<PixelT>(a, img, y0, g, own);
     for (int y = y0; y < y1; ++y) {
         const RadThrRow<PixelT> next = radthr_row<PixelT>(a, img, y + 1 < y1 ? y + 1 : a.in.H, g, own);
-        uint32_t p[8];
-        if constexpr (sizeof(PixelT) == 2) {
-            p[0] = row.p0.x & 0xFFFFu; p[1] = row.p0.x >> 16; p[2] = row.p0.y & 0xFFFFu; p[3] = row.p0.y >> 16;
-            p[4] = row.p0.z & 0xFFFFu; p[5] = row.p0.z >> 16; p[6] = row.p0.w & 0xFFFFu; p[7] = row.p0.w >> 16;
-        } else {
-            p[0] = row.p0.x; p[1] = row.p0.y; p[2] = row.p0.z; p[3] = row.p0.w;
-            p[4] = row.p1.x; p[5] = row.p1.y; p[6] = row.p1.z; p[7] = row.p1.w;
-        }
         uint32_t sb = 0u;
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
-            const uint32_t bw = j < 2 ? row.bn.x : j < 4 ? row.bn.y : j < 6 ? row.bn.z : row.bn.w;
-            const uint32_t b = (j & 1) ? bw >> 16 : bw & 0xFFFFu;
+            const uint32_t b = radial_bin_entry(row.bn, j);
+            const uint32_t p = sizeof(PixelT) == 2 ? lane_pixel<8>(row.p0, j) : lane_pixel<4>(j < 4 ? row.p0 : row.p1, j & 3);
             // (a pixel beyond W has no mask bit: bits at x >= W are never set)
-            const bool counts = ((row.mb >> j) & 1u) && b != kRadialNone && p[j] < a.in.limit;
+            const bool counts = ((row.mb >> j) & 1u) && b != kRadialNone && p < a.in.limit;   // (radial_counts, spelt out: through the helper the kernel compiles differently)
             const uint32_t cutoff = s_cut[b & (kRadThrMaxBins - 1u)];
-            if (counts && p[j] > cutoff && (double)p[j] > a.threshold) sb |= 1u << j;
+            if (counts && p > cutoff && (double)p > a.threshold) sb |= 1u << j;
         }
         if (sb) {
             plane[(uint64_t)y * a.in.mpitch + g] = (uint8_t)sb;   // (the plane is all zero when the kernel starts)

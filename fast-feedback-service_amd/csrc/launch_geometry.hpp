@@ -1,7 +1,8 @@
 // launch_geometry.hpp -- the launch geometry of the threshold stage as plain integer arithmetic: the frame layout, how the streaming
 // kernels cut a batch into super rows, strips and bands, the general-window kernel's and the extended first pass's strips and bands,
-// how many wave logs and band slots a launch needs, and the unit map the kernels invert.  No HIP header: host code, the kernels (through
-// ffs_device.h) and a plain C++ test program (tests/launch_geometry_check.cc) compile the same text.
+// how many wave logs and band slots a launch needs, the unit map the kernels invert, and the row bands and the pixel-count rule of the
+// per-frame products.  No HIP header: host code, the kernels (through ffs_device.h) and a plain C++ test program
+// (tests/launch_geometry_check.cc) compile the same text.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -189,6 +190,33 @@ inline ExtGeometry ext_geometry(const Layout& L, uint32_t n_frames) {
         a.ext_bands = (L.H + a.ext_band_rows - 1) / a.ext_band_rows;
     }
     return a;
+}
+
+// ---- per-frame products: bands of contiguous rows, a workgroup each (k_radial, k_radthr_hist) ---------------------------
+// About target_groups workgroups a launch and at most max_bands bands a frame, all of band_rows rows but the last; forced > 0: that many
+// bands instead, clamped to 1..H (0: the launch chooses).
+inline void uniform_row_bands(int H, uint32_t n_frames, uint32_t target_groups, uint32_t max_bands, int forced, uint32_t& n_bands, uint32_t& band_rows) {
+    const uint32_t h = (uint32_t)H;
+    const uint32_t want = forced > 0 ? std::clamp<uint32_t>((uint32_t)forced, 1u, h)
+                                     : std::clamp<uint32_t>((target_groups + n_frames - 1) / n_frames, 1u, std::min(h, max_bands));
+    band_rows = (h + want - 1) / want;
+    n_bands = (h + band_rows - 1) / band_rows;
+}
+// (frame, band) pairs of the largest launch any batch of 1 .. max_batch frames can make where the launch chooses its bands
+inline size_t max_uniform_band_slots(int H, uint32_t max_batch, uint32_t target_groups, uint32_t max_bands) {
+    size_t slots = 0;
+    for (uint32_t nf = 1; nf <= max_batch; ++nf) {
+        uint32_t nb = 0, rows = 0;
+        uniform_row_bands(H, nf, target_groups, max_bands, 0, nb, rows);
+        slots = std::max(slots, (size_t)nf * nb);
+    }
+    return slots;
+}
+// The pixel-count rule of the per-frame products, the per-spot background and the window scope's neighbour limit: a pixel counts when
+// p < counting_limit.  max_valid (>= 0) is inclusive and holds under both of its scopes; on top of it, and alone without a max_valid,
+// stands the oracle's p < 2^24 for 32-bit pixels (16-bit pixels never reach it).
+inline uint32_t counting_limit(long long max_valid) {
+    return max_valid >= 0 ? (uint32_t)std::min<long long>(max_valid, (1ll << 24) - 1) + 1u : 1u << 24;
 }
 
 // ---- the unit map: what the kernels invert ----------------------------------------------------------------------------

@@ -3,6 +3,7 @@
 // strides and tuning values; prints one line of geometry per case and batch size -- the test compares them with
 // tests/golden/launch_geometry.json, recorded from the arithmetic as it stood inside make_threshold_args -- and checks on every case what
 // the kernels and the buffer sizing rely on.  A line that starts with "FAIL" names a broken invariant; the exit status is then 1.
+#include <climits>
 #include <cstdio>
 #include <vector>
 
@@ -123,6 +124,35 @@ static void window_ext_case(const Shape& sh) {
     }
 }
 
+// The row bands of the per-frame products (uniform_row_bands) under the constants of their two launches -- the radial profile's 2048 groups and
+// 64 bands, the radial-profile threshold's histogram's 512 and 64 -- chosen and forced: they tile the frame, a chosen count keeps to its
+// bound, and no batch of 1 .. max_batch frames has more (frame, band) pairs than the partials are sized for.
+static void row_bands_case(const Shape& sh) {
+    const int H = (int)sh.H;
+    const uint32_t pairs[2][2] = {{2048u, 64u}, {512u, 64u}};
+    for (const auto& k : pairs) {
+        const size_t slots = max_uniform_band_slots(H, sh.max_batch, k[0], k[1]);
+        for (uint32_t nf = 1; nf <= sh.max_batch; ++nf)
+            for (int forced : {0, 1, 2, 5, H, H + 7}) {
+                uint32_t nb = 0, rows = 0;
+                uniform_row_bands(H, nf, k[0], k[1], forced, nb, rows);
+                check_uniform_bands("row bands", H, (int)rows, (int)nb);
+                if (forced > 0) continue;
+                CHECK(nb <= std::max(1u, std::min((uint32_t)H, k[1])), "row bands: H %d, %u frames, %u groups: %u bands of at most %u", H, nf, k[0], nb, k[1]);
+                CHECK((size_t)nf * nb <= slots, "row bands: H %d, %u frames x %u bands against %zu slots", H, nf, nb, slots);
+            }
+    }
+}
+
+// counting_limit against the expression as it stood at its five call sites
+static void counting_limit_case() {
+    for (long long mv : {-1ll, 0ll, 1ll, 65534ll, 65535ll, (1ll << 24) - 2, (1ll << 24) - 1, 1ll << 24, 1ll << 31, LLONG_MAX}) {
+        const uint32_t was = mv >= 0 ? (uint32_t)std::min<long long>(mv, (1ll << 24) - 1) + 1u : 1u << 24;
+        const uint32_t is = counting_limit(mv);
+        CHECK(is == was && is != 0u && is <= (1u << 24), "counting_limit(%lld) = %u, was %u", mv, is, was);
+    }
+}
+
 int main() {
     const Tuning dflt;
     const int F = dflt.frames_per_group;
@@ -148,7 +178,9 @@ int main() {
             if (sh.max_batch == 32) stream_case(sh, px, 1ull << 28, tunes[0]);            // ... and padded so far that the 2 GiB limit cuts the groups
         }
         window_ext_case(sh);
+        row_bands_case(sh);
     }
+    counting_limit_case();
     for (int rows : {47, 50, 74, 75, 96, 97, 100, 104, 150, 173, 1024}) {   // uniform bands of that height as the sparse stage's sub-bands
         const BandSplit split = band_split(StreamGeometry{1, 1, 1, 1, rows, rows, 1});
         std::printf("B %d | %d %d\n", rows, split.sub, split.sub_rows);
