@@ -35,7 +35,8 @@ extern "C" int ffs_bench_threshold(ffs_stream* s, const void* device_pixels, siz
     }
     const bool e_sparse = ext && ext_sparse_erode(c->tune);   // (the hot path clears the signal-region plane behind the previous batch)
     ta.eplane_clean = e_sparse ? 1 : 0;
-    const bool radial = route.stage == ThresholdStage::kRadial;   // (ms_dense: the histogram launch; ms_rest: the cut and strong launches)
+    // (ms_dense: the histogram launch; ms_rest: the cut and strong launches -- the blurred forms when the context has a blur, which the snapshot above took)
+    const bool radial = route.stage == ThresholdStage::kRadial;
     if (radial) {
         rc = radthr_ensure_buffers(s);
         if (rc != FFS_OK) return rc;

@@ -21,6 +21,7 @@
 //   spot_background_model.hpp  the decisions of the per-spot background: quartile positions, status order, fence (tests/spot_background_check.cc)
 //   radial_threshold_model.hpp the decisions of the radial-profile threshold (kernels_radthr.hpp, included by ffs_products.hip): status order and the
 //                        cutoff's two separately rounded operations (tests/radial_threshold_check.cc)
+//   radial_blur_model.hpp  the blur ahead of that threshold (ffs_ctx_set_radial_blur): weights, tap rule, v = S / Wn (tests/radial_blur_check.cc)
 // No exception leaves the library (guarded()).
 #pragma once
 #include <algorithm>
@@ -88,6 +89,7 @@ struct ParamSnapshot {
     // shell -- and n_iqr (ffs_ctx_set_radial_threshold).  The map itself is the context's, like the gain map.
     uint32_t radthr_bins = 0;
     double n_iqr = 6.0;
+    int radial_blur = 0;        // ffs_ctx_set_radial_blur at submit (FFS_RADIAL_BLUR_*); plays a part only where radthr_bins does
 };
 
 // A few helper threads per context for ffs_wait's result assembly (wire records -> boxes, reflections, centre rows): one thread
@@ -159,6 +161,7 @@ struct ffs_ctx {
     uint8_t* d_radial_map8 = nullptr;   // the same rows in one byte an entry (0xFF: in no bin), behind the two-byte rows in the same allocation; written for maps of at most 255 bins
     uint32_t radial_bins = 0;
     double n_iqr = 6.0;                           // ffs_ctx_set_radial_threshold: kept across ffs_ctx_set_params, snapshot per batch
+    int radial_blur = 0;                          // ffs_ctx_set_radial_blur: likewise
     // ffs_ctx_set_pixel_stats: the four accumulator planes are one allocation, made at the first start and kept (count,
     // max, sum, sum of squares, in that order; laid out in tiles: PixStatsLayout below).  stats_on: batches submitted from now on are folded in;
     // stats_started: there has been a start, ffs_ctx_get_pixel_stats has something to hand out.  stats_st: the context's own HIP stream for the
@@ -433,7 +436,7 @@ static int guarded(ffs_ctx* c, F&& body) {
 // ---- small helpers ------------------------------------------------------------------------------------------
 static inline ParamSnapshot snapshot_of(const ffs_ctx* c) {
     return ParamSnapshot{c->params, c->max_valid_scope, c->gain, c->has_gain_map, c->radial_bins, c->stats_on,
-                         c->params.algorithm == FFS_ALGO_RADIAL_PROFILE ? c->radial_bins : 0u, c->n_iqr};
+                         c->params.algorithm == FFS_ALGO_RADIAL_PROFILE ? c->radial_bins : 0u, c->n_iqr, c->radial_blur};
 }
 // Where the per-pixel statistics lie (kernels_pixstats.hpp has the why): a lane owns px = 16 / pixel_bytes pixels of a row, lanes are numbered
 // row by row, sixty-four of them are a tile, and in every plane a lane's entries are chunks of 16 B, chunk k of lane l of tile t at

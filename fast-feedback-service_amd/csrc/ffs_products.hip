@@ -242,6 +242,16 @@ extern "C" int ffs_ctx_set_radial_threshold(ffs_ctx* c, double n_iqr) {
     return FFS_OK;
 }
 
+extern "C" int ffs_ctx_set_radial_blur(ffs_ctx* c, int blur) {
+    if (!c) return FFS_ERR_INVALID;
+    if (blur != FFS_RADIAL_BLUR_NONE && blur != FFS_RADIAL_BLUR_NARROW && blur != FFS_RADIAL_BLUR_WIDE) {
+        c->err = "ffs_ctx_set_radial_blur: blur must be FFS_RADIAL_BLUR_NONE (0), _NARROW (1) or _WIDE (2), got " + std::to_string(blur);
+        return FFS_ERR_INVALID;
+    }
+    c->radial_blur = blur;
+    return FFS_OK;
+}
+
 // The histogram's workgroups hold a whole CU's LDS each, so a launch aims at two per CU and at most 64 bands a frame; tuning "radthr_bands"
 // sets the bands instead (clamped to 1..H).
 constexpr uint32_t kRadThrTargetGroups = 512, kRadThrMaxBands = 64;
@@ -252,6 +262,16 @@ static RadThrKernel radthr_hist_kernel(int pixel_bytes, int form) {
     const bool run = form == 0 ? pixel_bytes == 2 : form == 2;
     return pixel_bytes == 2 ? (run ? k_radthr_hist<uint16_t, true> : k_radthr_hist<uint16_t, false>)
                             : (run ? k_radthr_hist<uint32_t, true> : k_radthr_hist<uint32_t, false>);
+}
+// The blurred forms (ffs_ctx_set_radial_blur; blur = the kernel's radius, 1 or 2): one histogram kernel a pixel size and radius -- the
+// plain LDS add: tuning "radthr_form" has no meaning here -- and one strong kernel.
+static RadThrKernel radthr_hist_blur_kernel(int pixel_bytes, int blur) {
+    return pixel_bytes == 2 ? (blur == kRadBlurNarrow ? k_radthr_hist_blur<uint16_t, 1> : k_radthr_hist_blur<uint16_t, 2>)
+                            : (blur == kRadBlurNarrow ? k_radthr_hist_blur<uint32_t, 1> : k_radthr_hist_blur<uint32_t, 2>);
+}
+static RadThrKernel radthr_strong_blur_kernel(int pixel_bytes, int blur) {
+    return pixel_bytes == 2 ? (blur == kRadBlurNarrow ? k_radthr_strong_blur<uint16_t, 1> : k_radthr_strong_blur<uint16_t, 2>)
+                            : (blur == kRadBlurNarrow ? k_radthr_strong_blur<uint32_t, 1> : k_radthr_strong_blur<uint32_t, 2>);
 }
 
 void radthr_free(ffs_stream* s) {
@@ -269,9 +289,9 @@ void radthr_free(ffs_stream* s) {
 int radthr_ensure_buffers(ffs_stream* s) {
     if (s->d_radthr_hist) return FFS_OK;
     ffs_ctx* c = s->ctx;
-    for (int form = 1; form <= 2; ++form)
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(radthr_hist_kernel(c->pixel_bytes, form)), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)radthr_lds_bytes(kRadThrMaxBins)) != hipSuccess) {
+    for (int k = 1; k <= 4; ++k)   // the two forms, then the two blurred kernels
+        if (hipFuncSetAttribute(reinterpret_cast<const void*>(k <= 2 ? radthr_hist_kernel(c->pixel_bytes, k) : radthr_hist_blur_kernel(c->pixel_bytes, k - 2)),
+                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)radthr_lds_bytes(kRadThrMaxBins)) != hipSuccess) {
             (void)hipGetLastError();
             c->err = "radial_profile threshold: the device refuses the histogram's " + std::to_string(radthr_lds_bytes(kRadThrMaxBins)) + " bytes of LDS";
             return FFS_ERR_DEVICE;
@@ -329,13 +349,20 @@ static RadThrArgs make_radthr_args(const ffs_stream* s, const ThresholdArgs& t, 
 void launch_radthr_hist(ffs_stream* s, const ThresholdArgs& t, uint32_t n_frames, hipEvent_t start, hipEvent_t stop) {
     const RadThrArgs a = make_radthr_args(s, t, n_frames);
     (void)hipMemsetAsync(a.hist, 0, (size_t)n_frames * a.in.n_bins * kRadThrCounters * 4u, s->st);
-    hipExtLaunchKernelGGL(radthr_hist_kernel(s->ctx->pixel_bytes, s->ctx->tune.radthr_form), dim3(n_frames, a.in.n_bands), dim3(kRadThrHistThreads),
-                          radthr_lds_bytes(a.in.n_bins), s->st, start, stop, 0, a);
+    const int blur = s->batch.radial_blur;
+    hipExtLaunchKernelGGL(blur ? radthr_hist_blur_kernel(s->ctx->pixel_bytes, blur) : radthr_hist_kernel(s->ctx->pixel_bytes, s->ctx->tune.radthr_form),
+                          dim3(n_frames, a.in.n_bands), dim3(kRadThrHistThreads), radthr_lds_bytes(a.in.n_bins), s->st, start, stop, 0, a);
 }
 // ... and the cutoffs and the strong pixels behind it; `stop` rides on the last dispatch
 void launch_radthr_rest(ffs_stream* s, const ThresholdArgs& t, uint32_t n_frames, hipEvent_t stop) {
     const RadThrArgs a = make_radthr_args(s, t, n_frames);
     hipLaunchKernelGGL(k_radthr_cut, dim3(a.in.n_bins, n_frames), dim3(64), 0, s->st, a);
+    if (const int blur = s->batch.radial_blur) {   // a wave per run of rows of a strip of kRadBlurOwners groups (the kernel's radblur_strips)
+        const uint32_t strips = ((uint32_t)(a.in.W + 7) / 8u + kRadBlurOwners - 1u) / kRadBlurOwners;
+        const uint32_t runs = ((uint32_t)a.in.H + kRadBlurRunRows - 1u) / kRadBlurRunRows;
+        hipExtLaunchKernelGGL(radthr_strong_blur_kernel(s->ctx->pixel_bytes, blur), dim3(strips * runs, n_frames), dim3(64), 0, s->st, nullptr, stop, 0, a);
+        return;
+    }
     const dim3 grid(a.s_strips * (uint32_t)a.n_tiles, n_frames);
     if (s->ctx->pixel_bytes == 2) hipExtLaunchKernelGGL(k_radthr_strong<uint16_t>, grid, dim3(64), 0, s->st, nullptr, stop, 0, a);
     else hipExtLaunchKernelGGL(k_radthr_strong<uint32_t>, grid, dim3(64), 0, s->st, nullptr, stop, 0, a);

@@ -535,7 +535,8 @@ static BatchPlan plan_batch(ffs_stream* s, const void* d_img, size_t pitch, size
     P.chain_first = P.list_path && P.aside && P.will_chain && !P.banded && c->tune.chain_first > 0 && depth <= c->tune.chain_first;
     P.path_bits = (P.use_log ? FFS_PATH_WAVE_LOGS : 0u) | (P.will_chain && !P.banded ? FFS_PATH_FRAME_CHAIN : 0u) | (P.banded ? FFS_PATH_BANDS : 0u)
                   | (P.runs_launch ? FFS_PATH_RUNS : 0u) | (!P.will_chain ? FFS_PATH_GRID_KERNELS : 0u) | (P.ext ? FFS_PATH_EXTENDED : 0u)
-                  | (P.window ? FFS_PATH_WINDOW : 0u) | (P.radial ? FFS_PATH_RADIAL_THRESHOLD : 0u);
+                  | (P.window ? FFS_PATH_WINDOW : 0u) | (P.radial ? FFS_PATH_RADIAL_THRESHOLD : 0u)
+                  | (P.radial && s->batch.radial_blur ? FFS_PATH_RADIAL_BLUR : 0u);
     return P;
 }
 

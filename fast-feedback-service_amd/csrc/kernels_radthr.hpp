@@ -20,9 +20,22 @@
 // equal (shell, value) pairs kept in registers, as k_radial keeps its run of equal bins, and added when the pair changes; 0 (default), the
 // one that measured faster for the pixel size -- the run for 16-bit pixels (0.454 against 0.476 ms, 32 Eiger-16M frames, 100 shells), the
 // plain add for 32-bit (0.297 against 0.324 ms, Jungfrau-9M).  DESIGN.md section 3.9 has both.
+//
+// With a blur (ffs_ctx_set_radial_blur narrow | wide) the first and the third launch take their blurred forms, at the
+// end of this file, and decide on v = floor(S / Wn) of radial_blur_model.hpp in place of p; k_radthr_cut is the same.  Both recompute the
+// blur from the frame (no blurred frame is stored):
+//   k_radthr_hist_blur<PixelT, R>    the same grid, workgroup and table; a wave takes units of a band -- a run of up to 32 contiguous rows of
+//                                    a strip of 62 eight-pixel groups -- instead of every sixteenth row, with blur_walk below.
+//   k_radthr_strong_blur<PixelT, R>  grid (strips x runs, frames): a wave per such unit (four tiles), the tile count added every eight rows;
+//                                    a strong pixel also has p >= 1.
+//   blur_walk                        a ring of 2R + 1 rows of the lane's group (p x tap and the tap bits) in registers; per row the vertical
+//                                    pass, the R edge columns of either neighbour from the lanes beside (lanes 0 and 63 carry the neighbouring
+//                                    strips' groups and own no output), the horizontal pass, a shift where every tap is there and the
+//                                    division by the weight of the taps that are, under a branch, where not.
 #pragma once
 #include "ffs_device.h"
 #include "kernels_radial.hpp"
+#include "radial_blur_model.hpp"
 #include "radial_threshold_model.hpp"
 
 namespace ffsamd {
@@ -210,6 +223,221 @@ __global__ __launch_bounds__(64) void k_radthr_strong(RadThrArgs a) {
         const uint32_t total = __builtin_amdgcn_readlane(wave_inclusive_scan(cnt), 63);
         if (lane == 0u) atomicAdd(a.tile_counts + (uint64_t)frame * a.n_tiles + tile, total);
     }
+}
+
+// ---- the blurred forms (ffs_ctx_set_radial_blur) ---------------------------------------------------------------
+// A wave walks a run of contiguous rows of one strip.  Lanes 1 .. 62 own a group of eight pixels each; lanes 0 and 63 carry the last group
+// of the strip to the left and the first of the strip to the right and own no output, so every owning lane finds its horizontal neighbours
+// in the lanes beside it.  A run re-reads R rows above and below itself; rows outside the frame and groups outside the row are never read.
+constexpr int kRadBlurOwners = 62;      // groups a wave owns
+constexpr int kRadBlurRunRows = 32;     // rows of a wave's run (a multiple of kTileRows): 2R / 32 of the rows are read twice
+__device__ __forceinline__ uint32_t radblur_strips(int W) { return ((uint32_t)(W + 7) / 8u + (uint32_t)kRadBlurOwners - 1u) / (uint32_t)kRadBlurOwners; }
+
+// A row of a lane's group as it was loaded ...
+template <typename PixelT>
+struct BlurRaw {
+    uint4 p0, p1;
+    uint32_t mb;
+};
+// ... and as the stencil keeps it: p x tap, packed as the frame has the pixels, and the tap bits of the group with the R nearest of either
+// neighbour (bit i: the pixel at x = 8g - R + i)
+template <typename PixelT>
+struct BlurRow {
+    uint32_t w[2 * sizeof(PixelT)];
+    uint32_t te;
+};
+template <typename PixelT>
+__device__ __forceinline__ uint32_t blur_px(const BlurRow<PixelT>& r, int j) {
+    if constexpr (sizeof(PixelT) == 2) return (j & 1) ? r.w[j >> 1] >> 16 : r.w[j >> 1] & 0xFFFFu;
+    else return r.w[j];
+}
+
+template <typename PixelT>
+__device__ __forceinline__ BlurRaw<PixelT> blur_load(const RadialIn& in, const uint8_t* img, int y, int g, bool own) {
+    BlurRaw<PixelT> r;
+    r.p0 = make_uint4(0u, 0u, 0u, 0u);
+    r.p1 = r.p0;
+    r.mb = 0u;
+    // (radthr_row's reads: a group that straddles W stays inside the row's pitch_px pixels, and what it reads beyond W has no mask bit)
+    if (own && y >= 0 && y < in.H) {
+        const uint8_t* rp = img + (uint64_t)y * in.pitch + (uint64_t)g * (8u * sizeof(PixelT));
+        r.p0 = *reinterpret_cast<const uint4*>(rp);
+        if constexpr (sizeof(PixelT) == 4) r.p1 = *reinterpret_cast<const uint4*>(rp + 16);
+        r.mb = in.maskbits[(uint64_t)y * in.mpitch + (uint32_t)g];
+    }
+    return r;
+}
+__device__ __forceinline__ uint4 blur_bins(const RadialIn& in, int y, int g, bool own) {
+    if (own && y < in.H) return *reinterpret_cast<const uint4*>(in.bins + (uint64_t)y * in.bin_pitch + (uint64_t)g * 8u);
+    return make_uint4(0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu);
+}
+
+// The tap rule on a loaded row.  Called by the whole wave: the neighbours' tap bits come across the lanes.
+template <typename PixelT, int R>
+__device__ __forceinline__ BlurRow<PixelT> blur_taps(const BlurRaw<PixelT>& raw, uint32_t limit) {
+    BlurRow<PixelT> r;
+    uint32_t tb = 0u;
+    uint32_t p[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        p[j] = sizeof(PixelT) == 2 ? lane_pixel<8>(raw.p0, j) : lane_pixel<4>(j < 4 ? raw.p0 : raw.p1, j & 3);
+        const bool tap = radblur_tap((raw.mb >> j) & 1u, p[j], limit);
+        tb |= (tap ? 1u : 0u) << j;
+        p[j] = tap ? p[j] : 0u;
+    }
+    if constexpr (sizeof(PixelT) == 2) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) r.w[k] = p[2 * k] | (p[2 * k + 1] << 16);
+    } else {
+#pragma unroll
+        for (int k = 0; k < 8; ++k) r.w[k] = p[k];
+    }
+    const uint32_t left = (uint32_t)__shfl_up((int)tb, 1, 64), right = (uint32_t)__shfl_down((int)tb, 1, 64);
+    r.te = (left >> (8 - R)) | (tb << R) | ((right & ((1u << R) - 1u)) << (8 + R));
+    return r;
+}
+
+// The walk: rows ya .. yb - 1 of group g, row after row, the load of the row that enters the ring next in flight while this one is
+// decided.  each(y, v, counts, centre, bn): v[j] the blurred value of pixel j where bit j of `counts` says the pixel is a tap, the centre
+// row as the ring has it (p x tap) and the row's bin entries.  Called by the whole wave with ya, yb the same in every lane.
+template <typename PixelT, int R, typename Each>
+__device__ __forceinline__ void blur_walk(const RadialIn& in, const uint8_t* img, int g, bool own, int ya, int yb, Each&& each) {
+    constexpr int N = 2 * R + 1;
+    constexpr uint32_t kAll = (1u << N) - 1u;
+    BlurRow<PixelT> ring[N];   // rows y - R .. y + R
+#pragma unroll
+    for (int k = 0; k < N; ++k) ring[k] = blur_taps<PixelT, R>(blur_load<PixelT>(in, img, ya - R + k, g, own), in.limit);
+    for (int y = ya; y < yb; ++y) {
+        // (both loads are read behind the arithmetic below)
+        const BlurRaw<PixelT> raw = blur_load<PixelT>(in, img, y + 1 < yb ? y + 1 + R : in.H, g, own);
+        const uint4 bn = blur_bins(in, y, g, own);
+        // the vertical pass, then the horizontal one over the group and R columns of either neighbour
+        uint32_t e[8 + 2 * R];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            uint32_t s = 0u;
+#pragma unroll
+            for (int k = 0; k < N; ++k) s += radblur_w1(R, k - R) * blur_px(ring[k], j);
+            e[R + j] = s;
+        }
+#pragma unroll
+        for (int i = 0; i < R; ++i) {
+            e[i] = (uint32_t)__shfl_up((int)e[R + 8 - R + i], 1, 64);
+            e[R + 8 + i] = (uint32_t)__shfl_down((int)e[R + i], 1, 64);
+        }
+        uint32_t present = ring[0].te;   // columns whose taps are all there
+#pragma unroll
+        for (int k = 1; k < N; ++k) present &= ring[k].te;
+        const uint32_t counts = (ring[R].te >> R) & 0xFFu;
+        uint32_t v[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            uint32_t S = 0u;
+#pragma unroll
+            for (int d = -R; d <= R; ++d) S += radblur_w1(R, d) * e[R + j + d];
+            v[j] = S >> radblur_shift(R);
+            if (((counts >> j) & 1u) && ((present >> j) & kAll) != kAll) {   // a tap is missing: the weight of those that are there
+                uint32_t Wn = 0u;
+#pragma unroll
+                for (int k = 0; k < N; ++k) Wn += radblur_w1(R, k - R) * radblur_row_weight(R, (ring[k].te >> j) & kAll);
+                v[j] = radblur_value(R, S, Wn);
+            }
+        }
+        each(y, v, counts, ring[R], bn);
+#pragma unroll
+        for (int k = 0; k + 1 < N; ++k) ring[k] = ring[k + 1];
+        ring[N - 1] = blur_taps<PixelT, R>(raw, in.limit);
+    }
+}
+
+template <typename PixelT, int R>
+__global__ __launch_bounds__(kRadThrHistThreads) void k_radthr_hist_blur(RadThrArgs a) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t radthr_smem[];
+    uint32_t* tab = reinterpret_cast<uint32_t*>(radthr_smem);
+    const uint32_t n_tab = a.in.n_bins * (uint32_t)kRadThrCounters;
+    const uint32_t frame = blockIdx.x, band = blockIdx.y;
+    for (uint32_t i = threadIdx.x; i < n_tab; i += kRadThrHistThreads) tab[i] = 0u;
+    __syncthreads();
+
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const uint8_t* img = static_cast<const uint8_t*>(a.in.image) + (uint64_t)frame * a.in.frame_stride;
+    const int y0 = (int)(band * a.in.band_rows), y1 = min(a.in.H, y0 + (int)a.in.band_rows);
+    const uint32_t strips = radblur_strips(a.in.W);
+    const uint32_t units = strips * (uint32_t)((y1 - y0 + kRadBlurRunRows - 1) / kRadBlurRunRows);   // a unit: a run of rows of one strip
+    for (uint32_t u = wave; u < units; u += (uint32_t)kRadThrHistWaves) {
+        const uint32_t strip = u % strips, run = u / strips;
+        const int g = (int)(strip * (uint32_t)kRadBlurOwners + lane) - 1;
+        const bool own = g >= 0 && g * 8 < a.in.W;
+        const bool owner = own && lane >= 1u && lane <= (uint32_t)kRadBlurOwners;
+        const int ya = y0 + (int)run * kRadBlurRunRows, yb = min(y1, ya + kRadBlurRunRows);
+        blur_walk<PixelT, R>(a.in, img, g, own, ya, yb, [tab, owner](int, const uint32_t (&v)[8], uint32_t counts, const BlurRow<PixelT>&, const uint4& bn) {
+            if (!owner) return;
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                const uint32_t b = radial_bin_entry(bn, j);
+                if (((counts >> j) & 1u) && b != kRadialNone) atomicAdd(&tab[b * (uint32_t)kRadThrCounters + min(v[j], (uint32_t)kRadThrValues)], 1u);
+            }
+        });
+    }
+    __syncthreads();
+    uint32_t* out = a.hist + (uint64_t)frame * n_tab;
+    for (uint32_t i = threadIdx.x; i < n_tab; i += kRadThrHistThreads) {
+        const uint32_t c = tab[i];
+        if (c != 0u) atomicAdd(&out[i], c);
+    }
+}
+
+// grid (strips x runs, frames): a wave per run of kRadBlurRunRows rows of one strip; what k_radthr_strong leaves, decided on v, and p >= 1
+template <typename PixelT, int R>
+__global__ __launch_bounds__(64) void k_radthr_strong_blur(RadThrArgs a) {
+    __shared__ uint32_t s_cut[kRadThrMaxBins];
+    const uint32_t lane = threadIdx.x;
+    const uint32_t strips = radblur_strips(a.in.W);
+    const uint32_t strip = blockIdx.x % strips, run = blockIdx.x / strips, frame = blockIdx.y;
+    for (uint32_t i = lane; i < kRadThrMaxBins; i += 64u) s_cut[i] = i < a.in.n_bins ? a.cut[(uint64_t)frame * a.in.n_bins + i] : kRadThrNever;
+    __syncthreads();
+    const int g = (int)(strip * (uint32_t)kRadBlurOwners + lane) - 1;
+    const bool own = g >= 0 && g * 8 < a.in.W;
+    const bool owner = own && lane >= 1u && lane <= (uint32_t)kRadBlurOwners;
+    const int ya = (int)run * kRadBlurRunRows, yb = min(a.in.H, ya + kRadBlurRunRows);
+    const uint8_t* img = static_cast<const uint8_t*>(a.in.image) + (uint64_t)frame * a.in.frame_stride;
+    uint8_t* plane = a.bits + (uint64_t)frame * a.plane_frame_stride;
+    uint8_t* sbytes = a.strong_bytes + (uint64_t)frame * a.bytes_frame_stride;
+    uint32_t cnt = 0u;
+    blur_walk<PixelT, R>(a.in, img, g, own, ya, yb, [&](int y, const uint32_t (&v)[8], uint32_t counts, const BlurRow<PixelT>& centre, const uint4& bn) {
+        uint32_t sb = 0u;
+        if (owner) {
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                const uint32_t b = radial_bin_entry(bn, j);
+                const uint32_t cutoff = s_cut[b & (kRadThrMaxBins - 1u)];
+                const bool in_shell = ((counts >> j) & 1u) && b != kRadialNone;
+                if (in_shell && v[j] > cutoff && (double)v[j] > a.threshold && blur_px(centre, j) >= 1u) sb |= 1u << j;
+            }
+            if (sb) {
+                plane[(uint64_t)y * a.in.mpitch + (uint32_t)g] = (uint8_t)sb;   // (the plane is all zero when the kernel starts)
+                if (a.occ) {
+                    const uint32_t ob = (uint32_t)y * a.occ_spr + ((uint32_t)g >> 4);
+                    atomicOr(a.occ + (uint64_t)frame * a.occ_frame_words + (ob >> 5), 1u << (ob & 31u));
+                }
+            }
+            if (a.dense_mask) {
+                uint2 bytes;
+                bytes.x = (sb & 1u) | ((sb & 2u) << 7) | ((sb & 4u) << 14) | ((sb & 8u) << 21);
+                bytes.y = ((sb >> 4) & 1u) | ((sb & 0x20u) << 3) | ((sb & 0x40u) << 10) | ((sb & 0x80u) << 17);
+                *reinterpret_cast<uint2*>(sbytes + (uint64_t)y * a.bpitch + (uint64_t)g * 8u) = bytes;
+            }
+        }
+        cnt += (uint32_t)__popc(sb);
+        if ((y & (kTileRows - 1)) == kTileRows - 1 || y + 1 == yb) {   // the tile's count (a run starts on a tile's first row)
+            if (__ballot(cnt != 0u)) {
+                const uint32_t total = __builtin_amdgcn_readlane(wave_inclusive_scan(cnt), 63);
+                if (lane == 0u) atomicAdd(a.tile_counts + (uint64_t)frame * a.n_tiles + (uint32_t)(y / kTileRows), total);
+            }
+            cnt = 0u;
+        }
+    });
 }
 
 }  // namespace ffsamd

@@ -24,7 +24,7 @@ void usage() {
       "                  [--max-valid trusted|none|N] [--max-valid-scope centre|window] [--min-count N] [--kernel-size N | NX,NY]\n"
       "                  [--gain G] [--gain-map FILE] [--radial-bins N] [--pixel-stats PREFIX]\n"
       "                  [--spot-background B]\n"
-      "                  [--n-iqr X]\n"
+      "                  [--n-iqr X] [--radial-blur narrow|wide]\n"
       "                  [--devices D0,D1,... | --gpus N] [--no-numa-pinning] [--single-buffer] [--all-threads] [--read-only] [--clean-exit]\n"
       "--max-valid: a centre pixel above this value is never strong (the reference's kernels test it against the\n"
       "              data set's trusted maximum).  trusted (default) = the frame source's trusted-range maximum when it is\n"
@@ -48,11 +48,14 @@ void usage() {
       "              \"radial_count\", \"radial_sum\" and \"radial_sum_sq\" arrays in every image's JSON line (pixels above --max-valid and\n"
       "              masked pixels, --dmin / --dmax included, are left out).  Needs the detector geometry and the wavelength --dmin needs\n"
       "-a radial_profile: a pixel is a spot candidate when it stands above median + X x IQR of its resolution shell, both taken per image from\n"
-      "              the shell's valid pixels (DIALS spotfinder.threshold.algorithm = radial_profile, without its blur): for high or steeply\n"
+      "              the shell's valid pixels (DIALS spotfinder.threshold.algorithm = radial_profile): for high or steeply\n"
       "              radial background, ice and solvent rings.  The shells are --radial-bins's (default 100 here, at most 128); --n-iqr X\n"
       "              (default 6, 0 .. 2^20).  --min-count, --kernel-size, --gain and --gain-map play no part.  Every image's JSON line gains\n"
       "              \"radial_median\", \"radial_cutoff\" and \"radial_status\" (0 decided, 1 no pixels, 2 more than a quarter at or above 256: no\n"
-      "              spots in that shell).  Not with --validate\n"
+      "              spots in that shell).  --radial-blur narrow | wide (default none) smooths the image ahead of the threshold, over its valid\n"
+      "              pixels only, with the 3 x 3 kernel (1 2 1) x (1 2 1) / 16 or the 5 x 5 kernel (1 4 6 4 1) x (1 4 6 4 1) / 256 (DIALS's\n"
+      "              radial_profile.blur: fewer noise peaks, split spots combined); intensities and centroids stay the raw pixels', the three\n"
+      "              arrays are the blurred image's.  Not with --validate\n"
       "--pixel-stats: per pixel over the whole run, in how many images it was at or below --max-valid (32-bit pixels: and below 2^24), the sum\n"
       "              and the sum of squares of its values there, and the largest of them: what a mask, a gain map (variance / mean of a\n"
       "              flat run) and the maximum image of a serial run are made from.  Masked pixels are in them.  Written after the last\n"
@@ -219,6 +222,13 @@ Args parse_args(int argc, char** argv) {
             char* end = nullptr;
             r.n_iqr = std::strtod(v.c_str(), &end);
             if (v.empty() || *end || !(r.n_iqr >= 0.0 && r.n_iqr <= 1048576.0)) arg_error("--n-iqr takes a number in 0 .. 2^20: " + v);
+        }
+        else if (s == "--radial-blur") {
+            const std::string& v = need(i, s);
+            if (v == "none") r.radial_blur = 0;
+            else if (v == "narrow") r.radial_blur = 1;
+            else if (v == "wide") r.radial_blur = 2;
+            else arg_error("--radial-blur takes narrow or wide (or none): " + v);
         }
         else if (s == "--min-count") { r.min_count = u32(need(i, s), s); if (r.min_count < 2) arg_error("--min-count must be at least 2"); }
         else if (s == "--no-numa-pinning") r.no_numa_pinning = true;

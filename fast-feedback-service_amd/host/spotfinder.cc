@@ -988,9 +988,13 @@ int main(int argc, char** argv) {
     if (radial_algo) {
         for (ffs_ctx* cx : ctxs) {
             FFS_CHECK(cx, ffs_ctx_set_radial_threshold(cx, args.n_iqr));
+            FFS_CHECK(cx, ffs_ctx_set_radial_blur(cx, args.radial_blur));
             FFS_CHECK(cx, ffs_ctx_set_params(cx, &prm));
         }
         std::printf("Radial-profile threshold: a strong pixel stands above median + %g x IQR of its shell\n", args.n_iqr);
+        if (args.radial_blur)
+            std::printf("Radial blur: %s, a %d x %d kernel over the valid pixels ahead of the threshold\n", args.radial_blur == FFS_RADIAL_BLUR_NARROW ? "narrow" : "wide",
+                        2 * args.radial_blur + 1, 2 * args.radial_blur + 1);
     }
     // --pixel-stats: every context accumulates from its first batch on (the validation contexts see the same frames again, and do not)
     if (!args.pixel_stats.empty())

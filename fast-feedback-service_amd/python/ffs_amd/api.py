@@ -99,6 +99,8 @@ RADIAL_SHELL_DT = np.dtype([("n_pixels", "<u4"), ("n_overflow", "<u4"), ("q1", "
 assert RADIAL_SHELL_DT.itemsize == 32
 RADIAL_THR_OK, RADIAL_THR_EMPTY, RADIAL_THR_OVERFLOW = 0, 1, 2   # FFS_RADIAL_THR_*
 ALGO_RADIAL_PROFILE = 2   # FFS_ALGO_RADIAL_PROFILE: Context.set_params(algorithm=...), with a bin map of at most 128 bins set
+RADIAL_BLUR_NONE, RADIAL_BLUR_NARROW, RADIAL_BLUR_WIDE = 0, 1, 2   # FFS_RADIAL_BLUR_*: what Context.set_radial_blur takes ("none" / "narrow" / "wide")
+RADIAL_BLURS = {"none": RADIAL_BLUR_NONE, "narrow": RADIAL_BLUR_NARROW, "wide": RADIAL_BLUR_WIDE}
 
 
 PIXEL_STATS_MODES = {"off": 0, "start": 1, "resume": 2}   # FFS_PIXEL_STATS_OFF / _START / _RESUME
@@ -128,7 +130,7 @@ EXPORTS = [
     "ffs_ctx_set_radial_bins", "ffs_stream_radial_profile", "ffs_bench_radial",
     "ffs_ctx_set_pixel_stats", "ffs_ctx_get_pixel_stats", "ffs_bench_pixel_stats",
     "ffs_stream_spot_backgrounds",
-    "ffs_ctx_set_radial_threshold", "ffs_stream_radial_thresholds",
+    "ffs_ctx_set_radial_threshold", "ffs_stream_radial_thresholds", "ffs_ctx_set_radial_blur",
 ]
 
 _lib = None
@@ -159,6 +161,7 @@ def load_library():
         L.ffs_stream_radial_profile.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(_RadialProfile)]
         L.ffs_bench_radial.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_uint32, C.c_uint32, C.POINTER(C.c_float)]
         L.ffs_ctx_set_radial_threshold.argtypes = [C.c_void_p, C.c_double]
+        L.ffs_ctx_set_radial_blur.argtypes = [C.c_void_p, C.c_int]
         L.ffs_stream_radial_thresholds.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_void_p), C.POINTER(C.c_uint32)]
         L.ffs_ctx_set_pixel_stats.argtypes = [C.c_void_p, C.c_int]
         L.ffs_ctx_get_pixel_stats.argtypes = [C.c_void_p, C.POINTER(_PixelStats)]
@@ -359,6 +362,17 @@ class Context:
         strong above floor(median + n_iqr * iqr) of its shell.  Default 6.  Kept across set_params; a batch takes it as it is at submit.
         Refused (FfsError, state unchanged): NaN, infinite, below 0 or above 2^20."""
         self._check(self._lib.ffs_ctx_set_radial_threshold(self._h, float(n_iqr)))
+
+    def set_radial_blur(self, blur):
+        """ffs_ctx_set_radial_blur: "none" (default), "narrow" (3 x 3, (1 2 1) x (1 2 1) / 16) or "wide" (5 x 5, (1 4 6 4 1) x (1 4 6 4 1) / 256),
+        or the integers RADIAL_BLUR_* -- the radial-profile threshold then decides on the image smoothed over its valid pixels, and a strong
+        pixel also has p >= 1; everything behind the strong plane reads the raw pixels.  Kept across set_params, accepted under any
+        algorithm; a batch takes it as it is at submit.  Refused (FfsError, state unchanged): any other value."""
+        if isinstance(blur, str):
+            if blur not in RADIAL_BLURS:
+                raise ValueError('blur must be "none", "narrow" or "wide", got %r' % (blur,))
+            blur = RADIAL_BLURS[blur]
+        self._check(self._lib.ffs_ctx_set_radial_blur(self._h, int(blur)))
 
     def set_pixel_stats(self, mode: str):
         """ffs_ctx_set_pixel_stats: "start" (zero the per-pixel statistics and accumulate every frame submitted on the context from now
@@ -566,7 +580,7 @@ class Stream:
         return dict(zip(("h2d", "threshold", "ccl", "d2h", "total"), list(t)))
 
     PATH_BITS = {"wave_logs": 1, "frame_chain": 2, "bands": 4, "runs": 8, "grid_kernels": 16, "extended": 32, "window": 64, "radial": 128, "pixel_stats": 256,
-                 "radial_threshold": 512}
+                 "radial_threshold": 512, "radial_blur": 1024}
 
     def last_path(self):
         """ffs_stream_last_path: (set of the launches the last batch took, times ffs_wait ran it again)."""

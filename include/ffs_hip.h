@@ -78,7 +78,7 @@ typedef struct {
 /* The radial-profile threshold: a pixel is strong when it stands far above the background of its shell of the context's radial bin map
  * (ffs_ctx_set_radial_bins, at most 128 bins here), measured per frame by the shell's median and interquartile range.  The reference has
  * no counterpart (its `--algorithm` knows the two above, spotfinder/spotfinder.cc:338-342); modelled on DIALS's
- * spotfinder.threshold.algorithm = radial_profile without its blur, and no parity with DIALS is claimed: this definition is the contract.
+ * spotfinder.threshold.algorithm = radial_profile (its blur: ffs_ctx_set_radial_blur, off by default), and no parity with DIALS is claimed: this definition is the contract.
  *   A pixel COUNTS in shell b under the radial profile's rule (ffs_ctx_set_radial_bins): b != 0xFFFF, its valid-pixel mask bit is set (the
  *   mask as it stands at submit), p <= max_valid when max_valid >= 0 (both scopes), and for 32-bit pixels p < 2^24.
  *   Per frame and shell, over its N counting pixels, from a histogram of one-count bins 0..255 and a tail: n_overflow = those with p >= 256;
@@ -274,6 +274,34 @@ int ffs_ctx_set_radial_bins(ffs_ctx *ctx, const uint16_t *bin_of_pixel, uint32_t
  * stands.  Default 6 (DIALS's radial_profile.n_iqr).  Per context, kept across ffs_ctx_set_params; a batch takes it as it is at submit.
  * FFS_ERR_INVALID, state unchanged: n_iqr is not finite, below 0 or above 2^20 (the cutoff is a uint32).  (No counterpart in the reference.) */
 int ffs_ctx_set_radial_threshold(ffs_ctx *ctx, double n_iqr);
+
+/* The blur of the radial-profile threshold (FFS_ALGO_RADIAL_PROFILE): a small smoothing of the image ahead of the threshold, DIALS's
+ * radial_profile.blur = narrow | wide ("to reduce noise peaks and to combine split spots").  Everything is integers.
+ *   Weights, separable, w(dx, dy) = w1(dx) * w1(dy):  narrow w1 = (1, 2, 1), a 3 x 3 kernel of full weight 16 (DIALS's narrow kernel
+ *   exactly);  wide w1 = (1, 4, 6, 4, 1), a 5 x 5 kernel of full weight 256 (the binomial of variance 1 in place of DIALS's 5 x 5 table of
+ *   rounded Gaussian values: no parity with DIALS is claimed for it, as for the rest of this algorithm).
+ *   A pixel is a TAP when it lies inside the image, its bit in the valid-pixel mask (as it stands at submit) is set, p <= max_valid when
+ *   max_valid >= 0 (both scopes), and for 32-bit pixels p < 2^24.  The bin map plays no part for taps.  A pixel COUNTS in shell b when it
+ *   is a tap and its bin entry is b, not 0xFFFF: the rule of FFS_ALGO_RADIAL_PROFILE.
+ *   For a counting pixel at (x, y):  S = sum of w(dx, dy) * p(x + dx, y + dy) and Wn = sum of w(dx, dy), both over the offsets of the
+ *   kernel whose pixel is a tap (Wn is at least the centre's weight), and v = floor(S / Wn).  Masked pixels, overloads and the image
+ *   border leave the sum and the weight together: a constant patch keeps its value right up to a module gap or the image edge.
+ *   S <= 256 * (2^24 - 1) = 4 294 967 040 fits 32 unsigned bits.
+ *   With a blur, v takes the place of p in everything the algorithm decides: the histogram of one-count bins 0..255 and a tail (v >= 256),
+ *   hence n_pixels, n_overflow, the quartiles, the status and the cutoff of every ffs_radial_shell, and the strong test.  A pixel is
+ *   STRONG when it counts in shell b, b's status is 0, v > cutoff[b], (double)v > ffs_params.threshold, and p >= 1: a zero pixel beside a
+ *   bright one can have v > cutoff, and the peak search and the centroid division behind the strong plane rely on a strong pixel's
+ *   intensity being at least 1 (ffs_stack3d_add_slice).
+ *   Everything behind the strong plane reads the raw pixels and is what it is for any strong plane: lists, intensities, boxes,
+ *   reflections, the byte mask, the 3D stack, spot backgrounds; so do the radial profile of the batch and the pixel statistics.
+ * FFS_RADIAL_BLUR_NONE is the default.  Per context, kept across ffs_ctx_set_params, accepted under any algorithm and at any time; it
+ * plays a part only under FFS_ALGO_RADIAL_PROFILE.  A batch takes it as it stands at submit, and keeps it when ffs_wait runs it again;
+ * ffs_stream_last_path reports FFS_PATH_RADIAL_BLUR for a batch whose threshold ran blurred.  ffs_params keeps its layout.
+ * FFS_ERR_INVALID, state unchanged (ffs_last_error has the text): any other value.  (No counterpart in the reference.) */
+#define FFS_RADIAL_BLUR_NONE 0
+#define FFS_RADIAL_BLUR_NARROW 1
+#define FFS_RADIAL_BLUR_WIDE 2
+int ffs_ctx_set_radial_blur(ffs_ctx *ctx, int blur);
 
 /* Per-pixel statistics over a run: count, sum, sum of squares and maximum of every pixel over all frames the context sees -- what a
  * valid-pixel mask (dead pixels: mean 0; hot pixels: a mean far above the neighbours'), a gain map (variance / mean over a flat run) and
@@ -496,6 +524,7 @@ int ffs_stream_timings(ffs_stream *s, float ms[5]);
 #define FFS_PATH_RADIAL 128u       /* the batch computed a radial profile (ffs_ctx_set_radial_bins) */
 #define FFS_PATH_PIXEL_STATS 256u  /* the batch was folded into the per-pixel statistics (ffs_ctx_set_pixel_stats) */
 #define FFS_PATH_RADIAL_THRESHOLD 512u /* the radial-profile threshold decided the strong pixels (FFS_ALGO_RADIAL_PROFILE; no counterpart in the reference) */
+#define FFS_PATH_RADIAL_BLUR 1024u /* ... on the blurred image (ffs_ctx_set_radial_blur narrow or wide) */
 int ffs_stream_last_path(ffs_stream *s, uint32_t *path_bits, uint32_t *reruns);
 
 /* The radial profile (ffs_ctx_set_radial_bins) of frame `frame_in_batch` of the last batch ffs_wait returned on this stream: n_bins

@@ -12,7 +12,11 @@ pixels) and Jungfrau-9M (32-bit pixels), 32 frames a batch, 100 concentric shell
   pipeline  one process: ffs_bench_pipeline at the driver's shape (four streams, 32 frames, --steps after --warmup) on a context of
             algorithm 2 and on one of algorithm 0, alternating, --pipeline-rounds times; frames/s of each and their ratio.
 
+  blur      (--blur, instead of the two above) per workload and blur none | narrow | wide (ffs_ctx_set_radial_blur): the same two halves, the
+            stage over the unblurred stage of the same run, the read ceiling of the same run; held to tests/radial_blur_oracle.py.
+
   python3 tools/radial_threshold_cost.py --out profiles/NAME.jsonl
+  python3 tools/radial_threshold_cost.py --blur --out profiles/NAME.jsonl
 """
 import argparse
 import json
@@ -105,6 +109,64 @@ def kernel_workload(workload, args, out):
         c.close()
 
 
+def blur_workload(workload, args, out):
+    """--blur: the stage's two halves with blur none, narrow and wide (ffs_ctx_set_radial_blur), one context each on the same resident frames,
+    every row once per round, beside the read ceiling of the same run.  The first frames of every row are held to tests/radial_blur_oracle.py."""
+    import torch
+    import ffs_amd
+    import radial_blur_oracle as RB
+    import radial_oracle as R
+    from bench import WORKLOADS, make_inputs
+    W, H, dt, bpp = WORKLOADS[workload]
+    frames, mask = make_inputs(workload, args.frames, 0)
+    B, shells = args.batch, args.shells
+    bins = R.shell_bins(W, H, shells)
+    rows = {}
+    for blur in ("none", "narrow", "wide"):
+        c = ffs_amd.Context(W, H, dt, max_batch=B)
+        c.set_mask(mask)
+        c.set_radial_bins(bins, shells)
+        c.set_radial_blur(blur)
+        c.set_params(algorithm=ffs_amd.ALGO_RADIAL_PROFILE)
+        rows[blur] = (c, c.stream())
+    pitch, fstride = rows["none"][0].device_layout()
+    d = resident(torch, frames, B, H, W, dt, pitch)
+    hist = {k: [] for k in rows}
+    rest = {k: [] for k in rows}
+    hbm = []
+    for _ in range(args.rounds):
+        for blur, (c, st) in rows.items():
+            a, b = st.bench_threshold(d.data_ptr(), pitch, fstride, B, args.iters)
+            hist[blur].append(a)
+            rest[blur].append(b)
+        hbm.append(rows["none"][1].bench_hbm(args.iters)[0])
+    read = statistics.median(hbm)
+    must = 2.0 * float(W) * H * (np.dtype(dt).itemsize + 2 + 0.125) * B
+    base = statistics.median(hist["none"]) + statistics.median(rest["none"])
+    for blur, (c, st) in rows.items():
+        st.submit_device(d.data_ptr(), pitch, fstride, B)
+        res = st.wait()
+        match = None
+        if args.check > 0:
+            match = True
+            for f in range(args.check):
+                want = RB.threshold(frames[f % len(frames)], bins, shells, {"none": RB.NONE, "narrow": RB.NARROW, "wide": RB.WIDE}[blur], 6.0, 0.0, mask)
+                got = st.radial_thresholds(f)
+                match = match and all(np.array_equal(got[k], want[1][k]) for k in ("n_pixels", "n_overflow", "q1", "median", "q3", "cutoff", "status"))
+                match = bool(match and res[f].num_strong_pixels == int(want[0].sum()))
+        t_hist, t_rest = statistics.median(hist[blur]), statistics.median(rest[blur])
+        emit(out, {"mode": "blur", "workload": workload, "shells": shells, "blur": blur, "batch": B, "unique_frames": len(frames), "label": args.label,
+                   "rounds": args.rounds, "launches_per_round": args.iters, "ms_hist": round(t_hist, 4), "ms_cut_strong": round(t_rest, 4),
+                   "ms_stage": round(t_hist + t_rest, 4), "stage_over_unblurred": round((t_hist + t_rest) / base, 3),
+                   "ms_hist_rounds": [round(v, 4) for v in hist[blur]], "ms_cut_strong_rounds": [round(v, 4) for v in rest[blur]],
+                   "read_gbps": round(read, 1), "must_read_gbytes": round(must / 1e9, 4),
+                   "fraction_of_read_ceiling": round(must / (t_hist + t_rest) / 1e6 / read, 3),
+                   "strong_pixels": int(sum(r.num_strong_pixels for r in res)), "path": sorted(st.last_path()[0]), "oracle_match": match})
+    for c, st in rows.values():
+        st.close()
+        c.close()
+
+
 def pipeline(args, out):
     import torch
     import ffs_amd
@@ -154,9 +216,15 @@ def main():
     ap.add_argument("--pipeline-rounds", type=int, default=3)
     ap.add_argument("--label", default="")
     ap.add_argument("--no-j9", action="store_true")
+    ap.add_argument("--blur", action="store_true", help="only this: the stage's two halves with blur none, narrow and wide, both workloads, in one process")
     args = ap.parse_args()
     import torch  # noqa: F401  (before libffs_hip.so: one HIP runtime in the process)
     out = open(args.out, "a") if args.out else None
+    if args.blur:
+        blur_workload("eiger16m", args, out)
+        if not args.no_j9:
+            blur_workload("jungfrau9m", args, out)
+        return
     if "kernel" in args.modes:
         kernel_workload("eiger16m", args, out)
         if not args.no_j9:
