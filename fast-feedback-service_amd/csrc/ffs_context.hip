@@ -667,15 +667,15 @@ void stream_destroy_internal(ffs_stream* s) {
     radial_free(s);
     radthr_free(s);
     spotbg_free(s);
+    encoded_free(s);
     if (s->ev_stats) (void)hipEventDestroy(s->ev_stats);   // (the sparse stream, synchronised above, waited for it)
     // (d_n_comp, d_summary and d_overflow live inside the d_num_strong allocation)
     if (s->h_pack_tab) (void)hipHostFree(s->h_pack_tab);
     // (the stream's device buffers are one slab; what is allocated on first use is freed by itself)
-    void* dev[] = {s->d_slab, s->d_pack_k, s->d_pack_i, s->d_pack_tab, s->d_comp, s->d_tab, s->d_ext_pair[0], s->d_ext_pair[1], s->d_wlog, s->d_wlog_n, s->d_wpix,
-                   s->d_band_hdr, s->d_band_acc, s->d_band_seam, s->d_bo_frames, s->d_bo_lane, s->d_bo_map, s->d_bo_state};
+    void* dev[] = {s->d_slab, s->d_pack_k, s->d_pack_i, s->d_pack_tab, s->d_ext_pair[0], s->d_ext_pair[1], s->d_wlog, s->d_wlog_n, s->d_wpix, s->d_band_hdr, s->d_band_acc, s->d_band_seam};
     for (void* p : dev)
         if (p) (void)hipFree(p);
-    void* host[] = {s->h_tab, s->h_bo_frames, s->h_counts, s->h_recs, s->h_list_k, s->h_list_i, s->h_mask};
+    void* host[] = {s->h_counts, s->h_recs, s->h_list_k, s->h_list_i, s->h_mask};
     for (void* p : host)
         if (p) (void)hipHostFree(p);
     if (s->h_img) {   // kept for the next stream of the context

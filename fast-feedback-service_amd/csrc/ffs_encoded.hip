@@ -1,0 +1,285 @@
+// ffs_encoded.hip -- encoded input from entry point to teardown: bitshuffle-LZ4 chunks (kernels_decode.hpp) and CBF byte-offset chunks
+// (kernels_byteoffset.hpp) cross PCIe as they lie in the file and are decoded into the stream's pitched device image, which enqueue_batch
+// (ffs_submit.hip) then takes like any other.  The two decoders' kernels are included here and nowhere else.  What is decided about a batch
+// -- may a chunk be a frame, where do the chunks lie, which bytes are copied, the tables the kernels read -- is encoded_plan.hpp's, without
+// HIP; this unit allocates, copies, records and launches.  The codec is looked at by prepare and launch (and the chunk check) only.
+#include "ffs_internal.hpp"
+#include "kernels_decode.hpp"
+#include "kernels_byteoffset.hpp"
+
+static_assert(sizeof(BlockEntry) == sizeof(uint2), "DecodeArgs::table reads the block table as uint2");
+
+const char* encoded_corruption(uint32_t overflow) {
+    if (overflow & kOvfCorruptLz4) return "corrupt bitshuffle-LZ4 chunk: an LZ4 block did not decode to its block size";
+    if (overflow & kOvfCorruptByteOffset) return "corrupt byte-offset chunk: it holds fewer elements than the frame has pixels";
+    return nullptr;
+}
+
+void encoded_free(ffs_stream* s) {
+    EncodedState& E = s->enc;
+    for (void* p : {(void*)E.d_comp, (void*)E.d_tab, (void*)E.d_bo_frames, (void*)E.d_bo_lane, (void*)E.d_bo_map, (void*)E.d_bo_state}) (void)hipFree(p);
+    for (void* p : {(void*)E.h_tab, (void*)E.h_bo_frames}) (void)hipHostFree(p);
+    E = EncodedState{};
+}
+
+// a refusal: its text goes where the caller keeps errors (the context's text of the calling thread, or the helper thread's job_err)
+template <typename Err>
+static int refuse(Err& err, int rc, const std::string& text) { err = text; return rc; }
+
+// a table of max_batch rows the host writes and a kernel reads: its device and pinned host copies, made on first use
+template <typename T>
+static bool ensure_table(T** dev, T** host, size_t bytes) {
+    if (*dev) return true;
+    if (dmalloc(dev, bytes) == hipSuccess && hipHostMalloc(reinterpret_cast<void**>(host), bytes, hipHostMallocDefault) == hipSuccess) return true;
+    (void)hipGetLastError();
+    (void)hipFree(*dev);   // (both or neither: the next batch tries again)
+    *dev = nullptr;
+    return false;
+}
+
+// A batch whose chunks are on their way to the device: what prepare leaves for launch
+struct EncodedBatch {
+    int codec = FFS_CODEC_BSLZ4;
+    std::vector<size_t> base, sizes;   // per chunk: its offset in the staging buffer and in d_comp, its bytes
+    uint32_t bo_max_tiles = 0;         // byte-offset: tiles of the longest chunk, the launches' grid
+};
+
+// byte-offset chunks need no index: the frame table is written and the summary tables are sized here, on the caller's thread
+static int prepare_byte_offset(ffs_stream* s, EncodedBatch& b) {
+    ffs_ctx* c = s->ctx;
+    EncodedState& E = s->enc;
+    if (!ensure_table(&E.d_bo_frames, &E.h_bo_frames, (size_t)s->max_batch * sizeof(BoFrame)))
+        return refuse(c->err, FFS_ERR_NOMEM, "allocation of the byte-offset frame table failed");
+    const BoTiles t = bo_frame_table(b.base.data(), b.sizes.data(), (uint32_t)b.base.size(), (uint64_t)c->L.W * c->L.H, E.h_bo_frames);
+    b.bo_max_tiles = t.max_tiles;
+    if (t.sum <= E.bo_tiles_cap) return FFS_OK;
+    // (the stream is idle, but its last decode may still read the tables on a decode-only path: they are freed behind both streams)
+    if (E.d_bo_lane) {
+        HIP_TRY(c, hipStreamSynchronize(s->st_up));
+        HIP_TRY(c, hipStreamSynchronize(s->st));
+    }
+    (void)hipFree(E.d_bo_lane); (void)hipFree(E.d_bo_map); (void)hipFree(E.d_bo_state);
+    E.d_bo_lane = nullptr; E.d_bo_map = nullptr; E.d_bo_state = nullptr;
+    E.bo_tiles_cap = 0;
+    const size_t want = t.sum + t.sum / 4 + 16;
+    if (dmalloc(&E.d_bo_lane, want * 7 * 64 * sizeof(uint2)) != hipSuccess || dmalloc(&E.d_bo_map, want * 7 * sizeof(uint2)) != hipSuccess
+        || dmalloc(&E.d_bo_state, want * sizeof(uint4)) != hipSuccess) {
+        (void)hipGetLastError();
+        return refuse(c->err, FFS_ERR_NOMEM, "allocation of the byte-offset summary tables failed");
+    }
+    E.bo_tiles_cap = want;
+    return FFS_OK;
+}
+
+// Caller's thread: checks the chunks, places them in the pinned staging buffer (unless they already are there), starts their copy to the
+// device and records ev[6] behind it.  A failure leaves no copy reading memory the caller gets back.
+static int prepare(ffs_stream* s, int codec, const void* const* chunks, const size_t* chunk_bytes, uint32_t n, EncodedBatch& b) {
+    ffs_ctx* c = s->ctx;
+    EncodedState& E = s->enc;
+    const size_t W = (size_t)c->L.W, H = (size_t)c->L.H, es = (size_t)c->pixel_bytes;
+    const bool byte_offset = codec == FFS_CODEC_BYTE_OFFSET;
+    b.codec = codec;
+    if (!byte_offset && !E.d_tab) {
+        E.blocking = bshuf_blocking(W * H, es);
+        if (!ensure_table(&E.d_tab, &E.h_tab, (size_t)s->max_batch * (E.blocking.blocks + 1) * sizeof(BlockEntry)))
+            return refuse(c->err, FFS_ERR_NOMEM, "allocation of the compressed-chunk buffers failed");
+    }
+    std::string why;
+    for (uint32_t f = 0; f < n; ++f)
+        if (!chunk_ok(codec, chunks[f], chunk_bytes[f], W, H, es, why)) return refuse(c->err, FFS_ERR_INVALID, why);
+    Placement pl;
+    if (!place_chunks(chunks, chunk_bytes, n, s->h_img, s->h_img_bytes, b.base, pl))
+        return refuse(c->err, FFS_ERR_INVALID, "ffs_submit_compressed: either all chunks lie in the stream's host buffer or none");
+    if (!pl.in_place) {
+        FFS_TRY(ensure_host_staging(s, pl.staging));   // (grows with headroom; kept from then on)
+        for (uint32_t f = 0; f < n; ++f) std::memcpy(s->h_img + b.base[f], chunks[f], chunk_bytes[f]);
+    }
+    if (pl.hi > kMaxStagedBytes) return refuse(c->err, FFS_ERR_INVALID, "ffs_submit_compressed: more than 4 GiB of chunks in one batch");
+    if (E.d_comp_bytes < pl.hi + 64) {   // the device side of the staging area follows its size (hipMalloc is cheap)
+        if (E.d_comp) HIP_TRY(c, hipStreamSynchronize(s->st_up));
+        (void)hipFree(E.d_comp);
+        E.d_comp = nullptr;
+        E.d_comp_bytes = 0;
+        const size_t want = std::max(pl.hi + pl.hi / 4 + 4096, s->h_img_bytes) + 64;
+        if (dmalloc(&E.d_comp, want) != hipSuccess) {
+            (void)hipGetLastError();
+            return refuse(c->err, FFS_ERR_NOMEM, "allocation of the device buffer for compressed chunks failed");
+        }
+        E.d_comp_bytes = want;
+    }
+    if (pl.in_place) {
+        std::vector<std::pair<size_t, size_t>> ranges;   // (each copy costs ~10 us of the caller's time)
+        copy_ranges(b.base.data(), chunk_bytes, n, ranges);
+        for (const auto& [begin, end] : ranges) HIP_TRY(c, hipMemcpyAsync(E.d_comp + begin, s->h_img + begin, end - begin, hipMemcpyHostToDevice, s->st_up));
+    } else {
+        HIP_TRY(c, hipMemcpyAsync(E.d_comp + pl.lo, s->h_img + pl.lo, pl.hi - pl.lo, hipMemcpyHostToDevice, s->st_up));
+    }
+    // "this batch's chunks are on the device", recorded HERE: the upload stream is shared by the context's streams, and an event
+    // recorded later (by the helper thread, after the block index) would also wait for every other batch's chunks queued meanwhile
+    HIP_TRY(c, hipEventRecord(s->ev[6], s->st_up));
+    b.sizes.assign(chunk_bytes, chunk_bytes + n);
+    if (!byte_offset) return FFS_OK;
+    const int rc = prepare_byte_offset(s, b);
+    if (rc != FFS_OK) (void)hipStreamSynchronize(s->st_up);   // (the chunks' copy reads the staging buffer the caller gets back)
+    return rc;
+}
+
+// bitshuffle-LZ4 (may run on the stream's helper thread while the chunks cross PCIe): indexes the blocks -- a pointer chase of ~2 ms for 32
+// Eiger frames, on up to four threads -- and enqueues the table's copy.  Errors go to `err`, not to the context (another thread may own
+// that string).
+static int index_blocks(ffs_stream* s, const EncodedBatch& b, hipStream_t st, std::string& err) {
+    EncodedState& E = s->enc;
+    const uint32_t n = (uint32_t)b.base.size(), nb = E.blocking.blocks;
+    const size_t tail = (size_t)E.blocking.tail_elems * s->ctx->pixel_bytes;
+    std::vector<size_t> pos(n, 12);
+    std::atomic<bool> ok{true};
+    static const bool trace = std::getenv("FFS_TRACE_SUBMIT") != nullptr;
+    const auto t0 = std::chrono::steady_clock::now();
+    auto walk = [&](uint32_t f0, uint32_t f1) {
+        if (!walk_block_chains(s->h_img, b.base.data(), b.sizes.data(), pos.data(), f0, f1, nb, tail, E.h_tab)) ok = false;
+    };
+    const uint32_t n_thr = (uint64_t)n * nb >= 32768 ? std::min<uint32_t>(4, n) : 1;
+    std::vector<std::thread> th;
+    for (uint32_t t = 1; t < n_thr; ++t) th.emplace_back(walk, n * t / n_thr, n * (t + 1) / n_thr);
+    walk(0, n / n_thr);
+    for (auto& t : th) t.join();
+    if (trace)
+        std::fprintf(stderr, "[ffs] indexed %u blocks in %.3f ms (%u threads)\n", n * nb,
+                     std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(), n_thr);
+    if (!ok) return refuse(err, FFS_ERR_INVALID, "ffs_submit_compressed: block lengths run past the end of a chunk");
+    // (the table goes up in the stream the decode kernel runs in: half a megabyte that must not queue behind other batches' chunks)
+    const hipError_t e = hipMemcpyAsync(E.d_tab, E.h_tab, (size_t)n * (nb + 1) * sizeof(BlockEntry), hipMemcpyHostToDevice, st);
+    return e == hipSuccess ? FFS_OK : refuse(err, FFS_ERR_DEVICE, std::string("hipMemcpyAsync(block table): ") + hipGetErrorString(e));
+}
+
+// Puts a prepared batch's decode into `st`: the table its kernels read (with_table: the block index or the frame table, copied in `st`) and
+// the kernels (with_decode: one launch, byte-offset: summarise, compose, emit).  after: an event `st` waits for ahead of the kernels, or
+// null -- the block table does not wait for it, it is indexed from the host's copy while the chunks still travel; done: an event recorded
+// in `st` behind the kernels, or null.  Errors go to `err`.
+static int launch(ffs_stream* s, const EncodedBatch& b, hipStream_t st, bool with_table, bool with_decode, hipEvent_t after, hipEvent_t done, std::string& err) {
+    ffs_ctx* c = s->ctx;
+    EncodedState& E = s->enc;
+    const Layout& L = c->L;
+    const bool byte_offset = b.codec == FFS_CODEC_BYTE_OFFSET;
+    const uint32_t n = (uint32_t)b.base.size();
+    if (with_table && !byte_offset) FFS_TRY(index_blocks(s, b, st, err));
+    if (with_table) (void)hipGetLastError();
+    hipError_t e = after ? hipStreamWaitEvent(st, after, 0) : hipSuccess;
+    if (e == hipSuccess && with_table && byte_offset) e = hipMemcpyAsync(E.d_bo_frames, E.h_bo_frames, (size_t)n * sizeof(BoFrame), hipMemcpyHostToDevice, st);
+    if (e == hipSuccess && with_decode && byte_offset) {
+        const BoArgs a{.comp = E.d_comp, .frames = E.d_bo_frames, .lane_pre = E.d_bo_lane, .tile_map = E.d_bo_map, .tile_state = E.d_bo_state,
+                       .image = s->d_img, .frame_stride = L.frame_stride, .pitch = L.pitch, .W = (uint32_t)L.W, .H = (uint32_t)L.H, .error = s->d_overflow};
+        const dim3 grid(b.bo_max_tiles, n);
+        hipLaunchKernelGGL(k_bo_summarise, grid, dim3(64), 0, st, a);
+        hipLaunchKernelGGL(k_bo_compose, dim3(n), dim3(64), 0, st, a);
+        if (c->pixel_bytes == 2) hipLaunchKernelGGL(k_bo_emit<uint16_t>, grid, dim3(64), 0, st, a);
+        else hipLaunchKernelGGL(k_bo_emit<uint32_t>, grid, dim3(64), 0, st, a);
+    } else if (e == hipSuccess && with_decode) {
+        const BshufBlocking& k = E.blocking;
+        const DecodeArgs da{.comp = E.d_comp, .table = reinterpret_cast<const uint2*>(E.d_tab), .image = s->d_img, .frame_stride = L.frame_stride,
+                            .pitch = L.pitch, .W = L.W, .H = L.H, .elem_bytes = c->pixel_bytes, .blocks_per_frame = k.blocks, .block_elems = k.block_elems,
+                            .last_block_elems = k.last_elems, .tail_elems = k.tail_elems, .error = s->d_overflow};
+        const dim3 grid(k.blocks + 1, n);
+        if (c->pixel_bytes == 2) hipLaunchKernelGGL(k_bshuf_lz4_decode<2>, grid, dim3(64), 0, st, da);
+        else hipLaunchKernelGGL(k_bshuf_lz4_decode<4>, grid, dim3(64), 0, st, da);
+    }
+    if (e == hipSuccess && with_decode) e = hipGetLastError();
+    if (e == hipSuccess && done) e = hipEventRecord(done, st);
+    return e == hipSuccess ? FFS_OK : refuse(err, FFS_ERR_DEVICE, std::string("decode launch: ") + hipGetErrorString(e));
+}
+
+static bool codec_known(ffs_ctx* c, int codec, const char* who) {
+    if (codec == FFS_CODEC_BSLZ4 || codec == FFS_CODEC_BYTE_OFFSET) return true;
+    c->err = std::string(who) + ": unknown codec " + std::to_string(codec);
+    return false;
+}
+
+static int ffs_submit_encoded_impl(ffs_stream* s, int codec, const void* const* chunks, const size_t* chunk_bytes, uint32_t n_frames, int64_t first_frame_id) {
+    if (!s || !chunks || !chunk_bytes) return FFS_ERR_INVALID;
+    ffs_ctx* c = s->ctx;
+    if (s->busy) return refuse(c->err, FFS_ERR_INVALID, "stream already has a batch in flight: call ffs_wait() first");
+    if (n_frames == 0 || n_frames > s->max_batch) return refuse(c->err, FFS_ERR_INVALID, "n_frames must be in 1..max_batch");
+    if (!codec_known(c, codec, "ffs_submit_encoded")) return FFS_ERR_INVALID;
+    HIP_TRY(c, hipSetDevice(c->device));
+    s->radial_todo = true;
+    s->stats_todo = true;
+    s->dev_input = false;
+    HIP_TRY(c, hipEventRecord(s->ev[0], s->st_up));
+    EncodedBatch b;
+    FFS_TRY(prepare(s, codec, chunks, chunk_bytes, n_frames, b));
+    // The rest -- block index, table copy, decode kernel and the hot path's launches -- is enqueued by a
+    // helper thread, so that the caller gets its thread back while the index is built; ffs_wait joins it.
+    s->first_id = first_frame_id;
+    s->reruns = 0;
+    // (s->n_frames stays the PREVIOUS batch's until enqueue_batch has planned this one: plan_batch reads that batch's counts with it)
+    mark_busy(s);
+    s->job_rc = FFS_OK;
+    s->job_err.clear();
+    const ParamSnapshot snap = snapshot_of(c);
+    s->job = std::thread([s, c, snap, n_frames, b = std::move(b)]() {
+        if (hipSetDevice(c->device) != hipSuccess) {
+            s->job_rc = refuse(s->job_err, FFS_ERR_DEVICE, "hipSetDevice failed on the stream's helper thread");
+            return;
+        }
+        // the decode kernel runs with the dense kernels (in their order), behind the copies of its input
+        hipStream_t dst = c->tune.decode_in_dense_stream ? s->st : s->st_up;
+        int r = launch(s, b, dst, true, true, dst != s->st_up ? s->ev[6] : nullptr, s->ev[1], s->job_err);
+        if (r == FFS_OK) {
+            r = enqueue_batch(s, s->d_img, c->L.pitch, c->L.frame_stride, n_frames, &snap);
+            if (r != FFS_OK) s->job_err = c->err;
+        }
+        s->job_rc = r;
+        if (r == FFS_OK) ahead_register(s);
+    });
+    return FFS_OK;
+}
+
+extern "C" int ffs_decode_only_encoded(ffs_stream* s, int codec, const void* const* chunks, const size_t* chunk_bytes, uint32_t n_frames,
+                                       uint32_t iters, float* ms_decode, void* host_out) {
+    if (!s || !chunks || !chunk_bytes || iters == 0) return FFS_ERR_INVALID;
+    ffs_ctx* c = s->ctx;
+    if (s->busy || n_frames == 0 || n_frames > s->max_batch) return refuse(c->err, FFS_ERR_INVALID, "ffs_decode_only: stream busy or n_frames out of range");
+    if (!codec_known(c, codec, "ffs_decode_only_encoded")) return FFS_ERR_INVALID;
+    const Layout& L = c->L;
+    HIP_TRY(c, hipSetDevice(c->device));
+    s->waited_ok = false;   // (the decoded frames replace the last batch's in the stream's image buffer: ffs_stream_spot_backgrounds has nothing to read)
+    EncodedBatch b;
+    std::string err;
+    int rc = prepare(s, codec, chunks, chunk_bytes, n_frames, b);
+    if (rc == FFS_OK && (rc = launch(s, b, s->st_up, true, false, nullptr, nullptr, err)) != FFS_OK) c->err = err;
+    if (rc != FFS_OK) {
+        (void)hipStreamSynchronize(s->st_up);
+        return rc;
+    }
+    HIP_TRY(c, hipEventRecord(s->ev[0], s->st_up));
+    for (uint32_t i = 0; i < iters; ++i)
+        if ((rc = launch(s, b, s->st_up, false, true, nullptr, nullptr, err)) != FFS_OK) return refuse(c->err, rc, err);
+    HIP_TRY(c, hipEventRecord(s->ev[1], s->st_up));
+    uint32_t flag = 0;
+    HIP_TRY(c, hipMemcpyAsync(&flag, s->d_overflow, 4, hipMemcpyDeviceToHost, s->st_up));
+    HIP_TRY(c, hipStreamSynchronize(s->st_up));
+    float ms = 0;
+    HIP_TRY(c, hipEventElapsedTime(&ms, s->ev[0], s->ev[1]));
+    if (ms_decode) *ms_decode = ms / iters;
+    if (host_out) {
+        const size_t row = (size_t)L.W * c->pixel_bytes;
+        HIP_TRY(c, hipMemcpy2D(host_out, row, s->d_img, L.pitch, row, (size_t)L.H * n_frames, hipMemcpyDeviceToHost));
+    }
+    if (const char* text = encoded_corruption(flag)) {
+        HIP_TRY(c, hipMemset(s->d_overflow, 0, 4));
+        return refuse(c->err, FFS_ERR_INVALID, text);
+    }
+    return FFS_OK;
+}
+extern "C" int ffs_decode_only(ffs_stream* s, const void* const* chunks, const size_t* chunk_bytes, uint32_t n_frames, uint32_t iters, float* ms_decode, void* host_out) {
+    return ffs_decode_only_encoded(s, FFS_CODEC_BSLZ4, chunks, chunk_bytes, n_frames, iters, ms_decode, host_out);
+}
+
+extern "C" int ffs_submit_compressed(ffs_stream* s, const void* const* chunks, const size_t* chunk_bytes, uint32_t n_frames, int64_t first_frame_id) {
+    if (!s || !stream_handle_ok(s)) return FFS_ERR_INVALID;
+    return guarded(s->ctx, [&] { return ffs_submit_encoded_impl(s, FFS_CODEC_BSLZ4, chunks, chunk_bytes, n_frames, first_frame_id); });
+}
+extern "C" int ffs_submit_encoded(ffs_stream* s, int codec, const void* const* chunks, const size_t* chunk_bytes, uint32_t n_frames, int64_t first_frame_id) {
+    if (!s || !stream_handle_ok(s)) return FFS_ERR_INVALID;
+    return guarded(s->ctx, [&] { return ffs_submit_encoded_impl(s, codec, chunks, chunk_bytes, n_frames, first_frame_id); });
+}

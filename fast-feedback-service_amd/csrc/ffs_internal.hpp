@@ -3,8 +3,10 @@
 // live in kernels_*.hpp, each included by exactly one unit:
 //   ffs_context.hip  contexts, masks (kernels_mask.hpp), tuning, streams
 //   ffs_submit.hip   one batch (enqueue_batch: plan_batch decides its path once, a BatchPlan with the launch geometry and the threshold route; then the resets,
-//                    the threshold stage and the sparse stage are launched from that plan), submit entry points, compressed input
-//                    (kernels_stream / threshold / extended / window / ccl / chain / band / decode / byteoffset)
+//                    the threshold stage and the sparse stage are launched from that plan), ffs_submit and ffs_submit_device
+//                    (kernels_stream / threshold / extended / window / ccl / chain / band)
+//   ffs_encoded.hip  encoded input from entry point to teardown: bitshuffle-LZ4 and CBF byte-offset chunks are staged, decoded on the device
+//                    (kernels_decode / byteoffset) and handed to enqueue_batch; acts on the decisions of encoded_plan.hpp
 //   ffs_products.hip the per-frame products, each from its setter to its accessor: the radial profile, the radial-profile threshold, the per-pixel
 //                    statistics (kernels_radial / radthr / pixstats); ffs_submit.hip calls their launches at their places in a batch
 //   ffs_wait.hip     ffs_wait: overflow re-runs (rerun_batch: the same batch again with a Rerun override), result assembly,
@@ -21,6 +23,8 @@
 //   spot_background_model.hpp  the decisions of the per-spot background: quartile positions, status order, fence (tests/spot_background_check.cc)
 //   radial_threshold_model.hpp the decisions of the radial-profile threshold (kernels_radthr.hpp, included by ffs_products.hip): status order and the
 //                        cutoff's two separately rounded operations (tests/radial_threshold_check.cc)
+//   encoded_plan.hpp     the decisions about a batch of encoded frames: bitshuffle's blocking, the chunk checks, where the chunks lie in the
+//                        staging buffer and which ranges of it are copied, the block table, the byte-offset frame table (tests/encoded_plan_check.cc)
 //   radial_blur_model.hpp  the blur ahead of that threshold (ffs_ctx_set_radial_blur): weights, tap rule, v = S / Wn (tests/radial_blur_check.cc)
 // No exception leaves the library (guarded()).
 #pragma once
@@ -47,6 +51,7 @@
 
 #include "ffs_hip.h"
 #include "ffs_device.h"
+#include "encoded_plan.hpp"
 #include "radial_threshold_model.hpp"
 #include "threshold_route.hpp"
 #include "tuning.hpp"
@@ -214,6 +219,21 @@ struct ffs_ctx {
 
 struct OverflowFrame;
 
+// What a stream keeps for encoded input (ffs_encoded.hip), all allocated on first use and freed by encoded_free.  d_comp: the device side of
+// the staging area, d_comp_bytes long, regrown with the staged bytes.  bitshuffle-LZ4: the frame's blocking and the per-block tables
+// (device and pinned host, max_batch frames).  CBF byte-offset: the frame table (device and pinned host, max_batch frames) and the three
+// summary tables, which hold bo_tiles_cap tiles and follow the staged bytes as d_comp does.
+struct EncodedState {
+    uint8_t* d_comp = nullptr;
+    size_t d_comp_bytes = 0;
+    BshufBlocking blocking;
+    BlockEntry *d_tab = nullptr, *h_tab = nullptr;
+    BoFrame *d_bo_frames = nullptr, *h_bo_frames = nullptr;
+    uint2 *d_bo_lane = nullptr, *d_bo_map = nullptr;
+    uint4* d_bo_state = nullptr;
+    size_t bo_tiles_cap = 0;
+};
+
 constexpr uint32_t kBrightCap = 1u << 20;  // entries of the bright-window list per batch (8 MB)
 
 struct ffs_stream {
@@ -268,15 +288,7 @@ struct ffs_stream {
     bool dplane2_clean = false;                        // the first-pass plane the NEXT batch takes is zero
     bool eplane2_clean = false;                        // ... and so is the signal-region plane behind it
     bool ext_e_clean = false;                          // this batch's signal-region plane is zero (make_threshold_args passes it on)
-    uint8_t* d_comp = nullptr;                         // compressed chunks (allocated on first use)
-    uint2 *d_tab = nullptr, *h_tab = nullptr;          // per-block (offset, length) tables
-    uint32_t dec_blocks = 0, dec_last = 0, dec_tail = 0, dec_block_elems = 0;
-    // CBF byte-offset decode (kernels_byteoffset.hpp), allocated on the codec's first use: the frame table (device and pinned host,
-    // a BoFrame per frame) and the three summary tables, which hold bo_tiles_cap tiles and follow the staged bytes as d_comp does
-    uint4 *d_bo_frames = nullptr, *h_bo_frames = nullptr;
-    uint2 *d_bo_lane = nullptr, *d_bo_map = nullptr;
-    uint4* d_bo_state = nullptr;
-    size_t bo_tiles_cap = 0;
+    EncodedState enc;                                  // encoded input (ffs_encoded.hip)
     // Without direct records: copied back speculatively with the counts (one wait instead of two): room for the most
     // records per frame seen so far on this stream, +25 %; ffs_wait fetches the rest if a batch exceeds it.
     uint32_t spec_recs_per_frame = 256;
@@ -295,7 +307,6 @@ struct ffs_stream {
     uint8_t* h_img = nullptr;      // pinned staging: allocated on first use (ensure_host_staging), sized by what is asked for
     size_t h_img_bytes = 0;
     PinnedBuf h_img_buf;           // ... and how it was obtained
-    size_t d_comp_bytes = 0;
     uint32_t* h_counts = nullptr;  // the counter block (layout: ffs_device.h, counts_*_at; counts_host_words(max_batch) words)
     ReflOut* h_recs = nullptr;
     uint32_t* d_occ = nullptr;     // [max_batch][occ_frame_words] occupancy of the strong plane (one bit per 16-byte segment)
@@ -562,6 +573,9 @@ int pixstats_launch(ffs_ctx* c, const void* d_img, size_t pitch, size_t fstride,
                     hipEvent_t stop);
 int launch_pixel_stats(ffs_stream* s, uint32_t n);
 int join_pixel_stats(ffs_stream* s);
+// ffs_encoded.hip
+const char* encoded_corruption(uint32_t overflow);   // the text for a status word in which a decode kernel flagged a corrupt chunk, else null
+void encoded_free(ffs_stream* s);
 // ffs_wait.hip
 int ffs_wait_impl(ffs_stream* s, const ffs_frame_result** results, uint32_t* n_results);
 void ahead_register(ffs_stream* s);   // the batch just enqueued may be assembled ahead of its ffs_wait

@@ -1,6 +1,7 @@
 // ffs_submit.hip -- everything that puts a batch on the device: the threshold stage's arguments (their launch geometry comes from
 // launch_geometry.hpp), the launches of the threshold stage and of the sparse stage (compaction -> connected components -> records),
-// the submit entry points and compressed input.  All kernels of the hot path are included here and nowhere else (see ffs_internal.hpp).
+// ffs_submit and ffs_submit_device (encoded input: ffs_encoded.hip).  All kernels of the hot path are included here and nowhere else (see
+// ffs_internal.hpp).
 //
 // Reference: the per-frame section of spotfinder/spotfinder.cc:751-1008 (H2D, kernel launch wrapper
 // spotfinder/spotfinder.cu:148-189, D2H of the mask, host connected components).
@@ -11,8 +12,6 @@
 #include "kernels_ccl.hpp"
 #include "kernels_chain.hpp"
 #include "kernels_band.hpp"
-#include "kernels_decode.hpp"
-#include "kernels_byteoffset.hpp"
 #include "kernels_window.hpp"
 
 bool chain_prepare_device() {   // more than 64 KB of dynamic LDS has to be asked for, per device
@@ -988,431 +987,4 @@ extern "C" int ffs_submit(ffs_stream* s, const void* host_pixels, uint32_t n_fra
     const int rc = enqueue_batch(s, s->d_img, L.pitch, L.frame_stride, n_frames);
     if (rc == FFS_OK) ahead_register(s);
     return rc;
-}
-
-
-// ---- compressed input -------------------------------------------------------------------------------
-
-static int ensure_decode_buffers(ffs_stream* s) {
-    ffs_ctx* c = s->ctx;
-    if (s->d_tab) return FFS_OK;
-    const size_t es = c->pixel_bytes, nelem = (size_t)c->L.W * c->L.H;
-    // bitshuffle's blocking (bshuf_default_block_size, and the loop of bshuf_blocked_wrap_fun)
-    const size_t block = (size_t)kDecBlockBytes / es;
-    const size_t n_full = nelem / block, rem = nelem - n_full * block;
-    s->dec_block_elems = (uint32_t)block;
-    s->dec_blocks = (uint32_t)(n_full + (rem >= 8 ? 1 : 0));
-    s->dec_last = (uint32_t)(rem >= 8 ? rem / 8 * 8 : block);
-    s->dec_tail = (uint32_t)(rem % 8);
-    const size_t tab_bytes = (size_t)s->max_batch * (s->dec_blocks + 1) * sizeof(uint2);
-    if (dmalloc(&s->d_tab, tab_bytes) != hipSuccess
-        || hipHostMalloc(reinterpret_cast<void**>(&s->h_tab), tab_bytes, hipHostMallocDefault) != hipSuccess) {
-        (void)hipGetLastError();
-        c->err = "allocation of the compressed-chunk buffers failed";
-        return FFS_ERR_NOMEM;
-    }
-    return FFS_OK;
-}
-
-static inline uint32_t be32(const uint8_t* p) {
-    return ((uint32_t)p[0] << 24) | ((uint32_t)p[1] << 16) | ((uint32_t)p[2] << 8) | p[3];
-}
-
-// Step 1 (caller's thread): validates the headers, places the chunks in the pinned staging buffer
-// (unless they already are there) and starts their copy to the device.  Fills base[] = offset of every
-// chunk in the staging / device buffer.
-static int stage_chunks(ffs_stream* s, int codec, const void* const* chunks, const size_t* chunk_bytes, uint32_t n,
-                        std::vector<size_t>& base) {
-    ffs_ctx* c = s->ctx;
-    const Layout& L = c->L;
-    int rc = codec == FFS_CODEC_BYTE_OFFSET ? FFS_OK : ensure_decode_buffers(s);
-    if (rc != FFS_OK) return rc;
-    const size_t es = c->pixel_bytes, raw_bytes = (size_t)L.W * L.H * es;
-    uint32_t in_place = 0;
-    for (uint32_t f = 0; f < n; ++f) {
-        const uint8_t* p = static_cast<const uint8_t*>(chunks[f]);
-        if (codec == FFS_CODEC_BYTE_OFFSET) {   // (no header; every element takes at least one byte)
-            if (!p || chunk_bytes[f] < (size_t)L.W * L.H) {
-                c->err = "ffs_submit_encoded: a byte-offset chunk of " + std::to_string(p ? chunk_bytes[f] : 0) + " bytes cannot hold a frame of "
-                         + std::to_string((size_t)L.W * L.H) + " pixels";
-                return FFS_ERR_INVALID;
-            }
-        } else {
-            if (!p || chunk_bytes[f] < 12) {
-                c->err = "ffs_submit_compressed: a chunk is shorter than its 12-byte header";
-                return FFS_ERR_INVALID;
-            }
-            uint64_t total = 0;
-            for (int i = 0; i < 8; ++i) total = (total << 8) | p[i];
-            if (total != raw_bytes) {
-                c->err = "ffs_submit_compressed: chunk header says " + std::to_string(total) + " bytes, the context's frames have "
-                         + std::to_string(raw_bytes);
-                return FFS_ERR_INVALID;
-            }
-        }
-        if (p >= s->h_img && p + chunk_bytes[f] <= s->h_img + s->h_img_bytes) ++in_place;
-    }
-    if (in_place != 0 && in_place != n) {
-        c->err = "ffs_submit_compressed: either all chunks lie in the stream's host buffer or none";
-        return FFS_ERR_INVALID;
-    }
-    base.assign(n, 0);
-    size_t lo = 0, hi = 0;
-    if (in_place) {
-        lo = SIZE_MAX;
-        for (uint32_t f = 0; f < n; ++f) {
-            base[f] = (size_t)(static_cast<const uint8_t*>(chunks[f]) - s->h_img);
-            lo = std::min(lo, base[f]);
-            hi = std::max(hi, base[f] + chunk_bytes[f]);
-        }
-        lo &= ~(size_t)15;
-    } else {
-        size_t need = 0;
-        for (uint32_t f = 0; f < n; ++f) need += (chunk_bytes[f] + 15) & ~(size_t)15;
-        rc = ensure_host_staging(s, need + need / 4 + 4096);   // (grows with headroom; kept from then on)
-        if (rc != FFS_OK) return rc;
-        size_t cur = 0;
-        for (uint32_t f = 0; f < n; ++f) {
-            std::memcpy(s->h_img + cur, chunks[f], chunk_bytes[f]);
-            base[f] = cur;
-            cur = (cur + chunk_bytes[f] + 15) & ~(size_t)15;
-        }
-        hi = cur;
-    }
-    if (hi > 0xFFFFFFF0ull) {
-        c->err = "ffs_submit_compressed: more than 4 GiB of chunks in one batch";
-        return FFS_ERR_INVALID;
-    }
-    if (s->d_comp_bytes < hi + 64) {   // the device side of the staging area follows its size (hipMalloc is cheap)
-        if (s->d_comp) {
-            HIP_TRY(c, hipStreamSynchronize(s->st_up));
-            (void)hipFree(s->d_comp);
-            s->d_comp = nullptr;
-        }
-        const size_t want = std::max(hi + hi / 4 + 4096, s->h_img_bytes) + 64;
-        if (dmalloc(&s->d_comp, want) != hipSuccess) {
-            (void)hipGetLastError();
-            s->d_comp_bytes = 0;
-            c->err = "allocation of the device buffer for compressed chunks failed";
-            return FFS_ERR_NOMEM;
-        }
-        s->d_comp_bytes = want;
-    }
-    if (in_place) {
-        // chunks placed by the caller (a driver's fixed slots leave gaps between them): only the bytes of the chunks cross PCIe --
-        // ranges closer than 512 KB travel as one copy (the gap costs what a copy of its own would), each copy costs ~10 us of the caller's time
-        std::vector<std::pair<size_t, size_t>> r(n);
-        for (uint32_t f = 0; f < n; ++f) r[f] = {base[f] & ~(size_t)15, base[f] + chunk_bytes[f]};
-        std::sort(r.begin(), r.end());
-        size_t a = r[0].first, b = r[0].second;
-        for (uint32_t f = 1; f <= n; ++f) {
-            if (f < n && r[f].first <= b + 524288) { b = std::max(b, r[f].second); continue; }
-            HIP_TRY(c, hipMemcpyAsync(s->d_comp + a, s->h_img + a, b - a, hipMemcpyHostToDevice, s->st_up));
-            if (f < n) { a = r[f].first; b = r[f].second; }
-        }
-    } else {
-        HIP_TRY(c, hipMemcpyAsync(s->d_comp + lo, s->h_img + lo, hi - lo, hipMemcpyHostToDevice, s->st_up));
-    }
-    // "this batch's chunks are on the device", recorded HERE: the upload stream is shared by the context's streams, and an event
-    // recorded later (by the helper thread, after the block index) would also wait for every other batch's chunks queued meanwhile
-    HIP_TRY(c, hipEventRecord(s->ev[6], s->st_up));
-    return FFS_OK;
-}
-
-// Step 2 (may run on the stream's helper thread while the chunks cross PCIe): indexes the blocks --
-// each frame is a chain of [4-byte length][payload], a pointer chase of ~2 ms for 32 Eiger frames;
-// the frames' chains are walked side by side so that their cache misses overlap -- and enqueues the
-// table copy.  Errors go to `err`, not to the context (another thread may own that string).
-static int index_blocks(ffs_stream* s, const std::vector<size_t>& base, const std::vector<size_t>& chunk_bytes,
-                        std::string& err, hipStream_t tab_stream) {
-    ffs_ctx* c = s->ctx;
-    const uint32_t n = (uint32_t)base.size();
-    const size_t es = c->pixel_bytes;
-    const uint32_t nb = s->dec_blocks, stride = nb + 1;
-    std::vector<size_t> pos(n, 12);
-    std::atomic<bool> ok{true};
-    static const bool trace = std::getenv("FFS_TRACE_SUBMIT") != nullptr;
-    const auto t0 = std::chrono::steady_clock::now();
-    auto walk = [&](uint32_t f0, uint32_t f1) {  // frames [f0, f1), chains interleaved
-        for (uint32_t b = 0; b < nb; ++b)
-            for (uint32_t f = f0; f < f1; ++f) {
-                if (pos[f] + 4 > chunk_bytes[f]) { ok = false; return; }
-                const uint32_t clen = be32(s->h_img + base[f] + pos[f]);
-                s->h_tab[(size_t)f * stride + b] = make_uint2((uint32_t)(base[f] + pos[f] + 4), clen);
-                pos[f] += 4 + (size_t)clen;
-            }
-        for (uint32_t f = f0; f < f1; ++f) {
-            const size_t tail = (size_t)s->dec_tail * es;
-            if (pos[f] + tail > chunk_bytes[f]) ok = false;
-            s->h_tab[(size_t)f * stride + nb] = make_uint2((uint32_t)(base[f] + pos[f]), (uint32_t)tail);
-        }
-    };
-    const uint32_t n_thr = (uint64_t)n * nb >= 32768 ? std::min<uint32_t>(4, n) : 1;
-    if (n_thr <= 1) {
-        walk(0, n);
-    } else {
-        std::vector<std::thread> th;
-        for (uint32_t t = 1; t < n_thr; ++t) th.emplace_back(walk, n * t / n_thr, n * (t + 1) / n_thr);
-        walk(0, n / n_thr);
-        for (auto& t : th) t.join();
-    }
-    if (trace)
-        std::fprintf(stderr, "[ffs] indexed %u blocks in %.3f ms (%u threads)\n", n * nb,
-                     std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(), n_thr);
-    if (!ok) {
-        err = "ffs_submit_compressed: block lengths run past the end of a chunk";
-        return FFS_ERR_INVALID;
-    }
-    // (the table goes up in the stream the decode kernel runs in: half a megabyte that must not queue behind other batches' chunks)
-    const hipError_t e = hipMemcpyAsync(s->d_tab, s->h_tab, (size_t)n * stride * sizeof(uint2), hipMemcpyHostToDevice, tab_stream);
-    if (e != hipSuccess) {
-        err = std::string("hipMemcpyAsync(block table): ") + hipGetErrorString(e);
-        return FFS_ERR_DEVICE;
-    }
-    return FFS_OK;
-}
-
-static void launch_decode(ffs_stream* s, uint32_t n, hipStream_t st) {
-    ffs_ctx* c = s->ctx;
-    DecodeArgs da{};
-    da.comp = s->d_comp;
-    da.table = s->d_tab;
-    da.image = s->d_img;
-    da.frame_stride = c->L.frame_stride;
-    da.pitch = c->L.pitch;
-    da.W = c->L.W;
-    da.H = c->L.H;
-    da.elem_bytes = c->pixel_bytes;
-    da.blocks_per_frame = s->dec_blocks;
-    da.block_elems = s->dec_block_elems;
-    da.last_block_elems = s->dec_last;
-    da.tail_elems = s->dec_tail;
-    da.error = s->d_overflow;
-    const dim3 grid(s->dec_blocks + 1, n);
-    if (c->pixel_bytes == 2) hipLaunchKernelGGL(k_bshuf_lz4_decode<2>, grid, dim3(64), 0, st, da);
-    else hipLaunchKernelGGL(k_bshuf_lz4_decode<4>, grid, dim3(64), 0, st, da);
-}
-
-// ---- CBF byte-offset chunks (kernels_byteoffset.hpp) ----
-// Step 1 of a byte-offset batch, on the caller's thread after stage_chunks: the frame table (where every chunk lies, how much of it is
-// parsed, where its tiles lie in the summary tables) and the tables themselves, allocated on the codec's first use on the stream and
-// regrown with the staged bytes.  max_tiles: the launches' grid.
-static int prepare_byte_offset(ffs_stream* s, const std::vector<size_t>& base, const size_t* chunk_bytes, uint32_t n, uint32_t& max_tiles) {
-    ffs_ctx* c = s->ctx;
-    if (!s->d_bo_frames) {
-        if (dmalloc(&s->d_bo_frames, (size_t)s->max_batch * sizeof(uint4)) != hipSuccess
-            || hipHostMalloc(reinterpret_cast<void**>(&s->h_bo_frames), (size_t)s->max_batch * sizeof(uint4), hipHostMallocDefault) != hipSuccess) {
-            (void)hipGetLastError();
-            c->err = "allocation of the byte-offset frame table failed";
-            return FFS_ERR_NOMEM;
-        }
-    }
-    static_assert(sizeof(BoFrame) == sizeof(uint4), "the frame table is allocated as uint4");
-    BoFrame* fr = reinterpret_cast<BoFrame*>(s->h_bo_frames);
-    const uint64_t most = 7ull * c->L.W * c->L.H;   // (seven bytes per element at the most: nothing behind that is ever parsed)
-    size_t tiles = 0;
-    max_tiles = 0;
-    for (uint32_t f = 0; f < n; ++f) {
-        fr[f].base = (uint32_t)base[f];
-        fr[f].end = (uint32_t)std::min<uint64_t>(chunk_bytes[f], most);
-        fr[f].tile0 = (uint32_t)tiles;
-        fr[f].total = 0;
-        tiles += bo_tiles(fr[f].end);
-        max_tiles = std::max(max_tiles, bo_tiles(fr[f].end));
-    }
-    if (tiles > s->bo_tiles_cap) {
-        // (the stream is idle, but its last decode may still read the tables on a decode-only path: they are freed behind both streams)
-        if (s->d_bo_lane) {
-            HIP_TRY(c, hipStreamSynchronize(s->st_up));
-            HIP_TRY(c, hipStreamSynchronize(s->st));
-        }
-        (void)hipFree(s->d_bo_lane); (void)hipFree(s->d_bo_map); (void)hipFree(s->d_bo_state);
-        s->d_bo_lane = nullptr; s->d_bo_map = nullptr; s->d_bo_state = nullptr;
-        s->bo_tiles_cap = 0;
-        const size_t want = tiles + tiles / 4 + 16;
-        if (dmalloc(&s->d_bo_lane, want * 7 * 64 * sizeof(uint2)) != hipSuccess || dmalloc(&s->d_bo_map, want * 7 * sizeof(uint2)) != hipSuccess
-            || dmalloc(&s->d_bo_state, want * sizeof(uint4)) != hipSuccess) {
-            (void)hipGetLastError();
-            c->err = "allocation of the byte-offset summary tables failed";
-            return FFS_ERR_NOMEM;
-        }
-        s->bo_tiles_cap = want;
-    }
-    return FFS_OK;
-}
-
-// The three launches of a byte-offset batch (summarise, compose, emit), behind the copy of the frame table, all in `st`.
-static hipError_t launch_byte_offset(ffs_stream* s, uint32_t n, uint32_t max_tiles, hipStream_t st, bool table = true) {
-    ffs_ctx* c = s->ctx;
-    if (table) {
-        const hipError_t e = hipMemcpyAsync(s->d_bo_frames, s->h_bo_frames, (size_t)n * sizeof(uint4), hipMemcpyHostToDevice, st);
-        if (e != hipSuccess) return e;
-    }
-    BoArgs a{};
-    a.comp = s->d_comp;
-    a.frames = reinterpret_cast<BoFrame*>(s->d_bo_frames);
-    a.lane_pre = s->d_bo_lane;
-    a.tile_map = s->d_bo_map;
-    a.tile_state = s->d_bo_state;
-    a.image = s->d_img;
-    a.frame_stride = c->L.frame_stride;
-    a.pitch = (uint32_t)c->L.pitch;
-    a.W = (uint32_t)c->L.W;
-    a.H = (uint32_t)c->L.H;
-    a.error = s->d_overflow;
-    const dim3 grid(max_tiles, n);
-    hipLaunchKernelGGL(k_bo_summarise, grid, dim3(64), 0, st, a);
-    hipLaunchKernelGGL(k_bo_compose, dim3(n), dim3(64), 0, st, a);
-    if (c->pixel_bytes == 2) hipLaunchKernelGGL(k_bo_emit<uint16_t>, grid, dim3(64), 0, st, a);
-    else hipLaunchKernelGGL(k_bo_emit<uint32_t>, grid, dim3(64), 0, st, a);
-    return hipGetLastError();
-}
-
-static bool codec_known(ffs_ctx* c, int codec, const char* who) {
-    if (codec == FFS_CODEC_BSLZ4 || codec == FFS_CODEC_BYTE_OFFSET) return true;
-    c->err = std::string(who) + ": unknown codec " + std::to_string(codec);
-    return false;
-}
-
-static int ffs_submit_encoded_impl(ffs_stream* s, int codec, const void* const* chunks, const size_t* chunk_bytes,
-                                   uint32_t n_frames, int64_t first_frame_id) {
-    if (!s || !chunks || !chunk_bytes) return FFS_ERR_INVALID;
-    ffs_ctx* c = s->ctx;
-    if (s->busy) {
-        c->err = "stream already has a batch in flight: call ffs_wait() first";
-        return FFS_ERR_INVALID;
-    }
-    if (n_frames == 0 || n_frames > s->max_batch) {
-        c->err = "n_frames must be in 1..max_batch";
-        return FFS_ERR_INVALID;
-    }
-    if (!codec_known(c, codec, "ffs_submit_encoded")) return FFS_ERR_INVALID;
-    HIP_TRY(c, hipSetDevice(c->device));
-    s->radial_todo = true;
-    s->stats_todo = true;
-    s->dev_input = false;
-    HIP_TRY(c, hipEventRecord(s->ev[0], s->st_up));
-    std::vector<size_t> base;
-    int rc = stage_chunks(s, codec, chunks, chunk_bytes, n_frames, base);
-    if (rc != FFS_OK) return rc;
-    uint32_t bo_max_tiles = 0;   // (byte-offset chunks need no index: the tables are sized here, the helper thread only launches)
-    if (codec == FFS_CODEC_BYTE_OFFSET) {
-        rc = prepare_byte_offset(s, base, chunk_bytes, n_frames, bo_max_tiles);
-        if (rc != FFS_OK) {
-            (void)hipStreamSynchronize(s->st_up);   // (the chunks' copy reads the staging buffer the caller gets back)
-            return rc;
-        }
-    }
-    // The rest -- block index, table copy, decode kernel and the hot path's launches -- is enqueued by a
-    // helper thread, so that the caller gets its thread back while the index is built; ffs_wait joins it.
-    s->first_id = first_frame_id;
-    s->reruns = 0;
-    // (s->n_frames stays the PREVIOUS batch's until enqueue_batch has planned this one: plan_batch reads that batch's counts with it)
-    mark_busy(s);
-    s->job_rc = FFS_OK;
-    s->job_err.clear();
-    const ParamSnapshot snap = snapshot_of(c);
-    std::vector<size_t> sizes(chunk_bytes, chunk_bytes + n_frames);
-    s->job = std::thread([s, c, snap, n_frames, codec, bo_max_tiles, base = std::move(base), sizes = std::move(sizes)]() {
-        if (hipSetDevice(c->device) != hipSuccess) {
-            s->job_rc = FFS_ERR_DEVICE;
-            s->job_err = "hipSetDevice failed on the stream's helper thread";
-            return;
-        }
-        // the decode kernel runs with the dense kernels (in their order), behind the copies of its input
-        hipStream_t dst = c->tune.decode_in_dense_stream ? s->st : s->st_up;
-        int r = codec == FFS_CODEC_BYTE_OFFSET ? FFS_OK : index_blocks(s, base, sizes, s->job_err, dst);
-        if (r == FFS_OK) {
-            (void)hipGetLastError();
-            hipError_t e = hipSuccess;
-            if (dst != s->st_up) e = hipStreamWaitEvent(dst, s->ev[6], 0);
-            if (codec == FFS_CODEC_BYTE_OFFSET) {
-                if (e == hipSuccess) e = launch_byte_offset(s, n_frames, bo_max_tiles, dst);
-            } else {
-                launch_decode(s, n_frames, dst);
-            }
-            if (e == hipSuccess) e = hipGetLastError();
-            if (e == hipSuccess) e = hipEventRecord(s->ev[1], dst);
-            if (e != hipSuccess) {
-                s->job_err = std::string("decode launch: ") + hipGetErrorString(e);
-                r = FFS_ERR_DEVICE;
-            }
-        }
-        if (r == FFS_OK) {
-            r = enqueue_batch(s, s->d_img, c->L.pitch, c->L.frame_stride, n_frames, &snap);
-            if (r != FFS_OK) s->job_err = c->err;
-        }
-        s->job_rc = r;
-        if (r == FFS_OK) ahead_register(s);
-    });
-    return FFS_OK;
-}
-
-extern "C" int ffs_decode_only_encoded(ffs_stream* s, int codec, const void* const* chunks, const size_t* chunk_bytes, uint32_t n_frames,
-                                       uint32_t iters, float* ms_decode, void* host_out) {
-    if (!s || !chunks || !chunk_bytes || iters == 0) return FFS_ERR_INVALID;
-    ffs_ctx* c = s->ctx;
-    if (s->busy || n_frames == 0 || n_frames > s->max_batch) {
-        c->err = "ffs_decode_only: stream busy or n_frames out of range";
-        return FFS_ERR_INVALID;
-    }
-    if (!codec_known(c, codec, "ffs_decode_only_encoded")) return FFS_ERR_INVALID;
-    const Layout& L = c->L;
-    HIP_TRY(c, hipSetDevice(c->device));
-    s->waited_ok = false;   // (the decoded frames replace the last batch's in the stream's image buffer: ffs_stream_spot_backgrounds has nothing to read)
-    std::vector<size_t> base;
-    int rc = stage_chunks(s, codec, chunks, chunk_bytes, n_frames, base);
-    uint32_t bo_max_tiles = 0;
-    if (rc == FFS_OK && codec == FFS_CODEC_BYTE_OFFSET) {
-        rc = prepare_byte_offset(s, base, chunk_bytes, n_frames, bo_max_tiles);
-        if (rc == FFS_OK) HIP_TRY(c, hipMemcpyAsync(s->d_bo_frames, s->h_bo_frames, (size_t)n_frames * sizeof(uint4), hipMemcpyHostToDevice, s->st_up));
-    } else if (rc == FFS_OK) {
-        std::string err;
-        rc = index_blocks(s, base, std::vector<size_t>(chunk_bytes, chunk_bytes + n_frames), err, s->st_up);
-        if (rc != FFS_OK) c->err = err;
-    }
-    if (rc != FFS_OK) {
-        (void)hipStreamSynchronize(s->st_up);
-        return rc;
-    }
-    (void)hipGetLastError();
-    HIP_TRY(c, hipEventRecord(s->ev[0], s->st_up));
-    for (uint32_t i = 0; i < iters; ++i) {
-        if (codec == FFS_CODEC_BYTE_OFFSET) HIP_TRY(c, launch_byte_offset(s, n_frames, bo_max_tiles, s->st_up, false));
-        else launch_decode(s, n_frames, s->st_up);
-    }
-    HIP_TRY(c, hipEventRecord(s->ev[1], s->st_up));
-    HIP_TRY(c, hipGetLastError());
-    uint32_t flag = 0;
-    HIP_TRY(c, hipMemcpyAsync(&flag, s->d_overflow, 4, hipMemcpyDeviceToHost, s->st_up));
-    HIP_TRY(c, hipStreamSynchronize(s->st_up));
-    float ms = 0;
-    HIP_TRY(c, hipEventElapsedTime(&ms, s->ev[0], s->ev[1]));
-    if (ms_decode) *ms_decode = ms / iters;
-    if (host_out) {
-        const size_t row = (size_t)L.W * c->pixel_bytes;
-        HIP_TRY(c, hipMemcpy2D(host_out, row, s->d_img, L.pitch, row, (size_t)L.H * n_frames, hipMemcpyDeviceToHost));
-    }
-    if (flag & (kOvfCorruptLz4 | kOvfCorruptByteOffset)) {
-        HIP_TRY(c, hipMemset(s->d_overflow, 0, 4));
-        c->err = (flag & kOvfCorruptLz4) ? "corrupt bitshuffle-LZ4 chunk: an LZ4 block did not decode to its block size"
-                                         : "corrupt byte-offset chunk: it holds fewer elements than the frame has pixels";
-        return FFS_ERR_INVALID;
-    }
-    return FFS_OK;
-}
-extern "C" int ffs_decode_only(ffs_stream* s, const void* const* chunks, const size_t* chunk_bytes, uint32_t n_frames,
-                               uint32_t iters, float* ms_decode, void* host_out) {
-    return ffs_decode_only_encoded(s, FFS_CODEC_BSLZ4, chunks, chunk_bytes, n_frames, iters, ms_decode, host_out);
-}
-
-extern "C" int ffs_submit_compressed(ffs_stream* s, const void* const* chunks, const size_t* chunk_bytes,
-                                     uint32_t n_frames, int64_t first_frame_id) {
-    if (!s || !stream_handle_ok(s)) return FFS_ERR_INVALID;
-    return guarded(s->ctx, [&] { return ffs_submit_encoded_impl(s, FFS_CODEC_BSLZ4, chunks, chunk_bytes, n_frames, first_frame_id); });
-}
-extern "C" int ffs_submit_encoded(ffs_stream* s, int codec, const void* const* chunks, const size_t* chunk_bytes,
-                                  uint32_t n_frames, int64_t first_frame_id) {
-    if (!s || !stream_handle_ok(s)) return FFS_ERR_INVALID;
-    return guarded(s->ctx, [&] { return ffs_submit_encoded_impl(s, codec, chunks, chunk_bytes, n_frames, first_frame_id); });
 }

@@ -322,12 +322,8 @@ struct Recovery {
     Rerun how;   // kRerunBatch: what the enqueue overrides
 };
 static Recovery decide_recovery(ffs_stream* s, uint32_t overflow) {
-    if (overflow & kOvfCorruptLz4) {
-        s->ctx->err = "corrupt bitshuffle-LZ4 chunk: an LZ4 block did not decode to its block size";
-        return {Recovery::kFail, {}};
-    }
-    if (overflow & kOvfCorruptByteOffset) {
-        s->ctx->err = "corrupt byte-offset chunk: it holds fewer elements than the frame has pixels";
+    if (const char* corrupt = encoded_corruption(overflow)) {
+        s->ctx->err = corrupt;
         return {Recovery::kFail, {}};
     }
     if (overflow & kOvfBrightList) {

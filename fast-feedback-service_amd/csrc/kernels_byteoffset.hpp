@@ -1,4 +1,4 @@
-// kernels_byteoffset.hpp (included by ffs_submit.hip) -- CBF byte-offset chunk decode on the GPU.
+// kernels_byteoffset.hpp (included by ffs_encoded.hip) -- CBF byte-offset chunk decode on the GPU.
 //
 // What the reference does: CBFRead::get_image decodes the binary section on the reading thread (cbfread.hpp:49-106,
 // decompress_byte_offset) and the raw frame crosses PCIe.  Here the section crosses PCIe as it lies in the file and is decoded
@@ -25,20 +25,12 @@
 // run past the parse bound min(chunk_bytes, 7 W H) emits nothing, and neither does anything behind it (it lies past the bound).
 #pragma once
 #include "ffs_device.h"
+#include "encoded_plan.hpp"   // kBoSeg, kBoTile, BoFrame, bo_tiles: shared with the host's planning
 
 namespace ffsamd {
 
-constexpr int kBoSeg = 64;                               // bytes per lane
-constexpr int kBoTile = 64 * kBoSeg;                     // bytes per wave
 constexpr int kBoRowWords = kBoSeg / 4 + 3;              // a lane's LDS row: its segment, 8 bytes of the next one, one word that spreads rows over the banks (19 is odd)
 constexpr int kBoStageWords = kBoTile / 4 + 2;           // dwords staged per tile: the tile and the 8 bytes behind it
-
-struct BoFrame {            // one per frame of the batch (host-written; k_bo_compose fills in `total`)
-    uint32_t base;          // the chunk's offset in `comp`
-    uint32_t end;           // parse bound: min(chunk_bytes, 7 W H)
-    uint32_t tile0;         // index of the chunk's first tile in the batch's tables
-    uint32_t total;         // elements the chunk holds (k_bo_compose)
-};
 
 struct BoArgs {
     const uint8_t* comp;    // all chunks of the batch (64 bytes of slack behind them)
@@ -52,8 +44,6 @@ struct BoArgs {
     uint32_t W, H;
     uint32_t* error;        // the stream's status word: kOvfCorruptByteOffset when a chunk holds fewer than W * H elements
 };
-
-__host__ __device__ inline uint32_t bo_tiles(uint32_t end) { return (end + (uint32_t)kBoTile - 1u) / (uint32_t)kBoTile; }
 
 // Stage tile `t` of a chunk in LDS, row per lane segment.  Dwords are loaded aligned and shifted by the chunk's misalignment; a dword
 // is loaded only if it starts before the parse bound (what is not loaded reads as zero; bytes at or past the bound are never

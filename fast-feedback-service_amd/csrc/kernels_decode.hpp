@@ -1,4 +1,4 @@
-// kernels_decode.hpp (included by ffs_submit.hip) -- bitshuffle-LZ4 chunk decode on the GPU.
+// kernels_decode.hpp (included by ffs_encoded.hip) -- bitshuffle-LZ4 chunk decode on the GPU.
 //
 // What the reference does: every worker thread decompresses its frame on the CPU,
 // bshuf_decompress_lz4(buffer + 12, host_image, W*H, sizeof(pixel_t), 0) (spotfinder.cc:823-842,
@@ -27,10 +27,9 @@
 // checked; a malformed block raises an error flag and leaves zeros.
 #pragma once
 #include "ffs_device.h"
+#include "encoded_plan.hpp"   // kDecBlockBytes: shared with the host's planning
 
 namespace ffsamd {
-
-constexpr int kDecBlockBytes = 8192;                 // bitshuffle target block size
 
 struct DecodeArgs {
     const uint8_t* comp;        // all chunks of the batch

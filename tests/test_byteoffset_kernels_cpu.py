@@ -12,11 +12,12 @@ HERE = os.path.join(ROOT, "tests", "byteoffset_cpu")
 
 
 def test_kernels_on_host_threads(tmp_path):
-    for src in (os.path.join(PKG, "csrc", "kernels_byteoffset.hpp"), os.path.join(HERE, "ffs_device.h"),
+    # (encoded_plan.hpp: the tile size, BoFrame and bo_tiles the kernels share with the host's planning; it includes the ABI's header)
+    for src in (os.path.join(PKG, "csrc", "kernels_byteoffset.hpp"), os.path.join(PKG, "csrc", "encoded_plan.hpp"), os.path.join(HERE, "ffs_device.h"),
                 os.path.join(HERE, "byteoffset_kernels_check.cc")):
         shutil.copy(src, tmp_path)
     exe = tmp_path / "check"
-    subprocess.run(["g++", "-std=c++20", "-O1", "-fwrapv", "-pthread", "-I", os.path.join(PKG, "host"),
+    subprocess.run(["g++", "-std=c++20", "-O1", "-fwrapv", "-pthread", "-I", os.path.join(PKG, "host"), "-I", os.path.join(ROOT, "include"),
                     str(tmp_path / "byteoffset_kernels_check.cc"), "-o", str(exe)], check=True)
     p = subprocess.run([str(exe)], capture_output=True, text=True, timeout=300)
     assert p.returncode == 0 and "EMU OK" in p.stdout and "FAIL" not in p.stdout, p.stdout[-2000:] + p.stderr[-2000:]
