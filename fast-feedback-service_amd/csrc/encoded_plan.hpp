@@ -1,4 +1,4 @@
-// encoded_plan.hpp -- the host's decisions about a batch of encoded frames (bitshuffle-LZ4 and CBF byte-offset chunks) as plain
+// encoded_plan.hpp -- the host's decisions about a batch of encoded frames (bitshuffle-LZ4, CBF byte-offset and raw Jungfrau chunks) as plain
 // arithmetic: no HIP header, no allocation of device or pinned memory, no copy.  ffs_encoded.hip acts on them; the decode kernels
 // (kernels_decode.hpp, kernels_byteoffset.hpp) share the constants and BoFrame; tests/encoded_plan_check.cc compiles the same text.
 #pragma once
@@ -33,9 +33,21 @@ inline BshufBlocking bshuf_blocking(size_t nelem, size_t elem_bytes) {
 
 // ---- one chunk against the context's frames ------------------------------------------------------------------------------------
 // true: the chunk may hold a frame of W x H pixels of elem_bytes.  false: `why` has the refusal.  bitshuffle-LZ4: a 12-byte header whose
-// first 8 bytes are the frame's raw size, big-endian; byte-offset: no header, every element takes at least one byte.
+// first 8 bytes are the frame's raw size, big-endian; byte-offset: no header, every element takes at least one byte; raw Jungfrau words:
+// exactly W * H 16-bit words, into 32-bit pixels only.
 inline bool chunk_ok(int codec, const void* chunk, size_t bytes, size_t W, size_t H, size_t elem_bytes, std::string& why) {
     const uint8_t* p = static_cast<const uint8_t*>(chunk);
+    if (codec == FFS_CODEC_JUNGFRAU_RAW) {
+        if (elem_bytes != 4) {
+            why = "ffs_submit_encoded: raw Jungfrau words convert to 32-bit photon counts: the context must have pixel_bytes 4, this one has "
+                  + std::to_string(elem_bytes);
+            return false;
+        }
+        if (p && bytes == W * H * 2) return true;
+        why = "ffs_submit_encoded: a raw Jungfrau chunk of " + std::to_string(p ? bytes : 0) + " bytes is not a frame of " + std::to_string(W * H)
+              + " 16-bit words (" + std::to_string(W * H * 2) + " bytes)";
+        return false;
+    }
     if (codec == FFS_CODEC_BYTE_OFFSET) {
         if (p && bytes >= W * H) return true;
         why = "ffs_submit_encoded: a byte-offset chunk of " + std::to_string(p ? bytes : 0) + " bytes cannot hold a frame of " + std::to_string(W * H)
@@ -93,6 +105,14 @@ inline bool place_chunks(const void* const* chunks, const size_t* bytes, uint32_
         pl.staging = pl.hi + pl.hi / 4 + 4096;
     }
     return true;
+}
+
+// Raw Jungfrau words are loaded 16 bytes at a time from where the chunk lies: the staged bases are multiples of 16 by construction, a chunk
+// the caller placed in the buffer must be.  The index of the first chunk that is not, or n.
+inline uint32_t first_unaligned_base(const size_t* base, uint32_t n) {
+    for (uint32_t f = 0; f < n; ++f)
+        if (base[f] % 16 != 0) return f;
+    return n;
 }
 
 // Chunks placed by the caller (a driver's fixed slots leave gaps between them): only the bytes of the chunks cross PCIe.  r: n entries

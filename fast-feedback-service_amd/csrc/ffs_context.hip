@@ -3,6 +3,7 @@
 #include <sys/mman.h>
 
 #include "ffs_internal.hpp"
+#include "jungfrau_model.hpp"   // (the setter's ranges)
 #include "kernels_mask.hpp"
 
 static_assert(sizeof(ReflOut) == sizeof(ffs_reflection), "record layout");
@@ -310,6 +311,7 @@ static void ctx_destroy_internal(ffs_ctx* c) {
     }
     if (c->d_maskbits) (void)hipFree(c->d_maskbits);
     if (c->d_gain_map) (void)hipFree(c->d_gain_map);
+    if (c->d_jf_cal) (void)hipFree(c->d_jf_cal);
     if (c->d_radial_map) (void)hipFree(c->d_radial_map);
     if (c->stats_st) {   // (the streams are closed: nothing new comes, what is there is let finish)
         (void)hipStreamSynchronize(c->stats_st);
@@ -538,6 +540,62 @@ static int ffs_ctx_set_gain_map_impl(ffs_ctx* c, const float* host_gain) {
 extern "C" int ffs_ctx_set_gain_map(ffs_ctx* c, const float* host_gain) {
     if (!c) return FFS_ERR_INVALID;
     return guarded(c, [&] { return ffs_ctx_set_gain_map_impl(c, host_gain); });
+}
+
+// The Jungfrau calibration.  Everything is checked before anything changes; the device copy -- six dense planes, as they
+// come -- is written only while no batch of the context is in flight, so a batch's conversion reads the calibration it was submitted with.
+static int ffs_ctx_set_jungfrau_calibration_impl(ffs_ctx* c, const ffs_jungfrau_calibration* cal) {
+    if (c->inflight.load() > 0) {
+        c->err = "ffs_ctx_set_jungfrau_calibration: a batch of this context is in flight (ffs_wait for it first): a batch keeps the calibration it was "
+                 "submitted with";
+        return FFS_ERR_INVALID;
+    }
+    if (!cal) {
+        c->has_jf_cal = false;
+        return FFS_OK;
+    }
+    if (c->pixel_bytes != 4) {
+        c->err = "ffs_ctx_set_jungfrau_calibration: raw Jungfrau words convert to 32-bit photon counts: the context must have pixel_bytes 4";
+        return FFS_ERR_INVALID;
+    }
+    static const char* const names[6] = {"pedestal[0]", "pedestal[1]", "pedestal[2]", "factor[0]", "factor[1]", "factor[2]"};
+    const float* planes[6] = {cal->pedestal[0], cal->pedestal[1], cal->pedestal[2], cal->factor[0], cal->factor[1], cal->factor[2]};
+    const Layout& L = c->L;
+    const size_t n = (size_t)L.W * L.H;
+    for (int p = 0; p < 6; ++p) {
+        if (!planes[p]) {
+            c->err = std::string("ffs_ctx_set_jungfrau_calibration: ") + names[p] + " is NULL";
+            return FFS_ERR_INVALID;
+        }
+        for (size_t i = 0; i < n; ++i)
+            if (!jf_entry_ok(p >= 3, planes[p][i])) {
+                c->err = std::string("ffs_ctx_set_jungfrau_calibration: ") + names[p] + " entry " + std::to_string(i) + " (x = " + std::to_string(i % (size_t)L.W)
+                         + ", y = " + std::to_string(i / (size_t)L.W) + ") is " + std::to_string(planes[p][i])
+                         + (p >= 3 ? ": a factor must be 0 (no calibration) or finite with a magnitude in [2^-30, 2^16]"
+                                   : ": a pedestal must be finite and in [-65536, 65536]");
+                return FFS_ERR_INVALID;
+            }
+    }
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t stride = (n + 7) / 8 * 8;
+    if (!c->d_jf_cal) {
+        float* d = nullptr;
+        if (dmalloc(&d, 6 * stride * sizeof(float)) != hipSuccess) {
+            (void)hipGetLastError();
+            c->err = "ffs_ctx_set_jungfrau_calibration: hipMalloc(calibration planes) failed";
+            return FFS_ERR_NOMEM;
+        }
+        c->d_jf_cal = d;
+        c->jf_plane_stride = stride;
+    }
+    c->has_jf_cal = false;   // (a copy that fails half way leaves no mixed calibration in force)
+    for (int p = 0; p < 6; ++p) HIP_TRY(c, hipMemcpy(c->d_jf_cal + (size_t)p * stride, planes[p], n * sizeof(float), hipMemcpyHostToDevice));
+    c->has_jf_cal = true;
+    return FFS_OK;
+}
+extern "C" int ffs_ctx_set_jungfrau_calibration(ffs_ctx* c, const ffs_jungfrau_calibration* cal) {
+    if (!c) return FFS_ERR_INVALID;
+    return guarded(c, [&] { return ffs_ctx_set_jungfrau_calibration_impl(c, cal); });
 }
 
 extern "C" int ffs_ctx_set_max_valid_scope(ffs_ctx* c, int scope) {

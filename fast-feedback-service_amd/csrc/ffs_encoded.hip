@@ -1,11 +1,13 @@
-// ffs_encoded.hip -- encoded input from entry point to teardown: bitshuffle-LZ4 chunks (kernels_decode.hpp) and CBF byte-offset chunks
-// (kernels_byteoffset.hpp) cross PCIe as they lie in the file and are decoded into the stream's pitched device image, which enqueue_batch
-// (ffs_submit.hip) then takes like any other.  The two decoders' kernels are included here and nowhere else.  What is decided about a batch
-// -- may a chunk be a frame, where do the chunks lie, which bytes are copied, the tables the kernels read -- is encoded_plan.hpp's, without
-// HIP; this unit allocates, copies, records and launches.  The codec is looked at by prepare and launch (and the chunk check) only.
+// ffs_encoded.hip -- encoded input from entry point to teardown: bitshuffle-LZ4 chunks (kernels_decode.hpp), CBF byte-offset chunks
+// (kernels_byteoffset.hpp) and raw Jungfrau words (kernels_jungfrau.hpp) cross PCIe as they lie in the file and are decoded into the stream's
+// pitched device image, which enqueue_batch (ffs_submit.hip) then takes like any other.  The decoders' kernels are included here and nowhere
+// else.  What is decided about a batch -- may a chunk be a frame, where do the chunks lie, which bytes are copied, the tables the kernels
+// read -- is encoded_plan.hpp's, without HIP; this unit allocates, copies, records and launches.  The codec is looked at by prepare and
+// launch (and the chunk check) only.
 #include "ffs_internal.hpp"
 #include "kernels_decode.hpp"
 #include "kernels_byteoffset.hpp"
+#include "kernels_jungfrau.hpp"
 
 static_assert(sizeof(BlockEntry) == sizeof(uint2), "DecodeArgs::table reads the block table as uint2");
 
@@ -77,9 +79,9 @@ static int prepare(ffs_stream* s, int codec, const void* const* chunks, const si
     ffs_ctx* c = s->ctx;
     EncodedState& E = s->enc;
     const size_t W = (size_t)c->L.W, H = (size_t)c->L.H, es = (size_t)c->pixel_bytes;
-    const bool byte_offset = codec == FFS_CODEC_BYTE_OFFSET;
+    const bool byte_offset = codec == FFS_CODEC_BYTE_OFFSET, jungfrau = codec == FFS_CODEC_JUNGFRAU_RAW;
     b.codec = codec;
-    if (!byte_offset && !E.d_tab) {
+    if (!byte_offset && !jungfrau && !E.d_tab) {
         E.blocking = bshuf_blocking(W * H, es);
         if (!ensure_table(&E.d_tab, &E.h_tab, (size_t)s->max_batch * (E.blocking.blocks + 1) * sizeof(BlockEntry)))
             return refuse(c->err, FFS_ERR_NOMEM, "allocation of the compressed-chunk buffers failed");
@@ -90,6 +92,13 @@ static int prepare(ffs_stream* s, int codec, const void* const* chunks, const si
     Placement pl;
     if (!place_chunks(chunks, chunk_bytes, n, s->h_img, s->h_img_bytes, b.base, pl))
         return refuse(c->err, FFS_ERR_INVALID, "ffs_submit_compressed: either all chunks lie in the stream's host buffer or none");
+    if (jungfrau) {   // (no table: the conversion reads the context's calibration and the chunks where they lie)
+        if (!c->has_jf_cal)
+            return refuse(c->err, FFS_ERR_INVALID, "ffs_submit_encoded: raw Jungfrau words need a calibration and the context has none (ffs_ctx_set_jungfrau_calibration)");
+        if (const uint32_t f = first_unaligned_base(b.base.data(), n); f < n)
+            return refuse(c->err, FFS_ERR_INVALID, "ffs_submit_encoded: raw Jungfrau chunk " + std::to_string(f) + " lies in the stream's host buffer at offset "
+                                                       + std::to_string(b.base[f]) + ", which is not a multiple of 16");
+    }
     if (!pl.in_place) {
         FFS_TRY(ensure_host_staging(s, pl.staging));   // (grows with headroom; kept from then on)
         for (uint32_t f = 0; f < n; ++f) std::memcpy(s->h_img + b.base[f], chunks[f], chunk_bytes[f]);
@@ -160,9 +169,9 @@ static int launch(ffs_stream* s, const EncodedBatch& b, hipStream_t st, bool wit
     ffs_ctx* c = s->ctx;
     EncodedState& E = s->enc;
     const Layout& L = c->L;
-    const bool byte_offset = b.codec == FFS_CODEC_BYTE_OFFSET;
+    const bool byte_offset = b.codec == FFS_CODEC_BYTE_OFFSET, jungfrau = b.codec == FFS_CODEC_JUNGFRAU_RAW;
     const uint32_t n = (uint32_t)b.base.size();
-    if (with_table && !byte_offset) FFS_TRY(index_blocks(s, b, st, err));
+    if (with_table && !byte_offset && !jungfrau) FFS_TRY(index_blocks(s, b, st, err));
     if (with_table) (void)hipGetLastError();
     hipError_t e = after ? hipStreamWaitEvent(st, after, 0) : hipSuccess;
     if (e == hipSuccess && with_table && byte_offset) e = hipMemcpyAsync(E.d_bo_frames, E.h_bo_frames, (size_t)n * sizeof(BoFrame), hipMemcpyHostToDevice, st);
@@ -174,6 +183,17 @@ static int launch(ffs_stream* s, const EncodedBatch& b, hipStream_t st, bool wit
         hipLaunchKernelGGL(k_bo_compose, dim3(n), dim3(64), 0, st, a);
         if (c->pixel_bytes == 2) hipLaunchKernelGGL(k_bo_emit<uint16_t>, grid, dim3(64), 0, st, a);
         else hipLaunchKernelGGL(k_bo_emit<uint32_t>, grid, dim3(64), 0, st, a);
+    } else if (e == hipSuccess && with_decode && jungfrau) {
+        // one launch for up to kJfMaxFrames frames, whose bases travel in its arguments; a lane per group of eight pixels of the flat frame
+        const uint32_t n_px = (uint32_t)L.W * (uint32_t)L.H, groups = (n_px + kJfLanePixels - 1) / kJfLanePixels;
+        const dim3 grid((groups + kJfBlock - 1) / kJfBlock);
+        for (uint32_t f0 = 0; f0 < n; f0 += kJfMaxFrames) {
+            JfArgs a{.comp = E.d_comp, .planes = c->d_jf_cal, .plane_stride = c->jf_plane_stride, .image = s->d_img + (uint64_t)f0 * L.frame_stride,
+                     .frame_stride = L.frame_stride, .pitch = L.pitch, .W = (uint32_t)L.W, .n_px = n_px, .n_frames = std::min(n - f0, kJfMaxFrames), .base = {}};
+            for (uint32_t f = 0; f < a.n_frames; ++f) a.base[f] = (uint32_t)b.base[f0 + f];
+            if (L.W % kJfLanePixels == 0) hipLaunchKernelGGL(k_jungfrau_raw<true>, grid, dim3(kJfBlock), 0, st, a);
+            else hipLaunchKernelGGL(k_jungfrau_raw<false>, grid, dim3(kJfBlock), 0, st, a);
+        }
     } else if (e == hipSuccess && with_decode) {
         const BshufBlocking& k = E.blocking;
         const DecodeArgs da{.comp = E.d_comp, .table = reinterpret_cast<const uint2*>(E.d_tab), .image = s->d_img, .frame_stride = L.frame_stride,
@@ -189,7 +209,7 @@ static int launch(ffs_stream* s, const EncodedBatch& b, hipStream_t st, bool wit
 }
 
 static bool codec_known(ffs_ctx* c, int codec, const char* who) {
-    if (codec == FFS_CODEC_BSLZ4 || codec == FFS_CODEC_BYTE_OFFSET) return true;
+    if (codec == FFS_CODEC_BSLZ4 || codec == FFS_CODEC_BYTE_OFFSET || codec == FFS_CODEC_JUNGFRAU_RAW) return true;
     c->err = std::string(who) + ": unknown codec " + std::to_string(codec);
     return false;
 }

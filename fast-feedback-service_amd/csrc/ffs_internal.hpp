@@ -5,8 +5,8 @@
 //   ffs_submit.hip   one batch (enqueue_batch: plan_batch decides its path once, a BatchPlan with the launch geometry and the threshold route; then the resets,
 //                    the threshold stage and the sparse stage are launched from that plan), ffs_submit and ffs_submit_device
 //                    (kernels_stream / threshold / extended / window / ccl / chain / band)
-//   ffs_encoded.hip  encoded input from entry point to teardown: bitshuffle-LZ4 and CBF byte-offset chunks are staged, decoded on the device
-//                    (kernels_decode / byteoffset) and handed to enqueue_batch; acts on the decisions of encoded_plan.hpp
+//   ffs_encoded.hip  encoded input from entry point to teardown: bitshuffle-LZ4, CBF byte-offset and raw Jungfrau chunks are staged, decoded on the
+//                    device (kernels_decode / byteoffset / jungfrau) and handed to enqueue_batch; acts on the decisions of encoded_plan.hpp
 //   ffs_products.hip the per-frame products, each from its setter to its accessor: the radial profile, the radial-profile threshold, the per-pixel
 //                    statistics (kernels_radial / radthr / pixstats); ffs_submit.hip calls their launches at their places in a batch
 //   ffs_wait.hip     ffs_wait: overflow re-runs (rerun_batch: the same batch again with a Rerun override), result assembly,
@@ -26,6 +26,9 @@
 //   encoded_plan.hpp     the decisions about a batch of encoded frames: bitshuffle's blocking, the chunk checks, where the chunks lie in the
 //                        staging buffer and which ranges of it are copied, the block table, the byte-offset frame table (tests/encoded_plan_check.cc)
 //   radial_blur_model.hpp  the blur ahead of that threshold (ffs_ctx_set_radial_blur): weights, tap rule, v = S / Wn (tests/radial_blur_check.cc)
+//   jungfrau_model.hpp   raw Jungfrau words to photon counts (ffs_ctx_set_jungfrau_calibration, FFS_CODEC_JUNGFRAU_RAW): stage, invalid words, the
+//                        two float32 operations, rounding and clamp; the setter's ranges (kernels_jungfrau.hpp, included by ffs_encoded.hip;
+//                        host/codecs.hpp; tests/jungfrau_check.cc)
 // No exception leaves the library (guarded()).
 #pragma once
 #include <algorithm>
@@ -160,6 +163,12 @@ struct ffs_ctx {
     float* d_gain_map = nullptr;
     bool has_gain_map = false;
     float gain_map_min = 0.0f, gain_map_max = 0.0f;
+    // ffs_ctx_set_jungfrau_calibration: six dense planes of jf_plane_stride floats (W * H rounded up to 8, so that the
+    // kernel's last group loads inside them), pedestal G0 G1 G2 then factor G0 G1 G2, allocated at the first set and kept; has_jf_cal says
+    // whether a calibration is in force.  Written only while no batch of the context is in flight.
+    float* d_jf_cal = nullptr;
+    size_t jf_plane_stride = 0;
+    bool has_jf_cal = false;
     // ffs_ctx_set_radial_bins: [H][pitch_px] uint16 bin entries, allocated at the first set and kept (entries beyond W
     // are 0xFFFF); radial_bins says whether a map is in force and how many bins it has (0 = none).  Like the gain map it cannot change under a batch.
     uint16_t* d_radial_map = nullptr;

@@ -359,6 +359,15 @@ bool BatchPipeline::decode_into_slot(ReaderState& R, uint8_t* slot, uint32_t ima
         else byte_offset_decompress(chunk.data(), chunk.size(), reinterpret_cast<uint32_t*>(slot), n_px);
         break;
     case Reader::NONE:
+        if (cfg_.jungfrau_planes) {   // raw Jungfrau words: the rule the GPU kernel compiles (csrc/jungfrau_model.hpp), on this thread
+            if (chunk.size() != n_px * 2) {
+                std::printf("Error: image %u is %zu bytes, a frame of raw Jungfrau words is %zu\n", image_num, chunk.size(), n_px * 2);
+                fail();
+                break;
+            }
+            jungfrau_convert(reinterpret_cast<const uint16_t*>(chunk.data()), n_px, cfg_.jungfrau_planes, reinterpret_cast<uint32_t*>(slot));
+            break;
+        }
         std::memcpy(slot, chunk.data(), std::min(chunk.size(), frame_bytes_));
         break;
     }

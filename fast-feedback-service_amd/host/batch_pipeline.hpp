@@ -42,6 +42,9 @@ struct PipelineConfig {
     uint32_t readers = 1;      // reader threads, dealt round-robin to the GPUs
     bool gpu_decode = false;   // chunks go to the GPU as they are (ffs_submit_encoded with `codec`)
     int codec = FFS_CODEC_BSLZ4;
+    // --jungfrau-calibration: the six planes (6 x width x height float32), null: the frames are photon counts.  The source's frames are raw
+    // 16-bit words and bytes_per_pixel, the contexts', is 4; a frame the CPU decodes is converted by codecs.hpp's jungfrau_convert
+    const float* jungfrau_planes = nullptr;
     bool read_only = false, verbose = false;
     float timeout = 30.0f;     // seconds without a new image after which the readers stop
     float slot_margin = 2.0f;  // per cent of head room per chunk slot

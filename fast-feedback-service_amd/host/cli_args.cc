@@ -23,6 +23,7 @@ void usage() {
       "                  [-h5] [--output-for-index] [--batch N] [--cpu-decode] [--strict-dtype]\n"
       "                  [--max-valid trusted|none|N] [--max-valid-scope centre|window] [--min-count N] [--kernel-size N | NX,NY]\n"
       "                  [--gain G] [--gain-map FILE] [--radial-bins N] [--pixel-stats PREFIX]\n"
+      "                  [--jungfrau-calibration FILE]\n"
       "                  [--spot-background B]\n"
       "                  [--n-iqr X] [--radial-blur narrow|wide]\n"
       "                  [--devices D0,D1,... | --gpus N] [--no-numa-pinning] [--single-buffer] [--all-threads] [--read-only] [--clean-exit]\n"
@@ -43,6 +44,12 @@ void usage() {
       "              spotfinder.lookup.gain_map): FILE holds exactly width x height float32 values, little-endian, row-major, nothing\n"
       "              else; every value finite and in [2^-60, 2^60], under masked pixels too.  Each pixel is decided with the --gain\n"
       "              arithmetic and its own value.  Not together with --gain\n"
+      "--jungfrau-calibration: the frames are the raw 16-bit words of a Jungfrau (two bits of gain stage, 14 bits of ADC) and are converted\n"
+      "              to photon counts, 32 bits a pixel, with the calibration in FILE: exactly 6 x width x height float32 values, little-endian,\n"
+      "              row-major, nothing else -- the pedestals of the stages G0, G1, G2, then their factors (photons per ADU; 0 = no\n"
+      "              calibration for that pixel in that stage).  On the GPU (2 bytes a pixel cross PCIe), or with --cpu-decode on the worker\n"
+      "              thread by the same rule.  Saturated and uncalibrated pixels are masked for their frame; --max-valid trusted becomes\n"
+      "              min(trusted maximum, 2^24 - 1).  Needs a source of uncompressed 16-bit frames\n"
       "--radial-bins: per image, the count, sum and sum of squares of the valid pixels in each of N (1..1024) resolution shells of equal\n"
       "              width in 1/d^2, from the beam centre to the furthest pixel: the background level and its dispersion per shell, as\n"
       "              \"radial_count\", \"radial_sum\" and \"radial_sum_sq\" arrays in every image's JSON line (pixels above --max-valid and\n"
@@ -88,7 +95,7 @@ void usage() {
       "--cpu-decode: decompress the frames' chunks (bitshuffle-LZ4, CBF byte-offset) on the worker thread (the reference's way) instead\n"
       "              of sending them to the GPU as they are\n"
       "FILE: NXmx .nxs/.h5 (needs an HDF5 build), a /dev/shm directory, a ####.cbf template, or\n"
-      "      synth:<eiger16m|jungfrau9m|plumbing1k|sweep16m|tiny|tinysweep>[:n_images[:seed]]\n");
+      "      synth:<eiger16m|jungfrau9m|jungfrau9mraw|plumbing1k|sweep16m|tiny|tinyraw|tinysweep>[:n_images[:seed]]\n");
 }
 
 [[noreturn]] void arg_error(const std::string& m) {  // arg_parser.cc:72-77
@@ -199,7 +206,11 @@ Args parse_args(int argc, char** argv) {
             catch (...) { arg_error("pattern not found for '" + s + "': " + v); }
             if (!(r.gain > 0.0) || r.gain > 1.7976931348623157e308) arg_error("--gain takes a finite number above 0: " + v);
         }
-        else if (s == "--gain-map") {
+        else if (s == "--jungfrau-calibration") {
+            r.jungfrau_calibration = need(i, s);
+            if (r.jungfrau_calibration.empty() || !fs::is_regular_file(r.jungfrau_calibration))
+                arg_error("--jungfrau-calibration: no such file: " + r.jungfrau_calibration);
+        } else if (s == "--gain-map") {
             r.gain_map = need(i, s);
             if (r.gain_map.empty() || !fs::is_regular_file(r.gain_map)) arg_error("--gain-map: no such file: " + r.gain_map);
         }

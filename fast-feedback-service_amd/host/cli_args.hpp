@@ -24,6 +24,7 @@ struct Args {
     std::string max_valid = "trusted";   // trusted | none | N
     int max_valid_scope = 0;             // --max-valid-scope centre (FFS_MAX_VALID_CENTRE) | window (FFS_MAX_VALID_WINDOW)
     double gain = 0.0;                   // --gain G (> 0); 0 = not given: pixel values are photon counts
+    std::string jungfrau_calibration;    // --jungfrau-calibration FILE (raw float32, 6 x width x height values); empty = not given
     std::string gain_map;                // --gain-map FILE (raw float32, width x height values); empty = not given.  Not with --gain
     uint32_t radial_bins = 0;            // --radial-bins N (1..1024): the per-image radial profile over N resolution shells; 0 = not given
                                          // (-a radial_profile: its shells, 100 unless given, at most 128)

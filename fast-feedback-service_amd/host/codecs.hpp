@@ -1,6 +1,6 @@
 // codecs.hpp -- host decoders for the chunk formats the reference's readers hand over
 // (spotfinder/spotfinder.cc:823-842): bitshuffle+LZ4 (HDF5 filter 32008 framing) and the CBF
-// byte-offset codec (spotfinder/cbfread.hpp:49-106).  Own implementations of the published
+// byte-offset codec (spotfinder/cbfread.hpp:49-106); and the host's side of the raw Jungfrau conversion.  Own implementations of the published
 // formats (LZ4 block format; bitshuffle: blocks of elements stored as bit planes); encoders are
 // provided for the synthetic writers and the tests.
 #pragma once
@@ -9,6 +9,8 @@
 #include <cstring>
 #include <span>
 #include <vector>
+
+#include "../csrc/jungfrau_model.hpp"
 
 namespace ffshost {
 
@@ -245,6 +247,14 @@ inline std::vector<uint8_t> byte_offset_compress(const int32_t* v, size_t n) {
         cur = v[k];
     }
     return out;
+}
+
+// ---- raw Jungfrau words to photon counts: the rule of csrc/jungfrau_model.hpp, the text the GPU kernel compiles --------------------
+// planes: pedestal G0, G1, G2 then factor G0, G1, G2, n_px float32 each (the --jungfrau-calibration file); raw: n_px little-endian words
+inline void jungfrau_convert(const uint16_t* raw, size_t n_px, const float* planes, uint32_t* out) {
+    const float* const pedestal[3] = {planes, planes + n_px, planes + 2 * n_px};
+    const float* const factor[3] = {planes + 3 * n_px, planes + 4 * n_px, planes + 5 * n_px};
+    ffsamd::jf_convert_frame(raw, n_px, pedestal, factor, out);
 }
 
 }  // namespace ffshost

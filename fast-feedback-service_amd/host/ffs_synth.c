@@ -275,3 +275,43 @@ int ffs_synth_reference_sample(uint32_t n, int32_t pb, void *out) {
 #undef PUT
     return 0;
 }
+
+/* ---- raw Jungfrau words ------------------------------------------------------------- */
+
+int ffs_synth_jungfrau_calibration(uint32_t width, uint32_t height, uint64_t seed, float *planes) {
+    if (!planes || !width || !height) return -1;
+    const size_t n = (size_t)width * height;
+    for (size_t k = 0; k < n; ++k) {
+        const uint64_t h = hash3(seed, 0x4A46ULL, k);
+        planes[0 * n + k] = (float)(2600.0 + 0.5 * (double)(h & 1023));
+        planes[1 * n + k] = (float)(14400.0 + 0.5 * (double)((h >> 10) & 1023));
+        planes[2 * n + k] = (float)(15100.0 + 0.5 * (double)((h >> 20) & 1023));
+        planes[3 * n + k] = (float)(1.0 / (480.0 + (double)((h >> 30) & 63)));
+        planes[4 * n + k] = (float)(-1.0 / (17.0 + 0.25 * (double)((h >> 36) & 3)));
+        planes[5 * n + k] = (float)(-1.0 / (1.25 + 0.0625 * (double)((h >> 38) & 3)));
+        if (((h >> 40) & 511) == 0) planes[(3 + (h >> 49) % 3) * n + k] = 0.0f;
+    }
+    return 0;
+}
+
+int ffs_synth_jungfrau_encode(const uint32_t *photons, uint32_t width, uint32_t height, const float *planes, uint64_t seed,
+                              uint32_t frame, uint16_t *raw) {
+    if (!photons || !planes || !raw || !width || !height) return -1;
+    const size_t n = (size_t)width * height;
+    static const uint16_t code[3] = {0x0000, 0x4000, 0xC000};
+    for (size_t k = 0; k < n; ++k) {
+        const uint32_t ph = photons[k];
+        const int s = ph < 24 ? 0 : ph < 800 ? 1 : 2;
+        const double ped = planes[(size_t)s * n + k], fac = planes[(size_t)(3 + s) * n + k];
+        double adc = fac != 0.0 ? floor(ped + (double)ph / fac + 0.5) : floor(ped);
+        if (adc < 0.0) adc = 0.0;
+        if (adc > 16383.0) adc = 16383.0;
+        uint16_t r = (uint16_t)(code[s] | (uint16_t)adc);
+        const uint64_t h = hash3(seed ^ 0x4A46524157ULL, frame, k) & 4095;
+        if (h == 0) r = 0xFFFF;
+        else if (h == 1) r = (uint16_t)(0x8000 | (r & 0x3FFF));
+        else if (h == 2) r = 0xC000;
+        raw[k] = r;
+    }
+    return 0;
+}

@@ -83,6 +83,9 @@ class H5Read;
 // spotfinder <file>: directory -> SHMRead, *.cbf -> CBFRead, "synth:..." -> SynthRead,
 // anything else -> H5Read (spotfinder/spotfinder.cc:443-465)
 std::unique_ptr<Reader> make_synth_reader(const std::string& spec);
+// the calibration of a synthetic source of raw Jungfrau words ("synth:tinyraw", "synth:jungfrau9mraw"): six planes, the layout of the
+// driver's --jungfrau-calibration file; empty for any other synthetic source
+std::vector<float> synth_jungfrau_calibration(const std::string& spec);
 std::unique_ptr<Reader> make_cbf_reader(const std::string& templ, size_t num_images, size_t first_index);
 std::unique_ptr<Reader> make_shm_reader(const std::string& dir);
 std::unique_ptr<Reader> make_h5_reader(const std::string& master_file);  // NXmx / Eiger HDF5

@@ -30,15 +30,23 @@ class SynthRead : public Reader {
     size_t n_images_ = 10;
     std::vector<uint8_t> mask_;
     float osc_width_ = 0.f;
+    // jungfrau9mraw, tinyraw: the photon frames (p_, 32-bit) leave as the raw 16-bit words of a Jungfrau under the calibration that is a pure
+    // function of (pixel, seed) -- ffs_synth_jungfrau_calibration, what `ffs_hosttool jfcal` writes for --jungfrau-calibration
+    bool raw_words_ = false;
+    std::vector<float> jf_planes_;
 
   public:
     explicit SynthRead(const std::string& spec) {
-        // synth:<eiger16m|jungfrau9m|plumbing1k|sweep16m|tiny>[:n[:seed]]
+        // synth:<eiger16m|jungfrau9m|jungfrau9mraw|plumbing1k|sweep16m|tiny|tinyraw|tinysweep>[:n[:seed]]
         std::vector<std::string> parts;
         std::stringstream ss(spec);
         std::string tok;
         while (std::getline(ss, tok, ':')) parts.push_back(tok);
-        const std::string kind = parts.size() > 1 ? parts[1] : "eiger16m";
+        std::string kind = parts.size() > 1 ? parts[1] : "eiger16m";
+        if (kind == "jungfrau9mraw" || kind == "tinyraw") {
+            raw_words_ = true;
+            kind.resize(kind.size() - 3);
+        }
         if (parts.size() > 2 && !parts[2].empty()) n_images_ = std::stoul(parts[2]);
         const uint64_t seed = parts.size() > 3 ? std::stoull(parts[3]) : 0;
         p_.sigma_min = 0.8; p_.sigma_max = 1.6; p_.peak_min = 30; p_.peak_max = 5000;
@@ -72,23 +80,38 @@ class SynthRead : public Reader {
                 p_.n_frames = (uint32_t)n_images_; p_.sigma_z_min = 0.5; p_.sigma_z_max = 2.0;
                 osc_width_ = 0.1f;
             }
+            if (raw_words_) { p_.pixel_bytes = 4; p_.max_value = (1u << 24) - 1; }   // (tiny's 32-bit twin)
         } else {
             throw std::runtime_error("unknown synthetic workload '" + kind + "'");
         }
+        if (raw_words_) {
+            jf_planes_.resize((size_t)6 * p_.width * p_.height);
+            ffs_synth_jungfrau_calibration(p_.width, p_.height, p_.seed, jf_planes_.data());
+        }
     }
+    const std::vector<float>& jungfrau_planes() const { return jf_planes_; }
     bool is_image_available(size_t index) override { return index < n_images_; }
     std::span<uint8_t> get_raw_chunk(size_t index, std::span<uint8_t> dst) override {
-        const size_t bytes = (size_t)p_.width * p_.height * p_.pixel_bytes;
+        const size_t n_px = (size_t)p_.width * p_.height;
+        const size_t bytes = n_px * (raw_words_ ? 2 : (size_t)p_.pixel_bytes);
         if (dst.size() < bytes) return {dst.data(), 0};
+        if (raw_words_) {
+            static thread_local std::vector<uint32_t> photons;   // (reentrant: a frame per calling thread)
+            photons.resize(n_px);
+            ffs_synth_frame(&p_, (uint32_t)index, photons.data());
+            ffs_synth_jungfrau_encode(photons.data(), p_.width, p_.height, jf_planes_.data(), p_.seed, (uint32_t)index,
+                                      reinterpret_cast<uint16_t*>(dst.data()));
+            return {dst.data(), bytes};
+        }
         ffs_synth_frame(&p_, (uint32_t)index, dst.data());
         return {dst.data(), bytes};
     }
     bool reentrant() const override { return true; }  // frames are a pure function of (parameters, index)
     ChunkCompression get_raw_chunk_compression() override { return NONE; }
     size_t get_number_of_images() const override { return n_images_; }
-    h5read_dtype get_dtype() const override { return p_.pixel_bytes == 2 ? H5READ_DTYPE_UINT16 : H5READ_DTYPE_UINT32; }
+    h5read_dtype get_dtype() const override { return p_.pixel_bytes == 2 || raw_words_ ? H5READ_DTYPE_UINT16 : H5READ_DTYPE_UINT32; }
     std::array<int64_t, 2> get_trusted_range() const override {
-        return {0, p_.pixel_bytes == 2 ? 65535 : (int64_t)0xFFFFFFFFll};
+        return {0, p_.pixel_bytes == 2 ? 65535 : (int64_t)0xFFFFFFFFll};   // (raw words: of the photon counts they convert to)
     }
     std::array<size_t, 2> image_shape() const override { return {p_.height, p_.width}; }
     std::optional<std::span<const uint8_t>> get_mask() const override { return {{mask_.data(), mask_.size()}}; }
@@ -102,6 +125,7 @@ class SynthRead : public Reader {
 };
 
 std::unique_ptr<Reader> make_synth_reader(const std::string& spec) { return std::make_unique<SynthRead>(spec); }
+std::vector<float> synth_jungfrau_calibration(const std::string& spec) { return SynthRead(spec).jungfrau_planes(); }
 
 // ---- CBF (spotfinder/cbfread.cc) ----------------------------------------------------------------------
 static std::string expand_template(const std::string& templ, size_t index) {  // cbfread.cc:16-22

@@ -205,6 +205,39 @@ static std::vector<float> read_gain_map(const Args& args, uint32_t width, uint32
     return map;
 }
 
+// --jungfrau-calibration FILE: exactly 6 x width x height float32 values, little-endian, row-major -- pedestal G0, G1, G2, then factor G0, G1,
+// G2 -- for a source of uncompressed 16-bit frames.  The ranges are the library's to check (ffs_ctx_set_jungfrau_calibration names plane and
+// entry).  Anything else is a usage error.  Empty: the flag was not given.
+static std::vector<float> read_jungfrau_calibration(const Args& args, Reader& reader) {
+    std::vector<float> planes;
+    if (args.jungfrau_calibration.empty()) return planes;
+    const std::string& file = args.jungfrau_calibration;
+    if (reader.get_raw_chunk_compression() != Reader::NONE || reader.get_element_size() != 2)
+        arg_error("--jungfrau-calibration: raw Jungfrau words are uncompressed 16-bit frames; this frame source hands over "
+                  + std::string(reader.get_raw_chunk_compression() == Reader::NONE ? "uncompressed" : "compressed") + " frames of "
+                  + std::to_string(reader.get_element_size() * 8) + " bits (compressed raw frames are not supported)");
+    const uint32_t width = (uint32_t)reader.image_shape()[1], height = (uint32_t)reader.image_shape()[0];
+    const size_t n = (size_t)6 * width * height;
+    std::ifstream f(file, std::ios::binary | std::ios::ate);
+    if (!f) arg_error("--jungfrau-calibration: cannot open " + file);
+    const std::streamoff bytes = f.tellg();
+    if (bytes < 0 || (uint64_t)bytes != (uint64_t)n * sizeof(float))
+        arg_error("--jungfrau-calibration: " + file + " holds " + std::to_string((long long)bytes) + " bytes, the 6 x " + std::to_string(width) + " x "
+                  + std::to_string(height) + " float32 values of this detector are " + std::to_string(n * sizeof(float)));
+    planes.resize(n);
+    f.seekg(0);
+    if (!f.read(reinterpret_cast<char*>(planes.data()), bytes)) arg_error("--jungfrau-calibration: cannot read " + file);
+    return planes;
+}
+static int set_jungfrau_calibration(ffs_ctx* cx, const std::vector<float>& planes, size_t n_px) {
+    ffs_jungfrau_calibration cal{};
+    for (int s = 0; s < 3; ++s) {
+        cal.pedestal[s] = planes.data() + (size_t)s * n_px;
+        cal.factor[s] = planes.data() + (size_t)(3 + s) * n_px;
+    }
+    return ffs_ctx_set_jungfrau_calibration(cx, &cal);
+}
+
 // --pixel-stats PREFIX, after the last wait: the contexts' statistics merged on the host -- counts and sums add (the sums of squares modulo
 // 2^64, as each context's own), the maximum is the largest -- and written as four raw little-endian files of width x height values.
 static bool write_pixel_stats(const std::string& prefix, const std::vector<ffs_ctx*>& ctxs, uint32_t width, uint32_t height) {
@@ -248,7 +281,8 @@ static bool write_pixel_stats(const std::string& prefix, const std::vector<ffs_c
 
 // (--gain-map: the file is held against the frame source's shape as soon as the source is open, ahead of the verdict on the devices -- a
 // usage error is reported as one wherever the driver runs)
-static int open_source_beside_runtime(const Args& args, Stamps& stamp, std::unique_ptr<Reader>& reader, std::vector<float>& gain_map) {
+static int open_source_beside_runtime(const Args& args, Stamps& stamp, std::unique_ptr<Reader>& reader, std::vector<float>& gain_map,
+                                      std::vector<float>& jungfrau_planes) {
     int reader_rc = 0;
     std::atomic<bool> give_up{false};
     JoinedThread reader_holder;
@@ -259,6 +293,11 @@ static int open_source_beside_runtime(const Args& args, Stamps& stamp, std::uniq
         reader_holder.th.join();
         if (reader_rc != 0) return reader_rc;
         gain_map = read_gain_map(args, (uint32_t)reader->image_shape()[1], (uint32_t)reader->image_shape()[0]);
+    }
+    if (!args.jungfrau_calibration.empty()) {   // (likewise)
+        if (reader_holder.th.joinable()) reader_holder.th.join();
+        if (reader_rc != 0) return reader_rc;
+        jungfrau_planes = read_jungfrau_calibration(args, *reader);
     }
     if (args.radial_bins) {   // (--radial-bins needs the geometry --dmin needs: without it a usage error, like a bad --gain-map, wherever the driver runs)
         if (reader_holder.th.joinable()) reader_holder.th.join();
@@ -893,16 +932,21 @@ int main(int argc, char** argv) {
     }
     std::unique_ptr<Reader> reader_ptr;
     std::vector<float> gain_map;   // --gain-map: width x height values, checked; empty: none
-    if (const int rc = open_source_beside_runtime(args, stamp, reader_ptr, gain_map)) return rc;
+    std::vector<float> jungfrau_planes;   // --jungfrau-calibration: 6 x width x height values; empty: the frames are photon counts
+    if (const int rc = open_source_beside_runtime(args, stamp, reader_ptr, gain_map, jungfrau_planes)) return rc;
     Reader& reader = *reader_ptr;
+    const bool jungfrau = !jungfrau_planes.empty();
 
+    // (raw Jungfrau words are 16 bits in the source and 32-bit photon counts from the conversion on: the flag decides, not the source's type)
     FrameShape shape;
-    shape.bytes_per_pixel = reader.get_element_size();
+    shape.bytes_per_pixel = jungfrau ? 4 : reader.get_element_size();
     if (const int rc = check_dtype(args, argv[0], shape.bytes_per_pixel)) return rc;
     const uint32_t num_images = args.images_set ? args.images : (uint32_t)reader.get_number_of_images();
     shape.height = (uint32_t)reader.image_shape()[0];
     shape.width = (uint32_t)reader.image_shape()[1];
-    const int64_t max_valid = max_valid_pixel(args.max_valid, reader, shape.bytes_per_pixel);
+    int64_t max_valid = max_valid_pixel(args.max_valid, reader, shape.bytes_per_pixel);
+    // (converted frames mark saturated and uncalibrated pixels 0xFFFFFFFF: with a max_valid of at most 2^24 - 1 such a centre is never strong)
+    if (jungfrau && args.max_valid == "trusted") max_valid = max_valid < 0 ? (1ll << 24) - 1 : std::min<int64_t>(max_valid, (1ll << 24) - 1);
     Experiment ex;
     if (const int rc = read_experiment(args, reader, ex)) return rc;
     const bool rotation = ex.oscillation_width > 0;
@@ -914,7 +958,8 @@ int main(int argc, char** argv) {
     // bitshuffle-LZ4 chunks and CBF byte-offset sections go to the GPU as they are (read straight into the pinned staging area)
     // unless the pixels are needed on the host (--writeout) or --cpu-decode asks for the reference's way
     const bool byte_offset = reader.get_raw_chunk_compression() == Reader::BYTE_OFFSET_32;
-    const bool gpu_decode = (reader.get_raw_chunk_compression() == Reader::BITSHUFFLE_LZ4 || byte_offset) && !args.cpu_decode && !args.writeout;
+    // ... and so do raw Jungfrau words (--jungfrau-calibration), converted there
+    const bool gpu_decode = (reader.get_raw_chunk_compression() == Reader::BITSHUFFLE_LZ4 || byte_offset || jungfrau) && !args.cpu_decode && !args.writeout;
     const uint32_t n_dev_arg = (uint32_t)std::max<size_t>(1, args.devices.size());
     const uint32_t batch = args.batch ? args.batch : default_batch(gpu_decode, num_images, n_dev_arg);
     std::printf("Image:       %4u x %4u = %u px\n", shape.width, shape.height, shape.width * shape.height);
@@ -963,7 +1008,11 @@ int main(int argc, char** argv) {
         FFS_CHECK(cx, ffs_ctx_set_max_valid_scope(cx, args.max_valid_scope));
         FFS_CHECK(cx, ffs_ctx_set_gain(cx, args.gain));
         if (!gain_map.empty()) FFS_CHECK(cx, ffs_ctx_set_gain_map(cx, gain_map.data()));
+        if (jungfrau) FFS_CHECK(cx, set_jungfrau_calibration(cx, jungfrau_planes, shape.pixels()));
     }
+    if (jungfrau)
+        std::printf("Jungfrau calibration: %s (raw 16-bit words -> photon counts %s; saturated and uncalibrated pixels are masked for their frame)\n",
+                    args.jungfrau_calibration.c_str(), gpu_decode ? "on the GPU" : "on the worker threads");
     if (max_valid >= 0 && args.max_valid_scope == FFS_MAX_VALID_WINDOW)
         std::printf("Trusted range: pixels above %lld are masked for their frame (window scope: out of every window's sums, and not spots)\n", (long long)max_valid);
     else if (max_valid >= 0) std::printf("Trusted range: centre pixels above %lld are not spots\n", (long long)max_valid);
@@ -1000,6 +1049,8 @@ int main(int argc, char** argv) {
     if (!args.pixel_stats.empty())
         for (ffs_ctx* cx : ctxs) FFS_CHECK(cx, ffs_ctx_set_pixel_stats(cx, FFS_PIXEL_STATS_START));
     if (args.validate && !create_validation_contexts(devices, ctxs, shape, batch, prm, args.max_valid_scope, args.gain, gain_map, vctxs)) return 1;
+    if (args.validate && jungfrau && gpu_decode)   // (the validation streams are handed the same raw chunks)
+        for (ffs_ctx* v : vctxs) FFS_CHECK(v, set_jungfrau_calibration(v, jungfrau_planes, shape.pixels()));
     if (args.save_h5 && !h5_supported()) {
         std::printf("Error: --save-h5 needs an HDF5-enabled build\n");
         return 1;
@@ -1019,7 +1070,8 @@ int main(int argc, char** argv) {
     cfg.batch = batch;
     cfg.assemblies = args.single_buffer ? 1u : args.assemblies ? std::min(args.assemblies, 32u) : (gpu_decode ? 4u : 3u);
     cfg.gpu_decode = gpu_decode;
-    cfg.codec = byte_offset ? FFS_CODEC_BYTE_OFFSET : FFS_CODEC_BSLZ4;
+    cfg.codec = jungfrau ? FFS_CODEC_JUNGFRAU_RAW : byte_offset ? FFS_CODEC_BYTE_OFFSET : FFS_CODEC_BSLZ4;
+    cfg.jungfrau_planes = jungfrau ? jungfrau_planes.data() : nullptr;
     cfg.read_only = args.read_only;
     cfg.verbose = args.verbose;
     cfg.timeout = args.timeout;

@@ -115,6 +115,11 @@ MAX_VALID_CENTRE, MAX_VALID_WINDOW = 0, 1   # FFS_MAX_VALID_*: what Context.set_
 
 CODEC_BSLZ4 = 0         # FFS_CODEC_*: what Stream.submit_encoded / decode_only take
 CODEC_BYTE_OFFSET = 1
+CODEC_JUNGFRAU_RAW = 2  # raw Jungfrau words (uint16 arrays or bytes), converted with Context.set_jungfrau_calibration
+
+
+class _JungfrauCalibration(C.Structure):   # ffs_jungfrau_calibration
+    _fields_ = [("pedestal", C.c_void_p * 3), ("factor", C.c_void_p * 3)]
 
 # every symbol include/ffs_hip.h declares (tests check the library exports them all)
 EXPORTS = [
@@ -131,6 +136,7 @@ EXPORTS = [
     "ffs_ctx_set_pixel_stats", "ffs_ctx_get_pixel_stats", "ffs_bench_pixel_stats",
     "ffs_stream_spot_backgrounds",
     "ffs_ctx_set_radial_threshold", "ffs_stream_radial_thresholds", "ffs_ctx_set_radial_blur",
+    "ffs_ctx_set_jungfrau_calibration",
 ]
 
 _lib = None
@@ -157,6 +163,7 @@ def load_library():
         L.ffs_ctx_set_max_valid_scope.argtypes = [C.c_void_p, C.c_int]
         L.ffs_ctx_set_gain.argtypes = [C.c_void_p, C.c_double]
         L.ffs_ctx_set_gain_map.argtypes = [C.c_void_p, C.c_void_p]
+        L.ffs_ctx_set_jungfrau_calibration.argtypes = [C.c_void_p, C.POINTER(_JungfrauCalibration)]
         L.ffs_ctx_set_radial_bins.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
         L.ffs_stream_radial_profile.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(_RadialProfile)]
         L.ffs_bench_radial.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_uint32, C.c_uint32, C.POINTER(C.c_float)]
@@ -336,6 +343,26 @@ class Context:
             raise ValueError(f"the gain map must have shape (H, W) = {(self.H, self.W)}, not {g.shape}")
         self._check(self._lib.ffs_ctx_set_gain_map(self._h, g.ctypes.data_as(C.c_void_p)))
 
+    def set_jungfrau_calibration(self, pedestal: np.ndarray | None, factor: np.ndarray | None = None):
+        """ffs_ctx_set_jungfrau_calibration: what CODEC_JUNGFRAU_RAW converts raw words with -- pedestal and factor (photons per ADU,
+        0 = no calibration for the pixel in that stage), each (3, H, W) for the stages G0, G1, G2, converted to C-contiguous float32;
+        None drops the calibration.  A property of the context like the mask: kept across set_params, replaceable between batches.
+        Refused (FfsError, state unchanged): a uint16 context; an entry that is not finite, a pedestal outside [-65536, 65536], a
+        factor neither 0 nor of magnitude in [2^-30, 2^16] (the text names plane and index); while a batch is in flight.  A wrong
+        shape is a ValueError."""
+        if pedestal is None:
+            self._check(self._lib.ffs_ctx_set_jungfrau_calibration(self._h, None))
+            return
+        p = np.ascontiguousarray(pedestal, dtype=np.float32)
+        f = np.ascontiguousarray(factor, dtype=np.float32)
+        if p.shape != (3, self.H, self.W) or f.shape != (3, self.H, self.W):
+            raise ValueError(f"pedestal and factor must have shape (3, H, W) = {(3, self.H, self.W)}, not {p.shape} and {f.shape}")
+        cal = _JungfrauCalibration()
+        for s in range(3):
+            cal.pedestal[s] = p[s].ctypes.data
+            cal.factor[s] = f[s].ctypes.data
+        self._check(self._lib.ffs_ctx_set_jungfrau_calibration(self._h, C.byref(cal)))
+
     def set_radial_bins(self, bins: np.ndarray | None, n_bins=None):
         """ffs_ctx_set_radial_bins: the bin map of the per-frame radial profile, an H x W array of bin indices (converted to
         C-contiguous uint16; RADIAL_NO_BIN = 0xFFFF is "in no bin"), or None for no map (the default).  n_bins (1..1024) defaults
@@ -454,9 +481,10 @@ class Stream:
         return np.frombuffer((C.c_uint8 * n.value).from_address(p.value), dtype=np.uint8)
 
     def _chunk_args(self, chunks):
-        keep = [np.frombuffer(c, np.uint8) if not isinstance(c, np.ndarray) else c for c in chunks]
+        # (an array of any item size counts in bytes: raw Jungfrau frames are uint16 arrays; one that is not contiguous is copied)
+        keep = [np.frombuffer(c, np.uint8) if not isinstance(c, np.ndarray) else np.ascontiguousarray(c) for c in chunks]
         ptrs = (C.c_void_p * len(keep))(*[k.ctypes.data for k in keep])
-        sizes = (C.c_size_t * len(keep))(*[k.size for k in keep])
+        sizes = (C.c_size_t * len(keep))(*[k.nbytes for k in keep])
         return keep, ptrs, sizes
 
     def submit_compressed(self, chunks, first_frame_id: int = 0):
@@ -471,7 +499,8 @@ class Stream:
 
     def submit_encoded(self, chunks, codec: int, first_frame_id: int = 0):
         """chunks: one per frame, in `codec` (CODEC_BSLZ4: as submit_compressed; CODEC_BYTE_OFFSET: a CBF binary section, the
-        bytes behind its marker)."""
+        bytes behind its marker; CODEC_JUNGFRAU_RAW: H x W raw words as a uint16 array or W*H*2 bytes, little-endian, on a uint32
+        context with a calibration set)."""
         self._keep, ptrs, sizes = self._chunk_args(chunks)
         self.ctx._check(self._lib.ffs_submit_encoded(self._h, codec, ptrs, sizes, len(self._keep), first_frame_id))
         self._snapshot()

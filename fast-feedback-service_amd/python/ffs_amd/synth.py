@@ -132,3 +132,41 @@ def sweep_params(seed=5000, n_frames=100, n_spots=800, width=4148, height=4362) 
     return params(width, height, np.uint16, seed=seed, background=2.0, n_spots=n_spots,
                   sigma=(0.8, 1.6), peak=(30.0, 5000.0), max_value=65535,
                   n_frames=n_frames, sigma_z=(0.5, 2.0))
+
+
+# ---- raw Jungfrau words (the driver's synth:tinyraw / synth:jungfrau9mraw) ---------
+
+def jungfrau_calibration(width, height, seed):
+    """ffs_synth_jungfrau_calibration: (pedestal, factor), each (3, H, W) float32, a pure function of (pixel, seed).  The two stacked, pedestal
+    first, are the driver's --jungfrau-calibration file."""
+    planes = np.empty((6, height, width), np.float32)
+    if lib().ffs_synth_jungfrau_calibration(C.c_uint32(width), C.c_uint32(height), C.c_uint64(seed), planes.ctypes.data_as(C.c_void_p)) != 0:
+        raise ValueError("ffs_synth_jungfrau_calibration rejected its parameters")
+    return planes[:3], planes[3:]
+
+
+def jungfrau_encode(photons, pedestal, factor, seed, frame):
+    """ffs_synth_jungfrau_encode: one frame of photon counts (H, W) as raw uint16 words under the calibration."""
+    ph = np.ascontiguousarray(photons, np.uint32)
+    H, W = ph.shape
+    planes = np.ascontiguousarray(np.concatenate([pedestal, factor]), np.float32)
+    assert planes.shape == (6, H, W)
+    raw = np.empty((H, W), np.uint16)
+    if lib().ffs_synth_jungfrau_encode(ph.ctypes.data_as(C.c_void_p), C.c_uint32(W), C.c_uint32(H), planes.ctypes.data_as(C.c_void_p), C.c_uint64(seed),
+                                       C.c_uint32(frame), raw.ctypes.data_as(C.c_void_p)) != 0:
+        raise ValueError("ffs_synth_jungfrau_encode rejected its parameters")
+    return raw
+
+
+def tiny_params(seed=7, dtype=np.uint16) -> SynthParams:
+    """The driver's synth:tiny (300 x 200 u16); with uint32 its 32-bit twin, the photon frames behind synth:tinyraw."""
+    dt = np.dtype(dtype)
+    return params(300, 200, dt, seed=seed, background=2.0, n_spots=40, sigma=(0.8, 1.6), peak=(30.0, 5000.0),
+                  max_value=65535 if dt.itemsize == 2 else (1 << 24) - 1)
+
+
+def raw_frames(p: SynthParams, indices) -> np.ndarray:
+    """What synth:tinyraw / synth:jungfrau9mraw hand over: the photon frames of `p` (uint32) as raw words under jungfrau_calibration(seed)."""
+    assert p.pixel_bytes == 4
+    ped, fac = jungfrau_calibration(p.width, p.height, p.seed)
+    return np.stack([jungfrau_encode(frame(p, i), ped, fac, p.seed, i) for i in indices])

@@ -7,6 +7,10 @@
 //   ffs_hosttool mkh5 <synth:spec> <master.h5> [layout [frames_per_file [n_written]]]
 //                                         NXmx master + data files (host/h5_writer.cc)
 //   ffs_hosttool h5info <master.h5>       what the HDF5 reader sees; synthinfo prints the same checksums
+//   ffs_hosttool jfcal <synth:spec> <file>    the calibration of a synthetic source of raw Jungfrau words, as spotfinder's
+//                                         --jungfrau-calibration reads it (6 W H float32: pedestal G0 G1 G2, factor G0 G1 G2)
+//   ffs_hosttool jfconvert <raw> <cal> <W> <H> <out>   the host converter of codecs.hpp: frames of W H raw words -> uint32 photon counts
+//   ffs_hosttool synthframes <synth:spec> <file>        the source's frames as it hands them over, one behind the other
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -205,6 +209,46 @@ static int synthinfo(const std::string& spec) {
     return 0;
 }
 
+static std::vector<uint8_t> read_file(const std::string& path) {
+    std::ifstream f(path, std::ios::binary);
+    if (!f) throw std::runtime_error("cannot open " + path);
+    return std::vector<uint8_t>((std::istreambuf_iterator<char>(f)), std::istreambuf_iterator<char>());
+}
+
+static int jfcal(const std::string& spec, const std::string& file) {
+    const std::vector<float> planes = synth_jungfrau_calibration(spec);
+    if (planes.empty()) return fail("jfcal: not a source of raw Jungfrau words (synth:tinyraw, synth:jungfrau9mraw)");
+    std::ofstream f(file, std::ios::binary);
+    f.write(reinterpret_cast<const char*>(planes.data()), (std::streamsize)(planes.size() * sizeof(float)));
+    return f ? 0 : fail("jfcal: cannot write the file");
+}
+
+static int jfconvert(const std::string& raw_file, const std::string& cal_file, size_t W, size_t H, const std::string& out_file) {
+    const std::vector<uint8_t> raw = read_file(raw_file), cal = read_file(cal_file);
+    const size_t n_px = W * H;
+    if (n_px == 0 || cal.size() != 6 * n_px * sizeof(float) || raw.size() % (2 * n_px) != 0) return fail("jfconvert: file sizes do not match W x H");
+    std::vector<float> planes(6 * n_px);
+    std::memcpy(planes.data(), cal.data(), cal.size());
+    std::vector<uint16_t> words(raw.size() / 2);
+    std::memcpy(words.data(), raw.data(), raw.size());
+    std::vector<uint32_t> out(words.size());
+    for (size_t f = 0; f < words.size() / n_px; ++f) jungfrau_convert(words.data() + f * n_px, n_px, planes.data(), out.data() + f * n_px);
+    std::ofstream o(out_file, std::ios::binary);
+    o.write(reinterpret_cast<const char*>(out.data()), (std::streamsize)(out.size() * 4));
+    return o ? 0 : fail("jfconvert: cannot write the file");
+}
+
+static int synthframes(const std::string& spec, const std::string& file) {
+    auto r = make_synth_reader(spec);
+    std::vector<uint8_t> px(r->image_shape()[0] * r->image_shape()[1] * r->get_element_size());
+    std::ofstream o(file, std::ios::binary);
+    for (size_t i = 0; i < r->get_number_of_images(); ++i) {
+        if (r->get_raw_chunk(i, px).size() != px.size()) return fail("synthframes: short frame");
+        o.write(reinterpret_cast<const char*>(px.data()), (std::streamsize)px.size());
+    }
+    return o ? 0 : fail("synthframes: cannot write the file");
+}
+
 // chunkfnv <chunk file> <nelem> <elem bytes>: decode one bitshuffle-LZ4 chunk with the host codec and
 // print the FNV-1a of the pixels (cross-check for chunk writers)
 static int chunkfnv(const std::string& path, size_t nelem, size_t es) {
@@ -230,6 +274,10 @@ int main(int argc, char** argv) {
         if (cmd == "synthinfo" && argc == 3) return synthinfo(argv[2]);
         if (cmd == "chunkfnv" && argc == 5)
             return chunkfnv(argv[2], std::strtoull(argv[3], nullptr, 10), std::strtoull(argv[4], nullptr, 10));
+        if (cmd == "jfcal" && argc == 4) return jfcal(argv[2], argv[3]);
+        if (cmd == "jfconvert" && argc == 7)
+            return jfconvert(argv[2], argv[3], std::strtoull(argv[4], nullptr, 10), std::strtoull(argv[5], nullptr, 10), argv[6]);
+        if (cmd == "synthframes" && argc == 4) return synthframes(argv[2], argv[3]);
         if (cmd == "h5stats" && argc == 4) { h5_print_group_stats(argv[2], argv[3]); return 0; }
         if (cmd == "h5support") { std::printf("%d\n", h5_supported() ? 1 : 0); return 0; }
     } catch (const std::exception& e) {
@@ -239,6 +287,7 @@ int main(int argc, char** argv) {
     std::printf("usage: ffs_hosttool selftest | mkshm <synth:spec> <dir> | mkcbf <synth:spec> <prefix> |\n"
                 "       mkh5 <synth:spec> <master.h5> [vds-links|vds-files|plain [frames_per_file [n_written]]] |\n"
                 "       h5info <master.h5> | synthinfo <synth:spec> | h5support | h5stats <file.h5> <group> |\n"
-                "       chunkfnv <chunk> <nelem> <elem bytes>\n");
+                "       chunkfnv <chunk> <nelem> <elem bytes> | jfcal <synth:spec> <file> | jfconvert <raw> <cal> <W> <H> <out> |\n"
+                "       synthframes <synth:spec> <file>\n");
     return 2;
 }

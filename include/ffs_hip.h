@@ -242,6 +242,27 @@ int ffs_ctx_set_gain(ffs_ctx *ctx, double gain);
  *   - a map together with extended_flavour 1, whichever call comes second, as for the scalar. */
 int ffs_ctx_set_gain_map(ffs_ctx *ctx, const float *host_gain);
 
+/* The calibration that turns raw Jungfrau words into photon counts (FFS_CODEC_JUNGFRAU_RAW of ffs_submit_encoded; the rule is stated once,
+ * in csrc/jungfrau_model.hpp, and compiled by the kernel, the driver's host converter and a CPU check).  The reference has no counterpart:
+ * its readers hand over photon counts.
+ *   A raw word r has the gain code g = r >> 14 and adc = r & 0x3FFF; the stage is s = 0, 1, 2 for g = 0, 1, 3.
+ *   pedestal[s], factor[s]: W*H float32 each, row-major, dense; copied before the call returns.  The factor is photons per ADU,
+ *   1 / (gain_s x photon energy), negative for the inverted stages; 0 marks "no calibration for this pixel in this stage".
+ *   The pixel is 0xFFFFFFFF (invalid) when g == 2, r == 0xFFFF, r == 0xC000 (stage G2 with ADC 0: saturated) or factor[s][k] == 0.
+ *   Otherwise d = (float)adc - pedestal[s][k], v = d * factor[s][k] (two float32 operations, never fused), q = rintf(v) with ties to
+ *   even, and the pixel is 0 for q <= 0, 16777215 for q >= 16777215, (uint32_t)q otherwise.  Bit for bit on the GPU and the host.
+ *   An invalid pixel is >= 2^24 and so left out of every window, the radial profile, the pixel statistics, the blur and the spot
+ *   backgrounds, as any such 32-bit pixel is; with max_valid <= 2^24 - 1 it is never strong as a centre either.  Without a max_valid
+ *   it is compared as a centre like any value and comes out strong: set max_valid (the driver does).
+ * cal == NULL drops the calibration.  A property of the context like the mask: kept across ffs_ctx_set_params, replaceable between
+ * batches (pedestals drift).  FFS_ERR_INVALID, state unchanged (ffs_last_error has the text):
+ *   - a context of pixel_bytes 2, or a NULL plane;
+ *   - an entry that is not finite, a pedestal outside [-65536, 65536], a factor that is neither 0 nor of magnitude in [2^-30, 2^16]:
+ *     the text names the plane and the index of the first one;
+ *   - a calibration (or NULL) while any stream of the context has a batch between submit and ffs_wait. */
+typedef struct { const float *pedestal[3]; const float *factor[3]; } ffs_jungfrau_calibration;
+int ffs_ctx_set_jungfrau_calibration(ffs_ctx *ctx, const ffs_jungfrau_calibration *cal);
+
 /* The per-frame radial profile: per frame and bin of a caller-defined bin map (resolution shells, usually), how many pixels count, their
  * sum and their sum of squares -- the background level and its dispersion per shell, what DIALS builds its radial_profile threshold, its
  * ice-ring filter and its per-image analysis on.  The reference reports nothing of the kind (its per-image output is the strong mask and
@@ -485,9 +506,17 @@ int ffs_decode_only(ffs_stream *s, const void *const *chunks, const size_t *chun
  * frame (spotfinder.cc:846-862).  Placement as for ffs_submit_compressed (anywhere, or all of them inside the stream's host
  * buffer).  A chunk shorter than width*height bytes cannot hold a frame and is refused here (FFS_ERR_INVALID, "byte-offset ...");
  * a chunk that ends before its last element is reported by ffs_wait / ffs_decode_only_encoded (FFS_ERR_INVALID, "corrupt
- * byte-offset chunk"), its missing pixels are zeros.  Any other codec: FFS_ERR_INVALID. */
+ * byte-offset chunk"), its missing pixels are zeros.
+ * FFS_CODEC_JUNGFRAU_RAW: frames as a Jungfrau delivers them.  chunks[i] is exactly width*height 16-bit little-endian words, dense and
+ * row-major -- two bits of gain stage, 14 bits of ADC -- and is converted on the GPU into 32-bit photon counts with the context's
+ * calibration (ffs_ctx_set_jungfrau_calibration, which has the rule): 2 bytes a pixel cross PCIe instead of the 4 of a frame converted
+ * on the host.  One launch per batch of up to 64 frames.  Placement as for ffs_submit_compressed.  Refused here (FFS_ERR_INVALID, each
+ * with a text of its own, state unchanged): a chunk of any other size; a context of pixel_bytes 2; a context without a calibration; a
+ * chunk that lies in the stream's host buffer at an offset that is not a multiple of 16 (the words are loaded 16 bytes at a time).
+ * Any other codec: FFS_ERR_INVALID. */
 #define FFS_CODEC_BSLZ4 0        /* what ffs_submit_compressed / ffs_decode_only take */
 #define FFS_CODEC_BYTE_OFFSET 1  /* CBF byte-offset, cbfread.hpp:49-106; chunk = bytes after the binary marker */
+#define FFS_CODEC_JUNGFRAU_RAW 2 /* raw Jungfrau words (gain stage << 14 | ADC); chunk = width*height*2 bytes */
 int ffs_submit_encoded(ffs_stream *s, int codec, const void *const *chunks, const size_t *chunk_bytes,
                        uint32_t n_frames, int64_t first_frame_id);
 /* ffs_decode_only for any codec (byte-offset: the three decode launches of kernels_byteoffset.hpp are timed together) --

@@ -60,6 +60,21 @@ int ffs_synth_mask_rect(uint8_t *mask, uint32_t width, uint32_t height, uint32_t
  * Eiger-2XE-16M shaped (4148 x 4362), written as pixel_bytes-wide pixels. */
 int ffs_synth_reference_sample(uint32_t n, int32_t pixel_bytes, void *out);
 
+/* A Jungfrau calibration as a pure function of (pixel, seed), for raw-word sources (ffs_ctx_set_jungfrau_calibration of ffs_hip.h has the
+ * conversion): six planes of width*height float32, pedestal G0, G1, G2 then factor G0, G1, G2 -- the layout of the driver's
+ * --jungfrau-calibration file.  Pedestals are multiples of 1/2 ADU near 2900 / 14700 / 15400; the factors are those of 480-543 ADU per
+ * photon in G0, 17-17.75 in G1 and 1.25-1.44 in G2 (both inverted: negative factors); about one pixel in 500 has factor 0, "no
+ * calibration", in one stage.  Only IEEE division and exact sums: the same bytes on every host. */
+int ffs_synth_jungfrau_calibration(uint32_t width, uint32_t height, uint64_t seed, float *planes);
+
+/* Photon counts (width*height uint32) as the raw 16-bit words of a Jungfrau (gain code << 14 | ADC) under `planes` (as above).  The stage
+ * goes by magnitude: G0 below 24 photons, G1 below 800, G2 above; ADC = rint(pedestal + photons / factor), so the conversion gives the
+ * photons back to within the ADC's resolution.  A count that drives G2's ADC to 0 or below comes out as the saturated word 0xC000; a
+ * pixel without calibration in its stage keeps its stage and is invalid by its factor; and about one word in 4096 each is 0xFFFF,
+ * carries the gain code 2, or is 0xC000, as a pure function of (seed, frame, pixel). */
+int ffs_synth_jungfrau_encode(const uint32_t *photons, uint32_t width, uint32_t height, const float *planes, uint64_t seed,
+                              uint32_t frame, uint16_t *raw);
+
 #ifdef __cplusplus
 }
 #endif
