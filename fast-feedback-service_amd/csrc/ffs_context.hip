@@ -312,6 +312,7 @@ static void ctx_destroy_internal(ffs_ctx* c) {
     if (c->d_maskbits) (void)hipFree(c->d_maskbits);
     if (c->d_gain_map) (void)hipFree(c->d_gain_map);
     if (c->d_jf_cal) (void)hipFree(c->d_jf_cal);
+    jfped_free_ctx(c);
     if (c->d_radial_map) (void)hipFree(c->d_radial_map);
     if (c->stats_st) {   // (the streams are closed: nothing new comes, what is there is let finish)
         (void)hipStreamSynchronize(c->stats_st);
@@ -725,6 +726,7 @@ void stream_destroy_internal(ffs_stream* s) {
     radial_free(s);
     radthr_free(s);
     spotbg_free(s);
+    jfped_free_stream(s);
     encoded_free(s);
     if (s->ev_stats) (void)hipEventDestroy(s->ev_stats);   // (the sparse stream, synchronised above, waited for it)
     // (d_n_comp, d_summary and d_overflow live inside the d_num_strong allocation)

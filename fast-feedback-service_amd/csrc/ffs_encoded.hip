@@ -3,11 +3,13 @@
 // pitched device image, which enqueue_batch (ffs_submit.hip) then takes like any other.  The decoders' kernels are included here and nowhere
 // else.  What is decided about a batch -- may a chunk be a frame, where do the chunks lie, which bytes are copied, the tables the kernels
 // read -- is encoded_plan.hpp's, without HIP; this unit allocates, copies, records and launches.  The codec is looked at by prepare and
-// launch (and the chunk check) only.
+// launch (and the chunk check) only.  The dark-frame fold of raw Jungfrau words (kernels_jfped.hpp; at the end of this file, from begin to
+// end) reuses the chunk placement and the upload.
 #include "ffs_internal.hpp"
 #include "kernels_decode.hpp"
 #include "kernels_byteoffset.hpp"
 #include "kernels_jungfrau.hpp"
+#include "kernels_jfped.hpp"
 
 static_assert(sizeof(BlockEntry) == sizeof(uint2), "DecodeArgs::table reads the block table as uint2");
 
@@ -75,7 +77,8 @@ static int prepare_byte_offset(ffs_stream* s, EncodedBatch& b) {
 
 // Caller's thread: checks the chunks, places them in the pinned staging buffer (unless they already are there), starts their copy to the
 // device and records ev[6] behind it.  A failure leaves no copy reading memory the caller gets back.
-static int prepare(ffs_stream* s, int codec, const void* const* chunks, const size_t* chunk_bytes, uint32_t n, EncodedBatch& b) {
+// fold: the caller is the dark-frame fold (its name, for the texts), which converts nothing and needs no calibration; else null.
+static int prepare(ffs_stream* s, int codec, const void* const* chunks, const size_t* chunk_bytes, uint32_t n, EncodedBatch& b, const char* fold = nullptr) {
     ffs_ctx* c = s->ctx;
     EncodedState& E = s->enc;
     const size_t W = (size_t)c->L.W, H = (size_t)c->L.H, es = (size_t)c->pixel_bytes;
@@ -93,10 +96,10 @@ static int prepare(ffs_stream* s, int codec, const void* const* chunks, const si
     if (!place_chunks(chunks, chunk_bytes, n, s->h_img, s->h_img_bytes, b.base, pl))
         return refuse(c->err, FFS_ERR_INVALID, "ffs_submit_compressed: either all chunks lie in the stream's host buffer or none");
     if (jungfrau) {   // (no table: the conversion reads the context's calibration and the chunks where they lie)
-        if (!c->has_jf_cal)
+        if (!fold && !c->has_jf_cal)
             return refuse(c->err, FFS_ERR_INVALID, "ffs_submit_encoded: raw Jungfrau words need a calibration and the context has none (ffs_ctx_set_jungfrau_calibration)");
         if (const uint32_t f = first_unaligned_base(b.base.data(), n); f < n)
-            return refuse(c->err, FFS_ERR_INVALID, "ffs_submit_encoded: raw Jungfrau chunk " + std::to_string(f) + " lies in the stream's host buffer at offset "
+            return refuse(c->err, FFS_ERR_INVALID, std::string(fold ? fold : "ffs_submit_encoded") + ": raw Jungfrau chunk " + std::to_string(f) + " lies in the stream's host buffer at offset "
                                                        + std::to_string(b.base[f]) + ", which is not a multiple of 16");
     }
     if (!pl.in_place) {
@@ -302,4 +305,179 @@ extern "C" int ffs_submit_compressed(ffs_stream* s, const void* const* chunks, c
 extern "C" int ffs_submit_encoded(ffs_stream* s, int codec, const void* const* chunks, const size_t* chunk_bytes, uint32_t n_frames, int64_t first_frame_id) {
     if (!s || !stream_handle_ok(s)) return FFS_ERR_INVALID;
     return guarded(s->ctx, [&] { return ffs_submit_encoded_impl(s, codec, chunks, chunk_bytes, n_frames, first_frame_id); });
+}
+
+// ---- Jungfrau pedestals: dark frames folded into the context's accumulators (kernels_jfped.hpp) ------------------------
+// The accumulators are one allocation of nine dense planes: count[3] (uint32), then sum[3], then sum_sq[3] (uint64), jfped_stride entries each.
+static size_t jfped_bytes(size_t stride) { return stride * 3 * (sizeof(uint32_t) + 2 * sizeof(uint64_t)); }
+static uint32_t* jfped_count(const ffs_ctx* c) { return reinterpret_cast<uint32_t*>(c->d_jfped); }
+static uint64_t* jfped_sum(const ffs_ctx* c) { return reinterpret_cast<uint64_t*>(c->d_jfped + c->jfped_stride * 3 * sizeof(uint32_t)); }
+static uint64_t* jfped_sum_sq(const ffs_ctx* c) { return jfped_sum(c) + c->jfped_stride * 3; }
+
+void jfped_free_stream(ffs_stream* s) {
+    for (hipEvent_t& e : s->jfped_ev) {
+        if (e) (void)hipEventDestroy(e);
+        e = nullptr;
+    }
+}
+void jfped_free_ctx(ffs_ctx* c) {
+    if (c->jfped_st) {
+        (void)hipStreamSynchronize(c->jfped_st);
+        (void)hipStreamDestroy(c->jfped_st);
+        c->jfped_st = nullptr;
+    }
+    if (c->d_jfped) (void)hipFree(c->d_jfped);
+    c->d_jfped = nullptr;
+}
+
+static int jfped_begin_impl(ffs_ctx* c) {
+    if (c->pixel_bytes != 4)
+        return refuse(c->err, FFS_ERR_INVALID, "ffs_ctx_jungfrau_pedestal_begin: raw Jungfrau words belong to contexts of 32-bit photon counts: the context must have pixel_bytes 4");
+    if (c->inflight.load() > 0)
+        return refuse(c->err, FFS_ERR_INVALID, "ffs_ctx_jungfrau_pedestal_begin: a batch or a fold of this context is in flight (wait for it first): a begin zeroes the accumulators");
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (!c->jfped_st) HIP_TRY(c, hipStreamCreateWithFlags(&c->jfped_st, hipStreamNonBlocking));
+    if (!c->d_jfped) {
+        const size_t stride = ((size_t)c->L.W * c->L.H + kJfPedLanePixels - 1) / kJfPedLanePixels * kJfPedLanePixels;
+        uint8_t* d = nullptr;
+        if (dmalloc(&d, jfped_bytes(stride)) != hipSuccess) {
+            (void)hipGetLastError();
+            return refuse(c->err, FFS_ERR_NOMEM, "ffs_ctx_jungfrau_pedestal_begin: hipMalloc(accumulators, " + std::to_string(jfped_bytes(stride) >> 20) + " MB) failed");
+        }
+        c->d_jfped = d;
+        c->jfped_stride = stride;
+    }
+    HIP_TRY(c, hipMemsetAsync(c->d_jfped, 0, jfped_bytes(c->jfped_stride), c->jfped_st));
+    HIP_TRY(c, hipStreamSynchronize(c->jfped_st));
+    std::lock_guard<std::mutex> lock(c->jfped_mu);
+    c->jfped_frames = 0;
+    return FFS_OK;
+}
+extern "C" int ffs_ctx_jungfrau_pedestal_begin(ffs_ctx* c) {
+    if (!c) return FFS_ERR_INVALID;
+    return guarded(c, [&] { return jfped_begin_impl(c); });
+}
+
+extern "C" int ffs_ctx_jungfrau_pedestal_end(ffs_ctx* c) {
+    if (!c) return FFS_ERR_INVALID;
+    if (!c->d_jfped) return FFS_OK;
+    if (c->inflight.load() > 0)
+        return refuse(c->err, FFS_ERR_INVALID, "ffs_ctx_jungfrau_pedestal_end: a batch or a fold of this context is in flight (wait for it first)");
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipStreamSynchronize(c->jfped_st));
+    (void)hipFree(c->d_jfped);
+    c->d_jfped = nullptr;
+    return FFS_OK;
+}
+
+// A fold counts among the context's batches in flight from its first device call to its return -- begin, get, end and a calibration change see
+// it there -- on every way out.  The stream itself is not marked busy: the fold is synchronous on the thread that drives the stream, and its
+// host buffer may still grow for the chunks (ensure_host_staging).
+namespace {
+struct FoldInFlight {
+    ffs_ctx* c;
+    explicit FoldInFlight(ffs_ctx* c_) : c(c_) { ++c->inflight; }
+    ~FoldInFlight() { --c->inflight; }
+};
+}  // namespace
+
+static int jfped_fold_impl(ffs_stream* s, const void* const* chunks, const size_t* chunk_bytes, uint32_t n, float* ms_fold) {
+    static const char* const who = "ffs_stream_jungfrau_pedestal_fold";
+    ffs_ctx* c = s->ctx;
+    if (!chunks || !chunk_bytes) return refuse(c->err, FFS_ERR_INVALID, std::string(who) + ": chunks or chunk_bytes is NULL");
+    if (!c->d_jfped)
+        return refuse(c->err, FFS_ERR_INVALID, std::string(who) + ": the context has no accumulators (ffs_ctx_jungfrau_pedestal_begin first; ffs_ctx_jungfrau_pedestal_end frees them)");
+    if (s->busy) return refuse(c->err, FFS_ERR_INVALID, std::string(who) + ": the stream has a batch in flight: call ffs_wait() first");
+    if (n == 0 || n > s->max_batch) return refuse(c->err, FFS_ERR_INVALID, std::string(who) + ": n_frames must be in 1..max_batch (" + std::to_string(s->max_batch) + "), got " + std::to_string(n));
+    const size_t frame_bytes = (size_t)c->L.W * c->L.H * 2;
+    for (uint32_t f = 0; f < n; ++f)
+        if (!chunks[f] || chunk_bytes[f] != frame_bytes)
+            return refuse(c->err, FFS_ERR_INVALID, std::string(who) + ": chunk " + std::to_string(f) + (chunks[f] ? " of " + std::to_string(chunk_bytes[f]) + " bytes" : std::string(" (NULL)"))
+                                                       + " is not a dark frame of " + std::to_string((size_t)c->L.W * c->L.H) + " 16-bit words (" + std::to_string(frame_bytes) + " bytes)");
+    auto too_many = [&] {
+        return refuse(c->err, FFS_ERR_INVALID, std::string(who) + ": " + std::to_string(n) + " more frames would take n_frames past 2^32 - 1 (the counts are 32 bits)");
+    };
+    {
+        std::lock_guard<std::mutex> lock(c->jfped_mu);
+        if (!jf_pedestal_frames_fit(c->jfped_frames, n)) return too_many();
+    }
+    HIP_TRY(c, hipSetDevice(c->device));
+    for (hipEvent_t& e : s->jfped_ev)
+        if (!e) HIP_TRY(c, hipEventCreate(&e));
+    FoldInFlight in_flight(c);
+    EncodedBatch b;
+    FFS_TRY(prepare(s, FFS_CODEC_JUNGFRAU_RAW, chunks, chunk_bytes, n, b, who));
+    // from here on the chunks' copy reads memory the caller gets back: every way out waits for it
+    const uint32_t n_px = (uint32_t)c->L.W * (uint32_t)c->L.H, groups = (n_px + kJfPedLanePixels - 1) / kJfPedLanePixels;
+    const dim3 grid((groups + kJfPedBlock - 1) / kJfPedBlock);
+    hipError_t e = hipSuccess;
+    bool fits = true;
+    {
+        std::lock_guard<std::mutex> lock(c->jfped_mu);
+        fits = jf_pedestal_frames_fit(c->jfped_frames, n);   // (another stream's fold may have come in between)
+        if (fits) e = hipStreamWaitEvent(c->jfped_st, s->ev[6], 0);
+        for (uint32_t f0 = 0; fits && e == hipSuccess && f0 < n; f0 += kJfPedMaxLaunch) {
+            JfPedArgs a{.comp = s->enc.d_comp, .count = jfped_count(c), .sum = jfped_sum(c), .sum_sq = jfped_sum_sq(c), .plane_stride = c->jfped_stride,
+                        .n_px = n_px, .n_frames = std::min(n - f0, kJfPedMaxLaunch), .base = {}};
+            for (uint32_t f = 0; f < a.n_frames; ++f) a.base[f] = (uint32_t)b.base[f0 + f];
+            const bool first = f0 == 0, last = n - f0 <= kJfPedMaxLaunch;
+            hipExtLaunchKernelGGL(k_jungfrau_pedestal_fold, grid, dim3(kJfPedBlock), 0, c->jfped_st, first ? s->jfped_ev[0] : nullptr, last ? s->jfped_ev[1] : nullptr, 0, a);
+            e = hipGetLastError();
+        }
+        // (a launch that failed half way through a long batch leaves the accumulators undefined, like a failed ffs_wait the pixel statistics)
+        if (fits && e == hipSuccess) c->jfped_frames += n;
+    }
+    if (!fits || e != hipSuccess) {
+        (void)hipStreamSynchronize(s->st_up);
+        (void)hipStreamSynchronize(c->jfped_st);
+        if (!fits) return too_many();
+        return refuse(c->err, FFS_ERR_DEVICE, std::string(who) + ": " + hipGetErrorString(e));
+    }
+    HIP_TRY(c, hipEventSynchronize(s->jfped_ev[1]));   // (the launch waited for the chunks: the host buffer is free as well)
+    if (ms_fold) HIP_TRY(c, hipEventElapsedTime(ms_fold, s->jfped_ev[0], s->jfped_ev[1]));
+    return FFS_OK;
+}
+extern "C" int ffs_stream_jungfrau_pedestal_fold(ffs_stream* s, const void* const* chunks, const size_t* chunk_bytes, uint32_t n_frames, float* ms_fold) {
+    if (!s || !stream_handle_ok(s)) return FFS_ERR_INVALID;
+    return guarded(s->ctx, [&] { return jfped_fold_impl(s, chunks, chunk_bytes, n_frames, ms_fold); });
+}
+
+// Everything is checked before anything is copied; the planes are dense on the device as the caller reads them: nine plain copies.
+static int jfped_get_impl(ffs_ctx* c, ffs_jungfrau_pedestal_stats* out) {
+    if (!c->d_jfped)
+        return refuse(c->err, FFS_ERR_INVALID, "ffs_ctx_get_jungfrau_pedestal: the context has no accumulators (ffs_ctx_jungfrau_pedestal_begin first; ffs_ctx_jungfrau_pedestal_end frees them)");
+    if (c->inflight.load() > 0)
+        return refuse(c->err, FFS_ERR_INVALID, "ffs_ctx_get_jungfrau_pedestal: a batch or a fold of this context is in flight (wait for it first)");
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipStreamSynchronize(c->jfped_st));
+    const size_t n = (size_t)c->L.W * c->L.H, stride = c->jfped_stride;
+    for (size_t st = 0; st < 3; ++st) {
+        if (out->count[st]) HIP_TRY(c, hipMemcpy(out->count[st], jfped_count(c) + st * stride, n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        if (out->sum[st]) HIP_TRY(c, hipMemcpy(out->sum[st], jfped_sum(c) + st * stride, n * sizeof(uint64_t), hipMemcpyDeviceToHost));
+        if (out->sum_sq[st]) HIP_TRY(c, hipMemcpy(out->sum_sq[st], jfped_sum_sq(c) + st * stride, n * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    }
+    std::lock_guard<std::mutex> lock(c->jfped_mu);
+    out->n_frames = c->jfped_frames;
+    return FFS_OK;
+}
+extern "C" int ffs_ctx_get_jungfrau_pedestal(ffs_ctx* c, ffs_jungfrau_pedestal_stats* out) {
+    if (!c) return FFS_ERR_INVALID;
+    if (!out) return refuse(c->err, FFS_ERR_INVALID, "ffs_ctx_get_jungfrau_pedestal: out is NULL");
+    return guarded(c, [&] { return jfped_get_impl(c, out); });
+}
+
+// The planes rule on the host (jungfrau_pedestal_model.hpp): no context, no GPU; its texts go where ffs_last_error(NULL) reads them
+extern "C" int ffs_jungfrau_pedestal_planes(const ffs_jungfrau_pedestal_stats* stats, size_t n_px, uint32_t min_frames, float max_rms, float* const pedestal[3],
+                                            float* const rms[3], uint8_t* const ok[3]) {
+    static const char* const who = "ffs_jungfrau_pedestal_planes: ";
+    if (!stats || !pedestal || !rms || !ok) return refuse(g_create_error, FFS_ERR_INVALID, std::string(who) + "stats, pedestal, rms or ok is NULL");
+    for (int st = 0; st < 3; ++st)
+        if (!stats->count[st] || !stats->sum[st] || !stats->sum_sq[st])
+            return refuse(g_create_error, FFS_ERR_INVALID, std::string(who) + "a count, sum or sum_sq plane of stage " + std::to_string(st) + " is NULL");
+    if (min_frames == 0) return refuse(g_create_error, FFS_ERR_INVALID, std::string(who) + "min_frames must be at least 1");
+    if (!jf_pedestal_args_ok(min_frames, max_rms))
+        return refuse(g_create_error, FFS_ERR_INVALID, std::string(who) + "max_rms must be finite and >= 0 (0: no noise test), got " + std::to_string(max_rms));
+    for (int st = 0; st < 3; ++st)
+        jf_pedestal_plane(stats->count[st], stats->sum[st], stats->sum_sq[st], n_px, min_frames, max_rms, pedestal[st], rms[st], ok[st]);
+    return FFS_OK;
 }

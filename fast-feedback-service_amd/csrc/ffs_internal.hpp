@@ -29,6 +29,9 @@
 //   jungfrau_model.hpp   raw Jungfrau words to photon counts (ffs_ctx_set_jungfrau_calibration, FFS_CODEC_JUNGFRAU_RAW): stage, invalid words, the
 //                        two float32 operations, rounding and clamp; the setter's ranges (kernels_jungfrau.hpp, included by ffs_encoded.hip;
 //                        host/codecs.hpp; tests/jungfrau_check.cc)
+//   jungfrau_pedestal_model.hpp  pedestals from dark frames (ffs_stream_jungfrau_pedestal_fold, ffs_jungfrau_pedestal_planes): which words count
+//                        where, accumulators to pedestal / rms / ok planes, the re-pedestalled calibration (kernels_jfped.hpp, included by
+//                        ffs_encoded.hip, which owns the fold from begin to end; host/codecs.hpp; tools/ffs_hosttool.cc; tests/jungfrau_pedestal_check.cc)
 // No exception leaves the library (guarded()).
 #pragma once
 #include <algorithm>
@@ -169,6 +172,16 @@ struct ffs_ctx {
     float* d_jf_cal = nullptr;
     size_t jf_plane_stride = 0;
     bool has_jf_cal = false;
+    // ffs_ctx_jungfrau_pedestal_begin: the accumulators of the dark-frame fold, one allocation made at the first begin and
+    // freed by _end or with the context: count[3] (uint32), sum[3], sum_sq[3] (uint64), dense planes jfped_stride entries apart (W * H rounded
+    // up to 8: the kernel's last group stays inside them).  Null: not begun.  jfped_st: the context's own HIP stream, in which the fold
+    // launches follow one another -- every launch reads, adds and writes the accumulators, two must never overlap; jfped_mu makes "wait for
+    // the chunks, launch, count the frames" one step (folds come from distinct ffs_streams on distinct threads).
+    uint8_t* d_jfped = nullptr;
+    size_t jfped_stride = 0;
+    uint64_t jfped_frames = 0;
+    hipStream_t jfped_st = nullptr;
+    std::mutex jfped_mu;
     // ffs_ctx_set_radial_bins: [H][pitch_px] uint16 bin entries, allocated at the first set and kept (entries beyond W
     // are 0xFFFF); radial_bins says whether a map is in force and how many bins it has (0 = none).  Like the gain map it cannot change under a batch.
     uint16_t* d_radial_map = nullptr;
@@ -362,6 +375,9 @@ struct ffs_stream {
     // the batch's sparse stream, which waits for ev_stats (recorded behind it, made on first use) ahead of the batch's last event.
     bool stats_todo = false, stats_join = false;
     hipEvent_t ev_stats = nullptr;
+    // ffs_stream_jungfrau_pedestal_fold: the two events around the stream's fold launches (its own, made on first use: the batch's events keep
+    // the last batch's stage times)
+    hipEvent_t jfped_ev[2] = {nullptr, nullptr};
     // The per-spot backgrounds (ffs_spotbg.hip, kernels_spotbg.hpp), all made by the first ffs_stream_spot_backgrounds
     // on the stream: a non-blocking HIP stream of the ffs_stream's own with two events around its launch, the boxes of the last batch's
     // reflections (pinned host, written by the call, and their copy on the device) and the records the kernel writes straight into pinned host
@@ -585,6 +601,8 @@ int join_pixel_stats(ffs_stream* s);
 // ffs_encoded.hip
 const char* encoded_corruption(uint32_t overflow);   // the text for a status word in which a decode kernel flagged a corrupt chunk, else null
 void encoded_free(ffs_stream* s);
+void jfped_free_stream(ffs_stream* s);   // the stream's fold events, if it ever folded
+void jfped_free_ctx(ffs_ctx* c);         // the accumulators and the context's fold stream (context destroy; every stream is closed)
 // ffs_wait.hip
 int ffs_wait_impl(ffs_stream* s, const ffs_frame_result** results, uint32_t* n_results);
 void ahead_register(ffs_stream* s);   // the batch just enqueued may be assembled ahead of its ffs_wait

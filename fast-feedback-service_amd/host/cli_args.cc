@@ -23,7 +23,7 @@ void usage() {
       "                  [-h5] [--output-for-index] [--batch N] [--cpu-decode] [--strict-dtype]\n"
       "                  [--max-valid trusted|none|N] [--max-valid-scope centre|window] [--min-count N] [--kernel-size N | NX,NY]\n"
       "                  [--gain G] [--gain-map FILE] [--radial-bins N] [--pixel-stats PREFIX]\n"
-      "                  [--jungfrau-calibration FILE]\n"
+      "                  [--jungfrau-calibration FILE] [--jungfrau-pedestal PREFIX [--pedestal-min-frames N] [--pedestal-max-rms R]]\n"
       "                  [--spot-background B]\n"
       "                  [--n-iqr X] [--radial-blur narrow|wide]\n"
       "                  [--devices D0,D1,... | --gpus N] [--no-numa-pinning] [--single-buffer] [--all-threads] [--read-only] [--clean-exit]\n"
@@ -50,6 +50,15 @@ void usage() {
       "              calibration for that pixel in that stage).  On the GPU (2 bytes a pixel cross PCIe), or with --cpu-decode on the worker\n"
       "              thread by the same rule.  Saturated and uncalibrated pixels are masked for their frame; --max-valid trusted becomes\n"
       "              min(trusted maximum, 2^24 - 1).  Needs a source of uncompressed 16-bit frames\n"
+      "--jungfrau-pedestal: the frames are a DARK run of raw Jungfrau words (the detector in G0, then forced into G1, then into G2, in any\n"
+      "              order: the word decides the stage).  Every frame is folded into per-pixel, per-stage accumulators -- on the GPU, or with\n"
+      "              --cpu-decode on the worker threads by the same rule -- and no spots are found: one summary line, no JSON lines.  Written:\n"
+      "              PREFIX.count.u32, PREFIX.sum.u64, PREFIX.sum_sq.u64 (the accumulators), PREFIX.pedestal.f32, PREFIX.rms.f32, PREFIX.ok.u8\n"
+      "              (mean and noise of the ADC per stage, and whether the stage's pedestal is usable), three planes of width x height values\n"
+      "              each (G0, G1, G2), raw little-endian; with --jungfrau-calibration OLD also PREFIX.calibration.f32, OLD with the pedestals\n"
+      "              replaced and the factor set to 0 (no calibration) where the pedestal is not usable.  --pedestal-min-frames N (default 1):\n"
+      "              usable from N counted frames on; --pedestal-max-rms R (default 0: no test): ... and with a noise of at most R ADU.  One\n"
+      "              GPU; not with --validate or --writeout; needs a source of uncompressed 16-bit frames\n"
       "--radial-bins: per image, the count, sum and sum of squares of the valid pixels in each of N (1..1024) resolution shells of equal\n"
       "              width in 1/d^2, from the beam centre to the furthest pixel: the background level and its dispersion per shell, as\n"
       "              \"radial_count\", \"radial_sum\" and \"radial_sum_sq\" arrays in every image's JSON line (pixels above --max-valid and\n"
@@ -95,7 +104,7 @@ void usage() {
       "--cpu-decode: decompress the frames' chunks (bitshuffle-LZ4, CBF byte-offset) on the worker thread (the reference's way) instead\n"
       "              of sending them to the GPU as they are\n"
       "FILE: NXmx .nxs/.h5 (needs an HDF5 build), a /dev/shm directory, a ####.cbf template, or\n"
-      "      synth:<eiger16m|jungfrau9m|jungfrau9mraw|plumbing1k|sweep16m|tiny|tinyraw|tinysweep>[:n_images[:seed]]\n");
+      "      synth:<eiger16m|jungfrau9m|jungfrau9mraw|jungfrau9mdark|plumbing1k|sweep16m|tiny|tinyraw|tinydark|tinysweep>[:n_images[:seed]]\n");
 }
 
 [[noreturn]] void arg_error(const std::string& m) {  // arg_parser.cc:72-77
@@ -214,6 +223,21 @@ Args parse_args(int argc, char** argv) {
             r.gain_map = need(i, s);
             if (r.gain_map.empty() || !fs::is_regular_file(r.gain_map)) arg_error("--gain-map: no such file: " + r.gain_map);
         }
+        else if (s == "--jungfrau-pedestal") {
+            r.jungfrau_pedestal = need(i, s);
+            if (r.jungfrau_pedestal.empty()) arg_error("--jungfrau-pedestal takes the prefix of the files it writes");
+        }
+        else if (s == "--pedestal-min-frames") {
+            r.pedestal_min_frames = u32(need(i, s), s);
+            if (r.pedestal_min_frames < 1) arg_error("--pedestal-min-frames must be at least 1");
+        }
+        else if (s == "--pedestal-max-rms") {
+            const std::string& v = need(i, s);
+            char* end = nullptr;
+            r.pedestal_max_rms = std::strtof(v.c_str(), &end);
+            if (v.empty() || *end || !(r.pedestal_max_rms >= 0.0f && r.pedestal_max_rms <= 3.4028234663852886e38f))
+                arg_error("--pedestal-max-rms takes a finite number >= 0 (0: no noise test): " + v);
+        }
         else if (s == "--pixel-stats") {
             r.pixel_stats = need(i, s);
             if (r.pixel_stats.empty()) arg_error("--pixel-stats takes the prefix of the four files it writes");
@@ -255,6 +279,13 @@ Args parse_args(int argc, char** argv) {
     if (r.sample && !r.file.empty()) arg_error("Argument 'FILE.nxs' not allowed with '--sample'");
     if (!r.sample && r.file.empty() && !implicit_sample) arg_error("One of the arguments '--sample' or 'FILE.nxs' is required");
     if (r.file.empty()) r.sample = true;
+    if (!r.jungfrau_pedestal.empty()) {   // (the mode takes one context and finds no spots)
+        if (r.devices.size() > 1) arg_error("--jungfrau-pedestal takes one GPU: not with --devices / --gpus of more than one");
+        if (r.validate) arg_error("--jungfrau-pedestal finds no spots: not with --validate");
+        if (r.writeout) arg_error("--jungfrau-pedestal finds no spots: not with --writeout");
+    } else if (r.pedestal_min_frames != 1 || r.pedestal_max_rms != 0.0f) {
+        arg_error("--pedestal-min-frames and --pedestal-max-rms belong to --jungfrau-pedestal");
+    }
     if (r.gain > 0.0 && !r.gain_map.empty()) arg_error("--gain and --gain-map exclude each other: a constant map is the scalar gain");
     std::string lower = r.algorithm;   // DispersionAlgorithm, spotfinder.cc:180-203
     std::transform(lower.begin(), lower.end(), lower.begin(), [](unsigned char ch) { return (char)std::tolower(ch); });

@@ -25,6 +25,9 @@ struct Args {
     int max_valid_scope = 0;             // --max-valid-scope centre (FFS_MAX_VALID_CENTRE) | window (FFS_MAX_VALID_WINDOW)
     double gain = 0.0;                   // --gain G (> 0); 0 = not given: pixel values are photon counts
     std::string jungfrau_calibration;    // --jungfrau-calibration FILE (raw float32, 6 x width x height values); empty = not given
+    std::string jungfrau_pedestal;       // --jungfrau-pedestal PREFIX: fold the source's dark frames into pedestal statistics, write PREFIX.*, find no spots; empty = not given
+    uint32_t pedestal_min_frames = 1;    // --pedestal-min-frames N: a stage's pedestal is usable from N counted frames on
+    float pedestal_max_rms = 0.0f;       // --pedestal-max-rms R: ... and with a noise of at most R ADU; 0 = no test
     std::string gain_map;                // --gain-map FILE (raw float32, width x height values); empty = not given.  Not with --gain
     uint32_t radial_bins = 0;            // --radial-bins N (1..1024): the per-image radial profile over N resolution shells; 0 = not given
                                          // (-a radial_profile: its shells, 100 unless given, at most 128)

@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "../csrc/jungfrau_model.hpp"
+#include "../csrc/jungfrau_pedestal_model.hpp"
 
 namespace ffshost {
 
@@ -255,6 +256,33 @@ inline void jungfrau_convert(const uint16_t* raw, size_t n_px, const float* plan
     const float* const pedestal[3] = {planes, planes + n_px, planes + 2 * n_px};
     const float* const factor[3] = {planes + 3 * n_px, planes + 4 * n_px, planes + 5 * n_px};
     ffsamd::jf_convert_frame(raw, n_px, pedestal, factor, out);
+}
+
+// ---- Jungfrau pedestals from dark frames: the rule of csrc/jungfrau_pedestal_model.hpp, the text the GPU kernel and the library compile --
+// Each of count, sum, sum_sq, pedestal, rms, ok: three planes of n_px entries, G0 G1 G2 (the --jungfrau-pedestal files).
+inline void jungfrau_pedestal_fold(const uint16_t* raw, size_t n_px, uint32_t* count, uint64_t* sum, uint64_t* sum_sq) {
+    uint32_t* const c[3] = {count, count + n_px, count + 2 * n_px};
+    uint64_t* const s[3] = {sum, sum + n_px, sum + 2 * n_px};
+    uint64_t* const q[3] = {sum_sq, sum_sq + n_px, sum_sq + 2 * n_px};
+    ffsamd::jf_pedestal_fold_frame(raw, n_px, c, s, q);
+}
+// ... the pixels [lo, hi) of the frame only (worker threads take a slice each)
+inline void jungfrau_pedestal_fold_slice(const uint16_t* raw, size_t n_px, size_t lo, size_t hi, uint32_t* count, uint64_t* sum, uint64_t* sum_sq) {
+    uint32_t* const c[3] = {count + lo, count + n_px + lo, count + 2 * n_px + lo};
+    uint64_t* const s[3] = {sum + lo, sum + n_px + lo, sum + 2 * n_px + lo};
+    uint64_t* const q[3] = {sum_sq + lo, sum_sq + n_px + lo, sum_sq + 2 * n_px + lo};
+    ffsamd::jf_pedestal_fold_frame(raw + lo, hi - lo, c, s, q);
+}
+inline void jungfrau_pedestal_planes(const uint32_t* count, const uint64_t* sum, const uint64_t* sum_sq, size_t n_px, uint32_t min_frames, float max_rms,
+                                     float* pedestal, float* rms, uint8_t* ok) {
+    for (size_t s = 0; s < 3; ++s)
+        ffsamd::jf_pedestal_plane(count + s * n_px, sum + s * n_px, sum_sq + s * n_px, n_px, min_frames, max_rms, pedestal + s * n_px, rms + s * n_px, ok + s * n_px);
+}
+// old, out: six planes (the --jungfrau-calibration file): the pedestals replaced, a factor kept where ok holds and 0 elsewhere
+inline void jungfrau_repedestal(const float* old, size_t n_px, const float* pedestal, const uint8_t* ok, float* out) {
+    const float* const p[3] = {pedestal, pedestal + n_px, pedestal + 2 * n_px};
+    const uint8_t* const k[3] = {ok, ok + n_px, ok + 2 * n_px};
+    ffsamd::jf_repedestal(old, n_px, p, k, out);
 }
 
 }  // namespace ffshost

@@ -315,3 +315,26 @@ int ffs_synth_jungfrau_encode(const uint32_t *photons, uint32_t width, uint32_t 
     }
     return 0;
 }
+
+int ffs_synth_jungfrau_dark(uint32_t width, uint32_t height, const float *planes, uint64_t seed, uint32_t frame, uint32_t n_frames,
+                            uint16_t *raw) {
+    if (!planes || !raw || !width || !height || !n_frames || frame >= n_frames) return -1;
+    const size_t n = (size_t)width * height;
+    static const uint16_t code[3] = {0x0000, 0x4000, 0xC000};
+    const int forced = (int)(3ull * frame / n_frames);
+    for (size_t k = 0; k < n; ++k) {
+        const int stuck = (hash3(seed, 0x535455434BULL, k) & 1023) == 0;
+        const int s = stuck ? 0 : forced;
+        const uint64_t h = hash3(seed ^ 0x4A464441524BULL, frame, k);
+        double adc = floor((double)planes[(size_t)s * n + k]) + (double)(h % 5) - 2.0;
+        if (adc < 0.0) adc = 0.0;
+        if (adc > 16383.0) adc = 16383.0;
+        uint16_t r = (uint16_t)(code[s] | (uint16_t)adc);
+        if (((h >> 8) & 4095) == 0) {
+            const unsigned which = (unsigned)((h >> 20) % 3);
+            r = which == 0 ? 0xFFFF : which == 1 ? (uint16_t)(0x8000 | (r & 0x3FFF)) : 0xC000;
+        }
+        raw[k] = r;
+    }
+    return 0;
+}

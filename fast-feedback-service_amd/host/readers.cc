@@ -32,12 +32,14 @@ class SynthRead : public Reader {
     float osc_width_ = 0.f;
     // jungfrau9mraw, tinyraw: the photon frames (p_, 32-bit) leave as the raw 16-bit words of a Jungfrau under the calibration that is a pure
     // function of (pixel, seed) -- ffs_synth_jungfrau_calibration, what `ffs_hosttool jfcal` writes for --jungfrau-calibration
-    bool raw_words_ = false;
+    // jungfrau9mdark, tinydark: the dark run under the same calibration (ffs_synth_jungfrau_dark: thirds of the n frames in G0, G1, G2) -- what
+    // --jungfrau-pedestal measures the pedestals from
+    bool raw_words_ = false, dark_ = false;
     std::vector<float> jf_planes_;
 
   public:
     explicit SynthRead(const std::string& spec) {
-        // synth:<eiger16m|jungfrau9m|jungfrau9mraw|plumbing1k|sweep16m|tiny|tinyraw|tinysweep>[:n[:seed]]
+        // synth:<eiger16m|jungfrau9m|jungfrau9mraw|jungfrau9mdark|plumbing1k|sweep16m|tiny|tinyraw|tinydark|tinysweep>[:n[:seed]]
         std::vector<std::string> parts;
         std::stringstream ss(spec);
         std::string tok;
@@ -46,6 +48,9 @@ class SynthRead : public Reader {
         if (kind == "jungfrau9mraw" || kind == "tinyraw") {
             raw_words_ = true;
             kind.resize(kind.size() - 3);
+        } else if (kind == "jungfrau9mdark" || kind == "tinydark") {
+            raw_words_ = dark_ = true;
+            kind.resize(kind.size() - 4);
         }
         if (parts.size() > 2 && !parts[2].empty()) n_images_ = std::stoul(parts[2]);
         const uint64_t seed = parts.size() > 3 ? std::stoull(parts[3]) : 0;
@@ -95,6 +100,11 @@ class SynthRead : public Reader {
         const size_t n_px = (size_t)p_.width * p_.height;
         const size_t bytes = n_px * (raw_words_ ? 2 : (size_t)p_.pixel_bytes);
         if (dst.size() < bytes) return {dst.data(), 0};
+        if (dark_) {
+            if (ffs_synth_jungfrau_dark(p_.width, p_.height, jf_planes_.data(), p_.seed, (uint32_t)index, (uint32_t)n_images_, reinterpret_cast<uint16_t*>(dst.data())) != 0)
+                return {dst.data(), 0};
+            return {dst.data(), bytes};
+        }
         if (raw_words_) {
             static thread_local std::vector<uint32_t> photons;   // (reentrant: a frame per calling thread)
             photons.resize(n_px);

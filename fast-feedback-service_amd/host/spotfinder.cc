@@ -30,6 +30,7 @@
 #include "cli_args.hpp"
 #include "ffs_hip.h"
 #include "minijson.hpp"
+#include "pedestal_mode.hpp"
 #include "radial_bins.hpp"
 #include "kabsch_space.hpp"
 #include "png_writer.hpp"
@@ -935,6 +936,8 @@ int main(int argc, char** argv) {
     std::vector<float> jungfrau_planes;   // --jungfrau-calibration: 6 x width x height values; empty: the frames are photon counts
     if (const int rc = open_source_beside_runtime(args, stamp, reader_ptr, gain_map, jungfrau_planes)) return rc;
     Reader& reader = *reader_ptr;
+    // --jungfrau-pedestal: the source is a dark run; it is folded into pedestal statistics and no spots are found (pedestal_mode.cc)
+    if (!args.jungfrau_pedestal.empty()) return run_jungfrau_pedestal(args, reader, jungfrau_planes);
     const bool jungfrau = !jungfrau_planes.empty();
 
     // (raw Jungfrau words are 16 bits in the source and 32-bit photon counts from the conversion on: the flag decides, not the source's type)

@@ -121,6 +121,10 @@ CODEC_JUNGFRAU_RAW = 2  # raw Jungfrau words (uint16 arrays or bytes), converted
 class _JungfrauCalibration(C.Structure):   # ffs_jungfrau_calibration
     _fields_ = [("pedestal", C.c_void_p * 3), ("factor", C.c_void_p * 3)]
 
+
+class _JungfrauPedestalStats(C.Structure):   # ffs_jungfrau_pedestal_stats
+    _fields_ = [("n_frames", C.c_uint64), ("count", C.c_void_p * 3), ("sum", C.c_void_p * 3), ("sum_sq", C.c_void_p * 3)]
+
 # every symbol include/ffs_hip.h declares (tests check the library exports them all)
 EXPORTS = [
     "ffs_default_params", "ffs_device_count", "ffs_device_name", "ffs_device_total_mem",
@@ -137,6 +141,8 @@ EXPORTS = [
     "ffs_stream_spot_backgrounds",
     "ffs_ctx_set_radial_threshold", "ffs_stream_radial_thresholds", "ffs_ctx_set_radial_blur",
     "ffs_ctx_set_jungfrau_calibration",
+    "ffs_ctx_jungfrau_pedestal_begin", "ffs_ctx_jungfrau_pedestal_end", "ffs_stream_jungfrau_pedestal_fold", "ffs_ctx_get_jungfrau_pedestal",
+    "ffs_jungfrau_pedestal_planes",
 ]
 
 _lib = None
@@ -164,6 +170,12 @@ def load_library():
         L.ffs_ctx_set_gain.argtypes = [C.c_void_p, C.c_double]
         L.ffs_ctx_set_gain_map.argtypes = [C.c_void_p, C.c_void_p]
         L.ffs_ctx_set_jungfrau_calibration.argtypes = [C.c_void_p, C.POINTER(_JungfrauCalibration)]
+        L.ffs_ctx_jungfrau_pedestal_begin.argtypes = [C.c_void_p]
+        L.ffs_ctx_jungfrau_pedestal_end.argtypes = [C.c_void_p]
+        L.ffs_stream_jungfrau_pedestal_fold.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.c_uint32, C.POINTER(C.c_float)]
+        L.ffs_ctx_get_jungfrau_pedestal.argtypes = [C.c_void_p, C.POINTER(_JungfrauPedestalStats)]
+        L.ffs_jungfrau_pedestal_planes.argtypes = [C.POINTER(_JungfrauPedestalStats), C.c_size_t, C.c_uint32, C.c_float, C.POINTER(C.c_void_p),
+                                                   C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]
         L.ffs_ctx_set_radial_bins.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
         L.ffs_stream_radial_profile.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(_RadialProfile)]
         L.ffs_bench_radial.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_uint32, C.c_uint32, C.POINTER(C.c_float)]
@@ -422,6 +434,29 @@ class Context:
         self._check(self._lib.ffs_ctx_get_pixel_stats(self._h, C.byref(out)))
         return (int(out.n_frames), arrays.get("count"), arrays.get("sum"), arrays.get("sum_sq"), arrays.get("max"))
 
+    def jungfrau_pedestal_begin(self):
+        """ffs_ctx_jungfrau_pedestal_begin: allocate (first use) and zero the accumulators of the dark-frame fold (60 bytes a pixel) and the
+        frame count.  FfsError, state unchanged: a uint16 context; while a batch or a fold is in flight."""
+        self._check(self._lib.ffs_ctx_jungfrau_pedestal_begin(self._h))
+
+    def jungfrau_pedestal_end(self):
+        """ffs_ctx_jungfrau_pedestal_end: free the accumulators; idempotent.  FfsError while a batch or a fold is in flight."""
+        self._check(self._lib.ffs_ctx_jungfrau_pedestal_end(self._h))
+
+    def jungfrau_pedestal(self, planes=("count", "sum", "sum_sq")):
+        """ffs_ctx_get_jungfrau_pedestal: (n_frames, count uint32, sum uint64, sum_sq uint64), each (3, H, W) for the stages G0, G1, G2, over
+        every frame folded since the last begin (Stream.jungfrau_pedestal_fold); a plane set not named in `planes` is None (and is not
+        copied).  What jungfrau_pedestal_planes takes.  FfsError before begin, after end and while a batch or a fold is in flight."""
+        out = _JungfrauPedestalStats()
+        arrays = {}
+        for name, dt in (("count", np.uint32), ("sum", np.uint64), ("sum_sq", np.uint64)):
+            if name in planes:
+                arrays[name] = np.zeros((3, self.H, self.W), dt)
+                for s in range(3):
+                    getattr(out, name)[s] = arrays[name][s].ctypes.data
+        self._check(self._lib.ffs_ctx_get_jungfrau_pedestal(self._h, C.byref(out)))
+        return (int(out.n_frames), arrays.get("count"), arrays.get("sum"), arrays.get("sum_sq"))
+
     def set_tuning(self, **kw):
         """ffs_ctx_set_tuning: A/B partners, fall-backs and capacities (same results either way); see include/ffs_hip.h."""
         for k, v in kw.items():
@@ -508,6 +543,14 @@ class Stream:
     def process_encoded(self, chunks, codec: int, first_frame_id: int = 0):
         self.submit_encoded(chunks, codec, first_frame_id)
         return self.wait()
+
+    def jungfrau_pedestal_fold(self, chunks, want_ms: bool = False):
+        """ffs_stream_jungfrau_pedestal_fold: dark frames -- H x W raw words each, a uint16 array or W*H*2 bytes -- folded into the context's
+        pedestal accumulators (Context.jungfrau_pedestal_begin first).  Synchronous.  Returns the fold launches' milliseconds with want_ms."""
+        keep, ptrs, sizes = self._chunk_args(chunks)
+        ms = C.c_float()
+        self.ctx._check(self._lib.ffs_stream_jungfrau_pedestal_fold(self._h, ptrs, sizes, len(keep), C.byref(ms) if want_ms else None))
+        return ms.value if want_ms else None
 
     def decode_only(self, chunks, iters: int = 1, want_frames: bool = True, codec: int = CODEC_BSLZ4):
         """GPU decode alone: (average ms per decode -- one launch, byte-offset: its three --, decoded frames or None)."""
@@ -701,6 +744,33 @@ class Stream:
             self.close()
         except Exception:
             pass
+
+
+def jungfrau_pedestal_planes(stats, min_frames: int = 1, max_rms: float = 0.0):
+    """ffs_jungfrau_pedestal_planes: the accumulators of the dark-frame fold -- stats = (count, sum, sum_sq), each (3, ...) of one shape, or the
+    tuple Context.jungfrau_pedestal returns (its n_frames is ignored) -- as (pedestal float32, rms float32, ok bool) of that shape: per stage
+    and pixel the mean and the noise of the ADC in float64, rounded to float32, and ok = count >= min_frames and (max_rms == 0 or rms <=
+    max_rms).  On the host: no context, no GPU.  FfsError: min_frames 0, a negative or non-finite max_rms."""
+    lib = load_library()
+    if len(stats) == 4:
+        stats = stats[1:]
+    count = np.ascontiguousarray(stats[0], np.uint32)
+    total = np.ascontiguousarray(stats[1], np.uint64)
+    total_sq = np.ascontiguousarray(stats[2], np.uint64)
+    if count.ndim < 1 or count.shape[0] != 3 or total.shape != count.shape or total_sq.shape != count.shape:
+        raise ValueError(f"count, sum and sum_sq must share one shape (3, ...), not {count.shape}, {total.shape}, {total_sq.shape}")
+    n_px = count[0].size
+    st = _JungfrauPedestalStats()
+    pedestal, rms, ok = np.zeros(count.shape, np.float32), np.zeros(count.shape, np.float32), np.zeros(count.shape, np.uint8)
+    outs = [(C.c_void_p * 3)() for _ in range(3)]
+    for s in range(3):
+        st.count[s], st.sum[s], st.sum_sq[s] = count[s].ctypes.data, total[s].ctypes.data, total_sq[s].ctypes.data
+        for o, a in zip(outs, (pedestal, rms, ok)):
+            o[s] = a[s].ctypes.data
+    rc = lib.ffs_jungfrau_pedestal_planes(C.byref(st), n_px, min_frames, max_rms, *outs)
+    if rc != 0:
+        raise FfsError(rc, lib.ffs_last_error(None).decode())
+    return pedestal, rms, ok.astype(bool)
 
 
 def spot_intensities(reflections: np.ndarray, backgrounds: np.ndarray):

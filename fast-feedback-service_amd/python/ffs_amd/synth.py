@@ -170,3 +170,21 @@ def raw_frames(p: SynthParams, indices) -> np.ndarray:
     assert p.pixel_bytes == 4
     ped, fac = jungfrau_calibration(p.width, p.height, p.seed)
     return np.stack([jungfrau_encode(frame(p, i), ped, fac, p.seed, i) for i in indices])
+
+
+def jungfrau_dark(width, height, pedestal, seed, frame, n_frames):
+    """ffs_synth_jungfrau_dark: frame `frame` of a dark run of n_frames (thirds in G0, G1, G2) as raw uint16 words (H, W) around the
+    pedestals (3, H, W): ADC = floor(pedestal) + (-2 .. 2), a few invalid words, stuck pixels that stay in G0."""
+    planes = np.ascontiguousarray(pedestal, np.float32)
+    assert planes.shape == (3, height, width)
+    raw = np.empty((height, width), np.uint16)
+    if lib().ffs_synth_jungfrau_dark(C.c_uint32(width), C.c_uint32(height), planes.ctypes.data_as(C.c_void_p), C.c_uint64(seed), C.c_uint32(frame),
+                                     C.c_uint32(n_frames), raw.ctypes.data_as(C.c_void_p)) != 0:
+        raise ValueError("ffs_synth_jungfrau_dark rejected its parameters")
+    return raw
+
+
+def dark_frames(width, height, seed, n_frames) -> np.ndarray:
+    """What synth:tinydark / synth:jungfrau9mdark hand over: the n_frames frames of the dark run under jungfrau_calibration(seed)."""
+    ped, _ = jungfrau_calibration(width, height, seed)
+    return np.stack([jungfrau_dark(width, height, ped, seed, i, n_frames) for i in range(n_frames)])

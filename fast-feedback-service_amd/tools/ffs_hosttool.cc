@@ -11,6 +11,10 @@
 //                                         --jungfrau-calibration reads it (6 W H float32: pedestal G0 G1 G2, factor G0 G1 G2)
 //   ffs_hosttool jfconvert <raw> <cal> <W> <H> <out>   the host converter of codecs.hpp: frames of W H raw words -> uint32 photon counts
 //   ffs_hosttool synthframes <synth:spec> <file>        the source's frames as it hands them over, one behind the other
+//   ffs_hosttool jfrepedestal <old cal> <prefix> <new cal> [min_frames [max_rms]]
+//                                         the re-pedestalled calibration from spotfinder --jungfrau-pedestal's <prefix>.count.u32, .sum.u64 and
+//                                         .sum_sq.u64 (the rule of csrc/jungfrau_pedestal_model.hpp): pedestals replaced, a factor kept where the
+//                                         stage's pedestal is usable (count >= min_frames [1], rms <= max_rms [0: no test]) and 0 elsewhere
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -217,7 +221,7 @@ static std::vector<uint8_t> read_file(const std::string& path) {
 
 static int jfcal(const std::string& spec, const std::string& file) {
     const std::vector<float> planes = synth_jungfrau_calibration(spec);
-    if (planes.empty()) return fail("jfcal: not a source of raw Jungfrau words (synth:tinyraw, synth:jungfrau9mraw)");
+    if (planes.empty()) return fail("jfcal: not a source of raw Jungfrau words (synth:tinyraw, synth:jungfrau9mraw, synth:tinydark, synth:jungfrau9mdark)");
     std::ofstream f(file, std::ios::binary);
     f.write(reinterpret_cast<const char*>(planes.data()), (std::streamsize)(planes.size() * sizeof(float)));
     return f ? 0 : fail("jfcal: cannot write the file");
@@ -236,6 +240,35 @@ static int jfconvert(const std::string& raw_file, const std::string& cal_file, s
     std::ofstream o(out_file, std::ios::binary);
     o.write(reinterpret_cast<const char*>(out.data()), (std::streamsize)(out.size() * 4));
     return o ? 0 : fail("jfconvert: cannot write the file");
+}
+
+static int jfrepedestal(const std::string& old_file, const std::string& prefix, const std::string& new_file, const std::string& min_frames_s,
+                        const std::string& max_rms_s) {
+    char* end = nullptr;
+    const unsigned long long min_frames = std::strtoull(min_frames_s.c_str(), &end, 10);
+    if (min_frames_s.empty() || *end || min_frames_s[0] == '-' || min_frames > 0xFFFFFFFFull) return fail("jfrepedestal: min_frames is not a number in 1 .. 2^32 - 1");
+    const float max_rms = std::strtof(max_rms_s.c_str(), &end);
+    if (max_rms_s.empty() || *end) return fail("jfrepedestal: max_rms is not a number");
+    if (!ffsamd::jf_pedestal_args_ok((uint32_t)min_frames, max_rms)) return fail("jfrepedestal: min_frames must be at least 1, max_rms finite and >= 0 (0: no noise test)");
+    const std::vector<uint8_t> old = read_file(old_file);
+    if (old.empty() || old.size() % (6 * sizeof(float)) != 0) return fail("jfrepedestal: the calibration is not six planes of float32");
+    const size_t n_px = old.size() / (6 * sizeof(float));
+    const std::vector<uint8_t> count = read_file(prefix + ".count.u32"), sum = read_file(prefix + ".sum.u64"), sum_sq = read_file(prefix + ".sum_sq.u64");
+    if (count.size() != 3 * n_px * 4 || sum.size() != 3 * n_px * 8 || sum_sq.size() != 3 * n_px * 8)
+        return fail(("jfrepedestal: " + prefix + ".count.u32 / .sum.u64 / .sum_sq.u64 are not three planes each of the calibration's " + std::to_string(n_px) + " pixels").c_str());
+    std::vector<float> planes(6 * n_px), pedestal(3 * n_px), rms(3 * n_px), out(6 * n_px);
+    std::vector<uint32_t> c(3 * n_px);
+    std::vector<uint64_t> s(3 * n_px), q(3 * n_px);
+    std::vector<uint8_t> ok(3 * n_px);
+    std::memcpy(planes.data(), old.data(), old.size());
+    std::memcpy(c.data(), count.data(), count.size());
+    std::memcpy(s.data(), sum.data(), sum.size());
+    std::memcpy(q.data(), sum_sq.data(), sum_sq.size());
+    jungfrau_pedestal_planes(c.data(), s.data(), q.data(), n_px, (uint32_t)min_frames, max_rms, pedestal.data(), rms.data(), ok.data());
+    jungfrau_repedestal(planes.data(), n_px, pedestal.data(), ok.data(), out.data());
+    std::ofstream o(new_file, std::ios::binary);
+    o.write(reinterpret_cast<const char*>(out.data()), (std::streamsize)(out.size() * sizeof(float)));
+    return o ? 0 : fail("jfrepedestal: cannot write the file");
 }
 
 static int synthframes(const std::string& spec, const std::string& file) {
@@ -278,6 +311,7 @@ int main(int argc, char** argv) {
         if (cmd == "jfconvert" && argc == 7)
             return jfconvert(argv[2], argv[3], std::strtoull(argv[4], nullptr, 10), std::strtoull(argv[5], nullptr, 10), argv[6]);
         if (cmd == "synthframes" && argc == 4) return synthframes(argv[2], argv[3]);
+        if (cmd == "jfrepedestal" && argc >= 5 && argc <= 7) return jfrepedestal(argv[2], argv[3], argv[4], argc > 5 ? argv[5] : "1", argc > 6 ? argv[6] : "0");
         if (cmd == "h5stats" && argc == 4) { h5_print_group_stats(argv[2], argv[3]); return 0; }
         if (cmd == "h5support") { std::printf("%d\n", h5_supported() ? 1 : 0); return 0; }
     } catch (const std::exception& e) {
@@ -288,6 +322,6 @@ int main(int argc, char** argv) {
                 "       mkh5 <synth:spec> <master.h5> [vds-links|vds-files|plain [frames_per_file [n_written]]] |\n"
                 "       h5info <master.h5> | synthinfo <synth:spec> | h5support | h5stats <file.h5> <group> |\n"
                 "       chunkfnv <chunk> <nelem> <elem bytes> | jfcal <synth:spec> <file> | jfconvert <raw> <cal> <W> <H> <out> |\n"
-                "       synthframes <synth:spec> <file>\n");
+                "       synthframes <synth:spec> <file> | jfrepedestal <old cal> <prefix> <new cal> [min_frames [max_rms]]\n");
     return 2;
 }

@@ -374,6 +374,68 @@ typedef struct {
 } ffs_pixel_stats;
 int ffs_ctx_get_pixel_stats(ffs_ctx *ctx, ffs_pixel_stats *out);
 
+/* Jungfrau pedestals from dark frames: what the pedestal planes of ffs_ctx_set_jungfrau_calibration are measured from.  Before a
+ * collection the detector takes a few thousand dark frames in G0, then forced into G1, then into G2; these entries fold the raw words of
+ * such frames into per-pixel, per-stage accumulators on the device (2 bytes a pixel cross PCIe, as for data) and turn the accumulators
+ * into pedestal, noise and "usable" planes.  The per-pixel statistics above cannot do this: they would add the gain bits into the value
+ * and mix the stages.  The rule is stated once, in csrc/jungfrau_pedestal_model.hpp, and compiled by the kernel, this library's host
+ * function, the driver and a CPU check.  The reference has no counterpart.
+ *   FOLD.  A frame is W*H little-endian 16-bit words.  A word r at flat pixel k that is invalid by itself -- gain code 2, 0xFFFF, 0xC000 --
+ *   counts nowhere.  Otherwise, with the stage s = 0, 1, 2 for the gain codes 0, 1, 3 and a = r & 0x3FFF:
+ *     count[s][k] += 1 (uint32), sum[s][k] += a (uint64), sum_sq[s][k] += a*a (uint64); per context n_frames += 1 per frame.
+ *   The word decides the stage: a run needs no label, one accumulator set takes G0, G1 and G2 frames in any order, and no calibration
+ *   plays a part.  Nothing can wrap while n_frames < 2^32.  All integers: the result is bit for bit independent of batch size, stream,
+ *   thread and order.
+ *   PLANES.  One stage of one pixel, c = count: c == 0 gives pedestal 0, rms 0, ok 0.  Otherwise in float64, each operation rounded on its
+ *   own: m = (double)sum / (double)c, q = (double)sum_sq / (double)c, v = q - m*m, pedestal = (float)m, rms = (float)sqrt(v > 0 ? v : 0),
+ *   ok = c >= min_frames && (max_rms == 0 || rms <= max_rms).  Bit for bit the NumPy float64 / float32 rule.
+ *   A RE-PEDESTALLED CALIBRATION takes these pedestal planes and keeps factor[s][k] where ok[s][k] holds, 0 ("no calibration") elsewhere
+ *   (the driver's --jungfrau-pedestal and `ffs_hosttool jfrepedestal` write it).
+ *
+ * ffs_ctx_jungfrau_pedestal_begin: allocates the accumulators on first use (60 bytes a pixel, 566 MB on Jungfrau-9M; FFS_ERR_NOMEM when
+ * that fails), zeroes them and n_frames.  Calling it again starts again.
+ * ffs_ctx_jungfrau_pedestal_end: frees them; idempotent (FFS_OK when there are none).  They also go with the context.
+ * FFS_ERR_INVALID, state unchanged: a context of pixel_bytes 2 (begin; as for the calibration, raw words belong to 32-bit contexts);
+ * while any stream of the context has a batch or a fold in flight (both). */
+int ffs_ctx_jungfrau_pedestal_begin(ffs_ctx *ctx);
+int ffs_ctx_jungfrau_pedestal_end(ffs_ctx *ctx);
+
+/* Folds n_frames dark frames into the context's accumulators.  chunks[i] is exactly width*height 16-bit little-endian words, placed as
+ * for FFS_CODEC_JUNGFRAU_RAW: anywhere, or all of them inside the stream's host buffer at offsets that are multiples of 16.
+ * SYNCHRONOUS: on return the frames are in the accumulators, and the caller has its memory and the stream's host buffer back.
+ * ms_fold may be NULL; otherwise it receives the duration of the fold launch (one per 64 frames; of all of them together) from HIP events
+ * on the dispatches.  The fold needs no calibration, runs no conversion, no threshold and no sparse stage, and leaves
+ * ffs_stream_last_path, ffs_stream_timings, the pixel statistics, the radial profile and the results of the batches before and after it
+ * untouched.  It stages its chunks where an encoded batch stages them and writes nowhere else on the stream: the frames of the last
+ * waited batch stay where they are, so ffs_stream_spot_backgrounds REMAINS AVAILABLE after a fold on its stream and gives what it gave
+ * before it.
+ * Folds on different streams of one context may be called from different threads at once: the library keeps their launches on the
+ * accumulators apart (one HIP stream of the context, one launch behind the other), and the result does not depend on their order.
+ * FFS_ERR_INVALID, each with a text of its own, nothing folded and the state unchanged: a NULL stream, chunks or chunk_bytes; no
+ * accumulators (before ffs_ctx_jungfrau_pedestal_begin, after _end); a batch in flight on the stream; n_frames outside 1..max_batch; a
+ * NULL chunk or one of any size other than width*height*2; chunks partly inside the stream's host buffer; a chunk inside it at an
+ * offset that is not a multiple of 16; a fold that would take n_frames past 2^32 - 1. */
+int ffs_stream_jungfrau_pedestal_fold(ffs_stream *s, const void *const *chunks, const size_t *chunk_bytes,
+                                      uint32_t n_frames, float *ms_fold);
+
+/* Copies the accumulators out: each of the nine pointers is caller-owned, dense, W*H entries, row-major, and may be NULL (that plane is
+ * not copied); n_frames is always written.  Every fold that has returned is in them.  FFS_ERR_INVALID, nothing written: NULL out; no
+ * accumulators (before begin, after end); while any stream of the context has a batch or a fold in flight. */
+typedef struct {
+    uint64_t n_frames;   /* out (ffs_ctx_get_jungfrau_pedestal); not read by ffs_jungfrau_pedestal_planes */
+    uint32_t *count[3];
+    uint64_t *sum[3];
+    uint64_t *sum_sq[3];
+} ffs_jungfrau_pedestal_stats;
+int ffs_ctx_get_jungfrau_pedestal(ffs_ctx *ctx, ffs_jungfrau_pedestal_stats *out);
+
+/* The PLANES rule above on the host: no context, no GPU.  stats: nine planes of n_px entries, all needed.  pedestal[s], rms[s], ok[s]:
+ * n_px entries each; the three arrays of pointers must be given, any pointer in them may be NULL (that plane is not written).
+ * min_frames >= 1; max_rms finite and >= 0, 0 = no noise test.  FFS_ERR_INVALID, nothing written (ffs_last_error(NULL) has the text):
+ * NULL stats, a NULL plane in it, a NULL pedestal, rms or ok array; min_frames 0; a negative, infinite or NaN max_rms. */
+int ffs_jungfrau_pedestal_planes(const ffs_jungfrau_pedestal_stats *stats, size_t n_px, uint32_t min_frames, float max_rms,
+                                 float *const pedestal[3], float *const rms[3], uint8_t *const ok[3]);
+
 /* Selects between paths that give the SAME results (A/B partners, fall-backs, capacities that tests shrink) --
  * per context, never through the environment; nothing here can change a result.  Keys (default):
  *   "threshold_path"   (0) 0 = windows the streaming kernel cannot vouch for go onto a list (fix-up kernel),

@@ -75,6 +75,16 @@ int ffs_synth_jungfrau_calibration(uint32_t width, uint32_t height, uint64_t see
 int ffs_synth_jungfrau_encode(const uint32_t *photons, uint32_t width, uint32_t height, const float *planes, uint64_t seed,
                               uint32_t frame, uint16_t *raw);
 
+/* One frame of a DARK run under `planes` (as above; only the pedestals are read): what the pedestals are measured from
+ * (ffs_stream_jungfrau_pedestal_fold of ffs_hip.h).  Frame `frame` of `n_frames` is forced into stage 3 * frame / n_frames: the first third
+ * of a run is G0, the second G1, the last G2.  A pixel's word is that stage's gain code with ADC = clamp(floor(pedestal_s) + e, 0, 16383),
+ * e in -2 .. 2 a pure function of (seed, frame, pixel): every measured pedestal lies within 2 ADU of floor(pedestal).  About one word
+ * in 4096 is replaced by one of the three invalid words (0xFFFF, the gain code 2, 0xC000), and about one pixel in 1024 -- a pure function
+ * of (seed, pixel) -- is STUCK: it reports G0, with G0's pedestal, whatever the run forces, so its G1 and G2 counts stay 0.
+ * -1: a NULL pointer, a zero size, frame >= n_frames. */
+int ffs_synth_jungfrau_dark(uint32_t width, uint32_t height, const float *planes, uint64_t seed, uint32_t frame, uint32_t n_frames,
+                            uint16_t *raw);
+
 #ifdef __cplusplus
 }
 #endif
