@@ -18,7 +18,7 @@ extern "C" int ffs_bench_threshold(ffs_stream* s, const void* device_pixels, siz
     int rc = check_layout(s, pitch, fstride, n_frames);
     if (rc != FFS_OK) return rc;
     HIP_TRY(c, hipSetDevice(c->device));
-    s->batch = snapshot_of(c);
+    s->batch = snapshot_of(c->settings);
     const ThresholdRoute route = batch_route(s, Rerun{});
     const bool ext = route.ext();
     if (ext) {
@@ -99,14 +99,14 @@ extern "C" int ffs_bench_radial(ffs_stream* s, const void* device_pixels, size_t
         c->err = "stream busy";
         return FFS_ERR_INVALID;
     }
-    if (c->radial_bins == 0) {
+    if (c->settings.radial_bins == 0) {
         c->err = "ffs_bench_radial: the context has no bin map (ffs_ctx_set_radial_bins)";
         return FFS_ERR_INVALID;
     }
     int rc = check_layout(s, pitch, fstride, n_frames);
     if (rc != FFS_OK) return rc;
     HIP_TRY(c, hipSetDevice(c->device));
-    s->batch = snapshot_of(c);
+    s->batch = snapshot_of(c->settings);
     rc = radial_ensure_buffers(s, s->batch.radial_bins);
     if (rc != FFS_OK) return rc;
     std::vector<hipEvent_t> ev(2 * (size_t)iters, nullptr);
@@ -141,7 +141,7 @@ extern "C" int ffs_bench_radial(ffs_stream* s, const void* device_pixels, size_t
 extern "C" int ffs_bench_pixel_stats(ffs_stream* s, const void* device_pixels, size_t pitch, size_t fstride, uint32_t n_frames, uint32_t iters, float* ms) {
     if (!s || !device_pixels || iters == 0 || !stream_handle_ok(s)) return FFS_ERR_INVALID;
     ffs_ctx* c = s->ctx;
-    if (c->stats_on) {
+    if (c->settings.pixel_stats) {
         c->err = "ffs_bench_pixel_stats: accumulation is on (ffs_ctx_set_pixel_stats(ctx, FFS_PIXEL_STATS_OFF) first): the measurement leaves the accumulators undefined";
         return FFS_ERR_INVALID;
     }
@@ -165,7 +165,7 @@ extern "C" int ffs_bench_pixel_stats(ffs_stream* s, const void* device_pixels, s
     {
         std::lock_guard<std::mutex> lock(c->stats_mu);
         for (uint32_t i = 0; i < iters && rc == FFS_OK; ++i)
-            rc = pixstats_launch(c, device_pixels, pitch, fstride, n_frames, c->params.max_valid, s->st, ev[2 * i], ev[2 * i + 1]);
+            rc = pixstats_launch(c, device_pixels, pitch, fstride, n_frames, c->settings.params.max_valid, s->st, ev[2 * i], ev[2 * i + 1]);
     }
     hipError_t err = hipStreamSynchronize(s->st);
     double t = 0;

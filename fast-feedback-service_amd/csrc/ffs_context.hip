@@ -78,23 +78,7 @@ bool handle_live(HandleKind kind, const void* h) {
 bool process_exiting() { return registry().exiting.load(); }
 
 extern "C" void ffs_default_params(ffs_params* p) {
-    if (!p) return;
-    std::memset(p, 0, sizeof(*p));
-    p->min_count = 2;  // baseline/spotfinder/standalone.cc:17
-    p->nsig_b = 6.0;   // :19
-    p->nsig_s = 3.0;   // :20
-    p->threshold = 0.0;
-    p->max_valid = -1;
-    p->min_spot_size = 3;     // spotfinder/spotfinder.cc:321
-    p->min_spot_size_3d = 3;  // :327
-    p->max_peak_centroid_separation = 2.0f;  // :335
-    p->want_reflections = 1;
-    p->want_strong_list = 0;
-    p->want_strong_mask = 0;
-    p->algorithm = FFS_ALGO_DISPERSION;
-    p->extended_flavour = 0;
-    p->kernel_half_x = 3;     // standalone.cc:16 (kernel_size_ = 3,3)
-    p->kernel_half_y = 3;
+    if (p) *p = default_params();
 }
 
 extern "C" int ffs_device_count(void) {
@@ -157,7 +141,7 @@ extern "C" int ffs_ctx_create(int device, uint32_t width, uint32_t height, int p
         x.dummy_lds = std::max(0, std::min(65536, env_int("FFS_EXP_DUMMY_LDS", 0)));
     }
 #endif
-    c->pixel_bytes = pixel_bytes;
+    c->settings.pixel_bytes = pixel_bytes;
     c->max_batch = max_batch;
     c->L = default_layout(width, height, pixel_bytes);
     const Layout& L = c->L;
@@ -171,7 +155,7 @@ extern "C" int ffs_ctx_create(int device, uint32_t width, uint32_t height, int p
     c->cap = (uint32_t)std::min<uint64_t>(c->cap, npx);
     c->max_comp = std::min<uint32_t>(c->cap, 1u << 14);   // (a frame with more is run again with room for it, as for the lists)
     c->n_tiles = ((int)height + kTileRows - 1) / kTileRows;
-    ffs_default_params(&c->params);
+    c->settings.params = default_params();
     if (hipSetDevice(device) != hipSuccess) {
         g_create_error = "hipSetDevice failed";
         delete c;
@@ -334,11 +318,11 @@ static void ctx_destroy_internal(ffs_ctx* c) {
 // The tables of the one-kernel threshold path depend on the mask alone: rebuilt whenever it changes.
 static int rebuild_mask_tables(ffs_ctx* c) {
     const Layout& L = c->L;
-    const uint32_t gpitch = ginfo_pitch(L, c->pixel_bytes);
+    const uint32_t gpitch = ginfo_pitch(L, c->settings.pixel_bytes);
     HIP_TRY(c, hipMemset(c->d_ginfo, 0, (size_t)(L.H + kInfoExtraRows) * gpitch));
-    const int groups = L.pitch_px / (c->pixel_bytes == 2 ? 8 : 4);
+    const int groups = L.pitch_px / (c->settings.pixel_bytes == 2 ? 8 : 4);
     (void)hipGetLastError();  // drop any stale error state: the check below is for this launch
-    if (c->pixel_bytes == 2)
+    if (c->settings.pixel_bytes == 2)
         hipLaunchKernelGGL(k_build_maps, dim3((groups + 255) / 256, L.H), dim3(256), 0, 0, c->d_maskbits, L.mpitch, L.W, L.H,
                            L.pitch_px, c->d_mmap, c->d_ginfo, gpitch);
     else
@@ -416,73 +400,18 @@ extern "C" int ffs_ctx_apply_resolution_mask(ffs_ctx* c, float wavelength, float
     return rebuild_mask_tables(c);
 }
 
+// ---- the settings: every setter asks context_settings.hpp first, and stores into c->settings last ---------------------------------------
 extern "C" int ffs_ctx_set_params(ffs_ctx* c, const ffs_params* p) {
     if (!c || !p) return FFS_ERR_INVALID;
-    if (p->kernel_half_x < 0 || p->kernel_half_x > kWinMaxHalf || p->kernel_half_y < 0 || p->kernel_half_y > kWinMaxHalf) {
-        c->err = "ffs_ctx_set_params: kernel_half_x / kernel_half_y must be in 1..7 (0 = 3)";
-        return FFS_ERR_INVALID;
-    }
-    const int win_px = (2 * win_half(p->kernel_half_x) + 1) * (2 * win_half(p->kernel_half_y) + 1);
-    if (p->min_count < 2 || p->min_count > win_px || p->nsig_b < 0 || p->nsig_s < 0 || p->threshold < 0) {
-        c->err = "ffs_ctx_set_params: need 2 <= min_count <= (2*kernel_half_x+1)*(2*kernel_half_y+1) (49 for the 7x7 window), "
-                 "nsig_b >= 0, nsig_s >= 0, threshold >= 0";
-        return FFS_ERR_INVALID;  // the asserts of standalone.cc:52-63
-    }
-    if (p->algorithm == FFS_ALGO_DISPERSION_EXTENDED && !win_default(*p)) {
-        c->err = "ffs_ctx_set_params: the extended dispersion algorithm needs the 7x7 window (kernel_half_x = kernel_half_y = 3): "
-                 "its erosion and final pass derive from it";
-        return FFS_ERR_INVALID;
-    }
-    if ((p->algorithm != FFS_ALGO_DISPERSION && p->algorithm != FFS_ALGO_DISPERSION_EXTENDED && p->algorithm != FFS_ALGO_RADIAL_PROFILE)
-        || (p->extended_flavour != 0 && p->extended_flavour != 1)) {
-        c->err = "ffs_ctx_set_params: unknown algorithm / extended_flavour";
-        return FFS_ERR_INVALID;
-    }
-    // (whichever call comes second is refused: ffs_ctx_set_radial_bins has the other half)
-    if (p->algorithm == FFS_ALGO_RADIAL_PROFILE && c->radial_bins == 0) {
-        c->err = "ffs_ctx_set_params: the radial_profile algorithm needs a radial bin map (ffs_ctx_set_radial_bins) and the context has none";
-        return FFS_ERR_INVALID;
-    }
-    if (p->algorithm == FFS_ALGO_RADIAL_PROFILE && c->radial_bins > kRadThrMaxBins) {
-        c->err = "ffs_ctx_set_params: the radial_profile algorithm takes a radial bin map of at most 128 bins and the context's has "
-                 + std::to_string(c->radial_bins);
-        return FFS_ERR_INVALID;
-    }
-    if (p->extended_flavour == 1 && c->max_valid_scope == FFS_MAX_VALID_WINDOW) {
-        c->err = "ffs_ctx_set_params: extended_flavour 1 cannot be combined with the window scope of max_valid (ffs_ctx_set_max_valid_scope): "
-                 "the device-flavour erosion skips masked neighbours by the static mask";
-        return FFS_ERR_INVALID;
-    }
-    if (p->extended_flavour == 1 && c->gain > 0.0) {
-        c->err = "ffs_ctx_set_params: extended_flavour 1 cannot be combined with a detector gain (ffs_ctx_set_gain): "
-                 "the reference's device kernels, which that flavour copies, have no gain";
-        return FFS_ERR_INVALID;
-    }
-    if (p->extended_flavour == 1 && c->has_gain_map) {
-        c->err = "ffs_ctx_set_params: extended_flavour 1 cannot be combined with a gain map (ffs_ctx_set_gain_map): "
-                 "the reference's device kernels, which that flavour copies, have no gain";
-        return FFS_ERR_INVALID;
-    }
-    c->params = *p;
+    if (const std::string why = set_params(c->settings, *p); !why.empty()) return refuse(c->err, FFS_ERR_INVALID, why);
+    c->settings.params = *p;
     return FFS_OK;
 }
 
 extern "C" int ffs_ctx_set_gain(ffs_ctx* c, double gain) {
     if (!c) return FFS_ERR_INVALID;
-    if (!std::isfinite(gain) || gain < 0.0) {
-        c->err = "ffs_ctx_set_gain: the gain must be finite and >= 0 (0 = off: pixel values are photon counts)";
-        return FFS_ERR_INVALID;
-    }
-    if (gain > 0.0 && c->params.extended_flavour == 1) {
-        c->err = "ffs_ctx_set_gain: a detector gain cannot be combined with extended_flavour 1: the reference's device kernels, "
-                 "which that flavour copies, have no gain";
-        return FFS_ERR_INVALID;
-    }
-    if (gain > 0.0 && c->has_gain_map) {
-        c->err = "ffs_ctx_set_gain: a gain map is set (ffs_ctx_set_gain_map): drop it with ffs_ctx_set_gain_map(ctx, NULL) first";
-        return FFS_ERR_INVALID;
-    }
-    c->gain = gain;
+    if (const std::string why = set_gain(c->settings, gain); !why.empty()) return refuse(c->err, FFS_ERR_INVALID, why);
+    c->settings.gain = gain;
     return FFS_OK;
 }
 
@@ -490,52 +419,25 @@ extern "C" int ffs_ctx_set_gain(ffs_ctx* c, double gain) {
 // batch of the context is in flight, so a batch and its re-runs inside ffs_wait read the map they were submitted with.
 static int ffs_ctx_set_gain_map_impl(ffs_ctx* c, const float* host_gain) {
     if (!host_gain) {   // (the device buffer stays: a batch in flight was routed at submit and goes on reading the map it was submitted with)
-        c->has_gain_map = false;
+        c->settings.gain_map = false;
         return FFS_OK;
     }
-    if (c->inflight.load() > 0) {
-        c->err = "ffs_ctx_set_gain_map: a batch of this context is in flight (ffs_wait for it first): a batch keeps the map it was submitted with";
-        return FFS_ERR_INVALID;
-    }
-    if (c->gain > 0.0) {
-        c->err = "ffs_ctx_set_gain_map: a scalar gain is set (ffs_ctx_set_gain): switch it off with ffs_ctx_set_gain(ctx, 0) first";
-        return FFS_ERR_INVALID;
-    }
-    if (c->params.extended_flavour == 1) {
-        c->err = "ffs_ctx_set_gain_map: a gain map cannot be combined with extended_flavour 1: the reference's device kernels, "
-                 "which that flavour copies, have no gain";
-        return FFS_ERR_INVALID;
-    }
-    const Layout& L = c->L;
-    const size_t n = (size_t)L.W * L.H;
+    FFS_TRY(refuse_in_flight(c, "ffs_ctx_set_gain_map", ": a batch keeps the map it was submitted with"));
+    if (const std::string why = set_gain_map(c->settings, true); !why.empty()) return refuse(c->err, FFS_ERR_INVALID, why);
+    const size_t W = (size_t)c->L.W, n = W * c->L.H;
     float lo = host_gain[0], hi = host_gain[0];
     for (size_t i = 0; i < n; ++i) {
         const float g = host_gain[i];
-        if (!(g >= 0x1p-60f && g <= 0x1p60f)) {   // (false for a NaN)
-            c->err = "ffs_ctx_set_gain_map: entry " + std::to_string(i) + " (x = " + std::to_string(i % (size_t)L.W) + ", y = " + std::to_string(i / (size_t)L.W)
-                     + ") is " + std::to_string(g) + ": every entry must be finite and in [2^-60, 2^60], under masked pixels too";
-            return FFS_ERR_INVALID;
-        }
+        if (!(g >= 0x1p-60f && g <= 0x1p60f))   // (false for a NaN)
+            return refuse(c->err, FFS_ERR_INVALID, "ffs_ctx_set_gain_map: " + entry_text(i, W, g) + ": every entry must be finite and in [2^-60, 2^60], under masked pixels too");
         lo = std::min(lo, g);
         hi = std::max(hi, g);
     }
-    // rows of pitch_px entries, addressed like the pixel rows; the entries beyond W (whose pixels no mask bit covers) are 1
-    std::vector<float> rows((size_t)L.pitch_px * L.H, 1.0f);
-    for (int y = 0; y < L.H; ++y) std::memcpy(rows.data() + (size_t)y * L.pitch_px, host_gain + (size_t)y * L.W, (size_t)L.W * sizeof(float));
-    HIP_TRY(c, hipSetDevice(c->device));
-    if (!c->d_gain_map) {
-        float* d = nullptr;
-        if (hipMalloc(&d, rows.size() * sizeof(float)) != hipSuccess) {
-            (void)hipGetLastError();
-            c->err = "ffs_ctx_set_gain_map: hipMalloc(gain map) failed";
-            return FFS_ERR_NOMEM;
-        }
-        c->d_gain_map = d;
-    }
-    HIP_TRY(c, hipMemcpy(c->d_gain_map, rows.data(), rows.size() * sizeof(float), hipMemcpyHostToDevice));
+    std::vector<float> rows;   // (the entries beyond W, whose pixels no mask bit covers, are 1)
+    FFS_TRY(upload_pixel_table(c, "ffs_ctx_set_gain_map", "gain map", host_gain, 1.0f, 0, &c->d_gain_map, rows));
     c->gain_map_min = lo;
     c->gain_map_max = hi;
-    c->has_gain_map = true;
+    c->settings.gain_map = true;
     return FFS_OK;
 }
 extern "C" int ffs_ctx_set_gain_map(ffs_ctx* c, const float* host_gain) {
@@ -546,36 +448,23 @@ extern "C" int ffs_ctx_set_gain_map(ffs_ctx* c, const float* host_gain) {
 // The Jungfrau calibration.  Everything is checked before anything changes; the device copy -- six dense planes, as they
 // come -- is written only while no batch of the context is in flight, so a batch's conversion reads the calibration it was submitted with.
 static int ffs_ctx_set_jungfrau_calibration_impl(ffs_ctx* c, const ffs_jungfrau_calibration* cal) {
-    if (c->inflight.load() > 0) {
-        c->err = "ffs_ctx_set_jungfrau_calibration: a batch of this context is in flight (ffs_wait for it first): a batch keeps the calibration it was "
-                 "submitted with";
-        return FFS_ERR_INVALID;
-    }
+    FFS_TRY(refuse_in_flight(c, "ffs_ctx_set_jungfrau_calibration", ": a batch keeps the calibration it was submitted with"));
     if (!cal) {
-        c->has_jf_cal = false;
+        c->settings.jungfrau_calibration = false;
         return FFS_OK;
     }
-    if (c->pixel_bytes != 4) {
-        c->err = "ffs_ctx_set_jungfrau_calibration: raw Jungfrau words convert to 32-bit photon counts: the context must have pixel_bytes 4";
-        return FFS_ERR_INVALID;
-    }
+    if (const std::string why = set_jungfrau_calibration(c->settings, true); !why.empty()) return refuse(c->err, FFS_ERR_INVALID, why);
     static const char* const names[6] = {"pedestal[0]", "pedestal[1]", "pedestal[2]", "factor[0]", "factor[1]", "factor[2]"};
     const float* planes[6] = {cal->pedestal[0], cal->pedestal[1], cal->pedestal[2], cal->factor[0], cal->factor[1], cal->factor[2]};
-    const Layout& L = c->L;
-    const size_t n = (size_t)L.W * L.H;
+    const size_t W = (size_t)c->L.W, n = W * c->L.H;
     for (int p = 0; p < 6; ++p) {
-        if (!planes[p]) {
-            c->err = std::string("ffs_ctx_set_jungfrau_calibration: ") + names[p] + " is NULL";
-            return FFS_ERR_INVALID;
-        }
+        if (!planes[p]) return refuse(c->err, FFS_ERR_INVALID, std::string("ffs_ctx_set_jungfrau_calibration: ") + names[p] + " is NULL");
         for (size_t i = 0; i < n; ++i)
-            if (!jf_entry_ok(p >= 3, planes[p][i])) {
-                c->err = std::string("ffs_ctx_set_jungfrau_calibration: ") + names[p] + " entry " + std::to_string(i) + " (x = " + std::to_string(i % (size_t)L.W)
-                         + ", y = " + std::to_string(i / (size_t)L.W) + ") is " + std::to_string(planes[p][i])
-                         + (p >= 3 ? ": a factor must be 0 (no calibration) or finite with a magnitude in [2^-30, 2^16]"
-                                   : ": a pedestal must be finite and in [-65536, 65536]");
-                return FFS_ERR_INVALID;
-            }
+            if (!jf_entry_ok(p >= 3, planes[p][i]))
+                return refuse(c->err, FFS_ERR_INVALID,
+                              std::string("ffs_ctx_set_jungfrau_calibration: ") + names[p] + " " + entry_text(i, W, planes[p][i])
+                                  + (p >= 3 ? ": a factor must be 0 (no calibration) or finite with a magnitude in [2^-30, 2^16]"
+                                            : ": a pedestal must be finite and in [-65536, 65536]"));
     }
     HIP_TRY(c, hipSetDevice(c->device));
     const size_t stride = (n + 7) / 8 * 8;
@@ -583,15 +472,14 @@ static int ffs_ctx_set_jungfrau_calibration_impl(ffs_ctx* c, const ffs_jungfrau_
         float* d = nullptr;
         if (dmalloc(&d, 6 * stride * sizeof(float)) != hipSuccess) {
             (void)hipGetLastError();
-            c->err = "ffs_ctx_set_jungfrau_calibration: hipMalloc(calibration planes) failed";
-            return FFS_ERR_NOMEM;
+            return refuse(c->err, FFS_ERR_NOMEM, "ffs_ctx_set_jungfrau_calibration: hipMalloc(calibration planes) failed");
         }
         c->d_jf_cal = d;
         c->jf_plane_stride = stride;
     }
-    c->has_jf_cal = false;   // (a copy that fails half way leaves no mixed calibration in force)
+    c->settings.jungfrau_calibration = false;   // (a copy that fails half way leaves no mixed calibration in force)
     for (int p = 0; p < 6; ++p) HIP_TRY(c, hipMemcpy(c->d_jf_cal + (size_t)p * stride, planes[p], n * sizeof(float), hipMemcpyHostToDevice));
-    c->has_jf_cal = true;
+    c->settings.jungfrau_calibration = true;
     return FFS_OK;
 }
 extern "C" int ffs_ctx_set_jungfrau_calibration(ffs_ctx* c, const ffs_jungfrau_calibration* cal) {
@@ -601,16 +489,8 @@ extern "C" int ffs_ctx_set_jungfrau_calibration(ffs_ctx* c, const ffs_jungfrau_c
 
 extern "C" int ffs_ctx_set_max_valid_scope(ffs_ctx* c, int scope) {
     if (!c) return FFS_ERR_INVALID;
-    if (scope != FFS_MAX_VALID_CENTRE && scope != FFS_MAX_VALID_WINDOW) {
-        c->err = "ffs_ctx_set_max_valid_scope: scope must be FFS_MAX_VALID_CENTRE (0) or FFS_MAX_VALID_WINDOW (1)";
-        return FFS_ERR_INVALID;
-    }
-    if (scope == FFS_MAX_VALID_WINDOW && c->params.extended_flavour == 1) {
-        c->err = "ffs_ctx_set_max_valid_scope: the window scope cannot be combined with extended_flavour 1: the device-flavour erosion "
-                 "skips masked neighbours by the static mask";
-        return FFS_ERR_INVALID;
-    }
-    c->max_valid_scope = scope;
+    if (const std::string why = set_max_valid_scope(c->settings, scope); !why.empty()) return refuse(c->err, FFS_ERR_INVALID, why);
+    c->settings.max_valid_scope = scope;
     return FFS_OK;
 }
 
@@ -680,14 +560,10 @@ extern "C" int ffs_ctx_set_tuning(ffs_ctx* c, const char* key, long long value) 
     else if (k == "band_taper") { if ((ok = in(0, 99))) t.band_taper = (int)value; }
     else if (k == "rows_ahead") { if ((ok = in(2, 4))) t.rows_ahead = (int)value; }
     else if (k == "ccl_grid") { if ((ok = in(1, 1024))) t.ccl_grid = (int)value; }
-    else {
-        c->err = "ffs_ctx_set_tuning: unknown key '" + k + "'";
-        return FFS_ERR_INVALID;
-    }
-    if (!ok) {
-        c->err = "ffs_ctx_set_tuning: value out of range for '" + k + "' (sched / direct_records: before the first stream is created; stats_stream: while no batch is in flight)";
-        return FFS_ERR_INVALID;
-    }
+    else return refuse(c->err, FFS_ERR_INVALID, "ffs_ctx_set_tuning: unknown key '" + k + "'");
+    if (!ok)
+        return refuse(c->err, FFS_ERR_INVALID,
+                      "ffs_ctx_set_tuning: value out of range for '" + k + "' (sched / direct_records: before the first stream is created; stats_stream: while no batch is in flight)");
     return FFS_OK;
 }
 
@@ -871,7 +747,7 @@ int stream_create_sized(ffs_ctx* c, uint32_t max_batch, uint32_t cap, uint32_t m
 
 size_t default_staging_bytes(const ffs_stream* s) {
     // raw frames, or bitshuffle-LZ4 chunks (which can exceed the raw size by < 1 % when incompressible)
-    const size_t frame = (size_t)s->ctx->L.W * s->ctx->L.H * s->ctx->pixel_bytes;
+    const size_t frame = (size_t)s->ctx->L.W * s->ctx->L.H * s->ctx->settings.pixel_bytes;
     return (size_t)s->max_batch * (frame + frame / 128 + 4096);
 }
 
@@ -918,10 +794,7 @@ void pinned_free(PinnedBuf& b) {
 int ensure_host_staging(ffs_stream* s, size_t bytes) {
     ffs_ctx* c = s->ctx;
     if (s->h_img && s->h_img_bytes >= bytes) return FFS_OK;
-    if (s->busy) {
-        c->err = "the stream's host buffer cannot grow while a batch is in flight";
-        return FFS_ERR_INVALID;
-    }
+    if (s->busy) return refuse(c->err, FFS_ERR_INVALID, "the stream's host buffer cannot grow while a batch is in flight");
     HIP_TRY(c, hipSetDevice(c->device));
     {
         std::lock_guard<std::mutex> lock(c->stream_mu);
@@ -943,10 +816,7 @@ int ensure_host_staging(ffs_stream* s, size_t bytes) {
         }
     }
     if (!s->h_img_buf.p) s->h_img_buf = pinned_alloc(bytes);   // (outside the lock: page faults of several threads run side by side)
-    if (!s->h_img_buf.p) {
-        c->err = "allocation of the stream's pinned staging buffer (" + std::to_string(bytes >> 20) + " MiB) failed";
-        return FFS_ERR_NOMEM;
-    }
+    if (!s->h_img_buf.p) return refuse(c->err, FFS_ERR_NOMEM, "allocation of the stream's pinned staging buffer (" + std::to_string(bytes >> 20) + " MiB) failed");
     s->h_img = s->h_img_buf.p;
     s->h_img_bytes = s->h_img_buf.bytes;
     return FFS_OK;

@@ -26,10 +26,6 @@ void encoded_free(ffs_stream* s) {
     E = EncodedState{};
 }
 
-// a refusal: its text goes where the caller keeps errors (the context's text of the calling thread, or the helper thread's job_err)
-template <typename Err>
-static int refuse(Err& err, int rc, const std::string& text) { err = text; return rc; }
-
 // a table of max_batch rows the host writes and a kernel reads: its device and pinned host copies, made on first use
 template <typename T>
 static bool ensure_table(T** dev, T** host, size_t bytes) {
@@ -81,7 +77,7 @@ static int prepare_byte_offset(ffs_stream* s, EncodedBatch& b) {
 static int prepare(ffs_stream* s, int codec, const void* const* chunks, const size_t* chunk_bytes, uint32_t n, EncodedBatch& b, const char* fold = nullptr) {
     ffs_ctx* c = s->ctx;
     EncodedState& E = s->enc;
-    const size_t W = (size_t)c->L.W, H = (size_t)c->L.H, es = (size_t)c->pixel_bytes;
+    const size_t W = (size_t)c->L.W, H = (size_t)c->L.H, es = (size_t)c->settings.pixel_bytes;
     const bool byte_offset = codec == FFS_CODEC_BYTE_OFFSET, jungfrau = codec == FFS_CODEC_JUNGFRAU_RAW;
     b.codec = codec;
     if (!byte_offset && !jungfrau && !E.d_tab) {
@@ -96,7 +92,7 @@ static int prepare(ffs_stream* s, int codec, const void* const* chunks, const si
     if (!place_chunks(chunks, chunk_bytes, n, s->h_img, s->h_img_bytes, b.base, pl))
         return refuse(c->err, FFS_ERR_INVALID, "ffs_submit_compressed: either all chunks lie in the stream's host buffer or none");
     if (jungfrau) {   // (no table: the conversion reads the context's calibration and the chunks where they lie)
-        if (!fold && !c->has_jf_cal)
+        if (!fold && !c->settings.jungfrau_calibration)
             return refuse(c->err, FFS_ERR_INVALID, "ffs_submit_encoded: raw Jungfrau words need a calibration and the context has none (ffs_ctx_set_jungfrau_calibration)");
         if (const uint32_t f = first_unaligned_base(b.base.data(), n); f < n)
             return refuse(c->err, FFS_ERR_INVALID, std::string(fold ? fold : "ffs_submit_encoded") + ": raw Jungfrau chunk " + std::to_string(f) + " lies in the stream's host buffer at offset "
@@ -142,7 +138,7 @@ static int prepare(ffs_stream* s, int codec, const void* const* chunks, const si
 static int index_blocks(ffs_stream* s, const EncodedBatch& b, hipStream_t st, std::string& err) {
     EncodedState& E = s->enc;
     const uint32_t n = (uint32_t)b.base.size(), nb = E.blocking.blocks;
-    const size_t tail = (size_t)E.blocking.tail_elems * s->ctx->pixel_bytes;
+    const size_t tail = (size_t)E.blocking.tail_elems * s->ctx->settings.pixel_bytes;
     std::vector<size_t> pos(n, 12);
     std::atomic<bool> ok{true};
     static const bool trace = std::getenv("FFS_TRACE_SUBMIT") != nullptr;
@@ -184,7 +180,7 @@ static int launch(ffs_stream* s, const EncodedBatch& b, hipStream_t st, bool wit
         const dim3 grid(b.bo_max_tiles, n);
         hipLaunchKernelGGL(k_bo_summarise, grid, dim3(64), 0, st, a);
         hipLaunchKernelGGL(k_bo_compose, dim3(n), dim3(64), 0, st, a);
-        if (c->pixel_bytes == 2) hipLaunchKernelGGL(k_bo_emit<uint16_t>, grid, dim3(64), 0, st, a);
+        if (c->settings.pixel_bytes == 2) hipLaunchKernelGGL(k_bo_emit<uint16_t>, grid, dim3(64), 0, st, a);
         else hipLaunchKernelGGL(k_bo_emit<uint32_t>, grid, dim3(64), 0, st, a);
     } else if (e == hipSuccess && with_decode && jungfrau) {
         // one launch for up to kJfMaxFrames frames, whose bases travel in its arguments; a lane per group of eight pixels of the flat frame
@@ -200,10 +196,10 @@ static int launch(ffs_stream* s, const EncodedBatch& b, hipStream_t st, bool wit
     } else if (e == hipSuccess && with_decode) {
         const BshufBlocking& k = E.blocking;
         const DecodeArgs da{.comp = E.d_comp, .table = reinterpret_cast<const uint2*>(E.d_tab), .image = s->d_img, .frame_stride = L.frame_stride,
-                            .pitch = L.pitch, .W = L.W, .H = L.H, .elem_bytes = c->pixel_bytes, .blocks_per_frame = k.blocks, .block_elems = k.block_elems,
+                            .pitch = L.pitch, .W = L.W, .H = L.H, .elem_bytes = c->settings.pixel_bytes, .blocks_per_frame = k.blocks, .block_elems = k.block_elems,
                             .last_block_elems = k.last_elems, .tail_elems = k.tail_elems, .error = s->d_overflow};
         const dim3 grid(k.blocks + 1, n);
-        if (c->pixel_bytes == 2) hipLaunchKernelGGL(k_bshuf_lz4_decode<2>, grid, dim3(64), 0, st, da);
+        if (c->settings.pixel_bytes == 2) hipLaunchKernelGGL(k_bshuf_lz4_decode<2>, grid, dim3(64), 0, st, da);
         else hipLaunchKernelGGL(k_bshuf_lz4_decode<4>, grid, dim3(64), 0, st, da);
     }
     if (e == hipSuccess && with_decode) e = hipGetLastError();
@@ -238,7 +234,7 @@ static int ffs_submit_encoded_impl(ffs_stream* s, int codec, const void* const* 
     mark_busy(s);
     s->job_rc = FFS_OK;
     s->job_err.clear();
-    const ParamSnapshot snap = snapshot_of(c);
+    const ParamSnapshot snap = snapshot_of(c->settings);
     s->job = std::thread([s, c, snap, n_frames, b = std::move(b)]() {
         if (hipSetDevice(c->device) != hipSuccess) {
             s->job_rc = refuse(s->job_err, FFS_ERR_DEVICE, "hipSetDevice failed on the stream's helper thread");
@@ -285,7 +281,7 @@ extern "C" int ffs_decode_only_encoded(ffs_stream* s, int codec, const void* con
     HIP_TRY(c, hipEventElapsedTime(&ms, s->ev[0], s->ev[1]));
     if (ms_decode) *ms_decode = ms / iters;
     if (host_out) {
-        const size_t row = (size_t)L.W * c->pixel_bytes;
+        const size_t row = (size_t)L.W * c->settings.pixel_bytes;
         HIP_TRY(c, hipMemcpy2D(host_out, row, s->d_img, L.pitch, row, (size_t)L.H * n_frames, hipMemcpyDeviceToHost));
     }
     if (const char* text = encoded_corruption(flag)) {
@@ -331,7 +327,7 @@ void jfped_free_ctx(ffs_ctx* c) {
 }
 
 static int jfped_begin_impl(ffs_ctx* c) {
-    if (c->pixel_bytes != 4)
+    if (c->settings.pixel_bytes != 4)
         return refuse(c->err, FFS_ERR_INVALID, "ffs_ctx_jungfrau_pedestal_begin: raw Jungfrau words belong to contexts of 32-bit photon counts: the context must have pixel_bytes 4");
     if (c->inflight.load() > 0)
         return refuse(c->err, FFS_ERR_INVALID, "ffs_ctx_jungfrau_pedestal_begin: a batch or a fold of this context is in flight (wait for it first): a begin zeroes the accumulators");

@@ -1,7 +1,7 @@
 // ffs_internal.hpp -- what the translation units of libffs_hip.so share: the structs behind the opaque handles of
 // include/ffs_hip.h, error plumbing, and the few functions one unit calls in another.  Host side only; the kernels
 // live in kernels_*.hpp, each included by exactly one unit:
-//   ffs_context.hip  contexts, masks (kernels_mask.hpp), tuning, streams
+//   ffs_context.hip  contexts, masks (kernels_mask.hpp), the setters of parameters, scope, gain, gain map and calibration, tuning, streams
 //   ffs_submit.hip   one batch (enqueue_batch: plan_batch decides its path once, a BatchPlan with the launch geometry and the threshold route; then the resets,
 //                    the threshold stage and the sparse stage are launched from that plan), ffs_submit and ffs_submit_device
 //                    (kernels_stream / threshold / extended / window / ccl / chain / band)
@@ -20,6 +20,9 @@
 //   threshold_route.hpp  the predicate's variants, which instantiation of a kernel family serves one, and a batch's route through the
 //                        threshold stage (tests/threshold_route_check.cc)
 //   tuning.hpp           struct Tuning
+//   context_settings.hpp  a context's settings (ContextSettings, ffs_ctx::settings), the rules every ffs_ctx_set_* asks before it changes anything --
+//                        ranges, and the pairs of settings that do not combine, each stated once for both of its setters -- and what a batch
+//                        takes of the settings at submit (ParamSnapshot, snapshot_of) (tests/context_settings_check.cc)
 //   spot_background_model.hpp  the decisions of the per-spot background: quartile positions, status order, fence (tests/spot_background_check.cc)
 //   radial_threshold_model.hpp the decisions of the radial-profile threshold (kernels_radthr.hpp, included by ffs_products.hip): status order and the
 //                        cutoff's two separately rounded operations (tests/radial_threshold_check.cc)
@@ -57,6 +60,7 @@
 
 #include "ffs_hip.h"
 #include "ffs_device.h"
+#include "context_settings.hpp"
 #include "encoded_plan.hpp"
 #include "radial_threshold_model.hpp"
 #include "threshold_route.hpp"
@@ -84,24 +88,6 @@ struct ThreadError {
 // ---- tuning: struct Tuning, tuning.hpp ---------------------------------------------------------------------------
 
 struct ffs_stack3d;
-
-// What a batch is computed with: the context's parameters, its scope of max_valid and its detector gain as they were at submit (re-runs
-// inside ffs_wait keep them).  A new per-batch setting is a new field here.  gain_map: the context had a gain map at submit -- the route's
-// input; the map itself is a property of the context like the mask, and cannot change while a batch is in flight (ffs_ctx_set_gain_map).
-struct ParamSnapshot {
-    ffs_params params{};
-    int max_valid_scope = FFS_MAX_VALID_CENTRE;
-    double gain = 0.0;
-    bool gain_map = false;
-    uint32_t radial_bins = 0;   // bins of the context's radial bin map at submit (0: no map): the batch computes a profile over that many bins
-    bool pixel_stats = false;   // ffs_ctx_set_pixel_stats was on at submit: the batch's frames are folded into the context's per-pixel statistics, once
-    // The radial-profile threshold (FFS_ALGO_RADIAL_PROFILE): the shells of the map at submit when the parameters say that
-    // algorithm, else 0 -- its own field, because a one-frame re-run drops radial_bins (the profile is computed once) and still thresholds by
-    // shell -- and n_iqr (ffs_ctx_set_radial_threshold).  The map itself is the context's, like the gain map.
-    uint32_t radthr_bins = 0;
-    double n_iqr = 6.0;
-    int radial_blur = 0;        // ffs_ctx_set_radial_blur at submit (FFS_RADIAL_BLUR_*); plays a part only where radthr_bins does
-};
 
 // A few helper threads per context for ffs_wait's result assembly (wire records -> boxes, reflections, centre rows): one thread
 // moves a batch's 7 MB (45 000 components of 32 Eiger frames) in 0.21 ms -- two thirds of the time the GPU takes for the batch, and
@@ -153,25 +139,20 @@ struct ffs_ctx {
     int device = 0;
     Tuning tune;
     Layout L{};
-    int pixel_bytes = 2;
+    ContextSettings settings;   // what the ffs_ctx_set_* calls have stored (context_settings.hpp); snapshot per batch
     uint32_t max_batch = 1;
     uint32_t cap = 0;       // strong pixels per frame
     uint32_t max_comp = 0;  // components per frame
     int n_tiles = 0;
-    ffs_params params{};
-    int max_valid_scope = FFS_MAX_VALID_CENTRE;   // ffs_ctx_set_max_valid_scope: kept across ffs_ctx_set_params, snapshot per batch with the parameters
-    double gain = 0.0;                            // ffs_ctx_set_gain (0 = off): kept and snapshot the same way
-    // ffs_ctx_set_gain_map: [H][pitch_px] float32, allocated at the first set and kept (entries beyond W are 1); has_gain_map says whether it
-    // is in force, gain_map_min / _max are the extremes of its W * H entries (what the screens' per-batch switches are decided from)
+    // ffs_ctx_set_gain_map: [H][pitch_px] float32, allocated at the first set and kept (entries beyond W are 1); settings.gain_map says whether
+    // it is in force, gain_map_min / _max are the extremes of its W * H entries (what the screens' per-batch switches are decided from)
     float* d_gain_map = nullptr;
-    bool has_gain_map = false;
     float gain_map_min = 0.0f, gain_map_max = 0.0f;
     // ffs_ctx_set_jungfrau_calibration: six dense planes of jf_plane_stride floats (W * H rounded up to 8, so that the
-    // kernel's last group loads inside them), pedestal G0 G1 G2 then factor G0 G1 G2, allocated at the first set and kept; has_jf_cal says
-    // whether a calibration is in force.  Written only while no batch of the context is in flight.
+    // kernel's last group loads inside them), pedestal G0 G1 G2 then factor G0 G1 G2, allocated at the first set and kept;
+    // settings.jungfrau_calibration says whether one is in force.  Written only while no batch of the context is in flight.
     float* d_jf_cal = nullptr;
     size_t jf_plane_stride = 0;
-    bool has_jf_cal = false;
     // ffs_ctx_jungfrau_pedestal_begin: the accumulators of the dark-frame fold, one allocation made at the first begin and
     // freed by _end or with the context: count[3] (uint32), sum[3], sum_sq[3] (uint64), dense planes jfped_stride entries apart (W * H rounded
     // up to 8: the kernel's last group stays inside them).  Null: not begun.  jfped_st: the context's own HIP stream, in which the fold
@@ -183,19 +164,16 @@ struct ffs_ctx {
     hipStream_t jfped_st = nullptr;
     std::mutex jfped_mu;
     // ffs_ctx_set_radial_bins: [H][pitch_px] uint16 bin entries, allocated at the first set and kept (entries beyond W
-    // are 0xFFFF); radial_bins says whether a map is in force and how many bins it has (0 = none).  Like the gain map it cannot change under a batch.
+    // are 0xFFFF); settings.radial_bins says whether a map is in force and how many bins it has (0 = none).  Like the gain map it cannot change under a batch.
     uint16_t* d_radial_map = nullptr;
     uint8_t* d_radial_map8 = nullptr;   // the same rows in one byte an entry (0xFF: in no bin), behind the two-byte rows in the same allocation; written for maps of at most 255 bins
-    uint32_t radial_bins = 0;
-    double n_iqr = 6.0;                           // ffs_ctx_set_radial_threshold: kept across ffs_ctx_set_params, snapshot per batch
-    int radial_blur = 0;                          // ffs_ctx_set_radial_blur: likewise
     // ffs_ctx_set_pixel_stats: the four accumulator planes are one allocation, made at the first start and kept (count,
-    // max, sum, sum of squares, in that order; laid out in tiles: PixStatsLayout below).  stats_on: batches submitted from now on are folded in;
+    // max, sum, sum of squares, in that order; laid out in tiles: PixStatsLayout below).  settings.pixel_stats: batches submitted from now on are folded in;
     // stats_started: there has been a start, ffs_ctx_get_pixel_stats has something to hand out.  stats_st: the context's own HIP stream for the
     // launches (tuning "stats_stream" 0), made with the accumulators.  stats_mu: one launch at a time is put behind the previous one --
     // distinct ffs_streams are driven from distinct threads -- and adds its frames to stats_frames.
     uint8_t* d_stats = nullptr;
-    bool stats_on = false, stats_started = false;
+    bool stats_started = false;
     uint64_t stats_frames = 0;
     hipStream_t stats_st = nullptr;
     std::mutex stats_mu;
@@ -469,11 +447,11 @@ static int guarded(ffs_ctx* c, F&& body) {
         if (rc_ != FFS_OK) return rc_;   \
     } while (0)
 
+// a refusal: its text goes where the caller keeps errors (the context's text of the calling thread, or a helper thread's job_err)
+template <typename Err>
+static int refuse(Err& err, int rc, const std::string& text) { err = text; return rc; }
+
 // ---- small helpers ------------------------------------------------------------------------------------------
-static inline ParamSnapshot snapshot_of(const ffs_ctx* c) {
-    return ParamSnapshot{c->params, c->max_valid_scope, c->gain, c->has_gain_map, c->radial_bins, c->stats_on,
-                         c->params.algorithm == FFS_ALGO_RADIAL_PROFILE ? c->radial_bins : 0u, c->n_iqr, c->radial_blur};
-}
 // Where the per-pixel statistics lie (kernels_pixstats.hpp has the why): a lane owns px = 16 / pixel_bytes pixels of a row, lanes are numbered
 // row by row, sixty-four of them are a tile, and in every plane a lane's entries are chunks of 16 B, chunk k of lane l of tile t at
 // 16 B x ((t * chunks + k) * 64 + l).
@@ -489,7 +467,7 @@ struct PixStatsLayout {
 };
 static inline PixStatsLayout pixstats_layout(const ffs_ctx* c) {
     PixStatsLayout p;
-    p.px = 16u / (uint32_t)c->pixel_bytes;
+    p.px = 16u / (uint32_t)c->settings.pixel_bytes;
     p.groups = ((uint32_t)c->L.W + p.px - 1) / p.px;
     p.n_lanes = p.groups * (uint32_t)c->L.H;
     const size_t tiles = ((size_t)p.n_lanes + 63) / 64;
@@ -508,10 +486,6 @@ struct Rerun {
 };
 // extended algorithm: the strip erosion stores only the non-zero words of a signal-region plane that was cleared behind the previous batch
 static inline bool ext_sparse_erode(const Tuning& t) { return t.ext_erode != 0 && t.ext_e_sparse; }
-// window half-sizes of a parameter set (ffs_params.kernel_half_x / _y: 0 means 3)
-constexpr int kWinMaxHalf = 7;
-static inline int win_half(int v) { return v ? v : 3; }
-static inline bool win_default(const ffs_params& p) { return win_half(p.kernel_half_x) == 3 && win_half(p.kernel_half_y) == 3; }
 static inline uint32_t occ_frame_words(const Layout& L) { return (uint32_t)(((uint64_t)L.H * (L.mpitch / 16) + 31) / 32 + 2); }  // (+2: the chain reads a word ahead)
 // per-tile counts | ... | [last - 1] workgroups of k_frame_chain through with the bright list | [last] entries of the bright list;
 // a multiple of 256 bytes so that one fill clears it
@@ -527,6 +501,27 @@ static inline void mark_idle(ffs_stream* s) {
 template <typename T>
 static hipError_t dmalloc(T** p, size_t n_bytes) {
     return hipMalloc(reinterpret_cast<void**>(p), n_bytes + 256);
+}
+// What a setter may not do under a batch: FFS_OK while none of the context is in flight, else the refusal, `who` in front and `why` behind
+static inline int refuse_in_flight(ffs_ctx* c, const char* who, const char* why) {
+    if (c->inflight.load() == 0) return FFS_OK;
+    return refuse(c->err, FFS_ERR_INVALID, std::string(who) + ": a batch of this context is in flight (ffs_wait for it first)" + why);
+}
+// A per-pixel table of the context on the device: H rows of pitch_px entries, addressed like the pixel rows, the entries beyond W are `fill`.
+// *d_table is allocated at the first set, extra_bytes_per_entry behind the rows, and kept; `rows` is left holding what was copied.
+template <typename T>
+static int upload_pixel_table(ffs_ctx* c, const char* who, const char* what, const T* host, T fill, size_t extra_bytes_per_entry, T** d_table, std::vector<T>& rows) {
+    const Layout& L = c->L;
+    rows.assign((size_t)L.pitch_px * L.H, fill);
+    for (int y = 0; y < L.H; ++y) std::memcpy(rows.data() + (size_t)y * L.pitch_px, host + (size_t)y * L.W, (size_t)L.W * sizeof(T));
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (!*d_table && hipMalloc(reinterpret_cast<void**>(d_table), rows.size() * (sizeof(T) + extra_bytes_per_entry)) != hipSuccess) {
+        (void)hipGetLastError();
+        *d_table = nullptr;
+        return refuse(c->err, FFS_ERR_NOMEM, std::string(who) + ": hipMalloc(" + what + ") failed");
+    }
+    HIP_TRY(c, hipMemcpy(*d_table, rows.data(), rows.size() * sizeof(T), hipMemcpyHostToDevice));
+    return FFS_OK;
 }
 
 // ---- lifecycle: which handles are alive ---------------------------------------------------------------------

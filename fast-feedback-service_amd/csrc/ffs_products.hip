@@ -6,62 +6,34 @@
 #include "kernels_radthr.hpp"
 #include "kernels_pixstats.hpp"
 
+static_assert(kRadialBinsMax == kRadialMaxBins, "ffs_ctx_set_radial_bins accepts what k_radial's LDS holds");
+
 // ---- the radial profile (kernels_radial.hpp) -----------------------------------------------------------------
 // The bin map.  Everything is checked before anything changes; like the gain map, the device copy is written only while no batch of the
 // context is in flight, and NULL only switches the map off (a batch in flight took its bins at submit and its profile kernels read the
 // device copy, which stays).
 static int ffs_ctx_set_radial_bins_impl(ffs_ctx* c, const uint16_t* bin_of_pixel, uint32_t n_bins) {
-    const bool thresholds = c->params.algorithm == FFS_ALGO_RADIAL_PROFILE;   // (ffs_ctx_set_params has the other half of these two)
+    if (const std::string why = set_radial_bins(c->settings, bin_of_pixel != nullptr, n_bins); !why.empty()) return refuse(c->err, FFS_ERR_INVALID, why);
     if (!bin_of_pixel) {
-        if (thresholds) {
-            c->err = "ffs_ctx_set_radial_bins: the context's parameters say the radial_profile algorithm, which needs the map: set another algorithm first";
-            return FFS_ERR_INVALID;
-        }
-        c->radial_bins = 0;
+        c->settings.radial_bins = 0;
         return FFS_OK;
     }
-    if (n_bins < 1 || n_bins > kRadialMaxBins) {
-        c->err = "ffs_ctx_set_radial_bins: n_bins must be in 1.." + std::to_string(kRadialMaxBins) + ", got " + std::to_string(n_bins);
-        return FFS_ERR_INVALID;
-    }
-    if (thresholds && n_bins > kRadThrMaxBins) {
-        c->err = "ffs_ctx_set_radial_bins: the context's parameters say the radial_profile algorithm, which takes at most " + std::to_string(kRadThrMaxBins)
-                 + " bins, got " + std::to_string(n_bins);
-        return FFS_ERR_INVALID;
-    }
-    if (c->inflight.load() > 0) {
-        c->err = "ffs_ctx_set_radial_bins: a batch of this context is in flight (ffs_wait for it first): a batch keeps the map it was submitted with";
-        return FFS_ERR_INVALID;
-    }
-    const Layout& L = c->L;
-    const size_t n = (size_t)L.W * L.H;
+    FFS_TRY(refuse_in_flight(c, "ffs_ctx_set_radial_bins", ": a batch keeps the map it was submitted with"));
+    const size_t W = (size_t)c->L.W, n = W * c->L.H;
     for (size_t i = 0; i < n; ++i)
-        if (bin_of_pixel[i] >= n_bins && bin_of_pixel[i] != 0xFFFFu) {
-            c->err = "ffs_ctx_set_radial_bins: entry " + std::to_string(i) + " (x = " + std::to_string(i % (size_t)L.W) + ", y = " + std::to_string(i / (size_t)L.W)
-                     + ") is " + std::to_string(bin_of_pixel[i]) + ": every entry must be below n_bins = " + std::to_string(n_bins) + " or 0xFFFF (in no bin)";
-            return FFS_ERR_INVALID;
-        }
-    // rows of pitch_px entries, addressed like the pixel rows; the entries beyond W are in no bin
-    std::vector<uint16_t> rows((size_t)L.pitch_px * L.H, (uint16_t)0xFFFFu);
-    for (int y = 0; y < L.H; ++y) std::memcpy(rows.data() + (size_t)y * L.pitch_px, bin_of_pixel + (size_t)y * L.W, (size_t)L.W * sizeof(uint16_t));
-    HIP_TRY(c, hipSetDevice(c->device));
-    if (!c->d_radial_map) {
-        uint16_t* d = nullptr;
-        if (hipMalloc(reinterpret_cast<void**>(&d), rows.size() * (sizeof(uint16_t) + 1)) != hipSuccess) {
-            (void)hipGetLastError();
-            c->err = "ffs_ctx_set_radial_bins: hipMalloc(bin map) failed";
-            return FFS_ERR_NOMEM;
-        }
-        c->d_radial_map = d;
-        c->d_radial_map8 = reinterpret_cast<uint8_t*>(d + rows.size());
-    }
-    HIP_TRY(c, hipMemcpy(c->d_radial_map, rows.data(), rows.size() * sizeof(uint16_t), hipMemcpyHostToDevice));
+        if (bin_of_pixel[i] >= n_bins && bin_of_pixel[i] != 0xFFFFu)
+            return refuse(c->err, FFS_ERR_INVALID,
+                          "ffs_ctx_set_radial_bins: " + entry_text(i, W, bin_of_pixel[i]) + ": every entry must be below n_bins = " + std::to_string(n_bins) + " or 0xFFFF (in no bin)");
+    std::vector<uint16_t> rows;   // (the entries beyond W are in no bin; the one-byte rows lie behind the two-byte ones)
+    const bool first = !c->d_radial_map;
+    FFS_TRY(upload_pixel_table(c, "ffs_ctx_set_radial_bins", "bin map", bin_of_pixel, (uint16_t)0xFFFFu, 1, &c->d_radial_map, rows));
+    if (first) c->d_radial_map8 = reinterpret_cast<uint8_t*>(c->d_radial_map + rows.size());
     if (n_bins <= 255) {   // the one-byte form (tuning "radial_map8"): what a batch's launch takes is decided from n_bins and the tuning alone
         std::vector<uint8_t> rows8(rows.size());
         for (size_t i = 0; i < rows.size(); ++i) rows8[i] = (uint8_t)rows[i];   // (0xFFFF -> 0xFF; every other entry is below 255)
         HIP_TRY(c, hipMemcpy(c->d_radial_map8, rows8.data(), rows8.size(), hipMemcpyHostToDevice));
     }
-    c->radial_bins = n_bins;
+    c->settings.radial_bins = n_bins;
     return FFS_OK;
 }
 extern "C" int ffs_ctx_set_radial_bins(ffs_ctx* c, const uint16_t* bin_of_pixel, uint32_t n_bins) {
@@ -95,8 +67,7 @@ int radial_ensure_buffers(ffs_stream* s, uint32_t bins) {
         s->radial_part_entries = 0;
         if (hipMalloc(reinterpret_cast<void**>(&s->d_radial_part), slots * bins * 20u) != hipSuccess) {
             (void)hipGetLastError();
-            c->err = "radial profile: hipMalloc(partials) failed";
-            return FFS_ERR_NOMEM;
+            return refuse(c->err, FFS_ERR_NOMEM, "radial profile: hipMalloc(partials) failed");
         }
         s->radial_part_entries = slots * bins;
     }
@@ -114,8 +85,7 @@ int radial_ensure_buffers(ffs_stream* s, uint32_t bins) {
             if (hipHostMalloc(reinterpret_cast<void**>(&s->h_radial[i]), bytes, hipHostMallocDefault) != hipSuccess
                 || hipHostGetDevicePointer(reinterpret_cast<void**>(&s->h_radial_dev[i]), s->h_radial[i], 0) != hipSuccess) {
                 (void)hipGetLastError();
-                c->err = "radial profile: hipHostMalloc(results) failed";
-                return FFS_ERR_NOMEM;
+                return refuse(c->err, FFS_ERR_NOMEM, "radial profile: hipHostMalloc(results) failed");
             }
         }
         s->h_radial_bins = bins;
@@ -156,15 +126,12 @@ int radial_launch(ffs_stream* s, const void* d_img, size_t pitch, size_t fstride
     a.r_sum = reinterpret_cast<uint64_t*>(out);
     a.r_sq = a.r_sum + B * bins;
     a.r_count = reinterpret_cast<uint32_t*>(a.r_sq + B * bins);
-    if ((size_t)n_frames * a.in.n_bands * bins > part || bins > s->h_radial_bins || !a.in.bins) {
-        c->err = "radial profile: the stream's buffers do not hold this batch";
-        return FFS_ERR_INVALID;
-    }
+    if ((size_t)n_frames * a.in.n_bands * bins > part || bins > s->h_radial_bins || !a.in.bins) return refuse(c->err, FFS_ERR_INVALID, "radial profile: the stream's buffers do not hold this batch");
     const dim3 grid(n_frames, a.in.n_bands);
     // (the one-byte form of the map: tuning "radial_map8", for maps of at most 255 bins -- ffs_ctx_set_radial_bins keeps both forms then)
     a.in.bins8 = (c->tune.radial_map8 && bins <= 255) ? c->d_radial_map8 : nullptr;
     using RadialKernel = void (*)(RadialArgs);
-    const RadialKernel k = c->pixel_bytes == 2 ? (a.in.bins8 ? k_radial<uint16_t, true> : k_radial<uint16_t, false>)
+    const RadialKernel k = c->settings.pixel_bytes == 2 ? (a.in.bins8 ? k_radial<uint16_t, true> : k_radial<uint16_t, false>)
                                                : (a.in.bins8 ? k_radial<uint32_t, true> : k_radial<uint32_t, false>);
     hipExtLaunchKernelGGL(k, grid, dim3(kRadialThreads), radial_lds_bytes(bins), st, start, nullptr, 0, a);
     hipExtLaunchKernelGGL(k_radial_sum, dim3((bins + 255) / 256, n_frames), dim3(256), 0, st, nullptr, stop, 0, a);
@@ -213,14 +180,12 @@ void radial_publish(ffs_stream* s) {
 extern "C" int ffs_stream_radial_profile(ffs_stream* s, uint32_t frame_in_batch, ffs_radial_profile* out) {
     if (!s || !out || !stream_handle_ok(s)) return FFS_ERR_INVALID;
     ffs_ctx* c = s->ctx;
-    if (!s->radial_out || s->radial_out_bins == 0) {
-        c->err = "ffs_stream_radial_profile: the last batch ffs_wait returned on this stream was submitted without a bin map (ffs_ctx_set_radial_bins)";
-        return FFS_ERR_INVALID;
-    }
-    if (frame_in_batch >= s->radial_out_frames) {
-        c->err = "ffs_stream_radial_profile: frame_in_batch " + std::to_string(frame_in_batch) + " is out of range: the batch had " + std::to_string(s->radial_out_frames) + " frames";
-        return FFS_ERR_INVALID;
-    }
+    if (!s->radial_out || s->radial_out_bins == 0)
+        return refuse(c->err, FFS_ERR_INVALID,
+                      "ffs_stream_radial_profile: the last batch ffs_wait returned on this stream was submitted without a bin map (ffs_ctx_set_radial_bins)");
+    if (frame_in_batch >= s->radial_out_frames)
+        return refuse(c->err, FFS_ERR_INVALID,
+                      "ffs_stream_radial_profile: frame_in_batch " + std::to_string(frame_in_batch) + " is out of range: the batch had " + std::to_string(s->radial_out_frames) + " frames");
     // (the layout k_radial_sum writes: sums, sums of squares, counts, [max_batch][bins] each)
     const size_t bins = s->radial_out_bins, plane = (size_t)s->max_batch * bins;
     const uint64_t* sum = reinterpret_cast<const uint64_t*>(s->radial_out);
@@ -234,21 +199,15 @@ extern "C" int ffs_stream_radial_profile(ffs_stream* s, uint32_t frame_in_batch,
 // ---- the radial-profile threshold (kernels_radthr.hpp) --------------------------------------------------------
 extern "C" int ffs_ctx_set_radial_threshold(ffs_ctx* c, double n_iqr) {
     if (!c) return FFS_ERR_INVALID;
-    if (!std::isfinite(n_iqr) || n_iqr < 0.0 || n_iqr > kRadThrMaxNIqr) {
-        c->err = "ffs_ctx_set_radial_threshold: n_iqr must be finite and in 0 .. 2^20 (the cutoff median + n_iqr * iqr is a uint32)";
-        return FFS_ERR_INVALID;
-    }
-    c->n_iqr = n_iqr;
+    if (const std::string why = set_radial_threshold(c->settings, n_iqr); !why.empty()) return refuse(c->err, FFS_ERR_INVALID, why);
+    c->settings.n_iqr = n_iqr;
     return FFS_OK;
 }
 
 extern "C" int ffs_ctx_set_radial_blur(ffs_ctx* c, int blur) {
     if (!c) return FFS_ERR_INVALID;
-    if (blur != FFS_RADIAL_BLUR_NONE && blur != FFS_RADIAL_BLUR_NARROW && blur != FFS_RADIAL_BLUR_WIDE) {
-        c->err = "ffs_ctx_set_radial_blur: blur must be FFS_RADIAL_BLUR_NONE (0), _NARROW (1) or _WIDE (2), got " + std::to_string(blur);
-        return FFS_ERR_INVALID;
-    }
-    c->radial_blur = blur;
+    if (const std::string why = set_radial_blur(c->settings, blur); !why.empty()) return refuse(c->err, FFS_ERR_INVALID, why);
+    c->settings.radial_blur = blur;
     return FFS_OK;
 }
 
@@ -290,18 +249,16 @@ int radthr_ensure_buffers(ffs_stream* s) {
     if (s->d_radthr_hist) return FFS_OK;
     ffs_ctx* c = s->ctx;
     for (int k = 1; k <= 4; ++k)   // the two forms, then the two blurred kernels
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(k <= 2 ? radthr_hist_kernel(c->pixel_bytes, k) : radthr_hist_blur_kernel(c->pixel_bytes, k - 2)),
+        if (hipFuncSetAttribute(reinterpret_cast<const void*>(k <= 2 ? radthr_hist_kernel(c->settings.pixel_bytes, k) : radthr_hist_blur_kernel(c->settings.pixel_bytes, k - 2)),
                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)radthr_lds_bytes(kRadThrMaxBins)) != hipSuccess) {
             (void)hipGetLastError();
-            c->err = "radial_profile threshold: the device refuses the histogram's " + std::to_string(radthr_lds_bytes(kRadThrMaxBins)) + " bytes of LDS";
-            return FFS_ERR_DEVICE;
+            return refuse(c->err, FFS_ERR_DEVICE, "radial_profile threshold: the device refuses the histogram's " + std::to_string(radthr_lds_bytes(kRadThrMaxBins)) + " bytes of LDS");
         }
     const size_t shells = (size_t)s->max_batch * kRadThrMaxBins;
     uint32_t* d = nullptr;
     if (hipMalloc(reinterpret_cast<void**>(&d), shells * (kRadThrCounters + 1) * 4u) != hipSuccess) {
         (void)hipGetLastError();
-        c->err = "radial_profile threshold: hipMalloc(histograms) failed";
-        return FFS_ERR_NOMEM;
+        return refuse(c->err, FFS_ERR_NOMEM, "radial_profile threshold: hipMalloc(histograms) failed");
     }
     for (int i = 0; i < 2; ++i)
         if (hipHostMalloc(reinterpret_cast<void**>(&s->h_radthr[i]), shells * sizeof(ffs_radial_shell), hipHostMallocDefault) != hipSuccess
@@ -312,8 +269,7 @@ int radthr_ensure_buffers(ffs_stream* s) {
                 if (p) (void)hipHostFree(p);
                 p = nullptr;
             }
-            c->err = "radial_profile threshold: hipHostMalloc(records) failed";
-            return FFS_ERR_NOMEM;
+            return refuse(c->err, FFS_ERR_NOMEM, "radial_profile threshold: hipHostMalloc(records) failed");
         }
     s->d_radthr_hist = d;
     s->d_radthr_cut = d + shells * kRadThrCounters;
@@ -350,7 +306,7 @@ void launch_radthr_hist(ffs_stream* s, const ThresholdArgs& t, uint32_t n_frames
     const RadThrArgs a = make_radthr_args(s, t, n_frames);
     (void)hipMemsetAsync(a.hist, 0, (size_t)n_frames * a.in.n_bins * kRadThrCounters * 4u, s->st);
     const int blur = s->batch.radial_blur;
-    hipExtLaunchKernelGGL(blur ? radthr_hist_blur_kernel(s->ctx->pixel_bytes, blur) : radthr_hist_kernel(s->ctx->pixel_bytes, s->ctx->tune.radthr_form),
+    hipExtLaunchKernelGGL(blur ? radthr_hist_blur_kernel(s->ctx->settings.pixel_bytes, blur) : radthr_hist_kernel(s->ctx->settings.pixel_bytes, s->ctx->tune.radthr_form),
                           dim3(n_frames, a.in.n_bands), dim3(kRadThrHistThreads), radthr_lds_bytes(a.in.n_bins), s->st, start, stop, 0, a);
 }
 // ... and the cutoffs and the strong pixels behind it; `stop` rides on the last dispatch
@@ -360,11 +316,11 @@ void launch_radthr_rest(ffs_stream* s, const ThresholdArgs& t, uint32_t n_frames
     if (const int blur = s->batch.radial_blur) {   // a wave per run of rows of a strip of kRadBlurOwners groups (the kernel's radblur_strips)
         const uint32_t strips = ((uint32_t)(a.in.W + 7) / 8u + kRadBlurOwners - 1u) / kRadBlurOwners;
         const uint32_t runs = ((uint32_t)a.in.H + kRadBlurRunRows - 1u) / kRadBlurRunRows;
-        hipExtLaunchKernelGGL(radthr_strong_blur_kernel(s->ctx->pixel_bytes, blur), dim3(strips * runs, n_frames), dim3(64), 0, s->st, nullptr, stop, 0, a);
+        hipExtLaunchKernelGGL(radthr_strong_blur_kernel(s->ctx->settings.pixel_bytes, blur), dim3(strips * runs, n_frames), dim3(64), 0, s->st, nullptr, stop, 0, a);
         return;
     }
     const dim3 grid(a.s_strips * (uint32_t)a.n_tiles, n_frames);
-    if (s->ctx->pixel_bytes == 2) hipExtLaunchKernelGGL(k_radthr_strong<uint16_t>, grid, dim3(64), 0, s->st, nullptr, stop, 0, a);
+    if (s->ctx->settings.pixel_bytes == 2) hipExtLaunchKernelGGL(k_radthr_strong<uint16_t>, grid, dim3(64), 0, s->st, nullptr, stop, 0, a);
     else hipExtLaunchKernelGGL(k_radthr_strong<uint32_t>, grid, dim3(64), 0, s->st, nullptr, stop, 0, a);
 }
 
@@ -384,14 +340,12 @@ void radthr_publish(ffs_stream* s) {
 extern "C" int ffs_stream_radial_thresholds(ffs_stream* s, uint32_t frame_in_batch, const ffs_radial_shell** out, uint32_t* n_bins) {
     if (!s || !out || !n_bins || !stream_handle_ok(s)) return FFS_ERR_INVALID;
     ffs_ctx* c = s->ctx;
-    if (!s->radthr_out || s->radthr_out_bins == 0) {
-        c->err = "ffs_stream_radial_thresholds: the last batch ffs_wait returned on this stream did not run the radial_profile algorithm (FFS_ALGO_RADIAL_PROFILE)";
-        return FFS_ERR_INVALID;
-    }
-    if (frame_in_batch >= s->radthr_out_frames) {
-        c->err = "ffs_stream_radial_thresholds: frame_in_batch " + std::to_string(frame_in_batch) + " is out of range: the batch had " + std::to_string(s->radthr_out_frames) + " frames";
-        return FFS_ERR_INVALID;
-    }
+    if (!s->radthr_out || s->radthr_out_bins == 0)
+        return refuse(c->err, FFS_ERR_INVALID,
+                      "ffs_stream_radial_thresholds: the last batch ffs_wait returned on this stream did not run the radial_profile algorithm (FFS_ALGO_RADIAL_PROFILE)");
+    if (frame_in_batch >= s->radthr_out_frames)
+        return refuse(c->err, FFS_ERR_INVALID,
+                      "ffs_stream_radial_thresholds: frame_in_batch " + std::to_string(frame_in_batch) + " is out of range: the batch had " + std::to_string(s->radthr_out_frames) + " frames");
     *out = s->radthr_out + (size_t)frame_in_batch * s->radthr_out_bins;   // (the layout k_radthr_cut writes: [frame][bins of the batch])
     *n_bins = s->radthr_out_bins;
     return FFS_OK;
@@ -404,47 +358,38 @@ int pixstats_ensure(ffs_ctx* c) {
     if (!c->d_stats && hipMalloc(reinterpret_cast<void**>(&c->d_stats), pixstats_layout(c).bytes()) != hipSuccess) {
         (void)hipGetLastError();
         c->d_stats = nullptr;
-        c->err = "pixel statistics: hipMalloc(accumulators, " + std::to_string(pixstats_layout(c).bytes() >> 20) + " MB) failed";
-        return FFS_ERR_NOMEM;
+        return refuse(c->err, FFS_ERR_NOMEM, "pixel statistics: hipMalloc(accumulators, " + std::to_string(pixstats_layout(c).bytes() >> 20) + " MB) failed");
     }
     return FFS_OK;
 }
 
 extern "C" int ffs_ctx_set_pixel_stats(ffs_ctx* c, int mode) {
     if (!c) return FFS_ERR_INVALID;
-    if (mode != FFS_PIXEL_STATS_OFF && mode != FFS_PIXEL_STATS_START && mode != FFS_PIXEL_STATS_RESUME) {
-        c->err = "ffs_ctx_set_pixel_stats: mode must be FFS_PIXEL_STATS_OFF (0), _START (1) or _RESUME (2), got " + std::to_string(mode);
-        return FFS_ERR_INVALID;
-    }
+    if (mode != FFS_PIXEL_STATS_OFF && mode != FFS_PIXEL_STATS_START && mode != FFS_PIXEL_STATS_RESUME)
+        return refuse(c->err, FFS_ERR_INVALID, "ffs_ctx_set_pixel_stats: mode must be FFS_PIXEL_STATS_OFF (0), _START (1) or _RESUME (2), got " + std::to_string(mode));
     if (mode == FFS_PIXEL_STATS_OFF) {   // (at any time: a batch in flight carries its own "on")
-        c->stats_on = false;
+        c->settings.pixel_stats = false;
         return FFS_OK;
     }
     if (mode == FFS_PIXEL_STATS_RESUME && c->stats_started) {
-        c->stats_on = true;
+        c->settings.pixel_stats = true;
         return FFS_OK;
     }
-    if (c->inflight.load() > 0) {
-        c->err = "ffs_ctx_set_pixel_stats: a batch of this context is in flight (ffs_wait for it first): a start zeroes the accumulators";
-        return FFS_ERR_INVALID;
-    }
+    FFS_TRY(refuse_in_flight(c, "ffs_ctx_set_pixel_stats", ": a start zeroes the accumulators"));
     if (const int rc = pixstats_ensure(c); rc != FFS_OK) return rc;
     HIP_TRY(c, hipMemsetAsync(c->d_stats, 0, pixstats_layout(c).bytes(), c->stats_st));
     HIP_TRY(c, hipStreamSynchronize(c->stats_st));
     std::lock_guard<std::mutex> lock(c->stats_mu);
     c->stats_frames = 0;
     c->stats_started = true;
-    c->stats_on = true;
+    c->settings.pixel_stats = true;
     return FFS_OK;
 }
 
 int pixstats_launch(ffs_ctx* c, const void* d_img, size_t pitch, size_t fstride, uint32_t n_frames, long long max_valid, hipStream_t st, hipEvent_t start,
                     hipEvent_t stop) {
     const PixStatsLayout P = pixstats_layout(c);
-    if (!c->d_stats || n_frames == 0) {
-        c->err = "pixel statistics: the context has no accumulators";
-        return FFS_ERR_INVALID;
-    }
+    if (!c->d_stats || n_frames == 0) return refuse(c->err, FFS_ERR_INVALID, "pixel statistics: the context has no accumulators");
     PixStatsArgs a{};
     a.frame_stride = fstride;
     a.pitch = (uint32_t)pitch;
@@ -461,7 +406,7 @@ int pixstats_launch(ffs_ctx* c, const void* d_img, size_t pitch, size_t fstride,
         a.image = static_cast<const uint8_t*>(d_img) + (size_t)f0 * fstride;
         a.n_frames = std::min(n_frames - f0, kPixStatsMaxFrames);
         const bool first = f0 == 0, last = n_frames - f0 <= kPixStatsMaxFrames;
-        if (c->pixel_bytes == 2) hipExtLaunchKernelGGL(k_pixel_stats<uint16_t>, grid, dim3(kPixStatsThreads), 0, st, first ? start : nullptr, last ? stop : nullptr, 0, a);
+        if (c->settings.pixel_bytes == 2) hipExtLaunchKernelGGL(k_pixel_stats<uint16_t>, grid, dim3(kPixStatsThreads), 0, st, first ? start : nullptr, last ? stop : nullptr, 0, a);
         else hipExtLaunchKernelGGL(k_pixel_stats<uint32_t>, grid, dim3(kPixStatsThreads), 0, st, first ? start : nullptr, last ? stop : nullptr, 0, a);
     }
     HIP_TRY(c, hipGetLastError());
@@ -505,14 +450,8 @@ int join_pixel_stats(ffs_stream* s) {
 // Everything is checked before anything is copied.  No batch is in flight, so every launch lies ahead of an event some ffs_wait has seen
 // -- the streams are synchronised all the same, for a batch whose wait failed -- and the planes are copied one at a time and un-interleaved.
 static int ffs_ctx_get_pixel_stats_impl(ffs_ctx* c, ffs_pixel_stats* out) {
-    if (!c->stats_started) {
-        c->err = "ffs_ctx_get_pixel_stats: no statistics yet (ffs_ctx_set_pixel_stats(ctx, FFS_PIXEL_STATS_START) first)";
-        return FFS_ERR_INVALID;
-    }
-    if (c->inflight.load() > 0) {
-        c->err = "ffs_ctx_get_pixel_stats: a batch of this context is in flight (ffs_wait for it first)";
-        return FFS_ERR_INVALID;
-    }
+    if (!c->stats_started) return refuse(c->err, FFS_ERR_INVALID, "ffs_ctx_get_pixel_stats: no statistics yet (ffs_ctx_set_pixel_stats(ctx, FFS_PIXEL_STATS_START) first)");
+    FFS_TRY(refuse_in_flight(c, "ffs_ctx_get_pixel_stats", ""));
     HIP_TRY(c, hipSetDevice(c->device));
     HIP_TRY(c, hipStreamSynchronize(c->stats_st));
     if (c->dense_st) HIP_TRY(c, hipStreamSynchronize(c->dense_st));
@@ -541,9 +480,6 @@ static int ffs_ctx_get_pixel_stats_impl(ffs_ctx* c, ffs_pixel_stats* out) {
 }
 extern "C" int ffs_ctx_get_pixel_stats(ffs_ctx* c, ffs_pixel_stats* out) {
     if (!c) return FFS_ERR_INVALID;
-    if (!out) {
-        c->err = "ffs_ctx_get_pixel_stats: out is NULL";
-        return FFS_ERR_INVALID;
-    }
+    if (!out) return refuse(c->err, FFS_ERR_INVALID, "ffs_ctx_get_pixel_stats: out is NULL");
     return guarded(c, [&] { return ffs_ctx_get_pixel_stats_impl(c, out); });
 }

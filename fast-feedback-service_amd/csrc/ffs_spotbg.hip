@@ -134,7 +134,7 @@ static int spot_backgrounds_impl(ffs_stream* s, uint32_t border, const ffs_spot_
     (void)hipGetLastError();
     HIP_TRY(c, hipMemcpyAsync(s->d_bg_boxes, s->h_bg_boxes, n * sizeof(SpotBgBox), hipMemcpyHostToDevice, s->bg_st));
     const dim3 grid((uint32_t)((n + kSpotBgWaves - 1) / kSpotBgWaves));
-    if (c->pixel_bytes == 2) hipExtLaunchKernelGGL(k_spot_background<uint16_t>, grid, dim3(kSpotBgThreads), 0, s->bg_st, s->bg_ev[0], s->bg_ev[1], 0, a);
+    if (c->settings.pixel_bytes == 2) hipExtLaunchKernelGGL(k_spot_background<uint16_t>, grid, dim3(kSpotBgThreads), 0, s->bg_st, s->bg_ev[0], s->bg_ev[1], 0, a);
     else hipExtLaunchKernelGGL(k_spot_background<uint32_t>, grid, dim3(kSpotBgThreads), 0, s->bg_st, s->bg_ev[0], s->bg_ev[1], 0, a);
     HIP_TRY(c, hipGetLastError());
     HIP_TRY(c, hipEventSynchronize(s->bg_ev[1]));

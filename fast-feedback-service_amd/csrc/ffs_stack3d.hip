@@ -751,8 +751,8 @@ static int stack3d_finish_impl(ffs_stack3d* st, const ffs_reflection** reflectio
             sa.slice_begin = st->d_begin.p;
             sa.n_slices = nz;
             sa.zs = st->d_z.p;
-            sa.min_spot_size = c->params.min_spot_size_3d;
-            sa.max_sep = c->params.max_peak_centroid_separation;
+            sa.min_spot_size = c->settings.params.min_spot_size_3d;
+            sa.max_sep = c->settings.params.max_peak_centroid_separation;
             sa.recs = st->d_recs.p;
             sa.summary = st->d_small.p + 8;
             sa.chunk_roots = st->d_chunk_roots.p;

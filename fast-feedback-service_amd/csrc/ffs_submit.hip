@@ -27,7 +27,7 @@ bool chain_prepare_device() {   // more than 64 KB of dynamic LDS has to be aske
 // ---- the threshold stage's arguments: buffers and pitches, the predicate's constants, the launch geometry ------------------
 ThresholdRoute batch_route(const ffs_stream* s, const Rerun& how) {
     const ParamSnapshot& b = s->batch;
-    return threshold_route(b.params.algorithm, s->ctx->pixel_bytes, win_default(b.params), b.max_valid_scope, b.params.max_valid, b.gain, how.threshold_path,
+    return threshold_route(b.params.algorithm, s->ctx->settings.pixel_bytes, win_default(b.params), b.max_valid_scope, b.params.max_valid, b.gain, how.threshold_path,
                            s->ctx->tune, b.gain_map);
 }
 static void set_buffers(ThresholdArgs& a, const ffs_stream* s, const void* img, size_t pitch, size_t fstride, const ThresholdRoute& route) {
@@ -70,8 +70,8 @@ static void set_buffers(ThresholdArgs& a, const ffs_stream* s, const void* img, 
     a.dbg_prio = c->tune.stream_prio;
     a.ginfo = c->d_ginfo;
     a.mmap = c->d_mmap;
-    a.gpitch = ginfo_pitch(L, c->pixel_bytes);
-    a.gpf = groups_per_row(L, c->pixel_bytes);
+    a.gpitch = ginfo_pitch(L, c->settings.pixel_bytes);
+    a.gpf = groups_per_row(L, c->settings.pixel_bytes);
     a.dplane = s->d_dplane;
     a.eplane = s->d_eplane;
     a.eplane_clean = s->ext_e_clean ? 1 : 0;
@@ -151,7 +151,7 @@ static void set_geometry(ThresholdArgs& a, uint32_t n_frames, const StreamGeomet
     a.ext_bands = e.ext_bands;
 }
 StreamGeometry batch_stream_geometry(const ffs_stream* s, size_t fstride, uint32_t n_frames) {
-    return stream_geometry(s->ctx->L, s->ctx->pixel_bytes, fstride, n_frames, s->ctx->tune);
+    return stream_geometry(s->ctx->L, s->ctx->settings.pixel_bytes, fstride, n_frames, s->ctx->tune);
 }
 ThresholdArgs make_threshold_args(ffs_stream* s, const void* img, size_t pitch, size_t fstride, uint32_t n_frames, const StreamGeometry& g,
                                   const ThresholdRoute& route) {
@@ -172,8 +172,8 @@ static dim3 stream_grid(const ThresholdArgs& a, const StreamGeometry& g) {
 // the extended algorithm's first pass (16-bit pixels only) exist with two rows.
 using StreamKernel = void (*)(ThresholdArgs);
 static StreamKernel stream_kernel(const ffs_ctx* c, bool dense_mask, bool extended) {
-    const int rows = std::clamp(c->tune.rows_ahead, 2, c->pixel_bytes == 4 ? 3 : 4);
-    if (c->pixel_bytes == 4) return dense_mask ? k_stream_u32<2, true> : rows == 3 ? k_stream_u32<3, false> : k_stream_u32<2, false>;
+    const int rows = std::clamp(c->tune.rows_ahead, 2, c->settings.pixel_bytes == 4 ? 3 : 4);
+    if (c->settings.pixel_bytes == 4) return dense_mask ? k_stream_u32<2, true> : rows == 3 ? k_stream_u32<3, false> : k_stream_u32<2, false>;
     if (extended) return dense_mask ? k_stream_u16<2, true, true> : k_stream_u16<2, true, false>;
     if (dense_mask) return k_stream_u16<2, false, true>;
     return rows == 4 ? k_stream_u16<4, false, false> : rows == 3 ? k_stream_u16<3, false, false> : k_stream_u16<2, false, false>;
@@ -220,13 +220,13 @@ static void launch_window_t(const ThresholdArgs& a, dim3 grid, hipStream_t st, h
 }
 static void launch_window(ffs_stream* s, const ThresholdRoute& route, const ThresholdArgs& a, uint32_t n_frames, hipEvent_t start, hipEvent_t stop) {
     const dim3 grid((unsigned)(a.w_strips * a.w_bands), n_frames);
-    with_kernel_tag(s->ctx->pixel_bytes, route.variant, [&](auto tag) {
+    with_kernel_tag(s->ctx->settings.pixel_bytes, route.variant, [&](auto tag) {
         using T = decltype(tag);
         launch_window_t<typename T::pixel, T::of(KernelFamily::kWindow)>(a, grid, s->st, start, stop);
     });
 }
 static void launch_bright_fix(ffs_stream* s, const ThresholdArgs& a, hipStream_t st) {
-    if (s->ctx->pixel_bytes == 4) hipLaunchKernelGGL(k_bright_fix<uint32_t>, dim3(32), dim3(256), 0, st, a);
+    if (s->ctx->settings.pixel_bytes == 4) hipLaunchKernelGGL(k_bright_fix<uint32_t>, dim3(32), dim3(256), 0, st, a);
     else hipLaunchKernelGGL(k_bright_fix<uint16_t>, dim3(32), dim3(256), 0, st, a);
 }
 // path 1: every pixel marked in the plane (decided strong pixels and bright-window candidates alike) takes the gathered
@@ -234,7 +234,7 @@ static void launch_bright_fix(ffs_stream* s, const ThresholdArgs& a, hipStream_t
 static void launch_exact(ffs_stream* s, const ThresholdRoute& route, const ThresholdArgs& a, uint32_t n_frames, hipStream_t st) {
     const dim3 grid((unsigned)a.n_tiles, n_frames);
     // (a variant other than photon-count: the cross-check path, the only one that gets here with it)
-    with_kernel_tag(s->ctx->pixel_bytes, route.variant, [&](auto tag) {
+    with_kernel_tag(s->ctx->settings.pixel_bytes, route.variant, [&](auto tag) {
         using T = decltype(tag);
         if (route.window_3x3) hipLaunchKernelGGL((k_exact<typename T::pixel, T::of(KernelFamily::kExact)>), grid, dim3(256), 0, st, a);
         else hipLaunchKernelGGL((k_exact_w<typename T::pixel, T::of(KernelFamily::kExact)>), grid, dim3(256), 0, st, a);   // (the runtime-window gather: exact_strong_w)
@@ -258,7 +258,7 @@ static void launch_ext_first(ffs_stream* s, const ThresholdRoute& route, const T
         return;
     }
     dim3 g1((unsigned)(a.ext_strips * a.ext_bands), n_frames);
-    with_kernel_tag(s->ctx->pixel_bytes, route.variant, [&](auto tag) {
+    with_kernel_tag(s->ctx->settings.pixel_bytes, route.variant, [&](auto tag) {
         using T = decltype(tag);
         hipExtLaunchKernelGGL((k_ext_first<typename T::pixel, T::of(KernelFamily::kExtFirst)>), g1, dim3(64), 0, s->st, start, stop, 0, a);
     });
@@ -285,7 +285,7 @@ static void launch_ext_rest(ffs_stream* s, const ThresholdRoute& route, const Th
         const unsigned erode_lanes = (a.mpitch / 4) * (unsigned)((a.H + kErodeRows - 1) / kErodeRows);
         hipLaunchKernelGGL(k_ext_erode, dim3((erode_lanes + 255) / 256, n_frames), dim3(256), 0, st, a);
     }
-    with_kernel_tag(s->ctx->pixel_bytes, route.variant, [&](auto tag) {
+    with_kernel_tag(s->ctx->settings.pixel_bytes, route.variant, [&](auto tag) {
         using T = decltype(tag);
         hipLaunchKernelGGL((k_ext_final<typename T::pixel, T::of(KernelFamily::kExtFinal)>), g3, dim3(256), 0, st, a);
     });
@@ -315,7 +315,7 @@ static bool wave_logs_possible(const ffs_stream* s, const ThresholdArgs& a, cons
     const Layout& L = c->L;
     return c->tune.strong_log != 0 && !a.bright_to_plane && !s->log_off && !how.plane && s->st2 != s->st && c->chain_ok
            && s->batch.params.algorithm != FFS_ALGO_DISPERSION_EXTENDED && c->n_tiles <= kChainMaxTiles && L.H <= kChainMaxRows
-           && strips_per_frame(L, c->pixel_bytes) <= 16u && a.band_rows <= 1024 && L.W <= 65535;
+           && strips_per_frame(L, c->settings.pixel_bytes) <= 16u && a.band_rows <= 1024 && L.W <= 65535;
 }
 // The stream's logs hold `slots` waves: allocated on first use; false: no memory for them.
 static bool ensure_wave_logs(ffs_stream* s, size_t slots) {
@@ -346,7 +346,7 @@ bool wave_logs_for(ffs_stream* s, ThresholdArgs& a, const StreamGeometry& g, con
     // size never re-allocates: hipFree synchronises the whole device, i.e. every other worker's batches in flight.  (A stream is
     // idle here -- submit refuses a busy one, and a re-run inside ffs_wait comes after the batch's last event -- so nothing of
     // its own has to be waited for if it does happen: a tuning change between batches.)
-    if (slots > s->wlog_waves) slots = std::max(slots, max_stream_log_slots(s->ctx->L, s->ctx->pixel_bytes, a.frame_stride, s->max_batch, s->ctx->tune));
+    if (slots > s->wlog_waves) slots = std::max(slots, max_stream_log_slots(s->ctx->L, s->ctx->settings.pixel_bytes, a.frame_stride, s->max_batch, s->ctx->tune));
     if (!ensure_wave_logs(s, slots)) return false;
     a.wlog = s->d_wlog;
     a.wlog_n = s->d_wlog_n;
@@ -377,7 +377,7 @@ int check_layout(ffs_stream* s, size_t pitch, size_t fstride, uint32_t n_frames)
         c->err = "n_frames must be in 1..max_batch";
         return FFS_ERR_INVALID;
     }
-    if (pitch % 16 || pitch < (size_t)c->L.pitch_px * c->pixel_bytes || pitch >= (1ull << 32)
+    if (pitch % 16 || pitch < (size_t)c->L.pitch_px * c->settings.pixel_bytes || pitch >= (1ull << 32)
         || fstride < pitch * c->L.H || (pitch * c->L.H) >= (1ull << 32)) {
         c->err = "device layout: pitch must be a multiple of 16 bytes and >= round_up(width,128)*pixel_bytes; "
                  "frame_stride >= pitch*height";
@@ -418,10 +418,10 @@ static bool ensure_band_buffers(ffs_stream* s, uint32_t slots) {
 }
 static bool band_stage_for(ffs_stream* s, const StreamGeometry& g, size_t fstride, uint32_t n_frames) {
     const ffs_ctx* c = s->ctx;
-    if (!band_plan_holds(g, c->L, c->pixel_bytes)) return false;
+    if (!band_plan_holds(g, c->L, c->settings.pixel_bytes)) return false;
     uint32_t slots = band_slots(g, n_frames);
     // (sized once: hipFree synchronises the device -- see wave_logs_for)
-    if (slots > s->band_slots) slots = std::max(slots, max_band_slots(c->L, c->pixel_bytes, fstride, s->max_batch, c->tune));
+    if (slots > s->band_slots) slots = std::max(slots, max_band_slots(c->L, c->settings.pixel_bytes, fstride, s->max_batch, c->tune));
     return ensure_band_buffers(s, slots);
 }
 
@@ -492,7 +492,7 @@ static BatchPlan plan_batch(ffs_stream* s, const void* d_img, size_t pitch, size
     // Denser frames of 16-bit pixels stay in the one launch while their RUNS fit LDS (kernels_chain.hpp, the RUNS instantiation:
     // 61 k strong pixels are 12 k runs on the bench frames of the extended algorithm); a frame with more runs than that raises
     // kOvfRuns, ffs_wait() runs the batch again through the grid-wide kernels and the stream stays with them for dense batches.
-    P.runs_ok = c->pixel_bytes == 2 && L.W <= kChainRunMaxW && c->tune.chain_runs != 0 && !s->runs_overflowed;
+    P.runs_ok = c->settings.pixel_bytes == 2 && L.W <= kChainRunMaxW && c->tune.chain_runs != 0 && !s->runs_overflowed;
     if (can_chain && c->tune.sparse_stage == 2 && s->n_frames > 0) {
         uint32_t prev_max = 0;
         for (uint32_t f = 0; f < s->n_frames; ++f) prev_max = std::max(prev_max, s->h_counts[counts_strong_at(s->max_batch) + f]);
@@ -736,7 +736,7 @@ static CclArgs make_ccl_args(const ffs_stream* s, const BatchPlan& plan) {
     ca.n_tiles = c->n_tiles;
     ca.cap = s->cap;
     ca.max_comp = s->max_comp;
-    ca.pixel_bytes = c->pixel_bytes;
+    ca.pixel_bytes = c->settings.pixel_bytes;
     ca.strong_bytes = s->d_sbytes;
     ca.bpitch = L.bpitch;
     ca.bytes_frame_stride = L.bytes_frame_stride;
@@ -833,11 +833,11 @@ static int launch_one_launch_stage(ffs_stream* s, const BatchPlan& plan, const C
             BA.sub = plan.band.sub;
             BA.sub_rows = plan.band.sub_rows;
             const dim3 gb((unsigned)(plan.ta_launch.n_bands * BA.sub), n);
-            if (c->pixel_bytes == 2) hipExtLaunchKernelGGL(k_band_cc<uint16_t>, gb, dim3(64), 0, s->st2, c->chain_ev[slot], nullptr, 0, BA);
+            if (c->settings.pixel_bytes == 2) hipExtLaunchKernelGGL(k_band_cc<uint16_t>, gb, dim3(64), 0, s->st2, c->chain_ev[slot], nullptr, 0, BA);
             else hipExtLaunchKernelGGL(k_band_cc<uint32_t>, gb, dim3(64), 0, s->st2, c->chain_ev[slot], nullptr, 0, BA);
             hipLaunchKernelGGL(k_frame_merge, dim3(n), dim3(kMergeThreads), 0, s->st2, BA);
         } else {
-            hipExtLaunchKernelGGL(frame_chain_kernel(plan, c->pixel_bytes), dim3(n), dim3(kChainThreads), kChainDynBytes, s->st2, c->chain_ev[slot], nullptr, 0, A);
+            hipExtLaunchKernelGGL(frame_chain_kernel(plan, c->settings.pixel_bytes), dim3(n), dim3(kChainThreads), kChainDynBytes, s->st2, c->chain_ev[slot], nullptr, 0, A);
         }
         if (plan.aside) c->chain_ev_newest.store(slot);
     }
@@ -876,7 +876,7 @@ static int launch_grid_stage(ffs_stream* s, const BatchPlan& plan, const CclArgs
         sa.chunk_roots = s->d_chunk_roots;
         sa.chunks_max = s->cap / kRootChunk + 1;
         const dim3 gseg((unsigned)c->tune.ccl_grid, n), b256(256);
-        if (c->pixel_bytes == 2) hipLaunchKernelGGL(k_emit_list_w<uint16_t>, dim3(c->n_tiles, n), dim3(64), 0, s->st2, ca);
+        if (c->settings.pixel_bytes == 2) hipLaunchKernelGGL(k_emit_list_w<uint16_t>, dim3(c->n_tiles, n), dim3(64), 0, s->st2, ca);
         else hipLaunchKernelGGL(k_emit_list_w<uint32_t>, dim3(c->n_tiles, n), dim3(64), 0, s->st2, ca);
         hipLaunchKernelGGL(k_union<false>, gseg, b256, 0, s->st2, sa);
         hipLaunchKernelGGL(k_reduce_roots, gseg, b256, 0, s->st2, sa);
@@ -917,7 +917,7 @@ static int launch_sparse_stage(ffs_stream* s, const BatchPlan& plan) {
 }
 
 int enqueue_batch(ffs_stream* s, const void* d_img, size_t pitch, size_t fstride, uint32_t n, const ParamSnapshot* snapshot, const Rerun& how) {
-    s->batch = snapshot ? *snapshot : snapshot_of(s->ctx);
+    s->batch = snapshot ? *snapshot : snapshot_of(s->ctx->settings);
     s->cur_img = d_img;
     s->cur_pitch = pitch;
     s->cur_fstride = fstride;
@@ -978,7 +978,7 @@ extern "C" int ffs_submit(ffs_stream* s, const void* host_pixels, uint32_t n_fra
     s->dev_input = false;
     HIP_TRY(c, hipEventRecord(s->ev[0], s->st_up));
     // one 2D copy: the default device layout keeps frames contiguous (frame_stride = H * pitch)
-    const size_t row = (size_t)L.W * c->pixel_bytes;
+    const size_t row = (size_t)L.W * c->settings.pixel_bytes;
     HIP_TRY(c, hipMemcpy2DAsync(s->d_img, L.pitch, host_pixels, row, row, (size_t)L.H * n_frames,
                                 hipMemcpyHostToDevice, s->st_up));
     HIP_TRY(c, hipEventRecord(s->ev[1], s->st_up));
