@@ -4,6 +4,7 @@
 #include <stdint.h>
 
 #include "launch_geometry.hpp"
+#include "sweep_plan.hpp"
 #include "threshold_route.hpp"
 
 // Timing experiments (phases switched off, kernels stopped half way: results are wrong when used) exist only in builds
@@ -151,9 +152,7 @@ constexpr uint32_t kOvfWaveLog = 32u;     // a wave log or the list of undecided
 constexpr uint32_t kOvfLdsForest = 64u;   // a frame beyond the LDS forest met on the log path (k_frame_chain<LOG>): this batch again through the plane
 constexpr uint32_t kOvfBandPlan = 128u;   // a band beyond the band stage's plan (k_band_cc, k_frame_merge): the batch again through k_frame_chain, bands off for 32 batches
 constexpr uint32_t kOvfCorruptByteOffset = 256u;   // a byte-offset chunk holds fewer than W * H elements (kernels_byteoffset.hpp): the wait fails, FFS_ERR_INVALID
-// A different field: why a component is no reflection (filter_reflections), WireRec2::npx_flags >> 30 and ReflOut::flags
-constexpr uint32_t kRecTooSmall = 1u;     // fewer pixels than min_spot_size
-constexpr uint32_t kRecTooSpread = 2u;    // peak further than max_sep from the centre of mass
+// A different field, why a component is no reflection (kRecTooSmall, kRecTooSpread), is in sweep_plan.hpp, whose record classification reads it.
 
 // ---- the counter block of a stream (B = max_batch) -------------------------------------------------------------------------
 // [B] strong pixels | [B] components | [B][kSummaryWords] summary | [1] status word | [B] per-frame flag words, as 32-bit words.
@@ -275,14 +274,7 @@ struct SegArgs {
     uint32_t* zero_word;      // one more word to clear, or null
 };
 
-
-// One slice of the 3D stack's copy tables (kernels_stack3d.hpp)
-struct StackSlice {
-    uint32_t src;   // offset in the arrival buffers (k_stack_gather) / in the stream's list of that frame (k_stack_append)
-    uint32_t dst;   // offset in the destination buffers
-    uint32_t n;     // entries
-    uint32_t z;     // k_stack_gather: position of the slice in the stack
-};
+// (StackSlice, one row of the 3D stack's copy tables, is in sweep_plan.hpp, which has no HIP in it and fills them)
 
 // Matches ffs_reflection in include/ffs_hip.h
 struct ReflOut {

@@ -12,7 +12,10 @@
 //   ffs_wait.hip     ffs_wait: overflow re-runs (rerun_batch: the same batch again with a Rerun override), result assembly,
 //                    result accessors
 //   ffs_spotbg.hip   ffs_stream_spot_backgrounds: the per-spot constant background of the last waited batch (kernels_spotbg.hpp)
-//   ffs_stack3d.hip  rotation sweeps: the device-resident 3D stack and the exchange between GPUs (kernels_stack3d)
+//   ffs_stack3d.hip  rotation sweeps: the device-resident 3D stack -- create and pool, append a batch's lists, finish (kernels_stack3d); acts on
+//                    the decisions of sweep_plan.hpp
+//   ffs_multi.hip    several GPUs in one process: RCCL loaded with dlopen, the communicators and the choice of transport (ffs_multi_init), the
+//                    transfer of a batch's packed lists into a stack on another context, ffs_multi_gather_rows, ffs_device_numa_node; no kernels
 //   ffs_bench.hip    measurement entry points (kernel timings, memory ceiling, native pipeline loop, sqrt self-test)
 // Without HIP, shared with the kernels through ffs_device.h and compiled by a plain C++ test (tests/launch_geometry_check.cc):
 //   launch_geometry.hpp  the frame layout, the launch geometry of the threshold stage (super rows, strips, bands; wave logs and band
@@ -28,6 +31,9 @@
 //                        cutoff's two separately rounded operations (tests/radial_threshold_check.cc)
 //   encoded_plan.hpp     the decisions about a batch of encoded frames: bitshuffle's blocking, the chunk checks, where the chunks lie in the
 //                        staging buffer and which ranges of it are copied, the block table, the byte-offset frame table (tests/encoded_plan_check.cc)
+//   sweep_plan.hpp       rotation sweeps and the exchange (StackSlice lives here): the stack's growth and room rules, where a batch's lists land
+//                        and its append table, the finish's tables and launch sizes, which records are reflections, ranks and the order of the
+//                        gathered rows (host/spotfinder.cc reads them by the same function), the two transport decisions (tests/sweep_plan_check.cc)
 //   radial_blur_model.hpp  the blur ahead of that threshold (ffs_ctx_set_radial_blur): weights, tap rule, v = S / Wn (tests/radial_blur_check.cc)
 //   jungfrau_model.hpp   raw Jungfrau words to photon counts (ffs_ctx_set_jungfrau_calibration, FFS_CODEC_JUNGFRAU_RAW): stage, invalid words, the
 //                        two float32 operations, rounding and clamp; the setter's ranges (kernels_jungfrau.hpp, included by ffs_encoded.hip;
@@ -440,6 +446,16 @@ static int guarded(ffs_ctx* c, F&& body) {
         }                                                                               \
     } while (0)
 
+// (the same, as the stack's and the exchange's units have always spelt it)
+#define STK_TRY(c, expr)                                                        \
+    do {                                                                        \
+        hipError_t e_ = (expr);                                                 \
+        if (e_ != hipSuccess) {                                                 \
+            (c)->err = std::string(#expr) + ": " + hipGetErrorString(e_);       \
+            return e_ == hipErrorOutOfMemory ? FFS_ERR_NOMEM : FFS_ERR_DEVICE;  \
+        }                                                                       \
+    } while (0)
+
 // (a step that failed has left its text in the context's error: its code is passed on)
 #define FFS_TRY(expr)                    \
     do {                                 \
@@ -607,4 +623,8 @@ void ahead_stop(ffs_ctx* c, bool destroy);   // the thread leaves and is joined 
 void spotbg_free(ffs_stream* s);   // the stream's own HIP stream, events and buffers of ffs_stream_spot_backgrounds, if it was ever called
 // ffs_stack3d.hip
 void stack3d_free(ffs_stack3d* st);
+// ffs_multi.hip
 void gather_scratch_free(ffs_stream* s);   // what ffs_multi_gather_rows allocated for the stream, if anything
+// A batch's two packed arrays (s->d_pack_k / _i, `packed` entries, packed in s->st2) from the stream's device into dst_k / dst_i on the device
+// of `home`, ordered on home_st: RCCL send / recv in one group, or a peer (one GPU: device) copy behind s->ev_pack that leaves s->ev_sent
+int multi_move_packed(ffs_stream* s, ffs_ctx* home, hipStream_t home_st, uint32_t* dst_k, uint32_t* dst_i, uint64_t packed);

@@ -1,4 +1,5 @@
-// kernels_stack3d.hpp (included by ffs_stack3d.hip only) -- rotation sweeps: 3D connected components on the device.
+// kernels_stack3d.hpp (included by ffs_stack3d.hip only, which fills the kernels' tables and sizes their grids from sweep_plan.hpp; the
+// exchange between GPUs, ffs_multi.hip, has no kernels) -- rotation sweeps: 3D connected components on the device.
 //
 // What the reference does (spotfinder/connected_components/connected_components.cc:270-470): after the last
 // frame, one host thread copies every slice's 2D graph into one Boost graph, adds an edge for every linear

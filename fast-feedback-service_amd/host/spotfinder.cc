@@ -35,6 +35,7 @@
 #include "kabsch_space.hpp"
 #include "png_writer.hpp"
 #include "reader.hpp"
+#include "../csrc/sweep_plan.hpp"
 
 using namespace ffshost;
 using namespace std::chrono_literals;
@@ -567,9 +568,9 @@ class GatherRound {
     std::mutex mu_;
     std::condition_variable cv_;
     std::vector<ffs_stream*> streams_;
-    std::vector<uint32_t> n_rows_, row_at_;   // per GPU: rows of its batch, where they start in `rows_`
+    std::vector<uint64_t> n_rows_, row_at_;   // per GPU: rows of its batch, where they start in `rows_`
     std::vector<float> rows_;
-    std::vector<int> gpu_rank_;   // rank of a GPU's device in the communicator: distinct devices in order of appearance (ffs_multi_init)
+    const std::vector<int> devices_, comm_devices_;   // per GPU; and the communicator's, as ffs_multi_init made it from them
     uint32_t arrived_ = 0;
     uint64_t round_ = 0;                      // rounds served so far
     bool ok_ = false;                         // the round just served went through RCCL
@@ -577,14 +578,7 @@ class GatherRound {
     std::atomic<uint64_t> rccl_rounds{0}, host_rounds{0};
     GatherRound(const std::vector<int>& devices, const BatchPipeline& pipeline, Exchange& exchange)
         : pipeline_(pipeline), exchange_(exchange), n_dev_((uint32_t)devices.size()), streams_(n_dev_, nullptr), n_rows_(n_dev_, 0),
-          row_at_(n_dev_, 0), rows_((size_t)kCap * 4), gpu_rank_(n_dev_, 0) {
-        std::vector<int> distinct;
-        for (uint32_t di = 0; di < n_dev_; ++di) {
-            auto it = std::find(distinct.begin(), distinct.end(), devices[di]);
-            if (it == distinct.end()) { distinct.push_back(devices[di]); gpu_rank_[di] = (int)distinct.size() - 1; }
-            else gpu_rank_[di] = (int)(it - distinct.begin());
-        }
-    }
+          row_at_(n_dev_, 0), rows_((size_t)kCap * 4), devices_(devices), comm_devices_(ffsamd::distinct_devices(devices)) {}
     // -> pointer to this GPU's rows (frame id bits, x, y, z) of the round, or nullptr: read them from the host arrays
     const float* rows_of(uint32_t di, uint64_t q, ffs_stream* st, uint32_t my_rows) {
         const bool full_round = (q + 1) * n_dev_ <= pipeline_.total_batches();   // every GPU has a local batch q
@@ -597,13 +591,11 @@ class GatherRound {
         n_rows_[di] = my_rows;
         if (++arrived_ == n_dev_) {
             exchange_.join();
-            // rows arrive rank after rank, inside a rank in the order of `streams_` (= GPU order)
-            uint32_t at = 0;
-            for (int r = 0; r < (int)n_dev_; ++r)
-                for (uint32_t g = 0; g < n_dev_; ++g)
-                    if (gpu_rank_[g] == r) { row_at_[g] = at; at += n_rows_[g]; }
+            // where the library puts every GPU's rows: the layout it gathers by (csrc/sweep_plan.hpp)
+            const ffsamd::GatherLayout lay = ffsamd::gather_layout(devices_, n_rows_, comm_devices_);
+            for (uint32_t g = 0; g < n_dev_; ++g) row_at_[g] = lay.row_at(g);
             uint32_t got = 0;
-            ok_ = at <= kCap && ffs_multi_gather_rows(streams_.data(), n_dev_, 0, rows_.data(), kCap, &got) == FFS_OK && got == at;
+            ok_ = lay.total <= kCap && ffs_multi_gather_rows(streams_.data(), n_dev_, 0, rows_.data(), kCap, &got) == FFS_OK && got == lay.total;
             (ok_ ? rccl_rounds : host_rounds) += 1;
             arrived_ = 0;
             round_ = q + 1;

@@ -250,6 +250,59 @@ def test_delivery_by_add_batch(ffs, name):
     stack.close(); stream.close(); ctx.close()
 
 
+def _sweep_context(ffs, W, H):
+    ctx = ffs.Context(W, H, np.uint16, max_batch=3, max_strong_per_frame=600)
+    ctx.set_params(want_strong_list=1, min_spot_size_3d=4)
+    return ctx
+
+
+def _add_batch_of(stack, stream, frames, first_frame_id):
+    res = stream.process(frames, first_frame_id=first_frame_id)
+    stack.add_batch(stream)
+    return [(r.strong_k.copy(), r.strong_intensity.copy()) for r in res]
+
+
+def test_local_batches_with_overflow_frames_across_the_slot_ring(ffs):
+    """One stream, one context, nine batches of three: the ninth add_batch takes slot 0 of the stack's eight slice tables again.
+    Frames 4 (the middle of its batch) and 26 (the last of the ninth) hold ~50 % strong pixels, far beyond the lists' 600 entries
+    (as test_gpu_parity.py::test_stack3d_takes_an_overflowing_frame_from_the_second_context makes them): their lists go up from the
+    host to the places the batch's placement gives them, between and behind the frames the append kernel copies."""
+    from ffs_amd import synth
+    W, H, NZ = 200, 120, 27
+    frames = synth.frames(synth.sweep_params(seed=91, n_frames=NZ, n_spots=30, width=W, height=H), range(NZ)).copy()
+    rng = np.random.default_rng(5)
+    for z in (4, 26):
+        frames[z][rng.random((H, W)) < 0.5] += 400
+    ctx = _sweep_context(ffs, W, H)
+    stream = ctx.stream()
+    stack = ffs.Stack3D(ctx)
+    slices = []
+    for z0 in range(0, NZ, 3):
+        slices += _add_batch_of(stack, stream, frames[z0:z0 + 3], z0)
+    assert len(slices[4][0]) > 5000 and len(slices[26][0]) > 5000 and len(slices[5][0]) < 600 and len(slices[25][0]) < 600
+    refl, n_calc, fs, fp = stack.finish()
+    want = O.cc3d(slices, W, H, 4, 2.0)
+    assert (n_calc, fs, fp) == (want.n_calculated, want.n_filtered_size, want.n_filtered_sep)
+    assert_reflections_equal(refl, want.reflections)
+    stack.close(); stream.close(); ctx.close()
+
+
+def test_frame_ids_delivered_twice_by_add_batch(ffs):
+    """Ids 0-2, then ids 1-3 from other frames: the later lists count for 1 and 2, and the first batch's lists for them stay in
+    the arrival buffers, dead -- the held slices' arrival offsets are not the running sum of their lengths."""
+    from ffs_amd import synth
+    W, H = 200, 120
+    frames = synth.frames(synth.sweep_params(seed=91, n_frames=6, n_spots=30, width=W, height=H), range(6))
+    ctx = _sweep_context(ffs, W, H)
+    stream = ctx.stream()
+    stack = ffs.Stack3D(ctx)
+    first = _add_batch_of(stack, stream, frames[0:3], 0)
+    later = _add_batch_of(stack, stream, frames[3:6], 1)
+    assert all(len(k) > 0 for k, _ in first + later)
+    _assert_oracle(stack, W, H, [first[0]] + later, (4, 2.0))
+    stack.close(); stream.close(); ctx.close()
+
+
 @pytest.mark.parametrize("transport", ["peer", "rccl"])
 @pytest.mark.parametrize("name", ["late_join", "z_staircase"])
 def test_delivery_from_a_second_context(ffs, name, transport, monkeypatch):
