@@ -27,6 +27,7 @@
 //                        ranges, and the pairs of settings that do not combine, each stated once for both of its setters -- and what a batch
 //                        takes of the settings at submit (ParamSnapshot, snapshot_of) (tests/context_settings_check.cc)
 //   spot_background_model.hpp  the decisions of the per-spot background: quartile positions, status order, fence (tests/spot_background_check.cc)
+//   spot_background_glm_model.hpp  the robust Poisson GLM of the same ring: status order, seed, IRLS step, its own exp and log (tests/spot_background_glm_check.cc)
 //   radial_threshold_model.hpp the decisions of the radial-profile threshold (kernels_radthr.hpp, included by ffs_products.hip): status order and the
 //                        cutoff's two separately rounded operations (tests/radial_threshold_check.cc)
 //   encoded_plan.hpp     the decisions about a batch of encoded frames: bitshuffle's blocking, the chunk checks, where the chunks lie in the
@@ -373,6 +374,9 @@ struct ffs_stream {
     void *h_bg_boxes = nullptr, *d_bg_boxes = nullptr;
     ffs_spot_background *h_bg_out = nullptr, *h_bg_out_dev = nullptr;
     uint32_t bg_cap = 0;
+    // ffs_stream_spot_backgrounds_glm shares all of the above but the records: its own pinned buffer, room for bg_glm_cap reflections
+    ffs_spot_background_glm *h_bg_glm_out = nullptr, *h_bg_glm_out_dev = nullptr;
+    uint32_t bg_glm_cap = 0;
     // state of the batch in flight
     bool busy = false;
     uint32_t n_frames = 0;

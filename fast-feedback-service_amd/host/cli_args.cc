@@ -25,6 +25,7 @@ void usage() {
       "                  [--gain G] [--gain-map FILE] [--radial-bins N] [--pixel-stats PREFIX]\n"
       "                  [--jungfrau-calibration FILE] [--jungfrau-pedestal PREFIX [--pedestal-min-frames N] [--pedestal-max-rms R]]\n"
       "                  [--spot-background B]\n"
+      "                  [--spot-background-model constant|glm]\n"
       "                  [--n-iqr X] [--radial-blur narrow|wide]\n"
       "                  [--devices D0,D1,... | --gpus N] [--no-numa-pinning] [--single-buffer] [--all-threads] [--read-only] [--clean-exit]\n"
       "--max-valid: a centre pixel above this value is never strong (the reference's kernels test it against the\n"
@@ -85,6 +86,11 @@ void usage() {
       "              arrays in every image's JSON line, one entry per spot left after both filters, null where the ring gives no estimate\n"
       "              (no valid pixel, more than a quarter of it at or above 256, or a fence that reaches 256), and \"total_intensity\", the sum\n"
       "              of the image's estimated intensities.  Assumes photon counts (no gain is applied)\n"
+      "--spot-background-model: constant (default) is the fenced mean above; glm fits the same ring with the robust Poisson GLM DIALS\n"
+      "              integrates with (a constant mean with a log link, Huber's c = 1.345, at most 100 steps), which also answers where the\n"
+      "              fence cannot (a ring of mostly zeros).  The same JSON keys are filled from its records, the variance being sum +\n"
+      "              pixels^2 x mean / ring pixels; null where the ring has fewer than 10 valid pixels, more than a quarter of it at or above\n"
+      "              256, or the fit does not converge.  Needs --spot-background\n"
       "--validate:  every image is also decided by an independent path (every valid pixel's window gathered from memory,\n"
       "              no streaming kernel) and the two strong-pixel masks are compared: Match / Mismatch per image\n"
       "--devices / --gpus: one context and worker pool per GPU, all pulling frames from the one queue\n"
@@ -132,6 +138,7 @@ Args parse_args(int argc, char** argv) {
             if (!line.empty() && std::find(a.begin(), a.end(), line) == a.end()) a.push_back(line);
     }
     Args r;
+    bool model_given = false;   // --spot-background-model, in either spelling: refused without --spot-background
     if (const char* e = std::getenv("SPOTFINDER_TIMEOUT")) {  // spotfinder.cc:293-301
         try { r.timeout = std::stof(e); } catch (...) { std::printf("Ignoring invalid SPOTFINDER_TIMEOUT value: %s\n", e); }
     }
@@ -247,6 +254,13 @@ Args parse_args(int argc, char** argv) {
             r.spot_background = u32(v, s);
             if (r.spot_background < 1 || r.spot_background > 16) arg_error("--spot-background takes a border in 1..16: " + v);
         }
+        else if (s == "--spot-background-model") {
+            const std::string& v = need(i, s);
+            if (v == "constant") r.spot_background_glm = false;
+            else if (v == "glm") r.spot_background_glm = true;
+            else arg_error("--spot-background-model takes constant or glm: " + v);
+            model_given = true;
+        }
         else if (s == "--radial-bins") {
             const std::string& v = need(i, s);
             r.radial_bins = u32(v, s);
@@ -286,6 +300,7 @@ Args parse_args(int argc, char** argv) {
     } else if (r.pedestal_min_frames != 1 || r.pedestal_max_rms != 0.0f) {
         arg_error("--pedestal-min-frames and --pedestal-max-rms belong to --jungfrau-pedestal");
     }
+    if (model_given && !r.spot_background) arg_error("--spot-background-model belongs to --spot-background");
     if (r.gain > 0.0 && !r.gain_map.empty()) arg_error("--gain and --gain-map exclude each other: a constant map is the scalar gain");
     std::string lower = r.algorithm;   // DispersionAlgorithm, spotfinder.cc:180-203
     std::transform(lower.begin(), lower.end(), lower.begin(), [](unsigned char ch) { return (char)std::tolower(ch); });

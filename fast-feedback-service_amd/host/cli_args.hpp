@@ -33,6 +33,7 @@ struct Args {
                                          // (-a radial_profile: its shells, 100 unless given, at most 128)
     double n_iqr = 6.0;                  // --n-iqr X: -a radial_profile's cutoff is median + X x IQR of the shell
     int radial_blur = 0;                 // --radial-blur narrow | wide: FFS_RADIAL_BLUR_*, -a radial_profile's smoothing ahead of the threshold; 0 = not given
+    bool spot_background_glm = false;    // --spot-background-model glm: the ring's background by the robust Poisson GLM instead of Tukey's fence (constant); needs --spot-background
     uint32_t spot_background = 0;        // --spot-background B (1..16): per spot, the background of the ring of B pixels around its box and the background-subtracted intensity; 0 = not given
     std::string pixel_stats;             // --pixel-stats PREFIX: per-pixel count, sum, sum of squares and maximum over the run, into PREFIX.*; empty = not given
     uint32_t min_count = 2;

@@ -654,10 +654,12 @@ class BatchReport {
         }
         // --spot-background: the batch's backgrounds, once, between its wait and the stream's next submit (the collector releases the batch's
         // assembly only after this callback); image i's entries follow image i - 1's, n_reflections each
-        const ffs_spot_background* backgrounds = nullptr;
+        SpotBackgrounds backgrounds;
         if (args_.spot_background) {
             uint32_t n_bg = 0;
-            if (ffs_stream_spot_backgrounds(batch.stream, args_.spot_background, &backgrounds, &n_bg, nullptr) != FFS_OK) {
+            const int rc = args_.spot_background_glm ? ffs_stream_spot_backgrounds_glm(batch.stream, args_.spot_background, &backgrounds.glm, &n_bg, nullptr)
+                                                     : ffs_stream_spot_backgrounds(batch.stream, args_.spot_background, &backgrounds.tukey, &n_bg, nullptr);
+            if (rc != FFS_OK) {
                 std::printf("Error: %s\n", ffs_last_error(ctxs_[batch.gpu]));
                 return false;
             }
@@ -681,7 +683,8 @@ class BatchReport {
                 reflection_centers_2d[image_num + args_.start_index] = std::move(coms);
             }
             if (pipe_) append_json(r, batch.stream, i, round_rows, backgrounds, json_lines);
-            if (backgrounds) backgrounds += r.n_reflections;
+            if (backgrounds.tukey) backgrounds.tukey += r.n_reflections;
+            if (backgrounds.glm) backgrounds.glm += r.n_reflections;
             append_text(r, batch.validation ? &batch.validation[i] : nullptr, batch, text);
         }
         if (pipe_ && !json_lines.empty()) pipe_->send_lines(json_lines);
@@ -691,6 +694,12 @@ class BatchReport {
     }
 
   private:
+    // --spot-background: an image's slice of the batch's records under the model asked for (the other pointer is null; both are null for a
+    // batch without a single reflection)
+    struct SpotBackgrounds {
+        const ffs_spot_background* tukey = nullptr;
+        const ffs_spot_background_glm* glm = nullptr;
+    };
     // one image's JSON line; keys in alphabetical order, as nlohmann dumps them (:997-1008)
     // --radial-bins: the image's profile as three arrays of N integers (behind "num_strong_pixels": the keys stay in alphabetical order)
     // -a radial_profile: what the threshold decided per shell, "radial_cutoff", "radial_median" and "radial_status", between "radial_count" and
@@ -726,22 +735,25 @@ class BatchReport {
         if (valid) std::snprintf(buf, sizeof buf, "%.17g", v);
         j += valid ? buf : "null";
     }
-    void append_json(const ffs_frame_result& r, ffs_stream* stream, uint32_t frame_in_batch, const float*& round_rows, const ffs_spot_background* bg,
+    void append_json(const ffs_frame_result& r, ffs_stream* stream, uint32_t frame_in_batch, const float*& round_rows, const SpotBackgrounds& bg,
                      std::string& json_lines) const {
         std::string j = "{\"file\":" + json_escape(args_.file) + ",\"file-number\":" + std::to_string((uint32_t)r.frame_id)
                         + ",\"n_spots_total\":" + std::to_string(r.n_boxes)
                         + ",\"num_strong_pixels\":" + std::to_string(r.num_strong_pixels);
         if (args_.radial_bins) j += radial_json(stream, frame_in_batch);
         // the image's spots in reflection order: intensity = sum - pixels x mean; variance = sum + pixels^2 x mean / inliers (the counts' own
-        // Poisson variance plus that of the estimated mean); the keys stay in alphabetical order around "spot_centers"
+        // Poisson variance plus that of the estimated mean; under the GLM the mean rests on all the ring's pixels: / n_pixels); the keys stay
+        // in alphabetical order around "spot_centers"
         std::string intensity, variance;
         double total_intensity = 0.0;
         if (args_.spot_background) {   // (bg may be null: a batch without a single reflection)
             j += ",\"spot_background_mean\":[";
             for (uint32_t qq = 0; qq < r.n_reflections; ++qq) {
-                const bool ok = bg[qq].status == FFS_SPOT_BG_OK;
-                const double sum = (double)r.reflections[qq].sum_intensity, k = (double)r.reflections[qq].num_pixels, mean = bg[qq].mean;
-                const double i_spot = sum - k * mean, v_spot = ok ? sum + k * k * mean / (double)bg[qq].n_inliers : 0.0;
+                const bool glm = args_.spot_background_glm;
+                const bool ok = (glm ? bg.glm[qq].status : bg.tukey[qq].status) == FFS_SPOT_BG_OK;
+                const double sum = (double)r.reflections[qq].sum_intensity, k = (double)r.reflections[qq].num_pixels;
+                const double mean = glm ? bg.glm[qq].mean : bg.tukey[qq].mean, basis = glm ? (double)bg.glm[qq].n_pixels : (double)bg.tukey[qq].n_inliers;
+                const double i_spot = sum - k * mean, v_spot = ok ? sum + k * k * mean / basis : 0.0;
                 if (qq) { j += ","; intensity += ","; variance += ","; }
                 append_g17(j, ok, mean);
                 append_g17(intensity, ok, i_spot);
@@ -918,6 +930,7 @@ int main(int argc, char** argv) {
     std::printf("Spotfinder version: %s\n", FFS_VERSION);
     Args args = parse_args(argc, argv);
     stamp.verbose = args.verbose;
+    if (args.spot_background_glm) std::printf("Spot background model: glm (robust Poisson GLM of the ring of %u pixels)\n", args.spot_background);
     std::printf("Algorithm: %s\n", args.algo == FFS_ALGO_DISPERSION_EXTENDED ? "Dispersion Extended" : args.algo == FFS_ALGO_RADIAL_PROFILE ? "Radial Profile" : "Dispersion");
     if (args.threads < 1) {
         std::printf("Error: Thread count must be >= 1\n");

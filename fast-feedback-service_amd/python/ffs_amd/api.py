@@ -91,6 +91,18 @@ SPOT_BG_DT = np.dtype([("n_pixels", "<u4"), ("n_overflow", "<u4"), ("q1", "<i4")
 assert SPOT_BG_DT.itemsize == C.sizeof(_SpotBackground) == 48
 # FFS_SPOT_BG_*: the status of a spot's background estimate
 SPOT_BG_OK, SPOT_BG_NO_PIXELS, SPOT_BG_OVERFLOW, SPOT_BG_RANGE, SPOT_BG_NO_INLIERS = 0, 1, 2, 3, 4
+# ... continued by the robust GLM model (ffs_stream_spot_backgrounds_glm)
+SPOT_BG_FEW_PIXELS, SPOT_BG_DEGENERATE, SPOT_BG_NOT_CONVERGED = 5, 6, 7
+
+
+class _SpotBackgroundGlm(C.Structure):   # ffs_spot_background_glm
+    _fields_ = [("n_pixels", C.c_uint32), ("n_overflow", C.c_uint32), ("median", C.c_int32), ("n_iter", C.c_uint32), ("status", C.c_uint32),
+                ("reserved", C.c_uint32), ("beta", C.c_double), ("mean", C.c_double)]
+
+
+SPOT_BG_GLM_DT = np.dtype([("n_pixels", "<u4"), ("n_overflow", "<u4"), ("median", "<i4"), ("n_iter", "<u4"), ("status", "<u4"), ("reserved", "<u4"),
+                           ("beta", "<f8"), ("mean", "<f8")])
+assert SPOT_BG_GLM_DT.itemsize == C.sizeof(_SpotBackgroundGlm) == 40
 
 
 # ffs_radial_shell: what the radial-profile threshold decided for one (frame, shell) -- Stream.radial_thresholds
@@ -139,6 +151,7 @@ EXPORTS = [
     "ffs_ctx_set_radial_bins", "ffs_stream_radial_profile", "ffs_bench_radial",
     "ffs_ctx_set_pixel_stats", "ffs_ctx_get_pixel_stats", "ffs_bench_pixel_stats",
     "ffs_stream_spot_backgrounds",
+    "ffs_stream_spot_backgrounds_glm",
     "ffs_ctx_set_radial_threshold", "ffs_stream_radial_thresholds", "ffs_ctx_set_radial_blur",
     "ffs_ctx_set_jungfrau_calibration",
     "ffs_ctx_jungfrau_pedestal_begin", "ffs_ctx_jungfrau_pedestal_end", "ffs_stream_jungfrau_pedestal_fold", "ffs_ctx_get_jungfrau_pedestal",
@@ -186,6 +199,7 @@ def load_library():
         L.ffs_ctx_get_pixel_stats.argtypes = [C.c_void_p, C.POINTER(_PixelStats)]
         L.ffs_bench_pixel_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_uint32, C.c_uint32, C.POINTER(C.c_float)]
         L.ffs_stream_spot_backgrounds.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_void_p), C.POINTER(C.c_uint32), C.POINTER(C.c_float)]
+        L.ffs_stream_spot_backgrounds_glm.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_void_p), C.POINTER(C.c_uint32), C.POINTER(C.c_float)]
         L.ffs_bench_pipeline.argtypes = [C.POINTER(C.c_void_p), C.c_uint32, C.c_void_p, C.c_size_t, C.c_size_t, C.c_uint32,
                                          C.c_uint32, C.c_int64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
         L.ffs_device_numa_node.argtypes = [C.c_int]
@@ -700,6 +714,21 @@ class Stream:
             a = np.zeros(0, SPOT_BG_DT)
         return (a, ms.value) if want_ms else a
 
+    def spot_backgrounds_glm(self, border: int = 3, copy: bool = True, want_ms: bool = False):
+        """ffs_stream_spot_backgrounds_glm: the same ring under the robust Poisson GLM (constant mean, Huber's c = 1.345), as a structured
+        array (SPOT_BG_GLM_DT: n_pixels, n_overflow, median, n_iter, status, reserved, beta, mean) in the order of last_batch_reflections;
+        the device computes the whole record.  Conditions, copy and want_ms as for spot_backgrounds(); the buffer is this call's own, so a
+        view (copy=False) survives a spot_backgrounds() call on the same batch and the other way round.  spot_intensities_glm() turns it
+        into background-subtracted intensities."""
+        p, n, ms = C.c_void_p(), C.c_uint32(), C.c_float()
+        self.ctx._check(self._lib.ffs_stream_spot_backgrounds_glm(self._h, int(border), C.byref(p), C.byref(n), C.byref(ms)))
+        if n.value:
+            a = np.frombuffer((C.c_uint8 * (n.value * SPOT_BG_GLM_DT.itemsize)).from_address(p.value), SPOT_BG_GLM_DT)
+            a = a.copy() if copy else a
+        else:
+            a = np.zeros(0, SPOT_BG_GLM_DT)
+        return (a, ms.value) if want_ms else a
+
     def bench_radial(self, dev_ptr: int, pitch_bytes: int, frame_stride_bytes: int, n_frames: int, iters: int) -> float:
         """ffs_bench_radial: average ms of one batch's radial profile (its two launches), alone on resident frames."""
         ms = C.c_float()
@@ -785,6 +814,21 @@ def spot_intensities(reflections: np.ndarray, backgrounds: np.ndarray):
     ni = np.where(ok, backgrounds["n_inliers"], 1).astype(np.float64)
     intensity = np.where(ok, s - k * mean, np.nan)
     variance = np.where(ok, s + k * k * mean / ni, np.nan)
+    return intensity, variance
+
+
+def spot_intensities_glm(reflections: np.ndarray, backgrounds: np.ndarray):
+    """The same from the GLM backgrounds (Stream.spot_backgrounds_glm, same order): intensity = sum_intensity - num_pixels * mean; the
+    model puts all n_pixels ring pixels at the fitted mean, so the mean's variance is mean / n_pixels and the intensity's is sum_intensity
+    + num_pixels^2 * mean / n_pixels.  Both float64, NaN where status != 0."""
+    assert len(reflections) == len(backgrounds)
+    ok = backgrounds["status"] == SPOT_BG_OK
+    s = reflections["sum_intensity"].astype(np.float64)
+    k = reflections["num_pixels"].astype(np.float64)
+    mean = backgrounds["mean"].astype(np.float64)
+    n = np.where(ok, backgrounds["n_pixels"], 1).astype(np.float64)
+    intensity = np.where(ok, s - k * mean, np.nan)
+    variance = np.where(ok, s + k * k * mean / n, np.nan)
     return intensity, variance
 
 

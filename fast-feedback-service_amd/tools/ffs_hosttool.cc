@@ -15,6 +15,11 @@
 //                                         the re-pedestalled calibration from spotfinder --jungfrau-pedestal's <prefix>.count.u32, .sum.u64 and
 //                                         .sum_sq.u64 (the rule of csrc/jungfrau_pedestal_model.hpp): pedestals replaced, a factor kept where the
 //                                         stage's pedestal is usable (count >= min_frames [1], rms <= max_rms [0: no test]) and 0 elsewhere
+//   ffs_hosttool spotbgglm [file]         the robust Poisson GLM background (csrc/spot_background_glm_model.hpp, the text the kernel of
+//                                         ffs_stream_spot_backgrounds_glm compiles) of histograms read from the file or standard input, 257
+//                                         unsigned integers a line (the bins 0 .. 255, then the tail): one record a line, n_pixels n_overflow
+//                                         median n_iter status beta mean, the two doubles as the 16 hex digits of their bit patterns
+#include <cinttypes>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -23,6 +28,7 @@
 #include <iterator>
 #include <random>
 
+#include "../csrc/spot_background_glm_model.hpp"
 #include "codecs.hpp"
 #include "reader.hpp"
 
@@ -282,6 +288,33 @@ static int synthframes(const std::string& spec, const std::string& file) {
     return o ? 0 : fail("synthframes: cannot write the file");
 }
 
+static int spotbgglm(const char* path) {
+    std::FILE* in = path ? std::fopen(path, "r") : stdin;
+    if (!in) return fail("spotbgglm: cannot open the file");
+    std::vector<uint32_t> bins((size_t)ffsamd::kSpotBgBins);
+    int rc = 0;
+    for (unsigned long long line = 0;; ++line) {
+        int got = 0;
+        for (; got < ffsamd::kSpotBgBins; ++got)
+            if (std::fscanf(in, "%" SCNu32, &bins[(size_t)got]) != 1) break;
+        if (got == 0) break;
+        uint32_t tail = 0;
+        if (got != ffsamd::kSpotBgBins || std::fscanf(in, "%" SCNu32, &tail) != 1) {
+            std::fprintf(stderr, "spotbgglm: histogram %llu is short: 257 integers each\n", line);
+            rc = 2;
+            break;
+        }
+        const ffsamd::SpotBgGlmResult r = ffsamd::spotbg_glm_from_histogram(bins.data(), tail);
+        uint64_t beta, mean;
+        std::memcpy(&beta, &r.beta, sizeof beta);
+        std::memcpy(&mean, &r.mean, sizeof mean);
+        std::printf("%" PRIu32 " %" PRIu32 " %" PRId32 " %" PRIu32 " %" PRIu32 " %016" PRIx64 " %016" PRIx64 "\n", r.n_pixels, r.n_overflow, r.median, r.n_iter, r.status,
+                    beta, mean);
+    }
+    if (path) std::fclose(in);
+    return rc;
+}
+
 // chunkfnv <chunk file> <nelem> <elem bytes>: decode one bitshuffle-LZ4 chunk with the host codec and
 // print the FNV-1a of the pixels (cross-check for chunk writers)
 static int chunkfnv(const std::string& path, size_t nelem, size_t es) {
@@ -313,6 +346,7 @@ int main(int argc, char** argv) {
         if (cmd == "synthframes" && argc == 4) return synthframes(argv[2], argv[3]);
         if (cmd == "jfrepedestal" && argc >= 5 && argc <= 7) return jfrepedestal(argv[2], argv[3], argv[4], argc > 5 ? argv[5] : "1", argc > 6 ? argv[6] : "0");
         if (cmd == "h5stats" && argc == 4) { h5_print_group_stats(argv[2], argv[3]); return 0; }
+        if (cmd == "spotbgglm" && argc <= 3) return spotbgglm(argc == 3 ? argv[2] : nullptr);
         if (cmd == "h5support") { std::printf("%d\n", h5_supported() ? 1 : 0); return 0; }
     } catch (const std::exception& e) {
         std::printf("Error: %s\n", e.what());
@@ -322,6 +356,7 @@ int main(int argc, char** argv) {
                 "       mkh5 <synth:spec> <master.h5> [vds-links|vds-files|plain [frames_per_file [n_written]]] |\n"
                 "       h5info <master.h5> | synthinfo <synth:spec> | h5support | h5stats <file.h5> <group> |\n"
                 "       chunkfnv <chunk> <nelem> <elem bytes> | jfcal <synth:spec> <file> | jfconvert <raw> <cal> <W> <H> <out> |\n"
-                "       synthframes <synth:spec> <file> | jfrepedestal <old cal> <prefix> <new cal> [min_frames [max_rms]]\n");
+                "       synthframes <synth:spec> <file> | jfrepedestal <old cal> <prefix> <new cal> [min_frames [max_rms]] |\n"
+                "       spotbgglm [histograms]\n");
     return 2;
 }

@@ -707,6 +707,59 @@ typedef struct {
 } ffs_spot_background;            /* 48 bytes */
 int ffs_stream_spot_backgrounds(ffs_stream *s, uint32_t border, const ffs_spot_background **out, uint32_t *n, float *kernel_ms);
 
+/* The same ring under the second model of the reference's integrator: the robust Poisson GLM with a constant mean (Parkhurst et al. 2016,
+ * J. Appl. Cryst. 49, 1912; include/integrator/background.hpp, glm_constant_background; what DIALS calls `glm constant3d`).  It fits the
+ * rings the Tukey fence has no answer for (FFS_SPOT_BG_RANGE): a Poisson(0.1) ring has q1 = q3 = 0 and a fence of 0..0.
+ *   Ring, validity of a pixel, n_pixels = N and n_overflow: exactly those of ffs_stream_spot_backgrounds, from the same histogram of 256
+ *   one-count bins and a counted tail.  status, decided in this order:
+ *     FFS_SPOT_BG_NO_PIXELS (1)      N = 0;
+ *     FFS_SPOT_BG_FEW_PIXELS (5)     N < 10;
+ *     FFS_SPOT_BG_OVERFLOW (2)       4 * n_overflow > N;
+ *     otherwise median = the value at the 1-based sorted position N / 2 + 1 (integer division; below 256 then), and
+ *     the ALL-ZERO RING -- n_overflow = 0 and every counting pixel 0 -- is FFS_SPOT_BG_OK with mean = 0, beta = -inf, n_iter = 0.  It has
+ *     no finite beta; the reference walks beta down some seventy steps and returns a mean near 1e-33 whose digits are rounding noise.  0
+ *     is the maximum-likelihood mean and the limit of the fit; this is the one documented departure from the reference;
+ *     otherwise beta = log(median, or 1 when the median is 0) and at most 100 steps of iteratively reweighted least squares with Huber's
+ *     c = 1.345: mu = exp(beta), s = sqrt(mu), j1 = floor(mu - c s), j2 = floor(mu + c s); epsi1 = E[psi_c] and epsi2 of Poisson(mu) as
+ *     the reference's glm_expectation forms them from the Poisson probabilities around j1 and j2; b = epsi2 mu^2 / s;
+ *     U = sum over the pixels of (psi_c((p - mu) / s) - epsi1) mu / s, a pixel of the tail entering at psi = +c;
+ *     delta = U / (N b); beta += delta; the loop ends when sqrt(delta^2 / max(beta^2, 1e-10)) < 1e-3, beta taken before the update;
+ *     FFS_SPOT_BG_DEGENERATE (6)     inside the loop: mu or s not > 0, mu not < 512, b or delta not finite; after it: beta outside
+ *                                    (-300, 300).  The bound mu < 512 is this library's, not the reference's: it bounds the Poisson sums
+ *                                    at 600 terms and keeps exp(-mu) a normal number; with bins that end at 255 and at most a quarter of
+ *                                    the ring clipped at +c no fit the reference accepts gets there.  No histogram tried reached 6;
+ *     FFS_SPOT_BG_NOT_CONVERGED (7)  100 steps without meeting the tolerance (a ring of two levels far apart can cycle);
+ *     FFS_SPOT_BG_OK (0)             else: mean = exp(beta).
+ *   median is -1 under status 1, 2 and 5.  n_iter is the steps taken.  beta is the last value reached (0 under status 1, 2 and 5).  mean
+ *   is 0 when status != 0.
+ *   U is computed from four integers of the histogram's prefix sums (psi_c is -c up to j1, +c above j2, the residual between) and the
+ *   probabilities by one recurrence t_k = t_(k-1) mu / k; every floating-point operation is + - * / sqrt floor or an integer conversion,
+ *   exp and log included (csrc/spot_background_glm_model.hpp has its own), compiled without contraction.  So the record is the same,
+ *   bit for bit, on the device and from the same header on a CPU (`ffs_hosttool spotbgglm`), and independent of path, tuning and order.
+ *   Against the reference's own function the mean differs by rounding only (DESIGN.md section 3.8b has the measured figure).
+ *   A background-subtracted intensity is sum_intensity - num_pixels * mean; the model puts all N ring pixels at the fitted mean, so the
+ *   mean's variance is mean / N and the intensity's sum_intensity + num_pixels^2 * mean / n_pixels.
+ * One entry per reflection of the batch, in the order and with the per-frame slices of ffs_stream_batch_arrays, as for
+ * ffs_stream_spot_backgrounds; the device stores the whole record, the host computes nothing.  The result buffer is this call's own: *out
+ * stays valid until the next call of THIS function or the next ffs_wait on the stream, so both models may be asked for one batch and both
+ * pointers held.  kernel_ms may be NULL; a batch with no reflections: FFS_OK, *n = 0, nothing is launched.  The call is synchronous and
+ * belongs between ffs_wait and the stream's next submit; what it reads, and what must still be in place (an ffs_submit_device batch's
+ * frames, the context's mask, no ffs_decode_only* in between), is word for word ffs_stream_spot_backgrounds'.
+ * FFS_ERR_INVALID (ffs_last_error names the reason and this entry point): a dead handle; NULL out or n; border outside 1..16; no batch
+ * waited on the stream yet, or the last ffs_wait on it failed; a batch in flight on the stream; the last batch was submitted without
+ * want_reflections. */
+#define FFS_SPOT_BG_FEW_PIXELS 5u
+#define FFS_SPOT_BG_DEGENERATE 6u
+#define FFS_SPOT_BG_NOT_CONVERGED 7u
+typedef struct {
+    uint32_t n_pixels, n_overflow;
+    int32_t median;
+    uint32_t n_iter;
+    uint32_t status, reserved;
+    double beta, mean;
+} ffs_spot_background_glm;        /* 40 bytes */
+int ffs_stream_spot_backgrounds_glm(ffs_stream *s, uint32_t border, const ffs_spot_background_glm **out, uint32_t *n, float *kernel_ms);
+
 /* Centres of mass of the last batch's reflections as rows (frame_id, x, y, z) of float32 -- the
  * payload of `--output-for-index` (spot_centers, spotfinder.cc:919-933,1004-1006), in frame order;
  * used to feed a multi-GPU gather without a per-frame loop on the caller's side.  Lane 0 carries the

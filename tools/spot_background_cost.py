@@ -11,6 +11,10 @@ Jungfrau-9M (32-bit pixels), 32 frames a batch, border 3 (--border).  One proces
             times: frames/s and ms per step of either, and the ratio.  Both variants run with want_reflections on, so the difference is the
             call; neither is comparable with bench.py's figure (a native loop, no reflections).
 
+  --model glm: the call is ffs_stream_spot_backgrounds_glm (the robust Poisson GLM of the same ring).  Its `call` line stands beside a
+            line of the Tukey call measured in the same process on the same batch, and adds the GLM's status census, how many of the spots
+            the Tukey fence leaves without an estimate (status 3) get one, and the median and maximum n_iter.
+
   python3 tools/spot_background_cost.py --out profiles/NAME.jsonl
 """
 import argparse
@@ -41,7 +45,7 @@ def emit(args, record):
             f.write(line + "\n")
 
 
-def pipeline(streams, d, pitch, fstride, B, steps, border):
+def pipeline(streams, d, pitch, fstride, B, steps, border, model="constant"):
     """`steps` batches through the streams, all of them in flight; border > 0: the call after every wait.  -> seconds, spots measured."""
     inflight, spots = [], 0
     t0 = time.perf_counter()
@@ -50,7 +54,7 @@ def pipeline(streams, d, pitch, fstride, B, steps, border):
             st = inflight.pop(0)
             st.wait_counts()
             if border:
-                spots += len(st.spot_backgrounds(border, copy=False))
+                spots += len(st.spot_backgrounds_glm(border, copy=False) if model == "glm" else st.spot_backgrounds(border, copy=False))
         else:
             st = streams[step % len(streams)]
         if step < steps:
@@ -77,19 +81,29 @@ def workload(name, args):
     st = streams[0]
     st.submit_device(d.data_ptr(), pitch, fstride, B)
     st.wait_counts()
-    kernel, wall = [], []
-    for i in range(args.warmup_calls + args.reps):
-        t0 = time.perf_counter()
-        bg, ms = st.spot_backgrounds(args.border, copy=False, want_ms=True)
-        t1 = time.perf_counter()
-        if i >= args.warmup_calls:
-            kernel.append(ms)
-            wall.append((t1 - t0) * 1e3)
-    status = np.bincount(bg["status"], minlength=5)
-    emit(args, dict(common, mode="call", reps=args.reps, reflections=int(len(bg)), status_counts=[int(v) for v in status],
-                    ring_pixels_median=float(np.median(bg["n_pixels"])) if len(bg) else 0.0,
-                    kernel_ms_median=round(statistics.median(kernel), 4), kernel_ms_min=round(min(kernel), 4), kernel_ms_max=round(max(kernel), 4),
-                    call_wall_ms_median=round(statistics.median(wall), 4), call_wall_ms_min=round(min(wall), 4), call_wall_ms_max=round(max(wall), 4)))
+    tukey = None
+    for model in (["constant", "glm"] if args.model == "glm" else ["constant"]):
+        call = st.spot_backgrounds_glm if model == "glm" else st.spot_backgrounds
+        kernel, wall = [], []
+        for i in range(args.warmup_calls + args.reps):
+            t0 = time.perf_counter()
+            bg, ms = call(args.border, copy=False, want_ms=True)
+            t1 = time.perf_counter()
+            if i >= args.warmup_calls:
+                kernel.append(ms)
+                wall.append((t1 - t0) * 1e3)
+        status = np.bincount(bg["status"], minlength=8 if model == "glm" else 5)
+        extra = {}
+        if model == "glm":
+            fitted = bg["n_iter"][bg["status"] == 0]
+            extra = dict(tukey_status3=int((tukey["status"] == 3).sum()), tukey_status3_with_glm_estimate=int(((tukey["status"] == 3) & (bg["status"] == 0)).sum()),
+                         n_iter_median=float(np.median(fitted)) if len(fitted) else 0.0, n_iter_max=int(bg["n_iter"].max()) if len(bg) else 0)
+        else:
+            tukey = bg.copy()
+        emit(args, dict(common, mode="call", model=model, reps=args.reps, reflections=int(len(bg)), status_counts=[int(v) for v in status],
+                        ring_pixels_median=float(np.median(bg["n_pixels"])) if len(bg) else 0.0,
+                        kernel_ms_median=round(statistics.median(kernel), 4), kernel_ms_min=round(min(kernel), 4), kernel_ms_max=round(max(kernel), 4),
+                        call_wall_ms_median=round(statistics.median(wall), 4), call_wall_ms_min=round(min(wall), 4), call_wall_ms_max=round(max(wall), 4), **extra))
 
     if "pipeline" not in args.modes:
         for s in streams:
@@ -97,16 +111,16 @@ def workload(name, args):
         c.close()
         return
     pipeline(streams, d, pitch, fstride, B, args.warmup, 0)
-    pipeline(streams, d, pitch, fstride, B, args.warmup, args.border)
+    pipeline(streams, d, pitch, fstride, B, args.warmup, args.border, args.model)
     rates = {"without": [], "with": []}
     for r in range(args.rounds):
         for variant, border in (("without", 0), ("with", args.border)):
-            secs, spots = pipeline(streams, d, pitch, fstride, B, args.steps, border)
+            secs, spots = pipeline(streams, d, pitch, fstride, B, args.steps, border, args.model)
             rates[variant].append(B * args.steps / secs)
-            emit(args, dict(common, mode="pipeline", variant=variant, round=r, streams=args.streams, steps=args.steps, warmup=args.warmup,
+            emit(args, dict(common, mode="pipeline", model=args.model, variant=variant, round=r, streams=args.streams, steps=args.steps, warmup=args.warmup,
                             frames_per_s=round(B * args.steps / secs, 1), ms_per_step=round(secs / args.steps * 1e3, 4), spots_measured=spots))
     mean = {k: statistics.mean(v) for k, v in rates.items()}
-    emit(args, dict(common, mode="pipeline_ab", rounds=args.rounds, streams=args.streams, steps=args.steps,
+    emit(args, dict(common, mode="pipeline_ab", model=args.model, rounds=args.rounds, streams=args.streams, steps=args.steps,
                     frames_per_s_mean={k: round(v, 1) for k, v in mean.items()},
                     ms_per_step_mean={k: round(B / v * 1e3, 4) for k, v in mean.items()}, ratio_with_to_without=round(mean["with"] / mean["without"], 4)))
     for s in streams:
@@ -118,6 +132,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default="", help="the file the lines are appended to (profiles/NAME.jsonl)")
     ap.add_argument("--border", type=int, default=3)
+    ap.add_argument("--model", default="constant", choices=["constant", "glm"], help="glm: ffs_stream_spot_backgrounds_glm, beside the Tukey call in `call`")
     ap.add_argument("--batch", type=int, default=32)
     ap.add_argument("--frames", type=int, default=8, help="unique synthetic frames (bench.py's: seeds from 2000)")
     ap.add_argument("--reps", type=int, default=20)
