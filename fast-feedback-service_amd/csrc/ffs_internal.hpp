@@ -12,6 +12,8 @@
 //   ffs_wait.hip     ffs_wait: overflow re-runs (rerun_batch: the same batch again with a Rerun override), result assembly,
 //                    result accessors
 //   ffs_spotbg.hip   ffs_stream_spot_backgrounds: the per-spot constant background of the last waited batch (kernels_spotbg.hpp)
+//   ffs_shoebox.hip  summation integration of shoeboxes in Kabsch space, from begin to end: the job on a context, ffs_stream_shoebox_fold, the sums
+//                    (kernels_shoebox.hpp); acts on the decisions of shoebox_plan.hpp
 //   ffs_stack3d.hip  rotation sweeps: the device-resident 3D stack -- create and pool, append a batch's lists, finish (kernels_stack3d); acts on
 //                    the decisions of sweep_plan.hpp
 //   ffs_multi.hip    several GPUs in one process: RCCL loaded with dlopen, the communicators and the choice of transport (ffs_multi_init), the
@@ -42,6 +44,10 @@
 //   jungfrau_pedestal_model.hpp  pedestals from dark frames (ffs_stream_jungfrau_pedestal_fold, ffs_jungfrau_pedestal_planes): which words count
 //                        where, accumulators to pedestal / rms / ok planes, the re-pedestalled calibration (kernels_jfped.hpp, included by
 //                        ffs_encoded.hip, which owns the fold from begin to end; host/codecs.hpp; tools/ffs_hosttool.cc; tests/jungfrau_pedestal_check.cc)
+//   shoebox_model.hpp    summation integration: corner to Kabsch coordinates, the foreground decision, what a pixel adds to its reflection, the
+//                        final sums (kernels_shoebox.hpp, included by ffs_shoebox.hip; tools/ffs_hosttool.cc; tests/shoebox_check.cc)
+//   shoebox_plan.hpp     which shoebox tables are taken, the index over the boxes' z-ranges and the list a fold's launch receives
+//                        (tests/shoebox_plan_check.cc)
 // No exception leaves the library (guarded()).
 #pragma once
 #include <algorithm>
@@ -95,6 +101,7 @@ struct ThreadError {
 // ---- tuning: struct Tuning, tuning.hpp ---------------------------------------------------------------------------
 
 struct ffs_stack3d;
+struct ShoeboxJob;   // ffs_shoebox.hip
 
 // A few helper threads per context for ffs_wait's result assembly (wire records -> boxes, reflections, centre rows): one thread
 // moves a batch's 7 MB (45 000 components of 32 Eiger frames) in 0.21 ms -- two thirds of the time the GPU takes for the batch, and
@@ -184,6 +191,11 @@ struct ffs_ctx {
     uint64_t stats_frames = 0;
     hipStream_t stats_st = nullptr;
     std::mutex stats_mu;
+    // ffs_ctx_shoebox_begin: the open summation-integration job -- table, index, accumulators and a HIP stream of its
+    // own -- or null.  shoebox_mu: begin, fold, the getters and end are one step each; a fold reads, adds and writes the accumulators, and folds
+    // come from distinct ffs_streams on distinct threads.
+    ShoeboxJob* shoebox = nullptr;
+    std::mutex shoebox_mu;
     uint8_t* d_maskbits = nullptr;
     uint8_t* d_ginfo = nullptr;  // per-group mask bits + window-count bounds (kernels_stream.hpp)
     uint8_t* d_mmap = nullptr;   // per-pixel window counts
@@ -625,6 +637,8 @@ int ahead_take(ffs_stream* s);        // waits for the AheadThread to be done wi
 void ahead_stop(ffs_ctx* c, bool destroy);   // the thread leaves and is joined (context destroy, process exit)
 // ffs_spotbg.hip
 void spotbg_free(ffs_stream* s);   // the stream's own HIP stream, events and buffers of ffs_stream_spot_backgrounds, if it was ever called
+// ffs_shoebox.hip
+void shoebox_free_ctx(ffs_ctx* c);   // the open job, if any (context destroy; every stream is closed)
 // ffs_stack3d.hip
 void stack3d_free(ffs_stack3d* st);
 // ffs_multi.hip

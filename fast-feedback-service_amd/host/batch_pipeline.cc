@@ -243,13 +243,32 @@ bool BatchPipeline::ensure_assembly(Gpu& G, Assembly& A, uint32_t index, int thr
 // image `image_num`'s chunk into dst, once the frame source has it.  false: stopped
 bool BatchPipeline::read_chunk(ReaderState& R, uint32_t image_num, std::span<uint8_t> dst, std::span<uint8_t>& chunk) {
     const uint32_t offset_image_num = image_num + cfg_.start_index;  // :756
+    // The images the readers are after right now, this one among them from here to the return (a reader parked at the reader mutex below
+    // included): the time-out names the LOWEST of them, the first image the source did not deliver, whichever reader's patience ran out
+    // first -- which of them that is depends on when each received its last image, not on the data.
+    struct Awaited {
+        BatchPipeline& p;
+        const uint32_t image;
+        Awaited(BatchPipeline& p_, uint32_t image_) : p(p_), image(image_) {
+            std::lock_guard<std::mutex> l(p.awaited_mutex_);
+            p.awaited_.insert(image);
+        }
+        ~Awaited() {
+            std::lock_guard<std::mutex> l(p.awaited_mutex_);
+            p.awaited_.erase(p.awaited_.find(image));
+        }
+        uint32_t lowest() const {
+            std::lock_guard<std::mutex> l(p.awaited_mutex_);
+            return *p.awaited_.begin();
+        }
+    } awaited(*this, offset_image_num);
     // readers are not thread-safe in general (:763-765); those that say they are skip the lock
     std::unique_lock<std::mutex> lock(reader_mutex_, std::defer_lock);
     if (!reader_.reentrant()) lock.lock();
     const auto w0 = now();
     while (!reader_.is_image_available(offset_image_num) && !stop_.load()) {
         if (secs(R.last_received, now()) > cfg_.timeout) {  // :776-787
-            std::printf("Timeout waiting for image %u\n", offset_image_num);
+            std::printf("Timeout waiting for image %u\n", awaited.lowest());
             stop_.store(true);
             wake_all();
             break;

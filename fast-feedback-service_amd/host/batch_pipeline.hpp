@@ -21,6 +21,7 @@
 #include <mutex>
 #include <optional>
 #include <sched.h>
+#include <set>
 #include <span>
 #include <vector>
 
@@ -114,6 +115,8 @@ class BatchPipeline {
     const bool byte_offset_;
     std::vector<std::unique_ptr<Gpu>> gpus_;
     std::mutex reader_mutex_, print_mutex_;
+    std::mutex awaited_mutex_;            // guards awaited_
+    std::multiset<uint32_t> awaited_;     // the images the readers are reading or waiting for right now (read_chunk): a time-out names the lowest
     std::atomic<bool> readers_done_{false};   // no batch will be submitted any more: collectors stop at the first one that is missing
     std::atomic<size_t> chunk_estimate_{0};   // staging bytes per compressed chunk, from the first chunk anybody reads
     std::atomic<int> failed_{0};

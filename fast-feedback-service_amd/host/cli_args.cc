@@ -27,6 +27,8 @@ void usage() {
       "                  [--spot-background B]\n"
       "                  [--spot-background-model constant|glm]\n"
       "                  [--n-iqr X] [--radial-blur narrow|wide]\n"
+      "                  [--integrate FILE --sigma-b DEG --sigma-m DEG --integrate-out PREFIX [--integrate-algorithm ellipsoid|dials]\n"
+      "                   [--integrate-background tukey|glm] [--integrate-n-sigma 3]]\n"
       "                  [--devices D0,D1,... | --gpus N] [--no-numa-pinning] [--single-buffer] [--all-threads] [--read-only] [--clean-exit]\n"
       "--max-valid: a centre pixel above this value is never strong (the reference's kernels test it against the\n"
       "              data set's trusted maximum).  trusted (default) = the frame source's trusted-range maximum when it is\n"
@@ -91,6 +93,17 @@ void usage() {
       "              fence cannot (a ring of mostly zeros).  The same JSON keys are filled from its records, the variance being sum +\n"
       "              pixels^2 x mean / ring pixels; null where the ring has fewer than 10 valid pixels, more than a quarter of it at or above\n"
       "              256, or the fit does not converge.  Needs --spot-background\n"
+      "--integrate: summation integration of predicted reflections over the run.  FILE holds raw little-endian records of 48 bytes: the\n"
+      "              predicted centre x, y in pixels and z in images (three float64; z = 0 is the start of the first image), then the half-open\n"
+      "              shoebox x_min x_max y_min y_max z_min z_max (six int32; it may hang over the image's edge).  On every image of a box its\n"
+      "              pixels are foreground or background by an ellipsoid in Kabsch space of --integrate-n-sigma (default 3) x --sigma-b and\n"
+      "              x --sigma-m (degrees: the estimates a rotation run prints), or by its first two axes alone (--integrate-algorithm dials);\n"
+      "              the background is the box's own, by Tukey's fence or the robust Poisson GLM (--integrate-background).  Needs the detector\n"
+      "              geometry and the wavelength --dmin needs, and a rotation source.  Written after the last image: PREFIX.shoebox_sums, one\n"
+      "              record of 80 bytes per reflection in FILE's order (ffs_shoebox_sum of ffs_hip.h: foreground sum and count, the centroid\n"
+      "              moments, background pixels, flags, background status and mean, intensity, variance), and one summary line.  With several\n"
+      "              GPUs their integer accumulators are added.  Masked pixels and pixels above --max-valid do not count; a reflection whose\n"
+      "              foreground meets one is flagged.  Not with --validate\n"
       "--validate:  every image is also decided by an independent path (every valid pixel's window gathered from memory,\n"
       "              no streaming kernel) and the two strong-pixel masks are compared: Match / Mismatch per image\n"
       "--devices / --gpus: one context and worker pool per GPU, all pulling frames from the one queue\n"
@@ -139,6 +152,7 @@ Args parse_args(int argc, char** argv) {
     }
     Args r;
     bool model_given = false;   // --spot-background-model, in either spelling: refused without --spot-background
+    bool integrate_option_given = false;   // --sigma-b, --sigma-m and the --integrate-* options: refused without --integrate
     if (const char* e = std::getenv("SPOTFINDER_TIMEOUT")) {  // spotfinder.cc:293-301
         try { r.timeout = std::stof(e); } catch (...) { std::printf("Ignoring invalid SPOTFINDER_TIMEOUT value: %s\n", e); }
     }
@@ -261,6 +275,36 @@ Args parse_args(int argc, char** argv) {
             else arg_error("--spot-background-model takes constant or glm: " + v);
             model_given = true;
         }
+        else if (s == "--integrate") {
+            r.integrate = need(i, s);
+            if (r.integrate.empty()) arg_error("--integrate takes the file of predicted reflections");
+        }
+        else if (s == "--integrate-out") {
+            r.integrate_out = need(i, s);
+            if (r.integrate_out.empty()) arg_error("--integrate-out takes the prefix of the file it writes");
+        }
+        else if (s == "--sigma-b" || s == "--sigma-m" || s == "--integrate-n-sigma") {
+            const std::string& v = need(i, s);
+            char* end = nullptr;
+            const double x = std::strtod(v.c_str(), &end);
+            if (v.empty() || *end || !(x > 0.0 && x <= 1e6)) arg_error(s + " takes a finite number > 0: " + v);
+            (s == "--sigma-b" ? r.sigma_b : s == "--sigma-m" ? r.sigma_m : r.integrate_n_sigma) = x;
+            integrate_option_given = true;
+        }
+        else if (s == "--integrate-algorithm") {
+            const std::string& v = need(i, s);
+            if (v == "ellipsoid") r.integrate_algorithm = FFS_SHOEBOX_ELLIPSOID;
+            else if (v == "dials") r.integrate_algorithm = FFS_SHOEBOX_DIALS;
+            else arg_error("--integrate-algorithm takes ellipsoid or dials: " + v);
+            integrate_option_given = true;
+        }
+        else if (s == "--integrate-background") {
+            const std::string& v = need(i, s);
+            if (v == "tukey") r.integrate_background = 0;
+            else if (v == "glm") r.integrate_background = 1;
+            else arg_error("--integrate-background takes tukey or glm: " + v);
+            integrate_option_given = true;
+        }
         else if (s == "--radial-bins") {
             const std::string& v = need(i, s);
             r.radial_bins = u32(v, s);
@@ -301,6 +345,14 @@ Args parse_args(int argc, char** argv) {
         arg_error("--pedestal-min-frames and --pedestal-max-rms belong to --jungfrau-pedestal");
     }
     if (model_given && !r.spot_background) arg_error("--spot-background-model belongs to --spot-background");
+    if (!r.integrate.empty()) {
+        if (!(r.sigma_b > 0.0) || !(r.sigma_m > 0.0)) arg_error("--integrate needs both --sigma-b and --sigma-m (degrees): the foreground is an ellipsoid of n_sigma x sigma");
+        if (r.integrate_out.empty()) arg_error("--integrate needs --integrate-out PREFIX: the records go to PREFIX.shoebox_sums");
+        if (r.validate) arg_error("--integrate is not available with --validate");
+        if (!r.jungfrau_pedestal.empty()) arg_error("--jungfrau-pedestal finds no spots and integrates none: not with --integrate");
+    } else if (integrate_option_given || !r.integrate_out.empty()) {
+        arg_error("--sigma-b, --sigma-m and the --integrate-* options belong to --integrate");
+    }
     if (r.gain > 0.0 && !r.gain_map.empty()) arg_error("--gain and --gain-map exclude each other: a constant map is the scalar gain");
     std::string lower = r.algorithm;   // DispersionAlgorithm, spotfinder.cc:180-203
     std::transform(lower.begin(), lower.end(), lower.begin(), [](unsigned char ch) { return (char)std::tolower(ch); });

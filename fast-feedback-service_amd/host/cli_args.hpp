@@ -35,6 +35,12 @@ struct Args {
     int radial_blur = 0;                 // --radial-blur narrow | wide: FFS_RADIAL_BLUR_*, -a radial_profile's smoothing ahead of the threshold; 0 = not given
     bool spot_background_glm = false;    // --spot-background-model glm: the ring's background by the robust Poisson GLM instead of Tukey's fence (constant); needs --spot-background
     uint32_t spot_background = 0;        // --spot-background B (1..16): per spot, the background of the ring of B pixels around its box and the background-subtracted intensity; 0 = not given
+    // --integrate FILE: summation integration of the predicted reflections in FILE (48-byte records: centre x, y, z as float64, the half-open box as
+    // six int32) over the run; needs --sigma-b, --sigma-m (degrees, > 0) and --integrate-out PREFIX (PREFIX.shoebox_sums); empty = not given
+    std::string integrate, integrate_out;
+    double sigma_b = 0.0, sigma_m = 0.0, integrate_n_sigma = 3.0;
+    int integrate_algorithm = 0;         // --integrate-algorithm ellipsoid (FFS_SHOEBOX_ELLIPSOID) | dials (FFS_SHOEBOX_DIALS)
+    int integrate_background = 0;        // --integrate-background tukey (0) | glm (1)
     std::string pixel_stats;             // --pixel-stats PREFIX: per-pixel count, sum, sum of squares and maximum over the run, into PREFIX.*; empty = not given
     uint32_t min_count = 2;
     int kernel_half_x = 3, kernel_half_y = 3;   // --kernel-size

@@ -35,6 +35,8 @@
 #include "kabsch_space.hpp"
 #include "png_writer.hpp"
 #include "reader.hpp"
+#include "shoebox_geometry.hpp"
+#include "../csrc/shoebox_model.hpp"
 #include "../csrc/sweep_plan.hpp"
 
 using namespace ffshost;
@@ -405,6 +407,78 @@ static int read_experiment(const Args& args, const Reader& reader, Experiment& e
     return 0;
 }
 
+// --integrate FILE, ahead of the run: the flat single-panel geometry of kabsch_space.hpp and the file's records as a shoebox table
+// (shoebox_geometry.hpp), a job opened on every context.  The geometry is printed as the key=value words `ffs_hosttool shoebox` takes, every
+// number as %.17g (it parses back to the same float64).  -> 0, or the exit code
+static int open_integration(const Args& args, const Experiment& ex, bool rotation, const std::vector<ffs_ctx*>& ctxs, size_t& n_boxes) {
+    if (!rotation) {
+        std::printf("Error: --integrate needs a rotation source (an oscillation width above 0)\n");
+        return 1;
+    }
+    const DetectorGeometry& d = ex.detector;
+    const KabschGeometry kg{d.distance * 1000.0, d.beam_center_x, d.beam_center_y, d.pixel_size_x * 1000.0, d.pixel_size_y * 1000.0, ex.wavelength,
+                            ex.oscillation_start, ex.oscillation_width};
+    std::vector<ffs_shoebox> table;
+    try {
+        for (const ShoeboxRecord& r : read_shoebox_file(args.integrate)) table.push_back(shoebox_from_record(kg, r));
+    } catch (const std::exception& e) {
+        std::printf("Error: --integrate: %s\n", e.what());
+        return 1;
+    }
+    if (table.size() > 0xFFFFFFFFull) {
+        std::printf("Error: --integrate: more than 2^32 - 1 reflections\n");
+        return 1;
+    }
+    const ffs_scan_geometry g = shoebox_flat_geometry(kg);
+    const double delta_b = shoebox_delta(args.integrate_n_sigma, args.sigma_b), delta_m = shoebox_delta(args.integrate_n_sigma, args.sigma_m);
+    for (ffs_ctx* cx : ctxs)
+        FFS_CHECK(cx, ffs_ctx_shoebox_begin(cx, &g, table.data(), (uint32_t)table.size(), args.integrate_algorithm, delta_b, delta_m));
+    n_boxes = table.size();
+    std::printf("Integration: %zu reflections from %s, %s foreground of %.17g x sigma_b %.17g and sigma_m %.17g degrees, %s background\n", n_boxes, args.integrate.c_str(),
+                args.integrate_algorithm == FFS_SHOEBOX_DIALS ? "dials" : "ellipsoid", args.integrate_n_sigma, args.sigma_b, args.sigma_m,
+                args.integrate_background ? "glm" : "tukey");
+    std::printf("Integration geometry: distance=%.17g beam_x=%.17g beam_y=%.17g pixel_x=%.17g pixel_y=%.17g wavelength=%.17g osc_start=%.17g osc_width=%.17g\n",
+                kg.distance_mm, kg.beam_center_x_px, kg.beam_center_y_px, kg.pixel_size_x_mm, kg.pixel_size_y_mm, kg.wavelength, kg.oscillation_start, kg.oscillation_width);
+    return 0;
+}
+
+// --integrate, after the last wait: the records into PREFIX.shoebox_sums and the summary line.  One context hands out its records; with
+// several, their integer accumulators and histograms are added on the host (as --pixel-stats adds its planes) and the records are made from
+// the sums by the function the library calls (csrc/shoebox_model.hpp).
+static bool write_integration(const Args& args, const std::vector<ffs_ctx*>& ctxs, size_t n_boxes) {
+    std::vector<ffs_shoebox_sum> sums(n_boxes);
+    uint32_t n = 0;
+    if (ctxs.size() == 1) {
+        FFS_CHECK(ctxs[0], ffs_ctx_get_shoebox_sums(ctxs[0], args.integrate_background, sums.data(), (uint32_t)n_boxes, &n));
+    } else {
+        std::vector<ffsamd::ShoeboxAcc> acc(n_boxes, ffsamd::ShoeboxAcc{});
+        std::vector<uint32_t> hist(n_boxes * (size_t)ffsamd::kSpotBgBins, 0u), bins((size_t)ffsamd::kSpotBgBins);
+        std::vector<ffs_shoebox_sum> part(n_boxes);
+        for (ffs_ctx* cx : ctxs) {
+            FFS_CHECK(cx, ffs_ctx_get_shoebox_sums(cx, args.integrate_background, part.data(), (uint32_t)n_boxes, &n));
+            for (size_t i = 0; i < n_boxes; ++i) {
+                acc[i].fg_sum += part[i].fg_sum, acc[i].m_x += part[i].m_x, acc[i].m_y += part[i].m_y, acc[i].m_z += part[i].m_z;
+                acc[i].fg_count += part[i].fg_count, acc[i].n_overflow += part[i].n_overflow, acc[i].flags |= part[i].flags;
+                FFS_CHECK(cx, ffs_ctx_get_shoebox_histogram(cx, (uint32_t)i, bins.data()));
+                for (size_t v = 0; v < bins.size(); ++v) hist[i * bins.size() + v] += bins[v];
+            }
+        }
+        for (size_t i = 0; i < n_boxes; ++i) {
+            const ffsamd::ShoeboxSum r = ffsamd::shoebox_sum(acc[i], hist.data() + i * (size_t)ffsamd::kSpotBgBins, args.integrate_background);
+            static_assert(sizeof r == sizeof sums[i], "the model's record is ffs_shoebox_sum");
+            std::memcpy(&sums[i], &r, sizeof r);
+        }
+    }
+    const std::string name = args.integrate_out + ".shoebox_sums";
+    std::ofstream f(name, std::ios::binary | std::ios::trunc);
+    if (!f || !f.write(reinterpret_cast<const char*>(sums.data()), (std::streamsize)(sums.size() * sizeof(ffs_shoebox_sum))) || !f.flush()) {
+        std::printf("Error: --integrate-out: cannot write %s\n", name.c_str());
+        return false;
+    }
+    std::printf("Integration: %s -> %s\n", shoebox_summary_line(sums.data(), sums.size()).c_str(), name.c_str());
+    return true;
+}
+
 // frames per GPU batch.  Chunks: 16 for long runs (120 MB of staging per batch for Eiger-16M: the threshold kernels are tuned
 // for 16-32 frames and PCIe, not the GPU, is the limit), 8 for runs below 2048 images per GPU -- a stream's device buffers
 // (37 MB per frame of the batch) are prepared by the driver on FIRST USE at ~60 GB/s, so four assemblies of 16 frames cost a
@@ -663,6 +737,12 @@ class BatchReport {
                 std::printf("Error: %s\n", ffs_last_error(ctxs_[batch.gpu]));
                 return false;
             }
+        }
+        // --integrate: the batch's frames into the context's job, once, while they are still where the batch left them (image numbers are
+        // consecutive inside a batch: batch_pipeline.hpp)
+        if (!args_.integrate.empty() && nres > 0 && ffs_stream_shoebox_fold(batch.stream, res[0].frame_id, nullptr) != FFS_OK) {
+            std::printf("Error: %s\n", ffs_last_error(ctxs_[batch.gpu]));
+            return false;
         }
         // what this batch prints and sends goes out in one piece each (the collector is the one thread between the GPU and a
         // free staging area: a printf and a write per image, into pipes a Python caller drains, were on that path)
@@ -1056,6 +1136,9 @@ int main(int argc, char** argv) {
     // --pixel-stats: every context accumulates from its first batch on (the validation contexts see the same frames again, and do not)
     if (!args.pixel_stats.empty())
         for (ffs_ctx* cx : ctxs) FFS_CHECK(cx, ffs_ctx_set_pixel_stats(cx, FFS_PIXEL_STATS_START));
+    size_t n_shoeboxes = 0;
+    if (!args.integrate.empty())
+        if (const int rc = open_integration(args, ex, rotation, ctxs, n_shoeboxes)) return rc;
     if (args.validate && !create_validation_contexts(devices, ctxs, shape, batch, prm, args.max_valid_scope, args.gain, gain_map, vctxs)) return 1;
     if (args.validate && jungfrau && gpu_decode)   // (the validation streams are handed the same raw chunks)
         for (ffs_ctx* v : vctxs) FFS_CHECK(v, set_jungfrau_calibration(v, jungfrau_planes, shape.pixels()));
@@ -1106,6 +1189,7 @@ int main(int argc, char** argv) {
     else if (args.save_h5) write_2d_h5(report.reflection_centers_2d);
     print_summary(args, shape, pipeline, report, gather.get(), n_dev, all_start, stamp.process_start());
     if (!args.pixel_stats.empty() && !write_pixel_stats(args.pixel_stats, ctxs, shape.width, shape.height)) return 1;
+    if (!args.integrate.empty() && !write_integration(args, ctxs, n_shoeboxes)) return 1;
     pipe.reset();
     exchange.join();
     stamp("timed loop and reports done");

@@ -105,6 +105,24 @@ SPOT_BG_GLM_DT = np.dtype([("n_pixels", "<u4"), ("n_overflow", "<u4"), ("median"
 assert SPOT_BG_GLM_DT.itemsize == C.sizeof(_SpotBackgroundGlm) == 40
 
 
+# Summation integration of shoeboxes in Kabsch space (ffs_ctx_shoebox_begin, ffs_stream_shoebox_fold, ffs_ctx_get_shoebox_sums)
+class _ScanGeometry(C.Structure):   # ffs_scan_geometry
+    _fields_ = [("d_matrix", C.c_double * 9), ("pixel_size_mm", C.c_double * 2), ("wavelength", C.c_double), ("s0", C.c_double * 3),
+                ("rot_axis", C.c_double * 3), ("osc_start_deg", C.c_double), ("osc_width_deg", C.c_double)]
+
+
+SHOEBOX_DT = np.dtype([("s1", "<f8", (3,)), ("phi", "<f8"), ("x_min", "<i4"), ("x_max", "<i4"), ("y_min", "<i4"), ("y_max", "<i4"),
+                       ("z_min", "<i4"), ("z_max", "<i4")])   # ffs_shoebox
+SHOEBOX_SUM_DT = np.dtype([("fg_sum", "<u8"), ("m_x", "<u8"), ("m_y", "<u8"), ("m_z", "<u8"), ("fg_count", "<u4"), ("n_background", "<u4"),
+                           ("n_overflow", "<u4"), ("flags", "<u4"), ("bg_status", "<u4"), ("reserved", "<u4"), ("bg_mean", "<f8"),
+                           ("intensity", "<f8"), ("variance", "<f8")])   # ffs_shoebox_sum
+assert C.sizeof(_ScanGeometry) == 160 and SHOEBOX_DT.itemsize == 56 and SHOEBOX_SUM_DT.itemsize == 80
+SHOEBOX_ELLIPSOID, SHOEBOX_DIALS = 0, 1   # FFS_SHOEBOX_*: what Context.shoebox_begin takes ("ellipsoid" / "dials")
+SHOEBOX_ALGORITHMS = {"ellipsoid": SHOEBOX_ELLIPSOID, "dials": SHOEBOX_DIALS}
+SHOEBOX_FG_INVALID = 1                    # FFS_SHOEBOX_FG_INVALID, in a record's flags
+SHOEBOX_BACKGROUNDS = {"tukey": 0, "glm": 1}
+
+
 # ffs_radial_shell: what the radial-profile threshold decided for one (frame, shell) -- Stream.radial_thresholds
 RADIAL_SHELL_DT = np.dtype([("n_pixels", "<u4"), ("n_overflow", "<u4"), ("q1", "<i4"), ("median", "<i4"), ("q3", "<i4"), ("cutoff", "<u4"),
                             ("status", "<u4"), ("reserved", "<u4")])
@@ -156,6 +174,7 @@ EXPORTS = [
     "ffs_ctx_set_jungfrau_calibration",
     "ffs_ctx_jungfrau_pedestal_begin", "ffs_ctx_jungfrau_pedestal_end", "ffs_stream_jungfrau_pedestal_fold", "ffs_ctx_get_jungfrau_pedestal",
     "ffs_jungfrau_pedestal_planes",
+    "ffs_ctx_shoebox_begin", "ffs_ctx_shoebox_end", "ffs_stream_shoebox_fold", "ffs_ctx_get_shoebox_sums", "ffs_ctx_get_shoebox_histogram",
 ]
 
 _lib = None
@@ -200,6 +219,11 @@ def load_library():
         L.ffs_bench_pixel_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_uint32, C.c_uint32, C.POINTER(C.c_float)]
         L.ffs_stream_spot_backgrounds.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_void_p), C.POINTER(C.c_uint32), C.POINTER(C.c_float)]
         L.ffs_stream_spot_backgrounds_glm.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_void_p), C.POINTER(C.c_uint32), C.POINTER(C.c_float)]
+        L.ffs_ctx_shoebox_begin.argtypes = [C.c_void_p, C.POINTER(_ScanGeometry), C.c_void_p, C.c_uint32, C.c_int, C.c_double, C.c_double]
+        L.ffs_ctx_shoebox_end.argtypes = [C.c_void_p]
+        L.ffs_stream_shoebox_fold.argtypes = [C.c_void_p, C.c_int64, C.POINTER(C.c_float)]
+        L.ffs_ctx_get_shoebox_sums.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]
+        L.ffs_ctx_get_shoebox_histogram.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p]
         L.ffs_bench_pipeline.argtypes = [C.POINTER(C.c_void_p), C.c_uint32, C.c_void_p, C.c_size_t, C.c_size_t, C.c_uint32,
                                          C.c_uint32, C.c_int64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
         L.ffs_device_numa_node.argtypes = [C.c_int]
@@ -471,6 +495,53 @@ class Context:
         self._check(self._lib.ffs_ctx_get_jungfrau_pedestal(self._h, C.byref(out)))
         return (int(out.n_frames), arrays.get("count"), arrays.get("sum"), arrays.get("sum_sq"))
 
+    def shoebox_begin(self, geometry, shoeboxes, algorithm="ellipsoid", *, delta_b: float, delta_m: float):
+        """ffs_ctx_shoebox_begin: open a summation-integration job.  geometry: a mapping (or object) with d_matrix (9, row-major),
+        pixel_size_mm (2), wavelength, s0 (3), rot_axis (3), osc_start_deg, osc_width_deg; shoeboxes: a structured array of SHOEBOX_DT (s1,
+        phi in radians, the half-open box); algorithm "ellipsoid" or "dials" (or FFS_SHOEBOX_*); delta_b, delta_m: n_sigma * sigma in
+        radians.  FfsError (state unchanged): a batch in flight, a job already open, a delta that is not finite and positive, an unknown
+        algorithm, a table entry the library names."""
+        get = geometry.get if hasattr(geometry, "get") else (lambda k: getattr(geometry, k))
+        g = _ScanGeometry()
+        for name, n in (("d_matrix", 9), ("pixel_size_mm", 2), ("s0", 3), ("rot_axis", 3)):
+            v = np.asarray(get(name), np.float64).reshape(-1)
+            if v.size != n:
+                raise ValueError(f"geometry {name} must have {n} entries, not {v.size}")
+            setattr(g, name, (C.c_double * n)(*v))
+        for name in ("wavelength", "osc_start_deg", "osc_width_deg"):
+            setattr(g, name, float(get(name)))
+        t = np.ascontiguousarray(shoeboxes, dtype=SHOEBOX_DT)
+        algo = SHOEBOX_ALGORITHMS.get(algorithm, algorithm) if isinstance(algorithm, str) else algorithm
+        if isinstance(algo, str):
+            raise ValueError(f"algorithm must be one of {sorted(SHOEBOX_ALGORITHMS)}, not {algorithm!r}")
+        self._check(self._lib.ffs_ctx_shoebox_begin(self._h, C.byref(g), t.ctypes.data_as(C.c_void_p) if len(t) else None, len(t), int(algo),
+                                                    float(delta_b), float(delta_m)))
+
+    def shoebox_end(self):
+        """ffs_ctx_shoebox_end: free the job; idempotent."""
+        self._check(self._lib.ffs_ctx_shoebox_end(self._h))
+
+    def shoebox_sums(self, background="tukey"):
+        """ffs_ctx_get_shoebox_sums: one record (SHOEBOX_SUM_DT) per shoebox in table order, from everything folded so far
+        (Stream.shoebox_fold); background "tukey" or "glm" (or 0 / 1): the model the box's histogram is put through."""
+        model = SHOEBOX_BACKGROUNDS.get(background, background) if isinstance(background, str) else background
+        if isinstance(model, str):
+            raise ValueError(f"background must be one of {sorted(SHOEBOX_BACKGROUNDS)}, not {background!r}")
+        n = C.c_uint32()
+        rc = self._lib.ffs_ctx_get_shoebox_sums(self._h, int(model), None, 0, C.byref(n))
+        if rc != -4:   # FFS_ERR_OVERFLOW: the table's length is in n
+            self._check(rc)
+        out = np.zeros(n.value, SHOEBOX_SUM_DT)
+        if n.value:
+            self._check(self._lib.ffs_ctx_get_shoebox_sums(self._h, int(model), out.ctypes.data_as(C.c_void_p), n.value, C.byref(n)))
+        return out
+
+    def shoebox_histogram(self, index: int) -> np.ndarray:
+        """ffs_ctx_get_shoebox_histogram: the 256 raw bins of shoebox `index` (uint32)."""
+        bins = np.zeros(256, np.uint32)
+        self._check(self._lib.ffs_ctx_get_shoebox_histogram(self._h, int(index), bins.ctypes.data_as(C.c_void_p)))
+        return bins
+
     def set_tuning(self, **kw):
         """ffs_ctx_set_tuning: A/B partners, fall-backs and capacities (same results either way); see include/ffs_hip.h."""
         for k, v in kw.items():
@@ -713,6 +784,14 @@ class Stream:
         else:
             a = np.zeros(0, SPOT_BG_DT)
         return (a, ms.value) if want_ms else a
+
+    def shoebox_fold(self, first_image: int, want_ms: bool = False):
+        """ffs_stream_shoebox_fold: fold the frames of the last batch wait() returned into the context's job (Context.shoebox_begin); frame f
+        of the batch is image first_image + f of the scan.  Between wait() and the next submit on this stream; synchronous.  Folding an
+        image twice counts it twice.  Returns the kernel's milliseconds with want_ms (0 when no box met the images)."""
+        ms = C.c_float()
+        self.ctx._check(self._lib.ffs_stream_shoebox_fold(self._h, int(first_image), C.byref(ms) if want_ms else None))
+        return ms.value if want_ms else None
 
     def spot_backgrounds_glm(self, border: int = 3, copy: bool = True, want_ms: bool = False):
         """ffs_stream_spot_backgrounds_glm: the same ring under the robust Poisson GLM (constant mean, Huber's c = 1.345), as a structured

@@ -19,6 +19,14 @@
 //                                         ffs_stream_spot_backgrounds_glm compiles) of histograms read from the file or standard input, 257
 //                                         unsigned integers a line (the bins 0 .. 255, then the tail): one record a line, n_pixels n_overflow
 //                                         median n_iter status beta mean, the two doubles as the 16 hex digits of their bit patterns
+//   ffs_hosttool shoebox key=value ...   summation integration on the CPU by csrc/shoebox_model.hpp, the text the kernel of
+//                                         ffs_stream_shoebox_fold compiles: frames=<file of images, one behind the other> width= height=
+//                                         bytes=2|4 [mask=<W*H bytes, non-zero = valid>] [max_valid=N] distance= beam_x= beam_y= pixel_x=
+//                                         pixel_y= wavelength= osc_start= osc_width= boxes=<the file spotfinder --integrate reads> sigma_b=
+//                                         sigma_m= [n_sigma=3] [algorithm=ellipsoid|dials] [background=tukey|glm] out=<file>: writes the
+//                                         ffs_shoebox_sum records spotfinder writes to PREFIX.shoebox_sums and prints its summary line
+//   ffs_hosttool shoeboxgeom key=value ...  the geometry keys and boxes= of the above: the ffs_scan_geometry (20 doubles) and every box's
+//                                         s1 and phi as host/shoebox_geometry.hpp computes them, 16 hex digits a double
 #include <cinttypes>
 #include <cstdio>
 #include <cstdlib>
@@ -28,7 +36,13 @@
 #include <iterator>
 #include <random>
 
+#include <map>
+
+#include "../csrc/launch_geometry.hpp"
+#include "../csrc/shoebox_model.hpp"
+#include "../csrc/shoebox_plan.hpp"
 #include "../csrc/spot_background_glm_model.hpp"
+#include "shoebox_geometry.hpp"
 #include "codecs.hpp"
 #include "reader.hpp"
 
@@ -315,6 +329,111 @@ static int spotbgglm(const char* path) {
     return rc;
 }
 
+// key=value arguments of the two shoebox commands
+struct KeyValues {
+    std::map<std::string, std::string> kv;
+    KeyValues(int argc, char** argv) {
+        for (int i = 2; i < argc; ++i) {
+            const std::string a = argv[i];
+            const size_t eq = a.find('=');
+            if (eq == std::string::npos) throw std::runtime_error("expected key=value, got " + a);
+            kv[a.substr(0, eq)] = a.substr(eq + 1);
+        }
+    }
+    bool has(const std::string& k) const { return kv.count(k) != 0; }
+    std::string str(const std::string& k) const {
+        auto it = kv.find(k);
+        if (it == kv.end()) throw std::runtime_error("missing " + k + "=");
+        return it->second;
+    }
+    double num(const std::string& k) const { return std::stod(str(k)); }
+    KabschGeometry geometry() const {
+        return KabschGeometry{num("distance"), num("beam_x"), num("beam_y"), num("pixel_x"), num("pixel_y"), num("wavelength"), num("osc_start"), num("osc_width")};
+    }
+};
+
+static uint64_t bits_of(double v) {
+    uint64_t u;
+    std::memcpy(&u, &v, sizeof u);
+    return u;
+}
+
+static int shoeboxgeom(const KeyValues& kv) {
+    const KabschGeometry kg = kv.geometry();
+    const ffs_scan_geometry g = shoebox_flat_geometry(kg);
+    double v[20];   // (ffs_scan_geometry is twenty doubles)
+    static_assert(sizeof g == sizeof v, "ffs_scan_geometry is twenty doubles");
+    std::memcpy(v, &g, sizeof v);
+    for (int i = 0; i < 20; ++i) std::printf("%016" PRIx64 "%c", bits_of(v[i]), i == 19 ? '\n' : ' ');
+    for (const ShoeboxRecord& r : read_shoebox_file(kv.str("boxes"))) {
+        const ffs_shoebox b = shoebox_from_record(kg, r);
+        std::printf("%016" PRIx64 " %016" PRIx64 " %016" PRIx64 " %016" PRIx64 "\n", bits_of(b.s1[0]), bits_of(b.s1[1]), bits_of(b.s1[2]), bits_of(b.phi));
+    }
+    return 0;
+}
+
+template <typename PixelT>
+static void shoebox_fold_all(const ffsamd::ShoeboxGeometry& g, const std::vector<ffsamd::ShoeboxEntry>& table, int algorithm, double delta_b, double delta_m,
+                             const std::vector<uint8_t>& frames, int W, int H, const uint8_t* mask, uint32_t limit, std::vector<ffsamd::ShoeboxAcc>& acc,
+                             std::vector<uint32_t>& hist) {
+    const size_t frame_bytes = (size_t)W * H * sizeof(PixelT), n_images = frames.size() / frame_bytes;
+    for (size_t i = 0; i < table.size(); ++i)
+        for (int64_t n = std::max<int64_t>(table[i].z_min, 0); n < table[i].z_max && n < (int64_t)n_images; ++n)
+            ffsamd::shoebox_fold_image(g, table[i], algorithm, delta_b, delta_m, reinterpret_cast<const PixelT*>(frames.data() + (size_t)n * frame_bytes), (size_t)W, W, H, mask,
+                                       limit, n, acc[i], hist.data() + i * (size_t)ffsamd::kSpotBgBins);
+}
+
+static int shoebox(const KeyValues& kv) {
+    const KabschGeometry kg = kv.geometry();
+    const ffs_scan_geometry fg = shoebox_flat_geometry(kg);
+    ffsamd::ShoeboxGeometry g;
+    static_assert(sizeof g == sizeof fg, "the model's geometry is ffs_scan_geometry");
+    std::memcpy(&g, &fg, sizeof g);
+    const int W = (int)kv.num("width"), H = (int)kv.num("height"), bytes = (int)kv.num("bytes");
+    if (W <= 0 || H <= 0 || (bytes != 2 && bytes != 4)) return fail("shoebox: width and height must be positive, bytes 2 or 4");
+    const std::vector<uint8_t> frames = read_file(kv.str("frames"));
+    if (frames.size() % ((size_t)W * H * bytes) != 0) return fail("shoebox: the frames file is not a whole number of images");
+    std::vector<uint8_t> mask;
+    if (kv.has("mask")) {
+        mask = read_file(kv.str("mask"));
+        if (mask.size() != (size_t)W * H) return fail("shoebox: the mask file is not width * height bytes");
+    }
+    const long long max_valid = kv.has("max_valid") ? std::stoll(kv.str("max_valid")) : -1;
+    const std::string algo = kv.has("algorithm") ? kv.str("algorithm") : "ellipsoid", bg = kv.has("background") ? kv.str("background") : "tukey";
+    if ((algo != "ellipsoid" && algo != "dials") || (bg != "tukey" && bg != "glm")) return fail("shoebox: algorithm is ellipsoid or dials, background tukey or glm");
+    const double n_sigma = kv.has("n_sigma") ? kv.num("n_sigma") : 3.0;
+    const double delta_b = shoebox_delta(n_sigma, kv.num("sigma_b")), delta_m = shoebox_delta(n_sigma, kv.num("sigma_m"));
+    std::vector<ffsamd::ShoeboxEntry> table;
+    for (const ShoeboxRecord& r : read_shoebox_file(kv.str("boxes"))) {
+        const ffs_shoebox b = shoebox_from_record(kg, r);
+        ffsamd::ShoeboxEntry e;
+        static_assert(sizeof e == sizeof b, "the model's table entry is ffs_shoebox");
+        std::memcpy(&e, &b, sizeof e);
+        table.push_back(e);
+    }
+    // (what ffs_ctx_shoebox_begin refuses is refused here, by the same text)
+    std::string why = ffsamd::shoebox_job_refusal(g, algo == "dials" ? ffsamd::kShoeboxDials : ffsamd::kShoeboxEllipsoid, delta_b, delta_m);
+    if (!why.empty()) return fail(("shoebox: " + why).c_str());
+    const int64_t bad = ffsamd::shoebox_table_refusal(table.data(), (uint32_t)table.size(), g.s0, W, H, why);
+    if (bad >= 0) return fail(("shoebox: shoebox " + std::to_string(bad) + " " + why).c_str());
+    std::vector<ffsamd::ShoeboxAcc> acc(table.size(), ffsamd::ShoeboxAcc{});
+    std::vector<uint32_t> hist(table.size() * (size_t)ffsamd::kSpotBgBins, 0u);
+    const uint32_t limit = ffsamd::counting_limit(max_valid);
+    const int algorithm = algo == "dials" ? ffsamd::kShoeboxDials : ffsamd::kShoeboxEllipsoid;
+    if (bytes == 2) shoebox_fold_all<uint16_t>(g, table, algorithm, delta_b, delta_m, frames, W, H, mask.empty() ? nullptr : mask.data(), limit, acc, hist);
+    else shoebox_fold_all<uint32_t>(g, table, algorithm, delta_b, delta_m, frames, W, H, mask.empty() ? nullptr : mask.data(), limit, acc, hist);
+    std::vector<ffs_shoebox_sum> sums(table.size());
+    for (size_t i = 0; i < table.size(); ++i) {
+        const ffsamd::ShoeboxSum r = ffsamd::shoebox_sum(acc[i], hist.data() + i * (size_t)ffsamd::kSpotBgBins, bg == "glm" ? ffsamd::kShoeboxBgGlm : ffsamd::kShoeboxBgTukey);
+        static_assert(sizeof r == sizeof sums[i], "the model's record is ffs_shoebox_sum");
+        std::memcpy(&sums[i], &r, sizeof r);
+    }
+    std::ofstream o(kv.str("out"), std::ios::binary);
+    o.write(reinterpret_cast<const char*>(sums.data()), (std::streamsize)(sums.size() * sizeof(ffs_shoebox_sum)));
+    std::printf("%s\n", shoebox_summary_line(sums.data(), sums.size()).c_str());
+    return o ? 0 : fail("shoebox: cannot write the file");
+}
+
 // chunkfnv <chunk file> <nelem> <elem bytes>: decode one bitshuffle-LZ4 chunk with the host codec and
 // print the FNV-1a of the pixels (cross-check for chunk writers)
 static int chunkfnv(const std::string& path, size_t nelem, size_t es) {
@@ -347,6 +466,8 @@ int main(int argc, char** argv) {
         if (cmd == "jfrepedestal" && argc >= 5 && argc <= 7) return jfrepedestal(argv[2], argv[3], argv[4], argc > 5 ? argv[5] : "1", argc > 6 ? argv[6] : "0");
         if (cmd == "h5stats" && argc == 4) { h5_print_group_stats(argv[2], argv[3]); return 0; }
         if (cmd == "spotbgglm" && argc <= 3) return spotbgglm(argc == 3 ? argv[2] : nullptr);
+        if (cmd == "shoebox") return shoebox(KeyValues(argc, argv));
+        if (cmd == "shoeboxgeom") return shoeboxgeom(KeyValues(argc, argv));
         if (cmd == "h5support") { std::printf("%d\n", h5_supported() ? 1 : 0); return 0; }
     } catch (const std::exception& e) {
         std::printf("Error: %s\n", e.what());
@@ -357,6 +478,6 @@ int main(int argc, char** argv) {
                 "       h5info <master.h5> | synthinfo <synth:spec> | h5support | h5stats <file.h5> <group> |\n"
                 "       chunkfnv <chunk> <nelem> <elem bytes> | jfcal <synth:spec> <file> | jfconvert <raw> <cal> <W> <H> <out> |\n"
                 "       synthframes <synth:spec> <file> | jfrepedestal <old cal> <prefix> <new cal> [min_frames [max_rms]] |\n"
-                "       spotbgglm [histograms]\n");
+                "       spotbgglm [histograms] | shoebox key=value ... | shoeboxgeom key=value ...\n");
     return 2;
 }

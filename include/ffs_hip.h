@@ -491,7 +491,7 @@ int ffs_jungfrau_pedestal_planes(const ffs_jungfrau_pedestal_stats *stats, size_
  *                          clamped to 1..H, each ceil(H / bands) rows tall (tests put the band seams where they want them)
  *   "radthr_form"      (0) ... and how a lane's counts meet the workgroup's table in LDS: 1 = one add per counting pixel, 2 = a run of equal
  *                          (shell, value) pairs kept in registers, 0 = the one that measured faster for the pixel size (2 for 16-bit
- *                          pixels, 1 for 32-bit: DESIGN.md section 3.9)
+ *                          pixels, 1 for 32-bit: DESIGN.md section 3.8c)
  *   "assembly_threads" (7: helper threads that build a batch's result arrays; 3, 12 and 15 measure the same): see DESIGN.md.
  *   "band_taper" (0), "ext_rest_aside" (0), "ext_fused" (0): round 4's A/B partners (tapered bands of the streaming kernels;
  *                          extended algorithm: erosion + final pass in the sparse stream / fused into one kernel) -- measured, no
@@ -759,6 +759,87 @@ typedef struct {
     double beta, mean;
 } ffs_spot_background_glm;        /* 40 bytes */
 int ffs_stream_spot_backgrounds_glm(ffs_stream *s, uint32_t border, const ffs_spot_background_glm **out, uint32_t *n, float *kernel_ms);
+
+/* Summation integration of predicted reflections' shoeboxes in Kabsch space: the stage of the reference's pipeline
+ * that follows spot finding (integrator/kabsch.cu, integrator/integrator.cc), for a flat panel without parallax correction.  A job is a
+ * table of shoeboxes on a context; every batch's frames are folded into it after their ffs_wait; at the end one record per shoebox gives
+ * the foreground sum, the centroid moments, the background under one of the two models above, I = fg_sum - fg_count * b and its variance.
+ * THE RULE is stated once, in csrc/shoebox_model.hpp, which the kernel, this library's host side and `ffs_hosttool shoebox` compile; no
+ * parity with the reference's binaries (whose scalar type may be float) is claimed.  Every operation is an IEEE float64 + - * / sqrt in
+ * the order written there, compiled without contraction:
+ *   corner (cx, cy) -- integers, may lie outside the image: x = cx * pixel_size_mm[0], y = cy * pixel_size_mm[1],
+ *     L_i = (D[3i]*x + D[3i+1]*y) + D[3i+2], s = (L / |L|) / wavelength;
+ *   per reflection: e1 = normalized(cross(s1, s0)), e2 = normalized(cross(s1, e1)), len = |s1|, zeta = dot(rot_axis, e1);
+ *   per corner: eps1 = dot(e1, s - s1) / len, eps2 = dot(e2, s - s1) / len;
+ *   image n (0-based position in the scan): phi_low = (osc_start_deg + n * osc_width_deg) * (pi / 180), phi_high the same with n + 1,
+ *     centre = phi_low <= phi <= phi_high;
+ *   FFS_SHOEBOX_ELLIPSOID: a corner is foreground when (eps1^2 + eps2^2) / delta_b^2 + e3^2 / delta_m^2 <= 1 for e3 = zeta * (phi_low - phi),
+ *     e3 = zeta * (phi_high - phi) or, when centre holds, e3 = 0;  FFS_SHOEBOX_DIALS: (eps1^2 + eps2^2) / delta_b^2 <= 1;
+ *   a pixel is foreground when any of its four corners {px, px+1} x {py, py+1} is.
+ * A pixel COUNTS when it lies in the image, its mask bit is set, it is <= max_valid when that is set and, for 32-bit pixels, < 2^24 (the
+ * rule of ffs_stream_spot_backgrounds).  On image n a pixel p of a box with z_min <= n < z_max:
+ *   foreground and counting      fg_sum += p, fg_count += 1, m_x += p (2 px + 1), m_y += p (2 py + 1), m_z += p (2 n + 1);
+ *   foreground and not counting  flags |= FFS_SHOEBOX_FG_INVALID (the reference's d_success = 0);
+ *   background and counting      the box's histogram: bin p for p < 256, n_overflow otherwise;
+ *   background and not counting  nothing.
+ * Everything accumulated is an integer, so the result is bit for bit independent of batch size, stream, order and tuning.  (A bin and
+ * fg_count are 32 bits: a box of 2^20 pixels holds 4096 images.) */
+#define FFS_SHOEBOX_ELLIPSOID 0
+#define FFS_SHOEBOX_DIALS 1
+#define FFS_SHOEBOX_FG_INVALID 1u
+typedef struct {
+    double d_matrix[9];        /* row-major: lab = D (x_mm, y_mm, 1) */
+    double pixel_size_mm[2];
+    double wavelength;
+    double s0[3];
+    double rot_axis[3];
+    double osc_start_deg, osc_width_deg;
+} ffs_scan_geometry;              /* 160 bytes */
+typedef struct {
+    double s1[3];              /* the predicted diffracted beam vector */
+    double phi;                /* the predicted rotation angle, radians */
+    int32_t x_min, x_max, y_min, y_max, z_min, z_max;   /* half-open; pixels may lie outside the image, z counts images of the scan */
+} ffs_shoebox;                    /* 56 bytes */
+typedef struct {
+    uint64_t fg_sum, m_x, m_y, m_z;
+    uint32_t fg_count, n_background, n_overflow, flags;
+    uint32_t bg_status, reserved;   /* FFS_SPOT_BG_* of the chosen model */
+    double bg_mean, intensity, variance;
+} ffs_shoebox_sum;                /* 80 bytes */
+/* ffs_ctx_shoebox_begin opens a job: it copies the table, builds an index over the boxes' z-ranges, allocates and zeroes the accumulators
+ * (1072 bytes a shoebox; FFS_ERR_NOMEM with a text when they do not fit).  n = 0 is allowed.  delta_b and delta_m are n_sigma * sigma_b and
+ * n_sigma * sigma_m in radians.  FFS_ERR_INVALID, state unchanged (ffs_last_error has the text): a NULL geometry, or a NULL table with
+ * n > 0; a batch of the context in flight; a job already open; delta_b or delta_m not finite or not positive; an unknown algorithm; a
+ * geometry entry that is not finite, a wavelength or pixel size that is not positive; a table entry -- the text names it -- that is empty
+ * or reversed, wider or higher than 1024 pixels, does not meet the image padded by 1024 pixels, has a non-finite s1 or phi, or an s1
+ * parallel to s0.
+ * ffs_ctx_shoebox_end frees the job; idempotent (FFS_OK when there is none).  The job also goes with the context. */
+int ffs_ctx_shoebox_begin(ffs_ctx *ctx, const ffs_scan_geometry *geometry, const ffs_shoebox *shoeboxes, uint32_t n, int algorithm,
+                          double delta_b, double delta_m);
+int ffs_ctx_shoebox_end(ffs_ctx *ctx);
+/* Folds the frames of the last batch ffs_wait returned on the stream into the context's job: frame f of the batch is image
+ * first_image + f of the scan.  Runs between ffs_wait and the stream's next submit, on the frames where the batch left them (as
+ * ffs_stream_spot_backgrounds, with the same three conditions on what must still be in place), under the context's mask and the batch's
+ * max_valid.  Synchronous: one launch in a HIP stream of the job's own, a wave per shoebox the images meet; the folds of a context follow
+ * one another under a mutex, whichever streams and threads they come from.  kernel_ms may be NULL; otherwise the kernel's time from HIP
+ * events on its dispatch (0 when nothing was launched).  A fold that meets no box launches nothing and returns FFS_OK.  The stream's last
+ * batch stays as it was: its results, ffs_stream_last_path and ffs_stream_spot_backgrounds* are unchanged by a fold.
+ * FOLDING AN IMAGE TWICE COUNTS IT TWICE: which images have been folded is the caller's business.
+ * FFS_ERR_INVALID, nothing folded: a dead handle; a batch in flight on the stream; no batch waited on the stream yet, or the last
+ * ffs_wait on it failed; no job open; first_image negative, or first_image + frames beyond 2^31 - 1. */
+int ffs_stream_shoebox_fold(ffs_stream *s, int64_t first_image, float *kernel_ms);
+/* One record per shoebox, in table order, from everything folded so far; the job stays open.  background_model 0: the Tukey fence
+ * (ffs_stream_spot_backgrounds' model), 1: the robust Poisson GLM (ffs_stream_spot_backgrounds_glm's), each over the box's histogram and
+ * n_overflow, computed on the host by the function the kernels' wave-parallel forms are held to.  n_background is the model's n_pixels;
+ * bg_status its status; bg_mean = b = its mean when the status is 0, else 0.  B = b * fg_count, intensity = fg_sum - B,
+ * variance = |intensity| + |B| * (1 + fg_count / n_background) (the ratio taken as 0 without background pixels); a shoebox without
+ * foreground has intensity 0 and variance -1 (integrator.cc:1107-1161).  *n = the job's shoeboxes, always written; at most cap records
+ * are written, and FFS_ERR_OVERFLOW is returned when cap is smaller (the records written are valid).
+ * FFS_ERR_INVALID: no job open; NULL n, or NULL out with cap > 0; a background_model other than 0 and 1. */
+int ffs_ctx_get_shoebox_sums(ffs_ctx *ctx, int background_model, ffs_shoebox_sum *out, uint32_t cap, uint32_t *n);
+/* The raw 256 bins of shoebox `index`, for callers with a model of their own.  FFS_ERR_INVALID: no job open, index outside the table,
+ * NULL bins. */
+int ffs_ctx_get_shoebox_histogram(ffs_ctx *ctx, uint32_t index, uint32_t bins[256]);
 
 /* Centres of mass of the last batch's reflections as rows (frame_id, x, y, z) of float32 -- the
  * payload of `--output-for-index` (spot_centers, spotfinder.cc:919-933,1004-1006), in frame order;
