@@ -14,6 +14,8 @@
 //   ffs_spotbg.hip   ffs_stream_spot_backgrounds: the per-spot constant background of the last waited batch (kernels_spotbg.hpp)
 //   ffs_shoebox.hip  summation integration of shoeboxes in Kabsch space, from begin to end: the job on a context, ffs_stream_shoebox_fold, the sums
 //                    (kernels_shoebox.hpp); acts on the decisions of shoebox_plan.hpp
+//   ffs_predict.hip  scan prediction for a rotation sweep: ffs_predict_scan_settings and ffs_ctx_predict, a count pass, a scan and a write pass
+//                    in a HIP stream of the call's own (kernels_predict.hpp); acts on the decisions of predict_plan.hpp
 //   ffs_stack3d.hip  rotation sweeps: the device-resident 3D stack -- create and pool, append a batch's lists, finish (kernels_stack3d); acts on
 //                    the decisions of sweep_plan.hpp
 //   ffs_multi.hip    several GPUs in one process: RCCL loaded with dlopen, the communicators and the choice of transport (ffs_multi_init), the
@@ -48,6 +50,11 @@
 //                        final sums (kernels_shoebox.hpp, included by ffs_shoebox.hip; tools/ffs_hosttool.cc; tests/shoebox_check.cc)
 //   shoebox_plan.hpp     which shoebox tables are taken, the index over the boxes' z-ranges and the list a fold's launch receives
 //                        (tests/shoebox_plan_check.cc)
+//   predict_model.hpp    scan prediction: scan-point settings, candidate numbering and centring absences, the per-image ray, the impact on the
+//                        panel and the extent in Kabsch space (kernels_predict.hpp, included by ffs_predict.hip; tools/ffs_hosttool.cc;
+//                        tests/predict_check.cc)
+//   predict_plan.hpp     which prediction calls are taken, the candidate box, the call's constants, the scan-point settings from libm's cos and
+//                        sin, the whole rule on the CPU (tests/predict_plan_check.cc)
 // No exception leaves the library (guarded()).
 #pragma once
 #include <algorithm>
@@ -102,6 +109,7 @@ struct ThreadError {
 
 struct ffs_stack3d;
 struct ShoeboxJob;   // ffs_shoebox.hip
+struct PredictState; // ffs_predict.hip
 
 // A few helper threads per context for ffs_wait's result assembly (wire records -> boxes, reflections, centre rows): one thread
 // moves a batch's 7 MB (45 000 components of 32 Eiger frames) in 0.21 ms -- two thirds of the time the GPU takes for the batch, and
@@ -196,6 +204,10 @@ struct ffs_ctx {
     // come from distinct ffs_streams on distinct threads.
     ShoeboxJob* shoebox = nullptr;
     std::mutex shoebox_mu;
+    // ffs_ctx_predict: the HIP stream, events and device buffers its calls use, made by the first call and kept; a call
+    // is one step under predict_mu.  Nothing of a batch is in here.
+    PredictState* predict = nullptr;
+    std::mutex predict_mu;
     uint8_t* d_maskbits = nullptr;
     uint8_t* d_ginfo = nullptr;  // per-group mask bits + window-count bounds (kernels_stream.hpp)
     uint8_t* d_mmap = nullptr;   // per-pixel window counts
@@ -639,6 +651,8 @@ void ahead_stop(ffs_ctx* c, bool destroy);   // the thread leaves and is joined 
 void spotbg_free(ffs_stream* s);   // the stream's own HIP stream, events and buffers of ffs_stream_spot_backgrounds, if it was ever called
 // ffs_shoebox.hip
 void shoebox_free_ctx(ffs_ctx* c);   // the open job, if any (context destroy; every stream is closed)
+// ffs_predict.hip
+void predict_free_ctx(ffs_ctx* c);   // what ffs_ctx_predict kept (context destroy)
 // ffs_stack3d.hip
 void stack3d_free(ffs_stack3d* st);
 // ffs_multi.hip

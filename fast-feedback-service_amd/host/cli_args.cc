@@ -29,6 +29,8 @@ void usage() {
       "                  [--n-iqr X] [--radial-blur narrow|wide]\n"
       "                  [--integrate FILE --sigma-b DEG --sigma-m DEG --integrate-out PREFIX [--integrate-algorithm ellipsoid|dials]\n"
       "                   [--integrate-background tukey|glm] [--integrate-n-sigma 3]]\n"
+      "                  [--predict CRYSTAL --predict-dmin D --sigma-b DEG --sigma-m DEG --integrate-out PREFIX [--predict-centring P|I|F|A|B|C|R]\n"
+      "                   [--integrate-n-sigma 3] [--integrate-algorithm ...] [--integrate-background ...]]\n"
       "                  [--devices D0,D1,... | --gpus N] [--no-numa-pinning] [--single-buffer] [--all-threads] [--read-only] [--clean-exit]\n"
       "--max-valid: a centre pixel above this value is never strong (the reference's kernels test it against the\n"
       "              data set's trusted maximum).  trusted (default) = the frame source's trusted-range maximum when it is\n"
@@ -104,6 +106,12 @@ void usage() {
       "              moments, background pixels, flags, background status and mean, intensity, variance), and one summary line.  With several\n"
       "              GPUs their integer accumulators are added.  Masked pixels and pixels above --max-valid do not count; a reflection whose\n"
       "              foreground meets one is flagged.  Not with --validate\n"
+      "--predict:   instead of --integrate FILE, the reflections and their shoeboxes are predicted on the GPU before the first batch, for the\n"
+      "              source's geometry and image count.  CRYSTAL holds nine raw little-endian float64: the A matrix row-major in 1/Angstrom\n"
+      "              (r = A h in the laboratory frame at rotation angle 0).  --predict-dmin D is the resolution limit; --predict-centring leaves\n"
+      "              out the lattice's absent indices (default P); the boxes are --integrate-n-sigma x --sigma-b and x --sigma-m in Kabsch\n"
+      "              space.  One line says candidates, predictions and flagged records; PREFIX.predictions holds the records of 96 bytes\n"
+      "              (ffs_prediction of ffs_hip.h); the boxes not flagged as refused are then integrated exactly as --integrate does\n"
       "--validate:  every image is also decided by an independent path (every valid pixel's window gathered from memory,\n"
       "              no streaming kernel) and the two strong-pixel masks are compared: Match / Mismatch per image\n"
       "--devices / --gpus: one context and worker pool per GPU, all pulling frames from the one queue\n"
@@ -152,6 +160,7 @@ Args parse_args(int argc, char** argv) {
     }
     Args r;
     bool model_given = false;   // --spot-background-model, in either spelling: refused without --spot-background
+    bool predict_option_given = false;     // --predict-dmin and --predict-centring: refused without --predict
     bool integrate_option_given = false;   // --sigma-b, --sigma-m and the --integrate-* options: refused without --integrate
     if (const char* e = std::getenv("SPOTFINDER_TIMEOUT")) {  // spotfinder.cc:293-301
         try { r.timeout = std::stof(e); } catch (...) { std::printf("Ignoring invalid SPOTFINDER_TIMEOUT value: %s\n", e); }
@@ -279,6 +288,24 @@ Args parse_args(int argc, char** argv) {
             r.integrate = need(i, s);
             if (r.integrate.empty()) arg_error("--integrate takes the file of predicted reflections");
         }
+        else if (s == "--predict") {
+            r.predict = need(i, s);
+            if (r.predict.empty()) arg_error("--predict takes the crystal file (nine float64: the A matrix)");
+        }
+        else if (s == "--predict-dmin") {
+            const std::string& v = need(i, s);
+            char* end = nullptr;
+            r.predict_dmin = std::strtod(v.c_str(), &end);
+            if (v.empty() || *end || !(r.predict_dmin > 0.0 && r.predict_dmin <= 1e6)) arg_error("--predict-dmin takes a finite number > 0 (Angstrom): " + v);
+            predict_option_given = true;
+        }
+        else if (s == "--predict-centring") {
+            const std::string& v = need(i, s);
+            const size_t at = v.size() == 1 ? std::string("PIFABCR").find(v[0]) : std::string::npos;
+            if (at == std::string::npos) arg_error("--predict-centring takes one of P I F A B C R: " + v);
+            r.predict_centring = (int)at;
+            predict_option_given = true;
+        }
         else if (s == "--integrate-out") {
             r.integrate_out = need(i, s);
             if (r.integrate_out.empty()) arg_error("--integrate-out takes the prefix of the file it writes");
@@ -345,7 +372,16 @@ Args parse_args(int argc, char** argv) {
         arg_error("--pedestal-min-frames and --pedestal-max-rms belong to --jungfrau-pedestal");
     }
     if (model_given && !r.spot_background) arg_error("--spot-background-model belongs to --spot-background");
-    if (!r.integrate.empty()) {
+    if (!r.predict.empty()) {
+        if (!r.integrate.empty()) arg_error("--predict and --integrate exclude each other: the boxes are predicted or read from a file");
+        if (!(r.predict_dmin > 0.0)) arg_error("--predict needs --predict-dmin D (Angstrom): the resolution limit of the prediction");
+        if (!(r.sigma_b > 0.0) || !(r.sigma_m > 0.0)) arg_error("--predict needs both --sigma-b and --sigma-m (degrees): the boxes are n_sigma x sigma in Kabsch space");
+        if (r.integrate_out.empty()) arg_error("--predict needs --integrate-out PREFIX: the records go to PREFIX.predictions and PREFIX.shoebox_sums");
+        if (r.validate) arg_error("--predict is not available with --validate");
+        if (!r.jungfrau_pedestal.empty()) arg_error("--jungfrau-pedestal finds no spots and integrates none: not with --predict");
+    } else if (predict_option_given) {
+        arg_error("--predict-dmin and --predict-centring belong to --predict");
+    } else if (!r.integrate.empty()) {
         if (!(r.sigma_b > 0.0) || !(r.sigma_m > 0.0)) arg_error("--integrate needs both --sigma-b and --sigma-m (degrees): the foreground is an ellipsoid of n_sigma x sigma");
         if (r.integrate_out.empty()) arg_error("--integrate needs --integrate-out PREFIX: the records go to PREFIX.shoebox_sums");
         if (r.validate) arg_error("--integrate is not available with --validate");

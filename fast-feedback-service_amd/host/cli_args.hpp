@@ -41,6 +41,13 @@ struct Args {
     double sigma_b = 0.0, sigma_m = 0.0, integrate_n_sigma = 3.0;
     int integrate_algorithm = 0;         // --integrate-algorithm ellipsoid (FFS_SHOEBOX_ELLIPSOID) | dials (FFS_SHOEBOX_DIALS)
     int integrate_background = 0;        // --integrate-background tukey (0) | glm (1)
+    // --predict CRYSTAL: the reflections and their boxes are predicted on the GPU (ffs_ctx_predict) from CRYSTAL (nine raw float64: the A matrix,
+    // row-major, 1/Angstrom) instead of read from --integrate's file; needs --predict-dmin, --sigma-b, --sigma-m and --integrate-out PREFIX
+    // (PREFIX.predictions and PREFIX.shoebox_sums); not with --integrate; empty = not given
+    std::string predict;
+    double predict_dmin = 0.0;           // --predict-dmin D (Angstrom, > 0)
+    int predict_centring = 0;            // --predict-centring P|I|F|A|B|C|R: FFS_CENTRING_*
+    bool integrating() const { return !integrate.empty() || !predict.empty(); }
     std::string pixel_stats;             // --pixel-stats PREFIX: per-pixel count, sum, sum of squares and maximum over the run, into PREFIX.*; empty = not given
     uint32_t min_count = 2;
     int kernel_half_x = 3, kernel_half_y = 3;   // --kernel-size

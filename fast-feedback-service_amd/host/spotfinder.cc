@@ -36,6 +36,8 @@
 #include "png_writer.hpp"
 #include "reader.hpp"
 #include "shoebox_geometry.hpp"
+#include "predict_geometry.hpp"
+#include "../csrc/predict_plan.hpp"
 #include "../csrc/shoebox_model.hpp"
 #include "../csrc/sweep_plan.hpp"
 
@@ -442,6 +444,61 @@ static int open_integration(const Args& args, const Experiment& ex, bool rotatio
     return 0;
 }
 
+// --predict CRYSTAL, ahead of the run: the reflections of the source's geometry and image count predicted on the first context
+// (ffs_ctx_predict), the records into PREFIX.predictions, one summary line, and a shoebox job opened on every context with the boxes not flagged
+// FFS_PREDICT_BOX_REFUSED; from there on the run is --integrate's.  The candidate count of the line is csrc/predict_plan.hpp's.  -> 0, or the
+// exit code
+static int open_prediction(const Args& args, const Experiment& ex, bool rotation, uint32_t num_images, int W, int H, const std::vector<ffs_ctx*>& ctxs, size_t& n_boxes) {
+    if (!rotation) {
+        std::printf("Error: --predict needs a rotation source (an oscillation width above 0)\n");
+        return 1;
+    }
+    const DetectorGeometry& d = ex.detector;
+    const KabschGeometry kg{d.distance * 1000.0, d.beam_center_x, d.beam_center_y, d.pixel_size_x * 1000.0, d.pixel_size_y * 1000.0, ex.wavelength,
+                            ex.oscillation_start, ex.oscillation_width};
+    ffs_crystal crystal{};
+    try {
+        crystal = read_crystal_file(args.predict, args.predict_centring);
+    } catch (const std::exception& e) {
+        std::printf("Error: --predict: %s\n", e.what());
+        return 1;
+    }
+    const ffs_scan_geometry g = shoebox_flat_geometry(kg);
+    const double delta_b = shoebox_delta(args.integrate_n_sigma, args.sigma_b), delta_m = shoebox_delta(args.integrate_n_sigma, args.sigma_m);
+    ffs_ctx* cx0 = ctxs[0];
+    uint32_t n = 0;
+    float ms = 0.0f;
+    int rc = ffs_ctx_predict(cx0, &g, &crystal, num_images, args.predict_dmin, delta_b, delta_m, nullptr, 0, &n, nullptr);
+    if (rc != FFS_OK && rc != FFS_ERR_OVERFLOW) FFS_CHECK(cx0, rc);
+    std::vector<ffs_prediction> records(n);
+    if (n) FFS_CHECK(cx0, ffs_ctx_predict(cx0, &g, &crystal, num_images, args.predict_dmin, delta_b, delta_m, records.data(), n, &n, &ms));
+    ffsamd::ShoeboxGeometry mg;
+    ffsamd::PredictCrystal mx;
+    ffsamd::PredictSetup setup{};
+    std::memcpy(&mg, &g, sizeof mg);
+    std::memcpy(&mx, &crystal, sizeof mx);
+    (void)ffsamd::predict_refusal(mg, mx, num_images, args.predict_dmin, delta_b, delta_m, W, H, setup);   // (the library has taken the call)
+    const std::string name = args.integrate_out + ".predictions";
+    std::ofstream f(name, std::ios::binary | std::ios::trunc);
+    if (!f || !f.write(reinterpret_cast<const char*>(records.data()), (std::streamsize)(records.size() * sizeof(ffs_prediction))) || !f.flush()) {
+        std::printf("Error: --integrate-out: cannot write %s\n", name.c_str());
+        return 1;
+    }
+    std::printf("Prediction: %s -> %s (dmin %.17g, centring %c, %.3f ms on the GPU)\n", predict_summary_line(setup.n_candidates, records).c_str(), name.c_str(),
+                args.predict_dmin, "PIFABCR"[args.predict_centring], (double)ms);
+    const std::vector<ffs_shoebox> table = boxes_of_predictions(records);
+    for (ffs_ctx* cx : ctxs)
+        FFS_CHECK(cx, ffs_ctx_shoebox_begin(cx, &g, table.data(), (uint32_t)table.size(), args.integrate_algorithm, delta_b, delta_m));
+    n_boxes = table.size();
+    std::printf("Integration: %zu reflections from the prediction, %s foreground of %.17g x sigma_b %.17g and sigma_m %.17g degrees, %s background\n", n_boxes,
+                args.integrate_algorithm == FFS_SHOEBOX_DIALS ? "dials" : "ellipsoid", args.integrate_n_sigma, args.sigma_b, args.sigma_m,
+                args.integrate_background ? "glm" : "tukey");
+    std::printf("Integration geometry: distance=%.17g beam_x=%.17g beam_y=%.17g pixel_x=%.17g pixel_y=%.17g wavelength=%.17g osc_start=%.17g osc_width=%.17g\n",
+                kg.distance_mm, kg.beam_center_x_px, kg.beam_center_y_px, kg.pixel_size_x_mm, kg.pixel_size_y_mm, kg.wavelength, kg.oscillation_start, kg.oscillation_width);
+    std::printf("Prediction scan: width=%d height=%d n_images=%u\n", W, H, num_images);
+    return 0;
+}
+
 // --integrate, after the last wait: the records into PREFIX.shoebox_sums and the summary line.  One context hands out its records; with
 // several, their integer accumulators and histograms are added on the host (as --pixel-stats adds its planes) and the records are made from
 // the sums by the function the library calls (csrc/shoebox_model.hpp).
@@ -740,7 +797,7 @@ class BatchReport {
         }
         // --integrate: the batch's frames into the context's job, once, while they are still where the batch left them (image numbers are
         // consecutive inside a batch: batch_pipeline.hpp)
-        if (!args_.integrate.empty() && nres > 0 && ffs_stream_shoebox_fold(batch.stream, res[0].frame_id, nullptr) != FFS_OK) {
+        if (args_.integrating() && nres > 0 && ffs_stream_shoebox_fold(batch.stream, res[0].frame_id, nullptr) != FFS_OK) {
             std::printf("Error: %s\n", ffs_last_error(ctxs_[batch.gpu]));
             return false;
         }
@@ -1139,6 +1196,8 @@ int main(int argc, char** argv) {
     size_t n_shoeboxes = 0;
     if (!args.integrate.empty())
         if (const int rc = open_integration(args, ex, rotation, ctxs, n_shoeboxes)) return rc;
+    if (!args.predict.empty())
+        if (const int rc = open_prediction(args, ex, rotation, num_images, (int)shape.width, (int)shape.height, ctxs, n_shoeboxes)) return rc;
     if (args.validate && !create_validation_contexts(devices, ctxs, shape, batch, prm, args.max_valid_scope, args.gain, gain_map, vctxs)) return 1;
     if (args.validate && jungfrau && gpu_decode)   // (the validation streams are handed the same raw chunks)
         for (ffs_ctx* v : vctxs) FFS_CHECK(v, set_jungfrau_calibration(v, jungfrau_planes, shape.pixels()));
@@ -1189,7 +1248,7 @@ int main(int argc, char** argv) {
     else if (args.save_h5) write_2d_h5(report.reflection_centers_2d);
     print_summary(args, shape, pipeline, report, gather.get(), n_dev, all_start, stamp.process_start());
     if (!args.pixel_stats.empty() && !write_pixel_stats(args.pixel_stats, ctxs, shape.width, shape.height)) return 1;
-    if (!args.integrate.empty() && !write_integration(args, ctxs, n_shoeboxes)) return 1;
+    if (args.integrating() && !write_integration(args, ctxs, n_shoeboxes)) return 1;
     pipe.reset();
     exchange.join();
     stamp("timed loop and reports done");

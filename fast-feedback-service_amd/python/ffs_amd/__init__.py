@@ -10,4 +10,6 @@ from .api import (Context, FrameResult, Params, Stack3D, Stream, device_count,  
                   ALGO_DISPERSION, ALGO_DISPERSION_EXTENDED, CODEC_BSLZ4, CODEC_BYTE_OFFSET, CODEC_JUNGFRAU_RAW, MAX_VALID_CENTRE, MAX_VALID_WINDOW, multi_init,
                   SPOT_BG_DT, spot_intensities, SPOT_BG_GLM_DT, spot_intensities_glm, jungfrau_pedestal_planes, ALGO_RADIAL_PROFILE, RADIAL_SHELL_DT,
                   RADIAL_BLUR_NONE, RADIAL_BLUR_NARROW, RADIAL_BLUR_WIDE,
-                  SHOEBOX_DT, SHOEBOX_SUM_DT, SHOEBOX_ELLIPSOID, SHOEBOX_DIALS, SHOEBOX_FG_INVALID)
+                  SHOEBOX_DT, SHOEBOX_SUM_DT, SHOEBOX_ELLIPSOID, SHOEBOX_DIALS, SHOEBOX_FG_INVALID,
+                  PREDICTION_DT, CENTRINGS, PREDICT_ENTERING, PREDICT_CORNER_LOST, PREDICT_ZETA_SMALL, PREDICT_BOX_REFUSED,
+                  predict_scan_settings, shoeboxes_of)

@@ -123,6 +123,18 @@ SHOEBOX_FG_INVALID = 1                    # FFS_SHOEBOX_FG_INVALID, in a record'
 SHOEBOX_BACKGROUNDS = {"tukey": 0, "glm": 1}
 
 
+# Scan prediction for a rotation sweep (ffs_predict_scan_settings, ffs_ctx_predict)
+class _Crystal(C.Structure):   # ffs_crystal
+    _fields_ = [("a_matrix", C.c_double * 9), ("centring", C.c_int32), ("reserved", C.c_int32)]
+
+
+# ffs_prediction: the ffs_shoebox first (its fields by their own names), then the predicted centre, the index and the flags
+PREDICTION_DT = np.dtype(SHOEBOX_DT.descr + [("x_px", "<f8"), ("y_px", "<f8"), ("z", "<f8"), ("h", "<i4"), ("k", "<i4"), ("l", "<i4"), ("flags", "<u4")])
+assert C.sizeof(_Crystal) == 80 and PREDICTION_DT.itemsize == 96
+CENTRINGS = {"P": 0, "I": 1, "F": 2, "A": 3, "B": 4, "C": 5, "R": 6}   # FFS_CENTRING_*
+PREDICT_ENTERING, PREDICT_CORNER_LOST, PREDICT_ZETA_SMALL, PREDICT_BOX_REFUSED = 1, 2, 4, 8   # FFS_PREDICT_*, in a record's flags
+
+
 # ffs_radial_shell: what the radial-profile threshold decided for one (frame, shell) -- Stream.radial_thresholds
 RADIAL_SHELL_DT = np.dtype([("n_pixels", "<u4"), ("n_overflow", "<u4"), ("q1", "<i4"), ("median", "<i4"), ("q3", "<i4"), ("cutoff", "<u4"),
                             ("status", "<u4"), ("reserved", "<u4")])
@@ -175,6 +187,7 @@ EXPORTS = [
     "ffs_ctx_jungfrau_pedestal_begin", "ffs_ctx_jungfrau_pedestal_end", "ffs_stream_jungfrau_pedestal_fold", "ffs_ctx_get_jungfrau_pedestal",
     "ffs_jungfrau_pedestal_planes",
     "ffs_ctx_shoebox_begin", "ffs_ctx_shoebox_end", "ffs_stream_shoebox_fold", "ffs_ctx_get_shoebox_sums", "ffs_ctx_get_shoebox_histogram",
+    "ffs_predict_scan_settings", "ffs_ctx_predict",
 ]
 
 _lib = None
@@ -224,6 +237,9 @@ def load_library():
         L.ffs_stream_shoebox_fold.argtypes = [C.c_void_p, C.c_int64, C.POINTER(C.c_float)]
         L.ffs_ctx_get_shoebox_sums.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]
         L.ffs_ctx_get_shoebox_histogram.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p]
+        L.ffs_predict_scan_settings.argtypes = [C.POINTER(_ScanGeometry), C.POINTER(_Crystal), C.c_uint32, C.c_void_p]
+        L.ffs_ctx_predict.argtypes = [C.c_void_p, C.POINTER(_ScanGeometry), C.POINTER(_Crystal), C.c_uint32, C.c_double, C.c_double, C.c_double, C.c_void_p,
+                                      C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_float)]
         L.ffs_bench_pipeline.argtypes = [C.POINTER(C.c_void_p), C.c_uint32, C.c_void_p, C.c_size_t, C.c_size_t, C.c_uint32,
                                          C.c_uint32, C.c_int64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
         L.ffs_device_numa_node.argtypes = [C.c_int]
@@ -501,15 +517,7 @@ class Context:
         phi in radians, the half-open box); algorithm "ellipsoid" or "dials" (or FFS_SHOEBOX_*); delta_b, delta_m: n_sigma * sigma in
         radians.  FfsError (state unchanged): a batch in flight, a job already open, a delta that is not finite and positive, an unknown
         algorithm, a table entry the library names."""
-        get = geometry.get if hasattr(geometry, "get") else (lambda k: getattr(geometry, k))
-        g = _ScanGeometry()
-        for name, n in (("d_matrix", 9), ("pixel_size_mm", 2), ("s0", 3), ("rot_axis", 3)):
-            v = np.asarray(get(name), np.float64).reshape(-1)
-            if v.size != n:
-                raise ValueError(f"geometry {name} must have {n} entries, not {v.size}")
-            setattr(g, name, (C.c_double * n)(*v))
-        for name in ("wavelength", "osc_start_deg", "osc_width_deg"):
-            setattr(g, name, float(get(name)))
+        g = _scan_geometry(geometry)
         t = np.ascontiguousarray(shoeboxes, dtype=SHOEBOX_DT)
         algo = SHOEBOX_ALGORITHMS.get(algorithm, algorithm) if isinstance(algorithm, str) else algorithm
         if isinstance(algo, str):
@@ -541,6 +549,31 @@ class Context:
         bins = np.zeros(256, np.uint32)
         self._check(self._lib.ffs_ctx_get_shoebox_histogram(self._h, int(index), bins.ctypes.data_as(C.c_void_p)))
         return bins
+
+    def predict(self, geometry, a_matrix, n_images: int, dmin: float, delta_b: float, delta_m: float, centring="P", *, cap=None, want_ms: bool = False):
+        """ffs_ctx_predict: the reflections of images 0 .. n_images - 1 of a rotation scan on this context's image and their shoeboxes, as a
+        structured array of PREDICTION_DT in the order of candidate number, then image.  geometry: as Context.shoebox_begin takes it;
+        a_matrix: 9 entries row-major, 1/Angstrom, r = A h at rotation angle 0; delta_b, delta_m: n_sigma * sigma in radians; centring: one
+        of "PIFABCR" (or FFS_CENTRING_*).  cap (optional): at most that many records are fetched; FfsError -4 (FFS_ERR_OVERFLOW) when there
+        are more -- its `records` and `n` attributes carry what was written and the full count.  want_ms: also return the kernels' time.
+        May be called while batches of the context are in flight.  FfsError (nothing changed): what include/ffs_hip.h lists."""
+        g, x = _scan_geometry(geometry), _crystal(a_matrix, centring)
+        n, ms = C.c_uint32(), C.c_float()
+        args = (self._h, C.byref(g), C.byref(x), int(n_images), float(dmin), float(delta_b), float(delta_m))
+        if cap is None:
+            rc = self._lib.ffs_ctx_predict(*args, None, 0, C.byref(n), None)
+            if rc != -4:   # FFS_ERR_OVERFLOW: the count is in n
+                self._check(rc)
+            cap = n.value
+        out = np.zeros(int(cap), PREDICTION_DT)
+        rc = self._lib.ffs_ctx_predict(*args, out.ctypes.data_as(C.c_void_p) if cap else None, int(cap), C.byref(n), C.byref(ms))
+        if rc == -4:
+            err = FfsError(rc, self._lib.ffs_last_error(self._h).decode())
+            err.records, err.n = out, n.value
+            raise err
+        self._check(rc)
+        out = out[:n.value]
+        return (out, ms.value) if want_ms else out
 
     def set_tuning(self, **kw):
         """ffs_ctx_set_tuning: A/B partners, fall-backs and capacities (same results either way); see include/ffs_hip.h."""
@@ -852,6 +885,58 @@ class Stream:
             self.close()
         except Exception:
             pass
+
+
+def _scan_geometry(geometry) -> _ScanGeometry:
+    """ffs_scan_geometry from a mapping (or object) with d_matrix (9, row-major), pixel_size_mm (2), wavelength, s0 (3), rot_axis (3),
+    osc_start_deg, osc_width_deg."""
+    get = geometry.get if hasattr(geometry, "get") else (lambda k: getattr(geometry, k))
+    g = _ScanGeometry()
+    for name, n in (("d_matrix", 9), ("pixel_size_mm", 2), ("s0", 3), ("rot_axis", 3)):
+        v = np.asarray(get(name), np.float64).reshape(-1)
+        if v.size != n:
+            raise ValueError(f"geometry {name} must have {n} entries, not {v.size}")
+        setattr(g, name, (C.c_double * n)(*v))
+    for name in ("wavelength", "osc_start_deg", "osc_width_deg"):
+        setattr(g, name, float(get(name)))
+    return g
+
+
+def _crystal(a_matrix, centring) -> _Crystal:
+    a = np.asarray(a_matrix, np.float64).reshape(-1)
+    if a.size != 9:
+        raise ValueError(f"a_matrix must have 9 entries, not {a.size}")
+    code = CENTRINGS.get(centring, centring) if isinstance(centring, str) else centring
+    if isinstance(code, str):
+        raise ValueError(f"centring must be one of {sorted(CENTRINGS)}, not {centring!r}")
+    x = _Crystal()
+    x.a_matrix = (C.c_double * 9)(*a)
+    x.centring = int(code)
+    return x
+
+
+def predict_scan_settings(geometry, a_matrix, n_images: int, centring="P") -> np.ndarray:
+    """ffs_predict_scan_settings: the scan-point settings A_k = R(phi_k) A, k = 0 .. n_images, as Context.predict computes them, (n_images + 1,
+    9) float64.  On the host: no context, no GPU.  This is the one place libm's cos and sin enter the prediction."""
+    lib = load_library()
+    g, x = _scan_geometry(geometry), _crystal(a_matrix, centring)
+    out = np.zeros((max(int(n_images), 0) + 1, 9), np.float64)
+    rc = lib.ffs_predict_scan_settings(C.byref(g), C.byref(x), int(n_images), out.ctypes.data_as(C.c_void_p))
+    if rc != 0:
+        raise FfsError(rc, lib.ffs_last_error(None).decode())
+    return out
+
+
+def shoeboxes_of(predictions: np.ndarray, skip_refused: bool = True) -> np.ndarray:
+    """The table Context.shoebox_begin takes (SHOEBOX_DT) from Context.predict's records, in their order; skip_refused leaves out the records
+    flagged PREDICT_BOX_REFUSED, which ffs_ctx_shoebox_begin would refuse."""
+    p = np.asarray(predictions)
+    if skip_refused:
+        p = p[(p["flags"] & PREDICT_BOX_REFUSED) == 0]
+    out = np.zeros(len(p), SHOEBOX_DT)
+    for name in SHOEBOX_DT.names:
+        out[name] = p[name]
+    return out
 
 
 def jungfrau_pedestal_planes(stats, min_frames: int = 1, max_rms: float = 0.0):

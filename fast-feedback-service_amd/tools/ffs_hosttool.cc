@@ -22,11 +22,16 @@
 //   ffs_hosttool shoebox key=value ...   summation integration on the CPU by csrc/shoebox_model.hpp, the text the kernel of
 //                                         ffs_stream_shoebox_fold compiles: frames=<file of images, one behind the other> width= height=
 //                                         bytes=2|4 [mask=<W*H bytes, non-zero = valid>] [max_valid=N] distance= beam_x= beam_y= pixel_x=
-//                                         pixel_y= wavelength= osc_start= osc_width= boxes=<the file spotfinder --integrate reads> sigma_b=
+//                                         pixel_y= wavelength= osc_start= osc_width= boxes=<the file spotfinder --integrate reads> (or
+//                                         predictions=<a PREFIX.predictions file>: the boxes not flagged FFS_PREDICT_BOX_REFUSED, s1 and phi as recorded) sigma_b=
 //                                         sigma_m= [n_sigma=3] [algorithm=ellipsoid|dials] [background=tukey|glm] out=<file>: writes the
 //                                         ffs_shoebox_sum records spotfinder writes to PREFIX.shoebox_sums and prints its summary line
 //   ffs_hosttool shoeboxgeom key=value ...  the geometry keys and boxes= of the above: the ffs_scan_geometry (20 doubles) and every box's
 //                                         s1 and phi as host/shoebox_geometry.hpp computes them, 16 hex digits a double
+//   ffs_hosttool predict key=value ...   scan prediction on the CPU by csrc/predict_model.hpp, the text the kernels of ffs_ctx_predict compile:
+//                                         the geometry keys of the above, width= height= crystal=<nine float64> n_images= dmin= sigma_b= sigma_m=
+//                                         [n_sigma=3] [centring=P|I|F|A|B|C|R] out=<file>: writes the ffs_prediction records spotfinder --predict
+//                                         writes to PREFIX.predictions and prints its summary line
 #include <cinttypes>
 #include <cstdio>
 #include <cstdlib>
@@ -39,10 +44,13 @@
 #include <map>
 
 #include "../csrc/launch_geometry.hpp"
+#include "../csrc/predict_model.hpp"
+#include "../csrc/predict_plan.hpp"
 #include "../csrc/shoebox_model.hpp"
 #include "../csrc/shoebox_plan.hpp"
 #include "../csrc/spot_background_glm_model.hpp"
 #include "shoebox_geometry.hpp"
+#include "predict_geometry.hpp"
 #include "codecs.hpp"
 #include "reader.hpp"
 
@@ -404,8 +412,11 @@ static int shoebox(const KeyValues& kv) {
     const double n_sigma = kv.has("n_sigma") ? kv.num("n_sigma") : 3.0;
     const double delta_b = shoebox_delta(n_sigma, kv.num("sigma_b")), delta_m = shoebox_delta(n_sigma, kv.num("sigma_m"));
     std::vector<ffsamd::ShoeboxEntry> table;
-    for (const ShoeboxRecord& r : read_shoebox_file(kv.str("boxes"))) {
-        const ffs_shoebox b = shoebox_from_record(kg, r);
+    std::vector<ffs_shoebox> boxes;
+    if (kv.has("predictions")) boxes = boxes_of_predictions(read_prediction_file(kv.str("predictions")));
+    else
+        for (const ShoeboxRecord& r : read_shoebox_file(kv.str("boxes"))) boxes.push_back(shoebox_from_record(kg, r));
+    for (const ffs_shoebox& b : boxes) {
         ffsamd::ShoeboxEntry e;
         static_assert(sizeof e == sizeof b, "the model's table entry is ffs_shoebox");
         std::memcpy(&e, &b, sizeof e);
@@ -432,6 +443,38 @@ static int shoebox(const KeyValues& kv) {
     o.write(reinterpret_cast<const char*>(sums.data()), (std::streamsize)(sums.size() * sizeof(ffs_shoebox_sum)));
     std::printf("%s\n", shoebox_summary_line(sums.data(), sums.size()).c_str());
     return o ? 0 : fail("shoebox: cannot write the file");
+}
+
+static int predict(const KeyValues& kv) {
+    const KabschGeometry kg = kv.geometry();
+    const ffs_scan_geometry fg = shoebox_flat_geometry(kg);
+    ffsamd::ShoeboxGeometry g;
+    std::memcpy(&g, &fg, sizeof g);
+    const int W = (int)kv.num("width"), H = (int)kv.num("height");
+    if (W <= 0 || H <= 0) return fail("predict: width and height must be positive");
+    const ffs_crystal fx = read_crystal_file(kv.str("crystal"), centring_from_letter(kv.has("centring") ? kv.str("centring") : "P"));
+    ffsamd::PredictCrystal x;
+    static_assert(sizeof x == sizeof fx, "the model's crystal is ffs_crystal");
+    std::memcpy(&x, &fx, sizeof x);
+    const long long n_images = std::stoll(kv.str("n_images"));
+    if (n_images < 0 || n_images > 0xFFFFFFFFll) return fail("predict: n_images does not fit 32 bits");
+    const double n_sigma = kv.has("n_sigma") ? kv.num("n_sigma") : 3.0;
+    const double delta_b = shoebox_delta(n_sigma, kv.num("sigma_b")), delta_m = shoebox_delta(n_sigma, kv.num("sigma_m"));
+    // (what ffs_ctx_predict refuses is refused here, by the same text)
+    ffsamd::PredictSetup u;
+    const std::string why = ffsamd::predict_refusal(g, x, (uint32_t)n_images, kv.num("dmin"), delta_b, delta_m, W, H, u);
+    if (!why.empty()) return fail(("predict: " + why).c_str());
+    std::vector<double> settings(((size_t)n_images + 1) * 9);
+    ffsamd::predict_scan_settings(g, x.a_matrix, (uint32_t)n_images, settings.data());
+    std::vector<ffsamd::PredictRecord> records;
+    ffsamd::predict_all(u, settings.data(), records);
+    std::vector<ffs_prediction> out(records.size());
+    static_assert(sizeof(ffsamd::PredictRecord) == sizeof(ffs_prediction), "the model's record is ffs_prediction");
+    if (!records.empty()) std::memcpy(out.data(), records.data(), records.size() * sizeof(ffs_prediction));
+    std::ofstream o(kv.str("out"), std::ios::binary);
+    o.write(reinterpret_cast<const char*>(out.data()), (std::streamsize)(out.size() * sizeof(ffs_prediction)));
+    std::printf("%s\n", predict_summary_line(u.n_candidates, out).c_str());
+    return o ? 0 : fail("predict: cannot write the file");
 }
 
 // chunkfnv <chunk file> <nelem> <elem bytes>: decode one bitshuffle-LZ4 chunk with the host codec and
@@ -468,6 +511,7 @@ int main(int argc, char** argv) {
         if (cmd == "spotbgglm" && argc <= 3) return spotbgglm(argc == 3 ? argv[2] : nullptr);
         if (cmd == "shoebox") return shoebox(KeyValues(argc, argv));
         if (cmd == "shoeboxgeom") return shoeboxgeom(KeyValues(argc, argv));
+        if (cmd == "predict") return predict(KeyValues(argc, argv));
         if (cmd == "h5support") { std::printf("%d\n", h5_supported() ? 1 : 0); return 0; }
     } catch (const std::exception& e) {
         std::printf("Error: %s\n", e.what());
@@ -478,6 +522,6 @@ int main(int argc, char** argv) {
                 "       h5info <master.h5> | synthinfo <synth:spec> | h5support | h5stats <file.h5> <group> |\n"
                 "       chunkfnv <chunk> <nelem> <elem bytes> | jfcal <synth:spec> <file> | jfconvert <raw> <cal> <W> <H> <out> |\n"
                 "       synthframes <synth:spec> <file> | jfrepedestal <old cal> <prefix> <new cal> [min_frames [max_rms]] |\n"
-                "       spotbgglm [histograms] | shoebox key=value ... | shoeboxgeom key=value ...\n");
+                "       spotbgglm [histograms] | shoebox key=value ... | shoeboxgeom key=value ... | predict key=value ...\n");
     return 2;
 }

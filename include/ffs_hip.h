@@ -841,6 +841,65 @@ int ffs_ctx_get_shoebox_sums(ffs_ctx *ctx, int background_model, ffs_shoebox_sum
  * NULL bins. */
 int ffs_ctx_get_shoebox_histogram(ffs_ctx *ctx, uint32_t index, uint32_t bins[256]);
 
+/* Scan prediction for a rotation sweep: the two stages of the reference between indexing and integration -- the
+ * per-image ray predictor (predictor/predict.cc:31-128 over predict_ray_monochromatic_sv, predictor/ray_predictors.cc:115-201) and the
+ * Kabsch bounding boxes (compute_kabsch_bounding_boxes, integrator/extent.cc:14-198) -- for one flat panel, one s0 and one crystal setting
+ * over the scan.  A crystal setting and the scan's geometry give the table ffs_ctx_shoebox_begin takes.  THE RULE is stated once, in
+ * csrc/predict_model.hpp, which the kernels, this library's host side and `ffs_hosttool predict` compile; no parity with the reference's
+ * binaries is claimed.  Every operation is an IEEE float64 + - * / sqrt floor ceil, a comparison or an integer-to-double conversion in the
+ * order written there, compiled without contraction; the device evaluates no trigonometric function:
+ *   scan points k = 0 .. n_images: A_k = R(phi_k) A, phi_k = (osc_start_deg + k * osc_width_deg) * (pi / 180), R by Rodrigues' formula about
+ *     the normalized rot_axis, cos and sin from the host's libm once per call (ffs_predict_scan_settings hands the matrices out);
+ *   candidates: h_max = floor(|real-space axis| / dmin) + 1 per axis from the rows of inverse(A) (cofactors); every (h, k, l) of the box
+ *     [-h_max, h_max]^3 but (0,0,0) and the indices absent under the centring, numbered h slowest, l fastest;
+ *   image n: r1 = A_n h, r2 = A_{n+1} h; a ray when the two ends lie on different sides of the Ewald sphere (squared norms compared) and
+ *     r1.r1 <= 1 / dmin^2; alpha from the two quadratics, s1 = r1 + alpha (r2 - r1) + s0, phi = (phi_n + alpha osc_width) in radians,
+ *     entering = r1 outside;
+ *   impact: v = inverse(D) s1, v2 > 0, x_px = v0 / v2 / pixel_size_mm[0], y_px likewise, kept when 0 <= x_px < W and 0 <= y_px < H;
+ *     z = n + alpha in images from the scan's first;
+ *   extent: the four corners (+-delta_b, +-delta_b) in Kabsch space through inverse(D), floor and ceil of their extremes; the images from
+ *     phi -+ delta_m / zeta, clamped to the scan; the whole scan when |zeta| <= 1e-10.
+ * Records come in the order of candidate number, then image: the same bytes whatever the scheduling. */
+#define FFS_CENTRING_P 0
+#define FFS_CENTRING_I 1
+#define FFS_CENTRING_F 2
+#define FFS_CENTRING_A 3
+#define FFS_CENTRING_B 4
+#define FFS_CENTRING_C 5
+#define FFS_CENTRING_R 6           /* obverse setting: (-h + k + l) mod 3 == 0 is present */
+#define FFS_PREDICT_ENTERING 1u    /* the reflection starts the image outside the Ewald sphere */
+#define FFS_PREDICT_CORNER_LOST 2u /* a corner of the extent had a negative b (or no intersection) and was left out (extent.cc:98-112) */
+#define FFS_PREDICT_ZETA_SMALL 4u  /* |zeta| <= 1e-10: the box spans the whole scan (extent.cc:187-192) */
+#define FFS_PREDICT_BOX_REFUSED 8u /* ffs_ctx_shoebox_begin would refuse the box: no corner survived, an empty side, or one above 1024 pixels */
+typedef struct {
+    double a_matrix[9];        /* row-major, 1/Angstrom: r = A h in the laboratory frame at rotation angle 0, fixed and setting rotations applied */
+    int32_t centring, reserved;
+} ffs_crystal;                    /* 80 bytes */
+typedef struct {
+    ffs_shoebox box;           /* s1, phi in radians, the half-open box: what ffs_ctx_shoebox_begin takes */
+    double x_px, y_px, z;      /* the predicted centre; z in images from the scan's first */
+    int32_t h, k, l;
+    uint32_t flags;            /* FFS_PREDICT_* */
+} ffs_prediction;                 /* 96 bytes */
+/* The scan-point settings A_k, k = 0 .. n_images, as ffs_ctx_predict computes them (what predict.cc:68-73 builds per image with its Rotator):
+ * out receives (n_images + 1) * 9 doubles, row-major.  Host only: no context, no GPU.  This is the one place libm enters the prediction.
+ * FFS_ERR_INVALID (ffs_last_error(NULL) has the text): a NULL argument, an entry that is not finite, a zero rot_axis, n_images 0 or above
+ * 65 535. */
+int ffs_predict_scan_settings(const ffs_scan_geometry *geometry, const ffs_crystal *crystal, uint32_t n_images, double *out);
+/* Predicts the reflections of images 0 .. n_images - 1 of the scan on the context's image (its width and height are the panel's) and their
+ * shoeboxes for delta_b = n_sigma * sigma_b and delta_m = n_sigma * sigma_m in radians, as ffs_ctx_shoebox_begin takes them (replaces
+ * predict_rotation's thread pool over images, predict.cc:130-, and compute_kabsch_bounding_boxes).  Synchronous, in a HIP stream of its
+ * own: a count pass, a scan over the workgroups' counts and a write pass, a lane per candidate.  It changes no batch's plan, reads and
+ * writes no state of the context's streams and may run while batches are in flight; calls on one context follow one another under a mutex.
+ * *n = the number of predictions, always written when the call is taken; at most cap records are written, and FFS_ERR_OVERFLOW is returned
+ * when cap is smaller (the records written are valid): cap 0 with out NULL asks for the size.  kernel_ms may be NULL; otherwise the sum of
+ * the launches' times from HIP events on their dispatches.
+ * FFS_ERR_INVALID with a text, nothing changed: a NULL geometry, crystal or n, or a NULL out with cap > 0; an entry that is not finite; a
+ * singular a_matrix or d_matrix; dmin, delta_b, delta_m, wavelength or a pixel size not positive; osc_width_deg 0; a zero rot_axis or s0;
+ * n_images 0 or above 65 535; an unknown centring; a candidate box of more than 2^31 - 1 indices. */
+int ffs_ctx_predict(ffs_ctx *ctx, const ffs_scan_geometry *geometry, const ffs_crystal *crystal, uint32_t n_images, double dmin,
+                    double delta_b, double delta_m, ffs_prediction *out, uint32_t cap, uint32_t *n, float *kernel_ms);
+
 /* Centres of mass of the last batch's reflections as rows (frame_id, x, y, z) of float32 -- the
  * payload of `--output-for-index` (spot_centers, spotfinder.cc:919-933,1004-1006), in frame order;
  * used to feed a multi-GPU gather without a per-frame loop on the caller's side.  Lane 0 carries the
