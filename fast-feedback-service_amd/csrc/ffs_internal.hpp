@@ -16,6 +16,9 @@
 //                    (kernels_shoebox.hpp); acts on the decisions of shoebox_plan.hpp
 //   ffs_predict.hip  scan prediction for a rotation sweep: ffs_predict_scan_settings and ffs_ctx_predict, a count pass, a scan and a write pass
 //                    in a HIP stream of the call's own (kernels_predict.hpp); acts on the decisions of predict_plan.hpp
+//   ffs_index.hip    the indexer's basis-vector search: the host-only ffs_index_* entries and ffs_ctx_index_grid / index_load_grid / index_peaks --
+//                    scatter, three FFT passes, the statistics' trees, selection, union-find, per-root sums and records in a HIP stream of
+//                    the call's own (kernels_index.hpp); acts on the decisions of index_plan.hpp
 //   ffs_stack3d.hip  rotation sweeps: the device-resident 3D stack -- create and pool, append a batch's lists, finish (kernels_stack3d); acts on
 //                    the decisions of sweep_plan.hpp
 //   ffs_multi.hip    several GPUs in one process: RCCL loaded with dlopen, the communicators and the choice of transport (ffs_multi_init), the
@@ -55,6 +58,10 @@
 //                        tests/predict_check.cc)
 //   predict_plan.hpp     which prediction calls are taken, the candidate box, the call's constants, the scan-point settings from libm's cos and
 //                        sin, the whole rule on the CPU (tests/predict_plan_check.cc)
+//   index_model.hpp      the indexer's basis-vector search: spot to reciprocal-lattice point, the map on the grid, the FFT's schedule, the
+//                        statistics' tree, components and their records, the filter and the candidate vectors (kernels_index.hpp, included by
+//                        ffs_index.hip; tools/ffs_hosttool.cc; tests/index_check.cc)
+//   index_plan.hpp       which index calls are taken, the device buffers' sizes per n_points and the launches' shapes (tests/index_plan_check.cc)
 // No exception leaves the library (guarded()).
 #pragma once
 #include <algorithm>
@@ -110,6 +117,7 @@ struct ThreadError {
 struct ffs_stack3d;
 struct ShoeboxJob;   // ffs_shoebox.hip
 struct PredictState; // ffs_predict.hip
+struct IndexState;   // ffs_index.hip
 
 // A few helper threads per context for ffs_wait's result assembly (wire records -> boxes, reflections, centre rows): one thread
 // moves a batch's 7 MB (45 000 components of 32 Eiger frames) in 0.21 ms -- two thirds of the time the GPU takes for the batch, and
@@ -208,6 +216,9 @@ struct ffs_ctx {
     // is one step under predict_mu.  Nothing of a batch is in here.
     PredictState* predict = nullptr;
     std::mutex predict_mu;
+    // ffs_ctx_index_grid / index_load_grid / index_peaks: the same for the index calls, with the grids of the last n_points
+    IndexState* index = nullptr;
+    std::mutex index_mu;
     uint8_t* d_maskbits = nullptr;
     uint8_t* d_ginfo = nullptr;  // per-group mask bits + window-count bounds (kernels_stream.hpp)
     uint8_t* d_mmap = nullptr;   // per-pixel window counts
@@ -653,6 +664,8 @@ void spotbg_free(ffs_stream* s);   // the stream's own HIP stream, events and bu
 void shoebox_free_ctx(ffs_ctx* c);   // the open job, if any (context destroy; every stream is closed)
 // ffs_predict.hip
 void predict_free_ctx(ffs_ctx* c);   // what ffs_ctx_predict kept (context destroy)
+// ffs_index.hip
+void index_free_ctx(ffs_ctx* c);     // what the index calls kept (context destroy)
 // ffs_stack3d.hip
 void stack3d_free(ffs_stack3d* st);
 // ffs_multi.hip

@@ -31,6 +31,7 @@ void usage() {
       "                   [--integrate-background tukey|glm] [--integrate-n-sigma 3]]\n"
       "                  [--predict CRYSTAL --predict-dmin D --sigma-b DEG --sigma-m DEG --integrate-out PREFIX [--predict-centring P|I|F|A|B|C|R]\n"
       "                   [--integrate-n-sigma 3] [--integrate-algorithm ...] [--integrate-background ...]]\n"
+      "                  [--index-basis PREFIX --max-cell C [--index-dmin D] [--fft-npoints N]]\n"
       "                  [--devices D0,D1,... | --gpus N] [--no-numa-pinning] [--single-buffer] [--all-threads] [--read-only] [--clean-exit]\n"
       "--max-valid: a centre pixel above this value is never strong (the reference's kernels test it against the\n"
       "              data set's trusted maximum).  trusted (default) = the frame source's trusted-range maximum when it is\n"
@@ -112,6 +113,12 @@ void usage() {
       "              out the lattice's absent indices (default P); the boxes are --integrate-n-sigma x --sigma-b and x --sigma-m in Kabsch\n"
       "              space.  One line says candidates, predictions and flagged records; PREFIX.predictions holds the records of 96 bytes\n"
       "              (ffs_prediction of ffs_hip.h); the boxes not flagged as refused are then integrated exactly as --integrate does\n"
+      "--index-basis: after a rotation sweep's finish the 3D reflections' centres of mass are turned into candidate basis vectors on the GPU\n"
+      "              (spot FFT on a grid of --fft-npoints a side, default 256, and peak search; the reference's indexer up to peaks_to_rlvs).\n"
+      "              --max-cell C is the longest cell edge expected (Angstrom); --index-dmin D the resolution limit (default: from C and the\n"
+      "              data).  PREFIX.centres holds the n x 3 float64 used (x_px, y_px, z), PREFIX.peaks the 56-byte ffs_index_peak records,\n"
+      "              PREFIX.basis_vectors the 40-byte ffs_index_vector records; the vectors are printed as the reference logs them.  Needs a\n"
+      "              rotation sweep; one GPU only; not with --validate\n"
       "--validate:  every image is also decided by an independent path (every valid pixel's window gathered from memory,\n"
       "              no streaming kernel) and the two strong-pixel masks are compared: Match / Mismatch per image\n"
       "--devices / --gpus: one context and worker pool per GPU, all pulling frames from the one queue\n"
@@ -160,6 +167,7 @@ Args parse_args(int argc, char** argv) {
     }
     Args r;
     bool model_given = false;   // --spot-background-model, in either spelling: refused without --spot-background
+    bool index_option_given = false;       // --max-cell, --index-dmin and --fft-npoints: refused without --index-basis
     bool predict_option_given = false;     // --predict-dmin and --predict-centring: refused without --predict
     bool integrate_option_given = false;   // --sigma-b, --sigma-m and the --integrate-* options: refused without --integrate
     if (const char* e = std::getenv("SPOTFINDER_TIMEOUT")) {  // spotfinder.cc:293-301
@@ -306,6 +314,26 @@ Args parse_args(int argc, char** argv) {
             r.predict_centring = (int)at;
             predict_option_given = true;
         }
+        else if (s == "--index-basis") {
+            r.index_basis = need(i, s);
+            if (r.index_basis.empty()) arg_error("--index-basis takes the prefix of the files it writes");
+        }
+        else if (s == "--max-cell" || s == "--index-dmin") {
+            const std::string& v = need(i, s);
+            char* end = nullptr;
+            const double x = std::strtod(v.c_str(), &end);
+            if (v.empty() || *end || !(x > 0.0 && x <= 1e6)) arg_error(s + " takes a finite number > 0 (Angstrom): " + v);
+            (s == "--max-cell" ? r.index_max_cell : r.index_dmin) = x;
+            index_option_given = true;
+        }
+        else if (s == "--fft-npoints") {
+            const std::string& v = need(i, s);
+            char* end = nullptr;
+            const long n = std::strtol(v.c_str(), &end, 10);
+            if (v.empty() || *end || n < 16 || n > 256 || (n & (n - 1)) != 0) arg_error("--fft-npoints takes a power of two in 16 .. 256: " + v);
+            r.fft_npoints = (uint32_t)n;
+            index_option_given = true;
+        }
         else if (s == "--integrate-out") {
             r.integrate_out = need(i, s);
             if (r.integrate_out.empty()) arg_error("--integrate-out takes the prefix of the file it writes");
@@ -388,6 +416,14 @@ Args parse_args(int argc, char** argv) {
         if (!r.jungfrau_pedestal.empty()) arg_error("--jungfrau-pedestal finds no spots and integrates none: not with --integrate");
     } else if (integrate_option_given || !r.integrate_out.empty()) {
         arg_error("--sigma-b, --sigma-m and the --integrate-* options belong to --integrate");
+    }
+    if (!r.index_basis.empty()) {
+        if (!(r.index_max_cell > 0.0)) arg_error("--index-basis needs --max-cell C (Angstrom): the longest cell edge expected");
+        if (r.validate) arg_error("--index-basis is not available with --validate");
+        if (r.devices.size() > 1) arg_error("--index-basis takes one GPU: not with --devices / --gpus of more than one");
+        if (!r.jungfrau_pedestal.empty()) arg_error("--jungfrau-pedestal finds no spots: not with --index-basis");
+    } else if (index_option_given) {
+        arg_error("--max-cell, --index-dmin and --fft-npoints belong to --index-basis");
     }
     if (r.gain > 0.0 && !r.gain_map.empty()) arg_error("--gain and --gain-map exclude each other: a constant map is the scalar gain");
     std::string lower = r.algorithm;   // DispersionAlgorithm, spotfinder.cc:180-203

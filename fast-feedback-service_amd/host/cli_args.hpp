@@ -48,6 +48,13 @@ struct Args {
     double predict_dmin = 0.0;           // --predict-dmin D (Angstrom, > 0)
     int predict_centring = 0;            // --predict-centring P|I|F|A|B|C|R: FFS_CENTRING_*
     bool integrating() const { return !integrate.empty() || !predict.empty(); }
+    // --index-basis PREFIX: after a rotation sweep's finish the 3D reflections' centres of mass go through the indexer's basis-vector search
+    // (ffs_index_rlp .. ffs_ctx_index_grid / index_peaks .. ffs_index_basis_vectors); PREFIX.centres, PREFIX.peaks and PREFIX.basis_vectors are
+    // written; needs --max-cell C; one GPU; not with --validate; empty = not given
+    std::string index_basis;
+    double index_max_cell = 0.0;         // --max-cell C (Angstrom, > 0)
+    double index_dmin = 0.0;             // --index-dmin D (Angstrom, > 0); 0 = chosen from max_cell and the data
+    uint32_t fft_npoints = 256;          // --fft-npoints N: a power of two in 16 .. 256
     std::string pixel_stats;             // --pixel-stats PREFIX: per-pixel count, sum, sum of squares and maximum over the run, into PREFIX.*; empty = not given
     uint32_t min_count = 2;
     int kernel_half_x = 3, kernel_half_y = 3;   // --kernel-size

@@ -37,6 +37,7 @@
 #include "reader.hpp"
 #include "shoebox_geometry.hpp"
 #include "predict_geometry.hpp"
+#include "index_basis.hpp"
 #include "../csrc/predict_plan.hpp"
 #include "../csrc/shoebox_model.hpp"
 #include "../csrc/sweep_plan.hpp"
@@ -963,8 +964,50 @@ class BatchReport {
 
 // ---- after the run ---------------------------------------------------------------------------------------------------------------
 
+// --index-basis PREFIX, after the sweep's finish: the 3D reflections' centres of mass through the indexer's basis-vector search (the reference's
+// indexer.cc:171-245 with its constants), PREFIX.centres / .peaks / .basis_vectors and the lines the reference logs.  `ffs_hosttool indexbasis`
+// on PREFIX.centres and the printed geometry writes the same bytes.  -> false on an error, which has been printed
+static bool index_basis(const Args& args, ffs_ctx* ctx, const KabschGeometry& kg, const ffs_reflection* refl, uint32_t n) {
+    const ffs_scan_geometry g = shoebox_flat_geometry(kg);
+    std::vector<double> xyz(3 * (size_t)n), rlp(3 * (size_t)n), s1(3 * (size_t)n), mm(3 * (size_t)n);
+    for (uint32_t i = 0; i < n; ++i) xyz[3 * (size_t)i] = refl[i].com_x, xyz[3 * (size_t)i + 1] = refl[i].com_y, xyz[3 * (size_t)i + 2] = refl[i].com_z;
+    const auto failed = [&](int rc, ffs_ctx* c) {
+        if (rc == FFS_OK) return false;
+        std::printf("Error: --index-basis: %s\n", ffs_last_error(c));
+        return true;
+    };
+    double dmin = args.index_dmin, b_iso = 0.0;
+    if (failed(ffs_index_rlp(&g, xyz.data(), n, rlp.data(), s1.data(), mm.data()), nullptr)) return false;
+    if (failed(ffs_index_defaults(rlp.data(), n, args.index_max_cell, args.fft_npoints, &dmin, &b_iso), nullptr)) return false;
+    float grid_ms = 0.0f, peaks_ms = 0.0f;
+    if (failed(ffs_ctx_index_grid(ctx, rlp.data(), n, dmin, b_iso, args.fft_npoints, nullptr, nullptr, &grid_ms), ctx)) return false;
+    uint32_t n_peaks = 0, n_vectors = 0;
+    int rc = ffs_ctx_index_peaks(ctx, 15.0, nullptr, 0, &n_peaks, nullptr, nullptr);
+    if (rc != FFS_ERR_OVERFLOW && failed(rc, ctx)) return false;
+    std::vector<ffs_index_peak> peaks(n_peaks);
+    ffs_index_grid_stats st{};
+    if (failed(ffs_ctx_index_peaks(ctx, 15.0, peaks.data(), n_peaks, &n_peaks, &st, &peaks_ms), ctx)) return false;
+    std::vector<ffs_index_vector> vectors(n_peaks);
+    if (failed(ffs_index_basis_vectors(peaks.data(), n_peaks, args.fft_npoints, dmin, 0.15, 3.0, args.index_max_cell, vectors.data(), n_peaks, &n_vectors), nullptr)) return false;
+    vectors.resize(n_vectors);
+    try {
+        write_raw_file(args.index_basis + ".centres", xyz.data(), xyz.size() * sizeof(double));
+        write_raw_file(args.index_basis + ".peaks", peaks.data(), peaks.size() * sizeof(ffs_index_peak));
+        write_raw_file(args.index_basis + ".basis_vectors", vectors.data(), vectors.size() * sizeof(ffs_index_vector));
+    } catch (const std::exception& e) {
+        std::printf("Error: --index-basis: %s\n", e.what());
+        return false;
+    }
+    std::printf("Index: %u spots, dmin %.5f, b_iso %.3f, grid of %u points a side, %u voxels selected, %u peaks (%.3f + %.3f ms on the GPU; one GPU)\n", n, dmin, b_iso,
+                args.fft_npoints, st.n_selected, n_peaks, (double)grid_ms, (double)peaks_ms);
+    std::printf("Index geometry: distance=%.17g beam_x=%.17g beam_y=%.17g pixel_x=%.17g pixel_y=%.17g wavelength=%.17g osc_start=%.17g osc_width=%.17g\n",
+                kg.distance_mm, kg.beam_center_x_px, kg.beam_center_y_px, kg.pixel_size_x_mm, kg.pixel_size_y_mm, kg.wavelength, kg.oscillation_start, kg.oscillation_width);
+    std::printf("%s", index_vector_lines(vectors.data(), vectors.size()).c_str());
+    return true;
+}
+
 // 3D connected components (spotfinder.cc:1099-1148), spot variances for integration (:1152-1215), results_ffs.h5 (:1217-1262)
-static void finish_3d(const Args& args, ffs_ctx* ctx, ffs_stack3d* stack, const ffs_params& prm, const Experiment& ex, Clock::time_point t_joined) {
+static bool finish_3d(const Args& args, ffs_ctx* ctx, ffs_stack3d* stack, const ffs_params& prm, const Experiment& ex, Clock::time_point t_joined) {
     std::printf("Processing 3D spots\n");
     const ffs_reflection* refl = nullptr;
     uint32_t n = 0, n_calc = 0, f_size = 0, f_sep = 0;
@@ -1014,7 +1057,9 @@ static void finish_3d(const Args& args, ffs_ctx* ctx, ffs_stack3d* stack, const 
     }
     if (args.verbose) std::printf("3D analysis in all: %.1f ms\n", ms_between(t_joined, Clock::now()));
     std::printf("3D spot analysis complete\n");
+    const bool ok = args.index_basis.empty() || index_basis(args, ctx, geom, refl, n);
     ffs_stack3d_destroy(stack);
+    return ok;
 }
 
 // stills with -h5: every image's centres into results_ffs.h5, one experiment id per image (spotfinder.cc:1265-1306)
@@ -1196,6 +1241,10 @@ int main(int argc, char** argv) {
     size_t n_shoeboxes = 0;
     if (!args.integrate.empty())
         if (const int rc = open_integration(args, ex, rotation, ctxs, n_shoeboxes)) return rc;
+    if (!args.index_basis.empty() && !rotation) {
+        std::printf("Error: --index-basis needs a rotation source (an oscillation width above 0): the spots of stills have no rotation angle\n");
+        return 1;
+    }
     if (!args.predict.empty())
         if (const int rc = open_prediction(args, ex, rotation, num_images, (int)shape.width, (int)shape.height, ctxs, n_shoeboxes)) return rc;
     if (args.validate && !create_validation_contexts(devices, ctxs, shape, batch, prm, args.max_valid_scope, args.gain, gain_map, vctxs)) return 1;
@@ -1244,11 +1293,13 @@ int main(int argc, char** argv) {
     // ---- post-processing and the totals ------------------------------------------------------------------------------------------
     const auto t_joined = Clock::now();
     if (args.verbose) std::printf("Workers joined %.0f ms after the start\n", ms_between(all_start, t_joined));
-    if (rotation) finish_3d(args, ctx, stack, prm, ex, t_joined);
+    bool finished = true;
+    if (rotation) finished = finish_3d(args, ctx, stack, prm, ex, t_joined);
     else if (args.save_h5) write_2d_h5(report.reflection_centers_2d);
     print_summary(args, shape, pipeline, report, gather.get(), n_dev, all_start, stamp.process_start());
     if (!args.pixel_stats.empty() && !write_pixel_stats(args.pixel_stats, ctxs, shape.width, shape.height)) return 1;
     if (args.integrating() && !write_integration(args, ctxs, n_shoeboxes)) return 1;
+    if (!finished) return 1;   // (--index-basis has said why)
     pipe.reset();
     exchange.join();
     stamp("timed loop and reports done");

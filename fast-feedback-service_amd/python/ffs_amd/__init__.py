@@ -12,4 +12,6 @@ from .api import (Context, FrameResult, Params, Stack3D, Stream, device_count,  
                   RADIAL_BLUR_NONE, RADIAL_BLUR_NARROW, RADIAL_BLUR_WIDE,
                   SHOEBOX_DT, SHOEBOX_SUM_DT, SHOEBOX_ELLIPSOID, SHOEBOX_DIALS, SHOEBOX_FG_INVALID,
                   PREDICTION_DT, CENTRINGS, PREDICT_ENTERING, PREDICT_CORNER_LOST, PREDICT_ZETA_SMALL, PREDICT_BOX_REFUSED,
-                  predict_scan_settings, shoeboxes_of)
+                  predict_scan_settings, shoeboxes_of,
+                  INDEX_PEAK_DT, INDEX_VECTOR_DT, INDEX_NOT_USED, INDEX_LAUNCH_SPANS, INDEX_RMSD_CUTOFF, INDEX_PEAK_VOLUME_CUTOFF, INDEX_MIN_CELL,
+                  index_rlp, index_defaults, index_twiddles, index_map, index_basis_vectors)

@@ -135,6 +135,22 @@ CENTRINGS = {"P": 0, "I": 1, "F": 2, "A": 3, "B": 4, "C": 5, "R": 6}   # FFS_CEN
 PREDICT_ENTERING, PREDICT_CORNER_LOST, PREDICT_ZETA_SMALL, PREDICT_BOX_REFUSED = 1, 2, 4, 8   # FFS_PREDICT_*, in a record's flags
 
 
+# The indexer's basis-vector search (ffs_index_*, ffs_ctx_index_*)
+INDEX_PEAK_DT = np.dtype([("root", "<u4"), ("n_voxels", "<u4"), ("sum", "<i8", (3,)), ("frac", "<f8", (3,))])   # ffs_index_peak
+INDEX_VECTOR_DT = np.dtype([("v", "<f8", (3,)), ("length", "<f8"), ("volume", "<u4"), ("reserved", "<u4")])   # ffs_index_vector
+
+
+class _IndexGridStats(C.Structure):   # ffs_index_grid_stats
+    _fields_ = [("sum", C.c_double), ("mean", C.c_double), ("rmsd", C.c_double), ("cutoff", C.c_double), ("n_selected", C.c_uint32), ("n_peaks", C.c_uint32)]
+
+
+assert INDEX_PEAK_DT.itemsize == 56 and INDEX_VECTOR_DT.itemsize == 40 and C.sizeof(_IndexGridStats) == 40
+# the stages of ffs_ctx_index_launch_ms, in its order (FFS_INDEX_LAUNCH_SPANS of them)
+INDEX_LAUNCH_SPANS = ("fill_scatter", "fft_axis0", "fft_axis1", "fft_axis2_power", "sum_trees", "second_statistic", "selection", "union_flatten", "reduce_records")
+INDEX_NOT_USED = 0xFFFFFFFF   # ffs_index_map: a spot that is not mapped
+INDEX_RMSD_CUTOFF, INDEX_PEAK_VOLUME_CUTOFF, INDEX_MIN_CELL = 15.0, 0.15, 3.0   # the reference's constants (indexer.cc:234-245)
+
+
 # ffs_radial_shell: what the radial-profile threshold decided for one (frame, shell) -- Stream.radial_thresholds
 RADIAL_SHELL_DT = np.dtype([("n_pixels", "<u4"), ("n_overflow", "<u4"), ("q1", "<i4"), ("median", "<i4"), ("q3", "<i4"), ("cutoff", "<u4"),
                             ("status", "<u4"), ("reserved", "<u4")])
@@ -188,6 +204,8 @@ EXPORTS = [
     "ffs_jungfrau_pedestal_planes",
     "ffs_ctx_shoebox_begin", "ffs_ctx_shoebox_end", "ffs_stream_shoebox_fold", "ffs_ctx_get_shoebox_sums", "ffs_ctx_get_shoebox_histogram",
     "ffs_predict_scan_settings", "ffs_ctx_predict",
+    "ffs_index_rlp", "ffs_index_defaults", "ffs_index_twiddles", "ffs_index_map", "ffs_index_basis_vectors",
+    "ffs_ctx_index_grid", "ffs_ctx_index_load_grid", "ffs_ctx_index_peaks", "ffs_ctx_index_launch_ms",
 ]
 
 _lib = None
@@ -240,6 +258,16 @@ def load_library():
         L.ffs_predict_scan_settings.argtypes = [C.POINTER(_ScanGeometry), C.POINTER(_Crystal), C.c_uint32, C.c_void_p]
         L.ffs_ctx_predict.argtypes = [C.c_void_p, C.POINTER(_ScanGeometry), C.POINTER(_Crystal), C.c_uint32, C.c_double, C.c_double, C.c_double, C.c_void_p,
                                       C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_float)]
+        L.ffs_index_rlp.argtypes = [C.POINTER(_ScanGeometry), C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.ffs_index_defaults.argtypes = [C.c_void_p, C.c_uint32, C.c_double, C.c_uint32, C.POINTER(C.c_double), C.POINTER(C.c_double)]
+        L.ffs_index_twiddles.argtypes = [C.c_uint32, C.c_void_p]
+        L.ffs_index_map.argtypes = [C.c_void_p, C.c_uint32, C.c_double, C.c_double, C.c_uint32, C.c_void_p, C.c_void_p]
+        L.ffs_index_basis_vectors.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_double, C.c_double, C.c_double, C.c_double, C.c_void_p, C.c_uint32,
+                                              C.POINTER(C.c_uint32)]
+        L.ffs_ctx_index_grid.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_double, C.c_double, C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(C.c_float)]
+        L.ffs_ctx_index_load_grid.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
+        L.ffs_ctx_index_peaks.argtypes = [C.c_void_p, C.c_double, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(_IndexGridStats), C.POINTER(C.c_float)]
+        L.ffs_ctx_index_launch_ms.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
         L.ffs_bench_pipeline.argtypes = [C.POINTER(C.c_void_p), C.c_uint32, C.c_void_p, C.c_size_t, C.c_size_t, C.c_uint32,
                                          C.c_uint32, C.c_int64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
         L.ffs_device_numa_node.argtypes = [C.c_int]
@@ -574,6 +602,63 @@ class Context:
         self._check(rc)
         out = out[:n.value]
         return (out, ms.value) if want_ms else out
+
+    def index_grid(self, rlp, dmin: float, b_iso: float, n_points: int = 256, *, want_power: bool = False, want_ms: bool = False):
+        """ffs_ctx_index_grid: maps the reciprocal-lattice points (n, 3) on a grid of n_points a side, transforms it on the GPU and leaves the
+        power grid resident for index_peaks.  Returns `used` (n bools: the spot was mapped), then the power grid (n_points^3 float64, flat)
+        when want_power, then the launches' time when want_ms.  May be called while batches of the context are in flight."""
+        r = np.ascontiguousarray(np.asarray(rlp, np.float64).reshape(-1, 3))
+        used = np.zeros(len(r), np.uint8)
+        power = np.empty(int(n_points) ** 3, np.float64) if want_power and 0 < int(n_points) <= 256 else None
+        ms = C.c_float()
+        self._check(self._lib.ffs_ctx_index_grid(self._h, r.ctypes.data_as(C.c_void_p) if len(r) else None, len(r), float(dmin), float(b_iso), int(n_points),
+                                                 used.ctypes.data_as(C.c_void_p), power.ctypes.data_as(C.c_void_p) if power is not None else None, C.byref(ms)))
+        out = (used.astype(bool),) + ((power,) if want_power else ()) + ((ms.value,) if want_ms else ())
+        return out[0] if len(out) == 1 else out
+
+    def index_load_grid(self, power, n_points: int):
+        """ffs_ctx_index_load_grid: a caller's power grid (n_points^3 float64) in place of the resident one."""
+        g = np.ascontiguousarray(np.asarray(power, np.float64).reshape(-1))
+        if g.size != int(n_points) ** 3:
+            raise ValueError(f"power must have n_points^3 = {int(n_points) ** 3} entries, not {g.size}")
+        self._check(self._lib.ffs_ctx_index_load_grid(self._h, g.ctypes.data_as(C.c_void_p), int(n_points)))
+
+    def index_peaks(self, rmsd_cutoff: float = INDEX_RMSD_CUTOFF, *, cap=None, want_ms: bool = False):
+        """ffs_ctx_index_peaks: (records of INDEX_PEAK_DT in ascending order of root, the grid's statistics as a dict) of the resident grid.
+        cap (optional): at most that many records are fetched; FfsError -4 (FFS_ERR_OVERFLOW) when there are more -- its `records`, `n`
+        and `stats` attributes carry what was written.  want_ms: also return the kernels' time."""
+        n, ms, st = C.c_uint32(), C.c_float(), _IndexGridStats()
+        if cap is None:
+            rc = self._lib.ffs_ctx_index_peaks(self._h, float(rmsd_cutoff), None, 0, C.byref(n), None, None)
+            if rc != -4:   # FFS_ERR_OVERFLOW: the count is in n
+                self._check(rc)
+            cap = n.value
+        out = np.zeros(int(cap), INDEX_PEAK_DT)
+        rc = self._lib.ffs_ctx_index_peaks(self._h, float(rmsd_cutoff), out.ctypes.data_as(C.c_void_p) if cap else None, int(cap), C.byref(n), C.byref(st), C.byref(ms))
+        stats = {k: getattr(st, k) for k, _ in _IndexGridStats._fields_}
+        if rc == -4:
+            err = FfsError(rc, self._lib.ffs_last_error(self._h).decode())
+            err.records, err.n, err.stats = out, n.value, stats
+            raise err
+        self._check(rc)
+        out = out[:n.value]
+        return (out, stats, ms.value) if want_ms else (out, stats)
+
+    def index_launch_ms(self) -> dict:
+        """ffs_ctx_index_launch_ms: where the launches' time of the last index_grid and the last index_peaks went, in ms by stage."""
+        out = (C.c_float * len(INDEX_LAUNCH_SPANS))()
+        self._check(self._lib.ffs_ctx_index_launch_ms(self._h, out))
+        return dict(zip(INDEX_LAUNCH_SPANS, (float(v) for v in out)))
+
+    def index_basis(self, xyz_px, geometry, max_cell: float, dmin=None, n_points: int = 256):
+        """The chain of the reference's indexer up to its candidate basis vectors (indexer.cc:171-245) with its constants (rmsd_cutoff 15.0,
+        peak_volume_cutoff 0.15, min_cell 3.0): spot centres (n, 3) of (x_px, y_px, z in images) -> records of INDEX_VECTOR_DT in Angstrom,
+        sorted by volume.  The map, the filter and the vectors are host arithmetic; the transform and the peak search run on the GPU."""
+        rlp, _, _ = index_rlp(geometry, xyz_px)
+        dmin, b_iso = index_defaults(rlp, max_cell, n_points, dmin)
+        self.index_grid(rlp, dmin, b_iso, n_points)
+        peaks, _ = self.index_peaks(INDEX_RMSD_CUTOFF)
+        return index_basis_vectors(peaks, n_points, dmin, max_cell)
 
     def set_tuning(self, **kw):
         """ffs_ctx_set_tuning: A/B partners, fall-backs and capacities (same results either way); see include/ffs_hip.h."""
@@ -925,6 +1010,60 @@ def predict_scan_settings(geometry, a_matrix, n_images: int, centring="P") -> np
     if rc != 0:
         raise FfsError(rc, lib.ffs_last_error(None).decode())
     return out
+
+
+def _index_check(lib, rc):
+    if rc != 0:
+        raise FfsError(rc, lib.ffs_last_error(None).decode())
+
+
+def index_rlp(geometry, xyz_px):
+    """ffs_index_rlp: spot centres (n, 3) of (x_px, y_px, z in images from the scan's first) -> (rlp, s1, xyz_mm), each (n, 3) float64;
+    xyz_mm is (x_mm, y_mm, angle in radians).  On the host: no context, no GPU."""
+    lib = load_library()
+    g = _scan_geometry(geometry)
+    xyz = np.ascontiguousarray(np.asarray(xyz_px, np.float64).reshape(-1, 3))
+    out = [np.zeros((len(xyz), 3), np.float64) for _ in range(3)]
+    _index_check(lib, lib.ffs_index_rlp(C.byref(g), xyz.ctypes.data_as(C.c_void_p) if len(xyz) else None, len(xyz), *(o.ctypes.data_as(C.c_void_p) for o in out)))
+    return tuple(out)
+
+
+def index_defaults(rlp, max_cell: float, n_points: int = 256, dmin=None):
+    """ffs_index_defaults: (dmin, b_iso); dmin None (or 0) = max(5 max_cell / n_points, the highest resolution among rlp)."""
+    lib = load_library()
+    r = np.ascontiguousarray(np.asarray(rlp, np.float64).reshape(-1, 3))
+    d, b = C.c_double(0.0 if dmin is None else float(dmin)), C.c_double()
+    _index_check(lib, lib.ffs_index_defaults(r.ctypes.data_as(C.c_void_p) if len(r) else None, len(r), float(max_cell), int(n_points), C.byref(d), C.byref(b)))
+    return d.value, b.value
+
+
+def index_twiddles(n_points: int) -> np.ndarray:
+    """ffs_index_twiddles: the FFT's table, (n_points / 2, 2) float64 of (cos, -sin)(2 pi k / n_points)."""
+    lib = load_library()
+    out = np.zeros(max(int(n_points), 0) if int(n_points) <= 256 else 0, np.float64)
+    _index_check(lib, lib.ffs_index_twiddles(int(n_points), out.ctypes.data_as(C.c_void_p)))
+    return out.reshape(-1, 2)
+
+
+def index_map(rlp, dmin: float, b_iso: float, n_points: int = 256):
+    """ffs_index_map: per spot (cell, weight); cell INDEX_NOT_USED where the spot is not mapped."""
+    lib = load_library()
+    r = np.ascontiguousarray(np.asarray(rlp, np.float64).reshape(-1, 3))
+    cell, weight = np.zeros(len(r), np.uint32), np.zeros(len(r), np.float64)
+    _index_check(lib, lib.ffs_index_map(r.ctypes.data_as(C.c_void_p) if len(r) else None, len(r), float(dmin), float(b_iso), int(n_points),
+                                        cell.ctypes.data_as(C.c_void_p), weight.ctypes.data_as(C.c_void_p)))
+    return cell, weight
+
+
+def index_basis_vectors(peaks, n_points: int, dmin: float, max_cell: float, peak_volume_cutoff: float = INDEX_PEAK_VOLUME_CUTOFF, min_cell: float = INDEX_MIN_CELL):
+    """ffs_index_basis_vectors: Context.index_peaks' records -> the candidate basis vectors (INDEX_VECTOR_DT, Angstrom), sorted by volume."""
+    lib = load_library()
+    p = np.ascontiguousarray(np.asarray(peaks, INDEX_PEAK_DT))
+    out = np.zeros(len(p), INDEX_VECTOR_DT)
+    n = C.c_uint32()
+    _index_check(lib, lib.ffs_index_basis_vectors(p.ctypes.data_as(C.c_void_p) if len(p) else None, len(p), int(n_points), float(dmin), float(peak_volume_cutoff),
+                                                  float(min_cell), float(max_cell), out.ctypes.data_as(C.c_void_p) if len(p) else None, len(p), C.byref(n)))
+    return out[:n.value]
 
 
 def shoeboxes_of(predictions: np.ndarray, skip_refused: bool = True) -> np.ndarray:

@@ -32,6 +32,11 @@
 //                                         the geometry keys of the above, width= height= crystal=<nine float64> n_images= dmin= sigma_b= sigma_m=
 //                                         [n_sigma=3] [centring=P|I|F|A|B|C|R] out=<file>: writes the ffs_prediction records spotfinder --predict
 //                                         writes to PREFIX.predictions and prints its summary line
+//   ffs_hosttool indexbasis key=value ... the indexer's basis-vector search on the CPU by csrc/index_model.hpp, the text the kernels of
+//                                         ffs_ctx_index_grid / index_peaks compile (the twin of spotfinder --index-basis): the geometry keys of
+//                                         the above, centres=<n x 3 float64: x_px, y_px, z> max-cell= [dmin=] [npoints=256] out=<PREFIX>:
+//                                         writes PREFIX.peaks (ffs_index_peak), PREFIX.basis_vectors (ffs_index_vector) and PREFIX.grid_sha256
+//                                         (the digest of the power grid's bytes) and prints the candidate vectors as the reference logs them
 #include <cinttypes>
 #include <cstdio>
 #include <cstdlib>
@@ -43,6 +48,8 @@
 
 #include <map>
 
+#include "../csrc/index_model.hpp"
+#include "../csrc/index_plan.hpp"
 #include "../csrc/launch_geometry.hpp"
 #include "../csrc/predict_model.hpp"
 #include "../csrc/predict_plan.hpp"
@@ -51,6 +58,7 @@
 #include "../csrc/spot_background_glm_model.hpp"
 #include "shoebox_geometry.hpp"
 #include "predict_geometry.hpp"
+#include "index_basis.hpp"
 #include "codecs.hpp"
 #include "reader.hpp"
 
@@ -477,6 +485,48 @@ static int predict(const KeyValues& kv) {
     return o ? 0 : fail("predict: cannot write the file");
 }
 
+static int indexbasis(const KeyValues& kv) {
+    const ffs_scan_geometry fg = shoebox_flat_geometry(kv.geometry());
+    ffsamd::ShoeboxGeometry g;
+    std::memcpy(&g, &fg, sizeof g);
+    const std::vector<double> xyz = read_centres_file(kv.str("centres"));
+    const uint32_t n = (uint32_t)(xyz.size() / 3);
+    const double max_cell = kv.num("max-cell");
+    const long long points = kv.has("npoints") ? std::stoll(kv.str("npoints")) : 256;
+    if (points < 0 || points > 0xFFFFFFFFll) return fail("indexbasis: npoints does not fit 32 bits");
+    const uint32_t N = (uint32_t)points;
+    double dmin = kv.has("dmin") ? kv.num("dmin") : 0.0, b_iso = 0.0;
+    std::vector<double> rlp(xyz.size()), s1(xyz.size()), mm(xyz.size()), weight(n), weights;
+    std::vector<uint32_t> cell(n), cells;
+    // (what the library's entries refuse is refused here, by the same text)
+    std::string why = ffsamd::index_rlp_refusal(&g, xyz.data(), n, rlp.data(), s1.data(), mm.data());
+    if (why.empty() && kv.has("dmin") && !(dmin > 0.0)) why = "dmin must be finite and positive";
+    if (!why.empty()) return fail(("indexbasis: " + why).c_str());
+    for (uint32_t i = 0; i < n; ++i) ffsamd::index_rlp(g, &xyz[3 * (size_t)i], &rlp[3 * (size_t)i], &s1[3 * (size_t)i], &mm[3 * (size_t)i]);
+    why = ffsamd::index_defaults_refusal(rlp.data(), n, max_cell, N, &dmin, &b_iso);
+    if (!why.empty()) return fail(("indexbasis: " + why).c_str());
+    ffsamd::index_defaults(rlp.data(), n, max_cell, N, dmin, b_iso);
+    for (uint32_t i = 0; i < n; ++i) cell[i] = ffsamd::index_map_one(&rlp[3 * (size_t)i], dmin, b_iso, N, weight[i]);
+    ffsamd::index_map_dedup(cell.data(), weight.data(), n, cells, weights);
+    std::vector<double> tw(N), power(ffsamd::index_voxels(N));
+    ffsamd::index_twiddles(N, tw.data());
+    ffsamd::index_power_grid(cells.data(), weights.data(), cells.size(), N, tw.data(), power.data());
+    ffsamd::IndexGridStats st;
+    std::vector<ffsamd::IndexPeak> peaks;
+    ffsamd::index_peaks(power.data(), N, ffsamd::kIndexRmsdCutoff, st, peaks);
+    const std::vector<ffsamd::IndexVector> vectors =
+        ffsamd::index_basis_vectors(peaks.data(), (uint32_t)peaks.size(), N, dmin, ffsamd::kIndexPeakVolumeCutoff, ffsamd::kIndexMinCell, max_cell);
+    static_assert(sizeof(ffsamd::IndexPeak) == sizeof(ffs_index_peak) && sizeof(ffsamd::IndexVector) == sizeof(ffs_index_vector), "the model's records are the header's");
+    const std::string prefix = kv.str("out");
+    write_raw_file(prefix + ".peaks", peaks.data(), peaks.size() * sizeof(ffsamd::IndexPeak));
+    write_raw_file(prefix + ".basis_vectors", vectors.data(), vectors.size() * sizeof(ffsamd::IndexVector));
+    const std::string digest = sha256_hex(power.data(), power.size() * sizeof(double)) + "\n";
+    write_raw_file(prefix + ".grid_sha256", digest.data(), digest.size());
+    std::printf("index: %u spots, %zu cells, dmin %.5f, b_iso %.3f, %u voxels selected, %zu peaks\n", n, cells.size(), dmin, b_iso, st.n_selected, peaks.size());
+    std::printf("%s", index_vector_lines(reinterpret_cast<const ffs_index_vector*>(vectors.data()), vectors.size()).c_str());
+    return 0;
+}
+
 // chunkfnv <chunk file> <nelem> <elem bytes>: decode one bitshuffle-LZ4 chunk with the host codec and
 // print the FNV-1a of the pixels (cross-check for chunk writers)
 static int chunkfnv(const std::string& path, size_t nelem, size_t es) {
@@ -512,6 +562,7 @@ int main(int argc, char** argv) {
         if (cmd == "shoebox") return shoebox(KeyValues(argc, argv));
         if (cmd == "shoeboxgeom") return shoeboxgeom(KeyValues(argc, argv));
         if (cmd == "predict") return predict(KeyValues(argc, argv));
+        if (cmd == "indexbasis") return indexbasis(KeyValues(argc, argv));
         if (cmd == "h5support") { std::printf("%d\n", h5_supported() ? 1 : 0); return 0; }
     } catch (const std::exception& e) {
         std::printf("Error: %s\n", e.what());
@@ -522,6 +573,7 @@ int main(int argc, char** argv) {
                 "       h5info <master.h5> | synthinfo <synth:spec> | h5support | h5stats <file.h5> <group> |\n"
                 "       chunkfnv <chunk> <nelem> <elem bytes> | jfcal <synth:spec> <file> | jfconvert <raw> <cal> <W> <H> <out> |\n"
                 "       synthframes <synth:spec> <file> | jfrepedestal <old cal> <prefix> <new cal> [min_frames [max_rms]] |\n"
-                "       spotbgglm [histograms] | shoebox key=value ... | shoeboxgeom key=value ... | predict key=value ...\n");
+                "       spotbgglm [histograms] | shoebox key=value ... | shoeboxgeom key=value ... | predict key=value ... |\n"
+                "       indexbasis key=value ...\n");
     return 2;
 }

@@ -900,6 +900,78 @@ int ffs_predict_scan_settings(const ffs_scan_geometry *geometry, const ffs_cryst
 int ffs_ctx_predict(ffs_ctx *ctx, const ffs_scan_geometry *geometry, const ffs_crystal *crystal, uint32_t n_images, double dmin,
                     double delta_b, double delta_m, ffs_prediction *out, uint32_t cap, uint32_t *n, float *kernel_ms);
 
+/* The indexer's basis-vector search: from a sweep's spot centres to candidate real-space lattice vectors, the chain
+ * xyz_to_rlp -> fft3d -> flood_fill -> flood_fill_filter -> peaks_to_rlvs of the reference (baseline/indexer/indexer.cc:171-245) for one flat
+ * panel without parallax correction and identity setting and sample rotations.  THE RULE is stated once, in csrc/index_model.hpp, which the
+ * kernels, this library's host side and `ffs_hosttool indexbasis` compile; no parity with the reference's binaries is claimed.  The device
+ * evaluates no libm function: cos, sin (spot rotation, twiddles), exp (weights), log, acos and round enter on the host.
+ *   grid: n_points a side, a power of two 16 .. 256; a spot's cell is c2 + N c1 + N^2 c0 with c_j = (int)round(rlp_j * dmin * N / 2) + N/2;
+ *     where several spots meet in a cell the highest spot number gives the weight;
+ *   FFT: forward, complex float64, unnormalised, radix 2 decimation in time along axis 0, then 1, then 2, by the schedule of the header, so
+ *     that the device's grid is bit for bit the CPU twin's; power = re * re;
+ *   statistics: float64 sums in a balanced tree (x-lines, then the lines of a plane, then the planes); a voxel is selected at v >= cutoff;
+ *   peaks: six-connected components, periodic in all three axes, numbered by their smallest flat index (root), coordinates unwrapped relative
+ *     to the root, frac_j = sum_j / (n_voxels * N) with j = 0 the slowest grid axis; records in ascending order of root. */
+typedef struct {
+    uint32_t root, n_voxels;
+    int64_t sum[3];
+    double frac[3];
+} ffs_index_peak;                 /* 56 bytes */
+typedef struct {
+    double sum, mean, rmsd, cutoff;
+    uint32_t n_selected, n_peaks;
+} ffs_index_grid_stats;           /* 40 bytes */
+typedef struct {
+    double v[3], length;
+    uint32_t volume, reserved;
+} ffs_index_vector;               /* 40 bytes */
+/* Host only, no context, no GPU; FFS_ERR_INVALID with its text in ffs_last_error(NULL), nothing written: a NULL argument; an entry that is not
+ * finite; n_points not a power of two in 16 .. 256; dmin or max_cell not positive; a wavelength or pixel size not positive; a singular
+ * d_matrix; a zero rot_axis.
+ * ffs_index_rlp (replaces xyz_to_rlp, xyz_to_rlp.cc:46-109): xyz_px is n x 3 (x_px, y_px, z in images from the scan's first, the z of
+ *   ffs_prediction); rlp, s1 and xyz_mm (x_mm, y_mm, angle in radians) receive n x 3 doubles each.
+ * ffs_index_defaults (indexer.cc:184-206): *dmin 0 on entry = choose max(5 max_cell / n_points, the data's highest resolution); b_iso from it.
+ * ffs_index_twiddles: the FFT's table, n_points doubles: (cos, -sin) of 2 pi k / n_points for k = 0 .. n_points/2 - 1.
+ * ffs_index_map (map_centroids_to_reciprocal_space_grid, fft3d.cc:37-91): per spot its cell (0xFFFFFFFF: not used) and weight.
+ * ffs_index_basis_vectors (flood_fill_filter, flood_fill.cc:158-192, and peaks_to_rlvs, peaks_to_rlvs.cc:74-186): the candidate vectors in
+ *   Angstrom, sorted by volume; *n_out = their number, at most cap are written, FFS_ERR_OVERFLOW when cap is smaller. */
+int ffs_index_rlp(const ffs_scan_geometry *geometry, const double *xyz_px, uint32_t n, double *rlp, double *s1, double *xyz_mm);
+int ffs_index_defaults(const double *rlp, uint32_t n, double max_cell, uint32_t n_points, double *dmin, double *b_iso);
+int ffs_index_twiddles(uint32_t n_points, double *out);
+int ffs_index_map(const double *rlp, uint32_t n, double dmin, double b_iso, uint32_t n_points, uint32_t *cell, double *weight);
+int ffs_index_basis_vectors(const ffs_index_peak *peaks, uint32_t n, uint32_t n_points, double dmin, double peak_volume_cutoff,
+                            double min_cell, double max_cell, ffs_index_vector *out, uint32_t cap, uint32_t *n_out);
+/* ffs_ctx_index_grid (replaces fft3d, fft3d.cc:102-182: pocketfft's c2c on a thread pool): maps the n reciprocal-lattice points, transforms
+ * the grid on the device and leaves the power grid resident on the context.  used (may be NULL) receives n bytes, 1 where the spot was
+ * mapped; power_out (may be NULL) the N^3 doubles; kernel_ms (may be NULL) the launches' time from HIP events.  The grids are allocated at
+ * the first call for an n_points (24 N^3 bytes: 403 MB at 256) and freed with the context; a call at another n_points replaces them.
+ * ffs_ctx_index_load_grid puts a caller's power grid in place of the resident one: for tests and callers with a transform of their own.
+ * ffs_ctx_index_peaks (replaces flood_fill, flood_fill.cc:31-149) takes the resident grid's statistics, selects v >= rmsd_cutoff * rmsd and
+ * gives one record per connected peak.  *n = the number of peaks, always written when the call is taken; at most cap records are written,
+ * and FFS_ERR_OVERFLOW is returned when cap is smaller (the records written are valid): cap 0 with out NULL asks for the size.  stats may
+ * be NULL.  The list of selected voxels is sized from their count: 36 bytes a selected voxel.
+ * All three are synchronous, in a HIP stream of their own; they change no batch's plan, read and write no state of the context's streams
+ * and may run while batches are in flight (but see the first call's allocations below); index calls on one context follow one another
+ * under a mutex.
+ * FFS_ERR_INVALID with a text, state unchanged: a NULL rlp with n > 0, power or n, or a NULL out with cap > 0; an entry that is not finite;
+ * n_points not a power of two in 16 .. 256; dmin not positive; a negative or non-finite rmsd_cutoff; ffs_ctx_index_peaks with no grid
+ * resident. */
+int ffs_ctx_index_grid(ffs_ctx *ctx, const double *rlp, uint32_t n, double dmin, double b_iso, uint32_t n_points, uint8_t *used,
+                       double *power_out, float *kernel_ms);
+int ffs_ctx_index_load_grid(ffs_ctx *ctx, const double *power, uint32_t n_points);
+int ffs_ctx_index_peaks(ffs_ctx *ctx, double rmsd_cutoff, ffs_index_peak *out, uint32_t cap, uint32_t *n, ffs_index_grid_stats *stats,
+                        float *kernel_ms);
+/* The first call at an n_points allocates (and a call at another n_points first frees) the grids: hipMalloc and hipFree make the whole
+ * device wait, so THAT call can stall batches in flight; every later call uses only its own stream.  A call at another n_points drops the
+ * resident grid before its allocations can fail: after FFS_ERR_NOMEM no grid is resident.
+ * ffs_ctx_index_launch_ms: where the launches' time of the last ffs_ctx_index_grid (entries 0 .. 4) and the last ffs_ctx_index_peaks
+ * (5 .. 8) went, in ms from HIP events recorded between the stages in the calls' stream: 0 fill and scatter, 1 FFT along axis 0, 2 along
+ * axis 1, 3 along axis 2 with the power grid and the line sums, 4 the sums' trees; 5 the second statistic, 6 selection (count, scan,
+ * write), 7 union and flatten, 8 per-root sums and the records' compaction.  Zeros before the first call and for stages a call did not
+ * reach.  For measurements (tools/index_cost.py); FFS_ERR_INVALID: NULL out.  (No counterpart in the reference.) */
+#define FFS_INDEX_LAUNCH_SPANS 9
+int ffs_ctx_index_launch_ms(ffs_ctx *ctx, float *out);
+
 /* Centres of mass of the last batch's reflections as rows (frame_id, x, y, z) of float32 -- the
  * payload of `--output-for-index` (spot_centers, spotfinder.cc:919-933,1004-1006), in frame order;
  * used to feed a multi-GPU gather without a per-frame loop on the caller's side.  Lane 0 carries the
