@@ -62,11 +62,12 @@ CLI_SRCS := $(filter-out $(H5_SRCS),$(wildcard $(PKG)/host/*.cc))
 # tools/ffs_hosttool.cc compiles the robust GLM background from the header the kernel compiles, csrc/spot_background_glm_model.hpp,
 # summation integration from csrc/shoebox_model.hpp with the counting rule of csrc/launch_geometry.hpp, and scan prediction from
 # csrc/predict_model.hpp with the decisions of csrc/predict_plan.hpp; host/spotfinder.cc takes the candidate count from the latter;
-# tools/ffs_hosttool.cc compiles the indexer's basis-vector search from csrc/index_model.hpp with the decisions of csrc/index_plan.hpp)
+# tools/ffs_hosttool.cc compiles the indexer's basis-vector search from csrc/index_model.hpp with the decisions of csrc/index_plan.hpp,
+# and index assignment from csrc/assign_model.hpp with the refusals of csrc/assign_plan.hpp)
 CLI_HDRS := $(wildcard $(PKG)/host/*.hpp) $(wildcard include/*.h) $(PKG)/csrc/jungfrau_model.hpp $(PKG)/csrc/jungfrau_pedestal_model.hpp \
             $(PKG)/csrc/sweep_plan.hpp $(PKG)/csrc/spot_background_model.hpp $(PKG)/csrc/spot_background_glm_model.hpp \
             $(PKG)/csrc/shoebox_model.hpp $(PKG)/csrc/shoebox_plan.hpp $(PKG)/csrc/predict_model.hpp $(PKG)/csrc/predict_plan.hpp \
-            $(PKG)/csrc/index_model.hpp $(PKG)/csrc/index_plan.hpp \
+            $(PKG)/csrc/index_model.hpp $(PKG)/csrc/index_plan.hpp $(PKG)/csrc/assign_model.hpp $(PKG)/csrc/assign_plan.hpp \
             $(PKG)/csrc/launch_geometry.hpp $(PKG)/csrc/tuning.hpp
 cli: $(PKG)/bin/spotfinder $(PKG)/bin/ffs_hosttool
 $(PKG)/bin/ffs_hosttool: $(PKG)/tools/ffs_hosttool.cc $(PKG)/host/readers.cc $(CLI_HDRS) $(PKG)/libffs_synth.so $(PKG)/libffs_h5.so

@@ -300,6 +300,7 @@ static void ctx_destroy_internal(ffs_ctx* c) {
     shoebox_free_ctx(c);
     predict_free_ctx(c);
     index_free_ctx(c);
+    assign_free_ctx(c);
     if (c->d_radial_map) (void)hipFree(c->d_radial_map);
     if (c->stats_st) {   // (the streams are closed: nothing new comes, what is there is let finish)
         (void)hipStreamSynchronize(c->stats_st);

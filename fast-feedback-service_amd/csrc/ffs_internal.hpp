@@ -19,6 +19,9 @@
 //   ffs_index.hip    the indexer's basis-vector search: the host-only ffs_index_* entries and ffs_ctx_index_grid / index_load_grid / index_peaks --
 //                    scatter, three FFT passes, the statistics' trees, selection, union-find, per-root sums and records in a HIP stream of
 //                    the call's own (kernels_index.hpp); acts on the decisions of index_plan.hpp
+//   ffs_assign.hip   index assignment for candidate crystal settings: the host-only ffs_index_select / settings / absence_table / absence_detect /
+//                    reindex and ffs_ctx_index_assign -- assign with a key table, place, fill, resolve the duplicates, reduce, pass by pass in a
+//                    HIP stream of the call's own (kernels_assign.hpp); acts on the decisions of assign_plan.hpp
 //   ffs_stack3d.hip  rotation sweeps: the device-resident 3D stack -- create and pool, append a batch's lists, finish (kernels_stack3d); acts on
 //                    the decisions of sweep_plan.hpp
 //   ffs_multi.hip    several GPUs in one process: RCCL loaded with dlopen, the communicators and the choice of transport (ffs_multi_init), the
@@ -62,6 +65,11 @@
 //                        statistics' tree, components and their records, the filter and the candidate vectors (kernels_index.hpp, included by
 //                        ffs_index.hip; tools/ffs_hosttool.cc; tests/index_check.cc)
 //   index_plan.hpp       which index calls are taken, the device buffers' sizes per n_points and the launches' shapes (tests/index_plan_check.cc)
+//   assign_model.hpp     index assignment: the inverse by cofactors, a spot's index under a setting and its word, the duplicates' pair rule, the
+//                        integer counts, the absence table, detect, reindex, selection and the settings from basis vectors (kernels_assign.hpp,
+//                        included by ffs_assign.hip; tools/ffs_hosttool.cc; tests/assign_check.cc)
+//   assign_plan.hpp      which assignment calls are taken, the settings a pass takes under workspace_bytes, the launches' shapes and the bytes
+//                        of device state (tests/assign_plan_check.cc)
 // No exception leaves the library (guarded()).
 #pragma once
 #include <algorithm>
@@ -118,6 +126,7 @@ struct ffs_stack3d;
 struct ShoeboxJob;   // ffs_shoebox.hip
 struct PredictState; // ffs_predict.hip
 struct IndexState;   // ffs_index.hip
+struct AssignState;  // ffs_assign.hip
 
 // A few helper threads per context for ffs_wait's result assembly (wire records -> boxes, reflections, centre rows): one thread
 // moves a batch's 7 MB (45 000 components of 32 Eiger frames) in 0.21 ms -- two thirds of the time the GPU takes for the batch, and
@@ -219,6 +228,9 @@ struct ffs_ctx {
     // ffs_ctx_index_grid / index_load_grid / index_peaks: the same for the index calls, with the grids of the last n_points
     IndexState* index = nullptr;
     std::mutex index_mu;
+    // ffs_ctx_index_assign: the same for index assignment; its device buffers live for one call
+    AssignState* assign = nullptr;
+    std::mutex assign_mu;
     uint8_t* d_maskbits = nullptr;
     uint8_t* d_ginfo = nullptr;  // per-group mask bits + window-count bounds (kernels_stream.hpp)
     uint8_t* d_mmap = nullptr;   // per-pixel window counts
@@ -666,6 +678,8 @@ void shoebox_free_ctx(ffs_ctx* c);   // the open job, if any (context destroy; e
 void predict_free_ctx(ffs_ctx* c);   // what ffs_ctx_predict kept (context destroy)
 // ffs_index.hip
 void index_free_ctx(ffs_ctx* c);     // what the index calls kept (context destroy)
+// ffs_assign.hip
+void assign_free_ctx(ffs_ctx* c);    // what ffs_ctx_index_assign kept (context destroy)
 // ffs_stack3d.hip
 void stack3d_free(ffs_stack3d* st);
 // ffs_multi.hip

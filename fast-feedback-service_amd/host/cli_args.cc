@@ -31,7 +31,8 @@ void usage() {
       "                   [--integrate-background tukey|glm] [--integrate-n-sigma 3]]\n"
       "                  [--predict CRYSTAL --predict-dmin D --sigma-b DEG --sigma-m DEG --integrate-out PREFIX [--predict-centring P|I|F|A|B|C|R]\n"
       "                   [--integrate-n-sigma 3] [--integrate-algorithm ...] [--integrate-background ...]]\n"
-      "                  [--index-basis PREFIX --max-cell C [--index-dmin D] [--fft-npoints N]]\n"
+      "                  [--index-basis PREFIX --max-cell C [--index-dmin D] [--fft-npoints N]\n"
+      "                   [--index-assign PREFIX [--index-settings FILE] [--index-tolerance 0.3]]]\n"
       "                  [--devices D0,D1,... | --gpus N] [--no-numa-pinning] [--single-buffer] [--all-threads] [--read-only] [--clean-exit]\n"
       "--max-valid: a centre pixel above this value is never strong (the reference's kernels test it against the\n"
       "              data set's trusted maximum).  trusted (default) = the frame source's trusted-range maximum when it is\n"
@@ -113,6 +114,14 @@ void usage() {
       "              out the lattice's absent indices (default P); the boxes are --integrate-n-sigma x --sigma-b and x --sigma-m in Kabsch\n"
       "              space.  One line says candidates, predictions and flagged records; PREFIX.predictions holds the records of 96 bytes\n"
       "              (ffs_prediction of ffs_hip.h); the boxes not flagged as refused are then integrated exactly as --integrate does\n"
+      "--index-assign: after --index-basis, every candidate setting -- the triples of the run's basis vectors as the reference combines them, or\n"
+      "              the raw rows of nine float64 (A, 1/Angstrom, row-major) of --index-settings FILE -- is held against the centres on the GPU:\n"
+      "              Miller indices within --index-tolerance (default 0.3), duplicates resolved, a non-primitive basis detected and reindexed\n"
+      "              (no Niggli reduction, no refinement, no score beyond the indexed count).  Every centre is assigned: the reference's\n"
+      "              selection by resolution and rotation angle (ffs_index_select) is not applied, M below is the number of centres.\n"
+      "              One line a setting, then the best one and\n"
+      "              `Indexed N/M reflections`; PREFIX.settings holds the 160-byte ffs_index_setting records, PREFIX.assignments the 472-byte\n"
+      "              ffs_index_assignment records after correction, PREFIX.hkl the best setting's n x 3 int32.\n"
       "--index-basis: after a rotation sweep's finish the 3D reflections' centres of mass are turned into candidate basis vectors on the GPU\n"
       "              (spot FFT on a grid of --fft-npoints a side, default 256, and peak search; the reference's indexer up to peaks_to_rlvs).\n"
       "              --max-cell C is the longest cell edge expected (Angstrom); --index-dmin D the resolution limit (default: from C and the\n"
@@ -168,6 +177,7 @@ Args parse_args(int argc, char** argv) {
     Args r;
     bool model_given = false;   // --spot-background-model, in either spelling: refused without --spot-background
     bool index_option_given = false;       // --max-cell, --index-dmin and --fft-npoints: refused without --index-basis
+    bool assign_option_given = false;      // --index-settings and --index-tolerance: refused without --index-assign
     bool predict_option_given = false;     // --predict-dmin and --predict-centring: refused without --predict
     bool integrate_option_given = false;   // --sigma-b, --sigma-m and the --integrate-* options: refused without --integrate
     if (const char* e = std::getenv("SPOTFINDER_TIMEOUT")) {  // spotfinder.cc:293-301
@@ -318,6 +328,23 @@ Args parse_args(int argc, char** argv) {
             r.index_basis = need(i, s);
             if (r.index_basis.empty()) arg_error("--index-basis takes the prefix of the files it writes");
         }
+        else if (s == "--index-assign") {
+            r.index_assign = need(i, s);
+            if (r.index_assign.empty()) arg_error("--index-assign takes the prefix of the files it writes");
+        }
+        else if (s == "--index-settings") {
+            r.index_settings = need(i, s);
+            if (r.index_settings.empty()) arg_error("--index-settings takes a file of raw rows of nine float64");
+            assign_option_given = true;
+        }
+        else if (s == "--index-tolerance") {
+            const std::string& v = need(i, s);
+            char* end = nullptr;
+            const double x = std::strtod(v.c_str(), &end);
+            if (v.empty() || *end || !(x > 0.0 && x <= 0.5)) arg_error("--index-tolerance takes a number in (0, 0.5]: " + v);
+            r.index_tolerance = x;
+            assign_option_given = true;
+        }
         else if (s == "--max-cell" || s == "--index-dmin") {
             const std::string& v = need(i, s);
             char* end = nullptr;
@@ -425,6 +452,9 @@ Args parse_args(int argc, char** argv) {
     } else if (index_option_given) {
         arg_error("--max-cell, --index-dmin and --fft-npoints belong to --index-basis");
     }
+    // (--index-assign runs inside --index-basis' step: what that refuses -- --validate, several GPUs, --jungfrau-pedestal -- is refused with it)
+    if (!r.index_assign.empty() && r.index_basis.empty()) arg_error("--index-assign needs --index-basis PREFIX --max-cell C: it assigns this run's centres");
+    if (r.index_assign.empty() && assign_option_given) arg_error("--index-settings and --index-tolerance belong to --index-assign");
     if (r.gain > 0.0 && !r.gain_map.empty()) arg_error("--gain and --gain-map exclude each other: a constant map is the scalar gain");
     std::string lower = r.algorithm;   // DispersionAlgorithm, spotfinder.cc:180-203
     std::transform(lower.begin(), lower.end(), lower.begin(), [](unsigned char ch) { return (char)std::tolower(ch); });

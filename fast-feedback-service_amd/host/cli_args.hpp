@@ -55,6 +55,11 @@ struct Args {
     double index_max_cell = 0.0;         // --max-cell C (Angstrom, > 0)
     double index_dmin = 0.0;             // --index-dmin D (Angstrom, > 0); 0 = chosen from max_cell and the data
     uint32_t fft_npoints = 256;          // --fft-npoints N: a power of two in 16 .. 256
+    // --index-assign PREFIX (with --index-basis): the candidate settings -- the triples of the run's basis vectors, or the raw rows of nine
+    // float64 of --index-settings FILE -- are held against the centres on the GPU (ffs_ctx_index_assign), corrected for a non-primitive basis,
+    // and PREFIX.settings, PREFIX.assignments and PREFIX.hkl are written; empty = not given
+    std::string index_assign, index_settings;
+    double index_tolerance = 0.3;        // --index-tolerance T in (0, 0.5]
     std::string pixel_stats;             // --pixel-stats PREFIX: per-pixel count, sum, sum of squares and maximum over the run, into PREFIX.*; empty = not given
     uint32_t min_count = 2;
     int kernel_half_x = 3, kernel_half_y = 3;   // --kernel-size

@@ -38,6 +38,7 @@
 #include "shoebox_geometry.hpp"
 #include "predict_geometry.hpp"
 #include "index_basis.hpp"
+#include "index_assign.hpp"
 #include "../csrc/predict_plan.hpp"
 #include "../csrc/shoebox_model.hpp"
 #include "../csrc/sweep_plan.hpp"
@@ -1003,6 +1004,39 @@ static bool index_basis(const Args& args, ffs_ctx* ctx, const KabschGeometry& kg
     std::printf("Index geometry: distance=%.17g beam_x=%.17g beam_y=%.17g pixel_x=%.17g pixel_y=%.17g wavelength=%.17g osc_start=%.17g osc_width=%.17g\n",
                 kg.distance_mm, kg.beam_center_x_px, kg.beam_center_y_px, kg.pixel_size_x_mm, kg.pixel_size_y_mm, kg.wavelength, kg.oscillation_start, kg.oscillation_width);
     std::printf("%s", index_vector_lines(vectors.data(), vectors.size()).c_str());
+    if (args.index_assign.empty()) return true;
+    // --index-assign PREFIX: the candidate settings against the centres (host/index_assign.hpp has the step; `ffs_hosttool indexassign` on
+    // PREFIX.centres and the vectors or settings file writes the same bytes)
+    try {
+        std::vector<ffs_index_setting> settings;
+        if (!args.index_settings.empty()) {
+            settings = read_settings_file(args.index_settings);
+        } else {
+            std::vector<double> v(3 * vectors.size());
+            for (size_t k = 0; k < vectors.size(); ++k) v[3 * k] = vectors[k].v[0], v[3 * k + 1] = vectors[k].v[1], v[3 * k + 2] = vectors[k].v[2];
+            uint32_t n_settings = 0;
+            rc = ffs_index_settings(v.data(), (uint32_t)vectors.size(), 1000, nullptr, 0, &n_settings);
+            if (rc != FFS_ERR_OVERFLOW && rc != FFS_OK) throw std::runtime_error(ffs_last_error(nullptr));
+            settings.resize(n_settings);
+            if (ffs_index_settings(v.data(), (uint32_t)vectors.size(), 1000, settings.data(), n_settings, &n_settings) != FFS_OK) throw std::runtime_error(ffs_last_error(nullptr));
+        }
+        std::vector<double> phi(n);
+        for (uint32_t i = 0; i < n; ++i) phi[i] = mm[3 * (size_t)i + 2];
+        IndexAssignOps ops;
+        ops.assign = [&](const double* A, uint32_t m, ffs_index_assignment* out, int32_t* hkl) {
+            if (ffs_ctx_index_assign(ctx, rlp.data(), phi.data(), nullptr, n, A, m, args.index_tolerance, 0, out, hkl, nullptr) != FFS_OK) throw std::runtime_error(ffs_last_error(ctx));
+        };
+        ops.detect = [](const ffs_index_assignment& r) {
+            int32_t t = -1;
+            if (ffs_index_absence_detect(&r, 0.9, &t) != FFS_OK) throw std::runtime_error(ffs_last_error(nullptr));
+            return t;
+        };
+        ops.reindex = [](const double* A, int32_t t, double* out) { return ffs_index_reindex(A, t, out) == FFS_OK; };
+        std::printf("%s", index_assign_run(ops, settings, n, args.index_assign).c_str());
+    } catch (const std::exception& e) {
+        std::printf("Error: --index-assign: %s\n", e.what());
+        return false;
+    }
     return true;
 }
 

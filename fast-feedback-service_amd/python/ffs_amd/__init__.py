@@ -14,4 +14,7 @@ from .api import (Context, FrameResult, Params, Stack3D, Stream, device_count,  
                   PREDICTION_DT, CENTRINGS, PREDICT_ENTERING, PREDICT_CORNER_LOST, PREDICT_ZETA_SMALL, PREDICT_BOX_REFUSED,
                   predict_scan_settings, shoeboxes_of,
                   INDEX_PEAK_DT, INDEX_VECTOR_DT, INDEX_NOT_USED, INDEX_LAUNCH_SPANS, INDEX_RMSD_CUTOFF, INDEX_PEAK_VOLUME_CUTOFF, INDEX_MIN_CELL,
-                  index_rlp, index_defaults, index_twiddles, index_map, index_basis_vectors)
+                  index_rlp, index_defaults, index_twiddles, index_map, index_basis_vectors,
+                  INDEX_ABSENCE_TESTS, INDEX_ASSIGN_SINGULAR, INDEX_ASSIGNMENT_DT, INDEX_ABSENCE_TEST_DT, INDEX_SETTING_DT, INDEX_ASSIGN_LAUNCH_SPANS,
+                  INDEX_ASSIGN_TOLERANCE, INDEX_ABSENCE_THRESHOLD, INDEX_MAX_COMBINATIONS,
+                  index_select, index_settings, index_absence_table, index_absence_detect, index_reindex)

@@ -149,6 +149,15 @@ assert INDEX_PEAK_DT.itemsize == 56 and INDEX_VECTOR_DT.itemsize == 40 and C.siz
 INDEX_LAUNCH_SPANS = ("fill_scatter", "fft_axis0", "fft_axis1", "fft_axis2_power", "sum_trees", "second_statistic", "selection", "union_flatten", "reduce_records")
 INDEX_NOT_USED = 0xFFFFFFFF   # ffs_index_map: a spot that is not mapped
 INDEX_RMSD_CUTOFF, INDEX_PEAK_VOLUME_CUTOFF, INDEX_MIN_CELL = 15.0, 0.15, 3.0   # the reference's constants (indexer.cc:234-245)
+# Index assignment (ffs_index_select / settings / absence_* / reindex, ffs_ctx_index_assign)
+INDEX_ABSENCE_TESTS, INDEX_ASSIGN_SINGULAR = 111, 1
+INDEX_ASSIGNMENT_DT = np.dtype([("status", "<u4"), ("n_accepted", "<u4"), ("n_indexed", "<u4"), ("n_out_of_range", "<u4"), ("sum_lsq_q40", "<u8"),
+                                ("absent0", "<u4", (INDEX_ABSENCE_TESTS,)), ("reserved", "<u4")])   # ffs_index_assignment
+INDEX_ABSENCE_TEST_DT = np.dtype([("v", "<i4", (3,)), ("modularity", "<i4"), ("transform", "<i4", (9,)), ("reserved", "<i4")])   # ffs_index_absence_test
+INDEX_SETTING_DT = np.dtype([("triple", "<u4", (3,)), ("reserved", "<u4"), ("axes", "<f8", (9,)), ("A", "<f8", (9,))])   # ffs_index_setting
+assert INDEX_ASSIGNMENT_DT.itemsize == 472 and INDEX_ABSENCE_TEST_DT.itemsize == 56 and INDEX_SETTING_DT.itemsize == 160
+INDEX_ASSIGN_LAUNCH_SPANS = ("assign", "duplicates", "reduce")   # the stages of ffs_ctx_index_assign_launch_ms, in its order
+INDEX_ASSIGN_TOLERANCE, INDEX_ABSENCE_THRESHOLD, INDEX_MAX_COMBINATIONS = 0.3, 0.9, 1000   # the reference's defaults
 
 
 # ffs_radial_shell: what the radial-profile threshold decided for one (frame, shell) -- Stream.radial_thresholds
@@ -206,6 +215,8 @@ EXPORTS = [
     "ffs_predict_scan_settings", "ffs_ctx_predict",
     "ffs_index_rlp", "ffs_index_defaults", "ffs_index_twiddles", "ffs_index_map", "ffs_index_basis_vectors",
     "ffs_ctx_index_grid", "ffs_ctx_index_load_grid", "ffs_ctx_index_peaks", "ffs_ctx_index_launch_ms",
+    "ffs_index_select", "ffs_index_settings", "ffs_index_absence_table", "ffs_index_absence_detect", "ffs_index_reindex",
+    "ffs_ctx_index_assign", "ffs_ctx_index_assign_launch_ms",
 ]
 
 _lib = None
@@ -268,6 +279,14 @@ def load_library():
         L.ffs_ctx_index_load_grid.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
         L.ffs_ctx_index_peaks.argtypes = [C.c_void_p, C.c_double, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(_IndexGridStats), C.POINTER(C.c_float)]
         L.ffs_ctx_index_launch_ms.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
+        L.ffs_index_select.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_double, C.c_double, C.c_void_p]
+        L.ffs_index_settings.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32)]
+        L.ffs_index_absence_table.argtypes = [C.c_void_p]
+        L.ffs_index_absence_detect.argtypes = [C.c_void_p, C.c_double, C.POINTER(C.c_int32)]
+        L.ffs_index_reindex.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
+        L.ffs_ctx_index_assign.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_double, C.c_size_t, C.c_void_p,
+                                           C.c_void_p, C.c_void_p]
+        L.ffs_ctx_index_assign_launch_ms.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
         L.ffs_bench_pipeline.argtypes = [C.POINTER(C.c_void_p), C.c_uint32, C.c_void_p, C.c_size_t, C.c_size_t, C.c_uint32,
                                          C.c_uint32, C.c_int64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
         L.ffs_device_numa_node.argtypes = [C.c_int]
@@ -659,6 +678,51 @@ class Context:
         self.index_grid(rlp, dmin, b_iso, n_points)
         peaks, _ = self.index_peaks(INDEX_RMSD_CUTOFF)
         return index_basis_vectors(peaks, n_points, dmin, max_cell)
+
+    def index_assign(self, rlp, phi, A, *, selected=None, tolerance: float = INDEX_ASSIGN_TOLERANCE, workspace_bytes: int = 0, want_hkl: bool = False,
+                     want_lsq: bool = False, want_ms: bool = False):
+        """ffs_ctx_index_assign: the spots (rlp (n, 3), phi (n) in radians) under every setting of A (m, 9): records of INDEX_ASSIGNMENT_DT, then
+        hkl (m, n, 3) int32 when want_hkl, lsq (m, n) float64 when want_lsq, and the three stages' time in ms when want_ms.  selected: n
+        bools or None (all).  May be called while batches of the context are in flight."""
+        r = np.ascontiguousarray(np.asarray(rlp, np.float64).reshape(-1, 3))
+        p = np.ascontiguousarray(np.asarray(phi, np.float64).reshape(-1))
+        a = np.ascontiguousarray(np.asarray(A, np.float64).reshape(-1, 9))
+        if len(p) != len(r):
+            raise ValueError(f"phi must have one entry a spot: {len(p)} for {len(r)} spots")
+        sel = None
+        if selected is not None:
+            sel = np.ascontiguousarray(np.asarray(selected).astype(bool).astype(np.uint8).reshape(-1))
+            if len(sel) != len(r):
+                raise ValueError(f"selected must have one entry a spot: {len(sel)} for {len(r)} spots")
+        n, m = len(r), len(a)
+        out = np.zeros(m, INDEX_ASSIGNMENT_DT)
+        hkl = np.zeros((m, n, 3), np.int32) if want_hkl else None
+        lsq = np.full((m, n), -1.0, np.float64) if want_lsq else None
+
+        def ptr(x):
+            return x.ctypes.data_as(C.c_void_p) if x is not None and x.size else None
+        # (an empty hkl or lsq still says "wanted": a pointer to something)
+        dummy = np.zeros(1, np.float64)
+        self._check(self._lib.ffs_ctx_index_assign(self._h, ptr(r), ptr(p), ptr(sel), n, ptr(a), m, float(tolerance), int(workspace_bytes), ptr(out),
+                                                   (ptr(hkl) or ptr(dummy)) if want_hkl else None, (ptr(lsq) or ptr(dummy)) if want_lsq else None))
+        res = (out,) + ((hkl,) if want_hkl else ()) + ((lsq,) if want_lsq else ())
+        if want_ms:
+            ms = (C.c_float * 3)()
+            self._check(self._lib.ffs_ctx_index_assign_launch_ms(self._h, ms))
+            res += (dict(zip(INDEX_ASSIGN_LAUNCH_SPANS, (float(v) for v in ms))),)
+        return res[0] if len(res) == 1 else res
+
+    def index_correct(self, rlp, phi, A, *, selected=None, tolerance: float = INDEX_ASSIGN_TOLERANCE, threshold: float = INDEX_ABSENCE_THRESHOLD, workspace_bytes: int = 0):
+        """The loop of non_primitive_basis.cc:188-225 without its Niggli step, for one setting A (9): assign, detect, reindex, assign again
+        until no absence is detected.  Returns (A', record, hkl (n, 3), rounds); raises after 16 reindexings (each at least halves the cell)."""
+        a = np.ascontiguousarray(np.asarray(A, np.float64).reshape(9))
+        for rounds in range(17):
+            rec, hkl = self.index_assign(rlp, phi, a, selected=selected, tolerance=tolerance, workspace_bytes=workspace_bytes, want_hkl=True)
+            t = index_absence_detect(rec[0], threshold)
+            if t < 0:
+                return a, rec[0], hkl[0], rounds
+            a = index_reindex(a, t)
+        raise RuntimeError("index_correct: still an absence after 16 reindexings")
 
     def set_tuning(self, **kw):
         """ffs_ctx_set_tuning: A/B partners, fall-backs and capacities (same results either way); see include/ffs_hip.h."""
@@ -1064,6 +1128,62 @@ def index_basis_vectors(peaks, n_points: int, dmin: float, max_cell: float, peak
     _index_check(lib, lib.ffs_index_basis_vectors(p.ctypes.data_as(C.c_void_p) if len(p) else None, len(p), int(n_points), float(dmin), float(peak_volume_cutoff),
                                                   float(min_cell), float(max_cell), out.ctypes.data_as(C.c_void_p) if len(p) else None, len(p), C.byref(n)))
     return out[:n.value]
+
+
+def index_select(rlp, phi, dmin: float, osc_start_deg: float = 0.0) -> np.ndarray:
+    """ffs_index_select: n bools, False where 1 / |rlp| <= dmin or phi in degrees > osc_start_deg + 360 (indexer.cc:266-276)."""
+    lib = load_library()
+    r = np.ascontiguousarray(np.asarray(rlp, np.float64).reshape(-1, 3))
+    p = np.ascontiguousarray(np.asarray(phi, np.float64).reshape(-1))
+    if len(p) != len(r):
+        raise ValueError(f"phi must have one entry a spot: {len(p)} for {len(r)} spots")
+    out = np.zeros(len(r), np.uint8)
+    none = len(r) == 0
+    _index_check(lib, lib.ffs_index_select(None if none else r.ctypes.data_as(C.c_void_p), None if none else p.ctypes.data_as(C.c_void_p), len(r), float(dmin),
+                                           float(osc_start_deg), None if none else out.ctypes.data_as(C.c_void_p)))
+    return out.astype(bool)
+
+
+def index_settings(vectors, max_combinations: int = INDEX_MAX_COMBINATIONS) -> np.ndarray:
+    """ffs_index_settings: candidate settings (INDEX_SETTING_DT: triple, axes, A = inverse(axes)) from basis vectors: INDEX_VECTOR_DT records or an
+    (m, 3) array in Angstrom (combinations.cc without the Niggli reduction)."""
+    lib = load_library()
+    v = np.asarray(vectors)
+    v = np.ascontiguousarray((v["v"] if v.dtype.names else v).astype(np.float64).reshape(-1, 3))
+    n = C.c_uint32()
+    rc = lib.ffs_index_settings(v.ctypes.data_as(C.c_void_p) if len(v) else None, len(v), int(max_combinations), None, 0, C.byref(n))
+    if rc != -4:   # FFS_ERR_OVERFLOW: the count is in n
+        _index_check(lib, rc)
+    out = np.zeros(n.value, INDEX_SETTING_DT)
+    _index_check(lib, lib.ffs_index_settings(v.ctypes.data_as(C.c_void_p) if len(v) else None, len(v), int(max_combinations),
+                                             out.ctypes.data_as(C.c_void_p) if len(out) else None, len(out), C.byref(n)))
+    return out
+
+
+def index_absence_table() -> np.ndarray:
+    """ffs_index_absence_table: the 111 absence tests (INDEX_ABSENCE_TEST_DT)."""
+    lib = load_library()
+    out = np.zeros(INDEX_ABSENCE_TESTS, INDEX_ABSENCE_TEST_DT)
+    _index_check(lib, lib.ffs_index_absence_table(out.ctypes.data_as(C.c_void_p)))
+    return out
+
+
+def index_absence_detect(assignment, threshold: float = INDEX_ABSENCE_THRESHOLD) -> int:
+    """ffs_index_absence_detect: the first absence test a record of INDEX_ASSIGNMENT_DT passes, or -1."""
+    lib = load_library()
+    rec = np.ascontiguousarray(np.asarray(assignment, INDEX_ASSIGNMENT_DT).reshape(1))
+    t = C.c_int32()
+    _index_check(lib, lib.ffs_index_absence_detect(rec.ctypes.data_as(C.c_void_p), float(threshold), C.byref(t)))
+    return t.value
+
+
+def index_reindex(A, test: int) -> np.ndarray:
+    """ffs_index_reindex: the setting A (9) after the transform of absence test `test`."""
+    lib = load_library()
+    a = np.ascontiguousarray(np.asarray(A, np.float64).reshape(9))
+    out = np.zeros(9, np.float64)
+    _index_check(lib, lib.ffs_index_reindex(a.ctypes.data_as(C.c_void_p), int(test), out.ctypes.data_as(C.c_void_p)))
+    return out
 
 
 def shoeboxes_of(predictions: np.ndarray, skip_refused: bool = True) -> np.ndarray:

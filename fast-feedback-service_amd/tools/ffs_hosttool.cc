@@ -32,6 +32,8 @@
 //                                         the geometry keys of the above, width= height= crystal=<nine float64> n_images= dmin= sigma_b= sigma_m=
 //                                         [n_sigma=3] [centring=P|I|F|A|B|C|R] out=<file>: writes the ffs_prediction records spotfinder --predict
 //                                         writes to PREFIX.predictions and prints its summary line
+//   ffs_hosttool indexassign key=value ... index assignment for candidate settings on the CPU by csrc/assign_model.hpp, the text the kernels of
+//                                   ffs_ctx_index_assign compile: the twin of `spotfinder --index-assign` (host/index_assign.hpp)
 //   ffs_hosttool indexbasis key=value ... the indexer's basis-vector search on the CPU by csrc/index_model.hpp, the text the kernels of
 //                                         ffs_ctx_index_grid / index_peaks compile (the twin of spotfinder --index-basis): the geometry keys of
 //                                         the above, centres=<n x 3 float64: x_px, y_px, z> max-cell= [dmin=] [npoints=256] out=<PREFIX>:
@@ -48,6 +50,8 @@
 
 #include <map>
 
+#include "../csrc/assign_model.hpp"
+#include "../csrc/assign_plan.hpp"
 #include "../csrc/index_model.hpp"
 #include "../csrc/index_plan.hpp"
 #include "../csrc/launch_geometry.hpp"
@@ -59,6 +63,7 @@
 #include "shoebox_geometry.hpp"
 #include "predict_geometry.hpp"
 #include "index_basis.hpp"
+#include "index_assign.hpp"
 #include "codecs.hpp"
 #include "reader.hpp"
 
@@ -527,6 +532,67 @@ static int indexbasis(const KeyValues& kv) {
     return 0;
 }
 
+// indexassign: the CPU twin of `spotfinder --index-assign` (host/index_assign.hpp has the step; the rule is csrc/assign_model.hpp's).
+//   centres=FILE and the geometry as for indexbasis; vectors=FILE (40-byte ffs_index_vector records, as indexbasis and --index-basis write
+//   them: the settings are their triples) or settings=FILE (raw rows of nine float64); tolerance=0.3; out=PREFIX
+static int indexassign(const KeyValues& kv) {
+    const ffs_scan_geometry fg = shoebox_flat_geometry(kv.geometry());
+    ffsamd::ShoeboxGeometry g;
+    std::memcpy(&g, &fg, sizeof g);
+    const std::vector<double> xyz = read_centres_file(kv.str("centres"));
+    const uint32_t n = (uint32_t)(xyz.size() / 3);
+    const double tolerance = kv.has("tolerance") ? kv.num("tolerance") : ffsamd::kAssignTolerance;
+    std::vector<double> rlp(xyz.size()), s1(xyz.size()), mm(xyz.size()), phi(n);
+    std::string why = ffsamd::index_rlp_refusal(&g, xyz.data(), n, rlp.data(), s1.data(), mm.data());
+    if (!why.empty()) return fail(("indexassign: " + why).c_str());
+    for (uint32_t i = 0; i < n; ++i) {
+        ffsamd::index_rlp(g, &xyz[3 * (size_t)i], &rlp[3 * (size_t)i], &s1[3 * (size_t)i], &mm[3 * (size_t)i]);
+        phi[i] = mm[3 * (size_t)i + 2];
+    }
+    static_assert(sizeof(ffsamd::AssignSetting) == sizeof(ffs_index_setting) && sizeof(ffsamd::AssignRecord) == sizeof(ffs_index_assignment), "the model's records are the header's");
+    std::vector<ffs_index_setting> settings;
+    if (kv.has("settings")) {
+        settings = read_settings_file(kv.str("settings"));
+    } else {
+        if (!kv.has("vectors")) return fail("indexassign: missing vectors= or settings=");
+        std::ifstream f(kv.str("vectors"), std::ios::binary);
+        if (!f) return fail("indexassign: cannot open the vectors file");
+        const std::vector<char> raw((std::istreambuf_iterator<char>(f)), std::istreambuf_iterator<char>());
+        if (raw.size() % sizeof(ffs_index_vector) != 0) return fail("indexassign: the vectors file is not a whole number of 40-byte records");
+        std::vector<double> v(3 * (raw.size() / sizeof(ffs_index_vector)));
+        for (size_t k = 0; k < v.size() / 3; ++k) std::memcpy(&v[3 * k], raw.data() + k * sizeof(ffs_index_vector), 3 * sizeof(double));
+        why = ffsamd::assign_settings_refusal(v.data(), (uint32_t)(v.size() / 3), ffsamd::kAssignMaxCombinations, false, 0, false);
+        if (!why.empty()) return fail(("indexassign: " + why).c_str());
+        const std::vector<ffsamd::AssignSetting> made = ffsamd::assign_settings(v.data(), (uint32_t)(v.size() / 3), ffsamd::kAssignMaxCombinations);
+        settings.resize(made.size());
+        if (!made.empty()) std::memcpy(settings.data(), made.data(), made.size() * sizeof(ffs_index_setting));
+    }
+    const std::vector<ffsamd::AssignAbsenceTest> table = ffsamd::assign_absence_table();
+    IndexAssignOps ops;
+    ops.assign = [&](const double* A, uint32_t m, ffs_index_assignment* out, int32_t* hkl) {
+        // (what ffs_ctx_index_assign refuses is refused here, by the same text)
+        const std::string no = ffsamd::assign_refusal(rlp.data(), phi.data(), n, A, m, tolerance, !out);
+        if (!no.empty()) throw std::runtime_error(no);
+        for (uint32_t k = 0; k < m; ++k) {
+            ffsamd::AssignRecord rec;
+            ffsamd::assign_setting(rlp.data(), phi.data(), nullptr, n, A + 9 * (size_t)k, tolerance, rec, hkl ? hkl + 3 * (size_t)k * n : nullptr, nullptr);
+            std::memcpy(&out[k], &rec, sizeof rec);
+        }
+    };
+    ops.detect = [](const ffs_index_assignment& r) {
+        ffsamd::AssignRecord rec;
+        std::memcpy(&rec, &r, sizeof rec);
+        return ffsamd::assign_detect(rec, ffsamd::kAssignThreshold);
+    };
+    ops.reindex = [&](const double* A, int32_t t, double* out) { return ffsamd::assign_reindex(A, table[(size_t)t].transform, out); };
+    try {
+        std::printf("%s", index_assign_run(ops, settings, n, kv.str("out")).c_str());
+    } catch (const std::exception& e) {
+        return fail((std::string("indexassign: ") + e.what()).c_str());
+    }
+    return 0;
+}
+
 // chunkfnv <chunk file> <nelem> <elem bytes>: decode one bitshuffle-LZ4 chunk with the host codec and
 // print the FNV-1a of the pixels (cross-check for chunk writers)
 static int chunkfnv(const std::string& path, size_t nelem, size_t es) {
@@ -563,6 +629,7 @@ int main(int argc, char** argv) {
         if (cmd == "shoeboxgeom") return shoeboxgeom(KeyValues(argc, argv));
         if (cmd == "predict") return predict(KeyValues(argc, argv));
         if (cmd == "indexbasis") return indexbasis(KeyValues(argc, argv));
+        if (cmd == "indexassign") return indexassign(KeyValues(argc, argv));
         if (cmd == "h5support") { std::printf("%d\n", h5_supported() ? 1 : 0); return 0; }
     } catch (const std::exception& e) {
         std::printf("Error: %s\n", e.what());
@@ -574,6 +641,6 @@ int main(int argc, char** argv) {
                 "       chunkfnv <chunk> <nelem> <elem bytes> | jfcal <synth:spec> <file> | jfconvert <raw> <cal> <W> <H> <out> |\n"
                 "       synthframes <synth:spec> <file> | jfrepedestal <old cal> <prefix> <new cal> [min_frames [max_rms]] |\n"
                 "       spotbgglm [histograms] | shoebox key=value ... | shoeboxgeom key=value ... | predict key=value ... |\n"
-                "       indexbasis key=value ...\n");
+                "       indexbasis key=value ... | indexassign key=value ...\n");
     return 2;
 }

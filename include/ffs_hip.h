@@ -972,6 +972,71 @@ int ffs_ctx_index_peaks(ffs_ctx *ctx, double rmsd_cutoff, ffs_index_peak *out, u
 #define FFS_INDEX_LAUNCH_SPANS 9
 int ffs_ctx_index_launch_ms(ffs_ctx *ctx, float *out);
 
+/* Index assignment for candidate crystal settings: how many spots a setting A explains and which Miller index each
+ * gets -- the reference's assign_indices_global (assign_indices.cc:56-165), the absence tests and reindexing of non_primitive_basis.cc
+ * (:25-34, :43-146, :158-177, :214-217), the spot selection of indexer.cc:266-276 and the candidate settings of combinations.cc, for MANY
+ * settings in one call.  THE RULE is stated once, in csrc/assign_model.hpp, which the kernels, this library's host side and
+ * `ffs_hosttool indexassign` compile; no parity with the reference's binaries is claimed.  No fit, no refinement, no Niggli reduction, no
+ * reflection filter and no score are part of it.  The device evaluates no libm function.
+ *   A: 3x3 row-major in 1/Angstrom with r = A h at rotation angle 0 (ffs_ctx_predict's); rlp and phi (radians): ffs_index_rlp's rlp and
+ *     column 2 of its xyz_mm.
+ *   Per selected spot: hf = inverse(A) rlp (cofactors in one written order), h = round half away from zero, lsq = |h - hf|^2; accepted when
+ *     lsq <= tolerance^2 and h != 0; |hf_j| >= 2^19 is out of range (counted, lsq -1).  Of two accepted spots on one index within pi/4 of
+ *     phi the one with the smaller lsq stays (pairs in ascending spot number, a tie kills the later spot); survivors are indexed.
+ *   A singular setting (det == 0 or a non-finite inverse) has status FFS_INDEX_ASSIGN_SINGULAR, all counts 0, all indices 0, every lsq -1.
+ *   sum_lsq_q40 = the sum over indexed spots of (uint64)(lsq * 2^40); absent0[t] = the indexed spots with (h . v_t) mod m_t == 0 for the
+ *     111 absence tests of ffs_index_absence_table. */
+#define FFS_INDEX_ABSENCE_TESTS 111
+#define FFS_INDEX_ASSIGN_SINGULAR 1u
+typedef struct {
+    uint32_t status, n_accepted, n_indexed, n_out_of_range;
+    uint64_t sum_lsq_q40;
+    uint32_t absent0[FFS_INDEX_ABSENCE_TESTS];
+    uint32_t reserved;
+} ffs_index_assignment;           /* 472 bytes */
+typedef struct {
+    int32_t v[3];
+    int32_t modularity;
+    int32_t transform[9];
+    int32_t reserved;
+} ffs_index_absence_test;         /* 56 bytes */
+typedef struct {
+    uint32_t triple[3];
+    uint32_t reserved;
+    double axes[9];
+    double A[9];
+} ffs_index_setting;              /* 160 bytes */
+/* Host only, no context, no GPU; FFS_ERR_INVALID with its text in ffs_last_error(NULL), nothing written: a NULL argument, an entry that is
+ * not finite, a value outside its range.
+ * ffs_index_select (indexer.cc:266-276): selected[i] = 0 when 1 / |rlp_i| <= dmin or phi_i in degrees > osc_start_deg + 360, else 1 (an rlp
+ *   of zero is selected and never accepted).
+ * ffs_index_settings (combinations.cc): vectors is n x 3 (Angstrom, ffs_index_vector.v in order); the triples i < j < k of the first 100,
+ *   stable-sorted by i^2 + j^2 + k^2, the first max_combinations of them through the reference's angle tests (20 degrees), sign flips and
+ *   the volume test V > a b c / 100 on the cell as built (NOT Niggli-reduced); per survivor the triple, the axes (rows) and A =
+ *   inverse(axes).  *n_out = their number, at most cap are written, FFS_ERR_OVERFLOW when cap is smaller.
+ * ffs_index_absence_table: the FFS_INDEX_ABSENCE_TESTS entries (direction, modularity, integer reindexing transform).
+ * ffs_index_absence_detect (:158-177): *test = the first t with absent0[t] / n_indexed > threshold, or -1.
+ * ffs_index_reindex (:214-217): A_out = inverse(transpose(inverse(T_test)) inverse(A)); FFS_ERR_INVALID when A is singular. */
+int ffs_index_select(const double *rlp, const double *phi, uint32_t n, double dmin, double osc_start_deg, uint8_t *selected);
+int ffs_index_settings(const double *vectors, uint32_t n, uint32_t max_combinations, ffs_index_setting *out, uint32_t cap, uint32_t *n_out);
+int ffs_index_absence_table(ffs_index_absence_test *out);
+int ffs_index_absence_detect(const ffs_index_assignment *assignment, double threshold, int32_t *test);
+int ffs_index_reindex(const double *A, int32_t test, double *A_out);
+/* ffs_ctx_index_assign: rlp n x 3, phi n, selected n bytes or NULL (= all), A n_candidates x 9; out receives n_candidates records; hkl
+ * (NULL or n_candidates x n x 3 int32) the final indices, (0, 0, 0) where a spot is not indexed; lsq (NULL or n_candidates x n) each spot's
+ * lsq, -1 for unselected and out-of-range spots and under a singular setting.  n = 0 and n_candidates = 0 are allowed.  The settings are
+ * taken in passes of as many as fit workspace_bytes of device state (0 = 256 MiB; csrc/assign_plan.hpp has the bytes per setting);
+ * FFS_ERR_NOMEM with a text when not even one fits.  The result does not depend on the passes.  Synchronous, in a HIP stream of its own;
+ * it changes no batch's plan and may run while batches are in flight; calls on one context follow one another under a mutex.
+ * FFS_ERR_INVALID with a text, nothing written: a NULL rlp or phi with n > 0, a NULL A or out with n_candidates > 0; an entry of rlp, phi
+ * or A or a tolerance that is not finite; tolerance outside (0, 0.5]; n > 2^20; n_candidates > 4096.
+ * ffs_ctx_index_assign_launch_ms: the launches' time of the last call over all its passes, in ms from HIP events: 0 assign (with the key
+ * table), 1 duplicates (place, fill, resolve), 2 reduce.  Zeros before the first call. */
+int ffs_ctx_index_assign(ffs_ctx *ctx, const double *rlp, const double *phi, const uint8_t *selected, uint32_t n, const double *A,
+                         uint32_t n_candidates, double tolerance, size_t workspace_bytes, ffs_index_assignment *out, int32_t *hkl,
+                         double *lsq);
+int ffs_ctx_index_assign_launch_ms(ffs_ctx *ctx, float *out);
+
 /* Centres of mass of the last batch's reflections as rows (frame_id, x, y, z) of float32 -- the
  * payload of `--output-for-index` (spot_centers, spotfinder.cc:919-933,1004-1006), in frame order;
  * used to feed a multi-GPU gather without a per-frame loop on the caller's side.  Lane 0 carries the
