@@ -62,6 +62,53 @@ def cases():
     return out
 
 
+# ---- the scan launch at its seams ------------------------------------------------------------------------------------------------------
+# k_predict_scan is ONE workgroup of 1024 threads over the counts of all the workgroups of 256 candidates: thread t takes the
+# per = ceil(n_blocks / 1024) counts from t * per on, cut at n_blocks.  The cases of cases() have at most 14 workgroups: per = 1 and one count
+# a thread.  These have 1023, 1024 and 1025 workgroups (the last one: per = 2, thread 512 cut to one count, the threads behind it empty),
+# 1435 (per = 2, thread 717 cut, 306 threads empty) and 2065 (per = 3, thread 688 cut to one count).  The candidate count is a product of
+# three odd numbers 2 h_max + 1; an orthogonal cell with axes (h_max - 0.5) dmin has h_max = floor(|a_i| / dmin) + 1.
+SCAN_THREADS, SCAN_DMIN = 1024, 3.0
+#             name              2 h_max + 1     workgroups  per
+SCAN_SHAPES = [("scan-1023", (23, 55, 207), 1023, 1),
+               ("scan-1024", (21, 57, 219), 1024, 1),
+               ("scan-1025", (21, 55, 227), 1025, 2),
+               ("scan-1435", (19, 51, 379), 1435, 2),
+               ("scan-2065", (19, 73, 381), 2065, 3)]
+
+
+def scan_cases():
+    """A dozen images of 15 degrees, so that hundreds of the workgroups predict."""
+    out = []
+    for name, odd, n_blocks, per in SCAN_SHAPES:
+        cell = tuple(((n - 1) // 2 - 0.5) * SCAN_DMIN for n in odd)
+        c = case(name, g=geometry(osc_width=15.0), cell=cell, n_images=12, dmin=SCAN_DMIN)
+        c["scan"] = dict(h_max=[(n - 1) // 2 for n in odd], n_blocks=n_blocks, per=per)
+        out.append(c)
+    return out
+
+
+def assert_scan_census(c, census):
+    """On the oracle's census alone: the case has the workgroup count and the `per` it is named for, its predicting workgroups lie hundreds
+    apart, some scan thread with more than one count has records in two of its workgroups, the last thread with counts is cut short where
+    the case says so and the threads behind it are empty."""
+    want = c["scan"]
+    n_cand = census["candidates"]
+    assert n_cand == (2 * want["h_max"][0] + 1) * (2 * want["h_max"][1] + 1) * (2 * want["h_max"][2] + 1), (c["name"], n_cand)
+    n_blocks = (n_cand + 255) // 256
+    per = (n_blocks + SCAN_THREADS - 1) // SCAN_THREADS
+    assert (n_blocks, per) == (want["n_blocks"], want["per"]), (c["name"], n_blocks, per)
+    blocks = np.unique(census["q"] // 256)
+    assert len(blocks) > 300 and blocks[-1] - blocks[0] > 300 and blocks[-1] < n_blocks, (c["name"], len(blocks))
+    threads, in_thread = np.unique(blocks // per, return_counts=True)
+    if per >= 2:
+        assert np.max(in_thread) >= 2, c["name"]
+        used = (n_blocks + per - 1) // per
+        assert used < SCAN_THREADS and n_blocks - (used - 1) * per < per, (c["name"], "the last thread with counts is cut short, the threads behind it are empty")
+    assert np.any(threads >= 1) and census["kept"] > 10000
+    return dict(n_blocks=n_blocks, per=per, predicting_blocks=len(blocks), threads_with_two=int(np.sum(in_thread >= 2)), records=census["kept"])
+
+
 # zeta = axis . e1 vanishes when s1 lies in the plane of s0 and the axis.  A rotation only touches the sphere there (d|s0 + r|^2 / dphi =
 # 2 |s1 x s0| zeta), so no narrow image predicts such a ray; ONE IMAGE OF 180 DEGREES does: an aligned cubic cell, the axis along x, the beam
 # along -z -- (h, 0, l) with l > 0 starts at (h/a, 0, l/a) and ends at (h/a, ~1e-17, -l/a), the linear step runs inside the x-z plane, and
